@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
-"""bench.py -- MLUPS of the fused D2Q9-BGK timestep on MI355X, with roofline and CPU baseline.
+"""bench.py -- MLUPS of the fused D2Q9-BGK timestep on MI355X, with roofline (and, with --full, CPU baselines).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--grid NXxNY] [--math exact|fast]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps once and prints the result line.  --full adds everything else,
+measured after the headline: BASELINE.json's other configurations (1024x1024, 16384x16384, weak scaling), the
+one-step kernel and the two-slab split of the headline grid, the CPU baselines, and -- for a multi-rank run -- the
+bitwise check against a single-GPU run of the same workload.  --dump-outputs DIR writes what the headline engine
+holds after its last timed step: `av_vels.npy` (every step's average velocity), and, at a fixed seeded sample of
+at most 2^20 cells (every cell of a smaller grid, in row-major order), `cells.npy` (the 9 densities per cell),
+`u_x.npy`, `u_y.npy`, `u.npy` and `pressure.npy` (the final-state fields), all float32.
 
 One "step" is one lattice timestep (accelerate_flow + propagate + rebound + collision +
 av_velocity, /root/reference/SerialCode/d2q9-bgk.c:166-170) over the whole grid.  The default
@@ -10,11 +19,12 @@ obstacle map is the reference's 1024x1024 map tiled 8x8, uniform-equilibrium sta
 For N > 1 (launched by torch.distributed.run, one rank per GPU) the SAME grid is row-partitioned
 over the ranks (strong scaling), halo rows travelling by RCCL send/recv inside the engine.
 
-Timing: W untimed warm-up steps, then an untimed pre-warm until the device has been busy for
-LBM_BENCH_PREWARM_S (0.3 s: a cold GPU clocks up over the first ~0.1 s, which made a 20-step run
-15 % slower than a 200-step one), then the K-step timed region -- barrier + device sync on both
-sides, max over ranks -- LBM_BENCH_REPEATS (5) times back to back; `value`, `ms_per_step` and the
-roofline come from the MEDIAN repeat, every repeat is listed in `repeats_ms_per_step`.
+Timing: W untimed warm-up steps, then an untimed pre-warm of about LBM_BENCH_PREWARM_S (0.3 s: a cold GPU
+clocks up over the first ~0.1 s, which made a 20-step run 15 % slower than a 200-step one) -- a step count fixed
+by the grid size at the headline's rate of PREWARM_NOMINAL_MLUPS, so that the same arguments always advance the
+lattice by the same number of steps -- then the K-step timed region -- barrier + device sync on both sides, max
+over ranks -- LBM_BENCH_REPEATS (1) times back to back; `value`, `ms_per_step` and the roofline come from the
+MEDIAN repeat, every repeat is listed in `repeats_ms_per_step`.
 
 Launching: `python bench.py --gpus N` started WITHOUT a torch.distributed environment (no WORLD_SIZE) launches
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...`
@@ -51,6 +61,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 BYTES_PER_UPDATE = 72.0
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+PREWARM_NOMINAL_MLUPS = 250000.0  # the headline's rate (8192x8192, exact math): sizes the pre-warm in steps
+DUMP_SAMPLE_CELLS = 1 << 20       # --dump-outputs: cells sampled from a larger grid
+DUMP_SEED = 20261016
 
 
 def load_package():
@@ -278,7 +291,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--grid", default="8192x8192")
     ap.add_argument("--math", default="exact", choices=["exact", "fast"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the other configurations, the CPU baselines and the "
+                         "multi-rank check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's results after its last timed step as DIR/<name>.npy")
     args = ap.parse_args()
 
     nx, ny = (int(v) for v in args.grid.lower().split("x"))
@@ -290,7 +308,7 @@ def main():
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: start it as `python bench.py --gpus {args.gpus}` "
                          f"(it launches its ranks itself) or under torch.distributed.run with --nproc-per-node {args.gpus}")
-    repeats = max(1, int(os.environ.get("LBM_BENCH_REPEATS", "5")))
+    repeats = max(1, int(os.environ.get("LBM_BENCH_REPEATS", "1")))
     prewarm_s = float(os.environ.get("LBM_BENCH_PREWARM_S", "0.3"))
 
     # stdout must carry exactly ONE JSON line, but RCCL prints a five-line version banner on the C-level stdout
@@ -504,6 +522,37 @@ def main():
     watchdog = threading.Timer(extras_timeout, extras_watchdog)
     watchdog.daemon = True
 
+    def dump_outputs(eng, av, gx, gy):
+        """--dump-outputs: av_vels of every step, and the lattice and final-state fields at a fixed seeded sample of
+        cells (global row-major index y * gx + x, ascending), gathered from the ranks' rows; rank 0 writes them."""
+        cells_total = gx * gy
+        budget = 60_000_000 - av.nbytes                      # bytes; under 64 MB in all with the .npy headers
+        n = min(cells_total, DUMP_SAMPLE_CELLS, max(1, budget // (13 * 4)))
+        if n == cells_total:
+            idx = np.arange(cells_total, dtype=np.int64)
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(cells_total, size=n, replace=False))
+        info = eng.info()
+        lo, hi = info["row_first"] * gx, (info["row_first"] + info["row_count"]) * gx
+        mine = idx[(idx >= lo) & (idx < hi)]
+        local = mine - lo
+        part = {"index": mine, "cells": eng.cells().reshape(-1, 9)[local]}
+        part.update({k: v.reshape(-1)[local] for k, v in eng.final_state().items()})
+        parts = [part]
+        if use_rank_api and world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, part)
+        if rank != 0:
+            return
+        got = {k: np.concatenate([q[k] for q in parts]) for k in part}
+        order = np.argsort(got["index"], kind="stable")
+        if not np.array_equal(got["index"][order], idx):
+            raise SystemExit("bench.py --dump-outputs: the ranks' rows do not cover the grid")
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "av_vels.npy"), av.astype(np.float32))
+        for k in ("cells", "u_x", "u_y", "u", "pressure"):
+            np.save(os.path.join(args.dump_outputs, f"{k}.npy"), got[k][order].astype(np.float32))
+
     def measure(gx, gy, steps, warmup, verify=False, headline=False, n_repeats=1, prewarm=0.0):
         """`warmup` untimed timesteps of a gx x gy grid, an untimed pre-warm of about `prewarm` seconds, then
         `n_repeats` timed regions of `steps` timesteps each: barrier + device sync on both sides, max over
@@ -519,37 +568,17 @@ def main():
                 dist.barrier()
                 torch.cuda.synchronize()
 
-        def agree(v):   # every rank must run the same number of steps: take rank 0's view
-            if not use_rank_api:
-                return v
-            t = torch.tensor([float(v)], dtype=torch.float64, device=red_dev)
-            dist.broadcast(t, src=0)
-            return float(t[0])
-
         done = 0
         fence()
-        t0 = time.perf_counter()
         if warmup > 0:
             eng.run(warmup)
             done += warmup
         fence()
-        spent = time.perf_counter() - t0
-        prewarm_steps = 0
-        if prewarm > 0:
-            # chunks of `steps` until the device has been busy for `prewarm` seconds (clock ramp-up)
-            per_step = agree(spent / max(warmup, 1)) if warmup > 0 else 0.0
-            while agree(spent) < prewarm and prewarm_steps + steps <= prewarm_cap:
-                chunk = steps
-                if per_step > 0:
-                    chunk = int(min(max(steps, (prewarm - spent) / per_step), prewarm_cap - prewarm_steps))
-                    chunk = int(agree(chunk))
-                t1 = time.perf_counter()
-                eng.run(chunk)
-                fence()
-                dt = time.perf_counter() - t1
-                spent += dt
-                per_step = agree(dt / chunk)
-                prewarm_steps += chunk
+        # the clock ramp-up: a step count that depends on the arguments only, the same on every rank and in every run
+        prewarm_steps = min(prewarm_cap, int(np.ceil(prewarm * PREWARM_NOMINAL_MLUPS * 1e6 / (float(gx) * gy))))
+        if prewarm_steps > 0:
+            eng.run(prewarm_steps)
+            fence()
             done += prewarm_steps
         runs = []
         for _ in range(n_repeats):
@@ -568,6 +597,8 @@ def main():
         av = eng.av_vels(done)          # forces the cross-rank reduce too
         finite = bool(np.isfinite(av).all())
         info = eng.info()
+        if headline and args.dump_outputs:
+            dump_outputs(eng, av, gx, gy)
         if headline:
             rc_info = eng.rccl_info()
             if use_rank_api:
@@ -590,8 +621,8 @@ def main():
         eng.close()
         return elapsed, kernel_ms, info, finite, workload
 
-    # (outside the timed region) a multi-rank result is checked against a single-GPU run of the same workload
-    verify = use_rank_api and (world > 1 or os.environ.get("LBM_FORCE_HALO") == "1") and \
+    # (outside the timed region, --full) a multi-rank result is checked against a single-GPU run of the same workload
+    verify = args.full and use_rank_api and (world > 1 or os.environ.get("LBM_FORCE_HALO") == "1") and \
         os.environ.get("LBM_BENCH_VERIFY", "1") != "0"
     measure(nx, ny, args.steps, args.warmup, verify, headline=True, n_repeats=repeats, prewarm=prewarm_s)
 
@@ -599,7 +630,8 @@ def main():
     # the reference's own 1024x1024 data set (20 000 steps in the reference; Infinity-Cache resident,
     # so MLUPS only, no HBM figure; strong-scaling it over several GPUs is exchange-latency bound and
     # reported as measured) and the 16384x16384 synthetic grid of the scaling configuration
-    if os.environ.get("LBM_BENCH_ALSO", "1") != "0":
+    also_wanted = args.full and os.environ.get("LBM_BENCH_ALSO", "1") != "0"
+    if also_wanted:
         extra = [(1024, 1024, 2000, 200, "reference data set 1024x1024, cache resident"),
                  (16384, 16384, 100, 10, "synthetic 16384x16384 (BASELINE.json configs[4])")]
         if world > 1:
@@ -634,7 +666,7 @@ def main():
 
     # the one-timestep-per-pass kernel on the headline grid, measured in the same run: the kernel that IS bound by HBM
     # bandwidth (72 B per update actually move), beside the temporally blocked one whose limit is instruction issue
-    if world == 1 and not use_rank_api and os.environ.get("LBM_BENCH_ALSO", "1") != "0" and "LBM_FUSE2" not in os.environ:
+    if world == 1 and not use_rank_api and also_wanted and "LBM_FUSE2" not in os.environ:
         os.environ["LBM_FUSE2"] = "0"
         try:
             dt, k_ms, inf, fin, _ = measure(nx, ny, max(args.steps, 20), args.warmup, n_repeats=3)
@@ -654,7 +686,7 @@ def main():
     # rows by device copies): the waves of a single launch all start together and the strips that hold wall columns run
     # ~6 % longer than the others, so every launch ends with idle SIMDs; two half-size launches fill each other's tails.
     # A side line only: the headline keeps one launch per pass, whose roofline arithmetic is unambiguous.
-    if world == 1 and not use_rank_api and os.environ.get("LBM_BENCH_ALSO", "1") != "0" and main_result and \
+    if world == 1 and not use_rank_api and also_wanted and main_result and \
             main_result["info"]["band_rows"] > 0 and not any(k in os.environ for k in ("LBM_HALO", "LBM_BAND_ROWS", "LBM_FUSE2")):
         os.environ.update(LBM_HALO="memcpy", LBM_BAND_ROWS=str(main_result["info"]["band_rows"]))
         device_slabs[0] = 2
@@ -678,7 +710,7 @@ def main():
     failed = bool(check) and not check.get("fields_bitwise_equal_to_single_gpu_run", False)
     if rank == 0:
         line = compose_line()
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             base = cpu_baseline(nx, ny)
             if base:
                 line["cpu_baseline"] = base

@@ -20,6 +20,10 @@ Inputs and where each fixture comes from:
                                   recovered exactly), plus the md5 of the text files and the Reynolds
                                   number it printed.  For 1024x1024 only av_vels and pressure are kept
                                   (size).
+* check_py_128x128.json        -- the report (stdout, exit status) of the reference's own validator
+                                  check/check.py on its 128x128 goldens against the SerialCode fixture
+                                  unperturbed and scaled by 1.004 and 1.02: the files and the call of
+                                  tests/test_check_tool.py::test_same_output_as_reference_check_py.
 DIR (default /tmp/ref_out) holds one sub-directory per grid with the reference program's
 final_state.dat, av_vels.dat and stdout.txt; regenerate it with
 
@@ -29,8 +33,13 @@ final_state.dat, av_vels.dat and stdout.txt; regenerate it with
 """
 import argparse
 import hashlib
+import json
 import os
+import pathlib
 import shutil
+import subprocess
+import sys
+import tempfile
 
 import numpy as np
 
@@ -86,6 +95,25 @@ def main():
                     rec["compute_seconds_builder_container"] = np.array(float(line.split()[-2]))
         np.savez_compressed(os.path.join(HERE, f"serialcode_{g}.npz"), **rec)
         print(g, "av_vels", av.shape, "md5", rec["md5_final_state"])
+
+    record_check_py()
+
+
+def record_check_py():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import conftest
+    import test_check_tool as t
+    lbm = conftest.load_package()
+    tool = os.path.join(REF, "check", "check.py")
+    ref_av, ref_fs = (os.path.join(REF, "check", f"128x128.{k}.dat") for k in ("av_vels", "final_state"))
+    rec = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for perturb in (0.0, 0.004, 0.02):
+            av, fs = t.write_outputs(lbm, pathlib.Path(tmp), "128x128", perturb, "sim_")
+            out = t.run(tool, ref_av, ref_fs, av, fs)
+            rec[repr(perturb)] = {"returncode": out.returncode, "stdout": out.stdout}
+    with open(os.path.join(HERE, "check_py_128x128.json"), "w") as fh:
+        json.dump(rec, fh, indent=1)
 
 
 if __name__ == "__main__":

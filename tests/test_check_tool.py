@@ -1,7 +1,8 @@
 """tools/check.py: the repository's own validator must behave like the reference's check/check.py --
-same report, same verdict, same exit status.  Where /root/reference is mounted (builder container)
-the two programs are run side by side on the same files; elsewhere the tool is exercised on
-files written from the golden fixtures."""
+same report, same verdict, same exit status.  The reference's report on the reference's own 128x128
+goldens is recorded in tests/golden/check_py_128x128.json (tests/golden/make_golden.py); the goldens
+themselves are rebuilt from check_goldens.npz, and every other file is written from the fixtures."""
+import json
 import os
 import subprocess
 import sys
@@ -12,7 +13,6 @@ import pytest
 from conftest import GOLDEN, ROOT
 
 TOOL = os.path.join(ROOT, "tools", "check.py")
-REF_TOOL = "/root/reference/check/check.py"
 
 
 def write_outputs(lbm, tmp_path, name, perturb=0.0, prefix=""):
@@ -64,14 +64,25 @@ def test_mismatched_inputs(lbm, tmp_path):
     assert out.returncode == 1 and "Different number of steps" in out.stdout
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TOOL), reason="reference not mounted (GPU box)")
+def write_reference_goldens(tmp_path):
+    """The reference's check/128x128.{av_vels,final_state}.dat as check.py reads them (av_vels column 1; final_state
+    columns 0, 1 and 5), from the float64 values in check_goldens.npz: %.12E reprints the same digits."""
+    gold = np.load(os.path.join(GOLDEN, "check_goldens.npz"))
+    av, fs = tmp_path / "gold_av_vels.dat", tmp_path / "gold_final_state.dat"
+    with open(av, "w") as fh:
+        fh.writelines(f"{i}:\t{v:.12E}\n" for i, v in enumerate(gold["av_vels_128x128"]))
+    with open(fs, "w") as fh:
+        fh.writelines(f"{k % 128} {k // 128} 0 0 0 {v:.12E} 0\n" for k, v in enumerate(gold["pressure_128x128"].ravel()))
+    return str(av), str(fs)
+
+
 @pytest.mark.parametrize("perturb", [0.0, 0.004, 0.02])
 def test_same_output_as_reference_check_py(lbm, tmp_path, perturb):
-    """Side by side with the reference's own validator on the reference's own golden files."""
-    ref_av = "/root/reference/check/128x128.av_vels.dat"
-    ref_fs = "/root/reference/check/128x128.final_state.dat"
+    """Side by side with the reference's own validator on the reference's own golden files: its recorded report."""
+    with open(os.path.join(GOLDEN, "check_py_128x128.json")) as fh:
+        theirs = json.load(fh)[repr(perturb)]
+    ref_av, ref_fs = write_reference_goldens(tmp_path)
     av, fs = write_outputs(lbm, tmp_path, "128x128", perturb, "sim_")
     mine = run(TOOL, ref_av, ref_fs, av, fs)
-    theirs = run(REF_TOOL, ref_av, ref_fs, av, fs)
-    assert mine.returncode == theirs.returncode
-    assert mine.stdout == theirs.stdout
+    assert mine.returncode == theirs["returncode"]
+    assert mine.stdout == theirs["stdout"]

@@ -7,6 +7,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -59,7 +60,7 @@ def test_bench_multi_rank_path_rehearsed_on_one_gpu(ranks):
     (LBM_BENCH_REHEARSAL=hosted): the launch by bench.py itself, the agreement of the ranks on step counts, the
     max-over-ranks timing, the bitwise self-check against a single-GPU run and the exit status -- every line of the
     multi-rank path of bench.py except the RCCL transport -- run before the first real multi-GPU node sees them."""
-    out, _ = run_bench(["--gpus", str(ranks), "--steps", "8", "--warmup", "4", "--grid", "2048x1536"],
+    out, _ = run_bench(["--gpus", str(ranks), "--steps", "8", "--warmup", "4", "--grid", "2048x1536", "--full"],
                        {"LBM_BENCH_REHEARSAL": "hosted"}, 600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -98,3 +99,42 @@ def test_rccl_self_exchange_under_both_libraries(torch_first, forced):
         assert rc["library"].startswith("/opt/rocm"), rc
     # one RCCL per process unless a second one was asked for by name
     assert len([m for m in rec["mapped"] if "librccl" in m]) == (2 if forced else 1), rec["mapped"]
+
+
+def test_bench_dump_outputs_repeat_exactly(lbm, tmp_path):
+    """`bench.py --dump-outputs DIR`: a plain run times exactly --steps steps and writes the headline's results after its
+    last timed step -- float32, within 64 MB, bit-identical from run to run with the same arguments; the sampled
+    lattice and the sampled final-state fields belong to the same cells."""
+    dumps = []
+    for name in ("a", "b"):
+        env = dict(os.environ)
+        for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+            env.pop(k, None)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--grid", "2048x1024", "--steps", "12",
+                              "--warmup", "3", "--dump-outputs", str(tmp_path / name)],
+                             env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, out.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 12 and len(line["timing"]["repeats_ms_per_step"]) == 1 and line["ms_per_step"] > 0
+        assert "also" not in line and "cpu_baseline" not in line
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == sorted(f"{k}.npy" for k in ("av_vels", "cells", "u_x", "u_y", "u", "pressure"))
+        assert sum(os.path.getsize(tmp_path / name / f) for f in files) <= 64 << 20
+        dumps.append({f[:-4]: np.load(tmp_path / name / f) for f in files})
+    a, b = dumps
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
+    n = 1 << 20                                       # 2048 x 1024 cells: half of them sampled
+    assert a["cells"].shape == (n, 9) and all(a[k].shape == (n,) for k in ("u_x", "u_y", "u", "pressure"))
+    assert a["av_vels"].shape[0] > 3 + 12 and np.isfinite(a["av_vels"]).all()
+    idx = np.sort(np.random.default_rng(20261016).choice(2048 * 1024, size=n, replace=False))
+    tile = lbm.read_obstacles(os.path.join(ROOT, "tests", "golden", "inputs", "obstacles_1024x1024.dat"), 1024, 1024)
+    blocked = tile[(idx // 2048) % 1024, (idx % 2048) % 1024] == 1
+    rho = a["cells"][:, 0].copy()
+    for k in range(1, 9):
+        rho += a["cells"][:, k]
+    want_p = np.where(blocked, np.float32(0.1) * np.float32(1.0 / 3.0), rho * np.float32(1.0 / 3.0)).astype(np.float32)
+    assert np.array_equal(a["pressure"].view(np.uint32), want_p.view(np.uint32))
+    assert not a["u"][blocked].any()

@@ -226,7 +226,7 @@ def test_bench_rank_pipeline_checks_itself(lbm):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--grid", "4096x2048", "--steps", "31",
-                          "--warmup", "5", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+                          "--warmup", "5", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, out.stdout
