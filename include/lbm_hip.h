@@ -321,6 +321,41 @@ int   lbm_av_velocity(lbm_ctx* ctx, float* out);
 int   lbm_total_density(lbm_ctx* ctx, double* out);
 int   lbm_calc_reynolds(lbm_ctx* ctx, float* out);
 
+/* ---- batches: many small lattices advanced together ---------------------------------------
+ * A sweep over omega / accel / obstacle maps (each member reports its own calc_reynolds, :637-642) as ONE engine: B
+ * independent single-slab lattices of one shape on one device, each advanced by n trips of the driver loop
+ * (SerialCode/d2q9-bgk.c:166-170) per lbm_batch_run.  Every member's results are bit-identical to an lbm_create context
+ * run on the same inputs.  Where the shape runs the resident kernel (lbm_info.resident_steps > 0), calls of at least
+ * resident_min_steps timesteps advance members_per_launch members per launch of it -- 8 where one member fills one XCD
+ * (lbm_info.resident_one_xcd), else as many as have a CU for each of their workgroups -- and launches_per_chunk launches,
+ * one after the other on the batch's one stream, per chunk of up to resident_steps timesteps.  Shorter calls and other
+ * shapes run the members one after another on the per-pass kernels (correct, not faster).
+ *
+ * params    : lbm_params[n_members]: one nx, ny and max_iters for all; density, accel, omega, reynolds_dim per member.
+ * obstacles : int[n_members][ny*nx], as lbm_create's.
+ * cells_aos : NULL (every member from the uniform equilibrium) or float[n_members][ny*nx*9].
+ * lbm_batch_member: a borrowed handle of member `index`; the readers (lbm_read_av_vels, lbm_read_cells,
+ *   lbm_read_final_state, lbm_av_velocity, lbm_total_density, lbm_calc_reynolds, lbm_get_info) work on it and see every
+ *   batched launch; lbm_run / lbm_run_timed on it fail; lbm_destroy on it does nothing.  If a batched launch gives up
+ *   waiting (its workgroups were not co-resident), the next lbm_sync of EVERY member reports it.
+ */
+typedef struct lbm_batch lbm_batch; /* opaque batch handle */
+typedef struct {
+  int members;            /* B */
+  int members_per_launch; /* members one launch of the resident kernel advances (1 on the per-pass path) */
+  int launches_per_chunk; /* ceil(members / members_per_launch): sub-batches, issued in turn on one stream */
+  int resident_steps;     /* > 0: calls of at least resident_min_steps run batched, this many timesteps per chunk */
+  int resident_min_steps;
+  int steps_done;
+} lbm_batch_info;
+lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* obstacles, const float* cells_aos,
+                            int math_mode);
+lbm_ctx*   lbm_batch_member(lbm_batch* batch, int index);
+int        lbm_batch_run(lbm_batch* batch, int n_steps);
+int        lbm_batch_sync(lbm_batch* batch);
+int        lbm_batch_get_info(const lbm_batch* batch, lbm_batch_info* out);
+void       lbm_destroy_batch(lbm_batch* batch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ if the shared library is missing or no HIP device is usable, calls raise :class:
 Reference interfaces mirrored (``/root/reference/SerialCode/d2q9-bgk.c``):
 ``t_param`` (:66-75) -> :class:`Params`; ``initialise`` file formats (:460-613) ->
 :func:`read_params`, :func:`read_obstacles`; the ``timestep``/``av_velocity`` loop (:166-170) ->
-:meth:`Engine.run`; ``write_values`` (:662-743) -> :func:`write_final_state`, :func:`write_av_vels`.
+:meth:`Engine.run`, for many lattices at once :meth:`Batch.run`; ``write_values`` (:662-743) ->
+:func:`write_final_state`, :func:`write_av_vels`.
 """
 from __future__ import annotations
 
@@ -46,6 +47,7 @@ ABI_SYMBOLS = (
     "lbm_create_rank_hosted_tiled", "lbm_destroy",
     "lbm_get_info", "lbm_set_halo_mode", "lbm_read_halo_log", "lbm_run", "lbm_sync", "lbm_run_timed", "lbm_read_av_vels", "lbm_read_cells",
     "lbm_read_final_state", "lbm_av_velocity", "lbm_total_density", "lbm_calc_reynolds",
+    "lbm_create_batch", "lbm_batch_member", "lbm_batch_run", "lbm_batch_sync", "lbm_batch_get_info", "lbm_destroy_batch",
 )
 
 
@@ -68,6 +70,11 @@ class _CInfo(ctypes.Structure):
                 ("nontemporal", ctypes.c_int), ("graph_steps", ctypes.c_int),
                 ("resident_steps", ctypes.c_int), ("resident_min_steps", ctypes.c_int),
                 ("resident_rows", ctypes.c_int), ("resident_group", ctypes.c_int), ("resident_one_xcd", ctypes.c_int)]
+
+
+class _CBatchInfo(ctypes.Structure):
+    _fields_ = [("members", ctypes.c_int), ("members_per_launch", ctypes.c_int), ("launches_per_chunk", ctypes.c_int),
+                ("resident_steps", ctypes.c_int), ("resident_min_steps", ctypes.c_int), ("steps_done", ctypes.c_int)]
 
 
 class _CRcclStatus(ctypes.Structure):
@@ -166,6 +173,12 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_total_density.argtypes = [P, ctypes.POINTER(ctypes.c_double)]
     lib.lbm_total_density.restype = I
     lib.lbm_calc_reynolds.argtypes = [P, PF]; lib.lbm_calc_reynolds.restype = I
+    lib.lbm_create_batch.argtypes = [I, ctypes.POINTER(_CParams), P, P, I]; lib.lbm_create_batch.restype = P
+    lib.lbm_batch_member.argtypes = [P, I]; lib.lbm_batch_member.restype = P
+    lib.lbm_batch_run.argtypes = [P, I]; lib.lbm_batch_run.restype = I
+    lib.lbm_batch_sync.argtypes = [P]; lib.lbm_batch_sync.restype = I
+    lib.lbm_batch_get_info.argtypes = [P, ctypes.POINTER(_CBatchInfo)]; lib.lbm_batch_get_info.restype = I
+    lib.lbm_destroy_batch.argtypes = [P]; lib.lbm_destroy_batch.restype = None
     # a Python host wants exceptions, not exit(): switch from the reference's die() behaviour
     lib.lbm_set_error_mode(1)
     _lib = lib
@@ -431,6 +444,124 @@ class Engine:
         v = ctypes.c_float()
         _check(self.lib, self.lib.lbm_calc_reynolds(self.handle, ctypes.byref(v)))
         return float(v.value)
+
+
+# ------------------------------------------------------------------------------------------------
+# batches: many small lattices advanced together
+# ------------------------------------------------------------------------------------------------
+class Batch:
+    """B independent lattices of one shape on one device, advanced together (lbm_create_batch): a sweep over
+    omega / accel / obstacle maps in one engine.  Each member is bit-identical to an :class:`Engine` run on the same
+    inputs; :meth:`member` gives the readers of one of them."""
+
+    def __init__(self, params_list, obstacles, cells=None, math: str | int = "exact"):
+        self.lib = load_library()
+        self.handle = None
+        self.params = list(params_list)
+        n = len(self.params)
+        if n < 1:
+            raise LbmError("lbm_create_batch: n_members must be at least 1 (got 0)")
+        p0 = self.params[0]
+        for i, p in enumerate(self.params):
+            if p.nx < 1 or p.ny < 2 or p.max_iters < 0:
+                raise LbmError(f"lbm_create_batch: member {i} has invalid parameters")
+            if (p.nx, p.ny) != (p0.nx, p0.ny):
+                raise LbmError(f"lbm_create_batch: member {i} is {p.nx}x{p.ny}, member 0 is {p0.nx}x{p0.ny}")
+            if p.max_iters != p0.max_iters:
+                raise LbmError(f"lbm_create_batch: member {i} has max_iters {p.max_iters}, member 0 has {p0.max_iters}")
+        if math not in _MATH:
+            raise LbmError(f"lbm_create_batch: unknown math mode {math!r}")
+        self._obstacles = self._stack(obstacles, n, (p0.ny, p0.nx), np.int32, "obstacle maps")
+        self._cells = None if cells is None else self._stack(cells, n, (p0.ny, p0.nx, 9), np.float32, "initial lattices")
+        cparams = (_CParams * n)(*[p._c() for p in self.params])
+        h = self.lib.lbm_create_batch(n, cparams, self._obstacles.ctypes.data,
+                                      None if self._cells is None else self._cells.ctypes.data, _MATH[math])
+        if not h:
+            raise LbmError(self.lib.lbm_last_error().decode())
+        self.handle = ctypes.c_void_p(h)
+        self._members = [None] * n
+
+    @staticmethod
+    def _stack(arrays, n, shape, dtype, what) -> np.ndarray:
+        """A sequence of n arrays, or one stacked array, of `shape` each -> contiguous [n, *shape]."""
+        items = [np.asarray(a) for a in arrays]
+        if len(items) != n:
+            raise LbmError(f"lbm_create_batch: {len(items)} {what} for {n} members")
+        size = int(np.prod(shape))
+        for i, a in enumerate(items):
+            if a.size != size:
+                raise LbmError(f"lbm_create_batch: member {i}: {what[:-1]} of {a.size} values, expected {'x'.join(map(str, shape))}")
+        return np.ascontiguousarray(np.stack([a.reshape(shape) for a in items]), dtype=dtype)
+
+    def __len__(self) -> int:
+        return len(self.params)
+
+    # -- lifecycle ---------------------------------------------------------------------------
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self.lib.lbm_destroy_batch(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.handle:
+            raise LbmError("the batch is closed")
+        return self.handle
+
+    # -- hot path ----------------------------------------------------------------------------
+    def run(self, n_steps: int) -> None:
+        """Advance every member by n_steps (lbm_batch_run)."""
+        _check(self.lib, self.lib.lbm_batch_run(self._live(), int(n_steps)))
+
+    def sync(self) -> None:
+        _check(self.lib, self.lib.lbm_batch_sync(self._live()))
+
+    def info(self) -> dict:
+        bi = _CBatchInfo()
+        _check(self.lib, self.lib.lbm_batch_get_info(self._live(), ctypes.byref(bi)))
+        return {name: getattr(bi, name) for name, _ in _CBatchInfo._fields_}
+
+    def member(self, index: int) -> "BatchMember":
+        """Read-only view of member `index` (lbm_batch_member)."""
+        if not 0 <= index < len(self):
+            raise LbmError(f"lbm_batch_member: index {index} out of range (the batch has {len(self)} members)")
+        if self._members[index] is None:
+            h = self.lib.lbm_batch_member(self._live(), int(index))
+            if not h:
+                raise LbmError(self.lib.lbm_last_error().decode())
+            self._members[index] = BatchMember(self, index, ctypes.c_void_p(h))
+        return self._members[index]
+
+
+class BatchMember(Engine):
+    """One member of a :class:`Batch`: the readers of :class:`Engine` (av_vels, cells, final_state, av_velocity,
+    total_density, reynolds, info).  The batch advances and owns it: run() raises, close() does nothing."""
+
+    def __init__(self, batch: Batch, index: int, handle):
+        self.lib = batch.lib
+        self.params = batch.params[index]
+        self.index = index
+        self._batch = batch
+        self._handle = handle
+
+    @property
+    def handle(self):
+        self._batch._live()
+        return self._handle
+
+    def close(self) -> None:
+        pass
 
 
 # ------------------------------------------------------------------------------------------------

@@ -371,6 +371,25 @@ struct lbm_ctx {
   bool resident_used = false;       // a launch is in flight / unchecked: lbm_sync reads its status
   int tile_steps = 0;               // > 0: single slab advanced by the LDS-tile kernel, this many steps per launch
   int tile_shape = 0;               // index into kTileShapes
+  lbm_batch* batch = nullptr;       // member of this batch (lbm_create_batch): advanced, synchronised and freed by it
+};
+
+// B independent single-slab lattices of one shape on one device, advanced together (lbm_create_batch).  The members
+// are ordinary contexts that share ONE stream (member 0's compute stream), so every read through a member is ordered
+// behind every batched launch.  Resident shapes run each chunk of up to kResidentChunk timesteps as launches of
+// lbm::resident_band<..., BATCH = true>, members_per_launch members each, one after the other on that stream.
+struct lbm_batch {
+  std::vector<lbm_ctx*> members;
+  hipStream_t stream = nullptr;
+  int resident = 0;                 // the members are resident-eligible: long calls run batched
+  int member_wgs = 0;               // working workgroups of one member
+  int members_per_launch = 1;       // co-resident members in one launch: 8 one-XCD members, else floor(CUs / member_wgs)
+  int launches = 0;                 // launches per chunk (sub-batches)
+  int cur = 0;                      // lattice of every member holding the current state
+  int steps_done = 0;
+  lbm::ResidentMember* table = nullptr;  // device: [parity of cur][members]
+  int* status = nullptr;            // device: 0, or kResidentTimeout once a workgroup of any batched launch gave up
+  int* status_host = nullptr;       // pinned copy behind every run; every member's lbm_sync reports it
 };
 
 namespace {
@@ -1189,6 +1208,70 @@ int run_resident(lbm_ctx* c, int n_steps) {
   // the verdict of these launches travels to the host behind them; lbm_sync looks at it
   HIP_TRY(LBM_FAILURE, hipMemcpyAsync(sl.res_status_host, sl.res_status, sizeof(int), hipMemcpyDeviceToHost, sl.compute));
   c->resident_used = true;
+  return LBM_SUCCESS;
+}
+
+const void* resident_kernel_batch(int nx, int rows, int joint) {
+  if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, true>)
+                                   : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, true>);
+  if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, true>);
+  return joint ? reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, true>)
+               : reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, true>);
+}
+
+// run_resident for every member of a batch at once: the first step's accelerate_flow for all members, then per chunk
+// the sub-batch launches of the batched kernel and ONE reduce of every member's partials, all on the batch's stream
+int run_batch_resident(lbm_batch* bt, int n_steps) {
+  lbm_ctx* c0 = bt->members[0];
+  const Slab& sl0 = c0->slab[0];
+  const int n_members = (int)bt->members.size();
+  HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
+  hipLaunchKernelGGL(lbm::accelerate_row_batch, dim3(ceil_div(c0->p.nx, 256), n_members), dim3(256), 0, bt->stream,
+                     (const lbm::ResidentMember*)(bt->table + bt->cur * n_members), c0->plane_stride, c0->row_pitch,
+                     c0->pitch, c0->p.nx, sl0.accel_row);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  const void* kernel = resident_kernel_batch(c0->p.nx, c0->resident_rows, c0->resident_joint);
+  const int bands = c0->resident_bands;
+  for (int t = 0; t < n_steps;) {
+    const int n = (n_steps - t < kResidentChunk) ? n_steps - t : kResidentChunk;
+    const lbm::ResidentMember* tab = bt->table + bt->cur * n_members;
+    lbm::ResidentBatchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.plane_stride = c0->plane_stride;
+    a.row_pitch = c0->row_pitch;
+    a.pitch = c0->pitch;
+    a.nx = c0->p.nx;
+    a.ny = sl0.rows;
+    a.n_steps = n;
+    a.accel_row = sl0.accel_row;
+    a.accel_last = (t + n < n_steps) ? 1 : 0;
+    a.gran_bytes = (unsigned)resident_gran_bytes(c0);
+    a.xcd_affinity = env_int("LBM_RESIDENT_XCD", 1) ? 1 : 0;
+    a.epoch0 = (unsigned)(bt->steps_done + t);
+    a.status = bt->status;
+    a.timeout_ticks = c0->resident_timeout;
+    a.absent_band = env_int("LBM_RESIDENT_ABSENT_BAND", -1);
+    a.group = c0->resident_group;
+    a.one_xcd = c0->resident_one_xcd;
+    a.member_wgs = bt->member_wgs;
+    for (int first = 0; first < n_members; first += bt->members_per_launch) {
+      a.members = tab + first;
+      a.n_members = (n_members - first < bt->members_per_launch) ? n_members - first : bt->members_per_launch;
+      const int grid = a.one_xcd ? bt->member_wgs * 8 : a.n_members * (int)round_up(bt->member_wgs, 8);
+      void* args[] = {&a};
+      HIP_TRY(LBM_FAILURE, hipLaunchKernel(kernel, dim3(grid), dim3(c0->p.nx * a.group), args, 0, bt->stream));
+    }
+    hipLaunchKernelGGL(lbm::reduce_band_partials_batch, dim3(n, n_members), dim3(64), 0, bt->stream, tab, bands,
+                       bt->steps_done + t);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    bt->cur ^= 1;
+    t += n;
+  }
+  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(bt->status_host, bt->status, sizeof(int), hipMemcpyDeviceToHost, bt->stream));
+  for (lbm_ctx* c : bt->members) {
+    c->cur = bt->cur;
+    c->resident_used = true;
+  }
   return LBM_SUCCESS;
 }
 
@@ -2289,7 +2372,7 @@ lbm_ctx* lbm_create_rank_tiled(const lbm_params* params, const int* tile, int ti
 }
 
 void lbm_destroy(lbm_ctx* c) {
-  if (!c) return;
+  if (!c || c->batch) return;  // a batch member belongs to its batch (lbm_destroy_batch)
   if (c->team) {
     c->team->shutdown();
     delete c->team;
@@ -2348,9 +2431,15 @@ int lbm_set_halo_mode(lbm_ctx* c, int mode) {
   return LBM_SUCCESS;
 }
 
-int lbm_run(lbm_ctx* c, int n_steps) { return run_steps(c, n_steps, nullptr); }
+static const char kMemberRun[] = "%s: this context is a member of a batch (lbm_create_batch); lbm_batch_run advances all its members";
+
+int lbm_run(lbm_ctx* c, int n_steps) {
+  if (c && c->batch) LBM_FAIL(LBM_FAILURE, kMemberRun, "lbm_run");
+  return run_steps(c, n_steps, nullptr);
+}
 
 int lbm_run_timed(lbm_ctx* c, int n_steps, float* kernel_ms_per_step) {
+  if (c && c->batch) LBM_FAIL(LBM_FAILURE, kMemberRun, "lbm_run_timed");
   if (!kernel_ms_per_step) LBM_FAIL(LBM_FAILURE, "lbm_run_timed: NULL output");
   return run_steps(c, n_steps, kernel_ms_per_step);
 }
@@ -2363,8 +2452,8 @@ int lbm_sync(lbm_ctx* c) {
     HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].comm));
   }
   if (c->resident_used) {
-    // did every workgroup of the resident kernel get its neighbours' rows in time?
-    const int status = *c->slab[0].res_status_host;
+    // did every workgroup of the resident kernel get its neighbours' rows in time?  (a batch member: of any batched launch)
+    const int status = c->batch ? *c->batch->status_host : *c->slab[0].res_status_host;
     c->resident_used = false;
     if (status != 0)
       LBM_FAIL(LBM_FAILURE, "the resident kernel gave up waiting for a neighbouring band after %.0f ms (status %d): its %d workgroups "
@@ -2538,6 +2627,173 @@ int lbm_calc_reynolds(lbm_ctx* c, float* out) {
   if (lbm_av_velocity(c, &av) != LBM_SUCCESS) return LBM_FAILURE;
   const float viscosity = 1.f / 6.f * (2.f / c->p.omega - 1.f);  // SerialCode/d2q9-bgk.c:639
   *out = av * c->p.reynolds_dim / viscosity;                     // :641
+  return LBM_SUCCESS;
+}
+
+// ---- batches -----------------------------------------------------------------------------------------------------
+void lbm_destroy_batch(lbm_batch* bt) {
+  if (!bt) return;
+  if (bt->stream) {
+    (void)hipSetDevice(bt->members[0]->slab[0].device);
+    (void)hipStreamSynchronize(bt->stream);
+  }
+  // members 1.. borrow member 0's compute stream: they go first and leave it to member 0
+  for (size_t i = bt->members.size(); i-- > 0;) {
+    lbm_ctx* c = bt->members[i];
+    if (i > 0 && c->slab[0].compute == bt->stream) c->slab[0].compute = nullptr;
+    c->batch = nullptr;
+    lbm_destroy(c);
+  }
+  if (bt->table) (void)hipFree(bt->table);
+  if (bt->status) (void)hipFree(bt->status);
+  if (bt->status_host) (void)hipHostFree(bt->status_host);
+  delete bt;
+}
+
+lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* obstacles, const float* cells_aos,
+                            int math_mode) {
+  // everything that can be checked without a device is checked first
+  if (n_members < 1) LBM_FAIL(nullptr, "lbm_create_batch: n_members must be at least 1 (got %d)", n_members);
+  if (!params) LBM_FAIL(nullptr, "lbm_create_batch: params is NULL");
+  if (!obstacles) LBM_FAIL(nullptr, "lbm_create_batch: obstacles is NULL");
+  if (math_mode != LBM_MATH_EXACT && math_mode != LBM_MATH_FAST)
+    LBM_FAIL(nullptr, "lbm_create_batch: unknown math mode %d", math_mode);
+  for (int i = 0; i < n_members; i++) {
+    const lbm_params& p = params[i];
+    if (!validate_params(&p)) LBM_FAIL(nullptr, "lbm_create_batch: member %d has invalid parameters", i);
+    if (p.nx != params[0].nx || p.ny != params[0].ny)
+      LBM_FAIL(nullptr, "lbm_create_batch: member %d is %dx%d, member 0 is %dx%d", i, p.nx, p.ny, params[0].nx, params[0].ny);
+    if (p.max_iters != params[0].max_iters)
+      LBM_FAIL(nullptr, "lbm_create_batch: member %d has max_iters %d, member 0 has %d", i, p.max_iters, params[0].max_iters);
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+    LBM_FAIL(nullptr, "lbm_create_batch: no HIP device available (this library has no CPU path)");
+
+  lbm_batch* bt = new lbm_batch();
+  const size_t cells = (size_t)params[0].nx * params[0].ny;
+  for (int i = 0; i < n_members; i++) {
+    const ObstacleSource obst = {OBST_GLOBAL, obstacles + i * cells, 0, 0, false};
+    lbm_ctx* c = create_common(&params[i], obst, cells_aos ? cells_aos + i * cells * lbm::kQ : nullptr, 1, math_mode, 0, 1,
+                               nullptr, 0);
+    if (!c) {
+      char why[sizeof(g_last_error)];
+      strncpy(why, g_last_error, sizeof(why) - 1);
+      why[sizeof(why) - 1] = 0;
+      lbm_destroy_batch(bt);
+      LBM_FAIL(nullptr, "lbm_create_batch: member %d: %s", i, why);
+    }
+    bt->members.push_back(c);
+    c->batch = bt;
+    const lbm_ctx* c0 = bt->members[0];
+    if (c->halo != HALO_SELF || c->resident != c0->resident || c->resident_bands != c0->resident_bands ||
+        c->resident_group != c0->resident_group || c->resident_one_xcd != c0->resident_one_xcd || c->resident_rows != c0->resident_rows) {
+      lbm_destroy_batch(bt);
+      LBM_FAIL(nullptr, "lbm_create_batch: member %d is not a single periodic slab like member 0 (is LBM_FORCE_HALO set?)", i);
+    }
+  }
+  lbm_ctx* c0 = bt->members[0];
+  Slab& sl0 = c0->slab[0];
+  // one stream for all: members 1.. give theirs up (idle: creation ended with a synchronize)
+  bt->stream = sl0.compute;
+  for (int i = 1; i < n_members; i++) {
+    Slab& sl = bt->members[i]->slab[0];
+    (void)hipStreamDestroy(sl.compute);
+    sl.compute = bt->stream;
+  }
+  bt->members_per_launch = 1;
+  bt->launches = n_members;
+  if (c0->resident) {
+    // co-residency, checked here once: one-XCD members take one XCD each; other shapes one workgroup per CU, and no XCD
+    // may be dealt more working workgroups than it has CUs (member m's workgroup w runs on XCD w % 8)
+    int cus = 0;
+    if (hipSetDevice(sl0.device) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, sl0.device) != hipSuccess) {
+      lbm_destroy_batch(bt);
+      LBM_FAIL(nullptr, "lbm_create_batch: cannot query the device's CU count");
+    }
+    bt->resident = 1;
+    bt->member_wgs = c0->resident_bands / c0->resident_group;
+    int mpl = 8;
+    if (!c0->resident_one_xcd) {
+      mpl = cus / bt->member_wgs;
+      while (mpl > 1 && (long)mpl * ceil_div(bt->member_wgs, 8) > cus / 8) mpl--;
+      if (mpl < 1) mpl = 1;
+    }
+    bt->members_per_launch = mpl;
+    bt->launches = ceil_div(n_members, mpl);
+    std::vector<lbm::ResidentMember> h(2 * (size_t)n_members);
+    for (int par = 0; par < 2; par++)
+      for (int i = 0; i < n_members; i++) {
+        const lbm_ctx* c = bt->members[i];
+        const Slab& sl = c->slab[0];
+        lbm::ResidentMember& m = h[(size_t)par * n_members + i];
+        m.src = sl.lat[par];
+        m.dst = sl.lat[par ^ 1];
+        m.mask = sl.mask;
+        m.gran = sl.res_gran;
+        m.partials = sl.res_part;
+        m.tot_u = sl.tot_u;
+        m.omega = c->p.omega;
+        m.a1 = c->p.density * c->p.accel / 9.f;   // as run_steps / run_resident
+        m.a2 = c->p.density * c->p.accel / 36.f;
+      }
+    if (hipMalloc(&bt->table, h.size() * sizeof(h[0])) != hipSuccess ||
+        hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc(&bt->status, sizeof(int)) != hipSuccess || hipMemset(bt->status, 0, sizeof(int)) != hipSuccess ||
+        hipHostMalloc(&bt->status_host, sizeof(int)) != hipSuccess) {
+      lbm_destroy_batch(bt);
+      LBM_FAIL(nullptr, "lbm_create_batch: cannot allocate the member table");
+    }
+    *bt->status_host = 0;
+  }
+  return bt;
+}
+
+lbm_ctx* lbm_batch_member(lbm_batch* bt, int index) {
+  if (!bt) LBM_FAIL(nullptr, "lbm_batch_member: null batch");
+  if (index < 0 || index >= (int)bt->members.size())
+    LBM_FAIL(nullptr, "lbm_batch_member: index %d out of range (the batch has %d members)", index, (int)bt->members.size());
+  return bt->members[(size_t)index];
+}
+
+int lbm_batch_run(lbm_batch* bt, int n_steps) {
+  if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: null batch");
+  if (n_steps < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: negative step count");
+  if (n_steps == 0) return LBM_SUCCESS;
+  lbm_ctx* c0 = bt->members[0];
+  if (bt->steps_done + n_steps > c0->capacity)
+    LBM_FAIL(LBM_FAILURE, "lbm_batch_run: %d steps requested but the av_vels record holds %d (maxIters)",
+             bt->steps_done + n_steps, c0->capacity);
+  if (bt->resident && n_steps >= c0->resident_min_steps) {
+    if (run_batch_resident(bt, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
+    for (lbm_ctx* c : bt->members) c->steps_done += n_steps;
+  } else {
+    // short calls and shapes the resident kernel does not take: the members one after another, per-pass kernels
+    for (lbm_ctx* c : bt->members)
+      if (run_steps(c, n_steps, nullptr) != LBM_SUCCESS) return LBM_FAILURE;
+    bt->cur = c0->cur;
+  }
+  bt->steps_done += n_steps;
+  return LBM_SUCCESS;
+}
+
+int lbm_batch_sync(lbm_batch* bt) {
+  if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_sync: null batch");
+  int rc = LBM_SUCCESS;
+  for (lbm_ctx* c : bt->members)  // every member reports (and clears) the verdict of the launches it was part of
+    if (lbm_sync(c) != LBM_SUCCESS) rc = LBM_FAILURE;
+  return rc;
+}
+
+int lbm_batch_get_info(const lbm_batch* bt, lbm_batch_info* out) {
+  if (!bt || !out) LBM_FAIL(LBM_FAILURE, "lbm_batch_get_info: NULL argument");
+  const lbm_ctx* c0 = bt->members[0];
+  out->members = (int)bt->members.size();
+  out->members_per_launch = bt->members_per_launch;
+  out->launches_per_chunk = bt->launches;
+  out->resident_steps = bt->resident ? kResidentChunk : 0;
+  out->resident_min_steps = bt->resident ? c0->resident_min_steps : 0;
+  out->steps_done = bt->steps_done;
   return LBM_SUCCESS;
 }
 

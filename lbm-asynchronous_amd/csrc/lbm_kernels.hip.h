@@ -1506,6 +1506,16 @@ __global__ __launch_bounds__(THREADS) void step_tile(const TileArgs a) {
 // Arithmetic: relax_pair_core + the per-cell exception path, i.e. the lattice stays bit-identical to the oracle;
 // |u| from the pre-collision moments as in the stream kernels.
 // ---------------------------------------------------------------------------------------------
+// one lattice of a batch (lbm_create_batch): what a batched launch takes per member instead of ResidentArgs' fields
+struct ResidentMember {
+  float* src;                 // current lattice (the first step's accelerate_flow is applied to it in place)
+  float* dst;
+  const unsigned char* mask;
+  uint4* gran;                // the member's own seam granules and tags
+  float* partials;
+  double* tot_u;              // the member's per-step sums of |u|
+  float omega, a1, a2;
+};
 struct ResidentArgs {
   const float* src;           // lattice to start from (row 0 of the slab)
   float* dst;                 // lattice to leave the result in (may equal src)
@@ -1531,6 +1541,14 @@ struct ResidentArgs {
 #ifdef LBM_RESIDENT_PROFILE
   long long* prof;            // tools/resident_profile.sh: [band][8] shader-clock sums of the phases of a step
 #endif
+};
+// batched launches (resident_band<..., BATCH = true>): src, dst, mask, omega, a1, a2, gran and partials above are unused,
+// each member brings its own; status is shared by all members of all launches of a batch
+struct ResidentBatchArgs : ResidentArgs {
+  const ResidentMember* members;  // this launch's members
+  int n_members;
+  int member_wgs;             // working workgroups of one member; without one_xcd member m starts at block
+                              // m * round_up(member_wgs, 8), so the XCD-affinity band order holds inside every member
 };
 #ifdef LBM_RESIDENT_PROFILE
 __device__ __forceinline__ long long prof_clock() {
@@ -1632,8 +1650,12 @@ __device__ __forceinline__ granule_vec granule_load(__amdgpu_buffer_rsrc_t rsrc,
 // ROWS: rows per band, 4 (above) or 2 -- one pair per lane, both rows seam rows: twice the workgroups and half the
 // dependent work per lane and step, for grids small enough that the chip has CUs to spare (ny / 2 <= CUs): there the
 // step is one wave's chain "hop + collisions", and the shorter chain wins although nothing hides the hop any more.
-template <int MAXT, bool JOINT = false, int ROWS = 4>
-__global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgs a) {
+// BATCH: one launch advances up to 8 independent lattices (ResidentMember); the member index is uniform over a
+// workgroup, so the member's fields are scalar loads before the step loop and the loop itself is the same.  One-XCD
+// shapes: member m = blockIdx.x & 7 runs on XCD m, on the workgroups the single form leaves idle; other shapes: members
+// take consecutive ranges of round_up(member_wgs, 8) blocks.  The seam protocol is per member (own granules, own tags).
+template <int MAXT, bool JOINT = false, int ROWS = 4, bool BATCH = false>
+__global__ __launch_bounds__(MAXT) void resident_band(const std::conditional_t<BATCH, ResidentBatchArgs, ResidentArgs> a) {
   static_assert(ROWS == 4 || ROWS == 2, "bands of four or two rows");
   constexpr int NE = (ROWS == 4) ? 10 : 4;  // wave-edge values per side
   // a workgroup holds a.group bands side by side (1: the usual case; more where a band has fewer than four waves and
@@ -1641,8 +1663,16 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgs a) {
   // `wv` inside the workgroup
   const int grp = (int)threadIdx.x / a.nx;
   const int x = (int)threadIdx.x - grp * a.nx, lane = x & 63, wave = x >> 6, n_waves = a.nx >> 6, wv = (int)threadIdx.x >> 6, wv0 = wv - wave;
-  const int n_wgs = a.one_xcd ? (int)(gridDim.x >> 3) : (int)gridDim.x, wg = a.one_xcd ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-  if (a.one_xcd && (blockIdx.x & 7) != 0) return;
+  int n_wgs = a.one_xcd ? (int)(gridDim.x >> 3) : (int)gridDim.x, wg = a.one_xcd ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+  ResidentMember mb{};
+  if constexpr (BATCH) {
+    const int stride = (a.member_wgs + 7) & ~7;
+    const int member = a.one_xcd ? (int)(blockIdx.x & 7) : (int)blockIdx.x / stride;
+    if (!a.one_xcd) { n_wgs = a.member_wgs; wg = (int)blockIdx.x - member * stride; }
+    if (member >= a.n_members || wg >= n_wgs) return;
+    mb = a.members[member];
+  } else if (a.one_xcd && (blockIdx.x & 7) != 0) return;
+#define RES_M(field) (BATCH ? mb.field : a.field)
   const int bands = n_wgs * a.group;
   // Workgroups are dealt to the 8 XCDs round-robin (observed, not promised): consecutive bands are given to
   // workgroups 8 apart, so that most seams join two bands on ONE XCD.  Speed only -- which seams really do is
@@ -1658,7 +1688,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgs a) {
   constexpr int TOP = ROWS - 1;  // the band's last row: the .y half of the edge pair
   f2 ri[kQ], re[kQ];
   {
-    const float* base = a.src + (long)(ROWS * b) * a.row_pitch + x;
+    const float* base = RES_M(src) + (long)(ROWS * b) * a.row_pitch + x;
 #pragma unroll
     for (int k = 0; k < kQ; k++) {
       re[k] = f2{base[k * ps], base[TOP * a.row_pitch + k * ps]};
@@ -1666,7 +1696,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgs a) {
       else ri[k] = splat2(0.f);
     }
   }
-  const unsigned char* mp = a.mask + (long)(ROWS * b) * a.pitch + x;
+  const unsigned char* mp = RES_M(mask) + (long)(ROWS * b) * a.pitch + x;
   const unsigned blocked_e = (unsigned)mp[0] | ((unsigned)mp[TOP * a.pitch] << 8);
   unsigned blocked_i = 0;
   if constexpr (ROWS == 4) blocked_i = (unsigned)mp[a.pitch] | ((unsigned)mp[2 * a.pitch] << 8);
@@ -1677,7 +1707,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgs a) {
 
   // seam granules: `up` carries a band's top-row populations 2,5,6 northwards, `down` its row-0 populations 4,7,8;
   // byte offsets into the one buffer (32-bit: it is at most 16 MiB)
-  const __amdgpu_buffer_rsrc_t grsrc = granule_rsrc(a.gran, a.gran_bytes);
+  const __amdgpu_buffer_rsrc_t grsrc = granule_rsrc(RES_M(gran), a.gran_bytes);
   const unsigned band_bytes = 2u * (unsigned)a.nx * 16u, slot_bytes = (unsigned)a.nx * 16u;
   const unsigned down_base = (unsigned)bands * band_bytes;
   const int bs = (b == 0) ? bands - 1 : b - 1, bn = (b == bands - 1) ? 0 : b + 1;
@@ -1767,7 +1797,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgs a) {
     if (s > 0 && wave == 0) {
       // the per-wave sums of the previous step, written before this barrier: one partial per band and step
       const float v = row16_sum_dpp((lane < n_waves) ? wave_part[slot ^ 1][wv0 + lane] : 0.f);
-      if (lane == 0) a.partials[(long)(s - 1) * bands + b] = v;
+      if (lane == 0) RES_M(partials)[(long)(s - 1) * bands + b] = v;
     }
     float W[NE], E[NE];
     {
@@ -1823,7 +1853,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgs a) {
     }
     f2 ni[kQ];
     float sum = 0.f;
-    if constexpr (ROWS == 4 && !JOINT) sum = relax_pair_rows(ti, blocked_i, accel ? lid_i : 0u, a.omega, a.a1, a.a2, ni);
+    if constexpr (ROWS == 4 && !JOINT) sum = relax_pair_rows(ti, blocked_i, accel ? lid_i : 0u, RES_M(omega), RES_M(a1), RES_M(a2), ni);
 
     RESIDENT_PROF(2);  // partial of the previous step, LDS edges read, shifts, halo loads issued, interior pair (ROWS 4, !JOINT)
     // ---- edge pair: rows 0 and TOP also pull from the neighbouring bands --------------------------------------
@@ -1869,8 +1899,8 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgs a) {
     te[7].y = shift_from_east(__uint_as_float((unsigned)cn.y), side_n);
     te[8].y = shift_from_west(__uint_as_float((unsigned)cn.z), side_n);
     f2 ne[kQ];
-    if constexpr (ROWS == 4 && JOINT) sum = relax_two_pairs_rows(ti, te, blocked_i, blocked_e, accel ? lid_i : 0u, accel ? lid_e : 0u, a.omega, a.a1, a.a2, ni, ne);
-    else sum += relax_pair_rows(te, blocked_e, accel ? lid_e : 0u, a.omega, a.a1, a.a2, ne);
+    if constexpr (ROWS == 4 && JOINT) sum = relax_two_pairs_rows(ti, te, blocked_i, blocked_e, accel ? lid_i : 0u, accel ? lid_e : 0u, RES_M(omega), RES_M(a1), RES_M(a2), ni, ne);
+    else sum += relax_pair_rows(te, blocked_e, accel ? lid_e : 0u, RES_M(omega), RES_M(a1), RES_M(a2), ne);
 #pragma unroll
     for (int k = 0; k < kQ; k++) {
       re[k] = ne[k];
@@ -1894,9 +1924,9 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgs a) {
   __syncthreads();
   if (a.n_steps > 0 && wave == 0) {
     const float v = row16_sum_dpp((lane < n_waves) ? wave_part[(a.n_steps - 1) & 1][wv0 + lane] : 0.f);
-    if (lane == 0) a.partials[(long)(a.n_steps - 1) * bands + b] = v;
+    if (lane == 0) RES_M(partials)[(long)(a.n_steps - 1) * bands + b] = v;
   }
-  float* out = a.dst + (long)(ROWS * b) * a.row_pitch + x;
+  float* out = RES_M(dst) + (long)(ROWS * b) * a.row_pitch + x;
 #pragma unroll
   for (int k = 0; k < kQ; k++) {
     out[k * ps] = re[k].x;
@@ -1907,14 +1937,22 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgs a) {
     }
   }
 }
+#undef RES_M
 
 // resident kernel: sum the per-band partials of each step in a fixed order (double) -> tot_u[step_base + s]
-__global__ __launch_bounds__(64) void reduce_band_partials(const float* partials, int bands, double* tot_u, int step_base) {
-  const float* p = partials + (long)blockIdx.x * bands;
+__device__ __forceinline__ void reduce_band_partials_at(const float* p, int bands, double* out) {
   double acc = 0.0;
   for (int i = threadIdx.x; i < bands; i += 64) acc += (double)p[i];
   for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  if (threadIdx.x == 0) tot_u[step_base + blockIdx.x] = acc;
+  if (threadIdx.x == 0) *out = acc;
+}
+__global__ __launch_bounds__(64) void reduce_band_partials(const float* partials, int bands, double* tot_u, int step_base) {
+  reduce_band_partials_at(partials + (long)blockIdx.x * bands, bands, tot_u + step_base + blockIdx.x);
+}
+// the same for every member of a batch at once: grid (steps, members)
+__global__ __launch_bounds__(64) void reduce_band_partials_batch(const ResidentMember* members, int bands, int step_base) {
+  const ResidentMember& m = members[blockIdx.y];
+  reduce_band_partials_at(m.partials + (long)blockIdx.x * bands, bands, m.tot_u + step_base + blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1964,8 +2002,8 @@ __global__ __launch_bounds__(kBlock) void step_scalar(const StepArgs a) {
 
 // accelerate_flow() as its own pass (SerialCode/d2q9-bgk.c:216-246): used once before the first
 // step of a run; later steps get it from the epilogue of the step kernel.
-__global__ void accelerate_row(float* lat, const unsigned char* mask, long ps, long row_pitch,
-                               int pitch, int nx, int row, float a1, float a2) {
+__device__ __forceinline__ void accelerate_row_at(float* lat, const unsigned char* mask, long ps, long row_pitch,
+                                                  int pitch, int nx, int row, float a1, float a2) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   if (x >= nx) return;
   if (mask[(long)row * pitch + x]) return;
@@ -1976,6 +2014,15 @@ __global__ void accelerate_row(float* lat, const unsigned char* mask, long ps, l
   accelerate(f, a1, a2);
   lat[1 * ps + c] = f[1];  lat[3 * ps + c] = f[3];  lat[5 * ps + c] = f[5];
   lat[6 * ps + c] = f[6];  lat[7 * ps + c] = f[7];  lat[8 * ps + c] = f[8];
+}
+__global__ void accelerate_row(float* lat, const unsigned char* mask, long ps, long row_pitch,
+                               int pitch, int nx, int row, float a1, float a2) {
+  accelerate_row_at(lat, mask, ps, row_pitch, pitch, nx, row, a1, a2);
+}
+// the same on the current lattice of every member of a batch: grid (ceil(nx / block), members)
+__global__ void accelerate_row_batch(const ResidentMember* members, long ps, long row_pitch, int pitch, int nx, int row) {
+  const ResidentMember& m = members[blockIdx.y];
+  accelerate_row_at(m.src, m.mask, ps, row_pitch, pitch, nx, row, m.a1, m.a2);
 }
 
 // ---------------------------------------------------------------------------------------------
