@@ -321,6 +321,24 @@ int   lbm_av_velocity(lbm_ctx* ctx, float* out);
 int   lbm_total_density(lbm_ctx* ctx, double* out);
 int   lbm_calc_reynolds(lbm_ctx* ctx, float* out);
 
+/* ---- animation frames ----------------------------------------------------------------------
+ * The reference's main loop writes a velocity-magnitude frame every 100 steps
+ * (`if (tt % 100 == 0) write_animation_data(...)`, SerialCode/d2q9-bgk.c:171-173; the writer is :802-849).  Here the
+ * running kernels record them on the device, without splitting the run:
+ * lbm_set_frames(ctx, every, capacity): from now on, after global timestep tt (0-based, counted from the context's
+ *   creation: the step that takes steps_done from tt to tt+1) with tt % every == 0, record the frame of the lattice after
+ *   tt+1 timesteps: float[row_count][nx] over the owned rows, bit-identical to lbm_read_final_state's u_mag at that point
+ *   (0 for blocked cells).  Recording never changes the lattice or av_vels.  Frames wait in a device buffer of `capacity`
+ *   slots; an lbm_run / lbm_batch_run call that would record more frames than there are free slots fails before issuing
+ *   any work.  every == 0 disarms and frees the buffer; re-arming discards unread frames.  Refused in LBM_HALO_STALE and
+ *   LBM_HALO_FRESHEST (and lbm_set_halo_mode to those modes while armed).  Works on batch members too.
+ * lbm_read_frames: drains up to max_frames oldest frames into out[n][row_count*nx] and steps[n] (their tt, may be NULL);
+ *   out == NULL && steps == NULL: *n_read = frames waiting, nothing drained.  Synchronises like the other readers (so a
+ *   resident give-up is reported here too).
+ */
+int lbm_set_frames(lbm_ctx* ctx, int every, int capacity);
+int lbm_read_frames(lbm_ctx* ctx, int max_frames, float* out, int* steps, int* n_read);
+
 /* ---- batches: many small lattices advanced together ---------------------------------------
  * A sweep over omega / accel / obstacle maps (each member reports its own calc_reynolds, :637-642) as ONE engine: B
  * independent single-slab lattices of one shape on one device, each advanced by n trips of the driver loop

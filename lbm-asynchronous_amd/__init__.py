@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     "lbm_create_rank_hosted_tiled", "lbm_destroy",
     "lbm_get_info", "lbm_set_halo_mode", "lbm_read_halo_log", "lbm_run", "lbm_sync", "lbm_run_timed", "lbm_read_av_vels", "lbm_read_cells",
     "lbm_read_final_state", "lbm_av_velocity", "lbm_total_density", "lbm_calc_reynolds",
+    "lbm_set_frames", "lbm_read_frames",
     "lbm_create_batch", "lbm_batch_member", "lbm_batch_run", "lbm_batch_sync", "lbm_batch_get_info", "lbm_destroy_batch",
 )
 
@@ -173,6 +174,8 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_total_density.argtypes = [P, ctypes.POINTER(ctypes.c_double)]
     lib.lbm_total_density.restype = I
     lib.lbm_calc_reynolds.argtypes = [P, PF]; lib.lbm_calc_reynolds.restype = I
+    lib.lbm_set_frames.argtypes = [P, I, I]; lib.lbm_set_frames.restype = I
+    lib.lbm_read_frames.argtypes = [P, I, P, P, PI]; lib.lbm_read_frames.restype = I
     lib.lbm_create_batch.argtypes = [I, ctypes.POINTER(_CParams), P, P, I]; lib.lbm_create_batch.restype = P
     lib.lbm_batch_member.argtypes = [P, I]; lib.lbm_batch_member.restype = P
     lib.lbm_batch_run.argtypes = [P, I]; lib.lbm_batch_run.restype = I
@@ -407,6 +410,30 @@ class Engine:
     def sync(self) -> None:
         _check(self.lib, self.lib.lbm_sync(self.handle))
 
+    # -- animation frames (lbm_set_frames / lbm_read_frames) ---------------------------------
+    def set_frames(self, every: int, capacity: int = 0) -> None:
+        """Record |u| of the owned rows after every global timestep tt with tt % every == 0 (the reference's
+        write_animation_data hook, SerialCode/d2q9-bgk.c:171-173) into a device buffer of `capacity` frames.
+        every == 0 disarms; re-arming discards unread frames."""
+        every, capacity = _frame_args(every, capacity)
+        _check(self.lib, self.lib.lbm_set_frames(self.handle, every, capacity))
+
+    def frames(self, max_frames: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_frames (default: all) waiting frames, oldest first:
+        (steps int32[n], frames float32[n, row_count, nx])."""
+        if max_frames is not None and (isinstance(max_frames, bool) or not isinstance(max_frames, (int, np.integer))
+                                       or max_frames < 0):
+            raise LbmError(f"frames: max_frames must be a non-negative integer or None (got {max_frames!r})")
+        n = ctypes.c_int()
+        _check(self.lib, self.lib.lbm_read_frames(self.handle, 0, None, None, ctypes.byref(n)))  # frames waiting
+        max_frames = n.value if max_frames is None else min(int(max_frames), n.value)
+        rows = self.info()["row_count"]
+        frames = np.empty((int(max_frames), rows, self.params.nx), dtype=np.float32)
+        steps = np.empty(int(max_frames), dtype=np.int32)
+        _check(self.lib, self.lib.lbm_read_frames(self.handle, int(max_frames), frames.ctypes.data,
+                                                  steps.ctypes.data, ctypes.byref(n)))
+        return steps[:n.value].copy(), frames[:n.value].copy()
+
     # -- results -----------------------------------------------------------------------------
     def av_vels(self, n: int | None = None) -> np.ndarray:
         n = self.info()["steps_done"] if n is None else n
@@ -615,6 +642,30 @@ def write_av_vels(path: str, av_vels: np.ndarray) -> None:
     with open(path, "w") as fh:
         for i, v in enumerate(np.asarray(av_vels, dtype=np.float32)):
             fh.write("%d:\t%.12E\n" % (i, float(v)))
+
+
+def _frame_args(every, capacity) -> tuple[int, int]:
+    """Engine.set_frames' argument checks (no device needed)."""
+    for name, v in (("every", every), ("capacity", capacity)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise LbmError(f"set_frames: {name} must be an integer (got {v!r})")
+        if not 0 <= int(v) <= 2147483647:
+            raise LbmError(f"set_frames: {name} must lie in [0, 2^31) (got {v})")
+    if every > 0 and capacity < 1:
+        raise LbmError(f"set_frames: capacity {capacity}, at least one frame slot is needed")
+    return int(every), int(capacity)
+
+
+def write_animation_frame(path: str, frame: np.ndarray, tt: int) -> None:
+    """write_animation_data() (SerialCode/d2q9-bgk.c:802-849): '# nx=%d ny=%d timestep=%d' then one '%.6E' line per
+    cell, jj outer / ii inner; `frame` is float32 [ny, nx] |u| with 0 for blocked cells (Engine.frames)."""
+    frame = np.asarray(frame, dtype=np.float32)
+    if frame.ndim != 2:
+        raise LbmError(f"write_animation_frame: frame must be [ny, nx] (got shape {frame.shape})")
+    ny, nx = frame.shape
+    with open(path, "w") as fh:
+        fh.write("# nx=%d ny=%d timestep=%d\n" % (nx, ny, int(tt)))
+        fh.write("".join("%.6E\n" % v for v in frame.ravel().tolist()))
 
 
 def write_final_state(path: str, fields: dict, obstacles: np.ndarray) -> None:

@@ -171,6 +171,7 @@ struct Slab {
   float* res_part = nullptr;               // resident kernel: per-band partial sums of a launch, [kResidentChunk][bands]
   int* res_status = nullptr;               // resident kernel: 0, or the reason a workgroup gave up
   int* res_status_host = nullptr;          // pinned copy of it, refreshed behind every launch (read by lbm_sync)
+  float* frames = nullptr;                 // lbm_set_frames: [frame slots][rows][nx] |u| of the owned rows
   hipGraphExec_t chunk_graph[2] = {nullptr, nullptr};  // kPartSlots timesteps + their reduce, by lattice parity
   hipStream_t compute = nullptr, comm = nullptr;
   hipEvent_t ev_boundary = nullptr, ev_halo = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
@@ -372,6 +373,13 @@ struct lbm_ctx {
   int tile_steps = 0;               // > 0: single slab advanced by the LDS-tile kernel, this many steps per launch
   int tile_shape = 0;               // index into kTileShapes
   lbm_batch* batch = nullptr;       // member of this batch (lbm_create_batch): advanced, synchronised and freed by it
+  // animation frames (lbm_set_frames): after global step tt with tt % frame_every == 0, |u| of the owned rows goes to
+  // slot (tt / frame_every - frame_ord0) % frame_slots of every slab's frames buffer
+  int frame_every = 0;              // 0: not armed
+  int frame_slots = 0;
+  int frame_ord0 = 0;               // tt / frame_every of the first frame after arming
+  long long frames_written = 0;     // frames issued since arming (frame ordinals 0 .. frames_written - 1) ...
+  long long frames_read = 0;        // ... and drained by lbm_read_frames
 };
 
 // B independent single-slab lattices of one shape on one device, advanced together (lbm_create_batch).  The members
@@ -390,6 +398,8 @@ struct lbm_batch {
   lbm::ResidentMember* table = nullptr;  // device: [parity of cur][members]
   int* status = nullptr;            // device: 0, or kResidentTimeout once a workgroup of any batched launch gave up
   int* status_host = nullptr;       // pinned copy behind every run; every member's lbm_sync reports it
+  lbm::ResidentFrames* frame_table = nullptr;  // device: [members], allocated when the first member arms frames
+  int frames_armed = 0;             // members with frames armed: batched launches run the FRAMES kernel
 };
 
 namespace {
@@ -1127,7 +1137,14 @@ size_t resident_gran_bytes(const lbm_ctx* c) {
   return (2UL * c->resident_bands * 2 * c->p.nx + c->resident_bands) * sizeof(uint4);
 }
 
-const void* resident_kernel(int nx, int rows, int joint) {
+const void* resident_kernel(int nx, int rows, int joint, bool frames) {
+  if (frames) {
+    if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, false, true>)
+                                     : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, false, true>);
+    if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, false, true>);
+    return joint ? reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, false, true>)
+                 : reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, false, true>);
+  }
   if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2>)
                                    : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2>);
   if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024>);
@@ -1142,7 +1159,9 @@ int run_resident(lbm_ctx* c, int n_steps) {
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
   for (int t = 0; t < n_steps;) {
     const int n = (n_steps - t < kResidentChunk) ? n_steps - t : kResidentChunk;
-    lbm::ResidentArgs a;
+    lbm::ResidentFramesArgs fa;  // the FRAMES form's arguments: ResidentArgs + the frame fields
+    lbm::ResidentArgs& a = fa;
+    fa.fr = {sl.frames, c->frame_every, c->frame_ord0, c->frame_slots};
     a.src = sl.lat[c->cur];
     a.dst = sl.lat[c->cur ^ 1];
     a.mask = sl.mask;
@@ -1172,8 +1191,8 @@ int run_resident(lbm_ctx* c, int n_steps) {
 #endif
     a.group = c->resident_group;
     a.one_xcd = c->resident_one_xcd;
-    void* args[] = {&a};
-    HIP_TRY(LBM_FAILURE, hipLaunchKernel(resident_kernel(c->p.nx, c->resident_rows, c->resident_joint),
+    void* args[] = {&fa};
+    HIP_TRY(LBM_FAILURE, hipLaunchKernel(resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, c->frame_every > 0),
                                          dim3(c->resident_bands / a.group * (a.one_xcd ? 8 : 1)), dim3(c->p.nx * a.group), args, 0, sl.compute));
     hipLaunchKernelGGL(lbm::reduce_band_partials, dim3(n), dim3(64), 0, sl.compute, (const float*)sl.res_part,
                        c->resident_bands, sl.tot_u, c->steps_done + t);
@@ -1211,7 +1230,14 @@ int run_resident(lbm_ctx* c, int n_steps) {
   return LBM_SUCCESS;
 }
 
-const void* resident_kernel_batch(int nx, int rows, int joint) {
+const void* resident_kernel_batch(int nx, int rows, int joint, bool frames) {
+  if (frames) {
+    if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, true, true>)
+                                     : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, true, true>);
+    if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, true, true>);
+    return joint ? reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, true, true>)
+                 : reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, true, true>);
+  }
   if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, true>)
                                    : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, true>);
   if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, true>);
@@ -1230,13 +1256,14 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
                      (const lbm::ResidentMember*)(bt->table + bt->cur * n_members), c0->plane_stride, c0->row_pitch,
                      c0->pitch, c0->p.nx, sl0.accel_row);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
-  const void* kernel = resident_kernel_batch(c0->p.nx, c0->resident_rows, c0->resident_joint);
+  const void* kernel = resident_kernel_batch(c0->p.nx, c0->resident_rows, c0->resident_joint, bt->frames_armed > 0);
   const int bands = c0->resident_bands;
   for (int t = 0; t < n_steps;) {
     const int n = (n_steps - t < kResidentChunk) ? n_steps - t : kResidentChunk;
     const lbm::ResidentMember* tab = bt->table + bt->cur * n_members;
-    lbm::ResidentBatchArgs a;
-    memset(&a, 0, sizeof(a));
+    lbm::ResidentBatchFramesArgs fa;  // the FRAMES form's arguments: ResidentBatchArgs + the members' frame fields
+    memset(&fa, 0, sizeof(fa));
+    lbm::ResidentBatchArgs& a = fa;
     a.plane_stride = c0->plane_stride;
     a.row_pitch = c0->row_pitch;
     a.pitch = c0->pitch;
@@ -1256,9 +1283,10 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
     a.member_wgs = bt->member_wgs;
     for (int first = 0; first < n_members; first += bt->members_per_launch) {
       a.members = tab + first;
+      fa.frames = bt->frame_table ? bt->frame_table + first : nullptr;
       a.n_members = (n_members - first < bt->members_per_launch) ? n_members - first : bt->members_per_launch;
       const int grid = a.one_xcd ? bt->member_wgs * 8 : a.n_members * (int)round_up(bt->member_wgs, 8);
-      void* args[] = {&a};
+      void* args[] = {&fa};
       HIP_TRY(LBM_FAILURE, hipLaunchKernel(kernel, dim3(grid), dim3(c0->p.nx * a.group), args, 0, bt->stream));
     }
     hipLaunchKernelGGL(lbm::reduce_band_partials_batch, dim3(n, n_members), dim3(64), 0, bt->stream, tab, bands,
@@ -1275,16 +1303,43 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
   return LBM_SUCCESS;
 }
 
-int run_steps(lbm_ctx* c, int n_steps, float* kernel_ms) {
-  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_run: null context");
-  if (n_steps < 0) LBM_FAIL(LBM_FAILURE, "lbm_run: negative step count");
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (n_steps == 0) return LBM_SUCCESS;
-  if (c->steps_done + n_steps > c->capacity)
-    LBM_FAIL(LBM_FAILURE, "lbm_run: %d steps requested but the av_vels record holds %d (maxIters)",
-             c->steps_done + n_steps, c->capacity);
-  if (c->halo != HALO_SELF && c->halo_mode != LBM_HALO_SYNC) return run_steps_stale(c, n_steps, kernel_ms);
+// frames recorded by the global steps [from, to): those with tt % frame_every == 0
+long long frames_between(const lbm_ctx* c, long long from, long long to) {
+  if (c->frame_every <= 0) return 0;
+  const long long e = c->frame_every;
+  return (to + e - 1) / e - (from + e - 1) / e;
+}
 
+// lbm_run / lbm_batch_run refuse a call whose frames would not fit the free slots, before any work is issued
+int frames_fit(const lbm_ctx* c, int n_steps, const char* who) {
+  const long long add = frames_between(c, c->steps_done, (long long)c->steps_done + n_steps);
+  const long long waiting = c->frames_written - c->frames_read;
+  if (waiting + add > c->frame_slots)
+    LBM_FAIL(LBM_FAILURE, "%s: %d steps would record %lld frames, but the frame buffer holds %d and %lld frames are waiting "
+             "(lbm_read_frames drains them)", who, n_steps, add, c->frame_slots, waiting);
+  return LBM_SUCCESS;
+}
+
+// the frame of the current (stored) lattice, on every slab's compute stream, into the next slot
+int take_frame(lbm_ctx* c) {
+  const long slot = (long)(c->frames_written % c->frame_slots);
+  if (for_slabs(c, [&](int s) -> int {
+        Slab& sl = c->slab[s];
+        HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+        const long n = (long)sl.rows * c->p.nx;
+        hipLaunchKernelGGL(lbm::frame_umag, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, (const float*)sl.lat[c->cur],
+                           (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx, sl.rows,
+                           sl.frames + slot * n);
+        HIP_TRY(LBM_FAILURE, hipGetLastError());
+        return LBM_SUCCESS;
+      }) != LBM_SUCCESS)
+    return LBM_FAILURE;
+  c->frames_written++;
+  return LBM_SUCCESS;
+}
+
+// n_steps timesteps on the kernels chosen by `resident` (no timing read-out: the caller does it)
+int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
   const float a1 = c->p.density * c->p.accel / 9.f;
   const float a2 = c->p.density * c->p.accel / 36.f;
   const bool halo = (c->halo != HALO_SELF);
@@ -1300,15 +1355,17 @@ int run_steps(lbm_ctx* c, int n_steps, float* kernel_ms) {
                              sl.accel_row, a1, a2);
           HIP_TRY(LBM_FAILURE, hipGetLastError());
         }
-        if (kernel_ms) HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_t0, sl.compute));
+        if (record_t0) HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_t0, sl.compute));
         return LBM_SUCCESS;
       }) != LBM_SUCCESS)
     return LBM_FAILURE;
 
-  if (c->resident && n_steps >= c->resident_min_steps) {
+  if (resident) {
+    const long long frames = frames_between(c, c->steps_done, (long long)c->steps_done + n_steps);
     if (run_resident(c, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
     c->steps_done += n_steps;
-    return kernel_ms ? read_step_timing(c, n_steps, kernel_ms) : LBM_SUCCESS;
+    c->frames_written += frames;  // recorded by the kernel itself
+    return LBM_SUCCESS;
   }
 
   int flushed_upto = c->steps_done;
@@ -1338,7 +1395,36 @@ int run_steps(lbm_ctx* c, int n_steps, float* kernel_ms) {
   }
   c->steps_done += n_steps;
   // (the last flush made every compute stream wait for its final boundary kernel)
+  return LBM_SUCCESS;
+}
 
+int run_steps(lbm_ctx* c, int n_steps, float* kernel_ms) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_run: null context");
+  if (n_steps < 0) LBM_FAIL(LBM_FAILURE, "lbm_run: negative step count");
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (n_steps == 0) return LBM_SUCCESS;
+  if (c->steps_done + n_steps > c->capacity)
+    LBM_FAIL(LBM_FAILURE, "lbm_run: %d steps requested but the av_vels record holds %d (maxIters)",
+             c->steps_done + n_steps, c->capacity);
+  if (frames_fit(c, n_steps, "lbm_run") != LBM_SUCCESS) return LBM_FAILURE;
+  if (c->halo != HALO_SELF && c->halo_mode != LBM_HALO_SYNC) return run_steps_stale(c, n_steps, kernel_ms);
+
+  // resident or per-pass: decided once per call, whether frames are armed or not
+  const bool resident = c->resident && n_steps >= c->resident_min_steps;
+  if (c->frame_every > 0 && !resident) {
+    // per-pass kernels: the call runs as the sub-calls that end at its frame steps, each followed by its frame
+    const int e = c->frame_every;
+    for (int t = 0; t < n_steps;) {
+      const int tt = c->steps_done, r = tt % e;
+      const long long frame_tt = r ? (long long)tt + (e - r) : tt;  // next frame step
+      const int seg = (frame_tt - tt + 1 < n_steps - t) ? (int)(frame_tt - tt + 1) : n_steps - t;
+      if (run_passes(c, seg, false, kernel_ms && t == 0) != LBM_SUCCESS) return LBM_FAILURE;
+      if (c->steps_done - 1 == frame_tt && take_frame(c) != LBM_SUCCESS) return LBM_FAILURE;
+      t += seg;
+    }
+  } else if (run_passes(c, n_steps, resident, kernel_ms != nullptr) != LBM_SUCCESS) {
+    return LBM_FAILURE;
+  }
   return kernel_ms ? read_step_timing(c, n_steps, kernel_ms) : LBM_SUCCESS;
 }
 
@@ -1603,6 +1689,7 @@ void free_slab(Slab& sl) {
   if (sl.res_part) (void)hipFree(sl.res_part);
   if (sl.res_status) (void)hipFree(sl.res_status);
   if (sl.res_status_host) (void)hipHostFree(sl.res_status_host);
+  if (sl.frames) (void)hipFree(sl.frames);
   if (sl.ev_boundary) (void)hipEventDestroy(sl.ev_boundary);
   if (sl.ev_halo) (void)hipEventDestroy(sl.ev_halo);
   for (int i = 0; i < 2; i++) if (sl.ev_interior[i]) (void)hipEventDestroy(sl.ev_interior[i]);
@@ -2077,7 +2164,7 @@ lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, con
     if (shape_ok && env_int("LBM_RESIDENT", other_kernel ? 0 : 1)) {
       int per_cu = 0;
       const int joint = (rows == 4 && nx <= 512 && env_int("LBM_RESIDENT_JOINT", nx <= 256 ? 1 : 0)) ? 1 : 0;
-      if (cus > 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resident_kernel(nx, rows, joint), nx, 0) == hipSuccess &&
+      if (cus > 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resident_kernel(nx, rows, joint, false), nx, 0) == hipSuccess &&
           per_cu >= 1 && ny / rows <= cus) {
         c->resident = 1;
         c->resident_rows = rows;
@@ -2427,7 +2514,121 @@ int lbm_set_halo_mode(lbm_ctx* c, int mode) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: null context");
   if (mode != LBM_HALO_SYNC && mode != LBM_HALO_STALE && mode != LBM_HALO_FRESHEST) LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: unknown mode %d", mode);
   if (mode == LBM_HALO_FRESHEST && c->halo == HALO_HOST) LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: the freshest-available mode is not available with the hosted exchange");
+  if (mode != LBM_HALO_SYNC && c->frame_every > 0)
+    LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: animation frames are armed (lbm_set_frames); the stale and freshest halo modes "
+             "cannot record them -- disarm with lbm_set_frames(ctx, 0, 0) first");
   c->halo_mode = mode;
+  return LBM_SUCCESS;
+}
+
+int lbm_set_frames(lbm_ctx* c, int every, int capacity) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_frames: null context");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_frames: negative interval %d", every);
+  if (every > 0 && capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_frames: capacity %d, at least one frame slot is needed", capacity);
+  if (every > 0 && c->halo_mode != LBM_HALO_SYNC)
+    LBM_FAIL(LBM_FAILURE, "lbm_set_frames: the context runs the %s halo mode, where splitting a call at a frame would change "
+             "the results (every call starts from freshly exchanged halos); frames need LBM_HALO_SYNC",
+             c->halo_mode == LBM_HALO_STALE ? "stale" : "freshest");
+  if (every > 0 && c->resident) {
+    // the FRAMES form of four-row bands defers the acceleration of the interior pair only (lbm::resident_band): the lid
+    // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form must run one workgroup per CU
+    if (c->resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_frames: the lid row %d is not an interior row of a four-row band", c->slab[0].accel_row);
+    int per_cu = 0;
+    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
+    HIP_TRY(LBM_FAILURE, hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                             &per_cu, resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, true), c->p.nx * c->resident_group, 0));
+    if (per_cu < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_frames: the resident kernel's frame form does not fit a CU at this shape");
+  }
+  // the buffers may still be written by launches in flight
+  for (int s = 0; s < c->n_slabs; s++) {
+    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
+    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
+  }
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    if (sl.frames) {
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      HIP_TRY(LBM_FAILURE, hipFree(sl.frames));
+      sl.frames = nullptr;
+    }
+  }
+  lbm_batch* bt = c->batch;
+  // a batch member's entry of the table the batched launches read
+  auto set_entry = [&](const lbm::ResidentFrames& entry) -> int {
+    if (!bt) return LBM_SUCCESS;
+    int index = 0;
+    while (bt->members[(size_t)index] != c) index++;
+    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
+    if (!bt->frame_table) {
+      HIP_TRY(LBM_FAILURE, hipMalloc(&bt->frame_table, bt->members.size() * sizeof(lbm::ResidentFrames)));
+      HIP_TRY(LBM_FAILURE, hipMemset(bt->frame_table, 0, bt->members.size() * sizeof(lbm::ResidentFrames)));
+    }
+    HIP_TRY(LBM_FAILURE, hipMemcpy(bt->frame_table + index, &entry, sizeof(entry), hipMemcpyHostToDevice));
+    return LBM_SUCCESS;
+  };
+  if (bt && c->frame_every > 0) bt->frames_armed--;
+  c->frame_every = c->frame_slots = c->frame_ord0 = 0;
+  c->frames_written = c->frames_read = 0;
+  if (set_entry({nullptr, 0, 0, 0}) != LBM_SUCCESS) return LBM_FAILURE;
+  if (every > 0) {
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      const size_t bytes = (size_t)capacity * (size_t)sl.rows * (size_t)c->p.nx * sizeof(float);
+      if (hipMalloc(&sl.frames, bytes) != hipSuccess) {
+        (void)hipGetLastError();  // a failed allocation must not surface at the next launch
+        for (int q = 0; q <= s; q++)
+          if (c->slab[q].frames) { (void)hipSetDevice(c->slab[q].device); (void)hipFree(c->slab[q].frames); c->slab[q].frames = nullptr; }
+        LBM_FAIL(LBM_FAILURE, "lbm_set_frames: cannot allocate %d frame slots (%.1f MiB per slab); frames stay off", capacity,
+                 (double)bytes / 1048576.0);
+      }
+    }
+    c->frame_every = every;
+    c->frame_slots = capacity;
+    c->frame_ord0 = (int)(((long long)c->steps_done + every - 1) / every);
+    if (set_entry({c->slab[0].frames, every, c->frame_ord0, capacity}) != LBM_SUCCESS) {
+      (void)hipFree(c->slab[0].frames);
+      c->slab[0].frames = nullptr;
+      c->frame_every = c->frame_slots = c->frame_ord0 = 0;
+      return LBM_FAILURE;
+    }
+    if (bt) bt->frames_armed++;
+  }
+  return LBM_SUCCESS;
+}
+
+int lbm_read_frames(lbm_ctx* c, int max_frames, float* out, int* steps, int* n_read) {
+  if (!c || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_read_frames: NULL argument");
+  *n_read = 0;
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
+  const long long waiting = c->frames_written - c->frames_read;
+  if (!out && !steps) {
+    *n_read = (int)waiting;
+    return LBM_SUCCESS;
+  }
+  if (!out) LBM_FAIL(LBM_FAILURE, "lbm_read_frames: NULL frame output");
+  if (max_frames < 0) LBM_FAIL(LBM_FAILURE, "lbm_read_frames: negative max_frames %d", max_frames);
+  const int n = (waiting < max_frames) ? (int)waiting : max_frames;
+  const size_t frame_cells = (size_t)c->row_count * c->p.nx;
+  for (int i = 0; i < n; i++) {
+    const long long ord = c->frames_read + i;
+    const size_t slot = (size_t)(ord % c->frame_slots);
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      const size_t cells = (size_t)sl.rows * c->p.nx;
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(out + i * frame_cells + (size_t)(sl.row_first - c->row_first) * c->p.nx,
+                                          sl.frames + slot * cells, cells * sizeof(float), hipMemcpyDeviceToHost, sl.compute));
+    }
+    if (steps) steps[i] = (int)((c->frame_ord0 + ord) * c->frame_every);
+  }
+  for (int s = 0; s < c->n_slabs; s++) {
+    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
+    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
+  }
+  c->frames_read += n;
+  *n_read = n;
   return LBM_SUCCESS;
 }
 
@@ -2645,6 +2846,7 @@ void lbm_destroy_batch(lbm_batch* bt) {
     lbm_destroy(c);
   }
   if (bt->table) (void)hipFree(bt->table);
+  if (bt->frame_table) (void)hipFree(bt->frame_table);
   if (bt->status) (void)hipFree(bt->status);
   if (bt->status_host) (void)hipHostFree(bt->status_host);
   delete bt;
@@ -2764,14 +2966,31 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
   if (bt->steps_done + n_steps > c0->capacity)
     LBM_FAIL(LBM_FAILURE, "lbm_batch_run: %d steps requested but the av_vels record holds %d (maxIters)",
              bt->steps_done + n_steps, c0->capacity);
+  for (lbm_ctx* c : bt->members)  // every member's frames must fit before any member runs
+    if (frames_fit(c, n_steps, "lbm_batch_run") != LBM_SUCCESS) return LBM_FAILURE;
   if (bt->resident && n_steps >= c0->resident_min_steps) {
     if (run_batch_resident(bt, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
-    for (lbm_ctx* c : bt->members) c->steps_done += n_steps;
+    for (lbm_ctx* c : bt->members) {
+      c->frames_written += frames_between(c, c->steps_done, (long long)c->steps_done + n_steps);
+      c->steps_done += n_steps;
+    }
   } else {
     // short calls and shapes the resident kernel does not take: the members one after another, per-pass kernels
     for (lbm_ctx* c : bt->members)
       if (run_steps(c, n_steps, nullptr) != LBM_SUCCESS) return LBM_FAILURE;
     bt->cur = c0->cur;
+    // a member with frames armed ran its call split at its frame steps, i.e. possibly another number of passes: its
+    // lattice may lie in the other buffer.  Batched launches take every member's lattice at the batch's parity
+    // (bt->table), so such a member's lattice moves there (a device copy on the batch's stream).
+    for (lbm_ctx* c : bt->members) {
+      if (c->cur == bt->cur) continue;
+      Slab& sl = c->slab[0];
+      const size_t lat_bytes = (size_t)(sl.rows + 2 * kHaloRows) * c->row_pitch * sizeof(float);
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(sl.lat_alloc[bt->cur], sl.lat_alloc[c->cur], lat_bytes, hipMemcpyDeviceToDevice,
+                                          bt->stream));
+      c->cur = bt->cur;
+    }
   }
   bt->steps_done += n_steps;
   return LBM_SUCCESS;

@@ -1550,6 +1550,21 @@ struct ResidentBatchArgs : ResidentArgs {
   int member_wgs;             // working workgroups of one member; without one_xcd member m starts at block
                               // m * round_up(member_wgs, 8), so the XCD-affinity band order holds inside every member
 };
+// animation frames (lbm_set_frames, resident_band<..., FRAMES = true>): after global step tt with tt % every == 0 the
+// kernel stores |u| of every owned cell into slot (tt / every - ord0) % slots of base, one float[rows][nx] per slot.
+// Kept out of ResidentArgs / ResidentMember so that the FRAMES = false forms read their arguments at the same offsets.
+struct ResidentFrames {
+  float* base;                // slot 0; nullptr / every = 0: no frames
+  int every;
+  int ord0;                   // tt / every of the first frame after arming
+  int slots;
+};
+struct ResidentFramesArgs : ResidentArgs {
+  ResidentFrames fr;
+};
+struct ResidentBatchFramesArgs : ResidentBatchArgs {
+  const ResidentFrames* frames;  // [this launch's members], as members
+};
 #ifdef LBM_RESIDENT_PROFILE
 __device__ __forceinline__ long long prof_clock() {
   long long t;
@@ -1579,6 +1594,16 @@ __device__ __forceinline__ float relax_pair_rows(const f2 (&f)[kQ], unsigned blo
   float sp0 = __builtin_amdgcn_sqrtf(u_sq.x), sp1 = __builtin_amdgcn_sqrtf(u_sq.y);
   relax_pair_fixup_rows(f, ok, blocked, lid, omega, a1, a2, r, sp0, sp1);
   return sp0 + sp1;
+}
+
+// |u| of cell c of a relaxed pair as lbm_read_final_state reports it (final_state: moments_exact, IEEE sqrt), 0 if blocked
+__device__ __forceinline__ float frame_speed(const f2 (&r)[kQ], int c, bool blocked) {
+  float f[kQ];
+#pragma unroll
+  for (int k = 0; k < kQ; k++) f[k] = r[k][c];
+  float rho, ux, uy;
+  moments_exact(f, rho, ux, uy);
+  return blocked ? 0.f : sqrtf((ux * ux) + (uy * uy));
 }
 
 // sum over the first 16 lanes (one DPP row), valid in every lane of that row
@@ -1654,8 +1679,15 @@ __device__ __forceinline__ granule_vec granule_load(__amdgpu_buffer_rsrc_t rsrc,
 // workgroup, so the member's fields are scalar loads before the step loop and the loop itself is the same.  One-XCD
 // shapes: member m = blockIdx.x & 7 runs on XCD m, on the workgroups the single form leaves idle; other shapes: members
 // take consecutive ranges of round_up(member_wgs, 8) blocks.  The seam protocol is per member (own granules, own tags).
-template <int MAXT, bool JOINT = false, int ROWS = 4, bool BATCH = false>
-__global__ __launch_bounds__(MAXT) void resident_band(const std::conditional_t<BATCH, ResidentBatchArgs, ResidentArgs> a) {
+// FRAMES: also record animation frames (ResidentFrames).  On a frame step the lid cells are relaxed WITHOUT the next
+// step's accelerate_flow, |u| of the post-step lattice goes to the frame slot, and only then is accelerate_select applied
+// to the relaxed values: bit-identical to the fused epilogue, since accelerate_select is a pure select on the relaxed
+// values that never touches a blocked cell (the only cells bounce_select changes).
+template <bool BATCH, bool FRAMES>
+using ResidentArgsOf = std::conditional_t<BATCH, std::conditional_t<FRAMES, ResidentBatchFramesArgs, ResidentBatchArgs>,
+                                          std::conditional_t<FRAMES, ResidentFramesArgs, ResidentArgs>>;
+template <int MAXT, bool JOINT = false, int ROWS = 4, bool BATCH = false, bool FRAMES = false>
+__global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH, FRAMES> a) {
   static_assert(ROWS == 4 || ROWS == 2, "bands of four or two rows");
   constexpr int NE = (ROWS == 4) ? 10 : 4;  // wave-edge values per side
   // a workgroup holds a.group bands side by side (1: the usual case; more where a band has fewer than four waves and
@@ -1665,13 +1697,16 @@ __global__ __launch_bounds__(MAXT) void resident_band(const std::conditional_t<B
   const int x = (int)threadIdx.x - grp * a.nx, lane = x & 63, wave = x >> 6, n_waves = a.nx >> 6, wv = (int)threadIdx.x >> 6, wv0 = wv - wave;
   int n_wgs = a.one_xcd ? (int)(gridDim.x >> 3) : (int)gridDim.x, wg = a.one_xcd ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
   ResidentMember mb{};
+  ResidentFrames fr{};
   if constexpr (BATCH) {
     const int stride = (a.member_wgs + 7) & ~7;
     const int member = a.one_xcd ? (int)(blockIdx.x & 7) : (int)blockIdx.x / stride;
     if (!a.one_xcd) { n_wgs = a.member_wgs; wg = (int)blockIdx.x - member * stride; }
     if (member >= a.n_members || wg >= n_wgs) return;
     mb = a.members[member];
+    if constexpr (FRAMES) fr = a.frames[member];
   } else if (a.one_xcd && (blockIdx.x & 7) != 0) return;
+  if constexpr (FRAMES && !BATCH) fr = a.fr;
 #define RES_M(field) (BATCH ? mb.field : a.field)
   const int bands = n_wgs * a.group;
   // Workgroups are dealt to the 8 XCDs round-robin (observed, not promised): consecutive bands are given to
@@ -1758,6 +1793,37 @@ __global__ __launch_bounds__(MAXT) void resident_band(const std::conditional_t<B
     else granule_store(grsrc, my_down + off, re[4].x, re[7].x, re[8].x, tag);
   };
   if (a.n_steps > 0) publish(0);
+  // frames: local step of the next one (~0u: none) and its slot
+  unsigned f_next = ~0u;
+  int f_slot = 0;
+  if constexpr (FRAMES) {
+    if (fr.every > 0) {
+      const unsigned e = (unsigned)fr.every, r = a.epoch0 % e;
+      f_next = r ? e - r : 0u;
+      f_slot = (int)(((a.epoch0 + f_next) / e - (unsigned)fr.ord0) % (unsigned)fr.slots);
+    }
+  }
+
+  // frames: |u| of the band's post-step cells (re, ri) into the slot, then the deferred accelerate_flow of the next step
+  // on `lidp`, the pair that holds the lid row (ROWS = 4: ri, ROWS = 2: the new edge pair)
+  auto take_frame = [&](f2 (&lidp)[kQ], bool accel_next) {
+    // the slot as a buffer (scalar base, 32-bit lane offset computed here): no 64-bit address stays live in VGPRs
+    const unsigned row_bytes = (unsigned)a.nx * 4u;
+    const __amdgpu_buffer_rsrc_t frsrc = __builtin_amdgcn_make_buffer_rsrc(fr.base + (long)f_slot * a.ny * a.nx, 0, (int)(row_bytes * (unsigned)a.ny), 0x00020000);
+    const int lane_off = (int)((unsigned)(ROWS * b) * row_bytes + (unsigned)x * 4u);
+    const f2 (&fe)[kQ] = (ROWS == 4) ? re : lidp;
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(frame_speed(fe, 0, (blocked_e & 0xffu) != 0)), frsrc, lane_off, 0, 2);  // aux 2 = nt
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(frame_speed(fe, 1, (blocked_e & 0xff00u) != 0)), frsrc, lane_off, (int)(TOP * row_bytes), 2);
+    if constexpr (ROWS == 4) {
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(frame_speed(ri, 0, (blocked_i & 0xffu) != 0)), frsrc, lane_off, (int)row_bytes, 2);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(frame_speed(ri, 1, (blocked_i & 0xff00u) != 0)), frsrc, lane_off, (int)(2 * row_bytes), 2);
+    }
+    const unsigned lid = (ROWS == 4) ? lid_i : lid_e, blk = (ROWS == 4) ? blocked_i : blocked_e;
+    if (accel_next && lid != 0)
+      accelerate_select(lidp, (lid & 1u) != 0 && (blk & 0xffu) == 0, (lid & 2u) != 0 && (blk & 0xff00u) == 0, RES_M(a1), RES_M(a2));
+    f_next += (unsigned)fr.every;
+    f_slot = (f_slot + 1 == fr.slots) ? 0 : f_slot + 1;
+  };
 
   bool alive = true;
 #ifdef LBM_RESIDENT_PROFILE
@@ -1819,7 +1885,13 @@ __global__ __launch_bounds__(MAXT) void resident_band(const std::conditional_t<B
     granule_vec ss = granule_load(grsrc, gs + x_side);
     granule_vec sn = granule_load(grsrc, gn + x_side);
 
-    const bool accel = (s + 1 < a.n_steps) || a.accel_last;
+    bool frame_now = false;
+    if constexpr (FRAMES) frame_now = ((unsigned)s == f_next);  // wave-uniform
+    const bool accel_next = (s + 1 < a.n_steps) || a.accel_last;
+    // a frame step applies the lid's acceleration after taking the frame (take_frame).  ROWS = 4: the lid row is
+    // band row 2 (ny - 2 with ny % 4 == 0; run_resident checks it), an interior row, so only the interior pair defers
+    const bool accel = accel_next && !(ROWS == 2 && frame_now);
+    const bool accel_i = FRAMES ? accel_next && !frame_now : accel;
     // shifted populations (the value each cell receives from its west / east neighbour) and the streamed inputs of
     // the pair(s), as far as they come from inside the band
     f2 ti[kQ], te[kQ];
@@ -1853,7 +1925,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const std::conditional_t<B
     }
     f2 ni[kQ];
     float sum = 0.f;
-    if constexpr (ROWS == 4 && !JOINT) sum = relax_pair_rows(ti, blocked_i, accel ? lid_i : 0u, RES_M(omega), RES_M(a1), RES_M(a2), ni);
+    if constexpr (ROWS == 4 && !JOINT) sum = relax_pair_rows(ti, blocked_i, accel_i ? lid_i : 0u, RES_M(omega), RES_M(a1), RES_M(a2), ni);
 
     RESIDENT_PROF(2);  // partial of the previous step, LDS edges read, shifts, halo loads issued, interior pair (ROWS 4, !JOINT)
     // ---- edge pair: rows 0 and TOP also pull from the neighbouring bands --------------------------------------
@@ -1899,8 +1971,11 @@ __global__ __launch_bounds__(MAXT) void resident_band(const std::conditional_t<B
     te[7].y = shift_from_east(__uint_as_float((unsigned)cn.y), side_n);
     te[8].y = shift_from_west(__uint_as_float((unsigned)cn.z), side_n);
     f2 ne[kQ];
-    if constexpr (ROWS == 4 && JOINT) sum = relax_two_pairs_rows(ti, te, blocked_i, blocked_e, accel ? lid_i : 0u, accel ? lid_e : 0u, RES_M(omega), RES_M(a1), RES_M(a2), ni, ne);
+    if constexpr (ROWS == 4 && JOINT) sum = relax_two_pairs_rows(ti, te, blocked_i, blocked_e, accel_i ? lid_i : 0u, accel ? lid_e : 0u, RES_M(omega), RES_M(a1), RES_M(a2), ni, ne);
     else sum += relax_pair_rows(te, blocked_e, accel ? lid_e : 0u, RES_M(omega), RES_M(a1), RES_M(a2), ne);
+    if constexpr (FRAMES && ROWS == 2) {
+      if (frame_now) take_frame(ne, accel_next);
+    }
 #pragma unroll
     for (int k = 0; k < kQ; k++) {
       re[k] = ne[k];
@@ -1912,6 +1987,10 @@ __global__ __launch_bounds__(MAXT) void resident_band(const std::conditional_t<B
     // blocked cells report 0; sum over the wave, one partial per wave into LDS (summed after the next barrier)
     const float tot = wave_sum_dpp(sum);
     if (lane == 63) wave_part[slot][wv] = tot;
+    // ROWS = 4: the frame once the step's own work is out (fewest live registers: the 128-VGPR form does not spill)
+    if constexpr (FRAMES && ROWS == 4) {
+      if (frame_now) take_frame(ri, accel_next);
+    }
     RESIDENT_PROF(6);  // publish, wave sum
     // (a wave that gave up leaves the loop alone: the hardware barrier counts only waves that have not ended, and
     // the others find *status set in their next spin)
@@ -2187,6 +2266,26 @@ __global__ void final_state(const float* lat, const unsigned char* mask, long ps
     ux_o[i] = ux;  uy_o[i] = uy;
     um_o[i] = sqrtf((ux * ux) + (uy * uy));
     pr_o[i] = rho * kCsq;
+  }
+}
+
+// one animation frame of a stored lattice (lbm_set_frames, per-pass paths): final_state's |u| alone, into out[nrows][nx]
+__global__ void frame_umag(const float* lat, const unsigned char* mask, long ps, long row_pitch, int pitch, int nx,
+                           int nrows, float* out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long n = (long)nx * nrows;
+  if (i >= n) return;
+  const int r = (int)(i / nx), x = (int)(i - (long)r * nx);
+  const long c = (long)r * row_pitch + x;
+  if (mask[(long)r * pitch + x]) {
+    out[i] = 0.f;
+  } else {
+    float f[kQ];
+#pragma unroll
+    for (int k = 0; k < kQ; k++) f[k] = lat[k * ps + c];
+    float rho, ux, uy;
+    moments_exact(f, rho, ux, uy);
+    out[i] = sqrtf((ux * ux) + (uy * uy));
   }
 }
 

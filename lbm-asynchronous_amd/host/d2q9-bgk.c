@@ -14,10 +14,16 @@
  *                         nx x ny grid of the parameter file (synthetic 8192^2 / 16384^2 grids)
  *   LBM_OUTPUT=text|none  write final_state.dat / av_vels.dat (default) or skip final_state.dat
  *   LBM_PRESSURE_BIN=<f>  additionally dump the fp32 pressure field (ny*nx floats) to <f>
+ *   LBM_ANIMATION=<every> write animation_data/velocity_magnitude_%06d.dat after every timestep tt with
+ *                         tt % every == 0 (the reference's commented-out write_animation_data hook, :171-173,
+ *                         :802-849), created if missing; unset or 0: off.  The frames are recorded on the device
+ *                         (lbm_set_frames); the loop runs in segments whose frames fit 1 GiB and is drained after each.
+ *                         final_state.dat and av_vels.dat are unchanged.
  */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/stat.h>
 #include <sys/time.h>
 
 #include "lbm_io.h"
@@ -84,8 +90,42 @@ int main(int argc, char* argv[])
   lbm_sync(ctx);
   const double init_toc = wall_seconds();
 
+  int anim_every = 0;
+  if ((env = getenv("LBM_ANIMATION")) && *env) anim_every = atoi(env);
+
   /* Compute time: the whole timestep loop (:166-170) */
-  lbm_run(ctx, params.max_iters);
+  if (anim_every > 0) {
+    /* with frames: segments whose frames fit 1 GiB of device memory, each drained and written after it */
+    const size_t frame_cells = (size_t)params.nx * (size_t)params.ny;
+    long cap = (long)((1UL << 30) / (frame_cells * sizeof(float)));
+    const long total_frames = params.max_iters > 0 ? (params.max_iters + anim_every - 1) / anim_every : 0;
+    if (cap > total_frames) cap = total_frames;
+    if (cap < 1) cap = 1;
+    if (mkdir("animation_data", 0777) != 0) {
+      struct stat st;
+      if (stat("animation_data", &st) != 0 || !S_ISDIR(st.st_mode)) lbm_die("could not create animation_data", __LINE__, __FILE__);
+    }
+    if (lbm_set_frames(ctx, anim_every, (int)cap) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+    float* frames = (float*)malloc(frame_cells * sizeof(float) * (size_t)cap);
+    int* steps = (int*)malloc(sizeof(int) * (size_t)cap);
+    if (frames == NULL || steps == NULL) lbm_die("cannot allocate memory for animation frames", __LINE__, __FILE__);
+    const long seg = cap * (long)anim_every;
+    for (long t = 0; t < params.max_iters;) {
+      const int n = (int)((params.max_iters - t < seg) ? params.max_iters - t : seg);
+      if (lbm_run(ctx, n) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+      int n_read = 0;
+      if (lbm_read_frames(ctx, (int)cap, frames, steps, &n_read) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+      for (int i = 0; i < n_read; i++) {
+        lbm_write_animation_frame("animation_data", params.nx, params.ny, steps[i], frames + (size_t)i * frame_cells);
+        printf("Written animation data for timestep %d\n", steps[i]);
+      }
+      t += n;
+    }
+    free(frames);
+    free(steps);
+  } else {
+    lbm_run(ctx, params.max_iters);
+  }
   lbm_sync(ctx);
   const double comp_toc = wall_seconds();
 

@@ -148,3 +148,15 @@ void lbm_write_av_vels(const char* path, const float* av_vels, int n)
   for (int ii = 0; ii < n; ii++) fprintf(fp, "%d:\t%.12E\n", ii, av_vels[ii]);
   fclose(fp);
 }
+
+void lbm_write_animation_frame(const char* dir, int nx, int ny, int timestep, const float* u_mag)
+{
+  char filename[4096];
+  snprintf(filename, sizeof(filename), "%s/velocity_magnitude_%06d.dat", dir, timestep);
+  FILE* fp = fopen(filename, "w");
+  if (fp == NULL) lbm_die("could not open animation data file", __LINE__, __FILE__);
+  fprintf(fp, "# nx=%d ny=%d timestep=%d\n", nx, ny, timestep);
+  const size_t n = (size_t)nx * (size_t)ny;
+  for (size_t c = 0; c < n; c++) fprintf(fp, "%.6E\n", u_mag[c]);
+  fclose(fp);
+}

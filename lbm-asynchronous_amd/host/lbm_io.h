@@ -39,6 +39,9 @@ void lbm_write_final_state_rows(FILE* fp, const lbm_params* params, int row_firs
                                 const float* u_x, const float* u_y, const float* u_mag,
                                 const float* pressure, const int* obstacles);
 
+/* animation_data/velocity_magnitude_%06d.dat of write_animation_data() (:802-849): "# nx=%d ny=%d timestep=%d",
+ * then one "%.6E" line per cell of u_mag[ny*nx] (0 for blocked cells), jj outer / ii inner */
+void lbm_write_animation_frame(const char* dir, int nx, int ny, int timestep, const float* u_mag);
 /* av_vels.dat: "%d:\t%.12E\n" (:735-738) */
 void lbm_write_av_vels(const char* path, const float* av_vels, int n);
 
