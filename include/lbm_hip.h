@@ -103,6 +103,8 @@ typedef struct {
   int    resident_rows;      /* resident kernel: rows per band (4 or 2) ... */
   int    resident_group;     /* ... bands per workgroup (1, 2 or 4) ... */
   int    resident_one_xcd;   /* ... and 1 where the whole grid (at most 128 waves) runs on one XCD, one wave per SIMD */
+  int    band_groups;    /* single periodic slab: full-depth stream-kernel passes issued as this many row groups on their
+                            own streams, so that successive passes overlap (1: one launch per pass) */
 } lbm_info;
 
 /* ---- error handling -------------------------------------------------------------------- */

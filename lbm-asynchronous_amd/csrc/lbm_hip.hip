@@ -152,6 +152,8 @@ RcclApi* rccl() {
   RcclApi* rc_api_ = rccl();                                                    \
   if (!rc_api_) LBM_FAIL(ret, "RCCL is not available: %s", g_rccl_error)
 
+constexpr int kMaxBandGroups = 3;  // interior streams of the band-group path: with the seam stream four in all
+
 struct Slab {
   int device = 0;
   int row_first = 0;  // global row of slab row 0
@@ -180,6 +182,11 @@ struct Slab {
   hipEvent_t ev_step = nullptr;                    // stale-halo mode: whole-slab pass finished; graph replay: join
   hipEvent_t ev_fork = nullptr;                    // graph replay: the other streams join the capture / follow the chunks
   hipEvent_t ev_x[2] = {nullptr, nullptr};         // stale-halo mode: exchange for pass m landed -> [(m + 1) & 1]
+  // band groups (single periodic slab, c->band_groups > 1): interior bands of group g run on group_stream(g) -- the
+  // compute stream for g = 0, group_extra[g - 1] after it -- and the seam bands on the comm stream
+  hipStream_t group_extra[kMaxBandGroups - 1] = {nullptr, nullptr};
+  hipEvent_t ev_gi[2][kMaxBandGroups] = {};        // interior bands of group g in pass m done -> [m & 1][g]
+  hipEvent_t ev_gs[2] = {nullptr, nullptr};        // seam bands of pass m done -> [m & 1]
   // freshest-available mode (LBM_HALO_FRESHEST), allocated at its first use
   float* fresh_stage = nullptr;          // [parity][side: 0 south halo, 1 north halo][row_pitch]: this pass's rows, if they make it
   unsigned* fresh_arrived = nullptr;     // [parity][side]: id (global step + 1) of the step whose row the staging holds
@@ -357,6 +364,8 @@ struct lbm_ctx {
   int halo_lanes = 1;  // stream kernel: lanes at each end of a wave that only feed their neighbours
   int lds_windows = 0; // packed stream kernel: how many of the K-1 sliding windows live in LDS (LBM_LDS_WINDOWS, 0..2)
   int band_rows = 8, n_strips = 0;  // step2_stream geometry: band height, waves across x
+  int band_groups = 1;              // single periodic slab: full-depth passes as this many band groups (LBM_BAND_GROUPS)
+  bool groups_forked = false;       // ... the group and seam streams have been forked off the compute stream
   int lane_cells = 4;               // cells per lane in step2_stream (4 or 2; LBM_LANE_CELLS)
   SlabTeam* team = nullptr;         // one issuing thread per slab (one-process multi-GPU), or null
   int use_graph = 0;                // replay chunks of an even number of passes + their reduce as one hipGraph each
@@ -963,6 +972,98 @@ int issue_pass(lbm_ctx* c, int m, int tile, int k, bool accel_after, bool bound_
   return LBM_SUCCESS;
 }
 
+// Band groups: the full-depth (K-step) passes of a single periodic slab, issued so that successive passes overlap.
+// The rows are cut into G groups [lo_g, hi_g) (lo_g = g H, H = rows / G, the last group takes the remainder).  Of
+// pass m, the interior rows [lo_g + K, hi_g - K) of group g are I_g(m), on group stream g; the 2K seam rows
+// [lo_g - K, lo_g + K) around every group start (wrapping at row 0) are S(m), one launch of G bands H rows apart, on
+// the comm stream.  All of them read lat[cur] and write lat[cur ^ 1]; an output row y reads rows y-K .. y+K.
+//
+//   group stream g:  I_g(0) ───────► I_g(1) ───────► I_g(2) ...
+//                        ▲ waits S(m-1)   ▲
+//   comm stream:     S(0) ───────► S(1) ───────► S(2) ...
+//                        ▲ waits I_0(m-1) .. I_{G-1}(m-1)
+//
+//   I_g(m) reads rows [lo_g, hi_g) of lattice m: written by I_g(m-1) (stream order) and S(m-1) (waited for).  It
+//     writes rows [lo_g + K, hi_g - K) of lattice m+1, which pass m-1 read in I_g(m-1) and S(m-1) only.
+//   S(m) reads rows [lo_g - 2K, lo_g + 2K): written by S(m-1) (stream order) and the interiors of the two groups
+//     that meet there (waited for).  It writes the seam rows, which pass m-1 read in S(m-1) and in the interiors of
+//     both groups (waited for).
+// No edge runs from I_g(m) to I_h(m+1) (h != g): the interior chains drift up to a pass apart and fill the end of
+// each other's launches.  Every other kind of pass, the reduce of the partials, frames and the end of a call run on
+// the compute stream behind group_join; the streams fork off it again (group_fork) before the next grouped pass.
+hipStream_t group_stream(Slab& sl, int g) { return g == 0 ? sl.compute : sl.group_extra[g - 1]; }
+
+// the other streams follow everything enqueued on the compute stream; pass m is the next grouped pass
+int group_fork(lbm_ctx* c, int m) {
+  Slab& sl = c->slab[0];
+  const int prev = (m - 1) & 1;
+  if (q_record(c, sl.ev_gs[prev], sl.compute) != LBM_SUCCESS) return LBM_FAILURE;
+  for (int g = 0; g < c->band_groups; g++)
+    if (q_record(c, sl.ev_gi[prev][g], sl.compute) != LBM_SUCCESS) return LBM_FAILURE;
+  c->groups_forked = true;
+  return LBM_SUCCESS;
+}
+
+// the compute stream follows the last grouped pass m on every stream
+int group_join(lbm_ctx* c, int m) {
+  if (!c->groups_forked) return LBM_SUCCESS;
+  Slab& sl = c->slab[0];
+  if (q_wait(c, sl.compute, sl.ev_gs[m & 1]) != LBM_SUCCESS) return LBM_FAILURE;
+  for (int g = 1; g < c->band_groups; g++)
+    if (q_wait(c, sl.compute, sl.ev_gi[m & 1][g]) != LBM_SUCCESS) return LBM_FAILURE;
+  c->groups_forked = false;
+  return LBM_SUCCESS;
+}
+
+// rows [lo, hi) of group g; returns the group height H (the last group also takes the remainder)
+int group_rows(const lbm_ctx* c, int g, int* lo, int* hi) {
+  const int rows = c->slab[0].rows, h = rows / c->band_groups;
+  *lo = g * h;
+  *hi = (g == c->band_groups - 1) ? rows : *lo + h;
+  return h;
+}
+// waves of a grouped pass of k steps: the interior bands of every group and G seam bands; partial slots in this order
+int grouped_waves(const lbm_ctx* c, int k) {
+  int bands = c->band_groups;
+  for (int g = 0; g < c->band_groups; g++) {
+    int lo, hi;
+    group_rows(c, g, &lo, &hi);
+    bands += ceil_div(hi - lo - 2 * k, c->band_rows);
+  }
+  return c->n_strips * bands;
+}
+
+// pass m (k steps) of the single periodic slab as band groups; the streams have been forked (group_fork)
+int issue_grouped_pass(lbm_ctx* c, int m, int k, bool accel_after, bool bound_events) {
+  Slab& sl = c->slab[0];
+  const int G = c->band_groups, now = m & 1, prev = now ^ 1;
+  int off = 0, h = 0;
+  for (int g = 0; g < G; g++) {
+    int lo, hi;
+    h = group_rows(c, g, &lo, &hi);
+    const hipStream_t st = group_stream(sl, g);
+    if (q_wait(c, st, sl.ev_gs[prev]) != LBM_SUCCESS) return LBM_FAILURE;  // S(m-1)
+    const int bands = ceil_div(hi - lo - 2 * k, c->band_rows);
+    hipEvent_t done = bound_events ? sl.ev_gi[now][g] : nullptr;
+    if (launch_pass(c, 0, st, k, lo + k, hi - k, c->band_rows, c->band_rows, bands, off, accel_after, done) != LBM_SUCCESS)
+      return LBM_FAILURE;
+    if (!done && q_record(c, sl.ev_gi[now][g], st) != LBM_SUCCESS) return LBM_FAILURE;
+    off += c->n_strips * bands;
+  }
+  for (int g = 0; g < G; g++)
+    if (q_wait(c, sl.comm, sl.ev_gi[prev][g]) != LBM_SUCCESS) return LBM_FAILURE;  // I_g(m-1)
+  // seam band g: output rows [g h - k, g h + k); band 0 starts below row 0 and the kernel folds it to the top rows
+  hipEvent_t sdone = bound_events ? sl.ev_gs[now] : nullptr;
+  if (launch_pass(c, 0, sl.comm, k, -k, (G - 1) * h + k, 2 * k, h, G, off, accel_after, sdone) != LBM_SUCCESS)
+    return LBM_FAILURE;
+  if (!sdone && q_record(c, sl.ev_gs[now], sl.comm) != LBM_SUCCESS) return LBM_FAILURE;
+  off += c->n_strips * G;
+  for (int j = 0; j < k; j++) sl.slot_counts.n[c->slot_fill + j] = off;
+  c->cur ^= 1;
+  c->slot_fill += k;
+  return LBM_SUCCESS;
+}
+
 // ---- hipGraph replay of the timestep loop ---------------------------------------------------------------------
 // A chunk = an even number of passes (so that it starts and ends on the same lattice buffer) and the reduce of
 // their partial sums, built ONCE per lattice parity -- both streams of every slab, the halo exchange (RCCL
@@ -1385,9 +1486,19 @@ int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
     const int k = (!tile && c->fuse2 && n_steps - t >= 2) ? (n_steps - t >= c->pass_steps ? c->pass_steps : 2) : 0;
     const int adv = tile ? tile : (k ? k : 1);
     const bool last = (t + adv == n_steps);
-    if (issue_pass(c, m, tile, k, !last, ext_events != 0) != LBM_SUCCESS) return LBM_FAILURE;
+    // full-depth passes of a single periodic slab as band groups; every other pass behind a join
+    const bool grouped = (c->band_groups > 1 && !halo && !tile && k == c->pass_steps);
+    if (grouped) {
+      if (!c->groups_forked && group_fork(c, m) != LBM_SUCCESS) return LBM_FAILURE;
+      if (issue_grouped_pass(c, m, k, !last, ext_events != 0) != LBM_SUCCESS) return LBM_FAILURE;
+    } else {
+      if (group_join(c, m - 1) != LBM_SUCCESS) return LBM_FAILURE;
+      if (issue_pass(c, m, tile, k, !last, ext_events != 0) != LBM_SUCCESS) return LBM_FAILURE;
+    }
     t += adv;
     if (c->slot_fill + slots_per_pass > kPartSlots || last) {
+      // the reduce reads the partials of every stream; the streams fork again after it
+      if (grouped && group_join(c, m) != LBM_SUCCESS) return LBM_FAILURE;
       if (flush_partials(c, flushed_upto) != LBM_SUCCESS) return LBM_FAILURE;
       flushed_upto += c->slot_fill;
       c->slot_fill = 0;
@@ -1699,6 +1810,11 @@ void free_slab(Slab& sl) {
   for (int i = 0; i < 2; i++) if (sl.ev_x[i]) (void)hipEventDestroy(sl.ev_x[i]);
   if (sl.ev_t0) (void)hipEventDestroy(sl.ev_t0);
   if (sl.ev_t1) (void)hipEventDestroy(sl.ev_t1);
+  for (int i = 0; i < 2; i++) {
+    if (sl.ev_gs[i]) (void)hipEventDestroy(sl.ev_gs[i]);
+    for (int g = 0; g < kMaxBandGroups; g++) if (sl.ev_gi[i][g]) (void)hipEventDestroy(sl.ev_gi[i][g]);
+  }
+  for (int g = 0; g < kMaxBandGroups - 1; g++) if (sl.group_extra[g]) (void)hipStreamDestroy(sl.group_extra[g]);
   if (sl.compute) (void)hipStreamDestroy(sl.compute);
   if (sl.comm) (void)hipStreamDestroy(sl.comm);
   sl = Slab();
@@ -1733,6 +1849,13 @@ int build_slab(lbm_ctx* c, int s, const ObstacleSource& obst, const float* cells
   HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_halo, sl.comm));
   HIP_TRY(LBM_FAILURE, hipEventCreate(&sl.ev_t0));
   HIP_TRY(LBM_FAILURE, hipEventCreate(&sl.ev_t1));
+  if (c->band_groups > 1) {
+    for (int g = 0; g < c->band_groups - 1; g++) HIP_TRY(LBM_FAILURE, hipStreamCreateWithFlags(&sl.group_extra[g], hipStreamNonBlocking));
+    for (int i = 0; i < 2; i++) {
+      HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_gs[i], hipEventDisableTiming));
+      for (int g = 0; g < c->band_groups; g++) HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_gi[i][g], hipEventDisableTiming));
+    }
+  }
 
   // lattices with kHaloRows halo rows below and above the owned rows (zeroed: pitch padding and
   // unused halo rows stay finite); lat[] points at owned row 0
@@ -2053,6 +2176,15 @@ lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, con
   if (c->xcd_chunk < 0 || c->xcd_chunk > c->n_strips) c->xcd_chunk = 0;
   c->use_stepk = env_int("LBM_STEPK", 0) ? 1 : 0;
 
+  // Band groups (issue_grouped_pass): a single periodic slab issues its full-depth passes as G row groups on their own
+  // streams, so that the next pass of one group fills the end of the current pass of the others.  Default: two groups
+  // where four-step passes run on four-cell lanes (the launches there are one round of waves each, whose last waves
+  // leave most of the chip idle); LBM_BAND_GROUPS overrides (1 = one launch per pass; at most kMaxBandGroups).
+  if (!halo_on && n_slabs == 1 && c->fuse2 && !c->use_graph) {
+    c->band_groups = env_int("LBM_BAND_GROUPS", (c->lane_cells == 4 && c->pass_steps == 4) ? 2 : 1);
+    if (c->band_groups < 1) c->band_groups = 1;
+    if (c->band_groups > kMaxBandGroups) c->band_groups = kMaxBandGroups;
+  }
   // Band height.  A wave sweeps band_rows + 2 rows.
   //   4-cell form (256 CUs x 12 waves resident): short bands, by row width -- measured optimum 7 rows at 8192 cells
   //   per row (8192^2: 0.477-0.480 ms vs 0.481-0.484 at 6, 0.495 at 4; same in the halo pipeline), 4-5 rows for
@@ -2093,10 +2225,13 @@ lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, con
       // 24 / 32 rows 0.293 / 0.296; K = 3: 44 rows = 3.10 rounds 0.389, 46 rows 0.350).  Round 3: heights up to 160
       // rows -- ONE round of 2040 waves at 8192^2 (137 rows: 6 warm-up rows per 137 instead of per 46) 0.2691 vs
       // 0.2757 at 46, 0.2736 at 69 (two rounds), 0.284 at 92, 0.334 at 119, 0.321 at 180 (same box).
-      const long interior = (n_slabs > 1 || world > 1 || halo_on) ? rows_eff + 4 - 2 * c->pass_steps : rows_eff;
+      // band groups: the interiors of the G groups are in flight together, and their waves fill the rounds together
+      const int groups = c->band_groups;
+      const long interior = (n_slabs > 1 || world > 1 || halo_on) ? rows_eff + 4 - 2 * c->pass_steps
+                                                                  : (groups > 1 ? rows_eff / groups - 2 * c->pass_steps : rows_eff);
       const long r_int = interior > 1 ? interior : 1;
       const int warm = 2 * (c->pass_steps - 1);
-      if ((long)c->n_strips * ceil_div(r_int, 24) >= 16L * 1024) {
+      if (groups * (long)c->n_strips * ceil_div(r_int, 24) >= 16L * 1024) {
         pick = 32;  // many rounds (XCD-chunked order): flat in the height, 16384^2 24 / 32 / model (48) = 1.078 / 1.077 / 1.098
       } else {
         // rounds of 2048 resident waves; a last round that fills at most half of the slots leaves one wave per SIMD,
@@ -2104,7 +2239,7 @@ lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, con
         double best = -1.0;
         const int b_max = env_int("LBM_BAND_MAX", 160);
         for (int b = 8; b <= b_max; b++) {
-          const long waves = (long)c->n_strips * ceil_div(r_int, b);
+          const long waves = groups * (long)c->n_strips * ceil_div(r_int, b);
           const long full = waves / 2048, rest = waves % 2048;
           double rounds = (double)full + (rest == 0 ? 0.0 : (rest > 1024 ? 1.0 : 0.6));
           if (rounds < 1.0) rounds = 1.0;  // a lone wave on a SIMD hides no latency
@@ -2116,10 +2251,16 @@ lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, con
     c->band_rows = env_int("LBM_BAND_ROWS", pick);
   }
   if (c->band_rows < 1) c->band_rows = 1;
+  if (c->band_groups > 1) {
+    // every group keeps an interior: by default a couple of bands, at least one row when asked for
+    const int interior = c->row_count / c->band_groups - 2 * c->pass_steps;
+    if (interior < (getenv("LBM_BAND_GROUPS") ? 1 : 2 * c->band_rows)) c->band_groups = 1;
+  }
   for (int s = 0; s < n_slabs; s++) {
     const int waves = c->n_strips * (ceil_div(c->slab[s].rows, c->band_rows) + 2);
     if (c->fuse2 && waves > max_blocks) max_blocks = waves;
   }
+  if (c->band_groups > 1 && grouped_waves(c, c->pass_steps) > max_blocks) max_blocks = grouped_waves(c, c->pass_steps);
   // LDS-tile kernel (several timesteps per launch) for small single-slab grids: LBM_TILE_STEPS overrides
   if (!halo_on) {
     // measured (us per step; one-step kernels | 16x8 tiles, 4 steps per launch | 32x16 tiles, 3 steps per launch):
@@ -2136,6 +2277,7 @@ lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, con
     if (c->tile_shape < 0 || c->tile_shape >= kTileShapeCount) c->tile_shape = 0;
     if (c->tile_steps < 0 || c->tile_steps > kTileShapes[c->tile_shape].kmax) c->tile_steps = kTileShapes[c->tile_shape].kmax;
     if (c->tile_steps && tile_count_for(params, c->tile_shape) > max_blocks) max_blocks = tile_count_for(params, c->tile_shape);
+    if (c->tile_steps) c->band_groups = 1;  // (the tile kernel runs every pass)
     // a graph chunk is kPartSlots timesteps in an even number of passes
   }
   c->part_stride = round_up(max_blocks, 64);
@@ -2470,6 +2612,7 @@ void lbm_destroy(lbm_ctx* c) {
       (void)hipSetDevice(c->slab[s].device);
       (void)hipStreamSynchronize(c->slab[s].compute);
       (void)hipStreamSynchronize(c->slab[s].comm);
+      for (hipStream_t g : c->slab[s].group_extra) if (g) (void)hipStreamSynchronize(g);
     }
   }
   for (int s = 0; s < c->n_slabs; s++) free_slab(c->slab[s]);
@@ -2507,6 +2650,7 @@ int lbm_get_info(const lbm_ctx* c, lbm_info* out) {
   out->resident_rows = c->resident ? c->resident_rows : 0;
   out->resident_group = c->resident ? c->resident_group : 0;
   out->resident_one_xcd = c->resident ? c->resident_one_xcd : 0;
+  out->band_groups = stream_kernel ? c->band_groups : 1;
   return LBM_SUCCESS;
 }
 
@@ -2651,6 +2795,7 @@ int lbm_sync(lbm_ctx* c) {
     HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
     HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
     HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].comm));
+    for (hipStream_t g : c->slab[s].group_extra) if (g) HIP_TRY(LBM_FAILURE, hipStreamSynchronize(g));
   }
   if (c->resident_used) {
     // did every workgroup of the resident kernel get its neighbours' rows in time?  (a batch member: of any batched launch)
