@@ -341,6 +341,41 @@ int   lbm_calc_reynolds(lbm_ctx* ctx, float* out);
 int lbm_set_frames(lbm_ctx* ctx, int every, int capacity);
 int lbm_read_frames(lbm_ctx* ctx, int max_frames, float* out, int* steps, int* n_read);
 
+/* ---- steady-state runs ----------------------------------------------------------------------
+ * The reference runs a fixed number of timesteps (maxIters, SerialCode/d2q9-bgk.c:166); none of its data sets has
+ * stopped changing by then.  lbm_run_until advances the lattice until its average velocity has, with the decision taken
+ * on the device next to the per-step sums (four bytes come back per check), or until max_steps.
+ * The criterion, with check_every = E >= 1, tol >= 0, patience = P >= 1, max_steps = N >= 0: the call runs segments of
+ * E timesteps counted from its start.  After segment j (j = 1, 2, ...):
+ *   av[s]  = the float lbm_read_av_vels returns for step s ((float)tot_u[s] / (float)fluid_cells), for its E steps;
+ *   m_j    = (sum of av[s] as double) / (double)E, summed as a 64-lane reduction: lane i adds elements i, i+64, ... in
+ *            turn, then acc[i] += acc[i+off] for off = 32, 16, ..., 1;
+ *   r_j    = |m_j - m_(j-1)| / |m_j| from j = 2 on (m_j == 0: +inf, or 0 when both are 0); the check is met when
+ *            r_j <= tol; `streak` counts consecutive checks met.
+ * The run is steady when streak == P; the call ends with that segment, after j*E steps.  If N comes first the call ends
+ * there, not steady; a last segment shorter than E is run and not checked.  Window means and patience rather than two
+ * single values: an oscillating series (the 1024x1024 data set) crosses any single-value test on its zero crossings.
+ * The call is synchronous (it returns when the answer is known) and advances steps_done by steps_run; lattice and
+ * av_vels are exactly those of lbm_run(steps_run).  Single periodic slabs that run the resident kernel with
+ * E >= resident_min_steps keep one segment in flight while the host waits for the verdict of the one before (segments of
+ * at most resident_steps timesteps); a segment enqueued behind a "stop" is dropped without a trace.
+ * Refused before any work is issued: steps_done + max_steps beyond the av_vels record, E < 1, P < 1, tol negative or
+ * NaN, frames armed (lbm_set_frames), halo modes other than LBM_HALO_SYNC, multi-process (rank) contexts, contexts of
+ * several slabs, batch members.
+ * lbm_batch_run_until: the same for every member of a batch, one check launch for all; the batch stops when every member
+ * is steady (or at N).  Members that are steady keep stepping with the others, so each stays bit-identical to an
+ * lbm_create context advanced by *steps_run; out[i].steady_step tells when member i got there.
+ */
+typedef struct {
+  int    steps_run;    /* timesteps this call advanced */
+  int    steady;       /* 1: the criterion was met */
+  int    steady_step;  /* steps of this call after which it was first met (-1: never) */
+  int    checks;       /* checks made (r_j computed) until then */
+  double last_rel;     /* r_j of the last of them (+inf when none was made) */
+  double last_mean;    /* m_j of the last checked segment (0 when there was none) */
+} lbm_steady_result;
+int lbm_run_until(lbm_ctx* ctx, int max_steps, int check_every, double tol, int patience, lbm_steady_result* out);
+
 /* ---- batches: many small lattices advanced together ---------------------------------------
  * A sweep over omega / accel / obstacle maps (each member reports its own calc_reynolds, :637-642) as ONE engine: B
  * independent single-slab lattices of one shape on one device, each advanced by n trips of the driver loop
@@ -372,6 +407,8 @@ lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* 
                             int math_mode);
 lbm_ctx*   lbm_batch_member(lbm_batch* batch, int index);
 int        lbm_batch_run(lbm_batch* batch, int n_steps);
+int        lbm_batch_run_until(lbm_batch* batch, int max_steps, int check_every, double tol, int patience,
+                               lbm_steady_result* out /* [members] */, int* steps_run);
 int        lbm_batch_sync(lbm_batch* batch);
 int        lbm_batch_get_info(const lbm_batch* batch, lbm_batch_info* out);
 void       lbm_destroy_batch(lbm_batch* batch);

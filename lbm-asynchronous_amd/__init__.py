@@ -47,7 +47,7 @@ ABI_SYMBOLS = (
     "lbm_create_rank_hosted_tiled", "lbm_destroy",
     "lbm_get_info", "lbm_set_halo_mode", "lbm_read_halo_log", "lbm_run", "lbm_sync", "lbm_run_timed", "lbm_read_av_vels", "lbm_read_cells",
     "lbm_read_final_state", "lbm_av_velocity", "lbm_total_density", "lbm_calc_reynolds",
-    "lbm_set_frames", "lbm_read_frames",
+    "lbm_set_frames", "lbm_read_frames", "lbm_run_until", "lbm_batch_run_until",
     "lbm_create_batch", "lbm_batch_member", "lbm_batch_run", "lbm_batch_sync", "lbm_batch_get_info", "lbm_destroy_batch",
 )
 
@@ -77,6 +77,15 @@ class _CInfo(ctypes.Structure):
 class _CBatchInfo(ctypes.Structure):
     _fields_ = [("members", ctypes.c_int), ("members_per_launch", ctypes.c_int), ("launches_per_chunk", ctypes.c_int),
                 ("resident_steps", ctypes.c_int), ("resident_min_steps", ctypes.c_int), ("steps_done", ctypes.c_int)]
+
+
+class _CSteadyResult(ctypes.Structure):
+    _fields_ = [("steps_run", ctypes.c_int), ("steady", ctypes.c_int), ("steady_step", ctypes.c_int),
+                ("checks", ctypes.c_int), ("last_rel", ctypes.c_double), ("last_mean", ctypes.c_double)]
+
+    def as_dict(self) -> dict:
+        return {"steps_run": self.steps_run, "steady": bool(self.steady), "steady_step": self.steady_step,
+                "checks": self.checks, "last_rel": self.last_rel, "last_mean": self.last_mean}
 
 
 class _CRcclStatus(ctypes.Structure):
@@ -177,6 +186,10 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_calc_reynolds.argtypes = [P, PF]; lib.lbm_calc_reynolds.restype = I
     lib.lbm_set_frames.argtypes = [P, I, I]; lib.lbm_set_frames.restype = I
     lib.lbm_read_frames.argtypes = [P, I, P, P, PI]; lib.lbm_read_frames.restype = I
+    lib.lbm_run_until.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CSteadyResult)]
+    lib.lbm_run_until.restype = I
+    lib.lbm_batch_run_until.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CSteadyResult), PI]
+    lib.lbm_batch_run_until.restype = I
     lib.lbm_create_batch.argtypes = [I, ctypes.POINTER(_CParams), P, P, I]; lib.lbm_create_batch.restype = P
     lib.lbm_batch_member.argtypes = [P, I]; lib.lbm_batch_member.restype = P
     lib.lbm_batch_run.argtypes = [P, I]; lib.lbm_batch_run.restype = I
@@ -411,6 +424,15 @@ class Engine:
     def sync(self) -> None:
         _check(self.lib, self.lib.lbm_sync(self.handle))
 
+    def run_until(self, max_steps: int, check_every: int = 1024, tol: float = 1e-6, patience: int = 2) -> dict:
+        """Advance until the average velocity has stopped changing, or by max_steps (lbm_run_until): segments of
+        check_every steps; steady when the relative change of the segment means stayed <= tol for `patience` checks in
+        a row.  Returns steps_run, steady, steady_step (-1: never), checks, last_rel, last_mean."""
+        args = _steady_args(max_steps, check_every, tol, patience)
+        res = _CSteadyResult()
+        _check(self.lib, self.lib.lbm_run_until(self.handle, *args, ctypes.byref(res)))
+        return res.as_dict()
+
     # -- animation frames (lbm_set_frames / lbm_read_frames) ---------------------------------
     def set_frames(self, every: int, capacity: int = 0) -> None:
         """Record |u| of the owned rows after every global timestep tt with tt % every == 0 (the reference's
@@ -555,6 +577,15 @@ class Batch:
     def sync(self) -> None:
         _check(self.lib, self.lib.lbm_batch_sync(self._live()))
 
+    def run_until(self, max_steps: int, check_every: int = 1024, tol: float = 1e-6, patience: int = 2) -> list[dict]:
+        """Advance every member until all of them are steady, or by max_steps (lbm_batch_run_until).  One dict per
+        member as Engine.run_until's; steps_run is the batch's, steady_step the member's own."""
+        args = _steady_args(max_steps, check_every, tol, patience)
+        res = (_CSteadyResult * len(self))()
+        steps = ctypes.c_int()
+        _check(self.lib, self.lib.lbm_batch_run_until(self._live(), *args, res, ctypes.byref(steps)))
+        return [r.as_dict() for r in res]
+
     def info(self) -> dict:
         bi = _CBatchInfo()
         _check(self.lib, self.lib.lbm_batch_get_info(self._live(), ctypes.byref(bi)))
@@ -590,6 +621,9 @@ class BatchMember(Engine):
 
     def close(self) -> None:
         pass
+
+    def run_until(self, *args, **kwargs):
+        raise LbmError("run_until: this engine is a member of a batch; Batch.run_until advances all its members")
 
 
 # ------------------------------------------------------------------------------------------------
@@ -655,6 +689,20 @@ def _frame_args(every, capacity) -> tuple[int, int]:
     if every > 0 and capacity < 1:
         raise LbmError(f"set_frames: capacity {capacity}, at least one frame slot is needed")
     return int(every), int(capacity)
+
+
+def _steady_args(max_steps, check_every, tol, patience) -> tuple[int, int, float, int]:
+    """run_until's argument checks (no device needed)."""
+    for name, v, lo in (("max_steps", max_steps, 0), ("check_every", check_every, 1), ("patience", patience, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise LbmError(f"run_until: {name} must be an integer (got {v!r})")
+        if not lo <= int(v) <= 2147483647:
+            raise LbmError(f"run_until: {name} must lie in [{lo}, 2^31) (got {v})")
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)):
+        raise LbmError(f"run_until: tol must be a number (got {tol!r})")
+    if not float(tol) >= 0.0:
+        raise LbmError(f"run_until: tol must be a non-negative number (got {tol})")
+    return int(max_steps), int(check_every), float(tol), int(patience)
 
 
 def write_animation_frame(path: str, frame: np.ndarray, tt: int) -> None:

@@ -389,6 +389,10 @@ struct lbm_ctx {
   int frame_ord0 = 0;               // tt / frame_every of the first frame after arming
   long long frames_written = 0;     // frames issued since arming (frame ordinals 0 .. frames_written - 1) ...
   long long frames_read = 0;        // ... and drained by lbm_read_frames
+  // steady-state runs (lbm_run_until), allocated by the first such call
+  lbm::SteadyState* steady_state = nullptr;  // device: what the checks of the current call have found
+  int* steady_stop_host = nullptr;  // pinned: its stop word after segment j, in slot j & 1 ...
+  hipEvent_t ev_steady[2] = {nullptr, nullptr};  // ... behind these events
 };
 
 // B independent single-slab lattices of one shape on one device, advanced together (lbm_create_batch).  The members
@@ -409,6 +413,12 @@ struct lbm_batch {
   int* status_host = nullptr;       // pinned copy behind every run; every member's lbm_sync reports it
   lbm::ResidentFrames* frame_table = nullptr;  // device: [members], allocated when the first member arms frames
   int frames_armed = 0;             // members with frames armed: batched launches run the FRAMES kernel
+  // steady-state runs (lbm_batch_run_until), allocated by the first such call
+  lbm::SteadyState* steady_state = nullptr;    // device: [members]
+  lbm::SteadyMember* steady_members = nullptr; // device: [members]
+  lbm::SteadyBatch* steady_batch = nullptr;    // device
+  int* steady_stop_host = nullptr;  // pinned: all_steady after the last segment ...
+  hipEvent_t ev_steady = nullptr;   // ... behind this event
 };
 
 namespace {
@@ -2619,7 +2629,10 @@ void lbm_destroy(lbm_ctx* c) {
   for (int i = 0; i < 2; i++) {
     if (c->host_send[i]) (void)hipHostFree(c->host_send[i]);
     if (c->host_recv[i]) (void)hipHostFree(c->host_recv[i]);
+    if (c->ev_steady[i]) (void)hipEventDestroy(c->ev_steady[i]);
   }
+  if (c->steady_state) (void)hipFree(c->steady_state);
+  if (c->steady_stop_host) (void)hipHostFree(c->steady_stop_host);
   delete c;
 }
 
@@ -2994,6 +3007,11 @@ void lbm_destroy_batch(lbm_batch* bt) {
   if (bt->frame_table) (void)hipFree(bt->frame_table);
   if (bt->status) (void)hipFree(bt->status);
   if (bt->status_host) (void)hipHostFree(bt->status_host);
+  if (bt->steady_state) (void)hipFree(bt->steady_state);
+  if (bt->steady_members) (void)hipFree(bt->steady_members);
+  if (bt->steady_batch) (void)hipFree(bt->steady_batch);
+  if (bt->steady_stop_host) (void)hipHostFree(bt->steady_stop_host);
+  if (bt->ev_steady) (void)hipEventDestroy(bt->ev_steady);
   delete bt;
 }
 
@@ -3158,6 +3176,175 @@ int lbm_batch_get_info(const lbm_batch* bt, lbm_batch_info* out) {
   out->resident_steps = bt->resident ? kResidentChunk : 0;
   out->resident_min_steps = bt->resident ? c0->resident_min_steps : 0;
   out->steps_done = bt->steps_done;
+  return LBM_SUCCESS;
+}
+
+// ---- steady-state runs ---------------------------------------------------------------------------------------------
+// argument checks shared by lbm_run_until and lbm_batch_run_until (no device needed)
+static int steady_args_ok(const char* who, int steps_done, int capacity, int max_steps, int check_every, double tol, int patience) {
+  if (max_steps < 0) LBM_FAIL(LBM_FAILURE, "%s: negative step count", who);
+  if ((long long)steps_done + max_steps > capacity)
+    LBM_FAIL(LBM_FAILURE, "%s: %lld steps requested but the av_vels record holds %d (maxIters)", who,
+             (long long)steps_done + max_steps, capacity);
+  if (check_every < 1) LBM_FAIL(LBM_FAILURE, "%s: check_every must be at least 1 (got %d)", who, check_every);
+  if (patience < 1) LBM_FAIL(LBM_FAILURE, "%s: patience must be at least 1 (got %d)", who, patience);
+  if (!(tol >= 0.0)) LBM_FAIL(LBM_FAILURE, "%s: tol must be a non-negative number (got %g)", who, tol);
+  return LBM_SUCCESS;
+}
+static const char kSteadyFrames[] = "%s: animation frames are armed (lbm_set_frames); a steady-state run does not record frames";
+
+static void steady_fill(lbm_steady_result* out, const lbm::SteadyState& st, int steps_run) {
+  out->steps_run = steps_run;
+  out->steady = st.stop ? 1 : 0;
+  out->steady_step = st.steady_step;
+  out->checks = st.checks;
+  out->last_rel = st.last_rel;
+  out->last_mean = st.prev_mean;
+}
+
+// One segment of a resident lbm_run_until call: what lbm_run issues for `n` steps (first-step acceleration, the launches
+// of run_resident with accel_last = 0 on the last one), except that the acceleration stands back once the checks have
+// said "stop"; then the check of the segment and its stop word on the way to slot `slot` of the pinned pair.
+static int steady_segment_resident(lbm_ctx* c, int n, int slot, double tol, int patience, int steps_after) {
+  Slab& sl = c->slab[0];
+  HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+  hipLaunchKernelGGL(lbm::accelerate_row_unless, dim3(ceil_div(c->p.nx, 256)), dim3(256), 0, sl.compute, sl.lat[c->cur],
+                     (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx, sl.accel_row,
+                     c->p.density * c->p.accel / 9.f, c->p.density * c->p.accel / 36.f,
+                     (const lbm::SteadyState*)c->steady_state);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  if (run_resident(c, n) != LBM_SUCCESS) return LBM_FAILURE;
+  hipLaunchKernelGGL(lbm::steady_check, dim3(1), dim3(64), 0, sl.compute, (const double*)sl.tot_u, c->steps_done, n,
+                     (float)c->fluid_cells, tol, patience, steps_after, c->steady_state);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  c->steps_done += n;
+  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(c->steady_stop_host + slot, &c->steady_state->stop, sizeof(int), hipMemcpyDeviceToHost, sl.compute));
+  HIP_TRY(LBM_FAILURE, hipEventRecord(c->ev_steady[slot], sl.compute));
+  return LBM_SUCCESS;
+}
+
+int lbm_run_until(lbm_ctx* c, int max_steps, int check_every, double tol, int patience, lbm_steady_result* out) {
+  if (!c || !out) LBM_FAIL(LBM_FAILURE, "lbm_run_until: NULL argument");
+  if (c->batch) LBM_FAIL(LBM_FAILURE, kMemberRun, "lbm_run_until");
+  if (steady_args_ok("lbm_run_until", c->steps_done, c->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS)
+    return LBM_FAILURE;
+  if (c->frame_every > 0) LBM_FAIL(LBM_FAILURE, kSteadyFrames, "lbm_run_until");
+  if (c->halo_mode != LBM_HALO_SYNC)
+    LBM_FAIL(LBM_FAILURE, "lbm_run_until: only LBM_HALO_SYNC runs can be checked (the halo mode is %d)", c->halo_mode);
+  if (c->ranked || c->world > 1)
+    LBM_FAIL(LBM_FAILURE, "lbm_run_until: not available in a multi-process context (every rank would have to take the same decision)");
+  if (c->n_slabs != 1)
+    LBM_FAIL(LBM_FAILURE, "lbm_run_until: the context has %d slabs; the check reads one slab's sums (single-slab contexts only)", c->n_slabs);
+
+  Slab& sl = c->slab[0];
+  HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+  if (!c->steady_state) {
+    HIP_TRY(LBM_FAILURE, hipMalloc(&c->steady_state, sizeof(lbm::SteadyState)));
+    HIP_TRY(LBM_FAILURE, hipHostMalloc(&c->steady_stop_host, 2 * sizeof(int)));
+    for (int i = 0; i < 2; i++) HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&c->ev_steady[i], hipEventDisableTiming));
+  }
+  hipLaunchKernelGGL(lbm::steady_reset, dim3(1), dim3(64), 0, sl.compute, c->steady_state, 1, (lbm::SteadyBatch*)nullptr);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+
+  const int E = check_every, n_seg = max_steps / E, start = c->steps_done;
+  const bool resident = c->resident && E >= c->resident_min_steps;
+  // One segment of look-ahead where a segment is ONE launch of the resident kernel: it reads the lattice the segment in
+  // front left and writes the other one, so dropping it is `cur ^= 1`.  A longer segment (several launches, which would
+  // write both lattices) runs for milliseconds; there the host waits for each verdict first, as on the per-pass path.
+  const int depth = (resident && E <= kResidentChunk) ? 2 : 1;
+  int issued = 0, judged = 0;
+  bool steady = false;
+  while (judged < n_seg && !steady) {
+    while (issued < n_seg && issued - judged < depth) {
+      const int after = (issued + 1) * E;
+      if (resident) {
+        if (steady_segment_resident(c, E, issued & 1, tol, patience, after) != LBM_SUCCESS) return LBM_FAILURE;
+      } else {
+        const int first = c->steps_done;
+        if (run_passes(c, E, false, false) != LBM_SUCCESS) return LBM_FAILURE;
+        HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+        hipLaunchKernelGGL(lbm::steady_check, dim3(1), dim3(64), 0, sl.compute, (const double*)sl.tot_u, first, E,
+                           (float)c->fluid_cells, tol, patience, after, c->steady_state);
+        HIP_TRY(LBM_FAILURE, hipGetLastError());
+        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(c->steady_stop_host + (issued & 1), &c->steady_state->stop, sizeof(int),
+                                            hipMemcpyDeviceToHost, sl.compute));
+        HIP_TRY(LBM_FAILURE, hipEventRecord(c->ev_steady[issued & 1], sl.compute));
+      }
+      issued++;
+    }
+    HIP_TRY(LBM_FAILURE, hipEventSynchronize(c->ev_steady[judged & 1]));
+    steady = c->steady_stop_host[judged & 1] != 0;
+    judged++;
+    if (resident && *sl.res_status_host != 0) break;  // a launch gave up (its status travels in front of the stop word): lbm_sync below reports it
+  }
+  if (issued > judged) {
+    // The look-ahead segment is dropped: its acceleration did not happen (accelerate_row_unless), its one launch wrote
+    // the other lattice, its check changed nothing, and its tot_u entries lie beyond steps_done.  Its seam granules
+    // carry the tags of steps that will be run again, so they are cleared as at creation.
+    c->cur ^= 1;
+    c->steps_done -= E;
+    HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.res_gran, 0, resident_gran_bytes(c), sl.compute));
+  }
+  if (!steady && max_steps - n_seg * E > 0) {
+    // the rest of the cap, shorter than a segment: run as lbm_run runs it, not checked
+    const int rest = max_steps - n_seg * E;
+    if (run_passes(c, rest, c->resident && rest >= c->resident_min_steps, false) != LBM_SUCCESS) return LBM_FAILURE;
+  }
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;  // also reports a resident give-up
+  lbm::SteadyState st;
+  HIP_TRY(LBM_FAILURE, hipMemcpy(&st, c->steady_state, sizeof(st), hipMemcpyDeviceToHost));
+  steady_fill(out, st, c->steps_done - start);
+  return LBM_SUCCESS;
+}
+
+int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double tol, int patience, lbm_steady_result* out,
+                        int* steps_run) {
+  if (!bt || !out || !steps_run) LBM_FAIL(LBM_FAILURE, "lbm_batch_run_until: NULL argument");
+  lbm_ctx* c0 = bt->members[0];
+  const int n_members = (int)bt->members.size();
+  if (steady_args_ok("lbm_batch_run_until", bt->steps_done, c0->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS)
+    return LBM_FAILURE;
+  for (const lbm_ctx* c : bt->members)
+    if (c->frame_every > 0) LBM_FAIL(LBM_FAILURE, kSteadyFrames, "lbm_batch_run_until");
+
+  HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
+  if (!bt->steady_state) {
+    std::vector<lbm::SteadyMember> h((size_t)n_members);
+    for (int i = 0; i < n_members; i++) h[(size_t)i] = {bt->members[(size_t)i]->slab[0].tot_u, (float)bt->members[(size_t)i]->fluid_cells};
+    HIP_TRY(LBM_FAILURE, hipMalloc(&bt->steady_members, h.size() * sizeof(h[0])));
+    HIP_TRY(LBM_FAILURE, hipMemcpy(bt->steady_members, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice));
+    HIP_TRY(LBM_FAILURE, hipMalloc(&bt->steady_batch, sizeof(lbm::SteadyBatch)));
+    HIP_TRY(LBM_FAILURE, hipHostMalloc(&bt->steady_stop_host, sizeof(int)));
+    HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&bt->ev_steady, hipEventDisableTiming));
+    HIP_TRY(LBM_FAILURE, hipMalloc(&bt->steady_state, (size_t)n_members * sizeof(lbm::SteadyState)));
+  }
+  hipLaunchKernelGGL(lbm::steady_reset, dim3(ceil_div(n_members, 64)), dim3(64), 0, bt->stream, bt->steady_state, n_members,
+                     bt->steady_batch);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+
+  // the launches of lbm_batch_run per segment, then one check of every member; the host waits for each verdict (a
+  // dropped segment of B lattices would cost more than the wait).  Steady members keep stepping with the others.
+  const int E = check_every, n_seg = max_steps / E, start = bt->steps_done;
+  bool steady = false;
+  for (int j = 0; j < n_seg && !steady; j++) {
+    const int first = bt->steps_done;
+    if (lbm_batch_run(bt, E) != LBM_SUCCESS) return LBM_FAILURE;
+    HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
+    hipLaunchKernelGGL(lbm::steady_check_batch, dim3(n_members), dim3(64), 0, bt->stream,
+                       (const lbm::SteadyMember*)bt->steady_members, n_members, first, E, tol, patience, (j + 1) * E,
+                       bt->steady_state, bt->steady_batch);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    HIP_TRY(LBM_FAILURE, hipMemcpyAsync(bt->steady_stop_host, &bt->steady_batch->all_steady, sizeof(int), hipMemcpyDeviceToHost, bt->stream));
+    HIP_TRY(LBM_FAILURE, hipEventRecord(bt->ev_steady, bt->stream));
+    HIP_TRY(LBM_FAILURE, hipEventSynchronize(bt->ev_steady));
+    steady = *bt->steady_stop_host != 0;
+  }
+  if (!steady && max_steps - n_seg * E > 0 && lbm_batch_run(bt, max_steps - n_seg * E) != LBM_SUCCESS) return LBM_FAILURE;
+  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
+  std::vector<lbm::SteadyState> st((size_t)n_members);
+  HIP_TRY(LBM_FAILURE, hipMemcpy(st.data(), bt->steady_state, st.size() * sizeof(st[0]), hipMemcpyDeviceToHost));
+  *steps_run = bt->steps_done - start;
+  for (int i = 0; i < n_members; i++) steady_fill(&out[i], st[(size_t)i], *steps_run);
   return LBM_SUCCESS;
 }
 

@@ -2105,6 +2105,88 @@ __global__ void accelerate_row_batch(const ResidentMember* members, long ps, lon
 }
 
 // ---------------------------------------------------------------------------------------------
+// steady-state runs (lbm_run_until): the convergence verdict is taken on the device, next to tot_u
+// ---------------------------------------------------------------------------------------------
+// what one lattice's checks have found so far; lives on the device, reset at the start of every lbm_run_until call
+struct SteadyState {
+  double prev_mean;   // m_j of the last segment seen
+  double last_rel;    // r_j of the last check (+inf before the first)
+  int streak;         // consecutive checks met
+  int checks;         // checks made (segments 2, 3, ...)
+  int segments;       // segments seen
+  int stop;           // 1 once streak == patience: later checks change nothing, accelerate_row_unless does nothing
+  int steady_step;    // steps of the call after which that happened (-1: not yet)
+  int pad;
+};
+struct SteadyMember {  // one lattice of a batch, as steady_check_batch sees it
+  const double* tot_u;
+  float cells;         // (float)fluid_cells
+};
+struct SteadyBatch {
+  int n_steady;        // members whose stop is set
+  int all_steady;      // 1 once that is all of them
+};
+
+__global__ void steady_reset(SteadyState* st, int n, SteadyBatch* batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) st[i] = SteadyState{0.0, __builtin_inf(), 0, 0, 0, 0, -1, 0};
+  if (i == 0 && batch) *batch = SteadyBatch{0, 0};
+}
+
+// One wave: the mean of the segment's av_vels -- av[s] = (float)tot_u[s] / cells as lbm_read_av_vels computes it, summed
+// as doubles in the order of reduce_band_partials_at -- against the mean of the segment before.  Returns true (lane 0)
+// when this check made the lattice steady.
+__device__ __forceinline__ bool steady_check_at(const double* tot_u, int n, float cells, double tol, int patience,
+                                                int steps_after, SteadyState* st) {
+  if (st->stop) return false;  // uniform: the verdict stands, a look-ahead segment's check changes nothing
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 64) acc += (double)((float)tot_u[i] / cells);
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if (threadIdx.x != 0) return false;
+  const double m = acc / (double)n;
+  const int seg = st->segments + 1;
+  bool now_steady = false;
+  if (seg >= 2) {
+    const double prev = st->prev_mean;
+    const double r = (m == 0.0) ? (prev == 0.0 ? 0.0 : __builtin_inf()) : fabs(m - prev) / fabs(m);
+    const int streak = (r <= tol) ? st->streak + 1 : 0;
+    st->streak = streak;
+    st->checks += 1;
+    st->last_rel = r;
+    if (streak >= patience) {
+      st->stop = 1;
+      st->steady_step = steps_after;
+      now_steady = true;
+    }
+  }
+  st->segments = seg;
+  st->prev_mean = m;
+  return now_steady;
+}
+__global__ __launch_bounds__(64) void steady_check(const double* tot_u, int first, int n, float cells, double tol,
+                                                   int patience, int steps_after, SteadyState* st) {
+  steady_check_at(tot_u + first, n, cells, tol, patience, steps_after, st);
+}
+// every member of a batch at once, one wave per member: grid (members).  The member that completes the set raises
+// all_steady (an integer count: the outcome does not depend on the order the waves run in).
+__global__ __launch_bounds__(64) void steady_check_batch(const SteadyMember* members, int n_members, int first, int n,
+                                                         double tol, int patience, int steps_after, SteadyState* st,
+                                                         SteadyBatch* batch) {
+  const SteadyMember m = members[blockIdx.x];
+  if (steady_check_at(m.tot_u + first, n, m.cells, tol, patience, steps_after, st + blockIdx.x)) {
+    const int before = __hip_atomic_fetch_add(&batch->n_steady, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (before + 1 == n_members) __hip_atomic_store(&batch->all_steady, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// accelerate_row for the first step of a segment that was enqueued before the verdict of the segment in front of it was
+// known: nothing happens once that verdict is "stop", so the lattice the call returns is not accelerated a second time
+__global__ void accelerate_row_unless(float* lat, const unsigned char* mask, long ps, long row_pitch,
+                                      int pitch, int nx, int row, float a1, float a2, const SteadyState* st) {
+  if (st->stop) return;  // one scalar load, wave-uniform
+  accelerate_row_at(lat, mask, ps, row_pitch, pitch, nx, row, a1, a2);
+}
+
+// ---------------------------------------------------------------------------------------------
 // "freshest available" halo mode (LBM_HALO_FRESHEST): the reference's MPI_Testall idea, MPI_Testall_OptimizedVersion/
 // d2q9-bgk.c:279-290 -- look once whether this step's halo rows have arrived, never wait for them.  The rows travel
 // into a staging row per side, followed in stream order by the id of the step they belong to (fresh_mark / a 4-byte

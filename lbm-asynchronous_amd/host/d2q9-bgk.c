@@ -19,6 +19,11 @@
  *                         :802-849), created if missing; unset or 0: off.  The frames are recorded on the device
  *                         (lbm_set_frames); the loop runs in segments whose frames fit 1 GiB and is drained after each.
  *                         final_state.dat and av_vels.dat are unchanged.
+ *   LBM_STEADY=<tol>[:<check_every>[:<patience>]]
+ *                         run to the steady state instead of for maxIters steps (lbm_run_until; check_every defaults to
+ *                         1024, patience to 2): maxIters is the cap, av_vels.dat holds the steps that were run, and one
+ *                         line "Steady after N steps (rel. change X)" / "Not steady after N steps (rel. change X)" is
+ *                         printed before the ==done== block.  Not together with LBM_ANIMATION.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -35,6 +40,25 @@ static double wall_seconds(void)
   return t.tv_sec + (t.tv_usec / 1000000.0);
 }
 
+/* LBM_STEADY=<tol>[:<check_every>[:<patience>]]; dies on anything else, as lbm_read_params does on a bad file */
+static void parse_steady(const char* text, double* tol, int* check_every, int* patience)
+{
+  char* end = NULL;
+  *tol = strtod(text, &end);
+  int ok = (end != text) && *tol >= 0.0;
+  long v[2] = {1024, 2};
+  for (int i = 0; ok && i < 2 && *end == ':'; i++) {
+    const char* from = end + 1;
+    v[i] = strtol(from, &end, 10);
+    ok = (end != from) && v[i] >= 1 && v[i] <= 2147483647L;
+  }
+  if (!ok || *end != '\0')
+    lbm_die("could not read LBM_STEADY: expected <tol>[:<check_every>[:<patience>]] with tol >= 0, check_every >= 1, patience >= 1",
+            __LINE__, __FILE__);
+  *check_every = (int)v[0];
+  *patience = (int)v[1];
+}
+
 int main(int argc, char* argv[])
 {
   if (argc != 3) lbm_usage(argv[0]);
@@ -48,6 +72,12 @@ int main(int argc, char* argv[])
   if ((env = getenv("LBM_MATH")) && !strcmp(env, "fast")) math_mode = LBM_MATH_FAST;
   int write_text = 1;
   if ((env = getenv("LBM_OUTPUT")) && !strcmp(env, "none")) write_text = 0;
+
+  const char* steady_env = getenv("LBM_STEADY");
+  const int until = steady_env && *steady_env;
+  double steady_tol = 0.0;
+  int steady_every = 0, steady_patience = 0;
+  if (until) parse_steady(steady_env, &steady_tol, &steady_every, &steady_patience);
 
   /* Total/init time starts here (SerialCode/d2q9-bgk.c:156-159) */
   const double tot_tic = wall_seconds();
@@ -93,8 +123,18 @@ int main(int argc, char* argv[])
   int anim_every = 0;
   if ((env = getenv("LBM_ANIMATION")) && *env) anim_every = atoi(env);
 
+  if (until && anim_every > 0) lbm_die("LBM_STEADY and LBM_ANIMATION cannot be combined", __LINE__, __FILE__);
+  int steps_run = params.max_iters;
+  lbm_steady_result steady;
+  memset(&steady, 0, sizeof(steady));
+
   /* Compute time: the whole timestep loop (:166-170) */
-  if (anim_every > 0) {
+  if (until) {
+    /* maxIters is the cap: the loop ends when the average velocity has stopped changing */
+    if (lbm_run_until(ctx, params.max_iters, steady_every, steady_tol, steady_patience, &steady) != LBM_SUCCESS)
+      lbm_die(lbm_last_error(), __LINE__, __FILE__);
+    steps_run = steady.steps_run;
+  } else if (anim_every > 0) {
     /* with frames: segments whose frames fit 1 GiB of device memory, each drained and written after it */
     const size_t frame_cells = (size_t)params.nx * (size_t)params.ny;
     long cap = (long)((1UL << 30) / (frame_cells * sizeof(float)));
@@ -133,7 +173,7 @@ int main(int argc, char* argv[])
   const size_t n_cells = (size_t)params.nx * (size_t)params.ny;
   float* av_vels = (float*)malloc(sizeof(float) * (size_t)(params.max_iters > 0 ? params.max_iters : 1));
   if (av_vels == NULL) lbm_die("cannot allocate memory for av_vels", __LINE__, __FILE__);
-  lbm_read_av_vels(ctx, av_vels, params.max_iters);
+  lbm_read_av_vels(ctx, av_vels, steps_run);
   float reynolds = 0.f;
   lbm_calc_reynolds(ctx, &reynolds);
   float* fields = NULL;
@@ -145,6 +185,8 @@ int main(int argc, char* argv[])
   }
   const double col_toc = wall_seconds();
 
+  if (until)
+    printf("%s after %d steps (rel. change %.6E)\n", steady.steady ? "Steady" : "Not steady", steady.steps_run, steady.last_rel);
   /* the reference's report (:195-200) */
   printf("==done==\n");
   printf("Reynolds number:\t\t%.12E\n", reynolds);
@@ -162,7 +204,7 @@ int main(int argc, char* argv[])
                                fields + 3 * n_cells, obstacles);
     fclose(fp);
   }
-  lbm_write_av_vels(LBM_AVVELSFILE, av_vels, params.max_iters);
+  lbm_write_av_vels(LBM_AVVELSFILE, av_vels, steps_run);
   if ((env = getenv("LBM_PRESSURE_BIN")) && *env) {
     FILE* fp = fopen(env, "wb");
     if (fp == NULL) lbm_die("could not open file output file", __LINE__, __FILE__);
