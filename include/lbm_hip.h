@@ -341,6 +341,34 @@ int   lbm_calc_reynolds(lbm_ctx* ctx, float* out);
 int lbm_set_frames(lbm_ctx* ctx, int every, int capacity);
 int lbm_read_frames(lbm_ctx* ctx, int max_frames, float* out, int* steps, int* n_read);
 
+/* ---- point probes ---------------------------------------------------------------------------
+ * The time series of the flow at chosen cells, recorded by the running kernels.  The reference can only print
+ * av_vels per step (SerialCode/d2q9-bgk.c:169) and the whole field at the end (write_values, :662-743); a series at a
+ * point costs it a write_values per step.
+ * lbm_set_probes(ctx, n_probes, cells, every, capacity): from now on, after global timestep tt (0-based, counted from the
+ *   context's creation, the numbering of lbm_set_frames) with tt % every == 0, record one sample row: for probe i the four
+ *   values lbm_read_final_state gives at cells[i] (a GLOBAL cell) for the lattice after tt+1 timesteps, bit for bit; a
+ *   blocked cell gives 0, 0, 0, density * c_sq.  every == 1 is the per-step series.  Duplicate cells are recorded twice;
+ *   the order of a row is the caller's.  Recording never changes the lattice or av_vels.  Rows wait in a device ring of
+ *   `capacity` rows (capacity * n_probes * 16 bytes); an lbm_run / lbm_batch_run call that would record more rows than are
+ *   free fails before issuing any work.  n_probes == 0 or every == 0 disarms and frees; re-arming discards unread rows.
+ *   Calls that run the resident kernel record inside it; other calls run as the sub-calls that end at their sample steps
+ *   (every == 1: one-step passes -- correct, not fast; every a multiple of 4 keeps full-depth passes).
+ *   Works on lbm_create / lbm_create_tiled contexts of any number of slabs and on batch members (each its own probes).
+ *   Refused: n_probes outside [0, LBM_MAX_PROBES], a cell outside the grid, negative every, capacity < 1, a ring of
+ *   2 GiB or more, rank contexts (lbm_create_rank*), LBM_HALO_STALE / LBM_HALO_FRESHEST (and lbm_set_halo_mode to those
+ *   while armed), a context whose frames are armed (and lbm_set_frames while probes are armed: one recorder per
+ *   context; in a batch one KIND of recorder per batch), lbm_run_until / lbm_batch_run_until while armed.
+ * lbm_read_probes: drains up to max_samples oldest rows into out[n][n_probes] and steps[n] (their tt, may be NULL);
+ *   out == NULL && steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers (so a
+ *   resident give-up is reported here too).
+ */
+#define LBM_MAX_PROBES 256
+typedef struct { int x, y; } lbm_probe;                               /* a GLOBAL cell, 0 <= x < nx, 0 <= y < ny */
+typedef struct { float u_x, u_y, u_mag, pressure; } lbm_probe_sample; /* 16 bytes */
+int lbm_set_probes(lbm_ctx* ctx, int n_probes, const lbm_probe* cells, int every, int capacity);
+int lbm_read_probes(lbm_ctx* ctx, int max_samples, lbm_probe_sample* out /* [n][n_probes] */, int* steps, int* n_read);
+
 /* ---- steady-state runs ----------------------------------------------------------------------
  * The reference runs a fixed number of timesteps (maxIters, SerialCode/d2q9-bgk.c:166); none of its data sets has
  * stopped changing by then.  lbm_run_until advances the lattice until its average velocity has, with the decision taken

@@ -47,7 +47,7 @@ ABI_SYMBOLS = (
     "lbm_create_rank_hosted_tiled", "lbm_destroy",
     "lbm_get_info", "lbm_set_halo_mode", "lbm_read_halo_log", "lbm_run", "lbm_sync", "lbm_run_timed", "lbm_read_av_vels", "lbm_read_cells",
     "lbm_read_final_state", "lbm_av_velocity", "lbm_total_density", "lbm_calc_reynolds",
-    "lbm_set_frames", "lbm_read_frames", "lbm_run_until", "lbm_batch_run_until",
+    "lbm_set_frames", "lbm_read_frames", "lbm_set_probes", "lbm_read_probes", "lbm_run_until", "lbm_batch_run_until",
     "lbm_create_batch", "lbm_batch_member", "lbm_batch_run", "lbm_batch_sync", "lbm_batch_get_info", "lbm_destroy_batch",
 )
 
@@ -186,6 +186,8 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_calc_reynolds.argtypes = [P, PF]; lib.lbm_calc_reynolds.restype = I
     lib.lbm_set_frames.argtypes = [P, I, I]; lib.lbm_set_frames.restype = I
     lib.lbm_read_frames.argtypes = [P, I, P, P, PI]; lib.lbm_read_frames.restype = I
+    lib.lbm_set_probes.argtypes = [P, I, P, I, I]; lib.lbm_set_probes.restype = I
+    lib.lbm_read_probes.argtypes = [P, I, P, P, PI]; lib.lbm_read_probes.restype = I
     lib.lbm_run_until.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CSteadyResult)]
     lib.lbm_run_until.restype = I
     lib.lbm_batch_run_until.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CSteadyResult), PI]
@@ -457,6 +459,32 @@ class Engine:
                                                   steps.ctypes.data, ctypes.byref(n)))
         return steps[:n.value].copy(), frames[:n.value].copy()
 
+    # -- point probes (lbm_set_probes / lbm_read_probes) ---------------------------------------
+    def set_probes(self, cells, every: int = 1, capacity: int = 4096) -> None:
+        """Record u_x, u_y, |u| and pressure at `cells` -- a sequence of global (x, y), at most LBM_MAX_PROBES -- after
+        every global timestep tt with tt % every == 0, bit for bit what final_state() gives there after tt + 1 steps,
+        into a device ring of `capacity` sample rows.  No cells or every == 0 disarms; re-arming discards unread rows."""
+        flat, every, capacity = _probe_args(cells, every, capacity)
+        arr = (_CProbe * max(1, len(flat)))(*[_CProbe(x, y) for x, y in flat])
+        _check(self.lib, self.lib.lbm_set_probes(self.handle, len(flat), arr, every, capacity))
+        self._n_probes = len(flat) if every > 0 else 0
+
+    def probes(self, max_samples: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_samples (default: all) waiting sample rows, oldest first:
+        (steps int32[n], samples float32[n, n_probes, 4]), columns u_x, u_y, u, pressure."""
+        if max_samples is not None and (isinstance(max_samples, bool) or not isinstance(max_samples, (int, np.integer))
+                                        or max_samples < 0):
+            raise LbmError(f"probes: max_samples must be a non-negative integer or None (got {max_samples!r})")
+        n = ctypes.c_int()
+        _check(self.lib, self.lib.lbm_read_probes(self.handle, 0, None, None, ctypes.byref(n)))  # rows waiting
+        max_samples = n.value if max_samples is None else min(int(max_samples), n.value)
+        n_probes = getattr(self, "_n_probes", 0)
+        samples = np.empty((int(max_samples), n_probes, 4), dtype=np.float32)
+        steps = np.empty(int(max_samples), dtype=np.int32)
+        _check(self.lib, self.lib.lbm_read_probes(self.handle, int(max_samples), samples.ctypes.data,
+                                                  steps.ctypes.data, ctypes.byref(n)))
+        return steps[:n.value].copy(), samples[:n.value].copy()
+
     # -- results -----------------------------------------------------------------------------
     def av_vels(self, n: int | None = None) -> np.ndarray:
         n = self.info()["steps_done"] if n is None else n
@@ -689,6 +717,60 @@ def _frame_args(every, capacity) -> tuple[int, int]:
     if every > 0 and capacity < 1:
         raise LbmError(f"set_frames: capacity {capacity}, at least one frame slot is needed")
     return int(every), int(capacity)
+
+
+LBM_MAX_PROBES = 256
+
+
+class _CProbe(ctypes.Structure):
+    _fields_ = [("x", ctypes.c_int), ("y", ctypes.c_int)]
+
+
+class _CProbeSample(ctypes.Structure):
+    _fields_ = [("u_x", ctypes.c_float), ("u_y", ctypes.c_float), ("u_mag", ctypes.c_float), ("pressure", ctypes.c_float)]
+
+
+def _probe_args(cells, every, capacity) -> tuple[list, int, int]:
+    """Engine.set_probes' argument checks (no device needed): ([(x, y), ...], every, capacity)."""
+    for name, v in (("every", every), ("capacity", capacity)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise LbmError(f"set_probes: {name} must be an integer (got {v!r})")
+        if not 0 <= int(v) <= 2147483647:
+            raise LbmError(f"set_probes: {name} must lie in [0, 2^31) (got {v})")
+    try:
+        items = list(cells)
+    except TypeError:
+        raise LbmError(f"set_probes: cells must be a sequence of (x, y) pairs (got {cells!r})") from None
+    if len(items) > LBM_MAX_PROBES:
+        raise LbmError(f"set_probes: {len(items)} probes, at most LBM_MAX_PROBES = {LBM_MAX_PROBES} are possible")
+    flat = []
+    for i, cell in enumerate(items):
+        try:
+            pair = tuple(cell)
+        except TypeError:
+            pair = ()
+        if len(pair) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in pair):
+            raise LbmError(f"set_probes: cell {i} must be a pair of integers (x, y) (got {cell!r})")
+        if not all(-2147483648 <= int(v) <= 2147483647 for v in pair):
+            raise LbmError(f"set_probes: cell {i} must be a pair of integers (x, y) (got {cell!r})")
+        flat.append((int(pair[0]), int(pair[1])))
+    if flat and every > 0 and capacity < 1:
+        raise LbmError(f"set_probes: capacity {capacity}, at least one row of samples is needed")
+    return flat, int(every), int(capacity)
+
+
+def write_probes(path: str, cells, steps, samples) -> None:
+    """probes.dat of the command line: '%d %d %d %.12E %.12E %.12E %.12E\n' = tt x y u_x u_y u pressure, one line per
+    sample and probe, sample-major; `steps` int[n], `samples` float32 [n, n_probes, 4] (Engine.probes)."""
+    cells = [(int(x), int(y)) for x, y in cells]
+    samples = np.asarray(samples, dtype=np.float32)
+    steps = np.asarray(steps).ravel()
+    if samples.ndim != 3 or samples.shape[1:] != (len(cells), 4) or samples.shape[0] != steps.size:
+        raise LbmError(f"write_probes: samples must be [{steps.size}, {len(cells)}, 4] (got shape {samples.shape})")
+    with open(path, "w") as fh:
+        for tt, row in zip(steps.tolist(), samples):
+            fh.write("".join("%d %d %d %.12E %.12E %.12E %.12E\n" % (tt, x, y, *map(float, v))
+                             for (x, y), v in zip(cells, row)))
 
 
 def _steady_args(max_steps, check_every, tol, patience) -> tuple[int, int, float, int]:

@@ -174,6 +174,9 @@ struct Slab {
   int* res_status = nullptr;               // resident kernel: 0, or the reason a workgroup gave up
   int* res_status_host = nullptr;          // pinned copy of it, refreshed behind every launch (read by lbm_sync)
   float* frames = nullptr;                 // lbm_set_frames: [frame slots][rows][nx] |u| of the owned rows
+  lbm::probe_vec* probe_ring = nullptr;    // lbm_set_probes: [rows of samples][probes]; a slab writes the probes in its rows
+  lbm::ProbeEntry* probe_table = nullptr;  // ... those, sorted by row (+ one word per band where the resident kernel runs)
+  int probe_count = 0;                     // ... and how many they are
   hipGraphExec_t chunk_graph[2] = {nullptr, nullptr};  // kPartSlots timesteps + their reduce, by lattice parity
   hipStream_t compute = nullptr, comm = nullptr;
   hipEvent_t ev_boundary = nullptr, ev_halo = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
@@ -389,6 +392,14 @@ struct lbm_ctx {
   int frame_ord0 = 0;               // tt / frame_every of the first frame after arming
   long long frames_written = 0;     // frames issued since arming (frame ordinals 0 .. frames_written - 1) ...
   long long frames_read = 0;        // ... and drained by lbm_read_frames
+  // point probes (lbm_set_probes): the same bookkeeping for sample rows of probe_cells.size() samples; one recorder per
+  // context, so at most one of frame_every and probe_every is non-zero
+  std::vector<lbm_probe> probe_cells;  // global cells, in the caller's order
+  int probe_every = 0;              // 0: not armed
+  int probe_slots = 0;
+  int probe_ord0 = 0;
+  long long probes_written = 0;
+  long long probes_read = 0;
   // steady-state runs (lbm_run_until), allocated by the first such call
   lbm::SteadyState* steady_state = nullptr;  // device: what the checks of the current call have found
   int* steady_stop_host = nullptr;  // pinned: its stop word after segment j, in slot j & 1 ...
@@ -413,6 +424,8 @@ struct lbm_batch {
   int* status_host = nullptr;       // pinned copy behind every run; every member's lbm_sync reports it
   lbm::ResidentFrames* frame_table = nullptr;  // device: [members], allocated when the first member arms frames
   int frames_armed = 0;             // members with frames armed: batched launches run the FRAMES kernel
+  lbm::ResidentProbes* probe_table = nullptr;  // device: [members], allocated when the first member arms probes
+  int probes_armed = 0;             // members with probes armed: batched launches run the PROBES kernel (never both kinds)
   // steady-state runs (lbm_batch_run_until), allocated by the first such call
   lbm::SteadyState* steady_state = nullptr;    // device: [members]
   lbm::SteadyMember* steady_members = nullptr; // device: [members]
@@ -1248,8 +1261,17 @@ size_t resident_gran_bytes(const lbm_ctx* c) {
   return (2UL * c->resident_bands * 2 * c->p.nx + c->resident_bands) * sizeof(uint4);
 }
 
-const void* resident_kernel(int nx, int rows, int joint, bool frames) {
-  if (frames) {
+// rec: the recorder compiled in -- kRecNone, kRecFrames (lbm_set_frames) or kRecProbes (lbm_set_probes)
+enum { kRecNone = 0, kRecFrames = 1, kRecProbes = 2 };
+const void* resident_kernel(int nx, int rows, int joint, int rec) {
+  if (rec == kRecProbes) {
+    if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, false, false, true>)
+                                     : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, false, false, true>);
+    if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, false, false, true>);
+    return joint ? reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, false, false, true>)
+                 : reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, false, false, true>);
+  }
+  if (rec == kRecFrames) {
     if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, false, true>)
                                      : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, false, true>);
     if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, false, true>);
@@ -1271,8 +1293,11 @@ int run_resident(lbm_ctx* c, int n_steps) {
   for (int t = 0; t < n_steps;) {
     const int n = (n_steps - t < kResidentChunk) ? n_steps - t : kResidentChunk;
     lbm::ResidentFramesArgs fa;  // the FRAMES form's arguments: ResidentArgs + the frame fields
-    lbm::ResidentArgs& a = fa;
+    lbm::ResidentProbesArgs pa;  // the PROBES form's: ResidentArgs + the probe fields
+    const int rec = c->probe_every > 0 ? kRecProbes : (c->frame_every > 0 ? kRecFrames : kRecNone);
+    lbm::ResidentArgs& a = (rec == kRecProbes) ? static_cast<lbm::ResidentArgs&>(pa) : fa;
     fa.fr = {sl.frames, c->frame_every, c->frame_ord0, c->frame_slots};
+    pa.pr = {sl.probe_ring, sl.probe_table, c->probe_every, c->probe_ord0, c->probe_slots, sl.probe_count, c->p.density, 0};
     a.src = sl.lat[c->cur];
     a.dst = sl.lat[c->cur ^ 1];
     a.mask = sl.mask;
@@ -1302,8 +1327,8 @@ int run_resident(lbm_ctx* c, int n_steps) {
 #endif
     a.group = c->resident_group;
     a.one_xcd = c->resident_one_xcd;
-    void* args[] = {&fa};
-    HIP_TRY(LBM_FAILURE, hipLaunchKernel(resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, c->frame_every > 0),
+    void* args[] = {(rec == kRecProbes) ? static_cast<void*>(&pa) : static_cast<void*>(&fa)};
+    HIP_TRY(LBM_FAILURE, hipLaunchKernel(resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, rec),
                                          dim3(c->resident_bands / a.group * (a.one_xcd ? 8 : 1)), dim3(c->p.nx * a.group), args, 0, sl.compute));
     hipLaunchKernelGGL(lbm::reduce_band_partials, dim3(n), dim3(64), 0, sl.compute, (const float*)sl.res_part,
                        c->resident_bands, sl.tot_u, c->steps_done + t);
@@ -1341,8 +1366,15 @@ int run_resident(lbm_ctx* c, int n_steps) {
   return LBM_SUCCESS;
 }
 
-const void* resident_kernel_batch(int nx, int rows, int joint, bool frames) {
-  if (frames) {
+const void* resident_kernel_batch(int nx, int rows, int joint, int rec) {
+  if (rec == kRecProbes) {
+    if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, true, false, true>)
+                                     : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, true, false, true>);
+    if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, true, false, true>);
+    return joint ? reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, true, false, true>)
+                 : reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, true, false, true>);
+  }
+  if (rec == kRecFrames) {
     if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, true, true>)
                                      : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, true, true>);
     if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, true, true>);
@@ -1367,14 +1399,17 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
                      (const lbm::ResidentMember*)(bt->table + bt->cur * n_members), c0->plane_stride, c0->row_pitch,
                      c0->pitch, c0->p.nx, sl0.accel_row);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
-  const void* kernel = resident_kernel_batch(c0->p.nx, c0->resident_rows, c0->resident_joint, bt->frames_armed > 0);
+  const int rec = bt->probes_armed > 0 ? kRecProbes : (bt->frames_armed > 0 ? kRecFrames : kRecNone);
+  const void* kernel = resident_kernel_batch(c0->p.nx, c0->resident_rows, c0->resident_joint, rec);
   const int bands = c0->resident_bands;
   for (int t = 0; t < n_steps;) {
     const int n = (n_steps - t < kResidentChunk) ? n_steps - t : kResidentChunk;
     const lbm::ResidentMember* tab = bt->table + bt->cur * n_members;
     lbm::ResidentBatchFramesArgs fa;  // the FRAMES form's arguments: ResidentBatchArgs + the members' frame fields
+    lbm::ResidentBatchProbesArgs pa;  // the PROBES form's: ResidentBatchArgs + the members' probe fields
     memset(&fa, 0, sizeof(fa));
-    lbm::ResidentBatchArgs& a = fa;
+    memset(&pa, 0, sizeof(pa));
+    lbm::ResidentBatchArgs& a = (rec == kRecProbes) ? static_cast<lbm::ResidentBatchArgs&>(pa) : fa;
     a.plane_stride = c0->plane_stride;
     a.row_pitch = c0->row_pitch;
     a.pitch = c0->pitch;
@@ -1395,9 +1430,10 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
     for (int first = 0; first < n_members; first += bt->members_per_launch) {
       a.members = tab + first;
       fa.frames = bt->frame_table ? bt->frame_table + first : nullptr;
+      pa.probes = bt->probe_table ? bt->probe_table + first : nullptr;
       a.n_members = (n_members - first < bt->members_per_launch) ? n_members - first : bt->members_per_launch;
       const int grid = a.one_xcd ? bt->member_wgs * 8 : a.n_members * (int)round_up(bt->member_wgs, 8);
-      void* args[] = {&fa};
+      void* args[] = {(rec == kRecProbes) ? static_cast<void*>(&pa) : static_cast<void*>(&fa)};
       HIP_TRY(LBM_FAILURE, hipLaunchKernel(kernel, dim3(grid), dim3(c0->p.nx * a.group), args, 0, bt->stream));
     }
     hipLaunchKernelGGL(lbm::reduce_band_partials_batch, dim3(n, n_members), dim3(64), 0, bt->stream, tab, bands,
@@ -1415,11 +1451,14 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
 }
 
 // frames recorded by the global steps [from, to): those with tt % frame_every == 0
-long long frames_between(const lbm_ctx* c, long long from, long long to) {
-  if (c->frame_every <= 0) return 0;
-  const long long e = c->frame_every;
+long long recorded_between(int every, long long from, long long to) {
+  if (every <= 0) return 0;
+  const long long e = every;
   return (to + e - 1) / e - (from + e - 1) / e;
 }
+long long frames_between(const lbm_ctx* c, long long from, long long to) { return recorded_between(c->frame_every, from, to); }
+// ... and the sample rows of the point probes
+long long probes_between(const lbm_ctx* c, long long from, long long to) { return recorded_between(c->probe_every, from, to); }
 
 // lbm_run / lbm_batch_run refuse a call whose frames would not fit the free slots, before any work is issued
 int frames_fit(const lbm_ctx* c, int n_steps, const char* who) {
@@ -1428,6 +1467,35 @@ int frames_fit(const lbm_ctx* c, int n_steps, const char* who) {
   if (waiting + add > c->frame_slots)
     LBM_FAIL(LBM_FAILURE, "%s: %d steps would record %lld frames, but the frame buffer holds %d and %lld frames are waiting "
              "(lbm_read_frames drains them)", who, n_steps, add, c->frame_slots, waiting);
+  return LBM_SUCCESS;
+}
+
+// the same for the sample rows of the point probes and their ring
+int probes_fit(const lbm_ctx* c, int n_steps, const char* who) {
+  const long long add = probes_between(c, c->steps_done, (long long)c->steps_done + n_steps);
+  const long long waiting = c->probes_written - c->probes_read;
+  if (waiting + add > c->probe_slots)
+    LBM_FAIL(LBM_FAILURE, "%s: %d steps would record %lld probe samples, but the probe ring holds %d and %lld samples are waiting "
+             "(lbm_read_probes drains them)", who, n_steps, add, c->probe_slots, waiting);
+  return LBM_SUCCESS;
+}
+
+// the sample row of the current (stored) lattice: every slab gathers the probes in its rows, on its compute stream
+int take_probes(lbm_ctx* c) {
+  const size_t n_probes = c->probe_cells.size();
+  const size_t slot = (size_t)(c->probes_written % c->probe_slots);
+  if (for_slabs(c, [&](int s) -> int {
+        Slab& sl = c->slab[s];
+        if (sl.probe_count == 0) return LBM_SUCCESS;
+        HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+        hipLaunchKernelGGL(lbm::probe_gather, dim3(ceil_div(sl.probe_count, 64)), dim3(64), 0, sl.compute,
+                           (const float*)sl.lat[c->cur], (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch,
+                           c->p.density, (const lbm::ProbeEntry*)sl.probe_table, sl.probe_count, sl.probe_ring + slot * n_probes);
+        HIP_TRY(LBM_FAILURE, hipGetLastError());
+        return LBM_SUCCESS;
+      }) != LBM_SUCCESS)
+    return LBM_FAILURE;
+  c->probes_written++;
   return LBM_SUCCESS;
 }
 
@@ -1473,9 +1541,11 @@ int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
 
   if (resident) {
     const long long frames = frames_between(c, c->steps_done, (long long)c->steps_done + n_steps);
+    const long long samples = probes_between(c, c->steps_done, (long long)c->steps_done + n_steps);
     if (run_resident(c, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
     c->steps_done += n_steps;
     c->frames_written += frames;  // recorded by the kernel itself
+    c->probes_written += samples;
     return LBM_SUCCESS;
   }
 
@@ -1528,19 +1598,22 @@ int run_steps(lbm_ctx* c, int n_steps, float* kernel_ms) {
     LBM_FAIL(LBM_FAILURE, "lbm_run: %d steps requested but the av_vels record holds %d (maxIters)",
              c->steps_done + n_steps, c->capacity);
   if (frames_fit(c, n_steps, "lbm_run") != LBM_SUCCESS) return LBM_FAILURE;
+  if (probes_fit(c, n_steps, "lbm_run") != LBM_SUCCESS) return LBM_FAILURE;
   if (c->halo != HALO_SELF && c->halo_mode != LBM_HALO_SYNC) return run_steps_stale(c, n_steps, kernel_ms);
 
-  // resident or per-pass: decided once per call, whether frames are armed or not
+  // resident or per-pass: decided once per call, whether a recorder (frames or probes) is armed or not
   const bool resident = c->resident && n_steps >= c->resident_min_steps;
-  if (c->frame_every > 0 && !resident) {
-    // per-pass kernels: the call runs as the sub-calls that end at its frame steps, each followed by its frame
-    const int e = c->frame_every;
+  if ((c->frame_every > 0 || c->probe_every > 0) && !resident) {
+    // per-pass kernels: the call runs as the sub-calls that end at its recorder steps, each followed by its frame or
+    // its sample row (the step kernels themselves record nothing)
+    const bool probes = c->probe_every > 0;
+    const int e = probes ? c->probe_every : c->frame_every;
     for (int t = 0; t < n_steps;) {
       const int tt = c->steps_done, r = tt % e;
-      const long long frame_tt = r ? (long long)tt + (e - r) : tt;  // next frame step
-      const int seg = (frame_tt - tt + 1 < n_steps - t) ? (int)(frame_tt - tt + 1) : n_steps - t;
+      const long long rec_tt = r ? (long long)tt + (e - r) : tt;  // next recorder step
+      const int seg = (rec_tt - tt + 1 < n_steps - t) ? (int)(rec_tt - tt + 1) : n_steps - t;
       if (run_passes(c, seg, false, kernel_ms && t == 0) != LBM_SUCCESS) return LBM_FAILURE;
-      if (c->steps_done - 1 == frame_tt && take_frame(c) != LBM_SUCCESS) return LBM_FAILURE;
+      if (c->steps_done - 1 == rec_tt && (probes ? take_probes(c) : take_frame(c)) != LBM_SUCCESS) return LBM_FAILURE;
       t += seg;
     }
   } else if (run_passes(c, n_steps, resident, kernel_ms != nullptr) != LBM_SUCCESS) {
@@ -1811,6 +1884,8 @@ void free_slab(Slab& sl) {
   if (sl.res_status) (void)hipFree(sl.res_status);
   if (sl.res_status_host) (void)hipHostFree(sl.res_status_host);
   if (sl.frames) (void)hipFree(sl.frames);
+  if (sl.probe_ring) (void)hipFree(sl.probe_ring);
+  if (sl.probe_table) (void)hipFree(sl.probe_table);
   if (sl.ev_boundary) (void)hipEventDestroy(sl.ev_boundary);
   if (sl.ev_halo) (void)hipEventDestroy(sl.ev_halo);
   for (int i = 0; i < 2; i++) if (sl.ev_interior[i]) (void)hipEventDestroy(sl.ev_interior[i]);
@@ -2674,6 +2749,9 @@ int lbm_set_halo_mode(lbm_ctx* c, int mode) {
   if (mode != LBM_HALO_SYNC && c->frame_every > 0)
     LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: animation frames are armed (lbm_set_frames); the stale and freshest halo modes "
              "cannot record them -- disarm with lbm_set_frames(ctx, 0, 0) first");
+  if (mode != LBM_HALO_SYNC && c->probe_every > 0)
+    LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: point probes are armed (lbm_set_probes); the stale and freshest halo modes "
+             "cannot record them -- disarm with lbm_set_probes(ctx, 0, NULL, 0, 0) first");
   c->halo_mode = mode;
   return LBM_SUCCESS;
 }
@@ -2686,6 +2764,12 @@ int lbm_set_frames(lbm_ctx* c, int every, int capacity) {
     LBM_FAIL(LBM_FAILURE, "lbm_set_frames: the context runs the %s halo mode, where splitting a call at a frame would change "
              "the results (every call starts from freshly exchanged halos); frames need LBM_HALO_SYNC",
              c->halo_mode == LBM_HALO_STALE ? "stale" : "freshest");
+  if (every > 0 && c->probe_every > 0)
+    LBM_FAIL(LBM_FAILURE, "lbm_set_frames: point probes are armed (lbm_set_probes) and a context has one recorder -- disarm them "
+             "with lbm_set_probes(ctx, 0, NULL, 0, 0) first");
+  if (every > 0 && c->batch && c->batch->probes_armed > 0)
+    LBM_FAIL(LBM_FAILURE, "lbm_set_frames: a member of this batch has point probes armed (lbm_set_probes); a batch records one "
+             "kind, frames or probes");
   if (every > 0 && c->resident) {
     // the FRAMES form of four-row bands defers the acceleration of the interior pair only (lbm::resident_band): the lid
     // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form must run one workgroup per CU
@@ -2694,7 +2778,7 @@ int lbm_set_frames(lbm_ctx* c, int every, int capacity) {
     int per_cu = 0;
     HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
     HIP_TRY(LBM_FAILURE, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                             &per_cu, resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, true), c->p.nx * c->resident_group, 0));
+                             &per_cu, resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, kRecFrames), c->p.nx * c->resident_group, 0));
     if (per_cu < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_frames: the resident kernel's frame form does not fit a CU at this shape");
   }
   // the buffers may still be written by launches in flight
@@ -2785,6 +2869,173 @@ int lbm_read_frames(lbm_ctx* c, int max_frames, float* out, int* steps, int* n_r
     HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
   }
   c->frames_read += n;
+  *n_read = n;
+  return LBM_SUCCESS;
+}
+
+int lbm_set_probes(lbm_ctx* c, int n_probes, const lbm_probe* cells, int every, int capacity) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_probes: null context");
+  if (n_probes < 0 || n_probes > LBM_MAX_PROBES)
+    LBM_FAIL(LBM_FAILURE, "lbm_set_probes: %d probes, between 0 and LBM_MAX_PROBES = %d are possible", n_probes, LBM_MAX_PROBES);
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_probes: negative interval %d", every);
+  const bool arm = n_probes > 0 && every > 0;
+  if (arm) {
+    if (!cells) LBM_FAIL(LBM_FAILURE, "lbm_set_probes: NULL cells");
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_probes: capacity %d, at least one row of samples is needed", capacity);
+    if ((long long)capacity * n_probes * (long long)sizeof(lbm_probe_sample) >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_set_probes: a ring of %d rows of %d samples is 2 GiB or more", capacity, n_probes);
+    for (int i = 0; i < n_probes; i++)
+      if (cells[i].x < 0 || cells[i].x >= c->p.nx || cells[i].y < 0 || cells[i].y >= c->p.ny)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_probes: probe %d is the cell (%d, %d), outside the %d x %d grid", i, cells[i].x, cells[i].y,
+                 c->p.nx, c->p.ny);
+    if (c->ranked || c->world > 1)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_probes: not available in a multi-process (rank) context: a row of samples would be spread over the ranks");
+    if (c->halo_mode != LBM_HALO_SYNC)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_probes: the context runs the %s halo mode, where splitting a call at a sample step would change "
+               "the results (every call starts from freshly exchanged halos); probes need LBM_HALO_SYNC",
+               c->halo_mode == LBM_HALO_STALE ? "stale" : "freshest");
+    if (c->frame_every > 0)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_probes: animation frames are armed (lbm_set_frames) and a context has one recorder -- disarm "
+               "them with lbm_set_frames(ctx, 0, 0) first");
+    if (c->batch && c->batch->frames_armed > 0)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_probes: a member of this batch has animation frames armed (lbm_set_frames); a batch records one "
+               "kind, frames or probes");
+    if (c->resident) {
+      // as lbm_set_frames: four-row bands defer the lid's acceleration in the interior pair only, and the form must fit a CU
+      if (c->resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_probes: the lid row %d is not an interior row of a four-row band", c->slab[0].accel_row);
+      int per_cu = 0;
+      HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
+      HIP_TRY(LBM_FAILURE, hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                               &per_cu, resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, kRecProbes), c->p.nx * c->resident_group, 0));
+      if (per_cu < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_probes: the resident kernel's probes form does not fit a CU at this shape");
+    }
+  }
+  // the buffers may still be written by launches in flight
+  for (int s = 0; s < c->n_slabs; s++) {
+    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
+    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
+  }
+  auto release = [&]() {
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      (void)hipSetDevice(sl.device);
+      if (sl.probe_ring) (void)hipFree(sl.probe_ring);
+      if (sl.probe_table) (void)hipFree(sl.probe_table);
+      sl.probe_ring = nullptr;
+      sl.probe_table = nullptr;
+      sl.probe_count = 0;
+    }
+    c->probe_cells.clear();
+    c->probe_every = c->probe_slots = c->probe_ord0 = 0;
+    c->probes_written = c->probes_read = 0;
+  };
+  lbm_batch* bt = c->batch;
+  // a batch member's entry of the table the batched launches read
+  auto set_entry = [&](const lbm::ResidentProbes& entry) -> int {
+    if (!bt || (!bt->probe_table && !entry.ring)) return LBM_SUCCESS;
+    int index = 0;
+    while (bt->members[(size_t)index] != c) index++;
+    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
+    if (!bt->probe_table) {
+      HIP_TRY(LBM_FAILURE, hipMalloc(&bt->probe_table, bt->members.size() * sizeof(lbm::ResidentProbes)));
+      HIP_TRY(LBM_FAILURE, hipMemset(bt->probe_table, 0, bt->members.size() * sizeof(lbm::ResidentProbes)));
+    }
+    HIP_TRY(LBM_FAILURE, hipMemcpy(bt->probe_table + index, &entry, sizeof(entry), hipMemcpyHostToDevice));
+    return LBM_SUCCESS;
+  };
+  if (bt && c->probe_every > 0) bt->probes_armed--;
+  release();
+  if (set_entry(lbm::ResidentProbes{}) != LBM_SUCCESS) return LBM_FAILURE;
+  if (!arm) return LBM_SUCCESS;
+
+  const size_t ring_bytes = (size_t)capacity * (size_t)n_probes * sizeof(lbm::probe_vec);
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    // this slab's probes sorted by row (stable: ties keep the caller's order), then, where the resident kernel runs, the
+    // word of every band: first entry | entries << 12 | (a probe on the lid row) << 31
+    std::vector<int> mine;
+    for (int i = 0; i < n_probes; i++)
+      if (cells[i].y >= sl.row_first && cells[i].y < sl.row_first + sl.rows) mine.push_back(i);
+    std::stable_sort(mine.begin(), mine.end(), [&](int p, int q) { return cells[p].y < cells[q].y; });
+    const int bands = c->resident ? c->resident_bands : 0;
+    std::vector<unsigned> words(2 * mine.size() + (size_t)bands, 0u);
+    for (size_t j = 0; j < mine.size(); j++) {
+      const int row = cells[mine[j]].y - sl.row_first;
+      words[2 * j] = (unsigned)row;
+      words[2 * j + 1] = (unsigned)cells[mine[j]].x | ((unsigned)mine[j] << 20);
+      if (bands) {
+        unsigned& w = words[2 * mine.size() + (size_t)(row / c->resident_rows)];
+        if (((w >> 12) & 0xfffu) == 0) w |= (unsigned)j;
+        w += 1u << 12;
+        if (row == sl.accel_row) w |= 1u << 31;
+      }
+    }
+    static_assert(sizeof(lbm::ProbeEntry) == 2 * sizeof(unsigned), "a table entry is two words");
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    if (hipMalloc(&sl.probe_ring, ring_bytes) != hipSuccess ||
+        hipMalloc(&sl.probe_table, (words.size() + 2) * sizeof(unsigned)) != hipSuccess ||
+        hipMemset(sl.probe_ring, 0, ring_bytes) != hipSuccess ||
+        (!words.empty() && hipMemcpy(sl.probe_table, words.data(), words.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess)) {
+      (void)hipGetLastError();  // a failed allocation must not surface at the next launch
+      release();
+      LBM_FAIL(LBM_FAILURE, "lbm_set_probes: cannot allocate %d rows of %d samples (%.1f MiB per slab); probes stay off", capacity,
+               n_probes, (double)ring_bytes / 1048576.0);
+    }
+    sl.probe_count = (int)mine.size();
+  }
+  c->probe_cells.assign(cells, cells + n_probes);
+  c->probe_every = every;
+  c->probe_slots = capacity;
+  c->probe_ord0 = (int)(((long long)c->steps_done + every - 1) / every);
+  const Slab& s0 = c->slab[0];
+  if (set_entry({s0.probe_ring, s0.probe_table, every, c->probe_ord0, capacity, s0.probe_count, c->p.density, 0}) != LBM_SUCCESS) {
+    release();
+    return LBM_FAILURE;
+  }
+  if (bt) bt->probes_armed++;
+  return LBM_SUCCESS;
+}
+
+int lbm_read_probes(lbm_ctx* c, int max_samples, lbm_probe_sample* out, int* steps, int* n_read) {
+  if (!c || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_read_probes: NULL argument");
+  *n_read = 0;
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
+  const long long waiting = c->probes_written - c->probes_read;
+  if (!out && !steps) {
+    *n_read = (int)waiting;
+    return LBM_SUCCESS;
+  }
+  if (!out) LBM_FAIL(LBM_FAILURE, "lbm_read_probes: NULL sample output");
+  if (max_samples < 0) LBM_FAIL(LBM_FAILURE, "lbm_read_probes: negative max_samples %d", max_samples);
+  const int n = (waiting < max_samples) ? (int)waiting : max_samples;
+  const size_t np = c->probe_cells.size();
+  static_assert(sizeof(lbm_probe_sample) == sizeof(lbm::probe_vec), "a sample is one 16-byte store");
+  // the rows wait in at most two runs of the ring; one slab: straight into out, several: each slab's columns of a staged copy
+  std::vector<lbm_probe_sample> stage(c->n_slabs > 1 ? (size_t)n * np : 0);
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    if (sl.probe_count == 0 && c->n_slabs > 1) continue;
+    lbm_probe_sample* dst = c->n_slabs > 1 ? stage.data() : out;
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    for (int i = 0; i < n;) {
+      const size_t slot = (size_t)((c->probes_read + i) % c->probe_slots);
+      const int run = ((size_t)(n - i) < (size_t)c->probe_slots - slot) ? n - i : (int)((size_t)c->probe_slots - slot);
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(dst + (size_t)i * np, sl.probe_ring + slot * np, (size_t)run * np * sizeof(lbm_probe_sample),
+                                          hipMemcpyDeviceToHost, sl.compute));
+      i += run;
+    }
+    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+    if (c->n_slabs > 1)
+      for (size_t p = 0; p < np; p++) {
+        const int y = c->probe_cells[p].y;
+        if (y < sl.row_first || y >= sl.row_first + sl.rows) continue;
+        for (int i = 0; i < n; i++) out[(size_t)i * np + p] = stage[(size_t)i * np + p];
+      }
+  }
+  if (steps)
+    for (int i = 0; i < n; i++) steps[i] = (int)((c->probe_ord0 + c->probes_read + i) * c->probe_every);
+  c->probes_read += n;
   *n_read = n;
   return LBM_SUCCESS;
 }
@@ -3005,6 +3256,7 @@ void lbm_destroy_batch(lbm_batch* bt) {
   }
   if (bt->table) (void)hipFree(bt->table);
   if (bt->frame_table) (void)hipFree(bt->frame_table);
+  if (bt->probe_table) (void)hipFree(bt->probe_table);
   if (bt->status) (void)hipFree(bt->status);
   if (bt->status_host) (void)hipHostFree(bt->status_host);
   if (bt->steady_state) (void)hipFree(bt->steady_state);
@@ -3130,11 +3382,13 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
     LBM_FAIL(LBM_FAILURE, "lbm_batch_run: %d steps requested but the av_vels record holds %d (maxIters)",
              bt->steps_done + n_steps, c0->capacity);
   for (lbm_ctx* c : bt->members)  // every member's frames must fit before any member runs
-    if (frames_fit(c, n_steps, "lbm_batch_run") != LBM_SUCCESS) return LBM_FAILURE;
+    if (frames_fit(c, n_steps, "lbm_batch_run") != LBM_SUCCESS || probes_fit(c, n_steps, "lbm_batch_run") != LBM_SUCCESS)
+      return LBM_FAILURE;
   if (bt->resident && n_steps >= c0->resident_min_steps) {
     if (run_batch_resident(bt, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
     for (lbm_ctx* c : bt->members) {
       c->frames_written += frames_between(c, c->steps_done, (long long)c->steps_done + n_steps);
+      c->probes_written += probes_between(c, c->steps_done, (long long)c->steps_done + n_steps);
       c->steps_done += n_steps;
     }
   } else {
@@ -3142,7 +3396,7 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
     for (lbm_ctx* c : bt->members)
       if (run_steps(c, n_steps, nullptr) != LBM_SUCCESS) return LBM_FAILURE;
     bt->cur = c0->cur;
-    // a member with frames armed ran its call split at its frame steps, i.e. possibly another number of passes: its
+    // a member with frames (or probes) armed ran its call split at its recorder steps, i.e. possibly another number of passes: its
     // lattice may lie in the other buffer.  Batched launches take every member's lattice at the batch's parity
     // (bt->table), so such a member's lattice moves there (a device copy on the batch's stream).
     for (lbm_ctx* c : bt->members) {
@@ -3192,6 +3446,7 @@ static int steady_args_ok(const char* who, int steps_done, int capacity, int max
   return LBM_SUCCESS;
 }
 static const char kSteadyFrames[] = "%s: animation frames are armed (lbm_set_frames); a steady-state run does not record frames";
+static const char kSteadyProbes[] = "%s: point probes are armed (lbm_set_probes); a steady-state run does not record probes";
 
 static void steady_fill(lbm_steady_result* out, const lbm::SteadyState& st, int steps_run) {
   out->steps_run = steps_run;
@@ -3229,6 +3484,7 @@ int lbm_run_until(lbm_ctx* c, int max_steps, int check_every, double tol, int pa
   if (steady_args_ok("lbm_run_until", c->steps_done, c->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS)
     return LBM_FAILURE;
   if (c->frame_every > 0) LBM_FAIL(LBM_FAILURE, kSteadyFrames, "lbm_run_until");
+  if (c->probe_every > 0) LBM_FAIL(LBM_FAILURE, kSteadyProbes, "lbm_run_until");
   if (c->halo_mode != LBM_HALO_SYNC)
     LBM_FAIL(LBM_FAILURE, "lbm_run_until: only LBM_HALO_SYNC runs can be checked (the halo mode is %d)", c->halo_mode);
   if (c->ranked || c->world > 1)
@@ -3304,8 +3560,10 @@ int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double to
   const int n_members = (int)bt->members.size();
   if (steady_args_ok("lbm_batch_run_until", bt->steps_done, c0->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS)
     return LBM_FAILURE;
-  for (const lbm_ctx* c : bt->members)
+  for (const lbm_ctx* c : bt->members) {
     if (c->frame_every > 0) LBM_FAIL(LBM_FAILURE, kSteadyFrames, "lbm_batch_run_until");
+    if (c->probe_every > 0) LBM_FAIL(LBM_FAILURE, kSteadyProbes, "lbm_batch_run_until");
+  }
 
   HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
   if (!bt->steady_state) {

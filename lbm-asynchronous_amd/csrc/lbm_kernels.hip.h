@@ -1565,6 +1565,32 @@ struct ResidentFramesArgs : ResidentArgs {
 struct ResidentBatchFramesArgs : ResidentBatchArgs {
   const ResidentFrames* frames;  // [this launch's members], as members
 };
+// point probes (lbm_set_probes, resident_band<..., PROBES = true>): after global step tt with tt % every == 0 the kernel
+// stores {u_x, u_y, |u|, pressure} of every probed cell into row (tt / every - ord0) % slots of ring, one 16-byte sample
+// per probe, in the caller's probe order.  The host sorts the probes by row: `table` holds them in that order, followed by
+// one word per band of the resident kernel -- first entry | entries << 12 | (a probe lies on the lid row) << 31 -- so a
+// band without probes learns so from one word.  Appended like ResidentFrames: the other forms' arguments do not move.
+struct ProbeEntry {
+  int row;                    // slab row of the cell
+  unsigned xi;                // column | probe index << 20
+};
+typedef float probe_vec __attribute__((ext_vector_type(4)));
+struct ResidentProbes {
+  probe_vec* ring;            // row 0; nullptr / every = 0: no probes
+  const ProbeEntry* table;
+  int every;
+  int ord0;                   // tt / every of the first sample row after arming
+  int slots;
+  int n_probes;
+  float density;              // a blocked cell reports density * c_sq as its pressure
+  int pad;
+};
+struct ResidentProbesArgs : ResidentArgs {
+  ResidentProbes pr;
+};
+struct ResidentBatchProbesArgs : ResidentBatchArgs {
+  const ResidentProbes* probes;  // [this launch's members], as members
+};
 #ifdef LBM_RESIDENT_PROFILE
 __device__ __forceinline__ long long prof_clock() {
   long long t;
@@ -1604,6 +1630,15 @@ __device__ __forceinline__ float frame_speed(const f2 (&r)[kQ], int c, bool bloc
   float rho, ux, uy;
   moments_exact(f, rho, ux, uy);
   return blocked ? 0.f : sqrtf((ux * ux) + (uy * uy));
+}
+
+// the sample of one cell as lbm_read_final_state reports it (final_state: moments_exact, IEEE sqrt, the blocked constants)
+__device__ __forceinline__ probe_vec probe_sample(const float (&f)[kQ], bool blocked, float density) {
+  float rho, ux, uy;
+  moments_exact(f, rho, ux, uy);
+  const probe_vec fluid = {ux, uy, sqrtf((ux * ux) + (uy * uy)), rho * kCsq};
+  const probe_vec solid = {0.f, 0.f, 0.f, density * kCsq};
+  return blocked ? solid : fluid;
 }
 
 // sum over the first 16 lanes (one DPP row), valid in every lane of that row
@@ -1683,12 +1718,18 @@ __device__ __forceinline__ granule_vec granule_load(__amdgpu_buffer_rsrc_t rsrc,
 // step's accelerate_flow, |u| of the post-step lattice goes to the frame slot, and only then is accelerate_select applied
 // to the relaxed values: bit-identical to the fused epilogue, since accelerate_select is a pure select on the relaxed
 // values that never touches a blocked cell (the only cells bounce_select changes).
-template <bool BATCH, bool FRAMES>
-using ResidentArgsOf = std::conditional_t<BATCH, std::conditional_t<FRAMES, ResidentBatchFramesArgs, ResidentBatchArgs>,
-                                          std::conditional_t<FRAMES, ResidentFramesArgs, ResidentArgs>>;
-template <int MAXT, bool JOINT = false, int ROWS = 4, bool BATCH = false, bool FRAMES = false>
-__global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH, FRAMES> a) {
+// PROBES: also record point probes (ResidentProbes).  On a sample step a band without probes does nothing further; a
+// band with probes walks its entries wave-uniformly and the lane that holds the cell stores its sample (one dwordx4).
+// Only a band with a probe ON the lid row defers the lid's acceleration on sample steps, exactly as FRAMES does.
+// FRAMES && PROBES is never instantiated: one recorder per context.
+template <bool BATCH, bool FRAMES, bool PROBES>
+using ResidentArgsOf = std::conditional_t<
+    BATCH, std::conditional_t<FRAMES, ResidentBatchFramesArgs, std::conditional_t<PROBES, ResidentBatchProbesArgs, ResidentBatchArgs>>,
+    std::conditional_t<FRAMES, ResidentFramesArgs, std::conditional_t<PROBES, ResidentProbesArgs, ResidentArgs>>>;
+template <int MAXT, bool JOINT = false, int ROWS = 4, bool BATCH = false, bool FRAMES = false, bool PROBES = false>
+__global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH, FRAMES, PROBES> a) {
   static_assert(ROWS == 4 || ROWS == 2, "bands of four or two rows");
+  static_assert(!(FRAMES && PROBES), "one recorder per context");
   constexpr int NE = (ROWS == 4) ? 10 : 4;  // wave-edge values per side
   // a workgroup holds a.group bands side by side (1: the usual case; more where a band has fewer than four waves and
   // the whole grid fits one XCD with one wave per SIMD, see a.one_xcd): `wave`, `n_waves` count inside the band,
@@ -1698,6 +1739,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
   int n_wgs = a.one_xcd ? (int)(gridDim.x >> 3) : (int)gridDim.x, wg = a.one_xcd ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
   ResidentMember mb{};
   ResidentFrames fr{};
+  ResidentProbes pr{};
   if constexpr (BATCH) {
     const int stride = (a.member_wgs + 7) & ~7;
     const int member = a.one_xcd ? (int)(blockIdx.x & 7) : (int)blockIdx.x / stride;
@@ -1705,8 +1747,10 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     if (member >= a.n_members || wg >= n_wgs) return;
     mb = a.members[member];
     if constexpr (FRAMES) fr = a.frames[member];
+    if constexpr (PROBES) pr = a.probes[member];
   } else if (a.one_xcd && (blockIdx.x & 7) != 0) return;
   if constexpr (FRAMES && !BATCH) fr = a.fr;
+  if constexpr (PROBES && !BATCH) pr = a.pr;
 #define RES_M(field) (BATCH ? mb.field : a.field)
   const int bands = n_wgs * a.group;
   // Workgroups are dealt to the 8 XCDs round-robin (observed, not promised): consecutive bands are given to
@@ -1825,6 +1869,52 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     f_slot = (f_slot + 1 == fr.slots) ? 0 : f_slot + 1;
   };
 
+  // probes: the same bookkeeping (f_next, f_slot count sample rows) and this band's word of the table
+  unsigned p_range = 0;
+  if constexpr (PROBES) {
+    if (pr.every > 0) {
+      const unsigned e = (unsigned)pr.every, r = a.epoch0 % e;
+      f_next = r ? e - r : 0u;
+      f_slot = (int)(((a.epoch0 + f_next) / e - (unsigned)pr.ord0) % (unsigned)pr.slots);
+      p_range = (unsigned)__builtin_amdgcn_readfirstlane((int)reinterpret_cast<const unsigned*>(pr.table + pr.n_probes)[b]);
+    }
+  }
+  // probes: the samples of this band's probed cells -- edge pair `pe`, interior pair ri, both post-step -- into the ring's
+  // row, then the deferred accelerate_flow on `lidp` (see take_frame) where this band deferred it
+  auto take_probes = [&](const f2 (&pe)[kQ], f2 (&lidp)[kQ], bool deferred) {
+    const unsigned count = (p_range >> 12) & 0xfffu;
+    if (count != 0) {
+      const __amdgpu_buffer_rsrc_t prsrc = __builtin_amdgcn_make_buffer_rsrc(pr.ring, 0, pr.slots * pr.n_probes * 16, 0x00020000);
+      const ProbeEntry* ent = pr.table + (p_range & 0xfffu);
+      const int row0 = __builtin_amdgcn_readfirstlane(ROWS * b);
+      for (unsigned j = 0; j < count; j++) {  // wave-uniform
+        const int rb = __builtin_amdgcn_readfirstlane(ent[j].row) - row0;
+        const unsigned xi = (unsigned)__builtin_amdgcn_readfirstlane((int)ent[j].xi);
+        if ((int)(xi & 0xfffffu) == x) {
+          float f[kQ];
+          unsigned blk;
+          if constexpr (ROWS == 4) {
+#pragma unroll
+            for (int k = 0; k < kQ; k++) f[k] = (rb == 0) ? pe[k].x : (rb == 3) ? pe[k].y : (rb == 1) ? ri[k].x : ri[k].y;
+            blk = (rb == 0) ? (blocked_e & 0xffu) : (rb == 3) ? (blocked_e & 0xff00u) : (rb == 1) ? (blocked_i & 0xffu) : (blocked_i & 0xff00u);
+          } else {
+#pragma unroll
+            for (int k = 0; k < kQ; k++) f[k] = (rb == 0) ? pe[k].x : pe[k].y;
+            blk = (rb == 0) ? (blocked_e & 0xffu) : (blocked_e & 0xff00u);
+          }
+          const probe_vec v = probe_sample(f, blk != 0, pr.density);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(granule_vec, v), prsrc, 0, (f_slot * pr.n_probes + (int)(xi >> 20)) * 16, 0);
+        }
+      }
+    }
+    if (deferred) {
+      const unsigned lid = (ROWS == 4) ? lid_i : lid_e, blk = (ROWS == 4) ? blocked_i : blocked_e;
+      accelerate_select(lidp, (lid & 1u) != 0 && (blk & 0xffu) == 0, (lid & 2u) != 0 && (blk & 0xff00u) == 0, RES_M(a1), RES_M(a2));
+    }
+    f_next += (unsigned)pr.every;
+    f_slot = (f_slot + 1 == pr.slots) ? 0 : f_slot + 1;
+  };
+
   bool alive = true;
 #ifdef LBM_RESIDENT_PROFILE
   long long prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_t = prof_clock();
@@ -1887,11 +1977,17 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
 
     bool frame_now = false;
     if constexpr (FRAMES) frame_now = ((unsigned)s == f_next);  // wave-uniform
+    // probes: a sample step; only a band with a probe on the lid row defers the lid's acceleration as a frame step does
+    bool sample_now = false;
+    if constexpr (PROBES) {
+      sample_now = ((unsigned)s == f_next);
+      frame_now = sample_now && (p_range >> 31) != 0;
+    }
     const bool accel_next = (s + 1 < a.n_steps) || a.accel_last;
     // a frame step applies the lid's acceleration after taking the frame (take_frame).  ROWS = 4: the lid row is
     // band row 2 (ny - 2 with ny % 4 == 0; run_resident checks it), an interior row, so only the interior pair defers
     const bool accel = accel_next && !(ROWS == 2 && frame_now);
-    const bool accel_i = FRAMES ? accel_next && !frame_now : accel;
+    const bool accel_i = (FRAMES || PROBES) ? accel_next && !frame_now : accel;
     // shifted populations (the value each cell receives from its west / east neighbour) and the streamed inputs of
     // the pair(s), as far as they come from inside the band
     f2 ti[kQ], te[kQ];
@@ -1976,6 +2072,9 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     if constexpr (FRAMES && ROWS == 2) {
       if (frame_now) take_frame(ne, accel_next);
     }
+    if constexpr (PROBES && ROWS == 2) {
+      if (sample_now) take_probes(ne, ne, frame_now && accel_next && lid_e != 0);
+    }
 #pragma unroll
     for (int k = 0; k < kQ; k++) {
       re[k] = ne[k];
@@ -1990,6 +2089,9 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     // ROWS = 4: the frame once the step's own work is out (fewest live registers: the 128-VGPR form does not spill)
     if constexpr (FRAMES && ROWS == 4) {
       if (frame_now) take_frame(ri, accel_next);
+    }
+    if constexpr (PROBES && ROWS == 4) {
+      if (sample_now) take_probes(re, ri, frame_now && accel_next && lid_i != 0);
     }
     RESIDENT_PROF(6);  // publish, wave sum
     // (a wave that gave up leaves the loop alone: the hardware barrier counts only waves that have not ended, and
@@ -2369,6 +2471,21 @@ __global__ void frame_umag(const float* lat, const unsigned char* mask, long ps,
     moments_exact(f, rho, ux, uy);
     out[i] = sqrtf((ux * ux) + (uy * uy));
   }
+}
+
+// one sample row of a stored lattice (lbm_set_probes, per-pass paths): final_state's four values at the slab's probed
+// cells, one thread per probe, into row[probe index]
+__global__ void probe_gather(const float* lat, const unsigned char* mask, long ps, long row_pitch, int pitch, float density,
+                             const ProbeEntry* table, int n, probe_vec* row) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const ProbeEntry e = table[i];
+  const int x = (int)(e.xi & 0xfffffu);
+  const long c = (long)e.row * row_pitch + x;
+  float f[kQ];
+#pragma unroll
+  for (int k = 0; k < kQ; k++) f[k] = lat[k * ps + c];
+  row[e.xi >> 20] = probe_sample(f, mask[(long)e.row * pitch + x] != 0, density);
 }
 
 // av_velocity() of a stored lattice (SerialCode/d2q9-bgk.c:409-458): per-workgroup partials of

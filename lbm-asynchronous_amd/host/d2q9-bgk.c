@@ -59,6 +59,43 @@ static void parse_steady(const char* text, double* tol, int* check_every, int* p
   *patience = (int)v[1];
 }
 
+/* LBM_PROBES=x,y[;x,y...][:every] (every defaults to 1); plain decimal numbers only; dies on anything else */
+static int parse_probes(const char* text, lbm_probe* cells, int* every)
+{
+  const char* s = text;
+  int n = 0, ok = 1;
+  *every = 1;
+  for (;;) {
+    long v[2];
+    for (int i = 0; ok && i < 2; i++) {
+      char* end = NULL;
+      ok = (*s >= '0' && *s <= '9');
+      if (!ok) break;
+      v[i] = strtol(s, &end, 10);
+      ok = v[i] <= 2147483647L && (i == 1 || *end == ',');
+      s = (i == 0 && ok) ? end + 1 : end;
+    }
+    if (!ok || n == LBM_MAX_PROBES) { ok = 0; break; }
+    cells[n].x = (int)v[0];
+    cells[n].y = (int)v[1];
+    n++;
+    if (*s != ';') break;
+    s++;
+  }
+  if (ok && *s == ':') {
+    char* end = NULL;
+    s++;
+    ok = (*s >= '0' && *s <= '9');
+    const long e = ok ? strtol(s, &end, 10) : 0;
+    ok = ok && e >= 1 && e <= 2147483647L;
+    *every = (int)e;
+    if (ok) s = end;
+  }
+  if (!ok || *s != '\0')
+    lbm_die("could not read LBM_PROBES: expected <x>,<y>[;<x>,<y>...][:<every>] with at most 256 cells and every >= 1", __LINE__, __FILE__);
+  return n;
+}
+
 int main(int argc, char* argv[])
 {
   if (argc != 3) lbm_usage(argv[0]);
@@ -78,6 +115,12 @@ int main(int argc, char* argv[])
   double steady_tol = 0.0;
   int steady_every = 0, steady_patience = 0;
   if (until) parse_steady(steady_env, &steady_tol, &steady_every, &steady_patience);
+
+  const char* probes_env = getenv("LBM_PROBES");
+  static lbm_probe probe_cells[LBM_MAX_PROBES];
+  int probe_every = 0;
+  const int n_probes = (probes_env && *probes_env) ? parse_probes(probes_env, probe_cells, &probe_every) : 0;
+  if (n_probes > 0 && until) lbm_die("LBM_STEADY and LBM_PROBES cannot be combined", __LINE__, __FILE__);
 
   /* Total/init time starts here (SerialCode/d2q9-bgk.c:156-159) */
   const double tot_tic = wall_seconds();
@@ -124,6 +167,7 @@ int main(int argc, char* argv[])
   if ((env = getenv("LBM_ANIMATION")) && *env) anim_every = atoi(env);
 
   if (until && anim_every > 0) lbm_die("LBM_STEADY and LBM_ANIMATION cannot be combined", __LINE__, __FILE__);
+  if (n_probes > 0 && anim_every > 0) lbm_die("LBM_PROBES and LBM_ANIMATION cannot be combined", __LINE__, __FILE__);
   int steps_run = params.max_iters;
   lbm_steady_result steady;
   memset(&steady, 0, sizeof(steady));
@@ -162,6 +206,36 @@ int main(int argc, char* argv[])
       t += n;
     }
     free(frames);
+    free(steps);
+  } else if (n_probes > 0) {
+    /* with probes: segments whose sample rows fit a ring of 64 MiB, each drained and written after it */
+    const size_t row_bytes = (size_t)n_probes * sizeof(lbm_probe_sample);
+    long cap = (long)((64UL << 20) / row_bytes);
+    const long total_rows = params.max_iters > 0 ? (params.max_iters + probe_every - 1) / probe_every : 0;
+    if (cap > total_rows) cap = total_rows;
+    if (cap < 1) cap = 1;
+    if (lbm_set_probes(ctx, n_probes, probe_cells, probe_every, (int)cap) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+    lbm_probe_sample* samples = (lbm_probe_sample*)malloc(row_bytes * (size_t)cap);
+    int* steps = (int*)malloc(sizeof(int) * (size_t)cap);
+    FILE* fp = fopen(LBM_PROBESFILE, "w");
+    if (samples == NULL || steps == NULL) lbm_die("cannot allocate memory for probe samples", __LINE__, __FILE__);
+    if (fp == NULL) lbm_die("could not open file output file", __LINE__, __FILE__);
+    const long seg = cap * (long)probe_every;
+    for (long t = 0; t < params.max_iters;) {
+      const int n = (int)((params.max_iters - t < seg) ? params.max_iters - t : seg);
+      if (lbm_run(ctx, n) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+      int n_read = 0;
+      if (lbm_read_probes(ctx, (int)cap, samples, steps, &n_read) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+      for (int i = 0; i < n_read; i++)
+        for (int q = 0; q < n_probes; q++) {
+          const lbm_probe_sample* v = samples + (size_t)i * (size_t)n_probes + q;
+          fprintf(fp, "%d %d %d %.12E %.12E %.12E %.12E\n", steps[i], probe_cells[q].x, probe_cells[q].y, v->u_x, v->u_y, v->u_mag,
+                  v->pressure);
+        }
+      t += n;
+    }
+    fclose(fp);
+    free(samples);
     free(steps);
   } else {
     lbm_run(ctx, params.max_iters);
