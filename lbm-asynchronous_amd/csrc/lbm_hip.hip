@@ -331,6 +331,34 @@ struct GraphBuilder {
   }
 };
 
+// One recorder per context: after global step tt with tt % every == 0 the running kernels store a record -- a frame
+// (|u| of the owned rows, lbm_set_frames) or a row of probe samples (lbm_set_probes) -- into slot
+// (tt / every - ord0) % slots of every slab's buffer of that kind.
+enum { kRecNone = 0, kRecFrames = 1, kRecProbes = 2 };
+struct Recorder {
+  int kind = kRecNone;
+  int every = 0;
+  int slots = 0;
+  int ord0 = 0;             // tt / every of the first record after arming
+  long long written = 0;    // records issued since arming (ordinals 0 .. written - 1) ...
+  long long read = 0;       // ... and drained by the kind's reader
+};
+// what differs between the kinds in the host's messages (indexed by kind; kRecNone keeps the empty defaults)
+struct RecorderKind {
+  const char* name = "";    // "<name> are armed"
+  const char* noun = "";    // the short name
+  const char* record = "";  // one record: "<record>s are waiting"
+  const char* setter = "";
+  const char* reader = "";
+  const char* disarm = "";  // the call that disarms
+};
+constexpr RecorderKind kRecorderKinds[3] = {
+    {},
+    {.name = "animation frames", .noun = "frames", .record = "frame", .setter = "lbm_set_frames",
+     .reader = "lbm_read_frames", .disarm = "lbm_set_frames(ctx, 0, 0)"},
+    {.name = "point probes", .noun = "probes", .record = "sample", .setter = "lbm_set_probes",
+     .reader = "lbm_read_probes", .disarm = "lbm_set_probes(ctx, 0, NULL, 0, 0)"}};
+
 struct lbm_ctx {
   lbm_params p;
   int pitch = 0;
@@ -385,21 +413,8 @@ struct lbm_ctx {
   int tile_steps = 0;               // > 0: single slab advanced by the LDS-tile kernel, this many steps per launch
   int tile_shape = 0;               // index into kTileShapes
   lbm_batch* batch = nullptr;       // member of this batch (lbm_create_batch): advanced, synchronised and freed by it
-  // animation frames (lbm_set_frames): after global step tt with tt % frame_every == 0, |u| of the owned rows goes to
-  // slot (tt / frame_every - frame_ord0) % frame_slots of every slab's frames buffer
-  int frame_every = 0;              // 0: not armed
-  int frame_slots = 0;
-  int frame_ord0 = 0;               // tt / frame_every of the first frame after arming
-  long long frames_written = 0;     // frames issued since arming (frame ordinals 0 .. frames_written - 1) ...
-  long long frames_read = 0;        // ... and drained by lbm_read_frames
-  // point probes (lbm_set_probes): the same bookkeeping for sample rows of probe_cells.size() samples; one recorder per
-  // context, so at most one of frame_every and probe_every is non-zero
-  std::vector<lbm_probe> probe_cells;  // global cells, in the caller's order
-  int probe_every = 0;              // 0: not armed
-  int probe_slots = 0;
-  int probe_ord0 = 0;
-  long long probes_written = 0;
-  long long probes_read = 0;
+  Recorder rec;                     // the one recorder: animation frames (lbm_set_frames) or point probes (lbm_set_probes)
+  std::vector<lbm_probe> probe_cells;  // the probed global cells, in the caller's order (a probes row has that many samples)
   // steady-state runs (lbm_run_until), allocated by the first such call
   lbm::SteadyState* steady_state = nullptr;  // device: what the checks of the current call have found
   int* steady_stop_host = nullptr;  // pinned: its stop word after segment j, in slot j & 1 ...
@@ -423,9 +438,9 @@ struct lbm_batch {
   int* status = nullptr;            // device: 0, or kResidentTimeout once a workgroup of any batched launch gave up
   int* status_host = nullptr;       // pinned copy behind every run; every member's lbm_sync reports it
   lbm::ResidentFrames* frame_table = nullptr;  // device: [members], allocated when the first member arms frames
-  int frames_armed = 0;             // members with frames armed: batched launches run the FRAMES kernel
   lbm::ResidentProbes* probe_table = nullptr;  // device: [members], allocated when the first member arms probes
-  int probes_armed = 0;             // members with probes armed: batched launches run the PROBES kernel (never both kinds)
+  int armed[3] = {0, 0, 0};         // members with a recorder of each kind armed: batched launches run that kind's kernel
+                                    // (a batch records one kind, so at most one count is non-zero)
   // steady-state runs (lbm_batch_run_until), allocated by the first such call
   lbm::SteadyState* steady_state = nullptr;    // device: [members]
   lbm::SteadyMember* steady_members = nullptr; // device: [members]
@@ -435,6 +450,16 @@ struct lbm_batch {
 };
 
 namespace {
+
+// the acceleration weights of the lid row (SerialCode/d2q9-bgk.c:219-220), and the a1 / a2 fields of a kernel's arguments
+struct AccelWeights { float a1, a2; };
+AccelWeights accel_weights(const lbm_params& p) { return {p.density * p.accel / 9.f, p.density * p.accel / 36.f}; }
+template <class Args>
+void set_accel_weights(Args& a, const lbm_params& p) {
+  const AccelWeights w = accel_weights(p);
+  a.a1 = w.a1;
+  a.a2 = w.a2;
+}
 
 // run body(s) for every slab: concurrently on the slab team when there is one, else in order
 int for_slabs(lbm_ctx* c, const std::function<int(int)>& body) {
@@ -513,8 +538,7 @@ int launch_step(lbm_ctx* c, int s, hipStream_t stream, int row_first, int row_st
   a.n_rows = n_rows;
   a.accel_row = accel_epilogue ? sl.accel_row : lbm::kNoRow;
   a.omega = c->p.omega;
-  a.a1 = c->p.density * c->p.accel / 9.f;   // SerialCode/d2q9-bgk.c:219
-  a.a2 = c->p.density * c->p.accel / 36.f;  // :220
+  set_accel_weights(a, c->p);
   a.partials = sl.partials + (long)c->slot_fill * c->part_stride + part_offset;
   a.reverse = (c->snake && n_rows > 2) ? (c->cur & 1) : 0;
   a.wrap = (c->halo == HALO_SELF) ? 1 : 0;
@@ -566,8 +590,7 @@ int launch_step2(lbm_ctx* c, int s, hipStream_t stream, int row_first, int row_e
   a.accel_row = sl.accel_row;
   a.accel_after = accel_after ? 1 : 0;
   a.omega = c->p.omega;
-  a.a1 = c->p.density * c->p.accel / 9.f;
-  a.a2 = c->p.density * c->p.accel / 36.f;
+  set_accel_weights(a, c->p);
   a.partials1 = sl.partials + (long)c->slot_fill * c->part_stride + part_offset;
   a.partials2 = a.partials1 + c->part_stride;
   const int waves = c->n_strips * band_count;
@@ -611,8 +634,7 @@ int launch_stepk(lbm_ctx* c, int s, hipStream_t stream, int k, int row_first, in
   a.accel_row2 = sl.accel_row2;
   a.accel_after = accel_after ? 1 : 0;
   a.omega = c->p.omega;
-  a.a1 = c->p.density * c->p.accel / 9.f;
-  a.a2 = c->p.density * c->p.accel / 36.f;
+  set_accel_weights(a, c->p);
   a.partials = sl.partials + (long)c->slot_fill * c->part_stride + part_offset;
   a.slot_stride = c->part_stride;
   int waves = c->n_strips * band_count;
@@ -689,8 +711,7 @@ int launch_tile(lbm_ctx* c, hipStream_t stream, int n_steps, bool accel_after) {
   a.accel_row = sl.accel_row;
   a.accel_after = accel_after ? 1 : 0;
   a.omega = c->p.omega;
-  a.a1 = c->p.density * c->p.accel / 9.f;
-  a.a2 = c->p.density * c->p.accel / 36.f;
+  set_accel_weights(a, c->p);
   a.partials = sl.partials + (long)c->slot_fill * c->part_stride;
   a.slot_stride = c->part_stride;
   const TileShape& t = kTileShapes[c->tile_shape];
@@ -1261,27 +1282,57 @@ size_t resident_gran_bytes(const lbm_ctx* c) {
   return (2UL * c->resident_bands * 2 * c->p.nx + c->resident_bands) * sizeof(uint4);
 }
 
-// rec: the recorder compiled in -- kRecNone, kRecFrames (lbm_set_frames) or kRecProbes (lbm_set_probes)
-enum { kRecNone = 0, kRecFrames = 1, kRecProbes = 2 };
-const void* resident_kernel(int nx, int rows, int joint, int rec) {
-  if (rec == kRecProbes) {
-    if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, false, false, true>)
-                                     : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, false, false, true>);
-    if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, false, false, true>);
-    return joint ? reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, false, false, true>)
-                 : reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, false, false, true>);
+// The forms of lbm::resident_band, [batched][recorder compiled in] x the five shapes: MAXT 1024 / 512 with two-row
+// bands, MAXT 1024 with four-row bands, MAXT 512 with four-row bands relaxed jointly or not
+template <bool BATCH, int REC>
+const void* resident_form(int shape) {
+  constexpr bool F = (REC == kRecFrames), P = (REC == kRecProbes);
+  switch (shape) {
+    case 0: return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, BATCH, F, P>);
+    case 1: return reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, BATCH, F, P>);
+    case 2: return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, BATCH, F, P>);
+    case 3: return reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, BATCH, F, P>);
+    default: return reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, BATCH, F, P>);
   }
-  if (rec == kRecFrames) {
-    if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, false, true>)
-                                     : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, false, true>);
-    if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, false, true>);
-    return joint ? reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, false, true>)
-                 : reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, false, true>);
-  }
-  if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2>)
-                                   : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2>);
-  if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024>);
-  return joint ? reinterpret_cast<const void*>(lbm::resident_band<512, true>) : reinterpret_cast<const void*>(lbm::resident_band<512>);
+}
+const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = false) {
+  using Form = const void* (*)(int);
+  static const Form forms[2][3] = {
+      {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>},
+      {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>}};
+  return forms[batch][rec]((rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
+}
+
+// what the resident kernels read of a context's recorder (a batch keeps one such entry per member); all zero while that
+// kind is not armed
+lbm::ResidentFrames frames_entry(const lbm_ctx* c) {
+  if (c->rec.kind != kRecFrames) return {};
+  return {c->slab[0].frames, c->rec.every, c->rec.ord0, c->rec.slots};
+}
+lbm::ResidentProbes probes_entry(const lbm_ctx* c) {
+  if (c->rec.kind != kRecProbes) return {};
+  const Slab& s0 = c->slab[0];
+  return {s0.probe_ring, s0.probe_table, c->rec.every, c->rec.ord0, c->rec.slots, s0.probe_count, c->p.density, 0};
+}
+
+// the fields of ResidentArgs that plain and batched launches share: n timesteps from global step epoch0, last = the
+// call's last launch
+void fill_resident_args(lbm::ResidentArgs& a, const lbm_ctx* c, int n, bool last, int epoch0) {
+  a.plane_stride = c->plane_stride;
+  a.row_pitch = c->row_pitch;
+  a.pitch = c->pitch;
+  a.nx = c->p.nx;
+  a.ny = c->slab[0].rows;
+  a.n_steps = n;
+  a.accel_row = c->slab[0].accel_row;
+  a.accel_last = last ? 0 : 1;
+  a.gran_bytes = (unsigned)resident_gran_bytes(c);
+  a.xcd_affinity = env_int("LBM_RESIDENT_XCD", 1) ? 1 : 0;
+  a.epoch0 = (unsigned)epoch0;
+  a.timeout_ticks = c->resident_timeout;
+  a.absent_band = env_int("LBM_RESIDENT_ABSENT_BAND", -1);  // tests of the give-up path
+  a.group = c->resident_group;
+  a.one_xcd = c->resident_one_xcd;
 }
 
 // The timestep loop of a cache-resident single slab: launches of lbm::resident_band, each advancing up to
@@ -1290,45 +1341,30 @@ const void* resident_kernel(int nx, int rows, int joint, int rec) {
 int run_resident(lbm_ctx* c, int n_steps) {
   Slab& sl = c->slab[0];
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+  const bool probes = (c->rec.kind == kRecProbes);
   for (int t = 0; t < n_steps;) {
     const int n = (n_steps - t < kResidentChunk) ? n_steps - t : kResidentChunk;
-    lbm::ResidentFramesArgs fa;  // the FRAMES form's arguments: ResidentArgs + the frame fields
+    lbm::ResidentFramesArgs fa;  // the FRAMES form's arguments, ResidentArgs + the frame fields; the plain form reads its part
     lbm::ResidentProbesArgs pa;  // the PROBES form's: ResidentArgs + the probe fields
-    const int rec = c->probe_every > 0 ? kRecProbes : (c->frame_every > 0 ? kRecFrames : kRecNone);
-    lbm::ResidentArgs& a = (rec == kRecProbes) ? static_cast<lbm::ResidentArgs&>(pa) : fa;
-    fa.fr = {sl.frames, c->frame_every, c->frame_ord0, c->frame_slots};
-    pa.pr = {sl.probe_ring, sl.probe_table, c->probe_every, c->probe_ord0, c->probe_slots, sl.probe_count, c->p.density, 0};
+    lbm::ResidentArgs& a = probes ? static_cast<lbm::ResidentArgs&>(pa) : fa;
+    fa.fr = frames_entry(c);
+    pa.pr = probes_entry(c);
+    fill_resident_args(a, c, n, t + n == n_steps, c->steps_done + t);
     a.src = sl.lat[c->cur];
     a.dst = sl.lat[c->cur ^ 1];
     a.mask = sl.mask;
-    a.plane_stride = c->plane_stride;
-    a.row_pitch = c->row_pitch;
-    a.pitch = c->pitch;
-    a.nx = c->p.nx;
-    a.ny = sl.rows;
-    a.n_steps = n;
-    a.accel_row = sl.accel_row;
-    a.accel_last = (t + n < n_steps) ? 1 : 0;
     a.omega = c->p.omega;
-    a.a1 = c->p.density * c->p.accel / 9.f;
-    a.a2 = c->p.density * c->p.accel / 36.f;
+    set_accel_weights(a, c->p);
     a.gran = sl.res_gran;
-    a.gran_bytes = (unsigned)resident_gran_bytes(c);
-    a.xcd_affinity = env_int("LBM_RESIDENT_XCD", 1) ? 1 : 0;
-    a.epoch0 = (unsigned)(c->steps_done + t);
     a.partials = sl.res_part;
     a.status = sl.res_status;
-    a.timeout_ticks = c->resident_timeout;
-    a.absent_band = env_int("LBM_RESIDENT_ABSENT_BAND", -1);  // tests of the give-up path
 #ifdef LBM_RESIDENT_PROFILE
     static long long* prof_dev = nullptr;
     if (!prof_dev) HIP_TRY(LBM_FAILURE, hipMalloc(&prof_dev, 1024 * 8 * sizeof(long long)));
     a.prof = prof_dev;
 #endif
-    a.group = c->resident_group;
-    a.one_xcd = c->resident_one_xcd;
-    void* args[] = {(rec == kRecProbes) ? static_cast<void*>(&pa) : static_cast<void*>(&fa)};
-    HIP_TRY(LBM_FAILURE, hipLaunchKernel(resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, rec),
+    void* args[] = {probes ? static_cast<void*>(&pa) : static_cast<void*>(&fa)};
+    HIP_TRY(LBM_FAILURE, hipLaunchKernel(resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, c->rec.kind),
                                          dim3(c->resident_bands / a.group * (a.one_xcd ? 8 : 1)), dim3(c->p.nx * a.group), args, 0, sl.compute));
     hipLaunchKernelGGL(lbm::reduce_band_partials, dim3(n), dim3(64), 0, sl.compute, (const float*)sl.res_part,
                        c->resident_bands, sl.tot_u, c->steps_done + t);
@@ -1366,28 +1402,6 @@ int run_resident(lbm_ctx* c, int n_steps) {
   return LBM_SUCCESS;
 }
 
-const void* resident_kernel_batch(int nx, int rows, int joint, int rec) {
-  if (rec == kRecProbes) {
-    if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, true, false, true>)
-                                     : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, true, false, true>);
-    if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, true, false, true>);
-    return joint ? reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, true, false, true>)
-                 : reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, true, false, true>);
-  }
-  if (rec == kRecFrames) {
-    if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, true, true>)
-                                     : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, true, true>);
-    if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, true, true>);
-    return joint ? reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, true, true>)
-                 : reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, true, true>);
-  }
-  if (rows == 2) return (nx > 512) ? reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, true>)
-                                   : reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, true>);
-  if (nx > 512) return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, true>);
-  return joint ? reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, true>)
-               : reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, true>);
-}
-
 // run_resident for every member of a batch at once: the first step's accelerate_flow for all members, then per chunk
 // the sub-batch launches of the batched kernel and ONE reduce of every member's partials, all on the batch's stream
 int run_batch_resident(lbm_batch* bt, int n_steps) {
@@ -1399,8 +1413,8 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
                      (const lbm::ResidentMember*)(bt->table + bt->cur * n_members), c0->plane_stride, c0->row_pitch,
                      c0->pitch, c0->p.nx, sl0.accel_row);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
-  const int rec = bt->probes_armed > 0 ? kRecProbes : (bt->frames_armed > 0 ? kRecFrames : kRecNone);
-  const void* kernel = resident_kernel_batch(c0->p.nx, c0->resident_rows, c0->resident_joint, rec);
+  const int rec = bt->armed[kRecProbes] > 0 ? kRecProbes : (bt->armed[kRecFrames] > 0 ? kRecFrames : kRecNone);
+  const void* kernel = resident_kernel(c0->p.nx, c0->resident_rows, c0->resident_joint, rec, true);
   const int bands = c0->resident_bands;
   for (int t = 0; t < n_steps;) {
     const int n = (n_steps - t < kResidentChunk) ? n_steps - t : kResidentChunk;
@@ -1410,22 +1424,8 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
     memset(&fa, 0, sizeof(fa));
     memset(&pa, 0, sizeof(pa));
     lbm::ResidentBatchArgs& a = (rec == kRecProbes) ? static_cast<lbm::ResidentBatchArgs&>(pa) : fa;
-    a.plane_stride = c0->plane_stride;
-    a.row_pitch = c0->row_pitch;
-    a.pitch = c0->pitch;
-    a.nx = c0->p.nx;
-    a.ny = sl0.rows;
-    a.n_steps = n;
-    a.accel_row = sl0.accel_row;
-    a.accel_last = (t + n < n_steps) ? 1 : 0;
-    a.gran_bytes = (unsigned)resident_gran_bytes(c0);
-    a.xcd_affinity = env_int("LBM_RESIDENT_XCD", 1) ? 1 : 0;
-    a.epoch0 = (unsigned)(bt->steps_done + t);
+    fill_resident_args(a, c0, n, t + n == n_steps, bt->steps_done + t);
     a.status = bt->status;
-    a.timeout_ticks = c0->resident_timeout;
-    a.absent_band = env_int("LBM_RESIDENT_ABSENT_BAND", -1);
-    a.group = c0->resident_group;
-    a.one_xcd = c0->resident_one_xcd;
     a.member_wgs = bt->member_wgs;
     for (int first = 0; first < n_members; first += bt->members_per_launch) {
       a.members = tab + first;
@@ -1450,77 +1450,53 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
   return LBM_SUCCESS;
 }
 
-// frames recorded by the global steps [from, to): those with tt % frame_every == 0
-long long recorded_between(int every, long long from, long long to) {
-  if (every <= 0) return 0;
-  const long long e = every;
+// records made by the global steps [from, to): those with tt % every == 0
+long long recorded_between(const Recorder& r, long long from, long long to) {
+  if (r.every <= 0) return 0;
+  const long long e = r.every;
   return (to + e - 1) / e - (from + e - 1) / e;
 }
-long long frames_between(const lbm_ctx* c, long long from, long long to) { return recorded_between(c->frame_every, from, to); }
-// ... and the sample rows of the point probes
-long long probes_between(const lbm_ctx* c, long long from, long long to) { return recorded_between(c->probe_every, from, to); }
 
-// lbm_run / lbm_batch_run refuse a call whose frames would not fit the free slots, before any work is issued
-int frames_fit(const lbm_ctx* c, int n_steps, const char* who) {
-  const long long add = frames_between(c, c->steps_done, (long long)c->steps_done + n_steps);
-  const long long waiting = c->frames_written - c->frames_read;
-  if (waiting + add > c->frame_slots)
-    LBM_FAIL(LBM_FAILURE, "%s: %d steps would record %lld frames, but the frame buffer holds %d and %lld frames are waiting "
-             "(lbm_read_frames drains them)", who, n_steps, add, c->frame_slots, waiting);
+// lbm_run / lbm_batch_run refuse a call whose records would not fit the free slots, before any work is issued
+int recorder_fits(const lbm_ctx* c, int n_steps, const char* who) {
+  const Recorder& r = c->rec;
+  const RecorderKind& k = kRecorderKinds[r.kind];
+  const long long add = recorded_between(r, c->steps_done, (long long)c->steps_done + n_steps);
+  const long long waiting = r.written - r.read;
+  if (waiting + add > r.slots)
+    LBM_FAIL(LBM_FAILURE, "%s: %d steps would record %lld %ss, but the %s buffer holds %d and %lld %ss are waiting (%s drains them)",
+             who, n_steps, add, k.record, k.record, r.slots, waiting, k.record, k.reader);
   return LBM_SUCCESS;
 }
 
-// the same for the sample rows of the point probes and their ring
-int probes_fit(const lbm_ctx* c, int n_steps, const char* who) {
-  const long long add = probes_between(c, c->steps_done, (long long)c->steps_done + n_steps);
-  const long long waiting = c->probes_written - c->probes_read;
-  if (waiting + add > c->probe_slots)
-    LBM_FAIL(LBM_FAILURE, "%s: %d steps would record %lld probe samples, but the probe ring holds %d and %lld samples are waiting "
-             "(lbm_read_probes drains them)", who, n_steps, add, c->probe_slots, waiting);
-  return LBM_SUCCESS;
-}
-
-// the sample row of the current (stored) lattice: every slab gathers the probes in its rows, on its compute stream
-int take_probes(lbm_ctx* c) {
+// the record of the current (stored) lattice into the next slot, on every slab's compute stream: the frame of its rows,
+// or the gathered samples of the probes in its rows
+int take_record(lbm_ctx* c) {
+  const size_t slot = (size_t)(c->rec.written % c->rec.slots);
   const size_t n_probes = c->probe_cells.size();
-  const size_t slot = (size_t)(c->probes_written % c->probe_slots);
-  if (for_slabs(c, [&](int s) -> int {
-        Slab& sl = c->slab[s];
-        if (sl.probe_count == 0) return LBM_SUCCESS;
-        HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-        hipLaunchKernelGGL(lbm::probe_gather, dim3(ceil_div(sl.probe_count, 64)), dim3(64), 0, sl.compute,
-                           (const float*)sl.lat[c->cur], (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch,
-                           c->p.density, (const lbm::ProbeEntry*)sl.probe_table, sl.probe_count, sl.probe_ring + slot * n_probes);
-        HIP_TRY(LBM_FAILURE, hipGetLastError());
-        return LBM_SUCCESS;
-      }) != LBM_SUCCESS)
-    return LBM_FAILURE;
-  c->probes_written++;
-  return LBM_SUCCESS;
-}
-
-// the frame of the current (stored) lattice, on every slab's compute stream, into the next slot
-int take_frame(lbm_ctx* c) {
-  const long slot = (long)(c->frames_written % c->frame_slots);
   if (for_slabs(c, [&](int s) -> int {
         Slab& sl = c->slab[s];
         HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
         const long n = (long)sl.rows * c->p.nx;
-        hipLaunchKernelGGL(lbm::frame_umag, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, (const float*)sl.lat[c->cur],
-                           (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx, sl.rows,
-                           sl.frames + slot * n);
+        if (c->rec.kind == kRecFrames)
+          hipLaunchKernelGGL(lbm::frame_umag, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, (const float*)sl.lat[c->cur],
+                             (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx, sl.rows,
+                             sl.frames + slot * n);
+        else if (sl.probe_count > 0)
+          hipLaunchKernelGGL(lbm::probe_gather, dim3(ceil_div(sl.probe_count, 64)), dim3(64), 0, sl.compute,
+                             (const float*)sl.lat[c->cur], (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch,
+                             c->p.density, (const lbm::ProbeEntry*)sl.probe_table, sl.probe_count, sl.probe_ring + slot * n_probes);
         HIP_TRY(LBM_FAILURE, hipGetLastError());
         return LBM_SUCCESS;
       }) != LBM_SUCCESS)
     return LBM_FAILURE;
-  c->frames_written++;
+  c->rec.written++;
   return LBM_SUCCESS;
 }
 
 // n_steps timesteps on the kernels chosen by `resident` (no timing read-out: the caller does it)
 int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
-  const float a1 = c->p.density * c->p.accel / 9.f;
-  const float a2 = c->p.density * c->p.accel / 36.f;
+  const AccelWeights w = accel_weights(c->p);
   const bool halo = (c->halo != HALO_SELF);
   HotGuard hot_guard(c->team);
 
@@ -1531,7 +1507,7 @@ int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
         if (sl.accel_row >= 0 && sl.accel_row < sl.rows) {
           hipLaunchKernelGGL(lbm::accelerate_row, dim3(ceil_div(c->p.nx, 256)), dim3(256), 0, sl.compute,
                              sl.lat[c->cur], sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx,
-                             sl.accel_row, a1, a2);
+                             sl.accel_row, w.a1, w.a2);
           HIP_TRY(LBM_FAILURE, hipGetLastError());
         }
         if (record_t0) HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_t0, sl.compute));
@@ -1540,12 +1516,10 @@ int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
     return LBM_FAILURE;
 
   if (resident) {
-    const long long frames = frames_between(c, c->steps_done, (long long)c->steps_done + n_steps);
-    const long long samples = probes_between(c, c->steps_done, (long long)c->steps_done + n_steps);
+    const long long records = recorded_between(c->rec, c->steps_done, (long long)c->steps_done + n_steps);
     if (run_resident(c, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
     c->steps_done += n_steps;
-    c->frames_written += frames;  // recorded by the kernel itself
-    c->probes_written += samples;
+    c->rec.written += records;  // recorded by the kernel itself
     return LBM_SUCCESS;
   }
 
@@ -1597,23 +1571,21 @@ int run_steps(lbm_ctx* c, int n_steps, float* kernel_ms) {
   if (c->steps_done + n_steps > c->capacity)
     LBM_FAIL(LBM_FAILURE, "lbm_run: %d steps requested but the av_vels record holds %d (maxIters)",
              c->steps_done + n_steps, c->capacity);
-  if (frames_fit(c, n_steps, "lbm_run") != LBM_SUCCESS) return LBM_FAILURE;
-  if (probes_fit(c, n_steps, "lbm_run") != LBM_SUCCESS) return LBM_FAILURE;
+  if (recorder_fits(c, n_steps, "lbm_run") != LBM_SUCCESS) return LBM_FAILURE;
   if (c->halo != HALO_SELF && c->halo_mode != LBM_HALO_SYNC) return run_steps_stale(c, n_steps, kernel_ms);
 
   // resident or per-pass: decided once per call, whether a recorder (frames or probes) is armed or not
   const bool resident = c->resident && n_steps >= c->resident_min_steps;
-  if ((c->frame_every > 0 || c->probe_every > 0) && !resident) {
+  if (c->rec.kind != kRecNone && !resident) {
     // per-pass kernels: the call runs as the sub-calls that end at its recorder steps, each followed by its frame or
     // its sample row (the step kernels themselves record nothing)
-    const bool probes = c->probe_every > 0;
-    const int e = probes ? c->probe_every : c->frame_every;
+    const int e = c->rec.every;
     for (int t = 0; t < n_steps;) {
       const int tt = c->steps_done, r = tt % e;
       const long long rec_tt = r ? (long long)tt + (e - r) : tt;  // next recorder step
       const int seg = (rec_tt - tt + 1 < n_steps - t) ? (int)(rec_tt - tt + 1) : n_steps - t;
       if (run_passes(c, seg, false, kernel_ms && t == 0) != LBM_SUCCESS) return LBM_FAILURE;
-      if (c->steps_done - 1 == rec_tt && (probes ? take_probes(c) : take_frame(c)) != LBM_SUCCESS) return LBM_FAILURE;
+      if (c->steps_done - 1 == rec_tt && take_record(c) != LBM_SUCCESS) return LBM_FAILURE;
       t += seg;
     }
   } else if (run_passes(c, n_steps, resident, kernel_ms != nullptr) != LBM_SUCCESS) {
@@ -1756,8 +1728,7 @@ int fresh_exchange(lbm_ctx* c, int src, int par, unsigned id) {
 // boundary rows.  Every halo row is the row of this pass or of the pass before -- never older, never torn -- and
 // given the log of decisions the run is reproducible (tests/slab_model.py: run_slabs_freshest).
 int run_steps_stale(lbm_ctx* c, int n_steps, float* kernel_ms) {
-  const float a1 = c->p.density * c->p.accel / 9.f;
-  const float a2 = c->p.density * c->p.accel / 36.f;
+  const AccelWeights w = accel_weights(c->p);
   const int depth = 1;  // one timestep per pass (see above): only the adjacent row is read
   const bool freshest = (c->halo_mode == LBM_HALO_FRESHEST);
   // tests: "wait" makes every look find its rows (= the synchronous run), "never" sends none (= the stale mode)
@@ -1775,7 +1746,7 @@ int run_steps_stale(lbm_ctx* c, int n_steps, float* kernel_ms) {
         if (sl.accel_row >= 0 && sl.accel_row < sl.rows) {
           hipLaunchKernelGGL(lbm::accelerate_row, dim3(ceil_div(c->p.nx, 256)), dim3(256), 0, sl.compute,
                              sl.lat[c->cur], sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx,
-                             sl.accel_row, a1, a2);
+                             sl.accel_row, w.a1, w.a2);
           HIP_TRY(LBM_FAILURE, hipGetLastError());
         }
         HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_step, sl.compute));
@@ -2391,7 +2362,7 @@ lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, con
     if (shape_ok && env_int("LBM_RESIDENT", other_kernel ? 0 : 1)) {
       int per_cu = 0;
       const int joint = (rows == 4 && nx <= 512 && env_int("LBM_RESIDENT_JOINT", nx <= 256 ? 1 : 0)) ? 1 : 0;
-      if (cus > 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resident_kernel(nx, rows, joint, false), nx, 0) == hipSuccess &&
+      if (cus > 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resident_kernel(nx, rows, joint, kRecNone), nx, 0) == hipSuccess &&
           per_cu >= 1 && ny / rows <= cus) {
         c->resident = 1;
         c->resident_rows = rows;
@@ -2518,6 +2489,132 @@ lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, con
     c->team->start(n_slabs);
   }
   return c;
+}
+
+// ---- the recorder: what lbm_set_frames / lbm_set_probes and their readers share ----------------------------------
+// a batch member's entry of the table the batched launches of one kind read; the table is allocated, all zero, when the
+// first member arms that kind
+template <class Entry>
+int set_batch_entry(lbm_ctx* c, Entry*& table, const Entry& entry) {
+  const lbm_batch* bt = c->batch;
+  if (!table && entry.every == 0) return LBM_SUCCESS;
+  int index = 0;
+  while (bt->members[(size_t)index] != c) index++;
+  HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
+  if (!table) {
+    HIP_TRY(LBM_FAILURE, hipMalloc(&table, bt->members.size() * sizeof(Entry)));
+    HIP_TRY(LBM_FAILURE, hipMemset(table, 0, bt->members.size() * sizeof(Entry)));
+  }
+  HIP_TRY(LBM_FAILURE, hipMemcpy(table + index, &entry, sizeof(entry), hipMemcpyHostToDevice));
+  return LBM_SUCCESS;
+}
+int write_batch_entry(lbm_ctx* c, int kind) {
+  if (!c->batch) return LBM_SUCCESS;
+  return (kind == kRecFrames) ? set_batch_entry(c, c->batch->frame_table, frames_entry(c))
+                              : set_batch_entry(c, c->batch->probe_table, probes_entry(c));
+}
+
+// frees the record buffers of every slab and leaves the recorder off
+void release_recorder(lbm_ctx* c) {
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    (void)hipSetDevice(sl.device);
+    if (sl.frames) (void)hipFree(sl.frames);
+    if (sl.probe_ring) (void)hipFree(sl.probe_ring);
+    if (sl.probe_table) (void)hipFree(sl.probe_table);
+    sl.frames = nullptr;
+    sl.probe_ring = nullptr;
+    sl.probe_table = nullptr;
+    sl.probe_count = 0;
+  }
+  c->probe_cells.clear();
+  c->rec = Recorder{};
+}
+
+// What lbm_set_frames and lbm_set_probes share behind their own argument checks.  Arming (every > 0) is refused, with
+// nothing touched, where this kind cannot record.  Then the launches in flight are awaited and a recorder of this kind is
+// disarmed; to arm, allocate() provides the kind's buffers of every slab (and says what it could not) before the
+// recorder's fields, the member's batch entry and the batch's count of armed members are set.
+template <class Allocate>
+int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate allocate) {
+  const RecorderKind& k = kRecorderKinds[kind];
+  lbm_batch* bt = c->batch;
+  if (every > 0) {
+    const int other = kRecFrames + kRecProbes - kind;
+    const RecorderKind& o = kRecorderKinds[other];
+    if (c->halo_mode != LBM_HALO_SYNC)
+      LBM_FAIL(LBM_FAILURE, "%s: the context runs the %s halo mode, where splitting a call at a %s would change the results "
+               "(every call starts from freshly exchanged halos); %s need LBM_HALO_SYNC", k.setter,
+               c->halo_mode == LBM_HALO_STALE ? "stale" : "freshest", k.record, k.noun);
+    if (c->rec.kind == other)
+      LBM_FAIL(LBM_FAILURE, "%s: %s are armed (%s) and a context has one recorder -- disarm them with %s first", k.setter, o.name,
+               o.setter, o.disarm);
+    if (bt && bt->armed[other] > 0)
+      LBM_FAIL(LBM_FAILURE, "%s: a member of this batch has %s armed (%s); a batch records one kind, frames or probes", k.setter,
+               o.name, o.setter);
+    if (c->resident) {
+      // the recorder forms of four-row bands defer the acceleration of the interior pair only (lbm::resident_band): the lid
+      // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form must run one workgroup per CU
+      if (c->resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
+        LBM_FAIL(LBM_FAILURE, "%s: the lid row %d is not an interior row of a four-row band", k.setter, c->slab[0].accel_row);
+      int per_cu = 0;
+      HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
+      HIP_TRY(LBM_FAILURE, hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                               &per_cu, resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, kind), c->p.nx * c->resident_group, 0));
+      if (per_cu < 1) LBM_FAIL(LBM_FAILURE, "%s: the resident kernel's %s form does not fit a CU at this shape", k.setter, k.noun);
+    }
+  }
+  // the buffers may still be written by launches in flight
+  for (int s = 0; s < c->n_slabs; s++) {
+    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
+    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
+  }
+  if (c->rec.kind == kind) {
+    if (bt) bt->armed[kind]--;
+    release_recorder(c);
+    if (write_batch_entry(c, kind) != LBM_SUCCESS) return LBM_FAILURE;
+  }
+  if (every <= 0) return LBM_SUCCESS;
+  if (allocate() != LBM_SUCCESS) {
+    (void)hipGetLastError();  // a failed allocation must not surface at the next launch
+    release_recorder(c);
+    return LBM_FAILURE;
+  }
+  c->rec.kind = kind;
+  c->rec.every = every;
+  c->rec.slots = capacity;
+  c->rec.ord0 = (int)(((long long)c->steps_done + every - 1) / every);
+  if (write_batch_entry(c, kind) != LBM_SUCCESS) {
+    release_recorder(c);
+    return LBM_FAILURE;
+  }
+  if (bt) bt->armed[kind]++;
+  return LBM_SUCCESS;
+}
+
+// What lbm_read_frames and lbm_read_probes share: the work in flight is awaited; without outputs the call tells how many
+// records wait; else copy(n) fetches the n oldest (at most max_records) before their steps are told and they are retired.
+template <class Copy>
+int drain_recorder(lbm_ctx* c, int kind, int max_records, bool has_out, int* steps, int* n_read, Copy copy) {
+  const RecorderKind& k = kRecorderKinds[kind];
+  if (!c || !n_read) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", k.reader);
+  *n_read = 0;
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
+  Recorder& r = c->rec;
+  const long long waiting = (r.kind == kind) ? r.written - r.read : 0;
+  if (!has_out && !steps) {
+    *n_read = (int)waiting;
+    return LBM_SUCCESS;
+  }
+  if (!has_out) LBM_FAIL(LBM_FAILURE, "%s: NULL %s output", k.reader, k.record);
+  if (max_records < 0) LBM_FAIL(LBM_FAILURE, "%s: negative max_%ss %d", k.reader, k.record, max_records);
+  const int n = (waiting < max_records) ? (int)waiting : max_records;
+  if (n > 0 && copy(n) != LBM_SUCCESS) return LBM_FAILURE;
+  if (steps)
+    for (int i = 0; i < n; i++) steps[i] = (int)((r.ord0 + r.read + i) * r.every);
+  r.read += n;
+  *n_read = n;
+  return LBM_SUCCESS;
 }
 
 }  // namespace
@@ -2746,12 +2843,11 @@ int lbm_set_halo_mode(lbm_ctx* c, int mode) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: null context");
   if (mode != LBM_HALO_SYNC && mode != LBM_HALO_STALE && mode != LBM_HALO_FRESHEST) LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: unknown mode %d", mode);
   if (mode == LBM_HALO_FRESHEST && c->halo == HALO_HOST) LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: the freshest-available mode is not available with the hosted exchange");
-  if (mode != LBM_HALO_SYNC && c->frame_every > 0)
-    LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: animation frames are armed (lbm_set_frames); the stale and freshest halo modes "
-             "cannot record them -- disarm with lbm_set_frames(ctx, 0, 0) first");
-  if (mode != LBM_HALO_SYNC && c->probe_every > 0)
-    LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: point probes are armed (lbm_set_probes); the stale and freshest halo modes "
-             "cannot record them -- disarm with lbm_set_probes(ctx, 0, NULL, 0, 0) first");
+  if (mode != LBM_HALO_SYNC && c->rec.kind != kRecNone) {
+    const RecorderKind& k = kRecorderKinds[c->rec.kind];
+    LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: %s are armed (%s); the stale and freshest halo modes cannot record them -- "
+             "disarm with %s first", k.name, k.setter, k.disarm);
+  }
   c->halo_mode = mode;
   return LBM_SUCCESS;
 }
@@ -2760,117 +2856,38 @@ int lbm_set_frames(lbm_ctx* c, int every, int capacity) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_frames: null context");
   if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_frames: negative interval %d", every);
   if (every > 0 && capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_frames: capacity %d, at least one frame slot is needed", capacity);
-  if (every > 0 && c->halo_mode != LBM_HALO_SYNC)
-    LBM_FAIL(LBM_FAILURE, "lbm_set_frames: the context runs the %s halo mode, where splitting a call at a frame would change "
-             "the results (every call starts from freshly exchanged halos); frames need LBM_HALO_SYNC",
-             c->halo_mode == LBM_HALO_STALE ? "stale" : "freshest");
-  if (every > 0 && c->probe_every > 0)
-    LBM_FAIL(LBM_FAILURE, "lbm_set_frames: point probes are armed (lbm_set_probes) and a context has one recorder -- disarm them "
-             "with lbm_set_probes(ctx, 0, NULL, 0, 0) first");
-  if (every > 0 && c->batch && c->batch->probes_armed > 0)
-    LBM_FAIL(LBM_FAILURE, "lbm_set_frames: a member of this batch has point probes armed (lbm_set_probes); a batch records one "
-             "kind, frames or probes");
-  if (every > 0 && c->resident) {
-    // the FRAMES form of four-row bands defers the acceleration of the interior pair only (lbm::resident_band): the lid
-    // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form must run one workgroup per CU
-    if (c->resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_frames: the lid row %d is not an interior row of a four-row band", c->slab[0].accel_row);
-    int per_cu = 0;
-    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
-    HIP_TRY(LBM_FAILURE, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                             &per_cu, resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, kRecFrames), c->p.nx * c->resident_group, 0));
-    if (per_cu < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_frames: the resident kernel's frame form does not fit a CU at this shape");
-  }
-  // the buffers may still be written by launches in flight
-  for (int s = 0; s < c->n_slabs; s++) {
-    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
-    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
-  }
-  for (int s = 0; s < c->n_slabs; s++) {
-    Slab& sl = c->slab[s];
-    if (sl.frames) {
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      HIP_TRY(LBM_FAILURE, hipFree(sl.frames));
-      sl.frames = nullptr;
-    }
-  }
-  lbm_batch* bt = c->batch;
-  // a batch member's entry of the table the batched launches read
-  auto set_entry = [&](const lbm::ResidentFrames& entry) -> int {
-    if (!bt) return LBM_SUCCESS;
-    int index = 0;
-    while (bt->members[(size_t)index] != c) index++;
-    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
-    if (!bt->frame_table) {
-      HIP_TRY(LBM_FAILURE, hipMalloc(&bt->frame_table, bt->members.size() * sizeof(lbm::ResidentFrames)));
-      HIP_TRY(LBM_FAILURE, hipMemset(bt->frame_table, 0, bt->members.size() * sizeof(lbm::ResidentFrames)));
-    }
-    HIP_TRY(LBM_FAILURE, hipMemcpy(bt->frame_table + index, &entry, sizeof(entry), hipMemcpyHostToDevice));
-    return LBM_SUCCESS;
-  };
-  if (bt && c->frame_every > 0) bt->frames_armed--;
-  c->frame_every = c->frame_slots = c->frame_ord0 = 0;
-  c->frames_written = c->frames_read = 0;
-  if (set_entry({nullptr, 0, 0, 0}) != LBM_SUCCESS) return LBM_FAILURE;
-  if (every > 0) {
+  return rearm_recorder(c, kRecFrames, every, capacity, [&]() -> int {
     for (int s = 0; s < c->n_slabs; s++) {
       Slab& sl = c->slab[s];
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
       const size_t bytes = (size_t)capacity * (size_t)sl.rows * (size_t)c->p.nx * sizeof(float);
-      if (hipMalloc(&sl.frames, bytes) != hipSuccess) {
-        (void)hipGetLastError();  // a failed allocation must not surface at the next launch
-        for (int q = 0; q <= s; q++)
-          if (c->slab[q].frames) { (void)hipSetDevice(c->slab[q].device); (void)hipFree(c->slab[q].frames); c->slab[q].frames = nullptr; }
+      if (hipMalloc(&sl.frames, bytes) != hipSuccess)
         LBM_FAIL(LBM_FAILURE, "lbm_set_frames: cannot allocate %d frame slots (%.1f MiB per slab); frames stay off", capacity,
                  (double)bytes / 1048576.0);
-      }
     }
-    c->frame_every = every;
-    c->frame_slots = capacity;
-    c->frame_ord0 = (int)(((long long)c->steps_done + every - 1) / every);
-    if (set_entry({c->slab[0].frames, every, c->frame_ord0, capacity}) != LBM_SUCCESS) {
-      (void)hipFree(c->slab[0].frames);
-      c->slab[0].frames = nullptr;
-      c->frame_every = c->frame_slots = c->frame_ord0 = 0;
-      return LBM_FAILURE;
-    }
-    if (bt) bt->frames_armed++;
-  }
-  return LBM_SUCCESS;
+    return LBM_SUCCESS;
+  });
 }
 
 int lbm_read_frames(lbm_ctx* c, int max_frames, float* out, int* steps, int* n_read) {
-  if (!c || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_read_frames: NULL argument");
-  *n_read = 0;
-  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
-  const long long waiting = c->frames_written - c->frames_read;
-  if (!out && !steps) {
-    *n_read = (int)waiting;
-    return LBM_SUCCESS;
-  }
-  if (!out) LBM_FAIL(LBM_FAILURE, "lbm_read_frames: NULL frame output");
-  if (max_frames < 0) LBM_FAIL(LBM_FAILURE, "lbm_read_frames: negative max_frames %d", max_frames);
-  const int n = (waiting < max_frames) ? (int)waiting : max_frames;
-  const size_t frame_cells = (size_t)c->row_count * c->p.nx;
-  for (int i = 0; i < n; i++) {
-    const long long ord = c->frames_read + i;
-    const size_t slot = (size_t)(ord % c->frame_slots);
-    for (int s = 0; s < c->n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      const size_t cells = (size_t)sl.rows * c->p.nx;
-      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(out + i * frame_cells + (size_t)(sl.row_first - c->row_first) * c->p.nx,
-                                          sl.frames + slot * cells, cells * sizeof(float), hipMemcpyDeviceToHost, sl.compute));
+  return drain_recorder(c, kRecFrames, max_frames, out != nullptr, steps, n_read, [&](int n) -> int {
+    const size_t frame_cells = (size_t)c->row_count * c->p.nx;
+    for (int i = 0; i < n; i++) {
+      const size_t slot = (size_t)((c->rec.read + i) % c->rec.slots);
+      for (int s = 0; s < c->n_slabs; s++) {
+        Slab& sl = c->slab[s];
+        HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+        const size_t cells = (size_t)sl.rows * c->p.nx;
+        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(out + i * frame_cells + (size_t)(sl.row_first - c->row_first) * c->p.nx,
+                                            sl.frames + slot * cells, cells * sizeof(float), hipMemcpyDeviceToHost, sl.compute));
+      }
     }
-    if (steps) steps[i] = (int)((c->frame_ord0 + ord) * c->frame_every);
-  }
-  for (int s = 0; s < c->n_slabs; s++) {
-    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
-    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
-  }
-  c->frames_read += n;
-  *n_read = n;
-  return LBM_SUCCESS;
+    for (int s = 0; s < c->n_slabs; s++) {
+      HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
+    }
+    return LBM_SUCCESS;
+  });
 }
 
 int lbm_set_probes(lbm_ctx* c, int n_probes, const lbm_probe* cells, int every, int capacity) {
@@ -2890,154 +2907,74 @@ int lbm_set_probes(lbm_ctx* c, int n_probes, const lbm_probe* cells, int every, 
                  c->p.nx, c->p.ny);
     if (c->ranked || c->world > 1)
       LBM_FAIL(LBM_FAILURE, "lbm_set_probes: not available in a multi-process (rank) context: a row of samples would be spread over the ranks");
-    if (c->halo_mode != LBM_HALO_SYNC)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_probes: the context runs the %s halo mode, where splitting a call at a sample step would change "
-               "the results (every call starts from freshly exchanged halos); probes need LBM_HALO_SYNC",
-               c->halo_mode == LBM_HALO_STALE ? "stale" : "freshest");
-    if (c->frame_every > 0)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_probes: animation frames are armed (lbm_set_frames) and a context has one recorder -- disarm "
-               "them with lbm_set_frames(ctx, 0, 0) first");
-    if (c->batch && c->batch->frames_armed > 0)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_probes: a member of this batch has animation frames armed (lbm_set_frames); a batch records one "
-               "kind, frames or probes");
-    if (c->resident) {
-      // as lbm_set_frames: four-row bands defer the lid's acceleration in the interior pair only, and the form must fit a CU
-      if (c->resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
-        LBM_FAIL(LBM_FAILURE, "lbm_set_probes: the lid row %d is not an interior row of a four-row band", c->slab[0].accel_row);
-      int per_cu = 0;
-      HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
-      HIP_TRY(LBM_FAILURE, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                               &per_cu, resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, kRecProbes), c->p.nx * c->resident_group, 0));
-      if (per_cu < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_probes: the resident kernel's probes form does not fit a CU at this shape");
-    }
   }
-  // the buffers may still be written by launches in flight
-  for (int s = 0; s < c->n_slabs; s++) {
-    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
-    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
-  }
-  auto release = [&]() {
+  return rearm_recorder(c, kRecProbes, arm ? every : 0, capacity, [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * (size_t)n_probes * sizeof(lbm::probe_vec);
     for (int s = 0; s < c->n_slabs; s++) {
       Slab& sl = c->slab[s];
-      (void)hipSetDevice(sl.device);
-      if (sl.probe_ring) (void)hipFree(sl.probe_ring);
-      if (sl.probe_table) (void)hipFree(sl.probe_table);
-      sl.probe_ring = nullptr;
-      sl.probe_table = nullptr;
-      sl.probe_count = 0;
-    }
-    c->probe_cells.clear();
-    c->probe_every = c->probe_slots = c->probe_ord0 = 0;
-    c->probes_written = c->probes_read = 0;
-  };
-  lbm_batch* bt = c->batch;
-  // a batch member's entry of the table the batched launches read
-  auto set_entry = [&](const lbm::ResidentProbes& entry) -> int {
-    if (!bt || (!bt->probe_table && !entry.ring)) return LBM_SUCCESS;
-    int index = 0;
-    while (bt->members[(size_t)index] != c) index++;
-    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
-    if (!bt->probe_table) {
-      HIP_TRY(LBM_FAILURE, hipMalloc(&bt->probe_table, bt->members.size() * sizeof(lbm::ResidentProbes)));
-      HIP_TRY(LBM_FAILURE, hipMemset(bt->probe_table, 0, bt->members.size() * sizeof(lbm::ResidentProbes)));
-    }
-    HIP_TRY(LBM_FAILURE, hipMemcpy(bt->probe_table + index, &entry, sizeof(entry), hipMemcpyHostToDevice));
-    return LBM_SUCCESS;
-  };
-  if (bt && c->probe_every > 0) bt->probes_armed--;
-  release();
-  if (set_entry(lbm::ResidentProbes{}) != LBM_SUCCESS) return LBM_FAILURE;
-  if (!arm) return LBM_SUCCESS;
-
-  const size_t ring_bytes = (size_t)capacity * (size_t)n_probes * sizeof(lbm::probe_vec);
-  for (int s = 0; s < c->n_slabs; s++) {
-    Slab& sl = c->slab[s];
-    // this slab's probes sorted by row (stable: ties keep the caller's order), then, where the resident kernel runs, the
-    // word of every band: first entry | entries << 12 | (a probe on the lid row) << 31
-    std::vector<int> mine;
-    for (int i = 0; i < n_probes; i++)
-      if (cells[i].y >= sl.row_first && cells[i].y < sl.row_first + sl.rows) mine.push_back(i);
-    std::stable_sort(mine.begin(), mine.end(), [&](int p, int q) { return cells[p].y < cells[q].y; });
-    const int bands = c->resident ? c->resident_bands : 0;
-    std::vector<unsigned> words(2 * mine.size() + (size_t)bands, 0u);
-    for (size_t j = 0; j < mine.size(); j++) {
-      const int row = cells[mine[j]].y - sl.row_first;
-      words[2 * j] = (unsigned)row;
-      words[2 * j + 1] = (unsigned)cells[mine[j]].x | ((unsigned)mine[j] << 20);
-      if (bands) {
-        unsigned& w = words[2 * mine.size() + (size_t)(row / c->resident_rows)];
-        if (((w >> 12) & 0xfffu) == 0) w |= (unsigned)j;
-        w += 1u << 12;
-        if (row == sl.accel_row) w |= 1u << 31;
+      // this slab's probes sorted by row (stable: ties keep the caller's order), then, where the resident kernel runs, the
+      // word of every band: first entry | entries << 12 | (a probe on the lid row) << 31
+      std::vector<int> mine;
+      for (int i = 0; i < n_probes; i++)
+        if (cells[i].y >= sl.row_first && cells[i].y < sl.row_first + sl.rows) mine.push_back(i);
+      std::stable_sort(mine.begin(), mine.end(), [&](int p, int q) { return cells[p].y < cells[q].y; });
+      const int bands = c->resident ? c->resident_bands : 0;
+      std::vector<unsigned> words(2 * mine.size() + (size_t)bands, 0u);
+      for (size_t j = 0; j < mine.size(); j++) {
+        const int row = cells[mine[j]].y - sl.row_first;
+        words[2 * j] = (unsigned)row;
+        words[2 * j + 1] = (unsigned)cells[mine[j]].x | ((unsigned)mine[j] << 20);
+        if (bands) {
+          unsigned& w = words[2 * mine.size() + (size_t)(row / c->resident_rows)];
+          if (((w >> 12) & 0xfffu) == 0) w |= (unsigned)j;
+          w += 1u << 12;
+          if (row == sl.accel_row) w |= 1u << 31;
+        }
       }
+      static_assert(sizeof(lbm::ProbeEntry) == 2 * sizeof(unsigned), "a table entry is two words");
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      if (hipMalloc(&sl.probe_ring, ring_bytes) != hipSuccess ||
+          hipMalloc(&sl.probe_table, (words.size() + 2) * sizeof(unsigned)) != hipSuccess ||
+          hipMemset(sl.probe_ring, 0, ring_bytes) != hipSuccess ||
+          (!words.empty() && hipMemcpy(sl.probe_table, words.data(), words.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess))
+        LBM_FAIL(LBM_FAILURE, "lbm_set_probes: cannot allocate %d rows of %d samples (%.1f MiB per slab); probes stay off", capacity,
+                 n_probes, (double)ring_bytes / 1048576.0);
+      sl.probe_count = (int)mine.size();
     }
-    static_assert(sizeof(lbm::ProbeEntry) == 2 * sizeof(unsigned), "a table entry is two words");
-    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-    if (hipMalloc(&sl.probe_ring, ring_bytes) != hipSuccess ||
-        hipMalloc(&sl.probe_table, (words.size() + 2) * sizeof(unsigned)) != hipSuccess ||
-        hipMemset(sl.probe_ring, 0, ring_bytes) != hipSuccess ||
-        (!words.empty() && hipMemcpy(sl.probe_table, words.data(), words.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess)) {
-      (void)hipGetLastError();  // a failed allocation must not surface at the next launch
-      release();
-      LBM_FAIL(LBM_FAILURE, "lbm_set_probes: cannot allocate %d rows of %d samples (%.1f MiB per slab); probes stay off", capacity,
-               n_probes, (double)ring_bytes / 1048576.0);
-    }
-    sl.probe_count = (int)mine.size();
-  }
-  c->probe_cells.assign(cells, cells + n_probes);
-  c->probe_every = every;
-  c->probe_slots = capacity;
-  c->probe_ord0 = (int)(((long long)c->steps_done + every - 1) / every);
-  const Slab& s0 = c->slab[0];
-  if (set_entry({s0.probe_ring, s0.probe_table, every, c->probe_ord0, capacity, s0.probe_count, c->p.density, 0}) != LBM_SUCCESS) {
-    release();
-    return LBM_FAILURE;
-  }
-  if (bt) bt->probes_armed++;
-  return LBM_SUCCESS;
+    c->probe_cells.assign(cells, cells + n_probes);
+    return LBM_SUCCESS;
+  });
 }
 
 int lbm_read_probes(lbm_ctx* c, int max_samples, lbm_probe_sample* out, int* steps, int* n_read) {
-  if (!c || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_read_probes: NULL argument");
-  *n_read = 0;
-  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
-  const long long waiting = c->probes_written - c->probes_read;
-  if (!out && !steps) {
-    *n_read = (int)waiting;
-    return LBM_SUCCESS;
-  }
-  if (!out) LBM_FAIL(LBM_FAILURE, "lbm_read_probes: NULL sample output");
-  if (max_samples < 0) LBM_FAIL(LBM_FAILURE, "lbm_read_probes: negative max_samples %d", max_samples);
-  const int n = (waiting < max_samples) ? (int)waiting : max_samples;
-  const size_t np = c->probe_cells.size();
-  static_assert(sizeof(lbm_probe_sample) == sizeof(lbm::probe_vec), "a sample is one 16-byte store");
-  // the rows wait in at most two runs of the ring; one slab: straight into out, several: each slab's columns of a staged copy
-  std::vector<lbm_probe_sample> stage(c->n_slabs > 1 ? (size_t)n * np : 0);
-  for (int s = 0; s < c->n_slabs; s++) {
-    Slab& sl = c->slab[s];
-    if (sl.probe_count == 0 && c->n_slabs > 1) continue;
-    lbm_probe_sample* dst = c->n_slabs > 1 ? stage.data() : out;
-    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-    for (int i = 0; i < n;) {
-      const size_t slot = (size_t)((c->probes_read + i) % c->probe_slots);
-      const int run = ((size_t)(n - i) < (size_t)c->probe_slots - slot) ? n - i : (int)((size_t)c->probe_slots - slot);
-      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(dst + (size_t)i * np, sl.probe_ring + slot * np, (size_t)run * np * sizeof(lbm_probe_sample),
-                                          hipMemcpyDeviceToHost, sl.compute));
-      i += run;
-    }
-    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
-    if (c->n_slabs > 1)
-      for (size_t p = 0; p < np; p++) {
-        const int y = c->probe_cells[p].y;
-        if (y < sl.row_first || y >= sl.row_first + sl.rows) continue;
-        for (int i = 0; i < n; i++) out[(size_t)i * np + p] = stage[(size_t)i * np + p];
+  return drain_recorder(c, kRecProbes, max_samples, out != nullptr, steps, n_read, [&](int n) -> int {
+    const size_t np = c->probe_cells.size();
+    const size_t slots = (size_t)c->rec.slots;
+    static_assert(sizeof(lbm_probe_sample) == sizeof(lbm::probe_vec), "a sample is one 16-byte store");
+    // the rows wait in at most two runs of the ring; one slab: straight into out, several: each slab's columns of a staged copy
+    std::vector<lbm_probe_sample> stage(c->n_slabs > 1 ? (size_t)n * np : 0);
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      if (sl.probe_count == 0 && c->n_slabs > 1) continue;
+      lbm_probe_sample* dst = c->n_slabs > 1 ? stage.data() : out;
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      for (int i = 0; i < n;) {
+        const size_t slot = (size_t)((c->rec.read + i) % c->rec.slots);
+        const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
+        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(dst + (size_t)i * np, sl.probe_ring + slot * np, (size_t)run * np * sizeof(lbm_probe_sample),
+                                            hipMemcpyDeviceToHost, sl.compute));
+        i += run;
       }
-  }
-  if (steps)
-    for (int i = 0; i < n; i++) steps[i] = (int)((c->probe_ord0 + c->probes_read + i) * c->probe_every);
-  c->probes_read += n;
-  *n_read = n;
-  return LBM_SUCCESS;
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+      if (c->n_slabs > 1)
+        for (size_t p = 0; p < np; p++) {
+          const int y = c->probe_cells[p].y;
+          if (y < sl.row_first || y >= sl.row_first + sl.rows) continue;
+          for (int i = 0; i < n; i++) out[(size_t)i * np + p] = stage[(size_t)i * np + p];
+        }
+    }
+    return LBM_SUCCESS;
+  });
 }
 
 static const char kMemberRun[] = "%s: this context is a member of a batch (lbm_create_batch); lbm_batch_run advances all its members";
@@ -3351,8 +3288,7 @@ lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* 
         m.partials = sl.res_part;
         m.tot_u = sl.tot_u;
         m.omega = c->p.omega;
-        m.a1 = c->p.density * c->p.accel / 9.f;   // as run_steps / run_resident
-        m.a2 = c->p.density * c->p.accel / 36.f;
+        set_accel_weights(m, c->p);  // as run_steps / run_resident
       }
     if (hipMalloc(&bt->table, h.size() * sizeof(h[0])) != hipSuccess ||
         hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess ||
@@ -3381,14 +3317,12 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
   if (bt->steps_done + n_steps > c0->capacity)
     LBM_FAIL(LBM_FAILURE, "lbm_batch_run: %d steps requested but the av_vels record holds %d (maxIters)",
              bt->steps_done + n_steps, c0->capacity);
-  for (lbm_ctx* c : bt->members)  // every member's frames must fit before any member runs
-    if (frames_fit(c, n_steps, "lbm_batch_run") != LBM_SUCCESS || probes_fit(c, n_steps, "lbm_batch_run") != LBM_SUCCESS)
-      return LBM_FAILURE;
+  for (lbm_ctx* c : bt->members)  // every member's records must fit before any member runs
+    if (recorder_fits(c, n_steps, "lbm_batch_run") != LBM_SUCCESS) return LBM_FAILURE;
   if (bt->resident && n_steps >= c0->resident_min_steps) {
     if (run_batch_resident(bt, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
     for (lbm_ctx* c : bt->members) {
-      c->frames_written += frames_between(c, c->steps_done, (long long)c->steps_done + n_steps);
-      c->probes_written += probes_between(c, c->steps_done, (long long)c->steps_done + n_steps);
+      c->rec.written += recorded_between(c->rec, c->steps_done, (long long)c->steps_done + n_steps);
       c->steps_done += n_steps;
     }
   } else {
@@ -3445,8 +3379,7 @@ static int steady_args_ok(const char* who, int steps_done, int capacity, int max
   if (!(tol >= 0.0)) LBM_FAIL(LBM_FAILURE, "%s: tol must be a non-negative number (got %g)", who, tol);
   return LBM_SUCCESS;
 }
-static const char kSteadyFrames[] = "%s: animation frames are armed (lbm_set_frames); a steady-state run does not record frames";
-static const char kSteadyProbes[] = "%s: point probes are armed (lbm_set_probes); a steady-state run does not record probes";
+static const char kSteadyRecorder[] = "%s: %s are armed (%s); a steady-state run does not record %s";
 
 static void steady_fill(lbm_steady_result* out, const lbm::SteadyState& st, int steps_run) {
   out->steps_run = steps_run;
@@ -3463,9 +3396,10 @@ static void steady_fill(lbm_steady_result* out, const lbm::SteadyState& st, int 
 static int steady_segment_resident(lbm_ctx* c, int n, int slot, double tol, int patience, int steps_after) {
   Slab& sl = c->slab[0];
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+  const AccelWeights w = accel_weights(c->p);
   hipLaunchKernelGGL(lbm::accelerate_row_unless, dim3(ceil_div(c->p.nx, 256)), dim3(256), 0, sl.compute, sl.lat[c->cur],
                      (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx, sl.accel_row,
-                     c->p.density * c->p.accel / 9.f, c->p.density * c->p.accel / 36.f,
+                     w.a1, w.a2,
                      (const lbm::SteadyState*)c->steady_state);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
   if (run_resident(c, n) != LBM_SUCCESS) return LBM_FAILURE;
@@ -3483,8 +3417,10 @@ int lbm_run_until(lbm_ctx* c, int max_steps, int check_every, double tol, int pa
   if (c->batch) LBM_FAIL(LBM_FAILURE, kMemberRun, "lbm_run_until");
   if (steady_args_ok("lbm_run_until", c->steps_done, c->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS)
     return LBM_FAILURE;
-  if (c->frame_every > 0) LBM_FAIL(LBM_FAILURE, kSteadyFrames, "lbm_run_until");
-  if (c->probe_every > 0) LBM_FAIL(LBM_FAILURE, kSteadyProbes, "lbm_run_until");
+  if (c->rec.kind != kRecNone) {
+    const RecorderKind& k = kRecorderKinds[c->rec.kind];
+    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_run_until", k.name, k.setter, k.noun);
+  }
   if (c->halo_mode != LBM_HALO_SYNC)
     LBM_FAIL(LBM_FAILURE, "lbm_run_until: only LBM_HALO_SYNC runs can be checked (the halo mode is %d)", c->halo_mode);
   if (c->ranked || c->world > 1)
@@ -3561,8 +3497,10 @@ int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double to
   if (steady_args_ok("lbm_batch_run_until", bt->steps_done, c0->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS)
     return LBM_FAILURE;
   for (const lbm_ctx* c : bt->members) {
-    if (c->frame_every > 0) LBM_FAIL(LBM_FAILURE, kSteadyFrames, "lbm_batch_run_until");
-    if (c->probe_every > 0) LBM_FAIL(LBM_FAILURE, kSteadyProbes, "lbm_batch_run_until");
+    if (c->rec.kind != kRecNone) {
+      const RecorderKind& k = kRecorderKinds[c->rec.kind];
+      LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_batch_run_until", k.name, k.setter, k.noun);
+    }
   }
 
   HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));

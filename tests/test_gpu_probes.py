@@ -350,3 +350,52 @@ def test_cli_writes_probes_dat(lbm, oracle, datasets, tmp_path):
     twin = tmp_path / "twin.dat"
     lbm.write_probes(str(twin), cells, np.arange(250), np.stack([want[tt] for tt in range(250)]))
     assert (outs["probes"] / "probes.dat").read_bytes() == twin.read_bytes()
+
+
+def test_switching_recorder_kind(lbm, oracle, monkeypatch):
+    """One recorder per context, re-armed as the other kind mid-run: frames for 40 steps, then probes (one on the lid row)
+    for 40 more, on an engine and across the members of a batch, whose count of armed members must go back to zero."""
+    from test_gpu_frames import assert_frames, oracle_frames
+    monkeypatch.setenv("LBM_RESIDENT_MIN_STEPS", "16")
+    nx, ny = 128, 16
+    probes = [(5, 3), (77, ny - 2)]
+    cases = [random_case(lbm, nx, ny, seed, walls=False) for seed in (61, 62)]
+    refs = []   # per case: (frames of steps [0, 40), lattice after 80 steps, series of steps [40, 80))
+    for p, ob, cells in cases:
+        ref40, want_frames = oracle_frames(oracle, p, ob, cells, 0, 40, 7)
+        ref80, want_series = oracle_series(oracle, p, ob, ref40, 40, 80, 3, probes)
+        refs.append((want_frames, ref80, want_series))
+
+    # (a) engine
+    p, ob, cells = cases[0]
+    want_frames, ref80, want_series = refs[0]
+    with lbm.Engine(p, ob, cells) as eng:
+        assert eng.info()["resident_steps"] > 0
+        eng.set_frames(7, 16)
+        eng.run(40)
+        assert_frames(*eng.frames(), want_frames)
+        eng.set_frames(0)
+        eng.set_probes(probes, 3, 32)
+        eng.run(40)
+        steps, samples = eng.probes()
+        assert steps.tolist() == list(range(42, 79, 3))
+        assert_series(steps, samples, want_series)
+        assert eng.frames()[0].size == 0
+        assert np.array_equal(bits(eng.cells()), bits(ref80))
+
+    # (b) batch of two members: frames on member 0, then probes on member 1
+    with lbm.Batch([c[0] for c in cases], [c[1] for c in cases], [c[2] for c in cases]) as batch:
+        assert batch.info()["resident_steps"] > 0
+        m0, m1 = batch.member(0), batch.member(1)
+        m0.set_frames(7, 16)
+        batch.run(40)
+        assert_frames(*m0.frames(), refs[0][0])
+        m0.set_frames(0)
+        m1.set_probes(probes, 3, 32)        # not "one kind": no member has frames armed any more
+        batch.run(40)
+        steps, samples = m1.probes()
+        assert steps.tolist() == list(range(42, 79, 3))
+        assert_series(steps, samples, refs[1][2])
+        assert m0.frames()[0].size == 0
+        for m, (_, ref80, _) in zip((m0, m1), refs):
+            assert np.array_equal(bits(m.cells()), bits(ref80))
