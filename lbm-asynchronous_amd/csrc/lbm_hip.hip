@@ -6,6 +6,7 @@
 // No CPU compute path exists here: without a HIP device every compute entry point fails.
 #include "../../include/lbm_hip.h"
 #include "lbm_kernels.hip.h"
+#include "lbm_plan.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -27,10 +28,24 @@
 
 namespace {
 
-constexpr int kMaxSlabs = 8;
+// the kernel plan (lbm_plan.h): what plan_kernels decided for a context, and the arithmetic the launches share with it
+using lbm_plan::KernelPlan;
+using lbm_plan::PlanInput;
+using lbm_plan::SlabRows;
+using lbm_plan::HALO_SELF;
+using lbm_plan::HALO_MEMCPY;
+using lbm_plan::HALO_RCCL;
+using lbm_plan::HALO_HOST;
+using lbm_plan::ceil_div;
+using lbm_plan::round_up;
+using lbm_plan::env_int;
+using lbm_plan::kMaxSlabs;
+using lbm_plan::kMaxBandGroups;
+using lbm_plan::kHaloRows;
+using lbm_plan::kMaskHalo;
+using lbm_plan::kTileDims;
+static_assert(lbm_plan::kBlock == lbm::kBlock && lbm_plan::kNoRow == lbm::kNoRow, "lbm_plan.h mirrors the kernels' constants");
 constexpr int kPartSlots = lbm::kPartSlotsMax;  // steps whose partial sums are buffered before one reduce launch
-
-enum HaloMode { HALO_SELF = 0, HALO_MEMCPY = 1, HALO_RCCL = 2, HALO_HOST = 3 };
 
 // ---- error handling (reference: die(), SerialCode/d2q9-bgk.c:745-751) -----------------------
 int g_error_mode = LBM_ERRORS_DIE;
@@ -66,15 +81,6 @@ void raise_error(int line, const char* fmt, ...) {
     ncclResult_t r_ = (expr);                                                             \
     if (r_ != ncclSuccess) LBM_FAIL(ret, "RCCL error: %s (%s)", g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "?", #expr); \
   } while (0)
-
-inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
-inline long round_up(long a, long b) { return (a + b - 1) / b * b; }
-
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && *v) ? atoi(v) : dflt;
-}
-
 
 // ---- RCCL, bound at first use -----------------------------------------------------------------------------------
 // The library is NOT a link-time dependency: a single-GPU run never loads it, and WHICH librccl serves a multi-GPU
@@ -152,8 +158,6 @@ RcclApi* rccl() {
   RcclApi* rc_api_ = rccl();                                                    \
   if (!rc_api_) LBM_FAIL(ret, "RCCL is not available: %s", g_rccl_error)
 
-constexpr int kMaxBandGroups = 3;  // interior streams of the band-group path: with the seam stream four in all
-
 struct Slab {
   int device = 0;
   int row_first = 0;  // global row of slab row 0
@@ -185,7 +189,7 @@ struct Slab {
   hipEvent_t ev_step = nullptr;                    // stale-halo mode: whole-slab pass finished; graph replay: join
   hipEvent_t ev_fork = nullptr;                    // graph replay: the other streams join the capture / follow the chunks
   hipEvent_t ev_x[2] = {nullptr, nullptr};         // stale-halo mode: exchange for pass m landed -> [(m + 1) & 1]
-  // band groups (single periodic slab, c->band_groups > 1): interior bands of group g run on group_stream(g) -- the
+  // band groups (single periodic slab, c->plan.band_groups > 1): interior bands of group g run on group_stream(g) -- the
   // compute stream for g = 0, group_extra[g - 1] after it -- and the seam bands on the comm stream
   hipStream_t group_extra[kMaxBandGroups - 1] = {nullptr, nullptr};
   hipEvent_t ev_gi[2][kMaxBandGroups] = {};        // interior bands of group g in pass m done -> [m & 1][g]
@@ -206,22 +210,15 @@ struct Slab {
 
 constexpr int kSumBlocks = 1024;
 constexpr int kResidentChunk = 4096;  // most timesteps one launch of the resident kernel advances
-// step_tile instantiations: own cells per workgroup (tw x th), halo depth = most timesteps per launch, threads
-struct TileShape { int tw, th, kmax, threads; void (*exact)(const lbm::TileArgs); void (*fast)(const lbm::TileArgs); };
-#define LBM_TILE_SHAPE(TW, TH, K, T) {TW, TH, K, T, lbm::step_tile<0, TW, TH, K, T>, lbm::step_tile<1, TW, TH, K, T>}
-const TileShape kTileShapes[] = {
-    LBM_TILE_SHAPE(16, 8, 4, 384),   // 0: tiny grids: one thread per staged cell (24 x 16)
-    LBM_TILE_SHAPE(16, 8, 8, 768),   // 1: same, halo of 8
-    LBM_TILE_SHAPE(32, 16, 2, 640),  // 2..: larger tiles, less redundant halo work
-    LBM_TILE_SHAPE(32, 16, 3, 768),
-    LBM_TILE_SHAPE(32, 16, 4, 896),
-    LBM_TILE_SHAPE(64, 16, 2, 640),
-    LBM_TILE_SHAPE(64, 8, 2, 704),
-};
-constexpr int kTileShapeCount = (int)(sizeof(kTileShapes) / sizeof(kTileShapes[0]));
-constexpr int kHaloRows = 4;  // halo rows kept below and above every slab (a K-step pass reads K rows beyond the slab)
-constexpr int kMaskHalo = LBM_MASK_HALO_ROWS;  // mask rows kept beyond the slab: a K-step pass relaxes K-1 halo rows redundantly
-static_assert(kMaskHalo == kHaloRows - 1, "mask halo");
+// the step_tile instantiation of every shape of lbm_plan::kTileDims, in both arithmetics
+struct TileKernels { void (*exact)(const lbm::TileArgs); void (*fast)(const lbm::TileArgs); };
+#define LBM_TILE_KERNELS(I)                                                                       \
+  {lbm::step_tile<0, kTileDims[I].tw, kTileDims[I].th, kTileDims[I].kmax, kTileDims[I].threads>, \
+   lbm::step_tile<1, kTileDims[I].tw, kTileDims[I].th, kTileDims[I].kmax, kTileDims[I].threads>}
+const TileKernels kTileKernels[] = {LBM_TILE_KERNELS(0), LBM_TILE_KERNELS(1), LBM_TILE_KERNELS(2), LBM_TILE_KERNELS(3),
+                                    LBM_TILE_KERNELS(4), LBM_TILE_KERNELS(5), LBM_TILE_KERNELS(6)};
+static_assert(sizeof(kTileKernels) / sizeof(kTileKernels[0]) == lbm_plan::kTileShapeCount, "a kernel pair per tile shape");
+static_assert(kMaskHalo == LBM_MASK_HALO_ROWS && kMaskHalo == kHaloRows - 1, "mask halo");
 
 // where the obstacle flags come from (the reference: initialise() fills int[ny*nx] on rank 0 and, in the MPI variants,
 // sends every rank its rows, MPI_Waitall/d2q9-bgk.c:794-842)
@@ -381,37 +378,11 @@ struct lbm_ctx {
   float* host_recv[2] = {nullptr, nullptr};
   int row_first = 0, row_count = 0;
   int slot_fill = 0;  // partial slots used since the last reduce
-  long part_stride = 0;
-  bool vec4 = false;
-  int neigh = 0;  // step_vec4 NEIGH flavour (LBM_NEIGH overrides)
-  int nts = 1;    // nontemporal stores (LBM_NTS overrides)
-  int snake = 0;  // alternate the sweep direction every step (LBM_SNAKE overrides)
-  int fuse2 = 0;  // several timesteps per pass over memory (the stream kernels) where the slabs allow it
-  int pass_steps = 2;  // ... how many: 2 or 3 (LBM_PASS_STEPS)
-  int prefetch = 0;    // stream kernel: request the next row before relaxing the current one (LBM_PREFETCH)
-  int xcd_chunk = 0;   // stream kernel: strips per XCD chunk (LBM_XCD_CHUNK; 0 = plain workgroup order)
-  int use_stepk = 0;   // two-step passes through stepk_stream<K=2> instead of step2_stream (LBM_STEPK; experiments)
-  int packed = 0;      // stream kernel: collision on pairs of cells, v_pk_* instructions (LBM_PACKED)
-  int halo_lanes = 1;  // stream kernel: lanes at each end of a wave that only feed their neighbours
-  int lds_windows = 0; // packed stream kernel: how many of the K-1 sliding windows live in LDS (LBM_LDS_WINDOWS, 0..2)
-  int band_rows = 8, n_strips = 0;  // step2_stream geometry: band height, waves across x
-  int band_groups = 1;              // single periodic slab: full-depth passes as this many band groups (LBM_BAND_GROUPS)
-  bool groups_forked = false;       // ... the group and seam streams have been forked off the compute stream
-  int lane_cells = 4;               // cells per lane in step2_stream (4 or 2; LBM_LANE_CELLS)
+  KernelPlan plan;    // which kernels advance this context and their launch geometry (lbm_plan.h: plan_kernels)
+  bool groups_forked = false;       // band groups: the group and seam streams have been forked off the compute stream
   SlabTeam* team = nullptr;         // one issuing thread per slab (one-process multi-GPU), or null
-  int use_graph = 0;                // replay chunks of an even number of passes + their reduce as one hipGraph each
   GraphBuilder* builder = nullptr;  // non-null while a chunk is being built: launches become graph nodes
-  int resident = 0;                 // single periodic slab that fits the chip's registers: lbm_run calls of at least
-  int resident_min_steps = 16;      // ... this many timesteps run as launches of the resident kernel (lbm::resident_band)
-  int resident_bands = 0;           // its workgroups (bands of resident_rows rows)
-  int resident_joint = 0;           // narrow grids: both pairs of a lane relaxed as one block behind the halo wait
-  int resident_rows = 4;            // rows per band: 4, or 2 where the chip has CUs to spare (one pair per lane)
-  int resident_group = 1;           // bands per workgroup
-  int resident_one_xcd = 0;         // all workgroups on one XCD (8 x the workgroups launched, 7 of 8 leave at once)
-  long long resident_timeout = 0;   // bound of one halo wait, wall-clock ticks
-  bool resident_used = false;       // a launch is in flight / unchecked: lbm_sync reads its status
-  int tile_steps = 0;               // > 0: single slab advanced by the LDS-tile kernel, this many steps per launch
-  int tile_shape = 0;               // index into kTileShapes
+  bool resident_used = false;       // a resident launch is in flight / unchecked: lbm_sync reads its status
   lbm_batch* batch = nullptr;       // member of this batch (lbm_create_batch): advanced, synchronised and freed by it
   Recorder rec;                     // the one recorder: animation frames (lbm_set_frames) or point probes (lbm_set_probes)
   std::vector<lbm_probe> probe_cells;  // the probed global cells, in the caller's order (a probes row has that many samples)
@@ -539,12 +510,12 @@ int launch_step(lbm_ctx* c, int s, hipStream_t stream, int row_first, int row_st
   a.accel_row = accel_epilogue ? sl.accel_row : lbm::kNoRow;
   a.omega = c->p.omega;
   set_accel_weights(a, c->p);
-  a.partials = sl.partials + (long)c->slot_fill * c->part_stride + part_offset;
-  a.reverse = (c->snake && n_rows > 2) ? (c->cur & 1) : 0;
+  a.partials = sl.partials + (long)c->slot_fill * c->plan.part_stride + part_offset;
+  a.reverse = (c->plan.snake && n_rows > 2) ? (c->cur & 1) : 0;
   a.wrap = (c->halo == HALO_SELF) ? 1 : 0;
 
   const bool exact = (c->math_mode == LBM_MATH_EXACT);
-  if (c->vec4) {
+  if (c->plan.vec4) {
     const int blocks = ceil_div((long)(c->p.nx / 4) * n_rows, lbm::kBlock);
     // kernel flavour: [math][neighbour exchange][nontemporal stores]; tuned defaults, see DESIGN.md
     typedef void (*step_fn)(const lbm::StepArgs);
@@ -556,7 +527,7 @@ int launch_step(lbm_ctx* c, int s, hipStream_t stream, int row_first, int row_st
          {lbm::step_vec4<1, 1, false>, lbm::step_vec4<1, 1, true>},
          {lbm::step_vec4<1, 2, false>, lbm::step_vec4<1, 2, true>}}};
     void* args[] = {&a};
-    return q_kernel(c, stream, reinterpret_cast<const void*>(table[exact ? 0 : 1][c->neigh][c->nts]), dim3(blocks), dim3(lbm::kBlock), args, done);
+    return q_kernel(c, stream, reinterpret_cast<const void*>(table[exact ? 0 : 1][c->plan.neigh][c->plan.nts]), dim3(blocks), dim3(lbm::kBlock), args, done);
   } else {
     const int blocks = ceil_div((long)c->p.nx * n_rows, lbm::kBlock);
     const auto fn = exact ? lbm::step_scalar<true> : lbm::step_scalar<false>;
@@ -586,14 +557,14 @@ int launch_step2(lbm_ctx* c, int s, hipStream_t stream, int row_first, int row_e
   a.row_first = row_first;
   a.band_pitch = band_pitch;
   a.row_end = row_end;
-  a.n_strips = c->n_strips;
+  a.n_strips = c->plan.n_strips;
   a.accel_row = sl.accel_row;
   a.accel_after = accel_after ? 1 : 0;
   a.omega = c->p.omega;
   set_accel_weights(a, c->p);
-  a.partials1 = sl.partials + (long)c->slot_fill * c->part_stride + part_offset;
-  a.partials2 = a.partials1 + c->part_stride;
-  const int waves = c->n_strips * band_count;
+  a.partials1 = sl.partials + (long)c->slot_fill * c->plan.part_stride + part_offset;
+  a.partials2 = a.partials1 + c->plan.part_stride;
+  const int waves = c->plan.n_strips * band_count;
   typedef void (*fn)(const lbm::Step2Args);
   // [math][nontemporal stores][cells per lane: 0 -> 4, 1 -> 2]
   static const fn table[2][2][2] = {
@@ -601,7 +572,7 @@ int launch_step2(lbm_ctx* c, int s, hipStream_t stream, int row_first, int row_e
        {lbm::step2_stream<0, true, 4>, lbm::step2_stream<0, true, 2>}},
       {{lbm::step2_stream<1, false, 4>, lbm::step2_stream<1, false, 2>},
        {lbm::step2_stream<1, true, 4>, lbm::step2_stream<1, true, 2>}}};
-  const fn kernel = table[c->math_mode == LBM_MATH_EXACT ? 0 : 1][c->nts][c->lane_cells == 2 ? 1 : 0];
+  const fn kernel = table[c->math_mode == LBM_MATH_EXACT ? 0 : 1][c->plan.nts][c->plan.lane_cells == 2 ? 1 : 0];
   void* args[] = {&a};
   return q_kernel(c, stream, reinterpret_cast<const void*>(kernel), dim3(waves), dim3(64), args, done);
 }
@@ -626,20 +597,20 @@ int launch_stepk(lbm_ctx* c, int s, hipStream_t stream, int k, int row_first, in
   a.row_first = row_first;
   a.band_pitch = band_pitch;
   a.row_end = row_end;
-  a.n_strips = c->n_strips;
+  a.n_strips = c->plan.n_strips;
   a.n_bands = band_count;
-  a.chunk = c->xcd_chunk;
-  a.halo_lanes = c->halo_lanes;
+  a.chunk = c->plan.xcd_chunk;
+  a.halo_lanes = c->plan.halo_lanes;
   a.accel_row = sl.accel_row;
   a.accel_row2 = sl.accel_row2;
   a.accel_after = accel_after ? 1 : 0;
   a.omega = c->p.omega;
   set_accel_weights(a, c->p);
-  a.partials = sl.partials + (long)c->slot_fill * c->part_stride + part_offset;
-  a.slot_stride = c->part_stride;
-  int waves = c->n_strips * band_count;
+  a.partials = sl.partials + (long)c->slot_fill * c->plan.part_stride + part_offset;
+  a.slot_stride = c->plan.part_stride;
+  int waves = c->plan.n_strips * band_count;
   if (a.chunk > 0) {
-    const int chunks = band_count * ceil_div(c->n_strips, a.chunk);
+    const int chunks = band_count * ceil_div(c->plan.n_strips, a.chunk);
     waves = 8 * ceil_div(chunks, 8) * a.chunk;
   }
   typedef void (*fn)(const lbm::StepKArgs);
@@ -668,11 +639,11 @@ int launch_stepk(lbm_ctx* c, int s, hipStream_t stream, int k, int row_first, in
   static const fn table_pk1[2][3][2][2] = {LBM_PK1_ROW(false), LBM_PK1_ROW(true)};
 #undef LBM_PK1_ROW
 #undef LBM_PK1
-  const int lds_windows = c->lds_windows < k ? c->lds_windows : k - 1;
-  const bool packed = c->packed != 0;  // the packed kernels have one arithmetic (the exact one) and serve both math modes
-  const fn kernel = (packed && c->lane_cells == 2) ? table_pk1[c->nts][k - 2][c->prefetch ? 1 : 0][lds_windows ? 1 : 0]
-                    : packed ? table_pk[c->nts][k - 2][c->prefetch ? 1 : 0][lds_windows]
-                           : table[c->math_mode == LBM_MATH_EXACT ? 0 : 1][c->nts][k - 2][c->prefetch ? 1 : 0];
+  const int lds_windows = c->plan.lds_windows < k ? c->plan.lds_windows : k - 1;
+  const bool packed = c->plan.packed != 0;  // the packed kernels have one arithmetic (the exact one) and serve both math modes
+  const fn kernel = (packed && c->plan.lane_cells == 2) ? table_pk1[c->plan.nts][k - 2][c->plan.prefetch ? 1 : 0][lds_windows ? 1 : 0]
+                    : packed ? table_pk[c->plan.nts][k - 2][c->plan.prefetch ? 1 : 0][lds_windows]
+                           : table[c->math_mode == LBM_MATH_EXACT ? 0 : 1][c->plan.nts][k - 2][c->plan.prefetch ? 1 : 0];
   void* args[] = {&a};
   return q_kernel(c, stream, reinterpret_cast<const void*>(kernel), dim3(waves), dim3(64), args, done);
 }
@@ -680,21 +651,15 @@ int launch_stepk(lbm_ctx* c, int s, hipStream_t stream, int k, int row_first, in
 // the stream kernel for a k-step pass: the 2-cells-per-lane form exists for k = 2 only (step2_stream)
 int launch_pass(lbm_ctx* c, int s, hipStream_t stream, int k, int row_first, int row_end, int band_rows,
                 int band_pitch, int band_count, int part_offset, bool accel_after, hipEvent_t done = nullptr) {
-  if ((c->lane_cells == 4 && (k > 2 || c->prefetch || c->xcd_chunk || c->use_stepk || c->packed)) ||
-      (c->lane_cells == 2 && c->packed))
+  if ((c->plan.lane_cells == 4 && (k > 2 || c->plan.prefetch || c->plan.xcd_chunk || c->plan.use_stepk || c->plan.packed)) ||
+      (c->plan.lane_cells == 2 && c->plan.packed))
     return launch_stepk(c, s, stream, k, row_first, row_end, band_rows, band_pitch, band_count, part_offset, accel_after, done);
   return launch_step2(c, s, stream, row_first, row_end, band_rows, band_pitch, band_count, part_offset, accel_after, done);
 }
 
-int tile_count_for(const lbm_params* p, int shape) {
-  return ceil_div(p->nx, kTileShapes[shape].tw) * ceil_div(p->ny, kTileShapes[shape].th);
-}
-int tile_count(const lbm_ctx* c) {
-  const TileShape& t = kTileShapes[c->tile_shape];
-  return ceil_div(c->p.nx, t.tw) * ceil_div(c->slab[0].rows, t.th);
-}
+int tile_count(const lbm_ctx* c) { return lbm_plan::tile_count(c->p.nx, c->slab[0].rows, c->plan.tile_shape); }
 
-// n_steps <= c->tile_steps timesteps of the whole (single, periodic) slab from LDS tiles; partials of step j go
+// n_steps <= c->plan.tile_steps timesteps of the whole (single, periodic) slab from LDS tiles; partials of step j go
 // to slot slot_fill + j
 int launch_tile(lbm_ctx* c, hipStream_t stream, int n_steps, bool accel_after) {
   Slab& sl = c->slab[0];
@@ -712,20 +677,17 @@ int launch_tile(lbm_ctx* c, hipStream_t stream, int n_steps, bool accel_after) {
   a.accel_after = accel_after ? 1 : 0;
   a.omega = c->p.omega;
   set_accel_weights(a, c->p);
-  a.partials = sl.partials + (long)c->slot_fill * c->part_stride;
-  a.slot_stride = c->part_stride;
-  const TileShape& t = kTileShapes[c->tile_shape];
+  a.partials = sl.partials + (long)c->slot_fill * c->plan.part_stride;
+  a.slot_stride = c->plan.part_stride;
+  const lbm_plan::TileDims& t = kTileDims[c->plan.tile_shape];
+  const TileKernels& kernels = kTileKernels[c->plan.tile_shape];
   a.tiles_x = ceil_div(c->p.nx, t.tw);
   void* args[] = {&a};
-  return q_kernel(c, stream, reinterpret_cast<const void*>(c->math_mode == LBM_MATH_EXACT ? t.exact : t.fast), dim3(tile_count(c)),
-                  dim3(t.threads), args);
+  return q_kernel(c, stream, reinterpret_cast<const void*>(c->math_mode == LBM_MATH_EXACT ? kernels.exact : kernels.fast),
+                  dim3(tile_count(c)), dim3(t.threads), args);
 }
 
-int blocks_for_rows(const lbm_ctx* c, int n_rows) {
-  if (n_rows <= 0) return 0;
-  return c->vec4 ? ceil_div((long)(c->p.nx / 4) * n_rows, lbm::kBlock)
-                 : ceil_div((long)c->p.nx * n_rows, lbm::kBlock);
-}
+int blocks_for_rows(const lbm_ctx* c, int n_rows) { return lbm_plan::blocks_for_rows(c->plan.vec4, c->p.nx, n_rows); }
 
 // One halo exchange, enqueued on the comm streams: the `depth` boundary rows at each end of every
 // slab's lattice `src` travel, whole (all 9 speeds, as MPI_Waitall/d2q9-bgk.c:225-230 ships
@@ -878,7 +840,7 @@ int flush_partials(lbm_ctx* c, int step_base) {
     const bool split = (c->halo != HALO_SELF && c->halo_mode == LBM_HALO_SYNC);
     if (split) HIP_TRY(LBM_FAILURE, hipStreamWaitEvent(sl.compute, sl.ev_boundary, 0));
     hipLaunchKernelGGL(lbm::reduce_partials, dim3(c->slot_fill), dim3(lbm::kBlock), 0, sl.compute,
-                       sl.partials, sl.slot_counts, c->part_stride, sl.tot_u, step_base, (const int*)nullptr);
+                       sl.partials, sl.slot_counts, c->plan.part_stride, sl.tot_u, step_base, (const int*)nullptr);
     HIP_TRY(LBM_FAILURE, hipGetLastError());
     if (split) {
       // the next boundary kernels (comm stream) reuse the partial slots just read
@@ -956,7 +918,7 @@ int reset_pipeline(lbm_ctx* c) {
 int issue_pass(lbm_ctx* c, int m, int tile, int k, bool accel_after, bool bound_events) {
   const bool halo = (c->halo != HALO_SELF);
   const int adv = tile ? tile : (k ? k : 1);
-  const int depth = c->fuse2 ? c->pass_steps : 1;  // a K-step pass reads K rows beyond the slab
+  const int depth = c->plan.fuse2 ? c->plan.pass_steps : 1;  // a K-step pass reads K rows beyond the slab
   if (halo && exchange_halos(c, depth, c->cur, c->cur, -1) != LBM_SUCCESS) return LBM_FAILURE;
   // phase 1: rows that touch no halo row (or the whole slab) on the compute streams
   if (for_slabs(c, [&](int s) -> int {
@@ -968,7 +930,7 @@ int issue_pass(lbm_ctx* c, int m, int tile, int k, bool accel_after, bool bound_
           if (launch_tile(c, sl.compute, tile, accel_after) != LBM_SUCCESS) return LBM_FAILURE;
         } else if (k) {
           const int r0 = halo ? k : 0, r1 = halo ? sl.rows - k : sl.rows;
-          if (launch_pass(c, s, sl.compute, k, r0, r1, c->band_rows, c->band_rows, ceil_div(r1 - r0, c->band_rows), 0,
+          if (launch_pass(c, s, sl.compute, k, r0, r1, c->plan.band_rows, c->plan.band_rows, ceil_div(r1 - r0, c->plan.band_rows), 0,
                           accel_after, done) != LBM_SUCCESS)
             return LBM_FAILURE;
         } else if (!halo) {
@@ -994,7 +956,7 @@ int issue_pass(lbm_ctx* c, int m, int tile, int k, bool accel_after, bool bound_
         hipEvent_t bdone = bound_events ? sl.ev_boundary : nullptr;  // B(m) done
         if (k) {
           // rows [0, k) and [rows-k, rows) as two k-row bands in one launch
-          const int off = c->n_strips * ceil_div(sl.rows - 2 * k, c->band_rows);
+          const int off = c->plan.n_strips * ceil_div(sl.rows - 2 * k, c->plan.band_rows);
           if (launch_pass(c, s, sl.comm, k, 0, sl.rows, k, sl.rows - k, 2, off, accel_after, bdone) != LBM_SUCCESS) return LBM_FAILURE;
         } else {
           if (launch_step(c, s, sl.comm, 0, sl.rows - 1, 2, sl.blocks_main, accel_after, bdone) != LBM_SUCCESS) return LBM_FAILURE;
@@ -1006,8 +968,8 @@ int issue_pass(lbm_ctx* c, int m, int tile, int k, bool accel_after, bool bound_
   // bookkeeping of the partial slots written by this pass
   for (int s = 0; s < c->n_slabs; s++) {
     Slab& sl = c->slab[s];
-    const int fused_waves = halo ? c->n_strips * (ceil_div(sl.rows - 2 * k, c->band_rows) + 2)
-                                 : c->n_strips * ceil_div(sl.rows, c->band_rows);
+    const int fused_waves = halo ? c->plan.n_strips * (ceil_div(sl.rows - 2 * k, c->plan.band_rows) + 2)
+                                 : c->plan.n_strips * ceil_div(sl.rows, c->plan.band_rows);
     const int n_part = tile ? tile_count(c) : (k ? fused_waves : sl.blocks_main + sl.blocks_boundary);
     for (int j = 0; j < adv; j++) sl.slot_counts.n[c->slot_fill + j] = n_part;
   }
@@ -1042,7 +1004,7 @@ int group_fork(lbm_ctx* c, int m) {
   Slab& sl = c->slab[0];
   const int prev = (m - 1) & 1;
   if (q_record(c, sl.ev_gs[prev], sl.compute) != LBM_SUCCESS) return LBM_FAILURE;
-  for (int g = 0; g < c->band_groups; g++)
+  for (int g = 0; g < c->plan.band_groups; g++)
     if (q_record(c, sl.ev_gi[prev][g], sl.compute) != LBM_SUCCESS) return LBM_FAILURE;
   c->groups_forked = true;
   return LBM_SUCCESS;
@@ -1053,7 +1015,7 @@ int group_join(lbm_ctx* c, int m) {
   if (!c->groups_forked) return LBM_SUCCESS;
   Slab& sl = c->slab[0];
   if (q_wait(c, sl.compute, sl.ev_gs[m & 1]) != LBM_SUCCESS) return LBM_FAILURE;
-  for (int g = 1; g < c->band_groups; g++)
+  for (int g = 1; g < c->plan.band_groups; g++)
     if (q_wait(c, sl.compute, sl.ev_gi[m & 1][g]) != LBM_SUCCESS) return LBM_FAILURE;
   c->groups_forked = false;
   return LBM_SUCCESS;
@@ -1061,38 +1023,25 @@ int group_join(lbm_ctx* c, int m) {
 
 // rows [lo, hi) of group g; returns the group height H (the last group also takes the remainder)
 int group_rows(const lbm_ctx* c, int g, int* lo, int* hi) {
-  const int rows = c->slab[0].rows, h = rows / c->band_groups;
-  *lo = g * h;
-  *hi = (g == c->band_groups - 1) ? rows : *lo + h;
-  return h;
-}
-// waves of a grouped pass of k steps: the interior bands of every group and G seam bands; partial slots in this order
-int grouped_waves(const lbm_ctx* c, int k) {
-  int bands = c->band_groups;
-  for (int g = 0; g < c->band_groups; g++) {
-    int lo, hi;
-    group_rows(c, g, &lo, &hi);
-    bands += ceil_div(hi - lo - 2 * k, c->band_rows);
-  }
-  return c->n_strips * bands;
+  return lbm_plan::group_rows(c->slab[0].rows, c->plan.band_groups, g, lo, hi);
 }
 
 // pass m (k steps) of the single periodic slab as band groups; the streams have been forked (group_fork)
 int issue_grouped_pass(lbm_ctx* c, int m, int k, bool accel_after, bool bound_events) {
   Slab& sl = c->slab[0];
-  const int G = c->band_groups, now = m & 1, prev = now ^ 1;
+  const int G = c->plan.band_groups, now = m & 1, prev = now ^ 1;
   int off = 0, h = 0;
   for (int g = 0; g < G; g++) {
     int lo, hi;
     h = group_rows(c, g, &lo, &hi);
     const hipStream_t st = group_stream(sl, g);
     if (q_wait(c, st, sl.ev_gs[prev]) != LBM_SUCCESS) return LBM_FAILURE;  // S(m-1)
-    const int bands = ceil_div(hi - lo - 2 * k, c->band_rows);
+    const int bands = ceil_div(hi - lo - 2 * k, c->plan.band_rows);
     hipEvent_t done = bound_events ? sl.ev_gi[now][g] : nullptr;
-    if (launch_pass(c, 0, st, k, lo + k, hi - k, c->band_rows, c->band_rows, bands, off, accel_after, done) != LBM_SUCCESS)
+    if (launch_pass(c, 0, st, k, lo + k, hi - k, c->plan.band_rows, c->plan.band_rows, bands, off, accel_after, done) != LBM_SUCCESS)
       return LBM_FAILURE;
     if (!done && q_record(c, sl.ev_gi[now][g], st) != LBM_SUCCESS) return LBM_FAILURE;
-    off += c->n_strips * bands;
+    off += c->plan.n_strips * bands;
   }
   for (int g = 0; g < G; g++)
     if (q_wait(c, sl.comm, sl.ev_gi[prev][g]) != LBM_SUCCESS) return LBM_FAILURE;  // I_g(m-1)
@@ -1101,7 +1050,7 @@ int issue_grouped_pass(lbm_ctx* c, int m, int k, bool accel_after, bool bound_ev
   if (launch_pass(c, 0, sl.comm, k, -k, (G - 1) * h + k, 2 * k, h, G, off, accel_after, sdone) != LBM_SUCCESS)
     return LBM_FAILURE;
   if (!sdone && q_record(c, sl.ev_gs[now], sl.comm) != LBM_SUCCESS) return LBM_FAILURE;
-  off += c->n_strips * G;
+  off += c->plan.n_strips * G;
   for (int j = 0; j < k; j++) sl.slot_counts.n[c->slot_fill + j] = off;
   c->cur ^= 1;
   c->slot_fill += k;
@@ -1121,7 +1070,7 @@ int issue_grouped_pass(lbm_ctx* c, int m, int k, bool accel_after, bool bound_ev
 // stream joined, i.e. one exchange per chunk is not hidden behind interior rows (1 of 20-32).
 int chunk_passes(const lbm_ctx* c, int* steps_per_pass) {
   const int halo = (c->halo != HALO_SELF);
-  const int adv = (!halo && c->tile_steps) ? c->tile_steps : (c->fuse2 ? c->pass_steps : 1);
+  const int adv = (!halo && c->plan.tile_steps) ? c->plan.tile_steps : (c->plan.fuse2 ? c->plan.pass_steps : 1);
   int passes = kPartSlots / adv;
   const int cap = env_int("LBM_GRAPH_PASSES", 0);  // experiments and tests: shorter chunks
   if (cap > 0 && passes > cap) passes = cap;
@@ -1184,8 +1133,8 @@ int build_chunk(lbm_ctx* c, hipGraphExec_t* out) {
   if (passes < 2) LBM_FAIL(LBM_FAILURE, "hipGraph chunk: no even number of passes fits");
   for (int s = 1; s < c->n_slabs; s++)
     if (c->slab[s].device != c->slab[0].device) LBM_FAIL(LBM_FAILURE, "hipGraph chunk: the slabs of one graph must share a device");
-  const int tile = (!halo && c->tile_steps) ? c->tile_steps : 0;
-  const int k = (!tile && c->fuse2) ? c->pass_steps : 0;
+  const int tile = (!halo && c->plan.tile_steps) ? c->plan.tile_steps : 0;
+  const int k = (!tile && c->plan.fuse2) ? c->plan.pass_steps : 0;
   const int saved_cur = c->cur, saved_fill = c->slot_fill;
   GraphBuilder gb;
   HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
@@ -1200,7 +1149,7 @@ int build_chunk(lbm_ctx* c, hipGraphExec_t* out) {
     Slab& sl = c->slab[s];
     if (halo) rc = q_wait(c, sl.compute, sl.ev_boundary);  // the boundary rows' partials
     const float* partials = sl.partials;
-    long stride = c->part_stride;
+    long stride = c->plan.part_stride;
     double* tot_u = sl.tot_u;
     int zero = 0, fill = c->slot_fill;
     const int* base_dev = sl.flushed_dev;
@@ -1241,7 +1190,7 @@ int replay_chunks(lbm_ctx* c, int n_steps, int first_step, int* done) {
     // e.g. slabs on several devices: go on launch by launch
     fprintf(stderr, "lbm_hip: hipGraph chunk not built (%s); continuing with stream launches\n", g_last_error);
     exec = nullptr;
-    c->use_graph = 0;
+    c->plan.use_graph = 0;
     return LBM_SUCCESS;
   }
   // everything enqueued so far on the other streams precedes the chunks, which run "on" slab 0's compute stream
@@ -1279,7 +1228,7 @@ int run_steps_stale(lbm_ctx* c, int n_steps, float* kernel_ms);
 
 // seam granules: [2 directions][bands][2 slots][nx] + one XCC-id granule per band
 size_t resident_gran_bytes(const lbm_ctx* c) {
-  return (2UL * c->resident_bands * 2 * c->p.nx + c->resident_bands) * sizeof(uint4);
+  return (2UL * c->plan.resident_bands * 2 * c->p.nx + c->plan.resident_bands) * sizeof(uint4);
 }
 
 // The forms of lbm::resident_band, [batched][recorder compiled in] x the five shapes: MAXT 1024 / 512 with two-row
@@ -1329,10 +1278,10 @@ void fill_resident_args(lbm::ResidentArgs& a, const lbm_ctx* c, int n, bool last
   a.gran_bytes = (unsigned)resident_gran_bytes(c);
   a.xcd_affinity = env_int("LBM_RESIDENT_XCD", 1) ? 1 : 0;
   a.epoch0 = (unsigned)epoch0;
-  a.timeout_ticks = c->resident_timeout;
+  a.timeout_ticks = c->plan.resident_timeout;
   a.absent_band = env_int("LBM_RESIDENT_ABSENT_BAND", -1);  // tests of the give-up path
-  a.group = c->resident_group;
-  a.one_xcd = c->resident_one_xcd;
+  a.group = c->plan.resident_group;
+  a.one_xcd = c->plan.resident_one_xcd;
 }
 
 // The timestep loop of a cache-resident single slab: launches of lbm::resident_band, each advancing up to
@@ -1364,28 +1313,28 @@ int run_resident(lbm_ctx* c, int n_steps) {
     a.prof = prof_dev;
 #endif
     void* args[] = {probes ? static_cast<void*>(&pa) : static_cast<void*>(&fa)};
-    HIP_TRY(LBM_FAILURE, hipLaunchKernel(resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, c->rec.kind),
-                                         dim3(c->resident_bands / a.group * (a.one_xcd ? 8 : 1)), dim3(c->p.nx * a.group), args, 0, sl.compute));
+    HIP_TRY(LBM_FAILURE, hipLaunchKernel(resident_kernel(c->p.nx, c->plan.resident_rows, c->plan.resident_joint, c->rec.kind),
+                                         dim3(c->plan.resident_bands / a.group * (a.one_xcd ? 8 : 1)), dim3(c->p.nx * a.group), args, 0, sl.compute));
     hipLaunchKernelGGL(lbm::reduce_band_partials, dim3(n), dim3(64), 0, sl.compute, (const float*)sl.res_part,
-                       c->resident_bands, sl.tot_u, c->steps_done + t);
+                       c->plan.resident_bands, sl.tot_u, c->steps_done + t);
     HIP_TRY(LBM_FAILURE, hipGetLastError());
 #ifdef LBM_RESIDENT_PROFILE
     {
       static const char* const phase[8] = {"edges->LDS", "barrier", "shifts(+interior)", "first halo answer", "further polls", "collision", "publish+sum", "extra polls (count)"};
-      std::vector<long long> h(c->resident_bands * 8);
+      std::vector<long long> h(c->plan.resident_bands * 8);
       HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
       HIP_TRY(LBM_FAILURE, hipMemcpy(h.data(), prof_dev, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-      fprintf(stderr, "resident profile %dx%d rows %d, %d steps (s_memtime ticks per step, wave 0 of each band: mean / min / max over bands)\n", c->p.nx, sl.rows, c->resident_rows, n);
+      fprintf(stderr, "resident profile %dx%d rows %d, %d steps (s_memtime ticks per step, wave 0 of each band: mean / min / max over bands)\n", c->p.nx, sl.rows, c->plan.resident_rows, n);
       for (int i = 0; i < 8; i++) {
         double sum = 0, lo = 1e30, hi = 0;
-        for (int b = 0; b < c->resident_bands; b++) { const double v = (double)h[b * 8 + i] / n; sum += v; lo = v < lo ? v : lo; hi = v > hi ? v : hi; }
-        fprintf(stderr, "  %-20s %9.2f %9.2f %9.2f\n", phase[i], sum / c->resident_bands, lo, hi);
+        for (int b = 0; b < c->plan.resident_bands; b++) { const double v = (double)h[b * 8 + i] / n; sum += v; lo = v < lo ? v : lo; hi = v > hi ? v : hi; }
+        fprintf(stderr, "  %-20s %9.2f %9.2f %9.2f\n", phase[i], sum / c->plan.resident_bands, lo, hi);
       }
       // the bands that wait least for their neighbours set the pace: who are they, and where does their time go?
-      std::vector<int> order(c->resident_bands);
-      for (int b = 0; b < c->resident_bands; b++) order[b] = b;
+      std::vector<int> order(c->plan.resident_bands);
+      for (int b = 0; b < c->plan.resident_bands; b++) order[b] = b;
       std::sort(order.begin(), order.end(), [&](int x, int y) { return h[x * 8 + 4] < h[y * 8 + 4]; });
-      for (int k = 0; k < 6 && k < c->resident_bands; k++) {
+      for (int k = 0; k < 6 && k < c->plan.resident_bands; k++) {
         const int b = order[k];
         fprintf(stderr, "  band %3d:", b);
         for (int i = 0; i < 7; i++) fprintf(stderr, " %8.1f", (double)h[b * 8 + i] / n);
@@ -1414,8 +1363,8 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
                      c0->pitch, c0->p.nx, sl0.accel_row);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
   const int rec = bt->armed[kRecProbes] > 0 ? kRecProbes : (bt->armed[kRecFrames] > 0 ? kRecFrames : kRecNone);
-  const void* kernel = resident_kernel(c0->p.nx, c0->resident_rows, c0->resident_joint, rec, true);
-  const int bands = c0->resident_bands;
+  const void* kernel = resident_kernel(c0->p.nx, c0->plan.resident_rows, c0->plan.resident_joint, rec, true);
+  const int bands = c0->plan.resident_bands;
   for (int t = 0; t < n_steps;) {
     const int n = (n_steps - t < kResidentChunk) ? n_steps - t : kResidentChunk;
     const lbm::ResidentMember* tab = bt->table + bt->cur * n_members;
@@ -1525,7 +1474,7 @@ int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
 
   int flushed_upto = c->steps_done;
   int t_first = 0;
-  if (c->use_graph) {
+  if (c->plan.use_graph) {
     if (replay_chunks(c, n_steps, flushed_upto, &t_first) != LBM_SUCCESS) return LBM_FAILURE;
     flushed_upto += t_first;
   }
@@ -1533,15 +1482,15 @@ int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
 
   // passes launch by launch: pass_steps timesteps per pass where enabled and that many remain, else two, else one
   static const int ext_events = env_int("LBM_EXT_EVENTS", 1);
-  const int slots_per_pass = c->tile_steps > c->pass_steps ? c->tile_steps : c->pass_steps;
+  const int slots_per_pass = c->plan.tile_steps > c->plan.pass_steps ? c->plan.tile_steps : c->plan.pass_steps;
   int m = 0;  // pass counter (event parity)
   for (int t = t_first; t < n_steps; m++) {
-    const int tile = (!halo && c->tile_steps) ? (c->tile_steps < n_steps - t ? c->tile_steps : n_steps - t) : 0;
-    const int k = (!tile && c->fuse2 && n_steps - t >= 2) ? (n_steps - t >= c->pass_steps ? c->pass_steps : 2) : 0;
+    const int tile = (!halo && c->plan.tile_steps) ? (c->plan.tile_steps < n_steps - t ? c->plan.tile_steps : n_steps - t) : 0;
+    const int k = (!tile && c->plan.fuse2 && n_steps - t >= 2) ? (n_steps - t >= c->plan.pass_steps ? c->plan.pass_steps : 2) : 0;
     const int adv = tile ? tile : (k ? k : 1);
     const bool last = (t + adv == n_steps);
     // full-depth passes of a single periodic slab as band groups; every other pass behind a join
-    const bool grouped = (c->band_groups > 1 && !halo && !tile && k == c->pass_steps);
+    const bool grouped = (c->plan.band_groups > 1 && !halo && !tile && k == c->plan.pass_steps);
     if (grouped) {
       if (!c->groups_forked && group_fork(c, m) != LBM_SUCCESS) return LBM_FAILURE;
       if (issue_grouped_pass(c, m, k, !last, ext_events != 0) != LBM_SUCCESS) return LBM_FAILURE;
@@ -1575,7 +1524,7 @@ int run_steps(lbm_ctx* c, int n_steps, float* kernel_ms) {
   if (c->halo != HALO_SELF && c->halo_mode != LBM_HALO_SYNC) return run_steps_stale(c, n_steps, kernel_ms);
 
   // resident or per-pass: decided once per call, whether a recorder (frames or probes) is armed or not
-  const bool resident = c->resident && n_steps >= c->resident_min_steps;
+  const bool resident = c->plan.resident && n_steps >= c->plan.resident_min_steps;
   if (c->rec.kind != kRecNone && !resident) {
     // per-pass kernels: the call runs as the sub-calls that end at its recorder steps, each followed by its frame or
     // its sample row (the step kernels themselves record nothing)
@@ -1905,11 +1854,11 @@ int build_slab(lbm_ctx* c, int s, const ObstacleSource& obst, const float* cells
   HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_halo, sl.comm));
   HIP_TRY(LBM_FAILURE, hipEventCreate(&sl.ev_t0));
   HIP_TRY(LBM_FAILURE, hipEventCreate(&sl.ev_t1));
-  if (c->band_groups > 1) {
-    for (int g = 0; g < c->band_groups - 1; g++) HIP_TRY(LBM_FAILURE, hipStreamCreateWithFlags(&sl.group_extra[g], hipStreamNonBlocking));
+  if (c->plan.band_groups > 1) {
+    for (int g = 0; g < c->plan.band_groups - 1; g++) HIP_TRY(LBM_FAILURE, hipStreamCreateWithFlags(&sl.group_extra[g], hipStreamNonBlocking));
     for (int i = 0; i < 2; i++) {
       HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_gs[i], hipEventDisableTiming));
-      for (int g = 0; g < c->band_groups; g++) HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_gi[i][g], hipEventDisableTiming));
+      for (int g = 0; g < c->plan.band_groups; g++) HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_gi[i][g], hipEventDisableTiming));
     }
   }
 
@@ -1921,18 +1870,18 @@ int build_slab(lbm_ctx* c, int s, const ObstacleSource& obst, const float* cells
     HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.lat_alloc[i], 0, lat_bytes, sl.compute));
     sl.lat[i] = sl.lat_alloc[i] + (size_t)kHaloRows * c->row_pitch;
   }
-  HIP_TRY(LBM_FAILURE, hipMalloc(&sl.partials, (size_t)kPartSlots * c->part_stride * sizeof(float)));
-  HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.partials, 0, (size_t)kPartSlots * c->part_stride * sizeof(float), sl.compute));
+  HIP_TRY(LBM_FAILURE, hipMalloc(&sl.partials, (size_t)kPartSlots * c->plan.part_stride * sizeof(float)));
+  HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.partials, 0, (size_t)kPartSlots * c->plan.part_stride * sizeof(float), sl.compute));
   HIP_TRY(LBM_FAILURE, hipMalloc(&sl.tot_u, (size_t)(c->capacity > 0 ? c->capacity : 1) * sizeof(double)));
   HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.tot_u, 0, (size_t)(c->capacity > 0 ? c->capacity : 1) * sizeof(double), sl.compute));
   HIP_TRY(LBM_FAILURE, hipMalloc(&sl.scratch, 2 * kSumBlocks * sizeof(double)));
   HIP_TRY(LBM_FAILURE, hipMalloc(&sl.flushed_dev, sizeof(int)));
-  if (c->resident) {
+  if (c->plan.resident) {
     // granules start at tag 0 = "nothing"; tags are global step indices + 1, so they never need clearing again
     const size_t gran_bytes = resident_gran_bytes(c);
     HIP_TRY(LBM_FAILURE, hipMalloc(&sl.res_gran, gran_bytes));
     HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.res_gran, 0, gran_bytes, sl.compute));
-    HIP_TRY(LBM_FAILURE, hipMalloc(&sl.res_part, (size_t)kResidentChunk * c->resident_bands * sizeof(float)));
+    HIP_TRY(LBM_FAILURE, hipMalloc(&sl.res_part, (size_t)kResidentChunk * c->plan.resident_bands * sizeof(float)));
     HIP_TRY(LBM_FAILURE, hipMalloc(&sl.res_status, sizeof(int)));
     HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.res_status, 0, sizeof(int), sl.compute));
     HIP_TRY(LBM_FAILURE, hipHostMalloc(&sl.res_status_host, sizeof(int)));
@@ -2031,65 +1980,163 @@ int build_slab(lbm_ctx* c, int s, const ObstacleSource& obst, const float* cells
   return LBM_SUCCESS;
 }
 
-// Which step kernel advances a decomposition of the grid into `parts` row slabs (in one process or over ranks), and how
-// many timesteps it takes per pass -- from global numbers only, so every rank of a multi-process run decides alike.
-// create_common and the host-only query lbm_plan_halo_depth share it.
-struct StreamPlan { bool vec4; int fuse2, lane_cells, pass_steps; };
-StreamPlan plan_stream(const lbm_params* params, int parts, bool halo_on, int math_mode) {
-  StreamPlan pl;
-  // 4 cells per lane need nx % 4 == 0; tiny single-slab grids are latency-bound and run faster with one
-  // cell per lane (4x the waves, a quarter of the dependent arithmetic per lane: 128^2 3.2 vs 5.0 us per
-  // step, 256^2 3.8 vs 5.2; from 512^2 on the 4-cell kernel wins).  Asking for the stream kernel,
-  // which exists in the 4- and 2-cell forms only, implies vec4; so do halos.
-  pl.vec4 = (params->nx % 4 == 0) &&
-            env_int("LBM_VEC4", ((long)params->nx * params->ny >= 128L * 1024 || env_int("LBM_FUSE2", 0) == 1 || halo_on) ? 1 : 0);
-  const int min_rows = params->ny / (parts > 0 ? parts : 1);  // the thinnest slab of a balanced partition
-  const long min_cells = (long)params->nx * min_rows;
-  // Across slabs / ranks a pass costs one exchange and ~10 runtime calls per slab whatever it computes, so
-  // several timesteps per pass always pay there (1024^2 over 2/4/8 slabs on one device: 45/74/97 us per step
-  // vs 70/113/125 one-step; 2048^2 over 8: 96 vs 261).
-  pl.fuse2 = (pl.vec4 && env_int("LBM_FUSE2", (min_cells >= 300L * 1024 || halo_on) ? 1 : 0)) ? 1 : 0;
-  pl.lane_cells = env_int("LBM_LANE_CELLS", min_cells >= 7L * 512 * 1024 ? 4 : 2) == 2 ? 2 : 4;  // from 3.5 Mi cells
-  // Timesteps per pass of the stream kernel.  The two-step kernel at 8192^2 is bound by DRAM traffic (round-2 PMC:
-  // 5.4-5.8 TB/s at the memory controllers whatever the band height or the arithmetic), so the 4-cell form runs more
-  // steps per pass: K = 3 (stepk_stream, 2 waves per SIMD, next row prefetched) 0.345 vs 0.47-0.49 ms per step, at
-  // which point it is bound by VALU issue again (K = 4 with scalar arithmetic: 0.36); with the collision on PAIRS of
-  // cells (stepk_pk: v_pk_* instructions, 108 instead of 155 lane-instructions per update) K = 4 pays: 0.275-0.285.
-  // The packed kernel exists for the exact arithmetic only; the 2-cell form for K = 2 only.
-  // The two-cell form (one pair per lane, twice the waves: mid-size grids) takes two halo lanes per side beyond two
-  // steps and runs K = 3 as the packed kernel (124 VGPRs, 4 waves per SIMD): 1024^2 9.4 vs 10.7 us (K = 2), 1280^2
-  // 12.4 vs 15.2 (four-cell K = 4), 1536^2 15.2 vs 20.9, 1792^2 20.2 vs 22.3; from 2048^2 the four-cell form wins
-  // (24.9 vs 25.6-27.5).
-  // FAST math (reciprocal + FMA, scalar) is the faster arithmetic only in the one-step and LDS-tile kernels.  The
-  // multi-step stream kernels run the packed EXACT collision in both modes: it is faster than the scalar fast form
-  // (8192^2: 0.27 vs 0.345 ms per step) and at K = 4 it already sits at the DRAM bound of its access pattern (5.8 GB per
-  // launch at 5.4-5.8 TB/s), so a packed fast form could not be faster -- and exact results meet the fast mode's
-  // tolerance trivially.  LBM_PACKED=0 selects the scalar kernels (fast math: K = 3 / 2).
-  (void)math_mode;
-  const bool exact_packed = env_int("LBM_PACKED", 1) != 0;
-  pl.pass_steps = env_int("LBM_PASS_STEPS", pl.lane_cells == 4 ? (exact_packed ? 4 : 3) : (exact_packed ? 3 : 2));
-  if (pl.pass_steps < 2 || pl.pass_steps > kHaloRows) pl.pass_steps = 2;
-  if (pl.lane_cells != 4 && !exact_packed) pl.pass_steps = 2;  // the scalar two-cell kernel (step2_stream) is two-step
-  // across slabs a K-step pass needs slabs of at least 2K rows (the stream kernel at all: 4); a periodic slab at least K
-  if (halo_on && min_rows < 2 * pl.pass_steps) pl.pass_steps = 2;
-  if (halo_on && min_rows < 4) pl.fuse2 = 0;
-  if (min_rows < pl.pass_steps) pl.pass_steps = 2;
-  return pl;
+// ---- create: the steps of create_common, in its order --------------------------------------------------------------
+// 1. everything that can be refused before a context exists; *ndev: the visible devices
+bool validate_create(const lbm_params* params, const ObstacleSource& obst, int n_slabs, int math_mode, int rank, int world, int* ndev) {
+  if (!validate_params(params)) LBM_FAIL(false, "lbm_create: invalid parameters");
+  if (!obst.data) LBM_FAIL(false, "lbm_create: obstacles is NULL");
+  if (obst.kind == OBST_TILE && (obst.tile_nx < 1 || obst.tile_ny < 1))
+    LBM_FAIL(false, "lbm_create: invalid obstacle tile %dx%d", obst.tile_nx, obst.tile_ny);
+  if (math_mode != LBM_MATH_EXACT && math_mode != LBM_MATH_FAST)
+    LBM_FAIL(false, "lbm_create: unknown math mode %d", math_mode);
+  if (n_slabs < 1 || n_slabs > kMaxSlabs) LBM_FAIL(false, "lbm_create: n_gpus must be 1..%d", kMaxSlabs);
+  if (hipGetDeviceCount(ndev) != hipSuccess || *ndev < 1)
+    LBM_FAIL(false, "lbm_create: no HIP device available (this library has no CPU path)");
+  // rows of this context, then of its slabs: no part thinner than 2 rows
+  int row_count = 0;
+  if (lbm_partition_rows(params->ny, world, rank, nullptr, &row_count) != LBM_SUCCESS) return false;
+  if (n_slabs > 1 && lbm_partition_rows(row_count, n_slabs, 0, nullptr, nullptr) != LBM_SUCCESS) return false;
+  return true;
+}
+
+// 2. how the halo rows travel ...
+int decide_halo_kind(const lbm_ctx* c, int ndev) {
+  const bool force_halo = env_int("LBM_FORCE_HALO", 0) != 0;
+  if (c->world > 1 || (c->ranked && force_halo)) return c->hosted ? HALO_HOST : HALO_RCCL;
+  if (c->n_slabs == 1 && !force_halo) return HALO_SELF;
+  const char* h = getenv("LBM_HALO");
+  const bool distinct = (c->n_slabs <= ndev);
+  return (h && !strcmp(h, "memcpy")) ? HALO_MEMCPY : (h && !strcmp(h, "rccl")) ? HALO_RCCL : (distinct ? HALO_RCCL : HALO_MEMCPY);
+}
+// ... and how fresh they are (LBM_HALO_MODE); the experimental modes say so once per process and mode
+void warn_experimental_halo_mode(const lbm_ctx* c, bool* warned, const char* text) {
+  if (*warned || c->halo == HALO_SELF || c->rank != 0) return;
+  *warned = true;
+  fprintf(stderr, "lbm_hip: LBM_HALO_MODE=%s\n", text);
+}
+int decide_halo_mode(const lbm_ctx* c) {
+  static bool warned_stale = false, warned_freshest = false;
+  const char* hm = getenv("LBM_HALO_MODE");
+  if (hm && !strcmp(hm, "stale")) {
+    warn_experimental_halo_mode(c, &warned_stale,
+                                "stale is EXPERIMENTAL: halo rows one pass old; results differ from the "
+                                "synchronous run (measured up to 4.7 % on av_vels mid-transient, outside check.py's 1 % rule)");
+    return LBM_HALO_STALE;
+  }
+  if (hm && !strcmp(hm, "freshest") && !c->hosted) {
+    warn_experimental_halo_mode(c, &warned_freshest,
+                                "freshest is EXPERIMENTAL: every halo row is this step's or the step before's, "
+                                "whichever has arrived; results differ from the synchronous run and from run to run");
+    return LBM_HALO_FRESHEST;
+  }
+  return LBM_HALO_SYNC;
+}
+
+// 3. what plan_kernels is asked: the grid and its decomposition, and what the devices say
+PlanInput plan_input(const lbm_ctx* c, int ndev) {
+  PlanInput in;
+  in.nx = c->p.nx;
+  in.ny = c->p.ny;
+  in.world = c->world;
+  in.rank = c->rank;
+  in.n_slabs = c->n_slabs;
+  in.halo = c->halo;
+  in.n_devices = ndev;
+  const int dev = c->slab[0].device;
+  if (hipSetDevice(dev) != hipSuccess || hipDeviceGetAttribute(&in.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) in.cus = 0;
+  in.distinct_devices = c->n_slabs > 1;
+  for (int a = 0; a < c->n_slabs; a++)
+    for (int b = a + 1; b < c->n_slabs; b++)
+      if (c->slab[a].device == c->slab[b].device) in.distinct_devices = false;
+  return in;
+}
+
+// 4. the plan's resident candidate stands if the device can hold a workgroup of its kernel on a CU
+bool resident_fits(const lbm_ctx* c) {
+  int per_cu = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resident_kernel(c->p.nx, c->plan.resident_rows, c->plan.resident_joint, kRecNone),
+                                                      c->p.nx, 0) == hipSuccess && per_cu >= 1;
+}
+
+// 5. the slabs: their rows as the plan counted them, their buffers, mask and lattice
+int build_slabs(lbm_ctx* c, const PlanInput& in, const ObstacleSource& obst, const float* cells_aos) {
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    const SlabRows r = lbm_plan::slab_rows(in, c->plan.vec4, s);
+    sl.row_first = r.row_first;
+    sl.rows = r.rows;
+    sl.accel_row = r.accel_row;
+    sl.accel_row2 = r.accel_row2;
+    sl.blocks_main = r.blocks_main;
+    sl.blocks_boundary = r.blocks_boundary;
+    if (c->halo != HALO_SELF && sl.rows < 2) LBM_FAIL(LBM_FAILURE, "lbm_create: a slab needs at least 2 rows");
+  }
+  for (int s = 0; s < c->n_slabs; s++)
+    if (build_slab(c, s, obst, cells_aos) != LBM_SUCCESS) return LBM_FAILURE;
+  return LBM_SUCCESS;
+}
+
+// 6. what carries the halo rows between processes / slabs: pinned staging buffers for the host's message passing, or
+// RCCL communicators
+int connect_ranks(lbm_ctx* c, const void* unique_id) {
+  if (c->hosted) {
+    const size_t bytes = (size_t)kHaloRows * c->row_pitch * sizeof(float);
+    for (int i = 0; i < 2; i++)
+      if (hipHostMalloc(&c->host_send[i], bytes) != hipSuccess || hipHostMalloc(&c->host_recv[i], bytes) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_create_rank_hosted: cannot allocate the pinned exchange buffers");
+  } else if (c->ranked) {
+    // one process per GPU: the communicator spans the ranks (also used for the av_vels reduce)
+    ncclUniqueId id;
+    memcpy(&id, unique_id, sizeof(id));
+    RcclApi* nc = rccl();
+    ncclResult_t res = ncclSuccess;
+    if (!nc || hipSetDevice(c->slab[0].device) != hipSuccess ||
+        (res = nc->CommInitRank(&c->slab[0].nccl, c->world, id, c->rank)) != ncclSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_create_rank: ncclCommInitRank(rank %d of %d) failed: %s", c->rank, c->world,
+               nc ? nc->GetErrorString(res) : g_rccl_error);
+  } else if (c->halo == HALO_RCCL) {
+    ncclComm_t comms[kMaxSlabs];
+    int devs[kMaxSlabs];
+    for (int s = 0; s < c->n_slabs; s++) devs[s] = c->slab[s].device;
+    RcclApi* nc = rccl();
+    ncclResult_t res = ncclSuccess;
+    if (!nc || (res = nc->CommInitAll(comms, c->n_slabs, devs)) != ncclSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_create: ncclCommInitAll failed: %s (set LBM_HALO=memcpy when slabs share a device)",
+               nc ? nc->GetErrorString(res) : g_rccl_error);
+    for (int s = 0; s < c->n_slabs; s++) c->slab[s].nccl = comms[s];
+  }
+  return LBM_SUCCESS;
+}
+
+// 7. global number of fluid cells (av_velocity's divisor): the slabs' device-side counts, summed over the ranks
+// (the reference counts on rank 0 while parsing, MPI_Waitall/d2q9-bgk.c:794-804)
+int count_fluid_cells(lbm_ctx* c) {
+  long long fluid = 0;
+  for (int s = 0; s < c->n_slabs; s++) fluid += c->slab[s].fluid_cells;
+  if (c->hosted && c->world > 1) {
+    double v = (double)fluid;  // exact: a cell count is below 2^31
+    if (c->host_comm.allreduce_sum(c->host_comm.user, &v, 1) != 0)
+      LBM_FAIL(LBM_FAILURE, "lbm_create_rank_hosted: the host's all-reduce callback failed");
+    fluid = (long long)(v + 0.5);
+  } else if (c->ranked && c->world > 1) {
+    Slab& sl = c->slab[0];
+    long long* dev = reinterpret_cast<long long*>(sl.scratch);
+    if (hipSetDevice(sl.device) != hipSuccess ||
+        hipMemcpy(dev, &fluid, sizeof(fluid), hipMemcpyHostToDevice) != hipSuccess ||
+        !rccl() || g_rccl.AllReduce(dev, dev, 1, ncclInt64, ncclSum, sl.nccl, sl.comm) != ncclSuccess ||
+        hipStreamSynchronize(sl.comm) != hipSuccess ||
+        hipMemcpy(&fluid, dev, sizeof(fluid), hipMemcpyDeviceToHost) != hipSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_create_rank: all-reduce of the fluid-cell count failed");
+  }
+  c->fluid_cells = (int)fluid;
+  return LBM_SUCCESS;
 }
 
 lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, const float* cells_aos,
                        int n_slabs, int math_mode, int rank, int world, const void* unique_id,
                        int device, const lbm_host_comm* host_comm = nullptr) {
-  if (!validate_params(params)) LBM_FAIL(nullptr, "lbm_create: invalid parameters");
-  if (!obst.data) LBM_FAIL(nullptr, "lbm_create: obstacles is NULL");
-  if (obst.kind == OBST_TILE && (obst.tile_nx < 1 || obst.tile_ny < 1))
-    LBM_FAIL(nullptr, "lbm_create: invalid obstacle tile %dx%d", obst.tile_nx, obst.tile_ny);
-  if (math_mode != LBM_MATH_EXACT && math_mode != LBM_MATH_FAST)
-    LBM_FAIL(nullptr, "lbm_create: unknown math mode %d", math_mode);
-  if (n_slabs < 1 || n_slabs > kMaxSlabs) LBM_FAIL(nullptr, "lbm_create: n_gpus must be 1..%d", kMaxSlabs);
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    LBM_FAIL(nullptr, "lbm_create: no HIP device available (this library has no CPU path)");
+  if (!validate_create(params, obst, n_slabs, math_mode, rank, world, &ndev)) return nullptr;
 
   lbm_ctx* c = new lbm_ctx();
   c->p = *params;
@@ -2100,391 +2147,27 @@ lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, con
   c->pitch = (int)round_up(params->nx, 64);
   c->plane_stride = c->pitch + env_int("LBM_PLANE_PAD_FLOATS", 0) / 4 * 4;
   c->row_pitch = 9 * c->plane_stride;
-  c->neigh = env_int("LBM_NEIGH", 0);
-  if (c->neigh < 0 || c->neigh > 2) c->neigh = 0;
-  // nontemporal stores pay once the two lattices no longer fit the 256 MiB Infinity Cache
-  // (measured: +4 % at 4096^2 and above, -2..-20 % at 2048^2 and below; profiles/r01_tuning.md)
-  const double lattice_pair_bytes = 2.0 * 36.0 * (double)params->nx * (double)params->ny;
-  c->nts = env_int("LBM_NTS", lattice_pair_bytes > 512.0 * 1024 * 1024 ? 1 : 0) ? 1 : 0;
-  c->snake = env_int("LBM_SNAKE", 0) ? 1 : 0;
-  // hipGraph replay pays where the loop is bound by the host's launch rate (~3.5 us per launch): measured
-  // 128^2 3.11 vs 3.52 us per step, 128x256 3.22 vs 3.53; no difference from 256^2 on
-  c->use_graph = env_int("LBM_GRAPH", (long)params->nx * params->ny < 64L * 1024 ? 1 : 0) ? 1 : 0;
   c->n_slabs = n_slabs;
-
-  // rows of this context, then of each slab
-  if (lbm_partition_rows(params->ny, world, rank, &c->row_first, &c->row_count) != LBM_SUCCESS) {
-    delete c;
-    return nullptr;
-  }
-  const bool force_halo = env_int("LBM_FORCE_HALO", 0) != 0;
+  const lbm_plan::RowSpan mine = lbm_plan::row_span(params->ny, world, rank);
+  c->row_first = mine.first;
+  c->row_count = mine.count;
   c->ranked = (unique_id != nullptr) || (host_comm != nullptr);
   c->hosted = (host_comm != nullptr);
   if (c->hosted) c->host_comm = *host_comm;
-  if (world > 1 || (c->ranked && force_halo)) c->halo = c->hosted ? HALO_HOST : HALO_RCCL;
-  else if (n_slabs > 1 || force_halo) {
-    const char* h = getenv("LBM_HALO");
-    bool distinct = (n_slabs <= ndev);
-    c->halo = (h && !strcmp(h, "memcpy")) ? HALO_MEMCPY
-              : (h && !strcmp(h, "rccl")) ? HALO_RCCL
-              : (distinct ? HALO_RCCL : HALO_MEMCPY);
-  } else c->halo = HALO_SELF;
+  for (int s = 0; s < n_slabs; s++) c->slab[s].device = c->ranked ? device : (s % ndev);
+  c->halo = decide_halo_kind(c, ndev);
+  c->halo_mode = decide_halo_mode(c);
 
-  {
-    const char* hm = getenv("LBM_HALO_MODE");
-    if (hm && !strcmp(hm, "stale")) {
-      c->halo_mode = LBM_HALO_STALE;
-      static bool warned = false;
-      if (!warned && c->halo != HALO_SELF && rank == 0) {
-        warned = true;
-        fprintf(stderr, "lbm_hip: LBM_HALO_MODE=stale is EXPERIMENTAL: halo rows one pass old; results differ from the "
-                        "synchronous run (measured up to 4.7 %% on av_vels mid-transient, outside check.py's 1 %% rule)\n");
-      }
-    } else if (hm && !strcmp(hm, "freshest") && !c->hosted) {
-      c->halo_mode = LBM_HALO_FRESHEST;
-      static bool warned = false;
-      if (!warned && c->halo != HALO_SELF && rank == 0) {
-        warned = true;
-        fprintf(stderr, "lbm_hip: LBM_HALO_MODE=freshest is EXPERIMENTAL: every halo row is this step's or the step before's, "
-                        "whichever has arrived; results differ from the synchronous run and from run to run\n");
-      }
-    }
-  }
+  const PlanInput in = plan_input(c, ndev);
+  c->plan = lbm_plan::plan_kernels(in);
+  if (c->plan.resident && !resident_fits(c)) c->plan = lbm_plan::without_resident(c->plan);
 
-  const bool halo_on = (c->halo != HALO_SELF);
-  const StreamPlan plan = plan_stream(params, world * n_slabs, halo_on, math_mode);
-  c->vec4 = plan.vec4;
-
-  int max_blocks = 0;
-  for (int s = 0; s < n_slabs; s++) {
-    Slab& sl = c->slab[s];
-    int first = 0, count = c->row_count;
-    if (n_slabs > 1 && lbm_partition_rows(c->row_count, n_slabs, s, &first, &count) != LBM_SUCCESS) {
-      delete c;
-      return nullptr;
-    }
-    sl.device = c->ranked ? device : (s % ndev);
-    sl.row_first = c->row_first + first;
-    sl.rows = count;
-    const int lid = params->ny - 2;  // SerialCode/d2q9-bgk.c:223
-    // slab-local index of the lid row; with several slabs it may be one of MY halo rows (-kMaskHalo..-1 or
-    // rows..rows+kMaskHalo-1), which a multi-step pass relaxes redundantly and must accelerate like its owner does
-    sl.accel_row = sl.accel_row2 = lbm::kNoRow;
-    for (int shift = -1; shift <= 1; shift++) {
-      const int local = lid + shift * params->ny - sl.row_first;
-      const bool owned = (local >= 0 && local < sl.rows);
-      const bool in_halo = (c->halo != HALO_SELF) && ((local < 0 && local >= -kMaskHalo) || (local >= sl.rows && local < sl.rows + kMaskHalo));
-      if (owned || in_halo) {
-        if (sl.accel_row == lbm::kNoRow || owned) { if (sl.accel_row != lbm::kNoRow) sl.accel_row2 = sl.accel_row; sl.accel_row = local; }
-        else sl.accel_row2 = local;
-      }
-    }
-    if (c->halo == HALO_SELF) {
-      sl.blocks_main = blocks_for_rows(c, sl.rows);
-      sl.blocks_boundary = 0;
-    } else {
-      if (sl.rows < 2) {
-        raise_error(__LINE__, "lbm_create: a slab needs at least 2 rows");
-        delete c;
-        return nullptr;
-      }
-      sl.blocks_main = blocks_for_rows(c, sl.rows - 2);
-      sl.blocks_boundary = blocks_for_rows(c, 2);
-    }
-    if (sl.blocks_main + sl.blocks_boundary > max_blocks) max_blocks = sl.blocks_main + sl.blocks_boundary;
+  if (build_slabs(c, in, obst, cells_aos) != LBM_SUCCESS || connect_ranks(c, unique_id) != LBM_SUCCESS ||
+      count_fluid_cells(c) != LBM_SUCCESS) {
+    lbm_destroy(c);
+    return nullptr;
   }
-  // ---- which kernel, and its geometry (all measured on MI355X; profiles/r01_tuning.md) --------
-  //   single periodic slab below 300 Ki cells (round 2: the packed two-cell stream kernel wins from 576^2 on: 6.0 vs 7.2 us,
-  //                        640^2 7.2 vs 8.9, 704^2 7.2 vs 9.1; 512^2 5.8 vs 5.4): LDS tiles, 4 or 3 timesteps per launch (step_tile; set further
-  //                        down).  With halos: always several timesteps per pass (fewer exchanges).
-  //   (one timestep per pass, step_vec4 / step_scalar: the odd last step of a run, widths that are not a multiple
-  //                        of 4, LBM_FUSE2=0; it was the default up to 1.5 Mi cells until the two-step kernel stopped
-  //                        computing |u| on its warm-up rows: 768^2 9.8 vs 11.3 us, 1024^2 12.35 vs 13.23, 1152^2 15.3 vs 18.1)
-  //   0.3 .. 3.5 Mi cells : THREE timesteps per pass, 2 cells per lane (one pair, two halo lanes per side: 124 VGPRs,
-  //                        4 waves/SIMD, twice the waves of the 4-cell form; 1024^2 9.4 us vs 10.7 two-step)
-  //   >= 3.5 Mi cells    : FOUR timesteps per pass on pairs of cells, 4 cells per lane (16-byte accesses; us per step,
-  //                        this form | 2-cell two-step: 1024^2 15.1 | 10.7, 1280^2 15.2 | 17.2, 1536^2 20.9 | 22.1,
-  //                        1792^2 22.1 | 28.2; three-step scalar | two-step: 2048^2 31.8 | 35.4, 3072^2 59.0 | 76.0,
-  //                        4096^2 93 | 129, 8192^2 340 | 492; four-step packed: 2048^2 24.9, 4096^2 75.3, 8192^2 277-285)
-  // LBM_FUSE2, LBM_LANE_CELLS, LBM_BAND_ROWS override.  Ranks decide from global numbers only, so
-  // every rank of a multi-process run takes the same path.
-  c->fuse2 = plan.fuse2;
-  c->lane_cells = plan.lane_cells;
-  c->pass_steps = plan.pass_steps;
-  c->halo_lanes = ceil_div(c->pass_steps, c->lane_cells);
-  c->n_strips = ceil_div(params->nx / c->lane_cells > 0 ? params->nx / c->lane_cells : 1, 64 - 2 * c->halo_lanes);
-  // Packed arithmetic (exact mode, 4 cells per lane): on.  With K = 4 two of the three sliding windows live in LDS
-  // (18 KB per wave), which leaves registers to prefetch the next row (216 VGPRs): us per step, this form | packed
-  // without prefetch / LDS | scalar K = 3: 16384^2 1091 | 1097 | 1355, 12288^2 640 | 652 | 838, 6144^2 180 | 187 | 233,
-  // 4096^2 75.3 | 78.1 | 94.7, 3072^2 45.6 | 45.3 | 59.0, 2048^2 24.9 | 26.3 | 31.9; a rank's share through the halo
-  // pipeline 8192x1024 45.1 | 46.7 | 55.3, 8192x2048 77.5 | 81.4 | 98.9, 8192x4096 149 | 152 | 187.
-  c->packed = env_int("LBM_PACKED", 1) ? 1 : 0;  // both math modes (see plan_stream)
-  c->lds_windows = env_int("LBM_LDS_WINDOWS", (c->packed && c->pass_steps == 4) ? 2 : 0);
-  if (c->lds_windows < 0 || c->lds_windows > 2 || !c->packed) c->lds_windows = 0;
-  // scalar K = 4 with prefetch spills (245 + 36 VGPRs); the packed K = 4 needs its LDS windows for it
-  c->prefetch = env_int("LBM_PREFETCH", (c->lane_cells == 4 && (c->pass_steps == 3 || (c->pass_steps == 4 && c->lds_windows == 2))) ? 1 : 0) ? 1 : 0;
-  // strips per XCD chunk: a whole band of strips, for slabs of many rounds of waves only (16384^2, K = 4: 1.033 ms per
-  // step with 67-strip chunks, 1.088 with 34, 1.107 without; K = 3: 12288^2 0.793 vs 0.832).  Elsewhere the band height
-  // packs the waves tightly into rounds (below) and the few empty workgroups of the chunked order spill into an
-  // extra round (4096^2: 0.135 vs 0.093; 8192^2: 0.298 vs 0.288).
-  const bool many_rounds = (long)c->n_strips * ceil_div(c->row_count / n_slabs, 24) >= 16L * 1024;
-  c->xcd_chunk = env_int("LBM_XCD_CHUNK", (c->pass_steps >= 3 && many_rounds) ? c->n_strips : 0);
-  if (c->xcd_chunk < 0 || c->xcd_chunk > c->n_strips) c->xcd_chunk = 0;
-  c->use_stepk = env_int("LBM_STEPK", 0) ? 1 : 0;
-
-  // Band groups (issue_grouped_pass): a single periodic slab issues its full-depth passes as G row groups on their own
-  // streams, so that the next pass of one group fills the end of the current pass of the others.  Default: two groups
-  // where four-step passes run on four-cell lanes (the launches there are one round of waves each, whose last waves
-  // leave most of the chip idle); LBM_BAND_GROUPS overrides (1 = one launch per pass; at most kMaxBandGroups).
-  if (!halo_on && n_slabs == 1 && c->fuse2 && !c->use_graph) {
-    c->band_groups = env_int("LBM_BAND_GROUPS", (c->lane_cells == 4 && c->pass_steps == 4) ? 2 : 1);
-    if (c->band_groups < 1) c->band_groups = 1;
-    if (c->band_groups > kMaxBandGroups) c->band_groups = kMaxBandGroups;
-  }
-  // Band height.  A wave sweeps band_rows + 2 rows.
-  //   4-cell form (256 CUs x 12 waves resident): short bands, by row width -- measured optimum 7 rows at 8192 cells
-  //   per row (8192^2: 0.477-0.480 ms vs 0.481-0.484 at 6, 0.495 at 4; same in the halo pipeline), 4-5 rows for
-  //   narrower and for wider rows (7168^2: 0.384 at 4 vs 0.411 at 7; 6144^2: 0.277 at 5 vs 0.303 at 7; 4096^2
-  //   0.131-0.132 at 4-7; 12288: 5; 16384^2: 2.01 at 4 vs 2.23 at 6).  Fitting whole rounds of resident waves
-  //   does NOT pay here (4096^2: 0.146 with the round model's 23-row bands vs 0.131; 8192x2048: 0.139 vs 0.126).
-  //   2-cell form (mid-size grids, 256 x 20 waves resident): a slab that fits in a few rounds is quantised by
-  //   them -- pick the height that fills k rounds exactly (1536^2: 4 rows = 0.98 rounds 24.0 us, 8 rows 25.3 us).
-  {
-    int pick = (params->nx <= 7168) ? 5 : (params->nx <= 8192 ? 7 : (params->nx <= 12288 ? 5 : 4));
-    const long resident = 256L * 4 * 5;  // 2-cell waves resident at once
-    const long slab_rows = (n_slabs > 1 || world > 1) ? (c->row_count / n_slabs) - 4 : c->row_count;
-    const long rows_eff = slab_rows > 1 ? slab_rows : 1;
-    if (c->lane_cells == 2 && (long)c->n_strips * ceil_div(rows_eff, 8) < 5 * resident) {
-      const long lo = 3;
-      long best_cost = -1;
-      for (int k = 1; k <= 4; k++) {
-        long b = (rows_eff * c->n_strips + k * resident - 1) / (k * resident);
-        if (b < lo) b = lo;
-        if (b > 32) b = 32;
-        const long rounds = ((long)c->n_strips * ceil_div(rows_eff, b) + resident - 1) / resident;
-        const long cost = rounds * (b + 2);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; pick = (int)b; }
-      }
-    }
-    if (c->lane_cells == 2 && c->pass_steps >= 3) {
-      // two-cell packed kernel: these sizes are bound by latency, and the best height is the one that spreads the
-      // slab over one round of two waves per SIMD (2048 waves): 768^2 3, 1024^2 5, 1152^2 6, 1280^2 7-8, 1536^2 10,
-      // 1792^2 14-16 rows (profiles/r02_tuning.md)
-      const long interior = (n_slabs > 1 || world > 1 || halo_on) ? rows_eff + 4 - 2 * c->pass_steps : rows_eff;
-      long b = ((interior > 1 ? interior : 1) * c->n_strips + 2047) / 2048;
-      pick = (int)(b < 3 ? 3 : (b > 64 ? 64 : b));
-    }
-    if (c->lane_cells == 4 && c->pass_steps >= 3) {
-      // K >= 3 (2 waves per SIMD, bound by instruction issue): the waves run in rounds of 2048 and every wave of a round
-      // takes band + 2(K-1) row iterations, so the cost of a band height is rounds x iterations (8192^2, K = 4: 46 rows
-      // = 6086 waves = 2.97 rounds 0.274 ms per step; 55 rows = 2.47 rounds 0.288; 58 rows 0.300; 64 rows 0.309;
-      // 24 / 32 rows 0.293 / 0.296; K = 3: 44 rows = 3.10 rounds 0.389, 46 rows 0.350).  Round 3: heights up to 160
-      // rows -- ONE round of 2040 waves at 8192^2 (137 rows: 6 warm-up rows per 137 instead of per 46) 0.2691 vs
-      // 0.2757 at 46, 0.2736 at 69 (two rounds), 0.284 at 92, 0.334 at 119, 0.321 at 180 (same box).
-      // band groups: the interiors of the G groups are in flight together, and their waves fill the rounds together
-      const int groups = c->band_groups;
-      const long interior = (n_slabs > 1 || world > 1 || halo_on) ? rows_eff + 4 - 2 * c->pass_steps
-                                                                  : (groups > 1 ? rows_eff / groups - 2 * c->pass_steps : rows_eff);
-      const long r_int = interior > 1 ? interior : 1;
-      const int warm = 2 * (c->pass_steps - 1);
-      if (groups * (long)c->n_strips * ceil_div(r_int, 24) >= 16L * 1024) {
-        pick = 32;  // many rounds (XCD-chunked order): flat in the height, 16384^2 24 / 32 / model (48) = 1.078 / 1.077 / 1.098
-      } else {
-        // rounds of 2048 resident waves; a last round that fills at most half of the slots leaves one wave per SIMD,
-        // which then runs at nearly twice the speed
-        double best = -1.0;
-        const int b_max = env_int("LBM_BAND_MAX", 160);
-        for (int b = 8; b <= b_max; b++) {
-          const long waves = groups * (long)c->n_strips * ceil_div(r_int, b);
-          const long full = waves / 2048, rest = waves % 2048;
-          double rounds = (double)full + (rest == 0 ? 0.0 : (rest > 1024 ? 1.0 : 0.6));
-          if (rounds < 1.0) rounds = 1.0;  // a lone wave on a SIMD hides no latency
-          const double cost = rounds * (b + warm);
-          if (best < 0.0 || cost < best) { best = cost; pick = b; }
-        }
-      }
-    }
-    c->band_rows = env_int("LBM_BAND_ROWS", pick);
-  }
-  if (c->band_rows < 1) c->band_rows = 1;
-  if (c->band_groups > 1) {
-    // every group keeps an interior: by default a couple of bands, at least one row when asked for
-    const int interior = c->row_count / c->band_groups - 2 * c->pass_steps;
-    if (interior < (getenv("LBM_BAND_GROUPS") ? 1 : 2 * c->band_rows)) c->band_groups = 1;
-  }
-  for (int s = 0; s < n_slabs; s++) {
-    const int waves = c->n_strips * (ceil_div(c->slab[s].rows, c->band_rows) + 2);
-    if (c->fuse2 && waves > max_blocks) max_blocks = waves;
-  }
-  if (c->band_groups > 1 && grouped_waves(c, c->pass_steps) > max_blocks) max_blocks = grouped_waves(c, c->pass_steps);
-  // LDS-tile kernel (several timesteps per launch) for small single-slab grids: LBM_TILE_STEPS overrides
-  if (!halo_on) {
-    // measured (us per step; one-step kernels | 16x8 tiles, 4 steps per launch | 32x16 tiles, 3 steps per launch):
-    //   128^2 3.14 | 2.09 | -      256^2 3.84 | 2.82 | 3.54    384^2 5.65 | 4.19 | 5.43    448^2 6.14 | 5.44 | 5.26
-    //   512^2 6.56 | 6.02 | 5.34   640^2 9.38 | 8.34 | 8.89    768^2 11.28 | 11.22 | 10.14  896^2 12.70 | 14.7 | 13.8
-    //   1024^2 13.34 | 18.8 | 15.1 -- from there the redundant halo work costs more than the launches it saves
-    // (asking for one of the other kernels by LBM_FUSE2 / LBM_VEC4 takes the tile kernel out of the default)
-    const bool other_kernel_requested = getenv("LBM_FUSE2") || getenv("LBM_VEC4");
-    const long cells = (long)params->nx * params->ny;
-    const int dflt_shape = (cells <= 200L * 1024) ? 0 : 3;
-    const int dflt_steps = (other_kernel_requested || cells >= 300L * 1024) ? 0 : kTileShapes[dflt_shape].kmax;
-    c->tile_steps = env_int("LBM_TILE_STEPS", dflt_steps);
-    c->tile_shape = env_int("LBM_TILE_SHAPE", getenv("LBM_TILE_STEPS") ? (c->tile_steps > 4 ? 1 : 0) : dflt_shape);
-    if (c->tile_shape < 0 || c->tile_shape >= kTileShapeCount) c->tile_shape = 0;
-    if (c->tile_steps < 0 || c->tile_steps > kTileShapes[c->tile_shape].kmax) c->tile_steps = kTileShapes[c->tile_shape].kmax;
-    if (c->tile_steps && tile_count_for(params, c->tile_shape) > max_blocks) max_blocks = tile_count_for(params, c->tile_shape);
-    if (c->tile_steps) c->band_groups = 1;  // (the tile kernel runs every pass)
-    // a graph chunk is kPartSlots timesteps in an even number of passes
-  }
-  c->part_stride = round_up(max_blocks, 64);
-
-  // Resident kernel (lbm::resident_band): one launch advances up to kResidentChunk timesteps with the lattice in
-  // registers, bands of 4 rows x the full width per workgroup, seam rows through L2 granules.  For single periodic
-  // slabs whose bands are all co-resident (at most one workgroup per CU of the device) and whose rows are one lane
-  // per cell wide: the reference's own data sets (128x128 ... 1024x1024).  Both math modes run it (its arithmetic is
-  // the exact one, which meets the fast mode's tolerance and is the faster kernel at these sizes).  Asking for
-  // another kernel by any of the selection knobs leaves it off unless LBM_RESIDENT=1 says otherwise.
-  if (!halo_on && n_slabs == 1) {
-    static const char* const selectors[] = {"LBM_FUSE2", "LBM_VEC4", "LBM_TILE_STEPS", "LBM_TILE_SHAPE", "LBM_LANE_CELLS", "LBM_PASS_STEPS",
-                                            "LBM_PACKED", "LBM_BAND_ROWS", "LBM_GRAPH", "LBM_STEPK", "LBM_LDS_WINDOWS", "LBM_PREFETCH",
-                                            "LBM_XCD_CHUNK", "LBM_NEIGH", "LBM_SNAKE", "LBM_NTS"};
-    bool other_kernel = false;
-    for (const char* name : selectors) other_kernel = other_kernel || getenv(name) != nullptr;
-    const int nx = params->nx, ny = params->ny;
-    int cus = 0;
-    const int dev = c->slab[0].device;
-    if (hipSetDevice(dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-    // rows per band: 2 (one pair per lane) where every band still gets a CU of its own, else 4 (us per step, 4 | 2 rows:
-    // 128^2 1.88 | 1.54, 128x256 1.93 | 1.59, 256^2 2.03 | 1.62, 512^2 2.73 | 2.17, 1024x512 4.35 | 3.43)
-    int rows = env_int("LBM_RESIDENT_ROWS", 0);
-    if (rows != 2 && rows != 4) rows = (ny % 2 == 0 && ny / 2 <= cus && ny >= 4) ? 2 : 4;
-    const bool shape_ok = nx % 64 == 0 && nx >= 64 && nx <= 1024 && ny % rows == 0 && ny >= 2 * rows;
-    if (shape_ok && env_int("LBM_RESIDENT", other_kernel ? 0 : 1)) {
-      int per_cu = 0;
-      const int joint = (rows == 4 && nx <= 512 && env_int("LBM_RESIDENT_JOINT", nx <= 256 ? 1 : 0)) ? 1 : 0;
-      if (cus > 0 && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resident_kernel(nx, rows, joint, kRecNone), nx, 0) == hipSuccess &&
-          per_cu >= 1 && ny / rows <= cus) {
-        c->resident = 1;
-        c->resident_rows = rows;
-        c->resident_bands = ny / rows;
-        c->resident_joint = joint;
-        // Grids of at most 128 waves (two-row bands): everything on ONE XCD, one wave per SIMD -- workgroups of four
-        // waves (1, 2 or 4 bands side by side), at most one per CU of the XCD; 8 x the workgroups are launched and
-        // those not dealt to the first XCD leave at once.  Then no seam crosses the fabric (hand-off 0.29 instead of
-        // 0.63 us, tools/hop_flavours.hip): 128^2 1.10 vs 1.36 us per step, 64x128 1.06 vs 1.34, 128x64 1.05 vs 1.42
-        // (two bands per workgroup alone: no change; one XCD with two workgroups per CU: none either).
-        {
-          const int waves_per_band = nx / 64, cus_per_xcd = cus / 8;
-          int group = 1, one_xcd = 0;
-          if (rows == 2 && waves_per_band <= 4) {
-            for (int g = 1; g * waves_per_band <= 4 && !one_xcd; g *= 2)
-              if (c->resident_bands % g == 0 && c->resident_bands / g <= cus_per_xcd) { group = g; one_xcd = 1; }
-          }
-          one_xcd = env_int("LBM_RESIDENT_ONE_XCD", one_xcd) ? 1 : 0;
-          group = env_int("LBM_RESIDENT_GROUP", one_xcd ? group : 1);
-          if (group < 1 || c->resident_bands % group != 0 || nx * group > (nx > 512 ? 1024 : 512)) group = 1;
-          c->resident_group = group;
-          c->resident_one_xcd = one_xcd;
-        }
-        // a launch costs about 20 us before its first step (lattice into registers, back out, reduce, status copy);
-        // measured wall time of one lbm_run(n) + sync, per-pass kernels | resident (tools/resident_crossover.py):
-        // 128^2 n = 4 24.5 | 27.0, n = 8 32.9 | 32.4, n = 16 50.0 | 44.4; 256^2 n = 4 28.8 | 28.4, n = 8 41.0 | 35.4;
-        // 1024^2 n = 4 59.8 | 50.4, n = 8 96.2 | 69.1
-        const long cells = (long)nx * ny;
-        c->resident_min_steps = env_int("LBM_RESIDENT_MIN_STEPS", cells >= 48L * 1024 ? 4 : 8);
-        if (c->resident_min_steps < 1) c->resident_min_steps = 1;
-        c->resident_timeout = (long long)env_int("LBM_RESIDENT_TIMEOUT_MS", 2000) * 100000LL;  // wall_clock64(): 100 MHz
-      }
-    }
-  }
-
-  for (int s = 0; s < n_slabs; s++)
-    if (build_slab(c, s, obst, cells_aos) != LBM_SUCCESS) {
-      lbm_destroy(c);
-      return nullptr;
-    }
-
-  if (c->hosted) {
-    for (int i = 0; i < 2; i++) {
-      const size_t bytes = (size_t)kHaloRows * c->row_pitch * sizeof(float);
-      if (hipHostMalloc(&c->host_send[i], bytes) != hipSuccess || hipHostMalloc(&c->host_recv[i], bytes) != hipSuccess) {
-        raise_error(__LINE__, "lbm_create_rank_hosted: cannot allocate the pinned exchange buffers");
-        lbm_destroy(c);
-        return nullptr;
-      }
-    }
-  } else if (c->ranked) {
-    // one process per GPU: the communicator spans the ranks (also used for the av_vels reduce)
-    ncclUniqueId id;
-    memcpy(&id, unique_id, sizeof(id));
-    RcclApi* nc = rccl();
-    ncclResult_t res = ncclSuccess;
-    if (!nc || hipSetDevice(c->slab[0].device) != hipSuccess ||
-        (res = nc->CommInitRank(&c->slab[0].nccl, world, id, rank)) != ncclSuccess) {
-      raise_error(__LINE__, "lbm_create_rank: ncclCommInitRank(rank %d of %d) failed: %s", rank, world,
-                  nc ? nc->GetErrorString(res) : g_rccl_error);
-      lbm_destroy(c);
-      return nullptr;
-    }
-  } else if (c->halo == HALO_RCCL) {
-    ncclComm_t comms[kMaxSlabs];
-    int devs[kMaxSlabs];
-    for (int s = 0; s < n_slabs; s++) devs[s] = c->slab[s].device;
-    RcclApi* nc = rccl();
-    ncclResult_t res = ncclSuccess;
-    if (!nc || (res = nc->CommInitAll(comms, n_slabs, devs)) != ncclSuccess) {
-      raise_error(__LINE__, "lbm_create: ncclCommInitAll failed: %s (set LBM_HALO=memcpy when slabs share a device)",
-                  nc ? nc->GetErrorString(res) : g_rccl_error);
-      lbm_destroy(c);
-      return nullptr;
-    }
-    for (int s = 0; s < n_slabs; s++) c->slab[s].nccl = comms[s];
-  }
-  // global number of fluid cells (av_velocity's divisor): the slabs' device-side counts, summed over the ranks
-  // (the reference counts on rank 0 while parsing, MPI_Waitall/d2q9-bgk.c:794-804)
-  {
-    long long fluid = 0;
-    for (int s = 0; s < n_slabs; s++) fluid += c->slab[s].fluid_cells;
-    if (c->hosted && world > 1) {
-      double v = (double)fluid;  // exact: a cell count is below 2^31
-      if (c->host_comm.allreduce_sum(c->host_comm.user, &v, 1) != 0) {
-        raise_error(__LINE__, "lbm_create_rank_hosted: the host's all-reduce callback failed");
-        lbm_destroy(c);
-        return nullptr;
-      }
-      fluid = (long long)(v + 0.5);
-    } else if (c->ranked && world > 1) {
-      Slab& sl = c->slab[0];
-      long long* dev = reinterpret_cast<long long*>(sl.scratch);
-      if (hipSetDevice(sl.device) != hipSuccess ||
-          hipMemcpy(dev, &fluid, sizeof(fluid), hipMemcpyHostToDevice) != hipSuccess ||
-          !rccl() || g_rccl.AllReduce(dev, dev, 1, ncclInt64, ncclSum, sl.nccl, sl.comm) != ncclSuccess ||
-          hipStreamSynchronize(sl.comm) != hipSuccess ||
-          hipMemcpy(&fluid, dev, sizeof(fluid), hipMemcpyDeviceToHost) != hipSuccess) {
-        raise_error(__LINE__, "lbm_create_rank: all-reduce of the fluid-cell count failed");
-        lbm_destroy(c);
-        return nullptr;
-      }
-    }
-    c->fluid_cells = (int)fluid;
-  }
-  // One issuing thread per slab when one process drives several slabs on DISTINCT devices (LBM_GPUS=n on a multi-GPU
-  // node): a pass enqueues ~10 runtime calls per slab, 25-30 us on one thread -- more than an 8-GPU pass of 8192^2
-  // takes on the devices.  With several slabs on ONE device it is slower (the runtime serialises calls to a device:
-  // 65 vs 53 us per step for 2 slabs), so there it stays opt-in.  LBM_THREADS=0/1 overrides.
-  bool distinct_devices = n_slabs > 1;
-  for (int a = 0; a < n_slabs; a++)
-    for (int b = a + 1; b < n_slabs; b++)
-      if (c->slab[a].device == c->slab[b].device) distinct_devices = false;
-  const bool want_team = n_slabs > 1 && env_int("LBM_THREADS", distinct_devices ? 1 : 0);
-  // hipGraph replay of the halo pipeline (both streams of every slab, RCCL send/recv or device copies inside the
-  // capture) exists (capture_chunk) but is OFF unless LBM_GRAPH=1: measured on MI355X / ROCm 7.2 it buys nothing
-  // (host issue 11.1 vs 11.6 us per step for a rank with RCCL self-exchange at 256^2: the runtime still enqueues every
-  // node) and hipGraphInstantiate overflows its stack on the larger pipelines (3+ slabs with device-copy halos, a
-  // rank's 20-pass chunk at 8192x1024) -- profiles/r02_tuning.md.  The device-copy transport never uses it.
-  if (c->halo != HALO_SELF && (!getenv("LBM_GRAPH") || c->halo == HALO_HOST)) c->use_graph = 0;
-  if (want_team) {
-    c->use_graph = 0;
+  if (c->plan.want_team) {
     c->team = new SlabTeam();
     c->team->start(n_slabs);
   }
@@ -2552,15 +2235,15 @@ int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate alloc
     if (bt && bt->armed[other] > 0)
       LBM_FAIL(LBM_FAILURE, "%s: a member of this batch has %s armed (%s); a batch records one kind, frames or probes", k.setter,
                o.name, o.setter);
-    if (c->resident) {
+    if (c->plan.resident) {
       // the recorder forms of four-row bands defer the acceleration of the interior pair only (lbm::resident_band): the lid
       // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form must run one workgroup per CU
-      if (c->resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
+      if (c->plan.resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
         LBM_FAIL(LBM_FAILURE, "%s: the lid row %d is not an interior row of a four-row band", k.setter, c->slab[0].accel_row);
       int per_cu = 0;
       HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
       HIP_TRY(LBM_FAILURE, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                               &per_cu, resident_kernel(c->p.nx, c->resident_rows, c->resident_joint, kind), c->p.nx * c->resident_group, 0));
+                               &per_cu, resident_kernel(c->p.nx, c->plan.resident_rows, c->plan.resident_joint, kind), c->p.nx * c->plan.resident_group, 0));
       if (per_cu < 1) LBM_FAIL(LBM_FAILURE, "%s: the resident kernel's %s form does not fit a CU at this shape", k.setter, k.noun);
     }
   }
@@ -2662,7 +2345,12 @@ int lbm_halo_plan(int rows, int parts, int index, int depth, lbm_halo_op out[4])
 int lbm_plan_halo_depth(const lbm_params* params, int parts, int math_mode) {
   if (!validate_params(params) || parts < 1 || (math_mode != LBM_MATH_EXACT && math_mode != LBM_MATH_FAST))
     LBM_FAIL(0, "lbm_plan_halo_depth: bad arguments");
-  const StreamPlan pl = plan_stream(params, parts, true, math_mode);
+  PlanInput in;  // `parts` ranks of one slab each
+  in.nx = params->nx;
+  in.ny = params->ny;
+  in.world = parts;
+  in.halo = HALO_RCCL;
+  const KernelPlan pl = lbm_plan::plan_kernels(in);
   return pl.fuse2 ? pl.pass_steps : 1;
 }
 
@@ -2819,23 +2507,23 @@ int lbm_get_info(const lbm_ctx* c, lbm_info* out) {
   out->world_rank = c->rank;
   out->world_size = c->world;
   const bool stale = (c->halo != HALO_SELF && c->halo_mode != LBM_HALO_SYNC);
-  out->steps_per_launch = (c->tile_steps && c->halo == HALO_SELF) ? c->tile_steps : ((c->fuse2 && !stale) ? c->pass_steps : 1);
+  out->steps_per_launch = (c->plan.tile_steps && c->halo == HALO_SELF) ? c->plan.tile_steps : ((c->plan.fuse2 && !stale) ? c->plan.pass_steps : 1);
   out->halo_mode = c->halo_mode;
-  const bool stream_kernel = c->fuse2 && !stale && !(c->tile_steps && c->halo == HALO_SELF);
-  out->band_rows = stream_kernel ? c->band_rows : 0;
-  out->lane_cells = stream_kernel ? c->lane_cells : 0;
-  out->nontemporal = c->nts;
+  const bool stream_kernel = c->plan.fuse2 && !stale && !(c->plan.tile_steps && c->halo == HALO_SELF);
+  out->band_rows = stream_kernel ? c->plan.band_rows : 0;
+  out->lane_cells = stream_kernel ? c->plan.lane_cells : 0;
+  out->nontemporal = c->plan.nts;
   {
     int adv = 1;
     const int passes = chunk_passes(c, &adv);
-    out->graph_steps = (c->use_graph && !stale) ? passes * adv : 0;
+    out->graph_steps = (c->plan.use_graph && !stale) ? passes * adv : 0;
   }
-  out->resident_steps = c->resident ? kResidentChunk : 0;
-  out->resident_min_steps = c->resident ? c->resident_min_steps : 0;
-  out->resident_rows = c->resident ? c->resident_rows : 0;
-  out->resident_group = c->resident ? c->resident_group : 0;
-  out->resident_one_xcd = c->resident ? c->resident_one_xcd : 0;
-  out->band_groups = stream_kernel ? c->band_groups : 1;
+  out->resident_steps = c->plan.resident ? kResidentChunk : 0;
+  out->resident_min_steps = c->plan.resident ? c->plan.resident_min_steps : 0;
+  out->resident_rows = c->plan.resident ? c->plan.resident_rows : 0;
+  out->resident_group = c->plan.resident ? c->plan.resident_group : 0;
+  out->resident_one_xcd = c->plan.resident ? c->plan.resident_one_xcd : 0;
+  out->band_groups = stream_kernel ? c->plan.band_groups : 1;
   return LBM_SUCCESS;
 }
 
@@ -2918,14 +2606,14 @@ int lbm_set_probes(lbm_ctx* c, int n_probes, const lbm_probe* cells, int every, 
       for (int i = 0; i < n_probes; i++)
         if (cells[i].y >= sl.row_first && cells[i].y < sl.row_first + sl.rows) mine.push_back(i);
       std::stable_sort(mine.begin(), mine.end(), [&](int p, int q) { return cells[p].y < cells[q].y; });
-      const int bands = c->resident ? c->resident_bands : 0;
+      const int bands = c->plan.resident ? c->plan.resident_bands : 0;
       std::vector<unsigned> words(2 * mine.size() + (size_t)bands, 0u);
       for (size_t j = 0; j < mine.size(); j++) {
         const int row = cells[mine[j]].y - sl.row_first;
         words[2 * j] = (unsigned)row;
         words[2 * j + 1] = (unsigned)cells[mine[j]].x | ((unsigned)mine[j] << 20);
         if (bands) {
-          unsigned& w = words[2 * mine.size() + (size_t)(row / c->resident_rows)];
+          unsigned& w = words[2 * mine.size() + (size_t)(row / c->plan.resident_rows)];
           if (((w >> 12) & 0xfffu) == 0) w |= (unsigned)j;
           w += 1u << 12;
           if (row == sl.accel_row) w |= 1u << 31;
@@ -3006,7 +2694,7 @@ int lbm_sync(lbm_ctx* c) {
       LBM_FAIL(LBM_FAILURE, "the resident kernel gave up waiting for a neighbouring band after %.0f ms (status %d): its %d workgroups "
                "were not all running at once -- is another process using the device?  The lattice of this context is no "
                "longer valid; LBM_RESIDENT=0 selects the launch-per-pass kernels, LBM_RESIDENT_TIMEOUT_MS moves the bound",
-               (double)c->resident_timeout / 1e5, status, c->resident_bands);
+               (double)c->plan.resident_timeout / 1e5, status, c->plan.resident_bands);
   }
   return LBM_SUCCESS;
 }
@@ -3240,8 +2928,7 @@ lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* 
     bt->members.push_back(c);
     c->batch = bt;
     const lbm_ctx* c0 = bt->members[0];
-    if (c->halo != HALO_SELF || c->resident != c0->resident || c->resident_bands != c0->resident_bands ||
-        c->resident_group != c0->resident_group || c->resident_one_xcd != c0->resident_one_xcd || c->resident_rows != c0->resident_rows) {
+    if (c->halo != HALO_SELF || !lbm_plan::same_resident_launch(c->plan, c0->plan)) {
       lbm_destroy_batch(bt);
       LBM_FAIL(nullptr, "lbm_create_batch: member %d is not a single periodic slab like member 0 (is LBM_FORCE_HALO set?)", i);
     }
@@ -3257,7 +2944,7 @@ lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* 
   }
   bt->members_per_launch = 1;
   bt->launches = n_members;
-  if (c0->resident) {
+  if (c0->plan.resident) {
     // co-residency, checked here once: one-XCD members take one XCD each; other shapes one workgroup per CU, and no XCD
     // may be dealt more working workgroups than it has CUs (member m's workgroup w runs on XCD w % 8)
     int cus = 0;
@@ -3266,9 +2953,9 @@ lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* 
       LBM_FAIL(nullptr, "lbm_create_batch: cannot query the device's CU count");
     }
     bt->resident = 1;
-    bt->member_wgs = c0->resident_bands / c0->resident_group;
+    bt->member_wgs = c0->plan.resident_bands / c0->plan.resident_group;
     int mpl = 8;
-    if (!c0->resident_one_xcd) {
+    if (!c0->plan.resident_one_xcd) {
       mpl = cus / bt->member_wgs;
       while (mpl > 1 && (long)mpl * ceil_div(bt->member_wgs, 8) > cus / 8) mpl--;
       if (mpl < 1) mpl = 1;
@@ -3319,7 +3006,7 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
              bt->steps_done + n_steps, c0->capacity);
   for (lbm_ctx* c : bt->members)  // every member's records must fit before any member runs
     if (recorder_fits(c, n_steps, "lbm_batch_run") != LBM_SUCCESS) return LBM_FAILURE;
-  if (bt->resident && n_steps >= c0->resident_min_steps) {
+  if (bt->resident && n_steps >= c0->plan.resident_min_steps) {
     if (run_batch_resident(bt, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
     for (lbm_ctx* c : bt->members) {
       c->rec.written += recorded_between(c->rec, c->steps_done, (long long)c->steps_done + n_steps);
@@ -3362,7 +3049,7 @@ int lbm_batch_get_info(const lbm_batch* bt, lbm_batch_info* out) {
   out->members_per_launch = bt->members_per_launch;
   out->launches_per_chunk = bt->launches;
   out->resident_steps = bt->resident ? kResidentChunk : 0;
-  out->resident_min_steps = bt->resident ? c0->resident_min_steps : 0;
+  out->resident_min_steps = bt->resident ? c0->plan.resident_min_steps : 0;
   out->steps_done = bt->steps_done;
   return LBM_SUCCESS;
 }
@@ -3439,7 +3126,7 @@ int lbm_run_until(lbm_ctx* c, int max_steps, int check_every, double tol, int pa
   HIP_TRY(LBM_FAILURE, hipGetLastError());
 
   const int E = check_every, n_seg = max_steps / E, start = c->steps_done;
-  const bool resident = c->resident && E >= c->resident_min_steps;
+  const bool resident = c->plan.resident && E >= c->plan.resident_min_steps;
   // One segment of look-ahead where a segment is ONE launch of the resident kernel: it reads the lattice the segment in
   // front left and writes the other one, so dropping it is `cur ^= 1`.  A longer segment (several launches, which would
   // write both lattices) runs for milliseconds; there the host waits for each verdict first, as on the per-pass path.
@@ -3480,7 +3167,7 @@ int lbm_run_until(lbm_ctx* c, int max_steps, int check_every, double tol, int pa
   if (!steady && max_steps - n_seg * E > 0) {
     // the rest of the cap, shorter than a segment: run as lbm_run runs it, not checked
     const int rest = max_steps - n_seg * E;
-    if (run_passes(c, rest, c->resident && rest >= c->resident_min_steps, false) != LBM_SUCCESS) return LBM_FAILURE;
+    if (run_passes(c, rest, c->plan.resident && rest >= c->plan.resident_min_steps, false) != LBM_SUCCESS) return LBM_FAILURE;
   }
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;  // also reports a resident give-up
   lbm::SteadyState st;
