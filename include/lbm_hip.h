@@ -369,6 +369,41 @@ typedef struct { float u_x, u_y, u_mag, pressure; } lbm_probe_sample; /* 16 byte
 int lbm_set_probes(lbm_ctx* ctx, int n_probes, const lbm_probe* cells, int every, int capacity);
 int lbm_read_probes(lbm_ctx* ctx, int max_samples, lbm_probe_sample* out /* [n][n_probes] */, int* steps, int* n_read);
 
+/* ---- mean flow fields ------------------------------------------------------------------------
+ * The time-averaged field of a flow that never settles (none of the reference's data sets does within maxIters,
+ * SerialCode/d2q9-bgk.c:166; its only fields are the instant write_values prints at the end, :662-743): per-cell sums
+ * over a window of samples, accumulated by the running kernels.  A million samples cost the memory of one.
+ * lbm_set_mean(ctx, every), every >= 1: arms.  From now on, after global timestep tt (0-based, counted from the
+ *   context's creation, the numbering of lbm_set_frames) with tt % every == 0, one sample is taken: at every owned cell
+ *   the four floats lbm_read_final_state gives there for the lattice after tt+1 timesteps, bit for bit (a blocked cell
+ *   gives 0, 0, 0, density * c_sq).  Each cell has four accumulators, each a DOUBLE that starts at +0.0 at arming and is
+ *   updated as acc = acc + (double)sample, in step order.  The value after n samples is therefore defined exactly,
+ *   whatever the calls, chunks, launches or kernels that produced it: it is what a float64 loop over the per-step
+ *   final states gives.  (Sequential fp32 sums lose four to five digits over 10^5..10^6 samples of a value near 0.05.)
+ *   There is no capacity: an armed lbm_run / lbm_batch_run never fails for lack of room.  Memory: 4 * 8 bytes per owned
+ *   cell per slab, four planes double[rows][nx]; if they cannot be allocated the call fails, says the size, and leaves
+ *   the context disarmed.  every == 0 disarms and frees; arming again zeroes the sums and the count.
+ *   Recording never changes the lattice or av_vels.  Calls that run the resident kernel accumulate inside it
+ *   (bit-identical lattice and av_vels); other calls run as the sub-calls that end at their sample steps, each followed
+ *   by one accumulation pass (lattice and av_vels equal those of the same run issued as calls split there; every == 1:
+ *   one-step passes -- correct, not fast; every a multiple of 4 keeps full-depth passes).
+ *   Works on lbm_create / lbm_create_tiled contexts of any number of slabs and on batch members (each its own every;
+ *   members arm independently).
+ *   Refused: negative every; rank contexts (lbm_create_rank*); LBM_HALO_STALE / LBM_HALO_FRESHEST (and
+ *   lbm_set_halo_mode to those while armed); a context whose frames or probes are armed (and lbm_set_frames /
+ *   lbm_set_probes while the mean fields are: one recorder per context; in a batch one KIND of recorder per batch);
+ *   lbm_run_until / lbm_batch_run_until while armed (a dropped look-ahead segment would have added its samples); on
+ *   resident shapes with four-row bands, a lid row that is not an interior row of a band, and any shape whose mean form
+ *   of the resident kernel does not fit a CU (the checks lbm_set_frames makes, against this form).
+ * lbm_read_mean: the sums of the owned rows of all slabs, double[row_count * nx] each, row-major (y * nx + x); any of the
+ *   four may be NULL; *n_samples (may be NULL) = samples since arming.  With all four NULL it only reports n_samples.
+ *   It does NOT reset: for a windowed mean read, then arm again.  Synchronises like the other readers (so a resident
+ *   give-up is reported here too).  Fails on a context whose mean fields are not armed.
+ */
+int lbm_set_mean(lbm_ctx* ctx, int every);
+int lbm_read_mean(lbm_ctx* ctx, double* sum_u_x, double* sum_u_y, double* sum_u_mag, double* sum_pressure,
+                  long long* n_samples);
+
 /* ---- steady-state runs ----------------------------------------------------------------------
  * The reference runs a fixed number of timesteps (maxIters, SerialCode/d2q9-bgk.c:166); none of its data sets has
  * stopped changing by then.  lbm_run_until advances the lattice until its average velocity has, with the decision taken

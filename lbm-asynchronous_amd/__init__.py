@@ -13,7 +13,7 @@ Reference interfaces mirrored (``/root/reference/SerialCode/d2q9-bgk.c``):
 ``t_param`` (:66-75) -> :class:`Params`; ``initialise`` file formats (:460-613) ->
 :func:`read_params`, :func:`read_obstacles`; the ``timestep``/``av_velocity`` loop (:166-170) ->
 :meth:`Engine.run`, for many lattices at once :meth:`Batch.run`; ``write_values`` (:662-743) ->
-:func:`write_final_state`, :func:`write_av_vels`.
+:func:`write_final_state`, :func:`write_av_vels`; its time average :meth:`Engine.mean`, :func:`write_mean_state`.
 """
 from __future__ import annotations
 
@@ -47,7 +47,7 @@ ABI_SYMBOLS = (
     "lbm_create_rank_hosted_tiled", "lbm_destroy",
     "lbm_get_info", "lbm_set_halo_mode", "lbm_read_halo_log", "lbm_run", "lbm_sync", "lbm_run_timed", "lbm_read_av_vels", "lbm_read_cells",
     "lbm_read_final_state", "lbm_av_velocity", "lbm_total_density", "lbm_calc_reynolds",
-    "lbm_set_frames", "lbm_read_frames", "lbm_set_probes", "lbm_read_probes", "lbm_run_until", "lbm_batch_run_until",
+    "lbm_set_frames", "lbm_read_frames", "lbm_set_probes", "lbm_read_probes", "lbm_set_mean", "lbm_read_mean", "lbm_run_until", "lbm_batch_run_until",
     "lbm_create_batch", "lbm_batch_member", "lbm_batch_run", "lbm_batch_sync", "lbm_batch_get_info", "lbm_destroy_batch",
 )
 
@@ -188,6 +188,8 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_read_frames.argtypes = [P, I, P, P, PI]; lib.lbm_read_frames.restype = I
     lib.lbm_set_probes.argtypes = [P, I, P, I, I]; lib.lbm_set_probes.restype = I
     lib.lbm_read_probes.argtypes = [P, I, P, P, PI]; lib.lbm_read_probes.restype = I
+    lib.lbm_set_mean.argtypes = [P, I]; lib.lbm_set_mean.restype = I
+    lib.lbm_read_mean.argtypes = [P, P, P, P, P, ctypes.POINTER(ctypes.c_longlong)]; lib.lbm_read_mean.restype = I
     lib.lbm_run_until.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CSteadyResult)]
     lib.lbm_run_until.restype = I
     lib.lbm_batch_run_until.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CSteadyResult), PI]
@@ -485,6 +487,33 @@ class Engine:
                                                   steps.ctypes.data, ctypes.byref(n)))
         return steps[:n.value].copy(), samples[:n.value].copy()
 
+    # -- mean flow fields (lbm_set_mean / lbm_read_mean) ----------------------------------------
+    def set_mean(self, every: int) -> None:
+        """Accumulate u_x, u_y, |u| and pressure of every owned cell after every global timestep tt with tt % every == 0,
+        bit for bit what final_state() gives after tt + 1 steps, into float64 sums on the device.  every == 0 disarms;
+        arming again zeroes the sums and the count."""
+        _check(self.lib, self.lib.lbm_set_mean(self.handle, _mean_args(every)))
+
+    def mean_sums(self) -> tuple[dict, int]:
+        """The sums since arming and the number of samples: ({u_x, u_y, u, pressure: float64 (row_count, nx)}, n).
+        Reading does not reset them."""
+        rows = self.info()["row_count"]
+        f = {k: np.zeros((rows, self.params.nx), dtype=np.float64) for k in ("u_x", "u_y", "u", "pressure")}
+        n = ctypes.c_longlong()
+        _check(self.lib, self.lib.lbm_read_mean(self.handle, f["u_x"].ctypes.data, f["u_y"].ctypes.data, f["u"].ctypes.data,
+                                                f["pressure"].ctypes.data, ctypes.byref(n)))
+        return f, int(n.value)
+
+    def mean(self) -> dict:
+        """The mean fields over the samples since arming: the sums divided by their number, float64, under the keys of
+        final_state(), plus "samples"."""
+        sums, n = self.mean_sums()
+        if n == 0:
+            raise LbmError("mean: no sample has been taken since the mean fields were armed")
+        out = {k: v / float(n) for k, v in sums.items()}
+        out["samples"] = n
+        return out
+
     # -- results -----------------------------------------------------------------------------
     def av_vels(self, n: int | None = None) -> np.ndarray:
         n = self.info()["steps_done"] if n is None else n
@@ -757,6 +786,22 @@ def _probe_args(cells, every, capacity) -> tuple[list, int, int]:
     if flat and every > 0 and capacity < 1:
         raise LbmError(f"set_probes: capacity {capacity}, at least one row of samples is needed")
     return flat, int(every), int(capacity)
+
+
+def _mean_args(every) -> int:
+    """Engine.set_mean's argument checks (no device needed)."""
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)):
+        raise LbmError(f"set_mean: every must be an integer (got {every!r})")
+    if not 0 <= int(every) <= 2147483647:
+        raise LbmError(f"set_mean: every must lie in [0, 2^31) (got {every})")
+    return int(every)
+
+
+def write_mean_state(path: str, mean: dict, obstacles: np.ndarray) -> None:
+    """mean_state.dat of the command line: final_state.dat's line format, 'x y u_x u_y u pressure obstacle' with
+    '%.12E', from the mean fields (Engine.mean) rounded to float."""
+    write_final_state(path, {k: np.asarray(mean[k], dtype=np.float64).astype(np.float32) for k in ("u_x", "u_y", "u", "pressure")},
+                      np.asarray(obstacles))
 
 
 def write_probes(path: str, cells, steps, samples) -> None:

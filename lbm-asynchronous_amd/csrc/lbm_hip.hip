@@ -181,6 +181,7 @@ struct Slab {
   lbm::probe_vec* probe_ring = nullptr;    // lbm_set_probes: [rows of samples][probes]; a slab writes the probes in its rows
   lbm::ProbeEntry* probe_table = nullptr;  // ... those, sorted by row (+ one word per band where the resident kernel runs)
   int probe_count = 0;                     // ... and how many they are
+  double* mean_sums = nullptr;             // lbm_set_mean: four planes [rows][nx]: sums of u_x, u_y, |u|, pressure of the owned rows
   hipGraphExec_t chunk_graph[2] = {nullptr, nullptr};  // kPartSlots timesteps + their reduce, by lattice parity
   hipStream_t compute = nullptr, comm = nullptr;
   hipEvent_t ev_boundary = nullptr, ev_halo = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
@@ -330,8 +331,9 @@ struct GraphBuilder {
 
 // One recorder per context: after global step tt with tt % every == 0 the running kernels store a record -- a frame
 // (|u| of the owned rows, lbm_set_frames) or a row of probe samples (lbm_set_probes) -- into slot
-// (tt / every - ord0) % slots of every slab's buffer of that kind.
-enum { kRecNone = 0, kRecFrames = 1, kRecProbes = 2 };
+// (tt / every - ord0) % slots of every slab's buffer of that kind.  The mean fields (lbm_set_mean) are the kind without
+// slots: their record is added to per-cell sums, `written` counts the samples, `read`, `slots` and `ord0` stay unused.
+enum { kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3, kRecKinds = 4 };
 struct Recorder {
   int kind = kRecNone;
   int every = 0;
@@ -348,13 +350,16 @@ struct RecorderKind {
   const char* setter = "";
   const char* reader = "";
   const char* disarm = "";  // the call that disarms
+  bool slotted = true;      // records wait in `slots` slots until read (false: they are accumulated, no call lacks room)
 };
-constexpr RecorderKind kRecorderKinds[3] = {
+constexpr RecorderKind kRecorderKinds[kRecKinds] = {
     {},
     {.name = "animation frames", .noun = "frames", .record = "frame", .setter = "lbm_set_frames",
      .reader = "lbm_read_frames", .disarm = "lbm_set_frames(ctx, 0, 0)"},
     {.name = "point probes", .noun = "probes", .record = "sample", .setter = "lbm_set_probes",
-     .reader = "lbm_read_probes", .disarm = "lbm_set_probes(ctx, 0, NULL, 0, 0)"}};
+     .reader = "lbm_read_probes", .disarm = "lbm_set_probes(ctx, 0, NULL, 0, 0)"},
+    {.name = "mean fields", .noun = "mean fields", .record = "sample", .setter = "lbm_set_mean",
+     .reader = "lbm_read_mean", .disarm = "lbm_set_mean(ctx, 0)", .slotted = false}};
 
 struct lbm_ctx {
   lbm_params p;
@@ -384,7 +389,8 @@ struct lbm_ctx {
   GraphBuilder* builder = nullptr;  // non-null while a chunk is being built: launches become graph nodes
   bool resident_used = false;       // a resident launch is in flight / unchecked: lbm_sync reads its status
   lbm_batch* batch = nullptr;       // member of this batch (lbm_create_batch): advanced, synchronised and freed by it
-  Recorder rec;                     // the one recorder: animation frames (lbm_set_frames) or point probes (lbm_set_probes)
+  Recorder rec;                     // the one recorder: animation frames (lbm_set_frames), point probes (lbm_set_probes) or
+                                    // mean fields (lbm_set_mean)
   std::vector<lbm_probe> probe_cells;  // the probed global cells, in the caller's order (a probes row has that many samples)
   // steady-state runs (lbm_run_until), allocated by the first such call
   lbm::SteadyState* steady_state = nullptr;  // device: what the checks of the current call have found
@@ -410,7 +416,8 @@ struct lbm_batch {
   int* status_host = nullptr;       // pinned copy behind every run; every member's lbm_sync reports it
   lbm::ResidentFrames* frame_table = nullptr;  // device: [members], allocated when the first member arms frames
   lbm::ResidentProbes* probe_table = nullptr;  // device: [members], allocated when the first member arms probes
-  int armed[3] = {0, 0, 0};         // members with a recorder of each kind armed: batched launches run that kind's kernel
+  lbm::ResidentMean* mean_table = nullptr;     // device: [members], allocated when the first member arms the mean fields
+  int armed[kRecKinds] = {0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
                                     // (a batch records one kind, so at most one count is non-zero)
   // steady-state runs (lbm_batch_run_until), allocated by the first such call
   lbm::SteadyState* steady_state = nullptr;    // device: [members]
@@ -1235,20 +1242,20 @@ size_t resident_gran_bytes(const lbm_ctx* c) {
 // bands, MAXT 1024 with four-row bands, MAXT 512 with four-row bands relaxed jointly or not
 template <bool BATCH, int REC>
 const void* resident_form(int shape) {
-  constexpr bool F = (REC == kRecFrames), P = (REC == kRecProbes);
+  constexpr bool F = (REC == kRecFrames), P = (REC == kRecProbes), M = (REC == kRecMean);
   switch (shape) {
-    case 0: return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, BATCH, F, P>);
-    case 1: return reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, BATCH, F, P>);
-    case 2: return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, BATCH, F, P>);
-    case 3: return reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, BATCH, F, P>);
-    default: return reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, BATCH, F, P>);
+    case 0: return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, BATCH, F, P, M>);
+    case 1: return reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, BATCH, F, P, M>);
+    case 2: return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, BATCH, F, P, M>);
+    case 3: return reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, BATCH, F, P, M>);
+    default: return reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, BATCH, F, P, M>);
   }
 }
 const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = false) {
   using Form = const void* (*)(int);
-  static const Form forms[2][3] = {
-      {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>},
-      {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>}};
+  static const Form forms[2][kRecKinds] = {
+      {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>, resident_form<false, kRecMean>},
+      {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>, resident_form<true, kRecMean>}};
   return forms[batch][rec]((rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
 }
 
@@ -1262,6 +1269,11 @@ lbm::ResidentProbes probes_entry(const lbm_ctx* c) {
   if (c->rec.kind != kRecProbes) return {};
   const Slab& s0 = c->slab[0];
   return {s0.probe_ring, s0.probe_table, c->rec.every, c->rec.ord0, c->rec.slots, s0.probe_count, c->p.density, 0};
+}
+lbm::ResidentMean mean_entry(const lbm_ctx* c) {
+  if (c->rec.kind != kRecMean) return {};
+  const Slab& s0 = c->slab[0];
+  return {s0.mean_sums, (long)s0.rows * c->p.nx, c->rec.every, c->p.density};
 }
 
 // the fields of ResidentArgs that plain and batched launches share: n timesteps from global step epoch0, last = the
@@ -1290,14 +1302,16 @@ void fill_resident_args(lbm::ResidentArgs& a, const lbm_ctx* c, int n, bool last
 int run_resident(lbm_ctx* c, int n_steps) {
   Slab& sl = c->slab[0];
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-  const bool probes = (c->rec.kind == kRecProbes);
+  const bool probes = (c->rec.kind == kRecProbes), mean = (c->rec.kind == kRecMean);
   for (int t = 0; t < n_steps;) {
     const int n = (n_steps - t < kResidentChunk) ? n_steps - t : kResidentChunk;
     lbm::ResidentFramesArgs fa;  // the FRAMES form's arguments, ResidentArgs + the frame fields; the plain form reads its part
     lbm::ResidentProbesArgs pa;  // the PROBES form's: ResidentArgs + the probe fields
-    lbm::ResidentArgs& a = probes ? static_cast<lbm::ResidentArgs&>(pa) : fa;
+    lbm::ResidentMeanArgs ma;    // the MEAN form's: ResidentArgs + the mean fields
+    lbm::ResidentArgs& a = probes ? static_cast<lbm::ResidentArgs&>(pa) : (mean ? static_cast<lbm::ResidentArgs&>(ma) : fa);
     fa.fr = frames_entry(c);
     pa.pr = probes_entry(c);
+    ma.mn = mean_entry(c);
     fill_resident_args(a, c, n, t + n == n_steps, c->steps_done + t);
     a.src = sl.lat[c->cur];
     a.dst = sl.lat[c->cur ^ 1];
@@ -1312,7 +1326,7 @@ int run_resident(lbm_ctx* c, int n_steps) {
     if (!prof_dev) HIP_TRY(LBM_FAILURE, hipMalloc(&prof_dev, 1024 * 8 * sizeof(long long)));
     a.prof = prof_dev;
 #endif
-    void* args[] = {probes ? static_cast<void*>(&pa) : static_cast<void*>(&fa)};
+    void* args[] = {probes ? static_cast<void*>(&pa) : (mean ? static_cast<void*>(&ma) : static_cast<void*>(&fa))};
     HIP_TRY(LBM_FAILURE, hipLaunchKernel(resident_kernel(c->p.nx, c->plan.resident_rows, c->plan.resident_joint, c->rec.kind),
                                          dim3(c->plan.resident_bands / a.group * (a.one_xcd ? 8 : 1)), dim3(c->p.nx * a.group), args, 0, sl.compute));
     hipLaunchKernelGGL(lbm::reduce_band_partials, dim3(n), dim3(64), 0, sl.compute, (const float*)sl.res_part,
@@ -1362,7 +1376,9 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
                      (const lbm::ResidentMember*)(bt->table + bt->cur * n_members), c0->plane_stride, c0->row_pitch,
                      c0->pitch, c0->p.nx, sl0.accel_row);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
-  const int rec = bt->armed[kRecProbes] > 0 ? kRecProbes : (bt->armed[kRecFrames] > 0 ? kRecFrames : kRecNone);
+  int rec = kRecNone;  // the one kind this batch has armed, if any
+  for (int kind = kRecFrames; kind < kRecKinds; kind++)
+    if (bt->armed[kind] > 0) rec = kind;
   const void* kernel = resident_kernel(c0->p.nx, c0->plan.resident_rows, c0->plan.resident_joint, rec, true);
   const int bands = c0->plan.resident_bands;
   for (int t = 0; t < n_steps;) {
@@ -1370,9 +1386,12 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
     const lbm::ResidentMember* tab = bt->table + bt->cur * n_members;
     lbm::ResidentBatchFramesArgs fa;  // the FRAMES form's arguments: ResidentBatchArgs + the members' frame fields
     lbm::ResidentBatchProbesArgs pa;  // the PROBES form's: ResidentBatchArgs + the members' probe fields
+    lbm::ResidentBatchMeanArgs ma;    // the MEAN form's: ResidentBatchArgs + the members' mean fields
     memset(&fa, 0, sizeof(fa));
     memset(&pa, 0, sizeof(pa));
-    lbm::ResidentBatchArgs& a = (rec == kRecProbes) ? static_cast<lbm::ResidentBatchArgs&>(pa) : fa;
+    memset(&ma, 0, sizeof(ma));
+    lbm::ResidentBatchArgs& a = (rec == kRecProbes) ? static_cast<lbm::ResidentBatchArgs&>(pa)
+                                : (rec == kRecMean) ? static_cast<lbm::ResidentBatchArgs&>(ma) : fa;
     fill_resident_args(a, c0, n, t + n == n_steps, bt->steps_done + t);
     a.status = bt->status;
     a.member_wgs = bt->member_wgs;
@@ -1380,9 +1399,10 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
       a.members = tab + first;
       fa.frames = bt->frame_table ? bt->frame_table + first : nullptr;
       pa.probes = bt->probe_table ? bt->probe_table + first : nullptr;
+      ma.means = bt->mean_table ? bt->mean_table + first : nullptr;
       a.n_members = (n_members - first < bt->members_per_launch) ? n_members - first : bt->members_per_launch;
       const int grid = a.one_xcd ? bt->member_wgs * 8 : a.n_members * (int)round_up(bt->member_wgs, 8);
-      void* args[] = {(rec == kRecProbes) ? static_cast<void*>(&pa) : static_cast<void*>(&fa)};
+      void* args[] = {(rec == kRecProbes) ? static_cast<void*>(&pa) : (rec == kRecMean) ? static_cast<void*>(&ma) : static_cast<void*>(&fa)};
       HIP_TRY(LBM_FAILURE, hipLaunchKernel(kernel, dim3(grid), dim3(c0->p.nx * a.group), args, 0, bt->stream));
     }
     hipLaunchKernelGGL(lbm::reduce_band_partials_batch, dim3(n, n_members), dim3(64), 0, bt->stream, tab, bands,
@@ -1406,10 +1426,12 @@ long long recorded_between(const Recorder& r, long long from, long long to) {
   return (to + e - 1) / e - (from + e - 1) / e;
 }
 
-// lbm_run / lbm_batch_run refuse a call whose records would not fit the free slots, before any work is issued
+// lbm_run / lbm_batch_run refuse a call whose records would not fit the free slots, before any work is issued; a kind
+// that accumulates its records (the mean fields) has room for any call
 int recorder_fits(const lbm_ctx* c, int n_steps, const char* who) {
   const Recorder& r = c->rec;
   const RecorderKind& k = kRecorderKinds[r.kind];
+  if (!k.slotted) return LBM_SUCCESS;
   const long long add = recorded_between(r, c->steps_done, (long long)c->steps_done + n_steps);
   const long long waiting = r.written - r.read;
   if (waiting + add > r.slots)
@@ -1419,9 +1441,9 @@ int recorder_fits(const lbm_ctx* c, int n_steps, const char* who) {
 }
 
 // the record of the current (stored) lattice into the next slot, on every slab's compute stream: the frame of its rows,
-// or the gathered samples of the probes in its rows
+// or the gathered samples of the probes in its rows; or, for the mean fields, the sample of its rows added to their sums
 int take_record(lbm_ctx* c) {
-  const size_t slot = (size_t)(c->rec.written % c->rec.slots);
+  const size_t slot = kRecorderKinds[c->rec.kind].slotted ? (size_t)(c->rec.written % c->rec.slots) : 0;
   const size_t n_probes = c->probe_cells.size();
   if (for_slabs(c, [&](int s) -> int {
         Slab& sl = c->slab[s];
@@ -1431,6 +1453,10 @@ int take_record(lbm_ctx* c) {
           hipLaunchKernelGGL(lbm::frame_umag, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, (const float*)sl.lat[c->cur],
                              (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx, sl.rows,
                              sl.frames + slot * n);
+        else if (c->rec.kind == kRecMean)
+          hipLaunchKernelGGL(lbm::mean_accumulate, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, (const float*)sl.lat[c->cur],
+                             (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx, sl.rows,
+                             c->p.density, sl.mean_sums, n);
         else if (sl.probe_count > 0)
           hipLaunchKernelGGL(lbm::probe_gather, dim3(ceil_div(sl.probe_count, 64)), dim3(64), 0, sl.compute,
                              (const float*)sl.lat[c->cur], (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch,
@@ -1806,6 +1832,7 @@ void free_slab(Slab& sl) {
   if (sl.frames) (void)hipFree(sl.frames);
   if (sl.probe_ring) (void)hipFree(sl.probe_ring);
   if (sl.probe_table) (void)hipFree(sl.probe_table);
+  if (sl.mean_sums) (void)hipFree(sl.mean_sums);
   if (sl.ev_boundary) (void)hipEventDestroy(sl.ev_boundary);
   if (sl.ev_halo) (void)hipEventDestroy(sl.ev_halo);
   for (int i = 0; i < 2; i++) if (sl.ev_interior[i]) (void)hipEventDestroy(sl.ev_interior[i]);
@@ -2193,8 +2220,9 @@ int set_batch_entry(lbm_ctx* c, Entry*& table, const Entry& entry) {
 }
 int write_batch_entry(lbm_ctx* c, int kind) {
   if (!c->batch) return LBM_SUCCESS;
-  return (kind == kRecFrames) ? set_batch_entry(c, c->batch->frame_table, frames_entry(c))
-                              : set_batch_entry(c, c->batch->probe_table, probes_entry(c));
+  if (kind == kRecFrames) return set_batch_entry(c, c->batch->frame_table, frames_entry(c));
+  if (kind == kRecProbes) return set_batch_entry(c, c->batch->probe_table, probes_entry(c));
+  return set_batch_entry(c, c->batch->mean_table, mean_entry(c));
 }
 
 // frees the record buffers of every slab and leaves the recorder off
@@ -2205,6 +2233,8 @@ void release_recorder(lbm_ctx* c) {
     if (sl.frames) (void)hipFree(sl.frames);
     if (sl.probe_ring) (void)hipFree(sl.probe_ring);
     if (sl.probe_table) (void)hipFree(sl.probe_table);
+    if (sl.mean_sums) (void)hipFree(sl.mean_sums);
+    sl.mean_sums = nullptr;
     sl.frames = nullptr;
     sl.probe_ring = nullptr;
     sl.probe_table = nullptr;
@@ -2223,18 +2253,20 @@ int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate alloc
   const RecorderKind& k = kRecorderKinds[kind];
   lbm_batch* bt = c->batch;
   if (every > 0) {
-    const int other = kRecFrames + kRecProbes - kind;
-    const RecorderKind& o = kRecorderKinds[other];
     if (c->halo_mode != LBM_HALO_SYNC)
       LBM_FAIL(LBM_FAILURE, "%s: the context runs the %s halo mode, where splitting a call at a %s would change the results "
                "(every call starts from freshly exchanged halos); %s need LBM_HALO_SYNC", k.setter,
                c->halo_mode == LBM_HALO_STALE ? "stale" : "freshest", k.record, k.noun);
-    if (c->rec.kind == other)
-      LBM_FAIL(LBM_FAILURE, "%s: %s are armed (%s) and a context has one recorder -- disarm them with %s first", k.setter, o.name,
-               o.setter, o.disarm);
-    if (bt && bt->armed[other] > 0)
-      LBM_FAIL(LBM_FAILURE, "%s: a member of this batch has %s armed (%s); a batch records one kind, frames or probes", k.setter,
-               o.name, o.setter);
+    for (int other = kRecFrames; other < kRecKinds; other++) {  // every other kind
+      if (other == kind) continue;
+      const RecorderKind& o = kRecorderKinds[other];
+      if (c->rec.kind == other)
+        LBM_FAIL(LBM_FAILURE, "%s: %s are armed (%s) and a context has one recorder -- disarm them with %s first", k.setter, o.name,
+                 o.setter, o.disarm);
+      if (bt && bt->armed[other] > 0)
+        LBM_FAIL(LBM_FAILURE, "%s: a member of this batch has %s armed (%s); a batch records one kind: frames, probes or mean fields",
+                 k.setter, o.name, o.setter);
+    }
     if (c->plan.resident) {
       // the recorder forms of four-row bands defer the acceleration of the interior pair only (lbm::resident_band): the lid
       // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form must run one workgroup per CU
@@ -2665,6 +2697,49 @@ int lbm_read_probes(lbm_ctx* c, int max_samples, lbm_probe_sample* out, int* ste
   });
 }
 
+int lbm_set_mean(lbm_ctx* c, int every) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_mean: null context");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_mean: negative interval %d", every);
+  if (every > 0 && (c->ranked || c->world > 1))
+    LBM_FAIL(LBM_FAILURE, "lbm_set_mean: not available in a multi-process (rank) context");
+  // (re-)arming starts from zero sums and a zero count: the planes are cleared on each slab's compute stream, behind the
+  // quiesce of rearm_recorder and in front of whatever the next call enqueues there
+  return rearm_recorder(c, kRecMean, every, 0, [&]() -> int {
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      const size_t bytes = 4 * sizeof(double) * (size_t)sl.rows * (size_t)c->p.nx;
+      if (hipMalloc(&sl.mean_sums, bytes) != hipSuccess || hipMemsetAsync(sl.mean_sums, 0, bytes, sl.compute) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_mean: cannot allocate the four planes of sums (%.1f MiB per slab); the mean fields stay off",
+                 (double)bytes / 1048576.0);
+    }
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_read_mean(lbm_ctx* c, double* sum_u_x, double* sum_u_y, double* sum_u_mag, double* sum_pressure, long long* n_samples) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_read_mean: null context");
+  if (n_samples) *n_samples = 0;
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
+  if (c->rec.kind != kRecMean) LBM_FAIL(LBM_FAILURE, "lbm_read_mean: the mean fields are not armed (lbm_set_mean)");
+  double* const out[4] = {sum_u_x, sum_u_y, sum_u_mag, sum_pressure};
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    const size_t cells = (size_t)sl.rows * c->p.nx;
+    for (int j = 0; j < 4; j++)
+      if (out[j])
+        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(out[j] + (size_t)(sl.row_first - c->row_first) * c->p.nx, sl.mean_sums + (size_t)j * cells,
+                                            cells * sizeof(double), hipMemcpyDeviceToHost, sl.compute));
+  }
+  for (int s = 0; s < c->n_slabs; s++) {
+    HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
+    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
+  }
+  if (n_samples) *n_samples = c->rec.written;
+  return LBM_SUCCESS;
+}
+
 static const char kMemberRun[] = "%s: this context is a member of a batch (lbm_create_batch); lbm_batch_run advances all its members";
 
 int lbm_run(lbm_ctx* c, int n_steps) {
@@ -2882,6 +2957,7 @@ void lbm_destroy_batch(lbm_batch* bt) {
   if (bt->table) (void)hipFree(bt->table);
   if (bt->frame_table) (void)hipFree(bt->frame_table);
   if (bt->probe_table) (void)hipFree(bt->probe_table);
+  if (bt->mean_table) (void)hipFree(bt->mean_table);
   if (bt->status) (void)hipFree(bt->status);
   if (bt->status_host) (void)hipHostFree(bt->status_host);
   if (bt->steady_state) (void)hipFree(bt->steady_state);

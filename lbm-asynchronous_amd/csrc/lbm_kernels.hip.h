@@ -1591,6 +1591,22 @@ struct ResidentProbesArgs : ResidentArgs {
 struct ResidentBatchProbesArgs : ResidentBatchArgs {
   const ResidentProbes* probes;  // [this launch's members], as members
 };
+// mean fields (lbm_set_mean, resident_band<..., MEAN = true>): after global step tt with tt % every == 0 the kernel adds
+// {u_x, u_y, |u|, pressure} of every owned cell, each widened to double, to the cell's four sums: planes
+// double[rows][nx] at base + j * plane_stride, j = 0..3 in that order.  The record is an accumulation, not a slot: there
+// is no ordinal and no capacity, and a launch continues from whatever the planes hold.  Appended like ResidentFrames.
+struct ResidentMean {
+  double* base;               // plane 0, row 0; nullptr / every = 0: no mean
+  long plane_stride;          // doubles between the four planes (rows * nx)
+  int every;
+  float density;              // a blocked cell adds density * c_sq to its pressure sum
+};
+struct ResidentMeanArgs : ResidentArgs {
+  ResidentMean mn;
+};
+struct ResidentBatchMeanArgs : ResidentBatchArgs {
+  const ResidentMean* means;  // [this launch's members], as members
+};
 #ifdef LBM_RESIDENT_PROFILE
 __device__ __forceinline__ long long prof_clock() {
   long long t;
@@ -1685,6 +1701,7 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 // 16-byte seam granule: three populations and the tag in ONE naturally aligned dwordx4 access with sc1 (agent scope:
 // the store writes through the XCD's L2, the load bypasses L1 and refetches), i.e. the raw-buffer forms with aux = sc1
 typedef int granule_vec __attribute__((ext_vector_type(4)));
+typedef int mean_word __attribute__((ext_vector_type(2)));  // one double sum as the 8-byte buffer access moves it
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t granule_rsrc(uint4* base, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);
 }
@@ -1721,15 +1738,22 @@ __device__ __forceinline__ granule_vec granule_load(__amdgpu_buffer_rsrc_t rsrc,
 // PROBES: also record point probes (ResidentProbes).  On a sample step a band without probes does nothing further; a
 // band with probes walks its entries wave-uniformly and the lane that holds the cell stores its sample (one dwordx4).
 // Only a band with a probe ON the lid row defers the lid's acceleration on sample steps, exactly as FRAMES does.
-// FRAMES && PROBES is never instantiated: one recorder per context.
-template <bool BATCH, bool FRAMES, bool PROBES>
+// MEAN: also accumulate the mean fields (ResidentMean).  A sample step is a frame step in every respect -- the same
+// wave-uniform test, the same deferred acceleration of the lid cells, the same place in the step -- but instead of storing
+// |u| into a slot every lane adds the four values of each of its cells to the cell's double sums in memory (load, add,
+// store: a lane is the only writer of its cells and launches are stream-ordered, so neither atomics nor fences).  The
+// sums are not kept in registers across steps: the planes stay in L2 / Infinity Cache between samples.
+// At most one of FRAMES, PROBES, MEAN is instantiated: one recorder per context.
+template <bool BATCH, bool FRAMES, bool PROBES, bool MEAN>
 using ResidentArgsOf = std::conditional_t<
-    BATCH, std::conditional_t<FRAMES, ResidentBatchFramesArgs, std::conditional_t<PROBES, ResidentBatchProbesArgs, ResidentBatchArgs>>,
-    std::conditional_t<FRAMES, ResidentFramesArgs, std::conditional_t<PROBES, ResidentProbesArgs, ResidentArgs>>>;
-template <int MAXT, bool JOINT = false, int ROWS = 4, bool BATCH = false, bool FRAMES = false, bool PROBES = false>
-__global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH, FRAMES, PROBES> a) {
+    BATCH,
+    std::conditional_t<FRAMES, ResidentBatchFramesArgs,
+                       std::conditional_t<PROBES, ResidentBatchProbesArgs, std::conditional_t<MEAN, ResidentBatchMeanArgs, ResidentBatchArgs>>>,
+    std::conditional_t<FRAMES, ResidentFramesArgs, std::conditional_t<PROBES, ResidentProbesArgs, std::conditional_t<MEAN, ResidentMeanArgs, ResidentArgs>>>>;
+template <int MAXT, bool JOINT = false, int ROWS = 4, bool BATCH = false, bool FRAMES = false, bool PROBES = false, bool MEAN = false>
+__global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH, FRAMES, PROBES, MEAN> a) {
   static_assert(ROWS == 4 || ROWS == 2, "bands of four or two rows");
-  static_assert(!(FRAMES && PROBES), "one recorder per context");
+  static_assert((int)FRAMES + (int)PROBES + (int)MEAN <= 1, "one recorder per context");
   constexpr int NE = (ROWS == 4) ? 10 : 4;  // wave-edge values per side
   // a workgroup holds a.group bands side by side (1: the usual case; more where a band has fewer than four waves and
   // the whole grid fits one XCD with one wave per SIMD, see a.one_xcd): `wave`, `n_waves` count inside the band,
@@ -1740,6 +1764,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
   ResidentMember mb{};
   ResidentFrames fr{};
   ResidentProbes pr{};
+  ResidentMean mn{};
   if constexpr (BATCH) {
     const int stride = (a.member_wgs + 7) & ~7;
     const int member = a.one_xcd ? (int)(blockIdx.x & 7) : (int)blockIdx.x / stride;
@@ -1748,9 +1773,11 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     mb = a.members[member];
     if constexpr (FRAMES) fr = a.frames[member];
     if constexpr (PROBES) pr = a.probes[member];
+    if constexpr (MEAN) mn = a.means[member];
   } else if (a.one_xcd && (blockIdx.x & 7) != 0) return;
   if constexpr (FRAMES && !BATCH) fr = a.fr;
   if constexpr (PROBES && !BATCH) pr = a.pr;
+  if constexpr (MEAN && !BATCH) mn = a.mn;
 #define RES_M(field) (BATCH ? mb.field : a.field)
   const int bands = n_wgs * a.group;
   // Workgroups are dealt to the 8 XCDs round-robin (observed, not promised): consecutive bands are given to
@@ -1915,6 +1942,44 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     f_slot = (f_slot + 1 == pr.slots) ? 0 : f_slot + 1;
   };
 
+  // mean fields: the frames' test for the next sample step (f_next); nothing else is counted
+  if constexpr (MEAN) {
+    if (mn.every > 0) {
+      const unsigned e = (unsigned)mn.every, r = a.epoch0 % e;
+      f_next = r ? e - r : 0u;
+    }
+  }
+  // mean fields: the four values of the band's post-step cells -- edge pair `pe`, interior pair ri -- added to the cells'
+  // sums, then the deferred accelerate_flow of the next step on `lidp` (see take_frame)
+  auto take_mean = [&](const f2 (&pe)[kQ], f2 (&lidp)[kQ], bool accel_next) {
+    // the four planes as one buffer (scalar base, 32-bit lane offset; at most 32 MiB): no 64-bit address lives in VGPRs
+    const unsigned row_bytes = (unsigned)a.nx * 8u, plane_bytes = (unsigned)mn.plane_stride * 8u;
+    const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc(mn.base, 0, (int)(4u * plane_bytes), 0x00020000);
+    const int lane_off = (int)((unsigned)(ROWS * b) * row_bytes + (unsigned)x * 8u);
+    auto add_cell = [&](const f2 (&p)[kQ], int c, bool blocked, int row) {
+      float f[kQ];
+#pragma unroll
+      for (int k = 0; k < kQ; k++) f[k] = p[k][c];
+      const probe_vec v = probe_sample(f, blocked, mn.density);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int soff = (int)((unsigned)j * plane_bytes + (unsigned)row * row_bytes);
+        const double acc = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(mrsrc, lane_off, soff, 0));
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(mean_word, acc + (double)v[j]), mrsrc, lane_off, soff, 0);
+      }
+    };
+    add_cell(pe, 0, (blocked_e & 0xffu) != 0, 0);
+    add_cell(pe, 1, (blocked_e & 0xff00u) != 0, TOP);
+    if constexpr (ROWS == 4) {
+      add_cell(ri, 0, (blocked_i & 0xffu) != 0, 1);
+      add_cell(ri, 1, (blocked_i & 0xff00u) != 0, 2);
+    }
+    const unsigned lid = (ROWS == 4) ? lid_i : lid_e, blk = (ROWS == 4) ? blocked_i : blocked_e;
+    if (accel_next && lid != 0)
+      accelerate_select(lidp, (lid & 1u) != 0 && (blk & 0xffu) == 0, (lid & 2u) != 0 && (blk & 0xff00u) == 0, RES_M(a1), RES_M(a2));
+    f_next += (unsigned)mn.every;
+  };
+
   bool alive = true;
 #ifdef LBM_RESIDENT_PROFILE
   long long prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_t = prof_clock();
@@ -1976,7 +2041,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     granule_vec sn = granule_load(grsrc, gn + x_side);
 
     bool frame_now = false;
-    if constexpr (FRAMES) frame_now = ((unsigned)s == f_next);  // wave-uniform
+    if constexpr (FRAMES || MEAN) frame_now = ((unsigned)s == f_next);  // wave-uniform
     // probes: a sample step; only a band with a probe on the lid row defers the lid's acceleration as a frame step does
     bool sample_now = false;
     if constexpr (PROBES) {
@@ -1987,7 +2052,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     // a frame step applies the lid's acceleration after taking the frame (take_frame).  ROWS = 4: the lid row is
     // band row 2 (ny - 2 with ny % 4 == 0; run_resident checks it), an interior row, so only the interior pair defers
     const bool accel = accel_next && !(ROWS == 2 && frame_now);
-    const bool accel_i = (FRAMES || PROBES) ? accel_next && !frame_now : accel;
+    const bool accel_i = (FRAMES || PROBES || MEAN) ? accel_next && !frame_now : accel;
     // shifted populations (the value each cell receives from its west / east neighbour) and the streamed inputs of
     // the pair(s), as far as they come from inside the band
     f2 ti[kQ], te[kQ];
@@ -2075,6 +2140,9 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     if constexpr (PROBES && ROWS == 2) {
       if (sample_now) take_probes(ne, ne, frame_now && accel_next && lid_e != 0);
     }
+    if constexpr (MEAN && ROWS == 2) {
+      if (frame_now) take_mean(ne, ne, accel_next);
+    }
 #pragma unroll
     for (int k = 0; k < kQ; k++) {
       re[k] = ne[k];
@@ -2092,6 +2160,9 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     }
     if constexpr (PROBES && ROWS == 4) {
       if (sample_now) take_probes(re, ri, frame_now && accel_next && lid_i != 0);
+    }
+    if constexpr (MEAN && ROWS == 4) {
+      if (frame_now) take_mean(re, ri, accel_next);
     }
     RESIDENT_PROF(6);  // publish, wave sum
     // (a wave that gave up leaves the loop alone: the hardware barrier counts only waves that have not ended, and
@@ -2486,6 +2557,24 @@ __global__ void probe_gather(const float* lat, const unsigned char* mask, long p
 #pragma unroll
   for (int k = 0; k < kQ; k++) f[k] = lat[k * ps + c];
   row[e.xi >> 20] = probe_sample(f, mask[(long)e.row * pitch + x] != 0, density);
+}
+
+// one sample of a stored lattice added to the mean fields (lbm_set_mean, per-pass paths): final_state's four values of
+// every owned cell, each widened to double and added to the cell's sum in sums[j * plane + i], j = u_x, u_y, |u|, pressure.
+// One thread per cell, the only writer of its four sums; plain loads and stores (the sums are read again at the next sample)
+__global__ void mean_accumulate(const float* lat, const unsigned char* mask, long ps, long row_pitch, int pitch, int nx,
+                                int nrows, float density, double* sums, long plane) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long n = (long)nx * nrows;
+  if (i >= n) return;
+  const int r = (int)(i / nx), x = (int)(i - (long)r * nx);
+  const long c = (long)r * row_pitch + x;
+  float f[kQ];
+#pragma unroll
+  for (int k = 0; k < kQ; k++) f[k] = lat[k * ps + c];
+  const probe_vec v = probe_sample(f, mask[(long)r * pitch + x] != 0, density);
+#pragma unroll
+  for (int j = 0; j < 4; j++) sums[j * plane + i] = sums[j * plane + i] + (double)v[j];
 }
 
 // av_velocity() of a stored lattice (SerialCode/d2q9-bgk.c:409-458): per-workgroup partials of

@@ -24,6 +24,15 @@
  *                         1024, patience to 2): maxIters is the cap, av_vels.dat holds the steps that were run, and one
  *                         line "Steady after N steps (rel. change X)" / "Not steady after N steps (rel. change X)" is
  *                         printed before the ==done== block.  Not together with LBM_ANIMATION.
+ *   LBM_MEAN=<every>[:<from>]
+ *                         additionally write mean_state.dat, final_state.dat's format with the time averages of u_x, u_y,
+ *                         u and pressure (lbm_set_mean: float64 sums on the device, divided by the number of samples and
+ *                         rounded to float): the loop runs <from> steps (default 0) unarmed, arms, and runs the rest, so
+ *                         the samples are the steps tt >= from with tt % every == 0.  One line "Mean over N samples" is
+ *                         printed before the ==done== block.  final_state.dat is unchanged; av_vels.dat is unchanged where
+ *                         the run is resident (all four reference data sets), elsewhere it is that of the same run issued
+ *                         as calls split at <from> and at the sample steps.  Not together with LBM_ANIMATION, LBM_PROBES
+ *                         or LBM_STEADY.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -96,6 +105,28 @@ static int parse_probes(const char* text, lbm_probe* cells, int* every)
   return n;
 }
 
+/* LBM_MEAN=<every>[:<from>] (from defaults to 0); plain decimal numbers only; dies on anything else */
+static void parse_mean(const char* text, int* every, int* from)
+{
+  const char* s = text;
+  long v[2] = {0, 0};
+  int ok = 1;
+  for (int i = 0; ok && i < 2; i++) {
+    char* end = NULL;
+    ok = (*s >= '0' && *s <= '9');
+    if (!ok) break;
+    v[i] = strtol(s, &end, 10);
+    ok = v[i] <= 2147483647L;
+    s = end;
+    if (i == 0 && *s != ':') break;
+    if (i == 0) s++;
+  }
+  if (!ok || *s != '\0' || v[0] < 1)
+    lbm_die("could not read LBM_MEAN: expected <every>[:<from>] with every >= 1 and from >= 0", __LINE__, __FILE__);
+  *every = (int)v[0];
+  *from = (int)v[1];
+}
+
 int main(int argc, char* argv[])
 {
   if (argc != 3) lbm_usage(argv[0]);
@@ -122,6 +153,14 @@ int main(int argc, char* argv[])
   const int n_probes = (probes_env && *probes_env) ? parse_probes(probes_env, probe_cells, &probe_every) : 0;
   if (n_probes > 0 && until) lbm_die("LBM_STEADY and LBM_PROBES cannot be combined", __LINE__, __FILE__);
 
+  const char* mean_env = getenv("LBM_MEAN");
+  int mean_every = 0, mean_from = 0;
+  if (mean_env && *mean_env) parse_mean(mean_env, &mean_every, &mean_from);
+  if (mean_every > 0 && until) lbm_die("LBM_STEADY and LBM_MEAN cannot be combined", __LINE__, __FILE__);
+  if (mean_every > 0 && n_probes > 0) lbm_die("LBM_PROBES and LBM_MEAN cannot be combined", __LINE__, __FILE__);
+  if (mean_every > 0 && (env = getenv("LBM_ANIMATION")) && *env && atoi(env) > 0)
+    lbm_die("LBM_ANIMATION and LBM_MEAN cannot be combined", __LINE__, __FILE__);
+
   /* Total/init time starts here (SerialCode/d2q9-bgk.c:156-159) */
   const double tot_tic = wall_seconds();
   lbm_params params;
@@ -139,7 +178,7 @@ int main(int argc, char* argv[])
     tile_params.ny = tile_ny;
     int* tile = lbm_read_obstacles(obstaclefile, &tile_params);
     ctx = lbm_create_tiled(&params, tile, tile_nx, tile_ny, NULL, n_gpus, math_mode);
-    if (write_text) obstacles = lbm_tile_obstacles(tile, tile_nx, tile_ny, params.nx, params.ny);
+    if (write_text || mean_every > 0) obstacles = lbm_tile_obstacles(tile, tile_nx, tile_ny, params.nx, params.ny);
     free(tile);
   } else {
     obstacles = lbm_read_obstacles(obstaclefile, &params);
@@ -237,6 +276,12 @@ int main(int argc, char* argv[])
     fclose(fp);
     free(samples);
     free(steps);
+  } else if (mean_every > 0) {
+    /* with the mean fields: <from> steps unarmed, then the rest armed */
+    const int from = mean_from < params.max_iters ? mean_from : params.max_iters;
+    if (lbm_run(ctx, from) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+    if (lbm_set_mean(ctx, mean_every) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+    if (lbm_run(ctx, params.max_iters - from) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
   } else {
     lbm_run(ctx, params.max_iters);
   }
@@ -257,10 +302,19 @@ int main(int argc, char* argv[])
     if (fields == NULL) lbm_die("cannot allocate memory for cells", __LINE__, __FILE__);
     lbm_read_final_state(ctx, fields, fields + n_cells, fields + 2 * n_cells, fields + 3 * n_cells);
   }
+  double* mean_sums = NULL;
+  long long mean_samples = 0;
+  if (mean_every > 0) {
+    mean_sums = (double*)malloc(sizeof(double) * 4 * n_cells);
+    if (mean_sums == NULL) lbm_die("cannot allocate memory for the mean fields", __LINE__, __FILE__);
+    if (lbm_read_mean(ctx, mean_sums, mean_sums + n_cells, mean_sums + 2 * n_cells, mean_sums + 3 * n_cells, &mean_samples) != LBM_SUCCESS)
+      lbm_die(lbm_last_error(), __LINE__, __FILE__);
+  }
   const double col_toc = wall_seconds();
 
   if (until)
     printf("%s after %d steps (rel. change %.6E)\n", steady.steady ? "Steady" : "Not steady", steady.steps_run, steady.last_rel);
+  if (mean_every > 0) printf("Mean over %lld samples\n", mean_samples);
   /* the reference's report (:195-200) */
   printf("==done==\n");
   printf("Reynolds number:\t\t%.12E\n", reynolds);
@@ -279,6 +333,17 @@ int main(int argc, char* argv[])
     fclose(fp);
   }
   lbm_write_av_vels(LBM_AVVELSFILE, av_vels, steps_run);
+  if (mean_every > 0 && mean_samples > 0) {
+    /* the sums divided by the number of samples, rounded to float, in final_state.dat's format */
+    float* mean = (float*)malloc(sizeof(float) * 4 * n_cells);
+    if (mean == NULL) lbm_die("cannot allocate memory for the mean fields", __LINE__, __FILE__);
+    for (size_t i = 0; i < 4 * n_cells; i++) mean[i] = (float)(mean_sums[i] / (double)mean_samples);
+    FILE* fp = fopen(LBM_MEANSTATEFILE, "w");
+    if (fp == NULL) lbm_die("could not open file output file", __LINE__, __FILE__);
+    lbm_write_final_state_rows(fp, &params, 0, params.ny, mean, mean + n_cells, mean + 2 * n_cells, mean + 3 * n_cells, obstacles);
+    fclose(fp);
+    free(mean);
+  }
   if ((env = getenv("LBM_PRESSURE_BIN")) && *env) {
     FILE* fp = fopen(env, "wb");
     if (fp == NULL) lbm_die("could not open file output file", __LINE__, __FILE__);
@@ -288,6 +353,7 @@ int main(int argc, char* argv[])
 
   lbm_destroy(ctx);
   free(fields);
+  free(mean_sums);
   free(av_vels);
   free(obstacles);
   return EXIT_SUCCESS;
