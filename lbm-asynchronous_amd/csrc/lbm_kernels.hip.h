@@ -1595,11 +1595,16 @@ struct ResidentBatchProbesArgs : ResidentBatchArgs {
 // {u_x, u_y, |u|, pressure} of every owned cell, each widened to double, to the cell's four sums: planes
 // double[rows][nx] at base + j * plane_stride, j = 0..3 in that order.  The record is an accumulation, not a slot: there
 // is no ordinal and no capacity, and a launch continues from whatever the planes hold.  Appended like ResidentFrames.
+// order == 2 (lbm_set_mean_order): planes 4..7 follow in the same allocation, the sums of the products u_x u_x, u_y u_y,
+// u_x u_y and pressure pressure of the same samples, acc = acc + (double)a * (double)b: the product of two floats is exact
+// in a double, so the update rounds once, contracted into an FMA or not.
 struct ResidentMean {
   double* base;               // plane 0, row 0; nullptr / every = 0: no mean
-  long plane_stride;          // doubles between the four planes (rows * nx)
+  long plane_stride;          // doubles between the planes (rows * nx)
   int every;
   float density;              // a blocked cell adds density * c_sq to its pressure sum
+  int order;                  // 1: planes 0..3; 2: planes 0..7
+  int pad;
 };
 struct ResidentMeanArgs : ResidentArgs {
   ResidentMean mn;
@@ -1742,7 +1747,9 @@ __device__ __forceinline__ granule_vec granule_load(__amdgpu_buffer_rsrc_t rsrc,
 // wave-uniform test, the same deferred acceleration of the lid cells, the same place in the step -- but instead of storing
 // |u| into a slot every lane adds the four values of each of its cells to the cell's double sums in memory (load, add,
 // store: a lane is the only writer of its cells and launches are stream-ordered, so neither atomics nor fences).  The
-// sums are not kept in registers across steps: the planes stay in L2 / Infinity Cache between samples.
+// sums are not kept in registers across steps: the planes stay in L2 / Infinity Cache between samples.  At order 2
+// (ResidentMean::order, a scalar: the branch is wave-uniform and lies inside the sample branch) four more sums per cell,
+// of the products, are updated the same way through the same descriptor.
 // At most one of FRAMES, PROBES, MEAN is instantiated: one recorder per context.
 template <bool BATCH, bool FRAMES, bool PROBES, bool MEAN>
 using ResidentArgsOf = std::conditional_t<
@@ -1952,9 +1959,11 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
   // mean fields: the four values of the band's post-step cells -- edge pair `pe`, interior pair ri -- added to the cells'
   // sums, then the deferred accelerate_flow of the next step on `lidp` (see take_frame)
   auto take_mean = [&](const f2 (&pe)[kQ], f2 (&lidp)[kQ], bool accel_next) {
-    // the four planes as one buffer (scalar base, 32-bit lane offset; at most 32 MiB): no 64-bit address lives in VGPRs
+    // the armed planes, four or eight, as one buffer (scalar base, 32-bit lane offset; at most 32 MiB at order 1 and
+    // 64 MiB at order 2, the 1024 x 1024 lattice): no 64-bit address lives in VGPRs
+    const bool second = (mn.order == 2);  // wave-uniform
     const unsigned row_bytes = (unsigned)a.nx * 8u, plane_bytes = (unsigned)mn.plane_stride * 8u;
-    const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc(mn.base, 0, (int)(4u * plane_bytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc(mn.base, 0, (int)((second ? 8u : 4u) * plane_bytes), 0x00020000);
     const int lane_off = (int)((unsigned)(ROWS * b) * row_bytes + (unsigned)x * 8u);
     auto add_cell = [&](const f2 (&p)[kQ], int c, bool blocked, int row) {
       float f[kQ];
@@ -1966,6 +1975,17 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
         const int soff = (int)((unsigned)j * plane_bytes + (unsigned)row * row_bytes);
         const double acc = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(mrsrc, lane_off, soff, 0));
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(mean_word, acc + (double)v[j]), mrsrc, lane_off, soff, 0);
+      }
+      if (second) {
+        // planes 4..7: u_x u_x, u_y u_y, u_x u_y, pressure pressure; each product is exact in a double
+        const double ux = (double)v[0], uy = (double)v[1], pr = (double)v[3];
+        const double prod[4] = {ux * ux, uy * uy, ux * uy, pr * pr};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const int soff = (int)((unsigned)(4 + j) * plane_bytes + (unsigned)row * row_bytes);
+          const double acc = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(mrsrc, lane_off, soff, 0));
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(mean_word, acc + prod[j]), mrsrc, lane_off, soff, 0);
+        }
       }
     };
     add_cell(pe, 0, (blocked_e & 0xffu) != 0, 0);
@@ -2560,10 +2580,11 @@ __global__ void probe_gather(const float* lat, const unsigned char* mask, long p
 }
 
 // one sample of a stored lattice added to the mean fields (lbm_set_mean, per-pass paths): final_state's four values of
-// every owned cell, each widened to double and added to the cell's sum in sums[j * plane + i], j = u_x, u_y, |u|, pressure.
-// One thread per cell, the only writer of its four sums; plain loads and stores (the sums are read again at the next sample)
+// every owned cell, each widened to double and added to the cell's sum in sums[j * plane + i], j = u_x, u_y, |u|, pressure;
+// at order 2 also their exact products u_x u_x, u_y u_y, u_x u_y, pressure pressure to planes 4..7.
+// One thread per cell, the only writer of its sums; plain loads and stores (the sums are read again at the next sample)
 __global__ void mean_accumulate(const float* lat, const unsigned char* mask, long ps, long row_pitch, int pitch, int nx,
-                                int nrows, float density, double* sums, long plane) {
+                                int nrows, float density, double* sums, long plane, int order) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long n = (long)nx * nrows;
   if (i >= n) return;
@@ -2575,6 +2596,12 @@ __global__ void mean_accumulate(const float* lat, const unsigned char* mask, lon
   const probe_vec v = probe_sample(f, mask[(long)r * pitch + x] != 0, density);
 #pragma unroll
   for (int j = 0; j < 4; j++) sums[j * plane + i] = sums[j * plane + i] + (double)v[j];
+  if (order == 2) {
+    const double ux = (double)v[0], uy = (double)v[1], pr = (double)v[3];
+    const double prod[4] = {ux * ux, uy * uy, ux * uy, pr * pr};
+#pragma unroll
+    for (int j = 0; j < 4; j++) sums[(4 + j) * plane + i] = sums[(4 + j) * plane + i] + prod[j];
+  }
 }
 
 // av_velocity() of a stored lattice (SerialCode/d2q9-bgk.c:409-458): per-workgroup partials of

@@ -33,7 +33,12 @@
  *                         the run is resident (all four reference data sets), elsewhere it is that of the same run issued
  *                         as calls split at <from> and at the sample steps.  Not together with LBM_ANIMATION, LBM_PROBES
  *                         or LBM_STEADY.
+ *   LBM_MEAN_ORDER=1|2    with LBM_MEAN: 2 also accumulates the second moments (lbm_set_mean_order) and additionally writes
+ *                         rms_state.dat, final_state.dat's format with the columns rms u_x, rms u_y, the Reynolds shear
+ *                         stress <u'v'> and rms pressure over the same samples (var = max(<x x> - <x>^2, 0) in double,
+ *                         rounded to float).  The other files are unchanged.  Dies when set without LBM_MEAN.
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -156,6 +161,15 @@ int main(int argc, char* argv[])
   const char* mean_env = getenv("LBM_MEAN");
   int mean_every = 0, mean_from = 0;
   if (mean_env && *mean_env) parse_mean(mean_env, &mean_every, &mean_from);
+  const char* order_env = getenv("LBM_MEAN_ORDER");
+  int mean_order = 1;
+  if (order_env && *order_env) {
+    /* plain decimal 1 or 2, nothing else */
+    if ((order_env[0] != '1' && order_env[0] != '2') || order_env[1] != '\0')
+      lbm_die("could not read LBM_MEAN_ORDER: expected 1 or 2", __LINE__, __FILE__);
+    if (mean_every == 0) lbm_die("LBM_MEAN_ORDER needs LBM_MEAN", __LINE__, __FILE__);
+    mean_order = order_env[0] - '0';
+  }
   if (mean_every > 0 && until) lbm_die("LBM_STEADY and LBM_MEAN cannot be combined", __LINE__, __FILE__);
   if (mean_every > 0 && n_probes > 0) lbm_die("LBM_PROBES and LBM_MEAN cannot be combined", __LINE__, __FILE__);
   if (mean_every > 0 && (env = getenv("LBM_ANIMATION")) && *env && atoi(env) > 0)
@@ -280,7 +294,7 @@ int main(int argc, char* argv[])
     /* with the mean fields: <from> steps unarmed, then the rest armed */
     const int from = mean_from < params.max_iters ? mean_from : params.max_iters;
     if (lbm_run(ctx, from) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
-    if (lbm_set_mean(ctx, mean_every) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+    if (lbm_set_mean_order(ctx, mean_every, mean_order) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
     if (lbm_run(ctx, params.max_iters - from) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
   } else {
     lbm_run(ctx, params.max_iters);
@@ -305,9 +319,12 @@ int main(int argc, char* argv[])
   double* mean_sums = NULL;
   long long mean_samples = 0;
   if (mean_every > 0) {
-    mean_sums = (double*)malloc(sizeof(double) * 4 * n_cells);
+    mean_sums = (double*)malloc(sizeof(double) * 4 * (size_t)mean_order * n_cells);
     if (mean_sums == NULL) lbm_die("cannot allocate memory for the mean fields", __LINE__, __FILE__);
     if (lbm_read_mean(ctx, mean_sums, mean_sums + n_cells, mean_sums + 2 * n_cells, mean_sums + 3 * n_cells, &mean_samples) != LBM_SUCCESS)
+      lbm_die(lbm_last_error(), __LINE__, __FILE__);
+    if (mean_order == 2 &&
+        lbm_read_mean2(ctx, mean_sums + 4 * n_cells, mean_sums + 5 * n_cells, mean_sums + 6 * n_cells, mean_sums + 7 * n_cells, NULL) != LBM_SUCCESS)
       lbm_die(lbm_last_error(), __LINE__, __FILE__);
   }
   const double col_toc = wall_seconds();
@@ -342,6 +359,24 @@ int main(int argc, char* argv[])
     if (fp == NULL) lbm_die("could not open file output file", __LINE__, __FILE__);
     lbm_write_final_state_rows(fp, &params, 0, params.ny, mean, mean + n_cells, mean + 2 * n_cells, mean + 3 * n_cells, obstacles);
     fclose(fp);
+    if (mean_order == 2) {
+      /* m = S1 / n, q = S2 / n in double: rms = sqrt(max(q - m m, 0)), <u'v'> = q_xy - m_x m_y; rounded to float */
+      const double n = (double)mean_samples;
+      const double *s1x = mean_sums, *s1y = mean_sums + n_cells, *s1p = mean_sums + 3 * n_cells;
+      const double *sxx = mean_sums + 4 * n_cells, *syy = sxx + n_cells, *sxy = syy + n_cells, *spp = sxy + n_cells;
+      for (size_t i = 0; i < n_cells; i++) {
+        const double mx = s1x[i] / n, my = s1y[i] / n, mp = s1p[i] / n;
+        const double vx = sxx[i] / n - mx * mx, vy = syy[i] / n - my * my, vp = spp[i] / n - mp * mp;
+        mean[i] = (float)sqrt(vx > 0.0 ? vx : 0.0);
+        mean[n_cells + i] = (float)sqrt(vy > 0.0 ? vy : 0.0);
+        mean[2 * n_cells + i] = (float)(sxy[i] / n - mx * my);
+        mean[3 * n_cells + i] = (float)sqrt(vp > 0.0 ? vp : 0.0);
+      }
+      fp = fopen(LBM_RMSSTATEFILE, "w");
+      if (fp == NULL) lbm_die("could not open file output file", __LINE__, __FILE__);
+      lbm_write_final_state_rows(fp, &params, 0, params.ny, mean, mean + n_cells, mean + 2 * n_cells, mean + 3 * n_cells, obstacles);
+      fclose(fp);
+    }
     free(mean);
   }
   if ((env = getenv("LBM_PRESSURE_BIN")) && *env) {
