@@ -334,7 +334,7 @@ struct GraphBuilder {
 // (|u| of the owned rows, lbm_set_frames) or a row of probe samples (lbm_set_probes) -- into slot
 // (tt / every - ord0) % slots of every slab's buffer of that kind.  The mean fields (lbm_set_mean) are the kind without
 // slots: their record is added to per-cell sums, `written` counts the samples, `read`, `slots` and `ord0` stay unused.
-enum { kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3, kRecKinds = 4 };
+enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean, kRecKinds = 4 };
 struct Recorder {
   int kind = kRecNone;
   int every = 0;
@@ -498,6 +498,13 @@ int q_copy(lbm_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st)
 }
 
 // ---- launch helpers --------------------------------------------------------------------------
+// where a slab's lattices lie, as every kernel is told: the view that reads lattice `from` and writes lattice `to`
+// (from == to for the kernels that work in place), by default the current lattice into the other one
+lbm::LatticeArgs lattice_args(const lbm_ctx* c, const Slab& sl, int from, int to) {
+  return {sl.lat[from], sl.lat[to], sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx};
+}
+lbm::LatticeArgs lattice_args(const lbm_ctx* c, const Slab& sl) { return lattice_args(c, sl, c->cur, c->cur ^ 1); }
+
 // `done` (optional): event bound to the kernel's own completion signal (hipExtLaunchKernel's stop event)
 // -- what hipEventRecord right after the launch would mark, without a barrier packet of its own
 int launch_step(lbm_ctx* c, int s, hipStream_t stream, int row_first, int row_stride, int n_rows,
@@ -505,13 +512,7 @@ int launch_step(lbm_ctx* c, int s, hipStream_t stream, int row_first, int row_st
   Slab& sl = c->slab[s];
   if (n_rows <= 0) return LBM_SUCCESS;
   lbm::StepArgs a;
-  a.src = sl.lat[c->cur];
-  a.dst = sl.lat[c->cur ^ 1];
-  a.mask = sl.mask;
-  a.plane_stride = c->plane_stride;
-  a.pitch = c->pitch;
-  a.row_pitch = c->row_pitch;
-  a.nx = c->p.nx;
+  static_cast<lbm::LatticeArgs&>(a) = lattice_args(c, sl);
   a.rows = sl.rows;
   a.row_first = row_first;
   a.row_stride = row_stride;
@@ -553,13 +554,7 @@ int launch_step2(lbm_ctx* c, int s, hipStream_t stream, int row_first, int row_e
   Slab& sl = c->slab[s];
   if (band_count <= 0) return LBM_SUCCESS;
   lbm::Step2Args a;
-  a.src = sl.lat[c->cur];
-  a.dst = sl.lat[c->cur ^ 1];
-  a.mask = sl.mask;
-  a.plane_stride = c->plane_stride;
-  a.row_pitch = c->row_pitch;
-  a.pitch = c->pitch;
-  a.nx = c->p.nx;
+  static_cast<lbm::LatticeArgs&>(a) = lattice_args(c, sl);
   a.rows = sl.rows;
   a.wrap = (c->halo == HALO_SELF) ? 1 : 0;
   a.band_rows = band_rows;
@@ -593,13 +588,7 @@ int launch_stepk(lbm_ctx* c, int s, hipStream_t stream, int k, int row_first, in
   Slab& sl = c->slab[s];
   if (band_count <= 0) return LBM_SUCCESS;
   lbm::StepKArgs a;
-  a.src = sl.lat[c->cur];
-  a.dst = sl.lat[c->cur ^ 1];
-  a.mask = sl.mask;
-  a.plane_stride = c->plane_stride;
-  a.row_pitch = c->row_pitch;
-  a.pitch = c->pitch;
-  a.nx = c->p.nx;
+  static_cast<lbm::LatticeArgs&>(a) = lattice_args(c, sl);
   a.rows = sl.rows;
   a.wrap = (c->halo == HALO_SELF) ? 1 : 0;
   a.band_rows = band_rows;
@@ -673,13 +662,7 @@ int tile_count(const lbm_ctx* c) { return lbm_plan::tile_count(c->p.nx, c->slab[
 int launch_tile(lbm_ctx* c, hipStream_t stream, int n_steps, bool accel_after) {
   Slab& sl = c->slab[0];
   lbm::TileArgs a;
-  a.src = sl.lat[c->cur];
-  a.dst = sl.lat[c->cur ^ 1];
-  a.mask = sl.mask;
-  a.plane_stride = c->plane_stride;
-  a.row_pitch = c->row_pitch;
-  a.pitch = c->pitch;
-  a.nx = c->p.nx;
+  static_cast<lbm::LatticeArgs&>(a) = lattice_args(c, sl);
   a.ny = sl.rows;
   a.n_steps = n_steps;
   a.accel_row = sl.accel_row;
@@ -1244,13 +1227,12 @@ size_t resident_gran_bytes(const lbm_ctx* c) {
 // bands, MAXT 1024 with four-row bands, MAXT 512 with four-row bands relaxed jointly or not
 template <bool BATCH, int REC>
 const void* resident_form(int shape) {
-  constexpr bool F = (REC == kRecFrames), P = (REC == kRecProbes), M = (REC == kRecMean);
   switch (shape) {
-    case 0: return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, BATCH, F, P, M>);
-    case 1: return reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, BATCH, F, P, M>);
-    case 2: return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, BATCH, F, P, M>);
-    case 3: return reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, BATCH, F, P, M>);
-    default: return reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, BATCH, F, P, M>);
+    case 0: return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 2, BATCH, REC>);
+    case 1: return reinterpret_cast<const void*>(lbm::resident_band<512, false, 2, BATCH, REC>);
+    case 2: return reinterpret_cast<const void*>(lbm::resident_band<1024, false, 4, BATCH, REC>);
+    case 3: return reinterpret_cast<const void*>(lbm::resident_band<512, true, 4, BATCH, REC>);
+    default: return reinterpret_cast<const void*>(lbm::resident_band<512, false, 4, BATCH, REC>);
   }
 }
 const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = false) {
@@ -1281,10 +1263,7 @@ lbm::ResidentMean mean_entry(const lbm_ctx* c) {
 // the fields of ResidentArgs that plain and batched launches share: n timesteps from global step epoch0, last = the
 // call's last launch
 void fill_resident_args(lbm::ResidentArgs& a, const lbm_ctx* c, int n, bool last, int epoch0) {
-  a.plane_stride = c->plane_stride;
-  a.row_pitch = c->row_pitch;
-  a.pitch = c->pitch;
-  a.nx = c->p.nx;
+  static_cast<lbm::LatticeArgs&>(a) = lattice_args(c, c->slab[0]);  // a batched launch reads the strides only
   a.ny = c->slab[0].rows;
   a.n_steps = n;
   a.accel_row = c->slab[0].accel_row;
@@ -1307,17 +1286,14 @@ int run_resident(lbm_ctx* c, int n_steps) {
   const bool probes = (c->rec.kind == kRecProbes), mean = (c->rec.kind == kRecMean);
   for (int t = 0; t < n_steps;) {
     const int n = (n_steps - t < kResidentChunk) ? n_steps - t : kResidentChunk;
-    lbm::ResidentFramesArgs fa;  // the FRAMES form's arguments, ResidentArgs + the frame fields; the plain form reads its part
-    lbm::ResidentProbesArgs pa;  // the PROBES form's: ResidentArgs + the probe fields
-    lbm::ResidentMeanArgs ma;    // the MEAN form's: ResidentArgs + the mean fields
+    lbm::ResidentFramesArgs fa;  // the frames form's arguments, ResidentArgs + the frame fields; the plain form reads its part
+    lbm::ResidentProbesArgs pa;  // the probes form's: ResidentArgs + the probe fields
+    lbm::ResidentMeanArgs ma;    // the mean form's: ResidentArgs + the mean fields
     lbm::ResidentArgs& a = probes ? static_cast<lbm::ResidentArgs&>(pa) : (mean ? static_cast<lbm::ResidentArgs&>(ma) : fa);
     fa.fr = frames_entry(c);
     pa.pr = probes_entry(c);
     ma.mn = mean_entry(c);
     fill_resident_args(a, c, n, t + n == n_steps, c->steps_done + t);
-    a.src = sl.lat[c->cur];
-    a.dst = sl.lat[c->cur ^ 1];
-    a.mask = sl.mask;
     a.omega = c->p.omega;
     set_accel_weights(a, c->p);
     a.gran = sl.res_gran;
@@ -1375,8 +1351,7 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
   const int n_members = (int)bt->members.size();
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
   hipLaunchKernelGGL(lbm::accelerate_row_batch, dim3(ceil_div(c0->p.nx, 256), n_members), dim3(256), 0, bt->stream,
-                     (const lbm::ResidentMember*)(bt->table + bt->cur * n_members), c0->plane_stride, c0->row_pitch,
-                     c0->pitch, c0->p.nx, sl0.accel_row);
+                     (const lbm::ResidentMember*)(bt->table + bt->cur * n_members), lattice_args(c0, sl0), sl0.accel_row);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
   int rec = kRecNone;  // the one kind this batch has armed, if any
   for (int kind = kRecFrames; kind < kRecKinds; kind++)
@@ -1386,9 +1361,9 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
   for (int t = 0; t < n_steps;) {
     const int n = (n_steps - t < kResidentChunk) ? n_steps - t : kResidentChunk;
     const lbm::ResidentMember* tab = bt->table + bt->cur * n_members;
-    lbm::ResidentBatchFramesArgs fa;  // the FRAMES form's arguments: ResidentBatchArgs + the members' frame fields
-    lbm::ResidentBatchProbesArgs pa;  // the PROBES form's: ResidentBatchArgs + the members' probe fields
-    lbm::ResidentBatchMeanArgs ma;    // the MEAN form's: ResidentBatchArgs + the members' mean fields
+    lbm::ResidentBatchFramesArgs fa;  // the frames form's arguments: ResidentBatchArgs + the members' frame fields
+    lbm::ResidentBatchProbesArgs pa;  // the probes form's: ResidentBatchArgs + the members' probe fields
+    lbm::ResidentBatchMeanArgs ma;    // the mean form's: ResidentBatchArgs + the members' mean fields
     memset(&fa, 0, sizeof(fa));
     memset(&pa, 0, sizeof(pa));
     memset(&ma, 0, sizeof(ma));
@@ -1452,16 +1427,13 @@ int take_record(lbm_ctx* c) {
         HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
         const long n = (long)sl.rows * c->p.nx;
         if (c->rec.kind == kRecFrames)
-          hipLaunchKernelGGL(lbm::frame_umag, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, (const float*)sl.lat[c->cur],
-                             (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx, sl.rows,
+          hipLaunchKernelGGL(lbm::frame_umag, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              sl.frames + slot * n);
         else if (c->rec.kind == kRecMean)
-          hipLaunchKernelGGL(lbm::mean_accumulate, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, (const float*)sl.lat[c->cur],
-                             (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx, sl.rows,
+          hipLaunchKernelGGL(lbm::mean_accumulate, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              c->p.density, sl.mean_sums, n, c->rec.order);
         else if (sl.probe_count > 0)
-          hipLaunchKernelGGL(lbm::probe_gather, dim3(ceil_div(sl.probe_count, 64)), dim3(64), 0, sl.compute,
-                             (const float*)sl.lat[c->cur], (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch,
+          hipLaunchKernelGGL(lbm::probe_gather, dim3(ceil_div(sl.probe_count, 64)), dim3(64), 0, sl.compute, lattice_args(c, sl),
                              c->p.density, (const lbm::ProbeEntry*)sl.probe_table, sl.probe_count, sl.probe_ring + slot * n_probes);
         HIP_TRY(LBM_FAILURE, hipGetLastError());
         return LBM_SUCCESS;
@@ -1483,8 +1455,7 @@ int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
         HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
         if (sl.accel_row >= 0 && sl.accel_row < sl.rows) {
           hipLaunchKernelGGL(lbm::accelerate_row, dim3(ceil_div(c->p.nx, 256)), dim3(256), 0, sl.compute,
-                             sl.lat[c->cur], sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx,
-                             sl.accel_row, w.a1, w.a2);
+                             lattice_args(c, sl, c->cur, c->cur), sl.accel_row, w.a1, w.a2);
           HIP_TRY(LBM_FAILURE, hipGetLastError());
         }
         if (record_t0) HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_t0, sl.compute));
@@ -1722,8 +1693,7 @@ int run_steps_stale(lbm_ctx* c, int n_steps, float* kernel_ms) {
         HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
         if (sl.accel_row >= 0 && sl.accel_row < sl.rows) {
           hipLaunchKernelGGL(lbm::accelerate_row, dim3(ceil_div(c->p.nx, 256)), dim3(256), 0, sl.compute,
-                             sl.lat[c->cur], sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx,
-                             sl.accel_row, w.a1, w.a2);
+                             lattice_args(c, sl, c->cur, c->cur), sl.accel_row, w.a1, w.a2);
           HIP_TRY(LBM_FAILURE, hipGetLastError());
         }
         HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_step, sl.compute));
@@ -1984,7 +1954,7 @@ int build_slab(lbm_ctx* c, int s, const ObstacleSource& obst, const float* cells
     const float r1 = p.density / 9.f;
     const float r2 = p.density / 36.f;
     hipLaunchKernelGGL(lbm::init_equilibrium, dim3(ceil_div((long)p.nx * sl.rows, 256)), dim3(256), 0,
-                       sl.compute, sl.lat[0], c->plane_stride, c->row_pitch, p.nx, sl.rows, r0, r1, r2);
+                       sl.compute, lattice_args(c, sl, 0, 0), sl.rows, r0, r1, r2);
     HIP_TRY(LBM_FAILURE, hipGetLastError());
   } else {
     // upload in chunks of rows through a staging buffer, transposing AoS -> SoA on the device
@@ -2000,7 +1970,7 @@ int build_slab(lbm_ctx* c, int s, const ObstacleSource& obst, const float* cells
       HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage, cells_aos + (size_t)(sl.row_first - (obst.local_cells ? c->row_first : 0) + r0) * p.nx * lbm::kQ,
                                           n * sizeof(float), hipMemcpyHostToDevice, sl.compute));
       hipLaunchKernelGGL(lbm::aos_to_soa, dim3(ceil_div((long)n, 256)), dim3(256), 0, sl.compute, stage,
-                         sl.lat[0], c->plane_stride, c->row_pitch, p.nx, r0, nr);
+                         lattice_args(c, sl, 0, 0), r0, nr);
       HIP_TRY(LBM_FAILURE, hipGetLastError());
       HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
     }
@@ -2870,7 +2840,7 @@ int lbm_read_cells(lbm_ctx* c, float* cells_aos) {
       const int nr = (sl.rows - r0 < chunk_rows) ? sl.rows - r0 : (int)chunk_rows;
       const size_t n = (size_t)nr * nx * lbm::kQ;
       hipLaunchKernelGGL(lbm::soa_to_aos, dim3(ceil_div((long)n, 256)), dim3(256), 0, sl.compute,
-                         sl.lat[c->cur], stage, c->plane_stride, c->row_pitch, nx, r0, nr);
+                         lattice_args(c, sl), stage, r0, nr);
       HIP_TRY(LBM_FAILURE, hipGetLastError());
       HIP_TRY(LBM_FAILURE, hipMemcpyAsync(cells_aos + (size_t)(sl.row_first - c->row_first + r0) * nx * lbm::kQ, stage,
                                           n * sizeof(float), hipMemcpyDeviceToHost, sl.compute));
@@ -2898,7 +2868,7 @@ int lbm_read_final_state(lbm_ctx* c, float* u_x, float* u_y, float* u_mag, float
       const int nr = (sl.rows - r0 < chunk_rows) ? sl.rows - r0 : (int)chunk_rows;
       const size_t n = (size_t)nr * nx;
       hipLaunchKernelGGL(lbm::final_state, dim3(ceil_div((long)n, 256)), dim3(256), 0, sl.compute,
-                         sl.lat[c->cur], sl.mask, c->plane_stride, c->row_pitch, c->pitch, nx, r0, nr, c->p.density,
+                         lattice_args(c, sl), r0, nr, c->p.density,
                          stage, stage + chunk_cells, stage + 2 * chunk_cells, stage + 3 * chunk_cells);
       HIP_TRY(LBM_FAILURE, hipGetLastError());
       const size_t off = (size_t)(sl.row_first - c->row_first + r0) * nx;
@@ -2919,9 +2889,8 @@ static int lattice_totals(lbm_ctx* c, double* speed, double* mass) {
   for (int s = 0; s < c->n_slabs; s++) {
     Slab& sl = c->slab[s];
     HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-    hipLaunchKernelGGL(lbm::lattice_sums, dim3(kSumBlocks), dim3(lbm::kBlock), 0, sl.compute, sl.lat[c->cur],
-                       sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx, sl.rows, sl.scratch,
-                       sl.scratch + kSumBlocks);
+    hipLaunchKernelGGL(lbm::lattice_sums, dim3(kSumBlocks), dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl),
+                       sl.rows, sl.scratch, sl.scratch + kSumBlocks);
     HIP_TRY(LBM_FAILURE, hipGetLastError());
     HIP_TRY(LBM_FAILURE, hipMemcpyAsync(h.data(), sl.scratch, 2 * kSumBlocks * sizeof(double),
                                         hipMemcpyDeviceToHost, sl.compute));
@@ -3190,10 +3159,8 @@ static int steady_segment_resident(lbm_ctx* c, int n, int slot, double tol, int 
   Slab& sl = c->slab[0];
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
   const AccelWeights w = accel_weights(c->p);
-  hipLaunchKernelGGL(lbm::accelerate_row_unless, dim3(ceil_div(c->p.nx, 256)), dim3(256), 0, sl.compute, sl.lat[c->cur],
-                     (const unsigned char*)sl.mask, c->plane_stride, c->row_pitch, c->pitch, c->p.nx, sl.accel_row,
-                     w.a1, w.a2,
-                     (const lbm::SteadyState*)c->steady_state);
+  hipLaunchKernelGGL(lbm::accelerate_row_unless, dim3(ceil_div(c->p.nx, 256)), dim3(256), 0, sl.compute,
+                     lattice_args(c, sl, c->cur, c->cur), sl.accel_row, w.a1, w.a2, (const lbm::SteadyState*)c->steady_state);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
   if (run_resident(c, n) != LBM_SUCCESS) return LBM_FAILURE;
   hipLaunchKernelGGL(lbm::steady_check, dim3(1), dim3(64), 0, sl.compute, (const double*)sl.tot_u, c->steps_done, n,

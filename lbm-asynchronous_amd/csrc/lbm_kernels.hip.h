@@ -30,6 +30,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+#include <tuple>
 #include <type_traits>
 
 namespace lbm {
@@ -37,6 +39,8 @@ namespace lbm {
 constexpr int kBlock = 256;  // 4 waves of 64
 constexpr int kQ = 9;
 constexpr int kNoRow = -1000000;  // "no such row in this slab"
+// what a context records while it runs, at most one at a time: the host's Recorder::kind and resident_band's REC
+constexpr int kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3;
 
 // 1/3 rounded to fp32, and the two constant divisors of the equilibrium, folded in fp32
 // exactly as the reference's "2.f * c_sq" and "2.f * c_sq * c_sq" (SerialCode/d2q9-bgk.c:308,367-370)
@@ -47,14 +51,33 @@ constexpr float kW0 = 4.f / 9.f;
 constexpr float kW1 = 1.f / 9.f;
 constexpr float kW2 = 1.f / 36.f;
 
-struct StepArgs {
-  const float* src;           // plane 0 of the source lattice
-  float* dst;                 // plane 0 of the destination lattice
+// Where a lattice lies and how its rows are addressed: the leading fields of every kernel's arguments, filled in one
+// place on the host (lattice_args).  Value (k, row, x) is at k * plane_stride + row * row_pitch + x, mask byte (row, x) at
+// row * pitch + x.  A kernel that reads a stored lattice takes it as src; one that modifies a lattice in place
+// (accelerate_row*, init_equilibrium, aos_to_soa) takes it as dst.  48 bytes without padding: the structs derived from
+// it keep their own first field at offset 48 (asserted below each), so no kernel argument moves.
+struct LatticeArgs {
+  const float* src;           // plane 0, row 0 of the source lattice
+  float* dst;                 // plane 0, row 0 of the destination lattice
   const unsigned char* mask;  // rows x pitch, 1 = blocked
   long plane_stride;          // floats between planes
-  int pitch;                  // bytes between rows of the uint8 mask
   long row_pitch;             // floats between lattice rows of one plane
+  int pitch;                  // bytes between rows of the uint8 mask
   int nx;                     // cells per row
+};
+static_assert(sizeof(LatticeArgs) == 48, "no padding: derived arguments start at 48");
+
+// the nine populations of cell (row, x) of the source lattice
+__device__ __forceinline__ void gather_cell(const LatticeArgs& a, int row, int x, float (&f)[kQ]) {
+  const long c = (long)row * a.row_pitch + x;
+#pragma unroll
+  for (int k = 0; k < kQ; k++) f[k] = a.src[k * a.plane_stride + c];
+}
+__device__ __forceinline__ bool cell_blocked(const LatticeArgs& a, int row, int x) {
+  return a.mask[(long)row * a.pitch + x] != 0;
+}
+
+struct StepArgs : LatticeArgs {
   int rows;                   // rows owned by this slab
   int row_first;              // first slab row this launch advances
   int row_stride;             // distance between the rows this launch advances (1 = contiguous)
@@ -491,14 +514,7 @@ __global__ __launch_bounds__(BLOCK) void step_vec4(const StepArgs a) {
 // accelerate_flow: step t+1's acceleration is applied to the step-t results of the lid row
 // (always); step t+2's to the stored results when accel_after != 0 (not on the last step of a run).
 // ---------------------------------------------------------------------------------------------
-struct Step2Args {
-  const float* src;
-  float* dst;
-  const unsigned char* mask;
-  long plane_stride;
-  long row_pitch;
-  int pitch;
-  int nx;
+struct Step2Args : LatticeArgs {
   int rows;        // rows owned by the slab
   int wrap;        // 1: rows wrap periodically (single slab); 0: two halo rows surround the slab
   int band_rows;   // output rows per wave (band height)
@@ -719,14 +735,7 @@ __global__ __launch_bounds__(64) void step2_stream(const Step2Args a) {
 // horizontally adjacent strips of one band (a chunk), so the 128-byte lines that straddle two strips
 // (a strip is 62 x 16 B = 992 B wide) are fetched from the fabric once per chunk instead of once per strip.
 // ---------------------------------------------------------------------------------------------
-struct StepKArgs {
-  const float* src;
-  float* dst;
-  const unsigned char* mask;
-  long plane_stride;
-  long row_pitch;
-  int pitch;
-  int nx;
+struct StepKArgs : LatticeArgs {
   int rows;        // rows owned by the slab
   int wrap;        // 1: rows wrap periodically (single slab); 0: K halo rows surround the slab
   int band_rows;   // output rows per wave (band height)
@@ -1380,14 +1389,8 @@ __global__ __launch_bounds__(64, NP == 1 ? (K > 2 ? 3 : (PREFETCH ? 2 : 4)) : 2)
 // lattice stays bit-identical).  Periodic wrap in x and y is resolved when the tile is staged.
 // Sum of |u| per step: over the tile's own cells, one partial per workgroup and step.
 // ---------------------------------------------------------------------------------------------
-struct TileArgs {
-  const float* src;
-  float* dst;
-  const unsigned char* mask;
-  long plane_stride;
-  long row_pitch;
-  int pitch;
-  int nx, ny;
+struct TileArgs : LatticeArgs {
+  int ny;
   int tiles_x;      // workgroups across x
   int n_steps;      // timesteps this launch advances (1..KMAX)
   int accel_row;    // global row that receives accelerate_flow (ny - 2)
@@ -1516,14 +1519,8 @@ struct ResidentMember {
   double* tot_u;              // the member's per-step sums of |u|
   float omega, a1, a2;
 };
-struct ResidentArgs {
-  const float* src;           // lattice to start from (row 0 of the slab)
-  float* dst;                 // lattice to leave the result in (may equal src)
-  const unsigned char* mask;
-  long plane_stride;
-  long row_pitch;
-  int pitch;
-  int nx, ny;
+struct ResidentArgs : LatticeArgs {  // src: the lattice to start from, dst: where to leave the result (may equal src)
+  int ny;
   int n_steps;                // timesteps this launch advances
   int accel_row;              // global row of accelerate_flow (ny - 2)
   int accel_last;             // also apply the acceleration of the step after this launch's last one
@@ -1542,6 +1539,15 @@ struct ResidentArgs {
   long long* prof;            // tools/resident_profile.sh: [band][8] shader-clock sums of the phases of a step
 #endif
 };
+// the layouts the kernels were compiled and measured with: an edit that shifts a field fails here, not in a profile
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(offsetof(StepArgs, rows) == 48 && offsetof(StepArgs, partials) == 80, "StepArgs layout");
+static_assert(offsetof(Step2Args, rows) == 48 && offsetof(Step2Args, partials1) == 96, "Step2Args layout");
+static_assert(offsetof(StepKArgs, rows) == 48 && offsetof(StepKArgs, partials) == 112, "StepKArgs layout");
+static_assert(offsetof(TileArgs, ny) == 48 && offsetof(TileArgs, partials) == 80, "TileArgs layout");
+static_assert(offsetof(ResidentArgs, ny) == 48 && offsetof(ResidentArgs, gran) == 80, "ResidentArgs layout");
+#pragma clang diagnostic pop
 // batched launches (resident_band<..., BATCH = true>): src, dst, mask, omega, a1, a2, gran and partials above are unused,
 // each member brings its own; status is shared by all members of all launches of a batch
 struct ResidentBatchArgs : ResidentArgs {
@@ -1550,9 +1556,9 @@ struct ResidentBatchArgs : ResidentArgs {
   int member_wgs;             // working workgroups of one member; without one_xcd member m starts at block
                               // m * round_up(member_wgs, 8), so the XCD-affinity band order holds inside every member
 };
-// animation frames (lbm_set_frames, resident_band<..., FRAMES = true>): after global step tt with tt % every == 0 the
+// animation frames (lbm_set_frames, resident_band<..., REC = kRecFrames>): after global step tt with tt % every == 0 the
 // kernel stores |u| of every owned cell into slot (tt / every - ord0) % slots of base, one float[rows][nx] per slot.
-// Kept out of ResidentArgs / ResidentMember so that the FRAMES = false forms read their arguments at the same offsets.
+// Kept out of ResidentArgs / ResidentMember so that the other forms read their arguments at the same offsets.
 struct ResidentFrames {
   float* base;                // slot 0; nullptr / every = 0: no frames
   int every;
@@ -1565,7 +1571,7 @@ struct ResidentFramesArgs : ResidentArgs {
 struct ResidentBatchFramesArgs : ResidentBatchArgs {
   const ResidentFrames* frames;  // [this launch's members], as members
 };
-// point probes (lbm_set_probes, resident_band<..., PROBES = true>): after global step tt with tt % every == 0 the kernel
+// point probes (lbm_set_probes, resident_band<..., REC = kRecProbes>): after global step tt with tt % every == 0 the kernel
 // stores {u_x, u_y, |u|, pressure} of every probed cell into row (tt / every - ord0) % slots of ring, one 16-byte sample
 // per probe, in the caller's probe order.  The host sorts the probes by row: `table` holds them in that order, followed by
 // one word per band of the resident kernel -- first entry | entries << 12 | (a probe lies on the lid row) << 31 -- so a
@@ -1591,7 +1597,7 @@ struct ResidentProbesArgs : ResidentArgs {
 struct ResidentBatchProbesArgs : ResidentBatchArgs {
   const ResidentProbes* probes;  // [this launch's members], as members
 };
-// mean fields (lbm_set_mean, resident_band<..., MEAN = true>): after global step tt with tt % every == 0 the kernel adds
+// mean fields (lbm_set_mean, resident_band<..., REC = kRecMean>): after global step tt with tt % every == 0 the kernel adds
 // {u_x, u_y, |u|, pressure} of every owned cell, each widened to double, to the cell's four sums: planes
 // double[rows][nx] at base + j * plane_stride, j = 0..3 in that order.  The record is an accumulation, not a slot: there
 // is no ordinal and no capacity, and a launch continues from whatever the planes hold.  Appended like ResidentFrames.
@@ -1736,31 +1742,27 @@ __device__ __forceinline__ granule_vec granule_load(__amdgpu_buffer_rsrc_t rsrc,
 // workgroup, so the member's fields are scalar loads before the step loop and the loop itself is the same.  One-XCD
 // shapes: member m = blockIdx.x & 7 runs on XCD m, on the workgroups the single form leaves idle; other shapes: members
 // take consecutive ranges of round_up(member_wgs, 8) blocks.  The seam protocol is per member (own granules, own tags).
-// FRAMES: also record animation frames (ResidentFrames).  On a frame step the lid cells are relaxed WITHOUT the next
+// REC = kRecFrames: also record animation frames (ResidentFrames).  On a frame step the lid cells are relaxed WITHOUT the next
 // step's accelerate_flow, |u| of the post-step lattice goes to the frame slot, and only then is accelerate_select applied
 // to the relaxed values: bit-identical to the fused epilogue, since accelerate_select is a pure select on the relaxed
 // values that never touches a blocked cell (the only cells bounce_select changes).
-// PROBES: also record point probes (ResidentProbes).  On a sample step a band without probes does nothing further; a
+// REC = kRecProbes: also record point probes (ResidentProbes).  On a sample step a band without probes does nothing further; a
 // band with probes walks its entries wave-uniformly and the lane that holds the cell stores its sample (one dwordx4).
-// Only a band with a probe ON the lid row defers the lid's acceleration on sample steps, exactly as FRAMES does.
-// MEAN: also accumulate the mean fields (ResidentMean).  A sample step is a frame step in every respect -- the same
+// Only a band with a probe ON the lid row defers the lid's acceleration on sample steps, exactly as the frames do.
+// REC = kRecMean: also accumulate the mean fields (ResidentMean).  A sample step is a frame step in every respect -- the same
 // wave-uniform test, the same deferred acceleration of the lid cells, the same place in the step -- but instead of storing
 // |u| into a slot every lane adds the four values of each of its cells to the cell's double sums in memory (load, add,
 // store: a lane is the only writer of its cells and launches are stream-ordered, so neither atomics nor fences).  The
 // sums are not kept in registers across steps: the planes stay in L2 / Infinity Cache between samples.  At order 2
 // (ResidentMean::order, a scalar: the branch is wave-uniform and lies inside the sample branch) four more sums per cell,
 // of the products, are updated the same way through the same descriptor.
-// At most one of FRAMES, PROBES, MEAN is instantiated: one recorder per context.
-template <bool BATCH, bool FRAMES, bool PROBES, bool MEAN>
-using ResidentArgsOf = std::conditional_t<
-    BATCH,
-    std::conditional_t<FRAMES, ResidentBatchFramesArgs,
-                       std::conditional_t<PROBES, ResidentBatchProbesArgs, std::conditional_t<MEAN, ResidentBatchMeanArgs, ResidentBatchArgs>>>,
-    std::conditional_t<FRAMES, ResidentFramesArgs, std::conditional_t<PROBES, ResidentProbesArgs, std::conditional_t<MEAN, ResidentMeanArgs, ResidentArgs>>>>;
-template <int MAXT, bool JOINT = false, int ROWS = 4, bool BATCH = false, bool FRAMES = false, bool PROBES = false, bool MEAN = false>
-__global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH, FRAMES, PROBES, MEAN> a) {
+template <bool BATCH, int REC>
+using ResidentArgsOf = std::tuple_element_t<
+    REC, std::conditional_t<BATCH, std::tuple<ResidentBatchArgs, ResidentBatchFramesArgs, ResidentBatchProbesArgs, ResidentBatchMeanArgs>,
+                            std::tuple<ResidentArgs, ResidentFramesArgs, ResidentProbesArgs, ResidentMeanArgs>>>;
+template <int MAXT, bool JOINT = false, int ROWS = 4, bool BATCH = false, int REC = kRecNone>
+__global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH, REC> a) {
   static_assert(ROWS == 4 || ROWS == 2, "bands of four or two rows");
-  static_assert((int)FRAMES + (int)PROBES + (int)MEAN <= 1, "one recorder per context");
   constexpr int NE = (ROWS == 4) ? 10 : 4;  // wave-edge values per side
   // a workgroup holds a.group bands side by side (1: the usual case; more where a band has fewer than four waves and
   // the whole grid fits one XCD with one wave per SIMD, see a.one_xcd): `wave`, `n_waves` count inside the band,
@@ -1778,13 +1780,13 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     if (!a.one_xcd) { n_wgs = a.member_wgs; wg = (int)blockIdx.x - member * stride; }
     if (member >= a.n_members || wg >= n_wgs) return;
     mb = a.members[member];
-    if constexpr (FRAMES) fr = a.frames[member];
-    if constexpr (PROBES) pr = a.probes[member];
-    if constexpr (MEAN) mn = a.means[member];
+    if constexpr (REC == kRecFrames) fr = a.frames[member];
+    if constexpr (REC == kRecProbes) pr = a.probes[member];
+    if constexpr (REC == kRecMean) mn = a.means[member];
   } else if (a.one_xcd && (blockIdx.x & 7) != 0) return;
-  if constexpr (FRAMES && !BATCH) fr = a.fr;
-  if constexpr (PROBES && !BATCH) pr = a.pr;
-  if constexpr (MEAN && !BATCH) mn = a.mn;
+  if constexpr (REC == kRecFrames && !BATCH) fr = a.fr;
+  if constexpr (REC == kRecProbes && !BATCH) pr = a.pr;
+  if constexpr (REC == kRecMean && !BATCH) mn = a.mn;
 #define RES_M(field) (BATCH ? mb.field : a.field)
   const int bands = n_wgs * a.group;
   // Workgroups are dealt to the 8 XCDs round-robin (observed, not promised): consecutive bands are given to
@@ -1874,7 +1876,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
   // frames: local step of the next one (~0u: none) and its slot
   unsigned f_next = ~0u;
   int f_slot = 0;
-  if constexpr (FRAMES) {
+  if constexpr (REC == kRecFrames) {
     if (fr.every > 0) {
       const unsigned e = (unsigned)fr.every, r = a.epoch0 % e;
       f_next = r ? e - r : 0u;
@@ -1905,7 +1907,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
 
   // probes: the same bookkeeping (f_next, f_slot count sample rows) and this band's word of the table
   unsigned p_range = 0;
-  if constexpr (PROBES) {
+  if constexpr (REC == kRecProbes) {
     if (pr.every > 0) {
       const unsigned e = (unsigned)pr.every, r = a.epoch0 % e;
       f_next = r ? e - r : 0u;
@@ -1950,7 +1952,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
   };
 
   // mean fields: the frames' test for the next sample step (f_next); nothing else is counted
-  if constexpr (MEAN) {
+  if constexpr (REC == kRecMean) {
     if (mn.every > 0) {
       const unsigned e = (unsigned)mn.every, r = a.epoch0 % e;
       f_next = r ? e - r : 0u;
@@ -2061,10 +2063,10 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     granule_vec sn = granule_load(grsrc, gn + x_side);
 
     bool frame_now = false;
-    if constexpr (FRAMES || MEAN) frame_now = ((unsigned)s == f_next);  // wave-uniform
+    if constexpr (REC == kRecFrames || REC == kRecMean) frame_now = ((unsigned)s == f_next);  // wave-uniform
     // probes: a sample step; only a band with a probe on the lid row defers the lid's acceleration as a frame step does
     bool sample_now = false;
-    if constexpr (PROBES) {
+    if constexpr (REC == kRecProbes) {
       sample_now = ((unsigned)s == f_next);
       frame_now = sample_now && (p_range >> 31) != 0;
     }
@@ -2072,7 +2074,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     // a frame step applies the lid's acceleration after taking the frame (take_frame).  ROWS = 4: the lid row is
     // band row 2 (ny - 2 with ny % 4 == 0; run_resident checks it), an interior row, so only the interior pair defers
     const bool accel = accel_next && !(ROWS == 2 && frame_now);
-    const bool accel_i = (FRAMES || PROBES || MEAN) ? accel_next && !frame_now : accel;
+    const bool accel_i = (REC != kRecNone) ? accel_next && !frame_now : accel;
     // shifted populations (the value each cell receives from its west / east neighbour) and the streamed inputs of
     // the pair(s), as far as they come from inside the band
     f2 ti[kQ], te[kQ];
@@ -2154,13 +2156,13 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     f2 ne[kQ];
     if constexpr (ROWS == 4 && JOINT) sum = relax_two_pairs_rows(ti, te, blocked_i, blocked_e, accel_i ? lid_i : 0u, accel ? lid_e : 0u, RES_M(omega), RES_M(a1), RES_M(a2), ni, ne);
     else sum += relax_pair_rows(te, blocked_e, accel ? lid_e : 0u, RES_M(omega), RES_M(a1), RES_M(a2), ne);
-    if constexpr (FRAMES && ROWS == 2) {
+    if constexpr (REC == kRecFrames && ROWS == 2) {
       if (frame_now) take_frame(ne, accel_next);
     }
-    if constexpr (PROBES && ROWS == 2) {
+    if constexpr (REC == kRecProbes && ROWS == 2) {
       if (sample_now) take_probes(ne, ne, frame_now && accel_next && lid_e != 0);
     }
-    if constexpr (MEAN && ROWS == 2) {
+    if constexpr (REC == kRecMean && ROWS == 2) {
       if (frame_now) take_mean(ne, ne, accel_next);
     }
 #pragma unroll
@@ -2175,13 +2177,13 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     const float tot = wave_sum_dpp(sum);
     if (lane == 63) wave_part[slot][wv] = tot;
     // ROWS = 4: the frame once the step's own work is out (fewest live registers: the 128-VGPR form does not spill)
-    if constexpr (FRAMES && ROWS == 4) {
+    if constexpr (REC == kRecFrames && ROWS == 4) {
       if (frame_now) take_frame(ri, accel_next);
     }
-    if constexpr (PROBES && ROWS == 4) {
+    if constexpr (REC == kRecProbes && ROWS == 4) {
       if (sample_now) take_probes(re, ri, frame_now && accel_next && lid_i != 0);
     }
-    if constexpr (MEAN && ROWS == 4) {
+    if constexpr (REC == kRecMean && ROWS == 4) {
       if (frame_now) take_mean(re, ri, accel_next);
     }
     RESIDENT_PROF(6);  // publish, wave sum
@@ -2274,27 +2276,27 @@ __global__ __launch_bounds__(kBlock) void step_scalar(const StepArgs a) {
 
 // accelerate_flow() as its own pass (SerialCode/d2q9-bgk.c:216-246): used once before the first
 // step of a run; later steps get it from the epilogue of the step kernel.
-__device__ __forceinline__ void accelerate_row_at(float* lat, const unsigned char* mask, long ps, long row_pitch,
-                                                  int pitch, int nx, int row, float a1, float a2) {
+__device__ __forceinline__ void accelerate_row_at(const LatticeArgs& a, int row, float a1, float a2) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
-  if (x >= nx) return;
-  if (mask[(long)row * pitch + x]) return;
-  const long c = (long)row * row_pitch + x;
+  if (x >= a.nx) return;
+  if (cell_blocked(a, row, x)) return;
+  const long ps = a.plane_stride;
+  float* lat = a.dst + (long)row * a.row_pitch + x;
   float f[kQ];
 #pragma unroll
-  for (int k = 0; k < kQ; k++) f[k] = lat[k * ps + c];
+  for (int k = 0; k < kQ; k++) f[k] = lat[k * ps];
   accelerate(f, a1, a2);
-  lat[1 * ps + c] = f[1];  lat[3 * ps + c] = f[3];  lat[5 * ps + c] = f[5];
-  lat[6 * ps + c] = f[6];  lat[7 * ps + c] = f[7];  lat[8 * ps + c] = f[8];
+  lat[1 * ps] = f[1];  lat[3 * ps] = f[3];  lat[5 * ps] = f[5];
+  lat[6 * ps] = f[6];  lat[7 * ps] = f[7];  lat[8 * ps] = f[8];
 }
-__global__ void accelerate_row(float* lat, const unsigned char* mask, long ps, long row_pitch,
-                               int pitch, int nx, int row, float a1, float a2) {
-  accelerate_row_at(lat, mask, ps, row_pitch, pitch, nx, row, a1, a2);
-}
-// the same on the current lattice of every member of a batch: grid (ceil(nx / block), members)
-__global__ void accelerate_row_batch(const ResidentMember* members, long ps, long row_pitch, int pitch, int nx, int row) {
+__global__ void accelerate_row(const LatticeArgs a, int row, float a1, float a2) { accelerate_row_at(a, row, a1, a2); }
+// the same on the current lattice of every member of a batch: grid (ceil(nx / block), members); `a` gives the members'
+// common strides, each member its own lattice and mask
+__global__ void accelerate_row_batch(const ResidentMember* members, LatticeArgs a, int row) {
   const ResidentMember& m = members[blockIdx.y];
-  accelerate_row_at(m.src, m.mask, ps, row_pitch, pitch, nx, row, m.a1, m.a2);
+  a.dst = m.src;
+  a.mask = m.mask;
+  accelerate_row_at(a, row, m.a1, m.a2);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2373,10 +2375,9 @@ __global__ __launch_bounds__(64) void steady_check_batch(const SteadyMember* mem
 }
 // accelerate_row for the first step of a segment that was enqueued before the verdict of the segment in front of it was
 // known: nothing happens once that verdict is "stop", so the lattice the call returns is not accelerated a second time
-__global__ void accelerate_row_unless(float* lat, const unsigned char* mask, long ps, long row_pitch,
-                                      int pitch, int nx, int row, float a1, float a2, const SteadyState* st) {
+__global__ void accelerate_row_unless(const LatticeArgs a, int row, float a1, float a2, const SteadyState* st) {
   if (st->stop) return;  // one scalar load, wave-uniform
-  accelerate_row_at(lat, mask, ps, row_pitch, pitch, nx, row, a1, a2);
+  accelerate_row_at(a, row, a1, a2);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2486,56 +2487,51 @@ __global__ __launch_bounds__(256) void count_blocked(const unsigned char* mask, 
 }
 
 // uniform equilibrium start (SerialCode/d2q9-bgk.c:546-567)
-__global__ void init_equilibrium(float* lat, long ps, long row_pitch, int nx, int rows, float r0,
-                                 float r1, float r2) {
+__global__ void init_equilibrium(const LatticeArgs a, int rows, float r0, float r1, float r2) {
   const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= (long)nx * rows) return;
-  const long row = j / nx;
-  const long i = row * row_pitch + (j - row * nx);
-  lat[i] = r0;
-  lat[1 * ps + i] = r1;  lat[2 * ps + i] = r1;  lat[3 * ps + i] = r1;  lat[4 * ps + i] = r1;
-  lat[5 * ps + i] = r2;  lat[6 * ps + i] = r2;  lat[7 * ps + i] = r2;  lat[8 * ps + i] = r2;
+  if (j >= (long)a.nx * rows) return;
+  const long row = j / a.nx;
+  const long ps = a.plane_stride;
+  float* lat = a.dst + row * a.row_pitch + (j - row * a.nx);
+  lat[0] = r0;
+  lat[1 * ps] = r1;  lat[2 * ps] = r1;  lat[3 * ps] = r1;  lat[4 * ps] = r1;
+  lat[5 * ps] = r2;  lat[6 * ps] = r2;  lat[7 * ps] = r2;  lat[8 * ps] = r2;
 }
 
 // AoS (reference host layout, 9 floats per cell) <-> SoA planes, rows [row0, row0+nrows)
-__global__ void aos_to_soa(const float* aos, float* lat, long ps, long row_pitch, int nx, int row0,
-                           int nrows) {
+__global__ void aos_to_soa(const float* aos, const LatticeArgs a, int row0, int nrows) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long n = (long)nx * nrows * kQ;
+  const long n = (long)a.nx * nrows * kQ;
   if (i >= n) return;
   const long cell = i / kQ;
   const int k = (int)(i - cell * kQ);
-  const int r = (int)(cell / nx), x = (int)(cell - (long)r * nx);
-  lat[k * ps + (long)(row0 + r) * row_pitch + x] = aos[i];
+  const int r = (int)(cell / a.nx), x = (int)(cell - (long)r * a.nx);
+  a.dst[k * a.plane_stride + (long)(row0 + r) * a.row_pitch + x] = aos[i];
 }
 
-__global__ void soa_to_aos(const float* lat, float* aos, long ps, long row_pitch, int nx, int row0,
-                           int nrows) {
+__global__ void soa_to_aos(const LatticeArgs a, float* aos, int row0, int nrows) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long n = (long)nx * nrows * kQ;
+  const long n = (long)a.nx * nrows * kQ;
   if (i >= n) return;
   const long cell = i / kQ;
   const int k = (int)(i - cell * kQ);
-  const int r = (int)(cell / nx), x = (int)(cell - (long)r * nx);
-  aos[i] = lat[k * ps + (long)(row0 + r) * row_pitch + x];
+  const int r = (int)(cell / a.nx), x = (int)(cell - (long)r * a.nx);
+  aos[i] = a.src[k * a.plane_stride + (long)(row0 + r) * a.row_pitch + x];
 }
 
 // write_values() quantities (SerialCode/d2q9-bgk.c:684-719), always in the exact arithmetic
-__global__ void final_state(const float* lat, const unsigned char* mask, long ps, long row_pitch,
-                            int pitch, int nx, int row0, int nrows, float density, float* ux_o,
-                            float* uy_o, float* um_o, float* pr_o) {
+__global__ void final_state(const LatticeArgs a, int row0, int nrows, float density, float* ux_o, float* uy_o, float* um_o,
+                            float* pr_o) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long n = (long)nx * nrows;
+  const long n = (long)a.nx * nrows;
   if (i >= n) return;
-  const int r = (int)(i / nx), x = (int)(i - (long)r * nx);
-  const long c = (long)(row0 + r) * row_pitch + x;
-  if (mask[(long)(row0 + r) * pitch + x]) {
+  const int r = (int)(i / a.nx), x = (int)(i - (long)r * a.nx);
+  if (cell_blocked(a, row0 + r, x)) {
     ux_o[i] = 0.f;  uy_o[i] = 0.f;  um_o[i] = 0.f;
     pr_o[i] = density * kCsq;
   } else {
     float f[kQ];
-#pragma unroll
-    for (int k = 0; k < kQ; k++) f[k] = lat[k * ps + c];
+    gather_cell(a, row0 + r, x, f);
     float rho, ux, uy;
     moments_exact(f, rho, ux, uy);
     ux_o[i] = ux;  uy_o[i] = uy;
@@ -2545,19 +2541,16 @@ __global__ void final_state(const float* lat, const unsigned char* mask, long ps
 }
 
 // one animation frame of a stored lattice (lbm_set_frames, per-pass paths): final_state's |u| alone, into out[nrows][nx]
-__global__ void frame_umag(const float* lat, const unsigned char* mask, long ps, long row_pitch, int pitch, int nx,
-                           int nrows, float* out) {
+__global__ void frame_umag(const LatticeArgs a, int nrows, float* out) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long n = (long)nx * nrows;
+  const long n = (long)a.nx * nrows;
   if (i >= n) return;
-  const int r = (int)(i / nx), x = (int)(i - (long)r * nx);
-  const long c = (long)r * row_pitch + x;
-  if (mask[(long)r * pitch + x]) {
+  const int r = (int)(i / a.nx), x = (int)(i - (long)r * a.nx);
+  if (cell_blocked(a, r, x)) {
     out[i] = 0.f;
   } else {
     float f[kQ];
-#pragma unroll
-    for (int k = 0; k < kQ; k++) f[k] = lat[k * ps + c];
+    gather_cell(a, r, x, f);
     float rho, ux, uy;
     moments_exact(f, rho, ux, uy);
     out[i] = sqrtf((ux * ux) + (uy * uy));
@@ -2566,34 +2559,28 @@ __global__ void frame_umag(const float* lat, const unsigned char* mask, long ps,
 
 // one sample row of a stored lattice (lbm_set_probes, per-pass paths): final_state's four values at the slab's probed
 // cells, one thread per probe, into row[probe index]
-__global__ void probe_gather(const float* lat, const unsigned char* mask, long ps, long row_pitch, int pitch, float density,
-                             const ProbeEntry* table, int n, probe_vec* row) {
+__global__ void probe_gather(const LatticeArgs a, float density, const ProbeEntry* table, int n, probe_vec* row) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= n) return;
   const ProbeEntry e = table[i];
   const int x = (int)(e.xi & 0xfffffu);
-  const long c = (long)e.row * row_pitch + x;
   float f[kQ];
-#pragma unroll
-  for (int k = 0; k < kQ; k++) f[k] = lat[k * ps + c];
-  row[e.xi >> 20] = probe_sample(f, mask[(long)e.row * pitch + x] != 0, density);
+  gather_cell(a, e.row, x, f);
+  row[e.xi >> 20] = probe_sample(f, cell_blocked(a, e.row, x), density);
 }
 
 // one sample of a stored lattice added to the mean fields (lbm_set_mean, per-pass paths): final_state's four values of
 // every owned cell, each widened to double and added to the cell's sum in sums[j * plane + i], j = u_x, u_y, |u|, pressure;
 // at order 2 also their exact products u_x u_x, u_y u_y, u_x u_y, pressure pressure to planes 4..7.
 // One thread per cell, the only writer of its sums; plain loads and stores (the sums are read again at the next sample)
-__global__ void mean_accumulate(const float* lat, const unsigned char* mask, long ps, long row_pitch, int pitch, int nx,
-                                int nrows, float density, double* sums, long plane, int order) {
+__global__ void mean_accumulate(const LatticeArgs a, int nrows, float density, double* sums, long plane, int order) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long n = (long)nx * nrows;
+  const long n = (long)a.nx * nrows;
   if (i >= n) return;
-  const int r = (int)(i / nx), x = (int)(i - (long)r * nx);
-  const long c = (long)r * row_pitch + x;
+  const int r = (int)(i / a.nx), x = (int)(i - (long)r * a.nx);
   float f[kQ];
-#pragma unroll
-  for (int k = 0; k < kQ; k++) f[k] = lat[k * ps + c];
-  const probe_vec v = probe_sample(f, mask[(long)r * pitch + x] != 0, density);
+  gather_cell(a, r, x, f);
+  const probe_vec v = probe_sample(f, cell_blocked(a, r, x), density);
 #pragma unroll
   for (int j = 0; j < 4; j++) sums[j * plane + i] = sums[j * plane + i] + (double)v[j];
   if (order == 2) {
@@ -2606,23 +2593,18 @@ __global__ void mean_accumulate(const float* lat, const unsigned char* mask, lon
 
 // av_velocity() of a stored lattice (SerialCode/d2q9-bgk.c:409-458): per-workgroup partials of
 // sum |u| in double; reduced by reduce_doubles.  Also serves total_density() (:644-660).
-__global__ __launch_bounds__(kBlock) void lattice_sums(const float* lat, const unsigned char* mask,
-                                                       long ps, long row_pitch, int pitch, int nx,
-                                                       int rows, double* speed_part,
-                                                       double* mass_part) {
+__global__ __launch_bounds__(kBlock) void lattice_sums(const LatticeArgs a, int rows, double* speed_part, double* mass_part) {
   __shared__ double sh_s[kBlock], sh_m[kBlock];
   double s = 0.0, m = 0.0;
-  const long n = (long)nx * rows;
+  const long n = (long)a.nx * rows;
   for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long)gridDim.x * kBlock) {
-    const int r = (int)(i / nx), x = (int)(i - (long)r * nx);
-    const long c = (long)r * row_pitch + x;
+    const int r = (int)(i / a.nx), x = (int)(i - (long)r * a.nx);
     float f[kQ];
-#pragma unroll
-    for (int k = 0; k < kQ; k++) f[k] = lat[k * ps + c];
+    gather_cell(a, r, x, f);
     float rho, ux, uy;
     moments_exact(f, rho, ux, uy);
     m += (double)rho;
-    if (!mask[(long)r * pitch + x]) s += (double)sqrtf((ux * ux) + (uy * uy));
+    if (!cell_blocked(a, r, x)) s += (double)sqrtf((ux * ux) + (uy * uy));
   }
   sh_s[threadIdx.x] = s;  sh_m[threadIdx.x] = m;
   __syncthreads();

@@ -12,8 +12,13 @@ tolerance, the check.py rule: max |100*(ref-sim)/sim| <= 1 % on av_vels and on p
 """
 import os
 
+import functools
+
 import numpy as np
 import pytest
+
+import moments_model
+import test_frames_format as frames_model
 
 pytestmark = pytest.mark.gpu
 
@@ -478,3 +483,82 @@ def test_degenerate_grid_sizes_bitwise(lbm, oracle, monkeypatch, nx, ny, kernel)
     ref_cells, ref_av, got_cells, got_av, _ = run_both(lbm, oracle, p, ob, cells, 9)
     assert np.array_equal(ref_cells.view(np.uint32), got_cells.view(np.uint32))
     np.testing.assert_allclose(got_av, ref_av, rtol=AV_RTOL)
+
+
+PADDED_STEPS, PADDED_EVERY = 7, 2
+PADDED_PROBES = ((45, 4), (129, 8), (0, 0), (64, 7))   # inside the obstacle block; last column of the top row; ...
+
+
+@functools.lru_cache(maxsize=None)
+def padded_reference(lbm, oracle):
+    """The 130 x 9 case of test_readers_and_recorders_with_padded_planes and what the oracle makes of it, computed once:
+    the final_state after each of the first PADDED_STEPS steps, and the mean sums of both orders."""
+    p, ob, cells = random_case(lbm, 130, 9, 130, walls=False)
+    ob[3:6, 40:50] = 1
+    ref, states = cells.copy(), {}
+    for t in range(1, PADDED_STEPS + 1):
+        oracle.run(p, ref, ob, 1)
+        states[t] = oracle.final_state(p, ref, ob)
+    _, sums, sums2, n = moments_model.oracle_sums2(oracle, p, ob, cells, 0, PADDED_STEPS, PADDED_EVERY)
+    return p, ob, cells, ref, states, sums, sums2, n
+
+
+@pytest.mark.parametrize("slabs", [1, 3])
+def test_readers_and_recorders_with_padded_planes(lbm, oracle, monkeypatch, slabs):
+    """plane_stride (208) != mask pitch (192) != nx (130), the one layout in which a stride taken for another reads the
+    wrong plane or row: every reader of a stored lattice and every per-pass record kernel, bit for bit against the
+    oracle, on one slab and across three."""
+    monkeypatch.setenv("LBM_PLANE_PAD_FLOATS", "16")
+    monkeypatch.setenv("LBM_HALO", "memcpy")
+    p, ob, cells, ref, states, sums, sums2, n_samples = padded_reference(lbm, oracle)
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint64)
+    sample_steps = frames_model.frame_steps(0, PADDED_STEPS, PADDED_EVERY)
+    assert ob[PADDED_PROBES[0][1], PADDED_PROBES[0][0]] == 1 and n_samples == len(sample_steps) == 4
+
+    with lbm.Engine(p, ob, cells, n_gpus=slabs) as eng:                      # the readers
+        assert eng.info()["resident_steps"] == 0                               # 130 columns: the per-pass path
+        eng.run(PADDED_STEPS)
+        assert np.array_equal(bits(eng.cells()), bits(ref))
+        fields = eng.final_state()
+        for k in ("u_x", "u_y", "u", "pressure"):
+            assert np.array_equal(bits(fields[k]), bits(states[PADDED_STEPS][k])), k
+        assert eng.av_velocity() == pytest.approx(oracle.av_velocity(p, ref, ob), rel=AV_RTOL)
+        # the device adds the cells' fp32 densities (the nine populations summed in index order, as total_density()
+        # and av_velocity() form them) in double.  On 1170 random cells the fp32 rounding of each density does not
+        # average out of the total the way it does on a reference data set (1.1e-9 relative against a float64 sum of
+        # the populations), so the float64 sum is taken over those same fp32 densities
+        rho = ref[..., 0].copy()
+        for k in range(1, 9):
+            rho = rho + ref[..., k]
+        assert rho.dtype == np.float32
+        assert eng.total_density() == pytest.approx(float(rho.astype(np.float64).sum()), rel=1e-9)
+        assert eng.total_density() == pytest.approx(oracle.total_density(p, ref), rel=1e-3)
+
+    with lbm.Engine(p, ob, cells, n_gpus=slabs) as eng:                      # frames
+        eng.set_frames(PADDED_EVERY, 8)
+        eng.run(PADDED_STEPS)
+        steps, frames = eng.frames()
+        assert steps.tolist() == sample_steps
+        for i, tt in enumerate(sample_steps):
+            assert np.array_equal(bits(frames[i]), bits(states[tt + 1]["u"])), tt
+
+    xs, ys = np.array([c[0] for c in PADDED_PROBES]), np.array([c[1] for c in PADDED_PROBES])
+    with lbm.Engine(p, ob, cells, n_gpus=slabs) as eng:                      # probes
+        eng.set_probes(PADDED_PROBES, PADDED_EVERY, 8)
+        eng.run(PADDED_STEPS)
+        steps, samples = eng.probes()
+        assert steps.tolist() == sample_steps
+        for i, tt in enumerate(sample_steps):
+            want = np.stack([states[tt + 1][k][ys, xs] for k in ("u_x", "u_y", "u", "pressure")], axis=1)
+            assert np.array_equal(bits(samples[i]), bits(want)), tt
+
+    with lbm.Engine(p, ob, cells, n_gpus=slabs) as eng:                      # mean fields, both orders
+        eng.set_mean_order(PADDED_EVERY, 2)
+        eng.run(PADDED_STEPS)
+        got, n = eng.mean_sums()
+        got2, n2 = eng.moment_sums()
+        assert n == n2 == n_samples
+        for k in sums:
+            assert np.array_equal(bits(got[k]), bits(sums[k])), k
+        for k in sums2:
+            assert np.array_equal(bits(got2[k]), bits(sums2[k])), k

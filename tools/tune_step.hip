@@ -119,8 +119,8 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(mask, m.data(), (size_t)cells, hipMemcpyHostToDevice));
   }
   auto fill = [&](float* L, long ps) {
-    hipLaunchKernelGGL(init_equilibrium, dim3((cells + 255) / 256), dim3(256), 0, 0, L, ps, (long)nx, nx, ny,
-                       0.1f * 4.f / 9.f, 0.1f / 9.f, 0.1f / 36.f);
+    hipLaunchKernelGGL(init_equilibrium, dim3((cells + 255) / 256), dim3(256), 0, 0, LatticeArgs{nullptr, L, nullptr, ps, (long)nx, nx, nx},
+                       ny, 0.1f * 4.f / 9.f, 0.1f / 9.f, 0.1f / 36.f);
   };
 
   std::vector<Variant> vars = {
