@@ -6,6 +6,7 @@
 // No CPU compute path exists here: without a HIP device every compute entry point fails.
 #include "../../include/lbm_hip.h"
 #include "lbm_kernels.hip.h"
+#include "lbm_own.h"
 #include "lbm_plan.h"
 
 #include <hip/hip_runtime.h>
@@ -158,56 +159,115 @@ RcclApi* rccl() {
   RcclApi* rc_api_ = rccl();                                                    \
   if (!rc_api_) LBM_FAIL(ret, "RCCL is not available: %s", g_rccl_error)
 
+// ---- owned device resources (lbm_own.h) -------------------------------------------------------------------------
+// A member of one of these types is released with the struct that declares it; every release call of the file is here.
+using lbm_own::Own;
+template <class T> void free_device(T* p) { (void)hipFree(p); }
+template <class T> void free_pinned(T* p) { (void)hipHostFree(p); }
+void destroy_event(hipEvent_t e) { (void)hipEventDestroy(e); }
+void destroy_stream(hipStream_t s) { (void)hipStreamDestroy(s); }
+void destroy_graph(hipGraph_t g) { (void)hipGraphDestroy(g); }
+void destroy_graph_exec(hipGraphExec_t g) { (void)hipGraphExecDestroy(g); }
+
+// h takes what make(&raw) made, after releasing what it held (a failed make leaves it empty); returns make's verdict,
+// for HIP_TRY or a message of the caller's own
+template <class Handle, class Make>
+hipError_t remake(Handle& h, Make make) {
+  h.reset();
+  decltype(h.get()) raw{};
+  const hipError_t e = make(&raw);
+  h.reset(raw);
+  return e;
+}
+template <class T>
+struct DeviceBuf : Own<T*, free_device<T>> {
+  hipError_t alloc_bytes(size_t bytes) { return remake(*this, [&](T** p) { return hipMalloc(p, bytes); }); }
+  hipError_t alloc(size_t count) { return alloc_bytes(count * sizeof(T)); }
+};
+template <class T>
+struct PinnedBuf : Own<T*, free_pinned<T>> {
+  hipError_t alloc(size_t count) { return remake(*this, [&](T** p) { return hipHostMalloc(p, count * sizeof(T)); }); }
+};
+struct Event : Own<hipEvent_t, destroy_event> {
+  hipError_t create(unsigned flags) { return remake(*this, [&](hipEvent_t* e) { return hipEventCreateWithFlags(e, flags); }); }
+};
+struct Stream : Own<hipStream_t, destroy_stream> {
+  hipError_t create() { return remake(*this, [](hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }); }
+};
+using Graph = Own<hipGraph_t, destroy_graph>;
+using GraphExec = Own<hipGraphExec_t, destroy_graph_exec>;
+// scope guards of the RCCL exchange: a stream capture that was begun is ended (and its graph dropped), an RCCL group that
+// was opened is closed, on every way out; the success path takes them over with release() and ends them itself
+void abandon_capture(hipStream_t st) {
+  hipGraph_t g = nullptr;
+  (void)hipStreamEndCapture(st, &g);
+  Graph drop(g);
+}
+void close_group(const RcclApi* nc) { (void)nc->GroupEnd(); }
+using OpenCapture = Own<hipStream_t, abandon_capture>;
+using OpenGroup = Own<const RcclApi*, close_group>;
+
+// What a slab owns, it declares: the members go in reverse order of declaration once ~Slab has run, so the streams come
+// first (they go last, behind the events and buffers their work used) and the chunk graphs last (they go first).
 struct Slab {
   int device = 0;
   int row_first = 0;  // global row of slab row 0
   int rows = 0;       // owned rows
   int accel_row = lbm::kNoRow;  // slab row (may be a halo row) holding global row ny-2
   int accel_row2 = lbm::kNoRow; // its second periodic image among the halo rows (a ring of ONE slab with 3-step passes)
-  float* lat_alloc[2] = {nullptr, nullptr};  // (rows + 2*kHaloRows) x row_pitch each
-  float* lat[2] = {nullptr, nullptr};        // row 0 of each lattice (= lat_alloc + kHaloRows rows)
-  unsigned char* mask_alloc = nullptr;       // (rows + 2*kMaskHalo) x pitch: neighbour rows below and above
-  unsigned char* mask = nullptr;             // row 0 of the mask
-  float* partials = nullptr;  // kPartSlots x part_stride
-  double* tot_u = nullptr;    // capacity entries: per-step sum of |u| over this slab
-  double* scratch = nullptr;  // 2 x kSumBlocks doubles for lattice_sums
-  double* reduce_buf = nullptr;  // ranked contexts: capacity doubles for the av_vels all-reduce
-  int* flushed_dev = nullptr; // graph replay: index of the first step of the chunk being reduced
-  uint4* res_gran = nullptr;               // resident kernel: seam granules {v, v, v, tag}: [2][bands][2][nx]
-  float* res_part = nullptr;               // resident kernel: per-band partial sums of a launch, [kResidentChunk][bands]
-  int* res_status = nullptr;               // resident kernel: 0, or the reason a workgroup gave up
-  int* res_status_host = nullptr;          // pinned copy of it, refreshed behind every launch (read by lbm_sync)
-  float* frames = nullptr;                 // lbm_set_frames: [frame slots][rows][nx] |u| of the owned rows
-  lbm::probe_vec* probe_ring = nullptr;    // lbm_set_probes: [rows of samples][probes]; a slab writes the probes in its rows
-  lbm::ProbeEntry* probe_table = nullptr;  // ... those, sorted by row (+ one word per band where the resident kernel runs)
-  int probe_count = 0;                     // ... and how many they are
-  double* mean_sums = nullptr;             // lbm_set_mean: four planes [rows][nx]: sums of u_x, u_y, |u|, pressure of the owned rows;
-                                           // lbm_set_mean_order(.., 2): eight, then u_x u_x, u_y u_y, u_x u_y, pressure pressure
-  hipGraphExec_t chunk_graph[2] = {nullptr, nullptr};  // kPartSlots timesteps + their reduce, by lattice parity
-  hipStream_t compute = nullptr, comm = nullptr;
-  hipEvent_t ev_boundary = nullptr, ev_halo = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
-  hipEvent_t ev_interior[2] = {nullptr, nullptr};  // interior kernel of step t -> [t & 1]
-  hipEvent_t ev_flush = nullptr;                   // partials reduced: their slots may be reused
-  hipEvent_t ev_step = nullptr;                    // stale-halo mode: whole-slab pass finished; graph replay: join
-  hipEvent_t ev_fork = nullptr;                    // graph replay: the other streams join the capture / follow the chunks
-  hipEvent_t ev_x[2] = {nullptr, nullptr};         // stale-halo mode: exchange for pass m landed -> [(m + 1) & 1]
+  Stream compute_own, comm;
+  hipStream_t compute = nullptr;  // the compute stream in use: compute_own, or (members 1.. of a batch, whose compute_own
+                                  // is empty) member 0's, borrowed
   // band groups (single periodic slab, c->plan.band_groups > 1): interior bands of group g run on group_stream(g) -- the
   // compute stream for g = 0, group_extra[g - 1] after it -- and the seam bands on the comm stream
-  hipStream_t group_extra[kMaxBandGroups - 1] = {nullptr, nullptr};
-  hipEvent_t ev_gi[2][kMaxBandGroups] = {};        // interior bands of group g in pass m done -> [m & 1][g]
-  hipEvent_t ev_gs[2] = {nullptr, nullptr};        // seam bands of pass m done -> [m & 1]
-  // freshest-available mode (LBM_HALO_FRESHEST), allocated at its first use
-  float* fresh_stage = nullptr;          // [parity][side: 0 south halo, 1 north halo][row_pitch]: this pass's rows, if they make it
-  unsigned* fresh_arrived = nullptr;     // [parity][side]: id (global step + 1) of the step whose row the staging holds
-  unsigned* fresh_id_src = nullptr;      // [parity]: the id this slab ships behind its rows (device copies)
-  int* fresh_decision = nullptr;         // bit 0 / 1: south / north staging row adopted in the current pass
-  unsigned char* fresh_log = nullptr;    // [capacity]: the decision of every step (3 where the halos were fresh anyway)
-  hipEvent_t ev_fresh[2] = {nullptr, nullptr};  // LBM_FRESH_FORCE=wait: this pass's rows and ids are out
-  ncclComm_t nccl = nullptr;
+  Stream group_extra[kMaxBandGroups - 1];
+  Event ev_boundary, ev_halo, ev_t0, ev_t1;
+  Event ev_interior[2];               // interior kernel of step t -> [t & 1]
+  Event ev_flush;                     // partials reduced: their slots may be reused
+  Event ev_step;                      // stale-halo mode: whole-slab pass finished; graph replay: join
+  Event ev_fork;                      // graph replay: the other streams join the capture / follow the chunks
+  Event ev_x[2];                      // stale-halo mode: exchange for pass m landed -> [(m + 1) & 1]
+  Event ev_gi[2][kMaxBandGroups];     // interior bands of group g in pass m done -> [m & 1][g]
+  Event ev_gs[2];                     // seam bands of pass m done -> [m & 1]
+  DeviceBuf<float> lat_alloc[2];      // (rows + 2*kHaloRows) x row_pitch each
+  float* lat[2] = {nullptr, nullptr}; // row 0 of each lattice (= lat_alloc + kHaloRows rows)
+  DeviceBuf<unsigned char> mask_alloc;  // (rows + 2*kMaskHalo) x pitch: neighbour rows below and above
+  unsigned char* mask = nullptr;        // row 0 of the mask
+  DeviceBuf<float> partials;     // kPartSlots x part_stride
+  DeviceBuf<double> tot_u;       // capacity entries: per-step sum of |u| over this slab
+  DeviceBuf<double> scratch;     // 2 x kSumBlocks doubles for lattice_sums
+  DeviceBuf<double> reduce_buf;  // ranked contexts: capacity doubles for the av_vels all-reduce
+  DeviceBuf<int> flushed_dev;    // graph replay: index of the first step of the chunk being reduced
+  DeviceBuf<uint4> res_gran;               // resident kernel: seam granules {v, v, v, tag}: [2][bands][2][nx]
+  DeviceBuf<float> res_part;               // resident kernel: per-band partial sums of a launch, [kResidentChunk][bands]
+  DeviceBuf<int> res_status;               // resident kernel: 0, or the reason a workgroup gave up
+  PinnedBuf<int> res_status_host;          // pinned copy of it, refreshed behind every launch (read by lbm_sync)
+  DeviceBuf<float> frames;                 // lbm_set_frames: [frame slots][rows][nx] |u| of the owned rows
+  DeviceBuf<lbm::probe_vec> probe_ring;    // lbm_set_probes: [rows of samples][probes]; a slab writes the probes in its rows
+  DeviceBuf<lbm::ProbeEntry> probe_table;  // ... those, sorted by row (+ one word per band where the resident kernel runs)
+  int probe_count = 0;                     // ... and how many they are
+  DeviceBuf<double> mean_sums;             // lbm_set_mean: four planes [rows][nx]: sums of u_x, u_y, |u|, pressure of the owned rows;
+                                           // lbm_set_mean_order(.., 2): eight, then u_x u_x, u_y u_y, u_x u_y, pressure pressure
+  // freshest-available mode (LBM_HALO_FRESHEST), allocated at its first use in this order: whole once ev_fresh[1] exists
+  DeviceBuf<float> fresh_stage;          // [parity][side: 0 south halo, 1 north halo][row_pitch]: this pass's rows, if they make it
+  DeviceBuf<unsigned> fresh_arrived;     // [parity][side]: id (global step + 1) of the step whose row the staging holds
+  DeviceBuf<unsigned> fresh_id_src;      // [parity]: the id this slab ships behind its rows (device copies)
+  DeviceBuf<int> fresh_decision;         // bit 0 / 1: south / north staging row adopted in the current pass
+  DeviceBuf<unsigned char> fresh_log;    // [capacity]: the decision of every step (3 where the halos were fresh anyway)
+  Event ev_fresh[2];                     // LBM_FRESH_FORCE=wait: this pass's rows and ids are out
+  ncclComm_t nccl = nullptr;             // destroyed by ~Slab
+  GraphExec chunk_graph[2];  // kPartSlots timesteps + their reduce, by lattice parity
   lbm::SlotCounts slot_counts;  // partials written into each buffered slot (launch geometries differ)
   int blocks_main = 0;      // interior rows (or all rows in HALO_SELF)
   int blocks_boundary = 0;  // rows 0 and rows-1 (halo modes)
   long fluid_cells = 0;     // non-blocked cells among the owned rows
+
+  // the order-dependent part: graphs that captured RCCL operations hold on to the communicator, so they go first
+  ~Slab() {
+    if (!compute || hipSetDevice(device) != hipSuccess) return;  // never built: the compute stream is a slab's first resource
+    for (GraphExec& g : chunk_graph) g.reset();
+    if (nccl && g_rccl.CommDestroy) g_rccl.CommDestroy(nccl);
+  }
 };
 
 constexpr int kSumBlocks = 1024;
@@ -312,7 +372,7 @@ struct SlabTeam {
 // hip::Stream::EndCapture() of ROCm 7.2 recurses without end once three or more side streams have waited on each
 // other's events (profiles/r03_graph_capture_defect.md, tools/capture_ring_repro.hip).
 struct GraphBuilder {
-  hipGraph_t graph = nullptr;
+  Graph graph;
   struct VStream { hipStream_t key; std::vector<hipGraphNode_t> last; };
   struct VEvent { hipEvent_t key; std::vector<hipGraphNode_t> nodes; };
   std::vector<VStream> streams;
@@ -381,8 +441,7 @@ struct lbm_ctx {
   bool ranked = false;      // created by lbm_create_rank* (one process per GPU: rank / world describe the ring)
   bool hosted = false;      // ... with the host's own message passing instead of RCCL (lbm_create_rank_hosted)
   lbm_host_comm host_comm = {nullptr, nullptr, nullptr};
-  float* host_send[2] = {nullptr, nullptr};  // pinned staging buffers of the hosted exchange: kHaloRows rows each
-  float* host_recv[2] = {nullptr, nullptr};
+  PinnedBuf<float> host_send[2], host_recv[2];  // pinned staging buffers of the hosted exchange: kHaloRows rows each
   int row_first = 0, row_count = 0;
   int slot_fill = 0;  // partial slots used since the last reduce
   KernelPlan plan;    // which kernels advance this context and their launch geometry (lbm_plan.h: plan_kernels)
@@ -394,10 +453,10 @@ struct lbm_ctx {
   Recorder rec;                     // the one recorder: animation frames (lbm_set_frames), point probes (lbm_set_probes) or
                                     // mean fields (lbm_set_mean)
   std::vector<lbm_probe> probe_cells;  // the probed global cells, in the caller's order (a probes row has that many samples)
-  // steady-state runs (lbm_run_until), allocated by the first such call
-  lbm::SteadyState* steady_state = nullptr;  // device: what the checks of the current call have found
-  int* steady_stop_host = nullptr;  // pinned: its stop word after segment j, in slot j & 1 ...
-  hipEvent_t ev_steady[2] = {nullptr, nullptr};  // ... behind these events
+  // steady-state runs (lbm_run_until), allocated by the first such call in this order: whole once ev_steady[1] exists
+  DeviceBuf<lbm::SteadyState> steady_state;  // device: what the checks of the current call have found
+  PinnedBuf<int> steady_stop_host;  // pinned: its stop word after segment j, in slot j & 1 ...
+  Event ev_steady[2];               // ... behind these events
 };
 
 // B independent single-slab lattices of one shape on one device, advanced together (lbm_create_batch).  The members
@@ -406,27 +465,27 @@ struct lbm_ctx {
 // lbm::resident_band<..., BATCH = true>, members_per_launch members each, one after the other on that stream.
 struct lbm_batch {
   std::vector<lbm_ctx*> members;
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;      // member 0's compute stream, borrowed
   int resident = 0;                 // the members are resident-eligible: long calls run batched
   int member_wgs = 0;               // working workgroups of one member
   int members_per_launch = 1;       // co-resident members in one launch: 8 one-XCD members, else floor(CUs / member_wgs)
   int launches = 0;                 // launches per chunk (sub-batches)
   int cur = 0;                      // lattice of every member holding the current state
   int steps_done = 0;
-  lbm::ResidentMember* table = nullptr;  // device: [parity of cur][members]
-  int* status = nullptr;            // device: 0, or kResidentTimeout once a workgroup of any batched launch gave up
-  int* status_host = nullptr;       // pinned copy behind every run; every member's lbm_sync reports it
-  lbm::ResidentFrames* frame_table = nullptr;  // device: [members], allocated when the first member arms frames
-  lbm::ResidentProbes* probe_table = nullptr;  // device: [members], allocated when the first member arms probes
-  lbm::ResidentMean* mean_table = nullptr;     // device: [members], allocated when the first member arms the mean fields
+  DeviceBuf<lbm::ResidentMember> table;  // device: [parity of cur][members]
+  DeviceBuf<int> status;            // device: 0, or kResidentTimeout once a workgroup of any batched launch gave up
+  PinnedBuf<int> status_host;       // pinned copy behind every run; every member's lbm_sync reports it
+  DeviceBuf<lbm::ResidentFrames> frame_table;  // device: [members], allocated when the first member arms frames
+  DeviceBuf<lbm::ResidentProbes> probe_table;  // device: [members], allocated when the first member arms probes
+  DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
   int armed[kRecKinds] = {0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
                                     // (a batch records one kind, so at most one count is non-zero)
-  // steady-state runs (lbm_batch_run_until), allocated by the first such call
-  lbm::SteadyState* steady_state = nullptr;    // device: [members]
-  lbm::SteadyMember* steady_members = nullptr; // device: [members]
-  lbm::SteadyBatch* steady_batch = nullptr;    // device
-  int* steady_stop_host = nullptr;  // pinned: all_steady after the last segment ...
-  hipEvent_t ev_steady = nullptr;   // ... behind this event
+  // steady-state runs (lbm_batch_run_until), allocated by the first such call; steady_state last: the set is whole once it exists
+  DeviceBuf<lbm::SteadyMember> steady_members; // device: [members]
+  DeviceBuf<lbm::SteadyBatch> steady_batch;    // device
+  PinnedBuf<int> steady_stop_host;  // pinned: all_steady after the last segment ...
+  Event ev_steady;                  // ... behind this event
+  DeviceBuf<lbm::SteadyState> steady_state;    // device: [members]
 };
 
 namespace {
@@ -709,18 +768,25 @@ int exchange_halos(lbm_ctx* c, int depth, int src, int dst, int slot) {
       }
     }
     // one thread driving several communicators must group them; with one thread per slab each
-    // thread groups its own four operations.  A group once opened is closed on every path: an error inside it must
-    // not leave the communicator in group mode.
+    // thread groups its own four operations.  The guards (OpenGroup, OpenCapture) close a group once opened and end a
+    // capture once begun on every path: an error must leave neither the communicator in group mode nor the comm
+    // stream capturing.
     RCCL_OR_FAIL(LBM_FAILURE);
     const RcclApi& nc = *rc_api_;
     // while a chunk is being built: the group is captured on the (single) comm stream alone -- a capture with one
     // user stream, its origin -- and enters the chunk as a child-graph node behind the comm stream's dependencies
     const bool building = (c->builder != nullptr);
+    OpenCapture capture;
     if (building) {
       if (c->n_slabs != 1) LBM_FAIL(LBM_FAILURE, "hipGraph chunk: the RCCL transport is built for one communicator per process");
       HIP_TRY(LBM_FAILURE, hipStreamBeginCapture(c->slab[0].comm, hipStreamCaptureModeRelaxed));
+      capture.reset(c->slab[0].comm);
     }
-    if (!c->team) NCCL_TRY(LBM_FAILURE, nc.GroupStart());
+    OpenGroup group;  // the one group of a context without a team
+    if (!c->team) {
+      NCCL_TRY(LBM_FAILURE, nc.GroupStart());
+      group.reset(&nc);
+    }
     int rc = for_slabs(c, [&](int s) -> int {
       Slab& sl = c->slab[s];
       float* from = sl.lat[src];
@@ -731,9 +797,11 @@ int exchange_halos(lbm_ctx* c, int depth, int src, int dst, int slot) {
       // the first send pairs with the peer's first receive)
       lbm_halo_op ops[4];
       if (lbm_halo_plan(sl.rows, parts, me, depth, ops) != LBM_SUCCESS) return LBM_FAILURE;
+      OpenGroup own_group;  // with a team: this thread's
       if (c->team) {
         HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
         NCCL_TRY(LBM_FAILURE, nc.GroupStart());
+        own_group.reset(&nc);
       }
       ncclResult_t res = ncclSuccess;
       for (int i = 0; i < 4 && res == ncclSuccess; i++) {
@@ -743,20 +811,20 @@ int exchange_halos(lbm_ctx* c, int depth, int src, int dst, int slot) {
         res = ops[i].is_send ? nc.Send(ptr, count, ncclFloat, ops[i].peer, sl.nccl, sl.comm)
                              : nc.Recv(ptr, count, ncclFloat, ops[i].peer, sl.nccl, sl.comm);
       }
-      if (c->team) {
-        const ncclResult_t end = nc.GroupEnd();
+      if (own_group) {
+        const ncclResult_t end = own_group.release()->GroupEnd();
         if (res == ncclSuccess) res = end;
       }
       if (res != ncclSuccess) LBM_FAIL(LBM_FAILURE, "RCCL error in the halo exchange: %s", nc.GetErrorString(res));
       return LBM_SUCCESS;
     });
-    if (!c->team) {
-      const ncclResult_t end = nc.GroupEnd();
+    if (group) {
+      const ncclResult_t end = group.release()->GroupEnd();
       if (rc == LBM_SUCCESS && end != ncclSuccess) { raise_error(__LINE__, "RCCL error: %s (ncclGroupEnd)", nc.GetErrorString(end)); rc = LBM_FAILURE; }
     }
-    if (building) {
-      hipGraph_t child = nullptr;
-      const hipError_t ended = hipStreamEndCapture(c->slab[0].comm, &child);
+    if (capture) {
+      Graph child;  // the node holds its own copy
+      const hipError_t ended = remake(child, [&](hipGraph_t* g) { return hipStreamEndCapture(capture.release(), g); });
       if (rc == LBM_SUCCESS && ended != hipSuccess) { raise_error(__LINE__, "HIP error: %s (capture of the RCCL group)", hipGetErrorString(ended)); rc = LBM_FAILURE; }
       if (rc == LBM_SUCCESS) {
         std::vector<hipGraphNode_t>& last = c->builder->last_of(c->slab[0].comm);
@@ -765,7 +833,6 @@ int exchange_halos(lbm_ctx* c, int depth, int src, int dst, int slot) {
         if (added != hipSuccess) { raise_error(__LINE__, "HIP error: %s (hipGraphAddChildGraphNode)", hipGetErrorString(added)); rc = LBM_FAILURE; }
         else last.assign(1, node);
       }
-      if (child) (void)hipGraphDestroy(child);  // the node holds its own copy
     }
     if (rc != LBM_SUCCESS) return rc;
     if (stale) {
@@ -1118,7 +1185,7 @@ bool graph_is_sound(hipGraph_t graph, const char* dump_path) {
   return acyclic && self_edges == 0 && foreign == 0;
 }
 
-int build_chunk(lbm_ctx* c, hipGraphExec_t* out) {
+int build_chunk(lbm_ctx* c, GraphExec& out) {
   const bool halo = (c->halo != HALO_SELF);
   int adv;
   const int passes = chunk_passes(c, &adv);
@@ -1130,7 +1197,7 @@ int build_chunk(lbm_ctx* c, hipGraphExec_t* out) {
   const int saved_cur = c->cur, saved_fill = c->slot_fill;
   GraphBuilder gb;
   HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
-  HIP_TRY(LBM_FAILURE, hipGraphCreate(&gb.graph, 0));
+  HIP_TRY(LBM_FAILURE, remake(gb.graph, [](hipGraph_t* g) { return hipGraphCreate(g, 0); }));
   c->builder = &gb;
   c->slot_fill = 0;
   // Nothing is recorded yet: the first waits of pass 0 (I(-1), B(-1), the previous exchange) find no snapshot and
@@ -1156,16 +1223,12 @@ int build_chunk(lbm_ctx* c, hipGraphExec_t* out) {
   c->builder = nullptr;
   c->cur = saved_cur;  // an even number of passes
   c->slot_fill = saved_fill;
-  if (rc != LBM_SUCCESS) { (void)hipGraphDestroy(gb.graph); return LBM_FAILURE; }
+  if (rc != LBM_SUCCESS) return LBM_FAILURE;
   const char* dump_path = getenv("LBM_GRAPH_DUMP");
-  if ((dump_path && !graph_is_sound(gb.graph, dump_path)) || env_int("LBM_GRAPH_DUMP_ONLY", 0)) {
-    (void)hipGraphDestroy(gb.graph);
+  if ((dump_path && !graph_is_sound(gb.graph, dump_path)) || env_int("LBM_GRAPH_DUMP_ONLY", 0))
     LBM_FAIL(LBM_FAILURE, "hipGraph chunk: the graph is not instantiated (unsound, or LBM_GRAPH_DUMP_ONLY)");
-  }
-  const hipError_t inst = hipGraphInstantiate(out, gb.graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(gb.graph);
-  HIP_TRY(LBM_FAILURE, inst);
-  return LBM_SUCCESS;
+  HIP_TRY(LBM_FAILURE, remake(out, [&](hipGraphExec_t* e) { return hipGraphInstantiate(e, gb.graph, nullptr, nullptr, 0); }));
+  return LBM_SUCCESS;  // gb.graph goes with gb: the executable graph holds its own copy
 }
 
 // replays as many whole chunks as fit in front of the last timestep of this call; returns the timesteps done
@@ -1177,11 +1240,10 @@ int replay_chunks(lbm_ctx* c, int n_steps, int first_step, int* done) {
   const int n_chunks = (n_steps - 1) / chunk_steps;
   if (n_chunks <= 0 || c->slot_fill != 0) return LBM_SUCCESS;
   Slab& s0 = c->slab[0];
-  hipGraphExec_t& exec = s0.chunk_graph[c->cur];
-  if (!exec && build_chunk(c, &exec) != LBM_SUCCESS) {
+  GraphExec& exec = s0.chunk_graph[c->cur];
+  if (!exec && build_chunk(c, exec) != LBM_SUCCESS) {
     // e.g. slabs on several devices: go on launch by launch
     fprintf(stderr, "lbm_hip: hipGraph chunk not built (%s); continuing with stream launches\n", g_last_error);
-    exec = nullptr;
     c->plan.use_graph = 0;
     return LBM_SUCCESS;
   }
@@ -1546,17 +1608,17 @@ int run_steps(lbm_ctx* c, int n_steps, float* kernel_ms) {
 int ensure_fresh_buffers(lbm_ctx* c) {
   for (int s = 0; s < c->n_slabs; s++) {
     Slab& sl = c->slab[s];
-    if (sl.fresh_stage) continue;
+    if (sl.ev_fresh[1]) continue;  // created last: the set is whole (an attempt that failed half-way starts again)
     HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-    HIP_TRY(LBM_FAILURE, hipMalloc(&sl.fresh_stage, 4 * (size_t)c->row_pitch * sizeof(float)));
-    HIP_TRY(LBM_FAILURE, hipMalloc(&sl.fresh_arrived, 4 * sizeof(unsigned)));
-    HIP_TRY(LBM_FAILURE, hipMalloc(&sl.fresh_id_src, 2 * sizeof(unsigned)));
-    HIP_TRY(LBM_FAILURE, hipMalloc(&sl.fresh_decision, sizeof(int)));
-    HIP_TRY(LBM_FAILURE, hipMalloc(&sl.fresh_log, (size_t)c->capacity));
+    HIP_TRY(LBM_FAILURE, sl.fresh_stage.alloc(4 * (size_t)c->row_pitch));
+    HIP_TRY(LBM_FAILURE, sl.fresh_arrived.alloc(4));
+    HIP_TRY(LBM_FAILURE, sl.fresh_id_src.alloc(2));
+    HIP_TRY(LBM_FAILURE, sl.fresh_decision.alloc(1));
+    HIP_TRY(LBM_FAILURE, sl.fresh_log.alloc((size_t)c->capacity));
     HIP_TRY(LBM_FAILURE, hipMemset(sl.fresh_arrived, 0, 4 * sizeof(unsigned)));
     HIP_TRY(LBM_FAILURE, hipMemset(sl.fresh_decision, 0, sizeof(int)));
     HIP_TRY(LBM_FAILURE, hipMemset(sl.fresh_log, 3, (size_t)c->capacity));  // synchronous and first passes: both sides fresh
-    for (int i = 0; i < 2; i++) HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_fresh[i], hipEventDisableTiming));
+    for (int i = 0; i < 2; i++) HIP_TRY(LBM_FAILURE, sl.ev_fresh[i].create(hipEventDisableTiming));
   }
   return LBM_SUCCESS;
 }
@@ -1778,86 +1840,34 @@ int run_steps_stale(lbm_ctx* c, int n_steps, float* kernel_ms) {
   return kernel_ms ? read_step_timing(c, n_steps, kernel_ms) : LBM_SUCCESS;
 }
 
-void free_slab(Slab& sl) {
-  if (hipSetDevice(sl.device) != hipSuccess) return;
-  // graphs that captured RCCL operations hold on to the communicator: they go first
-  for (int i = 0; i < 2; i++)
-    if (sl.chunk_graph[i]) { (void)hipGraphExecDestroy(sl.chunk_graph[i]); sl.chunk_graph[i] = nullptr; }
-  if (sl.nccl && g_rccl.CommDestroy) g_rccl.CommDestroy(sl.nccl);
-  for (int i = 0; i < 2; i++) if (sl.lat_alloc[i]) (void)hipFree(sl.lat_alloc[i]);
-  if (sl.mask_alloc) (void)hipFree(sl.mask_alloc);
-  if (sl.partials) (void)hipFree(sl.partials);
-  if (sl.tot_u) (void)hipFree(sl.tot_u);
-  if (sl.scratch) (void)hipFree(sl.scratch);
-  if (sl.reduce_buf) (void)hipFree(sl.reduce_buf);
-  if (sl.flushed_dev) (void)hipFree(sl.flushed_dev);
-  if (sl.fresh_stage) (void)hipFree(sl.fresh_stage);
-  if (sl.fresh_arrived) (void)hipFree(sl.fresh_arrived);
-  if (sl.fresh_id_src) (void)hipFree(sl.fresh_id_src);
-  if (sl.fresh_decision) (void)hipFree(sl.fresh_decision);
-  if (sl.fresh_log) (void)hipFree(sl.fresh_log);
-  for (int i = 0; i < 2; i++) if (sl.ev_fresh[i]) (void)hipEventDestroy(sl.ev_fresh[i]);
-  if (sl.res_gran) (void)hipFree(sl.res_gran);
-  if (sl.res_part) (void)hipFree(sl.res_part);
-  if (sl.res_status) (void)hipFree(sl.res_status);
-  if (sl.res_status_host) (void)hipHostFree(sl.res_status_host);
-  if (sl.frames) (void)hipFree(sl.frames);
-  if (sl.probe_ring) (void)hipFree(sl.probe_ring);
-  if (sl.probe_table) (void)hipFree(sl.probe_table);
-  if (sl.mean_sums) (void)hipFree(sl.mean_sums);
-  if (sl.ev_boundary) (void)hipEventDestroy(sl.ev_boundary);
-  if (sl.ev_halo) (void)hipEventDestroy(sl.ev_halo);
-  for (int i = 0; i < 2; i++) if (sl.ev_interior[i]) (void)hipEventDestroy(sl.ev_interior[i]);
-  if (sl.ev_flush) (void)hipEventDestroy(sl.ev_flush);
-  if (sl.ev_step) (void)hipEventDestroy(sl.ev_step);
-  if (sl.ev_fork) (void)hipEventDestroy(sl.ev_fork);
-  for (int i = 0; i < 2; i++) if (sl.ev_x[i]) (void)hipEventDestroy(sl.ev_x[i]);
-  if (sl.ev_t0) (void)hipEventDestroy(sl.ev_t0);
-  if (sl.ev_t1) (void)hipEventDestroy(sl.ev_t1);
-  for (int i = 0; i < 2; i++) {
-    if (sl.ev_gs[i]) (void)hipEventDestroy(sl.ev_gs[i]);
-    for (int g = 0; g < kMaxBandGroups; g++) if (sl.ev_gi[i][g]) (void)hipEventDestroy(sl.ev_gi[i][g]);
-  }
-  for (int g = 0; g < kMaxBandGroups - 1; g++) if (sl.group_extra[g]) (void)hipStreamDestroy(sl.group_extra[g]);
-  if (sl.compute) (void)hipStreamDestroy(sl.compute);
-  if (sl.comm) (void)hipStreamDestroy(sl.comm);
-  sl = Slab();
-}
-
 bool validate_params(const lbm_params* p) {
   // the cell count must fit the reference's int counters (tot_cells, SerialCode/d2q9-bgk.c:411)
   return p && p->nx >= 1 && p->ny >= 2 && p->max_iters >= 0 && (long)p->nx * (long)p->ny <= 2147483647L;
 }
-
-// a device staging buffer that is freed on every way out of the scope that allocated it
-struct DeviceTemp {
-  void* p = nullptr;
-  ~DeviceTemp() { if (p) (void)hipFree(p); }
-  template <typename T> T* as() const { return static_cast<T*>(p); }
-};
 
 // Build one slab: allocate, build the mask on the device, fill the lattice.
 int build_slab(lbm_ctx* c, int s, const ObstacleSource& obst, const float* cells_aos) {
   Slab& sl = c->slab[s];
   const lbm_params& p = c->p;
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-  HIP_TRY(LBM_FAILURE, hipStreamCreateWithFlags(&sl.compute, hipStreamNonBlocking));
-  HIP_TRY(LBM_FAILURE, hipStreamCreateWithFlags(&sl.comm, hipStreamNonBlocking));
-  HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_boundary, hipEventDisableTiming));
-  HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_halo, hipEventDisableTiming));
-  for (int i = 0; i < 2; i++) HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_interior[i], hipEventDisableTiming));
-  HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_flush, hipEventDisableTiming));
-  HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_step, hipEventDisableTiming));
-  HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_fork, hipEventDisableTiming));
-  for (int i = 0; i < 2; i++) HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_x[i], hipEventDisableTiming));
+  HIP_TRY(LBM_FAILURE, sl.compute_own.create());
+  sl.compute = sl.compute_own;
+  HIP_TRY(LBM_FAILURE, sl.comm.create());
+  HIP_TRY(LBM_FAILURE, sl.ev_boundary.create(hipEventDisableTiming));
+  HIP_TRY(LBM_FAILURE, sl.ev_halo.create(hipEventDisableTiming));
+  for (int i = 0; i < 2; i++) HIP_TRY(LBM_FAILURE, sl.ev_interior[i].create(hipEventDisableTiming));
+  HIP_TRY(LBM_FAILURE, sl.ev_flush.create(hipEventDisableTiming));
+  HIP_TRY(LBM_FAILURE, sl.ev_step.create(hipEventDisableTiming));
+  HIP_TRY(LBM_FAILURE, sl.ev_fork.create(hipEventDisableTiming));
+  for (int i = 0; i < 2; i++) HIP_TRY(LBM_FAILURE, sl.ev_x[i].create(hipEventDisableTiming));
   HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_halo, sl.comm));
-  HIP_TRY(LBM_FAILURE, hipEventCreate(&sl.ev_t0));
-  HIP_TRY(LBM_FAILURE, hipEventCreate(&sl.ev_t1));
+  HIP_TRY(LBM_FAILURE, sl.ev_t0.create(hipEventDefault));
+  HIP_TRY(LBM_FAILURE, sl.ev_t1.create(hipEventDefault));
   if (c->plan.band_groups > 1) {
-    for (int g = 0; g < c->plan.band_groups - 1; g++) HIP_TRY(LBM_FAILURE, hipStreamCreateWithFlags(&sl.group_extra[g], hipStreamNonBlocking));
+    for (int g = 0; g < c->plan.band_groups - 1; g++) HIP_TRY(LBM_FAILURE, sl.group_extra[g].create());
     for (int i = 0; i < 2; i++) {
-      HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_gs[i], hipEventDisableTiming));
-      for (int g = 0; g < c->plan.band_groups; g++) HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&sl.ev_gi[i][g], hipEventDisableTiming));
+      HIP_TRY(LBM_FAILURE, sl.ev_gs[i].create(hipEventDisableTiming));
+      for (int g = 0; g < c->plan.band_groups; g++) HIP_TRY(LBM_FAILURE, sl.ev_gi[i][g].create(hipEventDisableTiming));
     }
   }
 
@@ -1865,28 +1875,28 @@ int build_slab(lbm_ctx* c, int s, const ObstacleSource& obst, const float* cells
   // unused halo rows stay finite); lat[] points at owned row 0
   const size_t lat_bytes = (size_t)(sl.rows + 2 * kHaloRows) * c->row_pitch * sizeof(float);
   for (int i = 0; i < 2; i++) {
-    HIP_TRY(LBM_FAILURE, hipMalloc(&sl.lat_alloc[i], lat_bytes));
+    HIP_TRY(LBM_FAILURE, sl.lat_alloc[i].alloc_bytes(lat_bytes));
     HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.lat_alloc[i], 0, lat_bytes, sl.compute));
     sl.lat[i] = sl.lat_alloc[i] + (size_t)kHaloRows * c->row_pitch;
   }
-  HIP_TRY(LBM_FAILURE, hipMalloc(&sl.partials, (size_t)kPartSlots * c->plan.part_stride * sizeof(float)));
+  HIP_TRY(LBM_FAILURE, sl.partials.alloc((size_t)kPartSlots * c->plan.part_stride));
   HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.partials, 0, (size_t)kPartSlots * c->plan.part_stride * sizeof(float), sl.compute));
-  HIP_TRY(LBM_FAILURE, hipMalloc(&sl.tot_u, (size_t)(c->capacity > 0 ? c->capacity : 1) * sizeof(double)));
+  HIP_TRY(LBM_FAILURE, sl.tot_u.alloc((size_t)(c->capacity > 0 ? c->capacity : 1)));
   HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.tot_u, 0, (size_t)(c->capacity > 0 ? c->capacity : 1) * sizeof(double), sl.compute));
-  HIP_TRY(LBM_FAILURE, hipMalloc(&sl.scratch, 2 * kSumBlocks * sizeof(double)));
-  HIP_TRY(LBM_FAILURE, hipMalloc(&sl.flushed_dev, sizeof(int)));
+  HIP_TRY(LBM_FAILURE, sl.scratch.alloc(2 * kSumBlocks));
+  HIP_TRY(LBM_FAILURE, sl.flushed_dev.alloc(1));
   if (c->plan.resident) {
     // granules start at tag 0 = "nothing"; tags are global step indices + 1, so they never need clearing again
     const size_t gran_bytes = resident_gran_bytes(c);
-    HIP_TRY(LBM_FAILURE, hipMalloc(&sl.res_gran, gran_bytes));
+    HIP_TRY(LBM_FAILURE, sl.res_gran.alloc_bytes(gran_bytes));
     HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.res_gran, 0, gran_bytes, sl.compute));
-    HIP_TRY(LBM_FAILURE, hipMalloc(&sl.res_part, (size_t)kResidentChunk * c->plan.resident_bands * sizeof(float)));
-    HIP_TRY(LBM_FAILURE, hipMalloc(&sl.res_status, sizeof(int)));
+    HIP_TRY(LBM_FAILURE, sl.res_part.alloc((size_t)kResidentChunk * c->plan.resident_bands));
+    HIP_TRY(LBM_FAILURE, sl.res_status.alloc(1));
     HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.res_status, 0, sizeof(int), sl.compute));
-    HIP_TRY(LBM_FAILURE, hipHostMalloc(&sl.res_status_host, sizeof(int)));
+    HIP_TRY(LBM_FAILURE, sl.res_status_host.alloc(1));
     *sl.res_status_host = 0;
   }
-  if (c->ranked) HIP_TRY(LBM_FAILURE, hipMalloc(&sl.reduce_buf, (size_t)(c->capacity > 0 ? c->capacity : 1) * sizeof(double)));
+  if (c->ranked) HIP_TRY(LBM_FAILURE, sl.reduce_buf.alloc((size_t)(c->capacity > 0 ? c->capacity : 1)));
 
   // obstacle mask: uint8 (rows + 2*kMaskHalo) x pitch with the (periodic) neighbour rows beyond the slab, which a
   // multi-step pass relaxes redundantly.  Built on the device: from the reference's host type (int, SerialCode/
@@ -1894,16 +1904,15 @@ int build_slab(lbm_ctx* c, int s, const ObstacleSource& obst, const float* cells
   {
     const int mrows = sl.rows + 2 * kMaskHalo;
     const long mask_cells = (long)mrows * c->pitch;
-    HIP_TRY(LBM_FAILURE, hipMalloc(&sl.mask_alloc, (size_t)mask_cells));
+    HIP_TRY(LBM_FAILURE, sl.mask_alloc.alloc((size_t)mask_cells));
     HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.mask_alloc, 0, (size_t)mask_cells, sl.compute));
     sl.mask = sl.mask_alloc + (size_t)kMaskHalo * c->pitch;
     if (obst.kind == OBST_TILE) {
       const size_t tn = (size_t)obst.tile_nx * obst.tile_ny;
       std::vector<unsigned char> t8(tn);
       for (size_t i = 0; i < tn; i++) t8[i] = obst.data[i] ? 1 : 0;
-      DeviceTemp tile_buf;
-      HIP_TRY(LBM_FAILURE, hipMalloc(&tile_buf.p, tn));
-      unsigned char* tile_dev = tile_buf.as<unsigned char>();
+      DeviceBuf<unsigned char> tile_dev;
+      HIP_TRY(LBM_FAILURE, tile_dev.alloc(tn));
       HIP_TRY(LBM_FAILURE, hipMemcpyAsync(tile_dev, t8.data(), tn, hipMemcpyHostToDevice, sl.compute));
       hipLaunchKernelGGL(lbm::mask_from_tile, dim3(ceil_div((long)p.nx * mrows, 256)), dim3(256), 0, sl.compute, tile_dev,
                          obst.tile_nx, obst.tile_ny, sl.mask_alloc, p.nx, c->pitch, sl.row_first - kMaskHalo, mrows, p.ny);
@@ -1912,9 +1921,8 @@ int build_slab(lbm_ctx* c, int s, const ObstacleSource& obst, const float* cells
     } else {
       long chunk_rows = (32L << 20) / ((long)p.nx * sizeof(int));
       if (chunk_rows < 1) chunk_rows = 1;
-      DeviceTemp stage_buf;
-      HIP_TRY(LBM_FAILURE, hipMalloc(&stage_buf.p, (size_t)chunk_rows * p.nx * sizeof(int)));
-      int* stage = stage_buf.as<int>();
+      DeviceBuf<int> stage;
+      HIP_TRY(LBM_FAILURE, stage.alloc((size_t)chunk_rows * p.nx));
       for (int r = 0; r < mrows;) {
         // source row of mask row r, and how many rows from there are contiguous in the source
         long src_row;
@@ -1937,7 +1945,7 @@ int build_slab(lbm_ctx* c, int s, const ObstacleSource& obst, const float* cells
       }
     }
     // fluid cells of the owned rows (the reference counts them while parsing, MPI_Waitall/d2q9-bgk.c:794-804)
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(sl.scratch);
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(sl.scratch.get());
     HIP_TRY(LBM_FAILURE, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), sl.compute));
     hipLaunchKernelGGL(lbm::count_blocked, dim3(ceil_div((long)c->pitch * sl.rows, 256 * 16)), dim3(256), 0, sl.compute,
                        sl.mask, (long)c->pitch * sl.rows, cnt);
@@ -1961,9 +1969,8 @@ int build_slab(lbm_ctx* c, int s, const ObstacleSource& obst, const float* cells
     const int chunk_rows = (int)(((64L << 20) / ((long)p.nx * lbm::kQ * sizeof(float))) > 0
                                      ? ((64L << 20) / ((long)p.nx * lbm::kQ * sizeof(float)))
                                      : 1);
-    DeviceTemp stage_buf;
-    HIP_TRY(LBM_FAILURE, hipMalloc(&stage_buf.p, (size_t)chunk_rows * p.nx * lbm::kQ * sizeof(float)));
-    float* stage = stage_buf.as<float>();
+    DeviceBuf<float> stage;
+    HIP_TRY(LBM_FAILURE, stage.alloc((size_t)chunk_rows * p.nx * lbm::kQ));
     for (int r0 = 0; r0 < sl.rows; r0 += chunk_rows) {
       const int nr = (sl.rows - r0 < chunk_rows) ? sl.rows - r0 : chunk_rows;
       const size_t n = (size_t)nr * p.nx * lbm::kQ;
@@ -2079,9 +2086,9 @@ int build_slabs(lbm_ctx* c, const PlanInput& in, const ObstacleSource& obst, con
 // RCCL communicators
 int connect_ranks(lbm_ctx* c, const void* unique_id) {
   if (c->hosted) {
-    const size_t bytes = (size_t)kHaloRows * c->row_pitch * sizeof(float);
+    const size_t floats = (size_t)kHaloRows * c->row_pitch;
     for (int i = 0; i < 2; i++)
-      if (hipHostMalloc(&c->host_send[i], bytes) != hipSuccess || hipHostMalloc(&c->host_recv[i], bytes) != hipSuccess)
+      if (c->host_send[i].alloc(floats) != hipSuccess || c->host_recv[i].alloc(floats) != hipSuccess)
         LBM_FAIL(LBM_FAILURE, "lbm_create_rank_hosted: cannot allocate the pinned exchange buffers");
   } else if (c->ranked) {
     // one process per GPU: the communicator spans the ranks (also used for the av_vels reduce)
@@ -2119,7 +2126,7 @@ int count_fluid_cells(lbm_ctx* c) {
     fluid = (long long)(v + 0.5);
   } else if (c->ranked && c->world > 1) {
     Slab& sl = c->slab[0];
-    long long* dev = reinterpret_cast<long long*>(sl.scratch);
+    long long* dev = reinterpret_cast<long long*>(sl.scratch.get());
     if (hipSetDevice(sl.device) != hipSuccess ||
         hipMemcpy(dev, &fluid, sizeof(fluid), hipMemcpyHostToDevice) != hipSuccess ||
         !rccl() || g_rccl.AllReduce(dev, dev, 1, ncclInt64, ncclSum, sl.nccl, sl.comm) != ncclSuccess ||
@@ -2177,15 +2184,17 @@ lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, con
 // a batch member's entry of the table the batched launches of one kind read; the table is allocated, all zero, when the
 // first member arms that kind
 template <class Entry>
-int set_batch_entry(lbm_ctx* c, Entry*& table, const Entry& entry) {
+int set_batch_entry(lbm_ctx* c, DeviceBuf<Entry>& table, const Entry& entry) {
   const lbm_batch* bt = c->batch;
   if (!table && entry.every == 0) return LBM_SUCCESS;
   int index = 0;
   while (bt->members[(size_t)index] != c) index++;
   HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
   if (!table) {
-    HIP_TRY(LBM_FAILURE, hipMalloc(&table, bt->members.size() * sizeof(Entry)));
-    HIP_TRY(LBM_FAILURE, hipMemset(table, 0, bt->members.size() * sizeof(Entry)));
+    DeviceBuf<Entry> zeroed;  // moved into place once it is
+    HIP_TRY(LBM_FAILURE, zeroed.alloc(bt->members.size()));
+    HIP_TRY(LBM_FAILURE, hipMemset(zeroed, 0, bt->members.size() * sizeof(Entry)));
+    table = std::move(zeroed);
   }
   HIP_TRY(LBM_FAILURE, hipMemcpy(table + index, &entry, sizeof(entry), hipMemcpyHostToDevice));
   return LBM_SUCCESS;
@@ -2202,14 +2211,10 @@ void release_recorder(lbm_ctx* c) {
   for (int s = 0; s < c->n_slabs; s++) {
     Slab& sl = c->slab[s];
     (void)hipSetDevice(sl.device);
-    if (sl.frames) (void)hipFree(sl.frames);
-    if (sl.probe_ring) (void)hipFree(sl.probe_ring);
-    if (sl.probe_table) (void)hipFree(sl.probe_table);
-    if (sl.mean_sums) (void)hipFree(sl.mean_sums);
-    sl.mean_sums = nullptr;
-    sl.frames = nullptr;
-    sl.probe_ring = nullptr;
-    sl.probe_table = nullptr;
+    sl.frames.reset();
+    sl.probe_ring.reset();
+    sl.probe_table.reset();
+    sl.mean_sums.reset();
     sl.probe_count = 0;
   }
   c->probe_cells.clear();
@@ -2490,15 +2495,7 @@ void lbm_destroy(lbm_ctx* c) {
       for (hipStream_t g : c->slab[s].group_extra) if (g) (void)hipStreamSynchronize(g);
     }
   }
-  for (int s = 0; s < c->n_slabs; s++) free_slab(c->slab[s]);
-  for (int i = 0; i < 2; i++) {
-    if (c->host_send[i]) (void)hipHostFree(c->host_send[i]);
-    if (c->host_recv[i]) (void)hipHostFree(c->host_recv[i]);
-    if (c->ev_steady[i]) (void)hipEventDestroy(c->ev_steady[i]);
-  }
-  if (c->steady_state) (void)hipFree(c->steady_state);
-  if (c->steady_stop_host) (void)hipHostFree(c->steady_stop_host);
-  delete c;
+  delete c;  // what the context and its slabs own goes with them (~Slab)
 }
 
 int lbm_get_info(const lbm_ctx* c, lbm_info* out) {
@@ -2554,7 +2551,7 @@ int lbm_set_frames(lbm_ctx* c, int every, int capacity) {
       Slab& sl = c->slab[s];
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
       const size_t bytes = (size_t)capacity * (size_t)sl.rows * (size_t)c->p.nx * sizeof(float);
-      if (hipMalloc(&sl.frames, bytes) != hipSuccess)
+      if (sl.frames.alloc_bytes(bytes) != hipSuccess)
         LBM_FAIL(LBM_FAILURE, "lbm_set_frames: cannot allocate %d frame slots (%.1f MiB per slab); frames stay off", capacity,
                  (double)bytes / 1048576.0);
     }
@@ -2626,8 +2623,8 @@ int lbm_set_probes(lbm_ctx* c, int n_probes, const lbm_probe* cells, int every, 
       }
       static_assert(sizeof(lbm::ProbeEntry) == 2 * sizeof(unsigned), "a table entry is two words");
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      if (hipMalloc(&sl.probe_ring, ring_bytes) != hipSuccess ||
-          hipMalloc(&sl.probe_table, (words.size() + 2) * sizeof(unsigned)) != hipSuccess ||
+      if (sl.probe_ring.alloc_bytes(ring_bytes) != hipSuccess ||
+          sl.probe_table.alloc_bytes((words.size() + 2) * sizeof(unsigned)) != hipSuccess ||
           hipMemset(sl.probe_ring, 0, ring_bytes) != hipSuccess ||
           (!words.empty() && hipMemcpy(sl.probe_table, words.data(), words.size() * sizeof(unsigned), hipMemcpyHostToDevice) != hipSuccess))
         LBM_FAIL(LBM_FAILURE, "lbm_set_probes: cannot allocate %d rows of %d samples (%.1f MiB per slab); probes stay off", capacity,
@@ -2686,7 +2683,7 @@ static int set_mean_order(lbm_ctx* c, int every, int order, const char* who) {
       Slab& sl = c->slab[s];
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
       const size_t bytes = (size_t)planes * sizeof(double) * (size_t)sl.rows * (size_t)c->p.nx;
-      if (hipMalloc(&sl.mean_sums, bytes) != hipSuccess || hipMemsetAsync(sl.mean_sums, 0, bytes, sl.compute) != hipSuccess)
+      if (sl.mean_sums.alloc_bytes(bytes) != hipSuccess || hipMemsetAsync(sl.mean_sums, 0, bytes, sl.compute) != hipSuccess)
         LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the %s planes of sums (%d bytes per cell, %.1f MiB per slab); the mean fields stay off",
                  who, planes == 4 ? "four" : "eight", planes * 8, (double)bytes / 1048576.0);
     }
@@ -2833,9 +2830,8 @@ int lbm_read_cells(lbm_ctx* c, float* cells_aos) {
   for (int s = 0; s < c->n_slabs; s++) {
     Slab& sl = c->slab[s];
     HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-    DeviceTemp stage_buf;
-    HIP_TRY(LBM_FAILURE, hipMalloc(&stage_buf.p, (size_t)chunk_rows * nx * lbm::kQ * sizeof(float)));
-    float* stage = stage_buf.as<float>();
+    DeviceBuf<float> stage;
+    HIP_TRY(LBM_FAILURE, stage.alloc((size_t)chunk_rows * nx * lbm::kQ));
     for (int r0 = 0; r0 < sl.rows; r0 += (int)chunk_rows) {
       const int nr = (sl.rows - r0 < chunk_rows) ? sl.rows - r0 : (int)chunk_rows;
       const size_t n = (size_t)nr * nx * lbm::kQ;
@@ -2860,10 +2856,9 @@ int lbm_read_final_state(lbm_ctx* c, float* u_x, float* u_y, float* u_mag, float
   for (int s = 0; s < c->n_slabs; s++) {
     Slab& sl = c->slab[s];
     HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-    DeviceTemp stage_buf;
+    DeviceBuf<float> stage;
     const size_t chunk_cells = (size_t)chunk_rows * nx;
-    HIP_TRY(LBM_FAILURE, hipMalloc(&stage_buf.p, 4 * chunk_cells * sizeof(float)));
-    float* stage = stage_buf.as<float>();
+    HIP_TRY(LBM_FAILURE, stage.alloc(4 * chunk_cells));
     for (int r0 = 0; r0 < sl.rows; r0 += (int)chunk_rows) {
       const int nr = (sl.rows - r0 < chunk_rows) ? sl.rows - r0 : (int)chunk_rows;
       const size_t n = (size_t)nr * nx;
@@ -2946,25 +2941,13 @@ void lbm_destroy_batch(lbm_batch* bt) {
     (void)hipSetDevice(bt->members[0]->slab[0].device);
     (void)hipStreamSynchronize(bt->stream);
   }
-  // members 1.. borrow member 0's compute stream: they go first and leave it to member 0
+  // members 1.. borrow member 0's compute stream, which member 0 owns: they go first
   for (size_t i = bt->members.size(); i-- > 0;) {
     lbm_ctx* c = bt->members[i];
-    if (i > 0 && c->slab[0].compute == bt->stream) c->slab[0].compute = nullptr;
     c->batch = nullptr;
     lbm_destroy(c);
   }
-  if (bt->table) (void)hipFree(bt->table);
-  if (bt->frame_table) (void)hipFree(bt->frame_table);
-  if (bt->probe_table) (void)hipFree(bt->probe_table);
-  if (bt->mean_table) (void)hipFree(bt->mean_table);
-  if (bt->status) (void)hipFree(bt->status);
-  if (bt->status_host) (void)hipHostFree(bt->status_host);
-  if (bt->steady_state) (void)hipFree(bt->steady_state);
-  if (bt->steady_members) (void)hipFree(bt->steady_members);
-  if (bt->steady_batch) (void)hipFree(bt->steady_batch);
-  if (bt->steady_stop_host) (void)hipHostFree(bt->steady_stop_host);
-  if (bt->ev_steady) (void)hipEventDestroy(bt->ev_steady);
-  delete bt;
+  delete bt;  // the batch's own tables go with it
 }
 
 lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* obstacles, const float* cells_aos,
@@ -3014,7 +2997,7 @@ lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* 
   bt->stream = sl0.compute;
   for (int i = 1; i < n_members; i++) {
     Slab& sl = bt->members[i]->slab[0];
-    (void)hipStreamDestroy(sl.compute);
+    sl.compute_own.reset();
     sl.compute = bt->stream;
   }
   bt->members_per_launch = 1;
@@ -3052,10 +3035,10 @@ lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* 
         m.omega = c->p.omega;
         set_accel_weights(m, c->p);  // as run_steps / run_resident
       }
-    if (hipMalloc(&bt->table, h.size() * sizeof(h[0])) != hipSuccess ||
+    if (bt->table.alloc(h.size()) != hipSuccess ||
         hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(&bt->status, sizeof(int)) != hipSuccess || hipMemset(bt->status, 0, sizeof(int)) != hipSuccess ||
-        hipHostMalloc(&bt->status_host, sizeof(int)) != hipSuccess) {
+        bt->status.alloc(1) != hipSuccess || hipMemset(bt->status, 0, sizeof(int)) != hipSuccess ||
+        bt->status_host.alloc(1) != hipSuccess) {
       lbm_destroy_batch(bt);
       LBM_FAIL(nullptr, "lbm_create_batch: cannot allocate the member table");
     }
@@ -3167,7 +3150,7 @@ static int steady_segment_resident(lbm_ctx* c, int n, int slot, double tol, int 
                      (float)c->fluid_cells, tol, patience, steps_after, c->steady_state);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
   c->steps_done += n;
-  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(c->steady_stop_host + slot, &c->steady_state->stop, sizeof(int), hipMemcpyDeviceToHost, sl.compute));
+  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(c->steady_stop_host + slot, &c->steady_state.get()->stop, sizeof(int), hipMemcpyDeviceToHost, sl.compute));
   HIP_TRY(LBM_FAILURE, hipEventRecord(c->ev_steady[slot], sl.compute));
   return LBM_SUCCESS;
 }
@@ -3190,10 +3173,10 @@ int lbm_run_until(lbm_ctx* c, int max_steps, int check_every, double tol, int pa
 
   Slab& sl = c->slab[0];
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-  if (!c->steady_state) {
-    HIP_TRY(LBM_FAILURE, hipMalloc(&c->steady_state, sizeof(lbm::SteadyState)));
-    HIP_TRY(LBM_FAILURE, hipHostMalloc(&c->steady_stop_host, 2 * sizeof(int)));
-    for (int i = 0; i < 2; i++) HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&c->ev_steady[i], hipEventDisableTiming));
+  if (!c->ev_steady[1]) {  // created last: the set is whole (an attempt that failed half-way starts again)
+    HIP_TRY(LBM_FAILURE, c->steady_state.alloc(1));
+    HIP_TRY(LBM_FAILURE, c->steady_stop_host.alloc(2));
+    for (int i = 0; i < 2; i++) HIP_TRY(LBM_FAILURE, c->ev_steady[i].create(hipEventDisableTiming));
   }
   hipLaunchKernelGGL(lbm::steady_reset, dim3(1), dim3(64), 0, sl.compute, c->steady_state, 1, (lbm::SteadyBatch*)nullptr);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
@@ -3218,7 +3201,7 @@ int lbm_run_until(lbm_ctx* c, int max_steps, int check_every, double tol, int pa
         hipLaunchKernelGGL(lbm::steady_check, dim3(1), dim3(64), 0, sl.compute, (const double*)sl.tot_u, first, E,
                            (float)c->fluid_cells, tol, patience, after, c->steady_state);
         HIP_TRY(LBM_FAILURE, hipGetLastError());
-        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(c->steady_stop_host + (issued & 1), &c->steady_state->stop, sizeof(int),
+        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(c->steady_stop_host + (issued & 1), &c->steady_state.get()->stop, sizeof(int),
                                             hipMemcpyDeviceToHost, sl.compute));
         HIP_TRY(LBM_FAILURE, hipEventRecord(c->ev_steady[issued & 1], sl.compute));
       }
@@ -3264,15 +3247,15 @@ int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double to
   }
 
   HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
-  if (!bt->steady_state) {
+  if (!bt->steady_state) {  // allocated last: the set is whole (an attempt that failed half-way starts again)
     std::vector<lbm::SteadyMember> h((size_t)n_members);
     for (int i = 0; i < n_members; i++) h[(size_t)i] = {bt->members[(size_t)i]->slab[0].tot_u, (float)bt->members[(size_t)i]->fluid_cells};
-    HIP_TRY(LBM_FAILURE, hipMalloc(&bt->steady_members, h.size() * sizeof(h[0])));
+    HIP_TRY(LBM_FAILURE, bt->steady_members.alloc(h.size()));
     HIP_TRY(LBM_FAILURE, hipMemcpy(bt->steady_members, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice));
-    HIP_TRY(LBM_FAILURE, hipMalloc(&bt->steady_batch, sizeof(lbm::SteadyBatch)));
-    HIP_TRY(LBM_FAILURE, hipHostMalloc(&bt->steady_stop_host, sizeof(int)));
-    HIP_TRY(LBM_FAILURE, hipEventCreateWithFlags(&bt->ev_steady, hipEventDisableTiming));
-    HIP_TRY(LBM_FAILURE, hipMalloc(&bt->steady_state, (size_t)n_members * sizeof(lbm::SteadyState)));
+    HIP_TRY(LBM_FAILURE, bt->steady_batch.alloc(1));
+    HIP_TRY(LBM_FAILURE, bt->steady_stop_host.alloc(1));
+    HIP_TRY(LBM_FAILURE, bt->ev_steady.create(hipEventDisableTiming));
+    HIP_TRY(LBM_FAILURE, bt->steady_state.alloc((size_t)n_members));
   }
   hipLaunchKernelGGL(lbm::steady_reset, dim3(ceil_div(n_members, 64)), dim3(64), 0, bt->stream, bt->steady_state, n_members,
                      bt->steady_batch);
@@ -3290,7 +3273,7 @@ int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double to
                        (const lbm::SteadyMember*)bt->steady_members, n_members, first, E, tol, patience, (j + 1) * E,
                        bt->steady_state, bt->steady_batch);
     HIP_TRY(LBM_FAILURE, hipGetLastError());
-    HIP_TRY(LBM_FAILURE, hipMemcpyAsync(bt->steady_stop_host, &bt->steady_batch->all_steady, sizeof(int), hipMemcpyDeviceToHost, bt->stream));
+    HIP_TRY(LBM_FAILURE, hipMemcpyAsync(bt->steady_stop_host, &bt->steady_batch.get()->all_steady, sizeof(int), hipMemcpyDeviceToHost, bt->stream));
     HIP_TRY(LBM_FAILURE, hipEventRecord(bt->ev_steady, bt->stream));
     HIP_TRY(LBM_FAILURE, hipEventSynchronize(bt->ev_steady));
     steady = *bt->steady_stop_host != 0;

@@ -193,6 +193,49 @@ def test_capacity_overflow_fails_before_any_work(lbm):
         assert eng.frames()[0].size == 0
 
 
+def refuse_frames(lbm, eng):
+    """One hipMalloc of about 128 TiB (2^31 - 1 slots of 128 x 128 floats): the runtime refuses it at once with an
+    out-of-memory return code, and nothing faults."""
+    with pytest.raises(lbm.LbmError, match="frames stay off"):
+        eng.set_frames(1, 2**31 - 1)
+
+
+def test_failed_allocation_leaves_the_engine_whole(lbm, oracle, datasets):
+    """lbm_set_frames whose buffer cannot be allocated returns an error and leaves nothing behind: the same engine runs
+    on, bit-identical to the oracle, and arms again.  Arming right after the refusal records the frames of steps 0, 10,
+    20 and 30 of a 40-step run; arming after 40 steps those of the next 40."""
+    p, ob = datasets("128x128")
+    cells = oracle.init_cells(p)
+    ref, want = oracle_frames(oracle, p, ob, cells, 0, 40, 10)
+    ref_av = oracle.run(p, cells.copy(), ob, 40)
+    ref80, want80 = oracle_frames(oracle, p, ob, ref, 40, 80, 10)
+    with lbm.Engine(p, ob, cells) as plain:
+        plain.run(40)
+        plain_av = plain.av_vels(40)
+    with lbm.Engine(p, ob, cells) as eng:
+        refuse_frames(lbm, eng)
+        eng.run(40)
+        assert np.array_equal(eng.cells().view(np.uint32), ref.view(np.uint32))
+        assert np.array_equal(eng.av_vels(40).view(np.uint32), plain_av.view(np.uint32)), "the refusal changed av_vels"
+        np.testing.assert_allclose(eng.av_vels(40), ref_av, rtol=2e-4, atol=0)    # test_gpu_parity.AV_RTOL
+        assert eng.frames()[0].size == 0
+        eng.set_frames(10, 4)
+        eng.run(40)
+        steps, frames = eng.frames()
+        assert steps.tolist() == [40, 50, 60, 70]
+        assert_frames(steps, frames, want80)
+        assert np.array_equal(eng.cells().view(np.uint32), ref80.view(np.uint32))
+    with lbm.Engine(p, ob, cells) as eng:
+        refuse_frames(lbm, eng)
+        eng.set_frames(10, 4)
+        eng.run(40)
+        steps, frames = eng.frames()
+        assert steps.tolist() == [0, 10, 20, 30]
+        assert_frames(steps, frames, want)
+        assert np.array_equal(eng.cells().view(np.uint32), ref.view(np.uint32))
+        assert np.array_equal(eng.av_vels(40).view(np.uint32), plain_av.view(np.uint32))
+
+
 def test_refused_in_stale_and_freshest_halo_modes(lbm, monkeypatch):
     monkeypatch.setenv("LBM_HALO", "memcpy")
     p, ob, cells = random_case(lbm, 128, 64, 4, walls=False)
