@@ -505,6 +505,52 @@ int        lbm_batch_sync(lbm_batch* batch);
 int        lbm_batch_get_info(const lbm_batch* batch, lbm_batch_info* out);
 void       lbm_destroy_batch(lbm_batch* batch);
 
+/* ---- double precision -----------------------------------------------------------------------
+ * The reference's programs are `float`, but its published golden results (the .dat files of check/) are its algorithm evaluated in
+ * IEEE double.  A double context computes exactly that: the driver loop of SerialCode/d2q9-bgk.c:166-170 with every
+ * `float` read as `double`, `sqrtf` as `sqrt` and every `1.f`-style literal as a double literal.  Each expression tree of
+ * :207-458 is kept, with IEEE / and sqrt and no contraction:
+ *   accelerate_flow adds a1 = density*accel/9.0 and a2 = density*accel/36.0 (:219-220);
+ *   the constant divides (u / c_sq, (u*u) / (2 c_sq c_sq), u_sq / (2 c_sq)) are divides -- the exhaustive check that let
+ *     the fp32 kernels multiply instead cannot be made over doubles;
+ *   tot_u[t] is the double sum of |u| over the fluid cells after step t+1 in the kernels' fixed order (the same bits
+ *     from run to run), and av_vels[t] = tot_u[t] / (double)fluid_cells (:457);
+ *   final_state's blocked cells give 0, 0, 0, density * c_sq.
+ * The run constants are doubles: 1.85 is the double 1.85, not (double)1.85f.  Layouts are the fp32 entry points' with
+ * double elements: cells_aos double[ny*nx*9], obstacles int[ny*nx], fields double[ny*nx] row-major.
+ * lbm_double_ctx is NOT an lbm_ctx: no fp32 entry point takes one.  One periodic slab on device 0, one timestep per
+ * launch (two cells per lane where nx is even, else one: lbm_double_info.lane_cells), every launch on one stream.
+ * Not offered in double: several slabs and rank contexts; recorders (frames, probes, mean fields); batches;
+ * lbm_run_until; the resident kernel and the multi-step kernels; hipGraph replay.
+ * Errors, lbm_last_error and the die() message are those of the fp32 entry points; lbm_double_run fails before any
+ * work when steps_done + n_steps exceeds max_iters.  The functions mirror their fp32 namesakes (lbm_create, lbm_run,
+ * lbm_run_timed, lbm_sync, lbm_read_av_vels, lbm_read_cells, lbm_read_final_state, lbm_av_velocity, lbm_total_density,
+ * lbm_calc_reynolds, lbm_get_info).
+ */
+typedef struct {
+  int    nx, ny, max_iters, reynolds_dim; /* as lbm_params */
+  double density, accel, omega;
+} lbm_params_double;
+typedef struct lbm_double_ctx lbm_double_ctx; /* opaque; not an lbm_ctx */
+typedef struct {
+  int fluid_cells; /* non-blocked cells (av_velocity's divisor) */
+  int steps_done;
+  int lane_cells;  /* 2: step_double (even nx), 1: step_double_scalar */
+  int nontemporal; /* 1: step_double stores with the nontemporal hint (lattice pair beyond 512 MiB) */
+} lbm_double_info;
+lbm_double_ctx* lbm_double_create(const lbm_params_double* params, const int* obstacles, const double* cells_aos /* or NULL */);
+void  lbm_double_destroy(lbm_double_ctx* ctx);
+int   lbm_double_get_info(const lbm_double_ctx* ctx, lbm_double_info* out);
+int   lbm_double_run(lbm_double_ctx* ctx, int n_steps);
+int   lbm_double_run_timed(lbm_double_ctx* ctx, int n_steps, float* kernel_ms_per_step);
+int   lbm_double_sync(lbm_double_ctx* ctx);
+int   lbm_double_read_av_vels(lbm_double_ctx* ctx, double* out, int n);
+int   lbm_double_read_cells(lbm_double_ctx* ctx, double* cells_aos);
+int   lbm_double_read_final_state(lbm_double_ctx* ctx, double* u_x, double* u_y, double* u_mag, double* pressure);
+int   lbm_double_av_velocity(lbm_double_ctx* ctx, double* out);
+int   lbm_double_total_density(lbm_double_ctx* ctx, double* out);
+int   lbm_double_calc_reynolds(lbm_double_ctx* ctx, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,9 @@ ABI_SYMBOLS = (
     "lbm_read_final_state", "lbm_av_velocity", "lbm_total_density", "lbm_calc_reynolds",
     "lbm_set_frames", "lbm_read_frames", "lbm_set_probes", "lbm_read_probes", "lbm_set_mean", "lbm_read_mean", "lbm_set_mean_order", "lbm_run_until", "lbm_batch_run_until",
     "lbm_create_batch", "lbm_batch_member", "lbm_batch_run", "lbm_batch_sync", "lbm_batch_get_info", "lbm_destroy_batch",
+    "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
+    "lbm_double_sync", "lbm_double_read_av_vels", "lbm_double_read_cells", "lbm_double_read_final_state",
+    "lbm_double_av_velocity", "lbm_double_total_density", "lbm_double_calc_reynolds",
 )
 # declared and exported too, kept apart: ABI_SYMBOLS is compared with a scan of the header for names of letters and
 # underscores (tests/test_abi.py), which a name that ends in a digit is not
@@ -64,6 +67,17 @@ class _CParams(ctypes.Structure):
     _fields_ = [("nx", ctypes.c_int), ("ny", ctypes.c_int), ("max_iters", ctypes.c_int),
                 ("reynolds_dim", ctypes.c_int), ("density", ctypes.c_float),
                 ("accel", ctypes.c_float), ("omega", ctypes.c_float)]
+
+
+class _CParamsDouble(ctypes.Structure):
+    _fields_ = [("nx", ctypes.c_int), ("ny", ctypes.c_int), ("max_iters", ctypes.c_int),
+                ("reynolds_dim", ctypes.c_int), ("density", ctypes.c_double),
+                ("accel", ctypes.c_double), ("omega", ctypes.c_double)]
+
+
+class _CDoubleInfo(ctypes.Structure):
+    _fields_ = [("fluid_cells", ctypes.c_int), ("steps_done", ctypes.c_int), ("lane_cells", ctypes.c_int),
+                ("nontemporal", ctypes.c_int)]
 
 
 class _CInfo(ctypes.Structure):
@@ -125,6 +139,22 @@ class Params:
     def _c(self) -> _CParams:
         return _CParams(self.nx, self.ny, self.max_iters, self.reynolds_dim,
                         self.density, self.accel, self.omega)
+
+
+@dataclass
+class ParamsDouble:
+    """The reference's t_param with its three floats read as doubles (lbm_params_double): Python floats, unrounded."""
+    nx: int
+    ny: int
+    max_iters: int
+    reynolds_dim: int
+    density: float
+    accel: float
+    omega: float
+
+    def _c(self) -> _CParamsDouble:
+        return _CParamsDouble(self.nx, self.ny, self.max_iters, self.reynolds_dim,
+                              self.density, self.accel, self.omega)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -206,6 +236,19 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_batch_sync.argtypes = [P]; lib.lbm_batch_sync.restype = I
     lib.lbm_batch_get_info.argtypes = [P, ctypes.POINTER(_CBatchInfo)]; lib.lbm_batch_get_info.restype = I
     lib.lbm_destroy_batch.argtypes = [P]; lib.lbm_destroy_batch.restype = None
+    PD = ctypes.POINTER(ctypes.c_double)
+    lib.lbm_double_create.argtypes = [ctypes.POINTER(_CParamsDouble), P, P]; lib.lbm_double_create.restype = P
+    lib.lbm_double_destroy.argtypes = [P]; lib.lbm_double_destroy.restype = None
+    lib.lbm_double_get_info.argtypes = [P, ctypes.POINTER(_CDoubleInfo)]; lib.lbm_double_get_info.restype = I
+    lib.lbm_double_run.argtypes = [P, I]; lib.lbm_double_run.restype = I
+    lib.lbm_double_run_timed.argtypes = [P, I, PF]; lib.lbm_double_run_timed.restype = I
+    lib.lbm_double_sync.argtypes = [P]; lib.lbm_double_sync.restype = I
+    lib.lbm_double_read_av_vels.argtypes = [P, P, I]; lib.lbm_double_read_av_vels.restype = I
+    lib.lbm_double_read_cells.argtypes = [P, P]; lib.lbm_double_read_cells.restype = I
+    lib.lbm_double_read_final_state.argtypes = [P, P, P, P, P]; lib.lbm_double_read_final_state.restype = I
+    lib.lbm_double_av_velocity.argtypes = [P, PD]; lib.lbm_double_av_velocity.restype = I
+    lib.lbm_double_total_density.argtypes = [P, PD]; lib.lbm_double_total_density.restype = I
+    lib.lbm_double_calc_reynolds.argtypes = [P, PD]; lib.lbm_double_calc_reynolds.restype = I
     # a Python host wants exceptions, not exit(): switch from the reference's die() behaviour
     lib.lbm_set_error_mode(1)
     _lib = lib
@@ -583,6 +626,102 @@ class Engine:
 
 
 # ------------------------------------------------------------------------------------------------
+# double precision: the reference's algorithm in IEEE double, what its golden results were computed in
+# ------------------------------------------------------------------------------------------------
+class DoubleEngine:
+    """One lattice advanced in double precision (lbm_double_*): the reference's loop with every float read as double,
+    bit for bit.  One periodic slab on one device, one timestep per launch; no slabs, ranks, recorders, batches or
+    run_until.  `cells`: (ny, nx, 9) float64 or None (uniform equilibrium)."""
+
+    def __init__(self, params: ParamsDouble, obstacles: np.ndarray, cells: np.ndarray | None = None):
+        self.lib = load_library()
+        self.params = params
+        self.handle = None
+        obstacles = np.asarray(obstacles)
+        if obstacles.size != params.nx * params.ny:
+            raise LbmError(f"obstacles has {obstacles.size} cells, the grid {params.nx * params.ny}")
+        ob = np.ascontiguousarray(obstacles, dtype=np.int32)
+        cp = None
+        if cells is not None:
+            cells = np.ascontiguousarray(cells, dtype=np.float64)
+            if cells.size != params.nx * params.ny * 9:
+                raise LbmError(f"cells has {cells.size} values, the grid {params.nx * params.ny * 9}")
+            cp = cells.ctypes.data
+        cpar = params._c()
+        self.handle = self.lib.lbm_double_create(ctypes.byref(cpar), ob.ctypes.data, cp)
+        if not self.handle:
+            raise LbmError(self.lib.lbm_last_error().decode())
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self.lib.lbm_double_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        ci = _CDoubleInfo()
+        _check(self.lib, self.lib.lbm_double_get_info(self.handle, ctypes.byref(ci)))
+        return {name: getattr(ci, name) for name, _ in _CDoubleInfo._fields_}
+
+    def run(self, n_steps: int) -> None:
+        _check(self.lib, self.lib.lbm_double_run(self.handle, int(n_steps)))
+
+    def run_timed(self, n_steps: int) -> float:
+        """Advance n_steps; returns the average device milliseconds per step (HIP events on the stream)."""
+        ms = ctypes.c_float()
+        _check(self.lib, self.lib.lbm_double_run_timed(self.handle, int(n_steps), ctypes.byref(ms)))
+        return float(ms.value)
+
+    def sync(self) -> None:
+        _check(self.lib, self.lib.lbm_double_sync(self.handle))
+
+    def av_vels(self, n: int | None = None) -> np.ndarray:
+        n = self.info()["steps_done"] if n is None else n
+        out = np.empty(n, dtype=np.float64)
+        _check(self.lib, self.lib.lbm_double_read_av_vels(self.handle, out.ctypes.data, n))
+        return out
+
+    def cells(self) -> np.ndarray:
+        """The lattice in the reference's AoS layout: (ny, nx, 9) float64."""
+        out = np.empty((self.params.ny, self.params.nx, 9), dtype=np.float64)
+        _check(self.lib, self.lib.lbm_double_read_cells(self.handle, out.ctypes.data))
+        return out
+
+    def final_state(self) -> dict:
+        shape = (self.params.ny, self.params.nx)
+        f = {k: np.empty(shape, dtype=np.float64) for k in ("u_x", "u_y", "u", "pressure")}
+        _check(self.lib, self.lib.lbm_double_read_final_state(
+            self.handle, f["u_x"].ctypes.data, f["u_y"].ctypes.data, f["u"].ctypes.data,
+            f["pressure"].ctypes.data))
+        return f
+
+    def _scalar(self, fn) -> float:
+        v = ctypes.c_double()
+        _check(self.lib, fn(self.handle, ctypes.byref(v)))
+        return float(v.value)
+
+    def av_velocity(self) -> float:
+        return self._scalar(self.lib.lbm_double_av_velocity)
+
+    def total_density(self) -> float:
+        return self._scalar(self.lib.lbm_double_total_density)
+
+    def reynolds(self) -> float:
+        return self._scalar(self.lib.lbm_double_calc_reynolds)
+
+
+# ------------------------------------------------------------------------------------------------
 # batches: many small lattices advanced together
 # ------------------------------------------------------------------------------------------------
 class Batch:
@@ -729,6 +868,12 @@ def read_params(path: str) -> Params:
         raise LbmError(f"could not read param file: {exc}") from None
 
 
+def read_params_double(path: str) -> ParamsDouble:
+    """The same file with density, accel and omega kept as doubles: 1.85 is 1.85, not float32(1.85)."""
+    p = read_params(path)
+    return ParamsDouble(p.nx, p.ny, p.max_iters, p.reynolds_dim, p.density, p.accel, p.omega)
+
+
 def read_obstacles(path: str, nx: int, ny: int) -> np.ndarray:
     """'x y 1' lines -> int32 (ny, nx) map; the reference's range checks (:590-597)."""
     grid = np.zeros((ny, nx), dtype=np.int32)
@@ -759,9 +904,12 @@ def tile_obstacles(tile: np.ndarray, nx: int, ny: int) -> np.ndarray:
 
 
 def write_av_vels(path: str, av_vels: np.ndarray) -> None:
-    """'%d:\\t%.12E\\n' (SerialCode/d2q9-bgk.c:735-738)."""
+    """'%d:\\t%.12E\\n' (SerialCode/d2q9-bgk.c:735-738).  A float64 series (DoubleEngine.av_vels) is written as it is."""
+    av_vels = np.asarray(av_vels)
+    if av_vels.dtype != np.float64:
+        av_vels = av_vels.astype(np.float32)
     with open(path, "w") as fh:
-        for i, v in enumerate(np.asarray(av_vels, dtype=np.float32)):
+        for i, v in enumerate(av_vels):
             fh.write("%d:\t%.12E\n" % (i, float(v)))
 
 

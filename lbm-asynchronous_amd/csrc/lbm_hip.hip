@@ -3288,3 +3288,6 @@ int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double to
 }
 
 }  // extern "C"
+
+// the double-precision engine (lbm_double_*): a handle type, entry points and kernels of its own
+#include "lbm_double.hip.h"

@@ -37,6 +37,11 @@
  *                         rms_state.dat, final_state.dat's format with the columns rms u_x, rms u_y, the Reynolds shear
  *                         stress <u'v'> and rms pressure over the same samples (var = max(<x x> - <x>^2, 0) in double,
  *                         rounded to float).  The other files are unchanged.  Dies when set without LBM_MEAN.
+ *   LBM_PRECISION=double  run the double-precision engine (lbm_double_*): the parameter file's density, accel and omega are
+ *                         read as doubles, and final_state.dat / av_vels.dat hold the double results in the same formats
+ *                         -- what the reference's golden files were computed in.  One GPU, plain runs only: dies together
+ *                         with LBM_GPUS > 1, LBM_MATH=fast, LBM_TILE, LBM_ANIMATION, LBM_STEADY, LBM_PROBES, LBM_MEAN or
+ *                         LBM_PRESSURE_BIN.  Unset or "single": everything above, unchanged.
  */
 #include <math.h>
 #include <stdio.h>
@@ -132,6 +137,73 @@ static void parse_mean(const char* text, int* every, int* from)
   *from = (int)v[1];
 }
 
+/* LBM_PRECISION=double: the same program on the double engine (main() :132-205 with every float read as double) */
+static int main_double(const char* paramfile, const char* obstaclefile)
+{
+  static const char* const not_offered[] = {"LBM_TILE", "LBM_ANIMATION", "LBM_STEADY", "LBM_PROBES", "LBM_MEAN",
+                                            "LBM_MEAN_ORDER", "LBM_PRESSURE_BIN"};
+  const char* env;
+  char message[256];
+  for (size_t i = 0; i < sizeof(not_offered) / sizeof(not_offered[0]); i++)
+    if ((env = getenv(not_offered[i])) && *env) {
+      snprintf(message, sizeof(message), "%s is not offered with LBM_PRECISION=double", not_offered[i]);
+      lbm_die(message, __LINE__, __FILE__);
+    }
+  if ((env = getenv("LBM_GPUS")) && *env && atoi(env) != 1) lbm_die("LBM_GPUS is not offered with LBM_PRECISION=double", __LINE__, __FILE__);
+  if ((env = getenv("LBM_MATH")) && !strcmp(env, "fast")) lbm_die("LBM_MATH=fast is not offered with LBM_PRECISION=double", __LINE__, __FILE__);
+  int write_text = 1;
+  if ((env = getenv("LBM_OUTPUT")) && !strcmp(env, "none")) write_text = 0;
+
+  const double tot_tic = wall_seconds();
+  lbm_params_double params;
+  lbm_read_params_double(paramfile, &params);
+  const lbm_params shape = {params.nx, params.ny, params.max_iters, params.reynolds_dim, 0.f, 0.f, 0.f};
+  int* obstacles = lbm_read_obstacles(obstaclefile, &shape);
+  lbm_double_ctx* ctx = lbm_double_create(&params, obstacles, NULL);
+  lbm_double_sync(ctx);
+  const double init_toc = wall_seconds();
+
+  lbm_double_run(ctx, params.max_iters);
+  lbm_double_sync(ctx);
+  const double comp_toc = wall_seconds();
+
+  const size_t n_cells = (size_t)params.nx * (size_t)params.ny;
+  double* av_vels = (double*)malloc(sizeof(double) * (size_t)(params.max_iters > 0 ? params.max_iters : 1));
+  if (av_vels == NULL) lbm_die("cannot allocate memory for av_vels", __LINE__, __FILE__);
+  lbm_double_read_av_vels(ctx, av_vels, params.max_iters);
+  double reynolds = 0.0;
+  lbm_double_calc_reynolds(ctx, &reynolds);
+  double* fields = NULL;
+  if (write_text) {
+    fields = (double*)malloc(sizeof(double) * 4 * n_cells);
+    if (fields == NULL) lbm_die("cannot allocate memory for cells", __LINE__, __FILE__);
+    lbm_double_read_final_state(ctx, fields, fields + n_cells, fields + 2 * n_cells, fields + 3 * n_cells);
+  }
+  const double col_toc = wall_seconds();
+
+  printf("==done==\n");
+  printf("Reynolds number:\t\t%.12E\n", reynolds);
+  printf("Elapsed Init time:\t\t\t%.6lf (s)\n", init_toc - tot_tic);
+  printf("Elapsed Compute time:\t\t\t%.6lf (s)\n", comp_toc - init_toc);
+  printf("Elapsed Collate time:\t\t\t%.6lf (s)\n", col_toc - comp_toc);
+  printf("Elapsed Total time:\t\t\t%.6lf (s)\n", col_toc - tot_tic);
+
+  if (write_text) {
+    FILE* fp = fopen(LBM_FINALSTATEFILE, "w");
+    if (fp == NULL) lbm_die("could not open file output file", __LINE__, __FILE__);
+    lbm_write_final_state_rows_double(fp, &params, 0, params.ny, fields, fields + n_cells, fields + 2 * n_cells,
+                                      fields + 3 * n_cells, obstacles);
+    fclose(fp);
+  }
+  lbm_write_av_vels_double(LBM_AVVELSFILE, av_vels, params.max_iters);
+
+  lbm_double_destroy(ctx);
+  free(fields);
+  free(av_vels);
+  free(obstacles);
+  return EXIT_SUCCESS;
+}
+
 int main(int argc, char* argv[])
 {
   if (argc != 3) lbm_usage(argv[0]);
@@ -139,6 +211,10 @@ int main(int argc, char* argv[])
   const char* obstaclefile = argv[2];
 
   const char* env;
+  if ((env = getenv("LBM_PRECISION")) && *env) {
+    if (!strcmp(env, "double")) return main_double(paramfile, obstaclefile);
+    if (strcmp(env, "single")) lbm_die("could not read LBM_PRECISION: expected single or double", __LINE__, __FILE__);
+  }
   int n_gpus = 1;
   if ((env = getenv("LBM_GPUS")) && *env) n_gpus = atoi(env);
   int math_mode = LBM_MATH_EXACT;

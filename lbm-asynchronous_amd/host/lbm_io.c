@@ -50,6 +50,31 @@ void lbm_read_params(const char* paramfile, lbm_params* params)
   fclose(fp);
 }
 
+void lbm_read_params_double(const char* paramfile, lbm_params_double* params)
+{
+  char message[1024];
+  FILE* fp = fopen(paramfile, "r");
+  if (fp == NULL) {
+    snprintf(message, sizeof(message), "could not open input parameter file: %s", paramfile);
+    lbm_die(message, __LINE__, __FILE__);
+  }
+
+  /* the same seven values; the last three scanned as doubles, so 1.85 is the double 1.85, not (double)1.85f */
+  struct { const char* fmt; void* dst; const char* what; } field[7] = {
+    { "%d\n",  &params->nx,           "could not read param file: nx" },
+    { "%d\n",  &params->ny,           "could not read param file: ny" },
+    { "%d\n",  &params->max_iters,    "could not read param file: maxIters" },
+    { "%d\n",  &params->reynolds_dim, "could not read param file: reynolds_dim" },
+    { "%lf\n", &params->density,      "could not read param file: density" },
+    { "%lf\n", &params->accel,        "could not read param file: accel" },
+    { "%lf\n", &params->omega,        "could not read param file: omega" },
+  };
+  for (int i = 0; i < 7; i++) {
+    if (fscanf(fp, field[i].fmt, field[i].dst) != 1) lbm_die(field[i].what, __LINE__, __FILE__);
+  }
+  fclose(fp);
+}
+
 int* lbm_read_obstacles(const char* obstaclefile, const lbm_params* params)
 {
   char message[1024];
@@ -93,11 +118,16 @@ int* lbm_tile_obstacles(const int* tile, int tile_nx, int tile_ny, int nx, int n
  * fprintf produces) and written out in order. */
 #define LBM_LINE_MAX 128 /* "%d %d" + 4 x "%.12E" (<= 20 chars each) + " %d\n" */
 
-void lbm_write_final_state_rows(FILE* fp, const lbm_params* params, int row_first, int row_count,
-                                const float* u_x, const float* u_y, const float* u_mag,
-                                const float* pressure, const int* obstacles)
+/* element c of a field of floats or of doubles, as printf receives it (a float argument is promoted to double) */
+static inline double field_at(const void* field, int is_double, size_t c)
 {
-  const int nx = params->nx;
+  return is_double ? ((const double*)field)[c] : (double)((const float*)field)[c];
+}
+
+static void write_final_state_rows(FILE* fp, int nx, int row_first, int row_count, int is_double,
+                                   const void* u_x, const void* u_y, const void* u_mag,
+                                   const void* pressure, const int* obstacles)
+{
   int n_threads = 1;
 #ifdef _OPENMP
   n_threads = omp_get_max_threads();
@@ -126,8 +156,9 @@ void lbm_write_final_state_rows(FILE* fp, const lbm_params* params, int row_firs
         for (int ii = 0; ii < nx; ii++) {
           const size_t c = (size_t)r * nx + ii;
           /* the reference's format, SerialCode/d2q9-bgk.c:722 */
-          out += snprintf(out, LBM_LINE_MAX, "%d %d %.12E %.12E %.12E %.12E %d\n", ii, jj, u_x[c], u_y[c],
-                          u_mag[c], pressure[c], obstacles[(size_t)jj * nx + ii]);
+          out += snprintf(out, LBM_LINE_MAX, "%d %d %.12E %.12E %.12E %.12E %d\n", ii, jj, field_at(u_x, is_double, c),
+                          field_at(u_y, is_double, c), field_at(u_mag, is_double, c), field_at(pressure, is_double, c),
+                          obstacles[(size_t)jj * nx + ii]);
         }
       }
       used[t] = (size_t)(out - buf[t]);
@@ -139,6 +170,28 @@ void lbm_write_final_state_rows(FILE* fp, const lbm_params* params, int row_firs
   for (int t = 0; t < n_threads; t++) free(buf[t]);
   free(buf);
   free(used);
+}
+
+void lbm_write_final_state_rows(FILE* fp, const lbm_params* params, int row_first, int row_count,
+                                const float* u_x, const float* u_y, const float* u_mag,
+                                const float* pressure, const int* obstacles)
+{
+  write_final_state_rows(fp, params->nx, row_first, row_count, 0, u_x, u_y, u_mag, pressure, obstacles);
+}
+
+void lbm_write_final_state_rows_double(FILE* fp, const lbm_params_double* params, int row_first, int row_count,
+                                       const double* u_x, const double* u_y, const double* u_mag,
+                                       const double* pressure, const int* obstacles)
+{
+  write_final_state_rows(fp, params->nx, row_first, row_count, 1, u_x, u_y, u_mag, pressure, obstacles);
+}
+
+void lbm_write_av_vels_double(const char* path, const double* av_vels, int n)
+{
+  FILE* fp = fopen(path, "w");
+  if (fp == NULL) lbm_die("could not open file output file", __LINE__, __FILE__);
+  for (int ii = 0; ii < n; ii++) fprintf(fp, "%d:\t%.12E\n", ii, av_vels[ii]);
+  fclose(fp);
 }
 
 void lbm_write_av_vels(const char* path, const float* av_vels, int n)

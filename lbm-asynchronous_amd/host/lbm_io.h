@@ -28,6 +28,9 @@ void lbm_usage(const char* exe);
 /* the seven fscanf reads of initialise() (:471-509); dies with the reference's messages */
 void lbm_read_params(const char* paramfile, lbm_params* params);
 
+/* the same file for the double engine: density, accel and omega scanned as doubles ("%lf") */
+void lbm_read_params_double(const char* paramfile, lbm_params_double* params);
+
 /* malloc + zero an int[ny*nx] map and fill it from the obstacle file (:541-604);
  * dies with the reference's messages on malformed or out-of-range lines */
 int* lbm_read_obstacles(const char* obstaclefile, const lbm_params* params);
@@ -47,5 +50,11 @@ void lbm_write_final_state_rows(FILE* fp, const lbm_params* params, int row_firs
 void lbm_write_animation_frame(const char* dir, int nx, int ny, int timestep, const float* u_mag);
 /* av_vels.dat: "%d:\t%.12E\n" (:735-738) */
 void lbm_write_av_vels(const char* path, const float* av_vels, int n);
+
+/* the two writers for the double engine's results: the same formats ("%.12E"), which show a double's first 13 digits */
+void lbm_write_final_state_rows_double(FILE* fp, const lbm_params_double* params, int row_first, int row_count,
+                                       const double* u_x, const double* u_y, const double* u_mag,
+                                       const double* pressure, const int* obstacles);
+void lbm_write_av_vels_double(const char* path, const double* av_vels, int n);
 
 #endif /* LBM_IO_H */
