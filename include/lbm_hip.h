@@ -433,6 +433,46 @@ int lbm_set_mean_order(lbm_ctx* ctx, int every, int order);   /* order 1 or 2 */
 int lbm_read_mean2(lbm_ctx* ctx, double* sum_uxux, double* sum_uyuy, double* sum_uxuy, double* sum_pp,
                    long long* n_samples);
 
+/* ---- field frames -----------------------------------------------------------------------------
+ * The time evolution of the flow field itself: what the reference's write_values prints once at the end
+ * (SerialCode/d2q9-bgk.c:662-743; final_state.dat, which its visualize_4plots.py draws), recorded every N steps by the
+ * running kernels, for a chosen subset of the four fields over a chosen rectangle -- the whole grid, a centreline
+ * (the u_x / u_y profiles of the lid-driven cavity), or a region of interest on a grid whose whole frame is too large.
+ * lbm_set_field_frames(ctx, every, capacity, fields, window): from now on, after global timestep tt (0-based, counted from
+ *   the context's creation, the numbering of lbm_set_frames) with tt % every == 0, record one frame of the lattice after
+ *   tt+1 timesteps: for every cell of the window and every selected field the float lbm_read_final_state gives there, bit
+ *   for bit (a blocked cell gives 0, 0, 0, density * c_sq).  `fields` is a non-empty set of LBM_FIELD_* bits; `window`
+ *   is a rectangle of GLOBAL cells [x0, x0+nx) x [y0, y0+ny) that does not wrap, NULL: the whole grid.  One frame is
+ *   float[F][window.ny][window.nx], the F selected planes in ascending bit order: u_x, u_y, |u|, pressure.
+ *   Frames wait in a device ring of `capacity` slots; an lbm_run / lbm_batch_run call that would record more field frames
+ *   than there are free slots fails before issuing any work.  every == 0 disarms and frees; re-arming discards unread
+ *   frames.  Memory: a slab holds only its own rows of the window (capacity * F * rows * window.nx * 4 bytes); a slab the
+ *   window misses allocates nothing and does nothing on sample steps.  If a ring cannot be allocated the call fails, says
+ *   the size, and leaves the context disarmed and whole.
+ *   Recording never changes the lattice or av_vels.  Calls that run the resident kernel record inside it (bit-identical
+ *   lattice and av_vels); other calls run as the sub-calls that end at their sample steps, each followed by one
+ *   field_frame pass (lattice and av_vels equal those of the same run issued as calls split there).
+ *   Works on lbm_create / lbm_create_tiled contexts of any number of slabs (frames are stitched by rows) and on batch
+ *   members (each its own every, fields, window and capacity; in a batch one KIND of recorder per batch).
+ *   Refused: negative every; capacity < 1 while arming; fields of 0 or outside LBM_FIELD_ALL; a window with nx < 1 or
+ *   ny < 1 or one that leaves the grid; rank contexts (lbm_create_rank*); LBM_HALO_STALE / LBM_HALO_FRESHEST (and
+ *   lbm_set_halo_mode to those while armed); a context with another recorder armed (and the other setters while this one
+ *   is armed); lbm_run_until / lbm_batch_run_until while armed; on resident shapes with four-row bands, a lid row that is
+ *   not an interior row of a band, and any shape whose field-frame form of the resident kernel does not fit a CU (the
+ *   checks lbm_set_frames makes, against this form).
+ * lbm_read_field_frames: drains up to max_frames oldest frames into out[n][F][window.ny][window.nx] and steps[n] (their
+ *   tt, may be NULL); out == NULL && steps == NULL: *n_read = frames waiting, nothing drained.  Synchronises like the
+ *   other readers (so a resident give-up is reported here too).
+ */
+#define LBM_FIELD_UX       1
+#define LBM_FIELD_UY       2
+#define LBM_FIELD_UMAG     4
+#define LBM_FIELD_PRESSURE 8
+#define LBM_FIELD_ALL      15
+typedef struct { int x0, y0, nx, ny; } lbm_window;   /* GLOBAL cells [x0, x0+nx) x [y0, y0+ny), no wrap */
+int lbm_set_field_frames(lbm_ctx* ctx, int every, int capacity, int fields, const lbm_window* window /* NULL: whole grid */);
+int lbm_read_field_frames(lbm_ctx* ctx, int max_frames, float* out, int* steps, int* n_read);
+
 /* ---- steady-state runs ----------------------------------------------------------------------
  * The reference runs a fixed number of timesteps (maxIters, SerialCode/d2q9-bgk.c:166); none of its data sets has
  * stopped changing by then.  lbm_run_until advances the lattice until its average velocity has, with the decision taken

@@ -48,7 +48,8 @@ ABI_SYMBOLS = (
     "lbm_create_rank_hosted_tiled", "lbm_destroy",
     "lbm_get_info", "lbm_set_halo_mode", "lbm_read_halo_log", "lbm_run", "lbm_sync", "lbm_run_timed", "lbm_read_av_vels", "lbm_read_cells",
     "lbm_read_final_state", "lbm_av_velocity", "lbm_total_density", "lbm_calc_reynolds",
-    "lbm_set_frames", "lbm_read_frames", "lbm_set_probes", "lbm_read_probes", "lbm_set_mean", "lbm_read_mean", "lbm_set_mean_order", "lbm_run_until", "lbm_batch_run_until",
+    "lbm_set_frames", "lbm_read_frames", "lbm_set_probes", "lbm_read_probes", "lbm_set_mean", "lbm_read_mean", "lbm_set_mean_order",
+    "lbm_set_field_frames", "lbm_read_field_frames", "lbm_run_until", "lbm_batch_run_until",
     "lbm_create_batch", "lbm_batch_member", "lbm_batch_run", "lbm_batch_sync", "lbm_batch_get_info", "lbm_destroy_batch",
     "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
     "lbm_double_sync", "lbm_double_read_av_vels", "lbm_double_read_cells", "lbm_double_read_final_state",
@@ -109,6 +110,10 @@ class _CSteadyResult(ctypes.Structure):
 class _CRcclStatus(ctypes.Structure):
     _fields_ = [("loaded", ctypes.c_int), ("version", ctypes.c_int), ("n_comms", ctypes.c_int),
                 ("nranks", ctypes.c_int), ("rank", ctypes.c_int), ("library", ctypes.c_char * 512)]
+
+
+class _CWindow(ctypes.Structure):
+    _fields_ = [("x0", ctypes.c_int), ("y0", ctypes.c_int), ("nx", ctypes.c_int), ("ny", ctypes.c_int)]
 
 
 class _CHaloOp(ctypes.Structure):
@@ -226,6 +231,8 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_read_mean.argtypes = [P, P, P, P, P, ctypes.POINTER(ctypes.c_longlong)]; lib.lbm_read_mean.restype = I
     lib.lbm_set_mean_order.argtypes = [P, I, I]; lib.lbm_set_mean_order.restype = I
     lib.lbm_read_mean2.argtypes = [P, P, P, P, P, ctypes.POINTER(ctypes.c_longlong)]; lib.lbm_read_mean2.restype = I
+    lib.lbm_set_field_frames.argtypes = [P, I, I, I, ctypes.POINTER(_CWindow)]; lib.lbm_set_field_frames.restype = I
+    lib.lbm_read_field_frames.argtypes = [P, I, P, P, PI]; lib.lbm_read_field_frames.restype = I
     lib.lbm_run_until.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CSteadyResult)]
     lib.lbm_run_until.restype = I
     lib.lbm_batch_run_until.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CSteadyResult), PI]
@@ -586,6 +593,38 @@ class Engine:
         sums2, _ = self.moment_sums()
         return fluctuations_of(sums, sums2, n)
 
+    # -- field frames (lbm_set_field_frames / lbm_read_field_frames) ------------------------------
+    def set_field_frames(self, every: int, capacity: int = 0, fields=("u_x", "u_y", "u", "pressure"), window=None) -> None:
+        """Record the chosen `fields` -- a non-empty subset of final_state()'s keys -- over `window` = (x0, y0, nx, ny) in
+        global cells (None: the whole grid) after every global timestep tt with tt % every == 0, bit for bit what
+        final_state() gives there after tt + 1 steps, into a device ring of `capacity` frames.  every == 0 disarms;
+        re-arming discards unread frames."""
+        every, capacity, mask, window = _field_frame_args(every, capacity, fields, window)
+        win = _CWindow(*window) if window is not None else None
+        _check(self.lib, self.lib.lbm_set_field_frames(self.handle, every, capacity, mask, ctypes.byref(win) if win else None))
+        if every > 0:
+            full = (0, 0, self.params.nx, self.params.ny)
+            self._field_frames = ([k for k in FIELD_NAMES if mask & FIELD_BITS[k]], window if window is not None else full)
+        else:
+            self._field_frames = None
+
+    def field_frames(self, max_frames: int | None = None) -> tuple[np.ndarray, dict]:
+        """Drain up to max_frames (default: all) waiting field frames, oldest first:
+        (steps int32[n], {name: float32[n, window ny, window nx]}) for the armed fields."""
+        if max_frames is not None and (isinstance(max_frames, bool) or not isinstance(max_frames, (int, np.integer))
+                                       or max_frames < 0):
+            raise LbmError(f"field_frames: max_frames must be a non-negative integer or None (got {max_frames!r})")
+        n = ctypes.c_int()
+        _check(self.lib, self.lib.lbm_read_field_frames(self.handle, 0, None, None, ctypes.byref(n)))  # frames waiting
+        max_frames = n.value if max_frames is None else min(int(max_frames), n.value)
+        names, window = getattr(self, "_field_frames", None) or ([], (0, 0, 0, 0))
+        out = np.empty((int(max_frames), len(names), window[3], window[2]), dtype=np.float32)
+        steps = np.empty(int(max_frames), dtype=np.int32)
+        if max_frames > 0:
+            _check(self.lib, self.lib.lbm_read_field_frames(self.handle, int(max_frames), out.ctypes.data, steps.ctypes.data,
+                                                            ctypes.byref(n)))
+        return steps[:n.value].copy(), {k: out[:n.value, j].copy() for j, k in enumerate(names)}
+
     # -- results -----------------------------------------------------------------------------
     def av_vels(self, n: int | None = None) -> np.ndarray:
         n = self.info()["steps_done"] if n is None else n
@@ -925,6 +964,50 @@ def _frame_args(every, capacity) -> tuple[int, int]:
     return int(every), int(capacity)
 
 
+# the fields of a field frame under final_state()'s keys, in the order of their planes (LBM_FIELD_* of include/lbm_hip.h)
+FIELD_NAMES = ("u_x", "u_y", "u", "pressure")
+FIELD_BITS = {"u_x": 1, "u_y": 2, "u": 4, "pressure": 8}
+
+
+def _field_frame_args(every, capacity, fields, window) -> tuple[int, int, int, tuple | None]:
+    """Engine.set_field_frames' argument checks (no device needed): (every, capacity, LBM_FIELD_* mask, window or None)."""
+    for name, v in (("every", every), ("capacity", capacity)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise LbmError(f"set_field_frames: {name} must be an integer (got {v!r})")
+        if not 0 <= int(v) <= 2147483647:
+            raise LbmError(f"set_field_frames: {name} must lie in [0, 2^31) (got {v})")
+    if every > 0 and capacity < 1:
+        raise LbmError(f"set_field_frames: capacity {capacity}, at least one frame slot is needed")
+    if isinstance(fields, str):
+        fields = (fields,)
+    try:
+        names = list(fields)
+    except TypeError:
+        raise LbmError(f"set_field_frames: fields must be a sequence of names among {FIELD_NAMES} (got {fields!r})") from None
+    if not names:
+        raise LbmError(f"set_field_frames: no fields, at least one of {FIELD_NAMES} is needed")
+    mask = 0
+    for name in names:
+        if not isinstance(name, str) or name not in FIELD_BITS:
+            raise LbmError(f"set_field_frames: unknown field {name!r}, the fields are {FIELD_NAMES}")
+        if mask & FIELD_BITS[name]:
+            raise LbmError(f"set_field_frames: field {name!r} is named twice")
+        mask |= FIELD_BITS[name]
+    if window is not None:
+        try:
+            win = tuple(window)
+        except TypeError:
+            win = ()
+        if len(win) != 4 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in win):
+            raise LbmError(f"set_field_frames: window must be four integers (x0, y0, nx, ny) (got {window!r})")
+        if not all(0 <= int(v) <= 2147483647 for v in win):
+            raise LbmError(f"set_field_frames: window values must lie in [0, 2^31) (got {window!r})")
+        if win[2] < 1 or win[3] < 1:
+            raise LbmError(f"set_field_frames: a window of {win[2]} x {win[3]} cells, at least 1 x 1 is needed")
+        window = tuple(int(v) for v in win)
+    return int(every), int(capacity), mask, window
+
+
 LBM_MAX_PROBES = 256
 
 
@@ -1071,6 +1154,25 @@ def write_final_state(path: str, fields: dict, obstacles: np.ndarray) -> None:
                                  fields["pressure"][jj], obstacles[jj])
             fh.write("".join("%d %d %.12E %.12E %.12E %.12E %d\n" %
                              (ii, jj, ux[ii], uy[ii], u[ii], pr[ii], ob[ii]) for ii in range(nx)))
+
+
+def write_state_frame(path: str, fields: dict, obstacles: np.ndarray, window) -> None:
+    """One field frame in final_state.dat's line format (write_final_state) for the cells of `window` = (x0, y0, nx, ny):
+    global 'ii jj', jj outer / ii inner.  `fields` holds the four fields over the window, [window ny, window nx] each
+    (one frame of Engine.field_frames); `obstacles` is the whole grid's map."""
+    x0, y0, wnx, wny = (int(v) for v in window)
+    obstacles = np.asarray(obstacles)
+    planes = [np.asarray(fields[k], dtype=np.float32) for k in FIELD_NAMES]
+    if any(p.shape != (wny, wnx) for p in planes):
+        raise LbmError(f"write_state_frame: every field must be [{wny}, {wnx}] (got {[p.shape for p in planes]})")
+    if x0 < 0 or y0 < 0 or y0 + wny > obstacles.shape[0] or x0 + wnx > obstacles.shape[1]:
+        raise LbmError(f"write_state_frame: the window {tuple(window)} leaves the {obstacles.shape[1]} x {obstacles.shape[0]} grid")
+    with open(path, "w") as fh:
+        for j in range(wny):
+            ux, uy, u, pr = (p[j] for p in planes)
+            ob = obstacles[y0 + j]
+            fh.write("".join("%d %d %.12E %.12E %.12E %.12E %d\n" %
+                             (x0 + i, y0 + j, ux[i], uy[i], u[i], pr[i], ob[x0 + i]) for i in range(wnx)))
 
 
 # ------------------------------------------------------------------------------------------------

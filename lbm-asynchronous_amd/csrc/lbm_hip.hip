@@ -248,6 +248,8 @@ struct Slab {
   int probe_count = 0;                     // ... and how many they are
   DeviceBuf<double> mean_sums;             // lbm_set_mean: four planes [rows][nx]: sums of u_x, u_y, |u|, pressure of the owned rows;
                                            // lbm_set_mean_order(.., 2): eight, then u_x u_x, u_y u_y, u_x u_y, pressure pressure
+  DeviceBuf<float> field_ring;             // lbm_set_field_frames: [slots][F][field_ny][window nx], this slab's rows of the window
+  int field_y0 = 0, field_ny = 0;          // ... those rows: slab rows [field_y0, field_y0 + field_ny); none: no ring
   // freshest-available mode (LBM_HALO_FRESHEST), allocated at its first use in this order: whole once ev_fresh[1] exists
   DeviceBuf<float> fresh_stage;          // [parity][side: 0 south halo, 1 north halo][row_pitch]: this pass's rows, if they make it
   DeviceBuf<unsigned> fresh_arrived;     // [parity][side]: id (global step + 1) of the step whose row the staging holds
@@ -394,7 +396,9 @@ struct GraphBuilder {
 // (|u| of the owned rows, lbm_set_frames) or a row of probe samples (lbm_set_probes) -- into slot
 // (tt / every - ord0) % slots of every slab's buffer of that kind.  The mean fields (lbm_set_mean) are the kind without
 // slots: their record is added to per-cell sums, `written` counts the samples, `read`, `slots` and `ord0` stay unused.
-enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean, kRecKinds = 4 };
+// Field frames (lbm_set_field_frames) are slotted like the frames: chosen fields over a window instead of |u| everywhere.
+enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean,
+       kRecFields = lbm::kRecFields, kRecKinds = 5 };
 struct Recorder {
   int kind = kRecNone;
   int every = 0;
@@ -403,6 +407,8 @@ struct Recorder {
   long long written = 0;    // records issued since arming (ordinals 0 .. written - 1) ...
   long long read = 0;       // ... and drained by the kind's reader
   int order = 0;            // mean fields: 1 = the four sums, 2 = also the four sums of products (lbm_set_mean_order)
+  int fields = 0;           // field frames: the LBM_FIELD_* bits ...
+  lbm_window window = {0, 0, 0, 0};  // ... and the window, global cells
 };
 // what differs between the kinds in the host's messages (indexed by kind; kRecNone keeps the empty defaults)
 struct RecorderKind {
@@ -421,7 +427,9 @@ constexpr RecorderKind kRecorderKinds[kRecKinds] = {
     {.name = "point probes", .noun = "probes", .record = "sample", .setter = "lbm_set_probes",
      .reader = "lbm_read_probes", .disarm = "lbm_set_probes(ctx, 0, NULL, 0, 0)"},
     {.name = "mean fields", .noun = "mean fields", .record = "sample", .setter = "lbm_set_mean",
-     .reader = "lbm_read_mean", .disarm = "lbm_set_mean(ctx, 0)", .slotted = false}};
+     .reader = "lbm_read_mean", .disarm = "lbm_set_mean(ctx, 0)", .slotted = false},
+    {.name = "field frames", .noun = "field frames", .record = "field frame", .setter = "lbm_set_field_frames",
+     .reader = "lbm_read_field_frames", .disarm = "lbm_set_field_frames(ctx, 0, 0, 0, NULL)"}};
 
 struct lbm_ctx {
   lbm_params p;
@@ -451,7 +459,7 @@ struct lbm_ctx {
   bool resident_used = false;       // a resident launch is in flight / unchecked: lbm_sync reads its status
   lbm_batch* batch = nullptr;       // member of this batch (lbm_create_batch): advanced, synchronised and freed by it
   Recorder rec;                     // the one recorder: animation frames (lbm_set_frames), point probes (lbm_set_probes) or
-                                    // mean fields (lbm_set_mean)
+                                    // mean fields (lbm_set_mean) or field frames (lbm_set_field_frames)
   std::vector<lbm_probe> probe_cells;  // the probed global cells, in the caller's order (a probes row has that many samples)
   // steady-state runs (lbm_run_until), allocated by the first such call in this order: whole once ev_steady[1] exists
   DeviceBuf<lbm::SteadyState> steady_state;  // device: what the checks of the current call have found
@@ -478,7 +486,8 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentFrames> frame_table;  // device: [members], allocated when the first member arms frames
   DeviceBuf<lbm::ResidentProbes> probe_table;  // device: [members], allocated when the first member arms probes
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
-  int armed[kRecKinds] = {0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
+  DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
+  int armed[kRecKinds] = {0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
                                     // (a batch records one kind, so at most one count is non-zero)
   // steady-state runs (lbm_batch_run_until), allocated by the first such call; steady_state last: the set is whole once it exists
   DeviceBuf<lbm::SteadyMember> steady_members; // device: [members]
@@ -1300,8 +1309,10 @@ const void* resident_form(int shape) {
 const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = false) {
   using Form = const void* (*)(int);
   static const Form forms[2][kRecKinds] = {
-      {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>, resident_form<false, kRecMean>},
-      {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>, resident_form<true, kRecMean>}};
+      {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>, resident_form<false, kRecMean>,
+       resident_form<false, kRecFields>},
+      {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>, resident_form<true, kRecMean>,
+       resident_form<true, kRecFields>}};
   return forms[batch][rec]((rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
 }
 
@@ -1320,6 +1331,12 @@ lbm::ResidentMean mean_entry(const lbm_ctx* c) {
   if (c->rec.kind != kRecMean) return {};
   const Slab& s0 = c->slab[0];
   return {s0.mean_sums, (long)s0.rows * c->p.nx, c->rec.every, c->p.density, c->rec.order, 0};
+}
+lbm::ResidentFields fields_entry(const lbm_ctx* c) {
+  if (c->rec.kind != kRecFields) return {};
+  const Slab& s0 = c->slab[0];
+  return {s0.field_ring, c->rec.every, c->rec.ord0, c->rec.slots, c->rec.fields, c->rec.window.x0, s0.field_y0, c->rec.window.nx,
+          s0.field_ny, c->p.density, 0};
 }
 
 // the fields of ResidentArgs that plain and batched launches share: n timesteps from global step epoch0, last = the
@@ -1345,13 +1362,16 @@ void fill_resident_args(lbm::ResidentArgs& a, const lbm_ctx* c, int n, bool last
 int run_resident(lbm_ctx* c, int n_steps) {
   Slab& sl = c->slab[0];
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-  const bool probes = (c->rec.kind == kRecProbes), mean = (c->rec.kind == kRecMean);
+  const bool probes = (c->rec.kind == kRecProbes), mean = (c->rec.kind == kRecMean), fields = (c->rec.kind == kRecFields);
   for (int t = 0; t < n_steps;) {
     const int n = (n_steps - t < kResidentChunk) ? n_steps - t : kResidentChunk;
     lbm::ResidentFramesArgs fa;  // the frames form's arguments, ResidentArgs + the frame fields; the plain form reads its part
     lbm::ResidentProbesArgs pa;  // the probes form's: ResidentArgs + the probe fields
     lbm::ResidentMeanArgs ma;    // the mean form's: ResidentArgs + the mean fields
-    lbm::ResidentArgs& a = probes ? static_cast<lbm::ResidentArgs&>(pa) : (mean ? static_cast<lbm::ResidentArgs&>(ma) : fa);
+    lbm::ResidentFieldsArgs da;  // the field frames' form's: ResidentArgs + the field-frame fields
+    lbm::ResidentArgs& a = probes ? static_cast<lbm::ResidentArgs&>(pa)
+                           : mean ? static_cast<lbm::ResidentArgs&>(ma) : fields ? static_cast<lbm::ResidentArgs&>(da) : fa;
+    da.fd = fields_entry(c);
     fa.fr = frames_entry(c);
     pa.pr = probes_entry(c);
     ma.mn = mean_entry(c);
@@ -1366,7 +1386,7 @@ int run_resident(lbm_ctx* c, int n_steps) {
     if (!prof_dev) HIP_TRY(LBM_FAILURE, hipMalloc(&prof_dev, 1024 * 8 * sizeof(long long)));
     a.prof = prof_dev;
 #endif
-    void* args[] = {probes ? static_cast<void*>(&pa) : (mean ? static_cast<void*>(&ma) : static_cast<void*>(&fa))};
+    void* args[] = {&a};  // (the form's own arguments start at the base's address)
     HIP_TRY(LBM_FAILURE, hipLaunchKernel(resident_kernel(c->p.nx, c->plan.resident_rows, c->plan.resident_joint, c->rec.kind),
                                          dim3(c->plan.resident_bands / a.group * (a.one_xcd ? 8 : 1)), dim3(c->p.nx * a.group), args, 0, sl.compute));
     hipLaunchKernelGGL(lbm::reduce_band_partials, dim3(n), dim3(64), 0, sl.compute, (const float*)sl.res_part,
@@ -1428,9 +1448,12 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
     lbm::ResidentBatchMeanArgs ma;    // the mean form's: ResidentBatchArgs + the members' mean fields
     memset(&fa, 0, sizeof(fa));
     memset(&pa, 0, sizeof(pa));
+    lbm::ResidentBatchFieldsArgs da;  // the field frames' form's: ResidentBatchArgs + the members' field-frame fields
     memset(&ma, 0, sizeof(ma));
+    memset(&da, 0, sizeof(da));
     lbm::ResidentBatchArgs& a = (rec == kRecProbes) ? static_cast<lbm::ResidentBatchArgs&>(pa)
-                                : (rec == kRecMean) ? static_cast<lbm::ResidentBatchArgs&>(ma) : fa;
+                                : (rec == kRecMean) ? static_cast<lbm::ResidentBatchArgs&>(ma)
+                                : (rec == kRecFields) ? static_cast<lbm::ResidentBatchArgs&>(da) : fa;
     fill_resident_args(a, c0, n, t + n == n_steps, bt->steps_done + t);
     a.status = bt->status;
     a.member_wgs = bt->member_wgs;
@@ -1439,9 +1462,10 @@ int run_batch_resident(lbm_batch* bt, int n_steps) {
       fa.frames = bt->frame_table ? bt->frame_table + first : nullptr;
       pa.probes = bt->probe_table ? bt->probe_table + first : nullptr;
       ma.means = bt->mean_table ? bt->mean_table + first : nullptr;
+      da.fields = bt->field_table ? bt->field_table + first : nullptr;
       a.n_members = (n_members - first < bt->members_per_launch) ? n_members - first : bt->members_per_launch;
       const int grid = a.one_xcd ? bt->member_wgs * 8 : a.n_members * (int)round_up(bt->member_wgs, 8);
-      void* args[] = {(rec == kRecProbes) ? static_cast<void*>(&pa) : (rec == kRecMean) ? static_cast<void*>(&ma) : static_cast<void*>(&fa)};
+      void* args[] = {&a};
       HIP_TRY(LBM_FAILURE, hipLaunchKernel(kernel, dim3(grid), dim3(c0->p.nx * a.group), args, 0, bt->stream));
     }
     hipLaunchKernelGGL(lbm::reduce_band_partials_batch, dim3(n, n_members), dim3(64), 0, bt->stream, tab, bands,
@@ -1491,7 +1515,14 @@ int take_record(lbm_ctx* c) {
         if (c->rec.kind == kRecFrames)
           hipLaunchKernelGGL(lbm::frame_umag, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              sl.frames + slot * n);
-        else if (c->rec.kind == kRecMean)
+        else if (c->rec.kind == kRecFields) {
+          const lbm_window& w = c->rec.window;
+          const long cells = (long)sl.field_ny * w.nx;  // 0: the window misses this slab
+          if (cells > 0)
+            hipLaunchKernelGGL(lbm::field_frame, dim3(ceil_div(cells, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), c->p.density,
+                               c->rec.fields, w.x0, sl.field_y0, w.nx, sl.field_ny,
+                               sl.field_ring + slot * (size_t)__builtin_popcount((unsigned)c->rec.fields) * (size_t)cells);
+        } else if (c->rec.kind == kRecMean)
           hipLaunchKernelGGL(lbm::mean_accumulate, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              c->p.density, sl.mean_sums, n, c->rec.order);
         else if (sl.probe_count > 0)
@@ -2203,6 +2234,7 @@ int write_batch_entry(lbm_ctx* c, int kind) {
   if (!c->batch) return LBM_SUCCESS;
   if (kind == kRecFrames) return set_batch_entry(c, c->batch->frame_table, frames_entry(c));
   if (kind == kRecProbes) return set_batch_entry(c, c->batch->probe_table, probes_entry(c));
+  if (kind == kRecFields) return set_batch_entry(c, c->batch->field_table, fields_entry(c));
   return set_batch_entry(c, c->batch->mean_table, mean_entry(c));
 }
 
@@ -2215,6 +2247,8 @@ void release_recorder(lbm_ctx* c) {
     sl.probe_ring.reset();
     sl.probe_table.reset();
     sl.mean_sums.reset();
+    sl.field_ring.reset();
+    sl.field_y0 = sl.field_ny = 0;
     sl.probe_count = 0;
   }
   c->probe_cells.clear();
@@ -2242,7 +2276,7 @@ int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate alloc
         LBM_FAIL(LBM_FAILURE, "%s: %s are armed (%s) and a context has one recorder -- disarm them with %s first", setter, o.name,
                  o.setter, o.disarm);
       if (bt && bt->armed[other] > 0)
-        LBM_FAIL(LBM_FAILURE, "%s: a member of this batch has %s armed (%s); a batch records one kind: frames, probes or mean fields",
+        LBM_FAIL(LBM_FAILURE, "%s: a member of this batch has %s armed (%s); a batch records one kind: frames, probes, mean fields or field frames",
                  setter, o.name, o.setter);
     }
     if (c->plan.resident) {
@@ -2697,6 +2731,80 @@ int lbm_set_mean(lbm_ctx* c, int every) { return set_mean_order(c, every, 1, "lb
 
 int lbm_set_mean_order(lbm_ctx* c, int every, int order) {
   return set_mean_order(c, every, order, "lbm_set_mean_order");
+}
+
+int lbm_set_field_frames(lbm_ctx* c, int every, int capacity, int fields, const lbm_window* window) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_field_frames: null context");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_field_frames: negative interval %d", every);
+  lbm_window w = {0, 0, c->p.nx, c->p.ny};
+  if (every > 0) {
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_field_frames: capacity %d, at least one frame slot is needed", capacity);
+    if (fields == 0 || (fields & ~LBM_FIELD_ALL) != 0)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_field_frames: fields 0x%x, a non-empty set of LBM_FIELD_* bits (within 0x%x) is needed", (unsigned)fields,
+               (unsigned)LBM_FIELD_ALL);
+    if (window) w = *window;
+    if (w.nx < 1 || w.ny < 1)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_field_frames: a window of %d x %d cells, at least 1 x 1 is needed", w.nx, w.ny);
+    if (w.x0 < 0 || w.y0 < 0 || w.x0 > c->p.nx - w.nx || w.y0 > c->p.ny - w.ny)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_field_frames: the window [%d, %lld) x [%d, %lld) leaves the %d x %d grid (windows do not wrap)", w.x0,
+               (long long)w.x0 + w.nx, w.y0, (long long)w.y0 + w.ny, c->p.nx, c->p.ny);
+    if (c->ranked || c->world > 1)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_field_frames: not available in a multi-process (rank) context: a frame would be spread over the ranks");
+  }
+  const size_t planes = (size_t)__builtin_popcount((unsigned)fields);
+  return rearm_recorder(c, kRecFields, every, capacity, [&]() -> int {
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      // this slab's rows of the window
+      const int lo = (w.y0 > sl.row_first) ? w.y0 : sl.row_first;
+      const int hi = (w.y0 + w.ny < sl.row_first + sl.rows) ? w.y0 + w.ny : sl.row_first + sl.rows;
+      if (hi <= lo) continue;  // the window misses this slab: nothing to allocate, nothing to record
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      const size_t slot_bytes = planes * (size_t)(hi - lo) * (size_t)w.nx * sizeof(float);
+      // (a slot is one buffer of the resident kernel's, 32-bit offsets; the ring's size is computed without overflow)
+      if (slot_bytes > ((size_t)-1) / (size_t)capacity || sl.field_ring.alloc_bytes((size_t)capacity * slot_bytes) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_field_frames: cannot allocate %d frame slots of %d fields x %d x %d cells (%.1f MiB per slab); field frames stay off",
+                 capacity, (int)planes, hi - lo, w.nx, (double)capacity * (double)slot_bytes / 1048576.0);
+      sl.field_y0 = lo - sl.row_first;
+      sl.field_ny = hi - lo;
+    }
+    c->rec.fields = fields;  // read by fields_entry when rearm_recorder writes the member's batch entry
+    c->rec.window = w;
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_read_field_frames(lbm_ctx* c, int max_frames, float* out, int* steps, int* n_read) {
+  return drain_recorder(c, kRecFields, max_frames, out != nullptr, steps, n_read, [&](int n) -> int {
+    const lbm_window& w = c->rec.window;
+    const size_t planes = (size_t)__builtin_popcount((unsigned)c->rec.fields);
+    const size_t plane_cells = (size_t)w.ny * w.nx, frame_cells = planes * plane_cells;
+    for (int i = 0; i < n; i++) {
+      const size_t slot = (size_t)((c->rec.read + i) % c->rec.slots);
+      for (int s = 0; s < c->n_slabs; s++) {
+        Slab& sl = c->slab[s];
+        if (sl.field_ny == 0) continue;
+        HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+        // a slab's slot is float[F][field_ny][window nx]: its rows of every plane go to their place in the frame (one
+        // copy where the slab holds the whole window)
+        const size_t cells = (size_t)sl.field_ny * w.nx;
+        const size_t row_off = (size_t)(sl.row_first + sl.field_y0 - w.y0) * w.nx;
+        const float* src = sl.field_ring + slot * planes * cells;
+        if (sl.field_ny == w.ny) {
+          HIP_TRY(LBM_FAILURE, hipMemcpyAsync(out + i * frame_cells, src, frame_cells * sizeof(float), hipMemcpyDeviceToHost, sl.compute));
+        } else {
+          for (size_t j = 0; j < planes; j++)
+            HIP_TRY(LBM_FAILURE, hipMemcpyAsync(out + i * frame_cells + j * plane_cells + row_off, src + j * cells, cells * sizeof(float),
+                                                hipMemcpyDeviceToHost, sl.compute));
+        }
+      }
+    }
+    for (int s = 0; s < c->n_slabs; s++) {
+      HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
+    }
+    return LBM_SUCCESS;
+  });
 }
 
 // the planes [first, first + 4) of every slab's sums, stitched by row_first; lbm_read_mean and lbm_read_mean2

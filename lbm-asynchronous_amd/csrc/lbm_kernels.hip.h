@@ -40,7 +40,7 @@ constexpr int kBlock = 256;  // 4 waves of 64
 constexpr int kQ = 9;
 constexpr int kNoRow = -1000000;  // "no such row in this slab"
 // what a context records while it runs, at most one at a time: the host's Recorder::kind and resident_band's REC
-constexpr int kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3;
+constexpr int kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3, kRecFields = 4;
 
 // 1/3 rounded to fp32, and the two constant divisors of the equilibrium, folded in fp32
 // exactly as the reference's "2.f * c_sq" and "2.f * c_sq * c_sq" (SerialCode/d2q9-bgk.c:308,367-370)
@@ -1618,6 +1618,27 @@ struct ResidentMeanArgs : ResidentArgs {
 struct ResidentBatchMeanArgs : ResidentBatchArgs {
   const ResidentMean* means;  // [this launch's members], as members
 };
+// field frames (lbm_set_field_frames, resident_band<..., REC = kRecFields>): after global step tt with tt % every == 0 the
+// kernel stores the selected ones of {u_x, u_y, |u|, pressure} (bits 0..3 of `fields`, planes in ascending bit order) of
+// every cell of the window into slot (tt / every - ord0) % slots of base, one float[F][wny][wnx] per slot.  The window is
+// slab-local: columns [wx0, wx0 + wnx), slab rows [wy0, wy0 + wny) -- the slab's own rows of the caller's window, so the
+// ring of a slab holds nothing else.  Appended like ResidentFrames: the other forms' arguments do not move.
+struct ResidentFields {
+  float* base;                // slot 0; nullptr / every = 0: no field frames
+  int every;
+  int ord0;                   // tt / every of the first frame after arming
+  int slots;
+  int fields;                 // LBM_FIELD_* bits
+  int wx0, wy0, wnx, wny;
+  float density;              // a blocked cell reports density * c_sq as its pressure
+  int pad;
+};
+struct ResidentFieldsArgs : ResidentArgs {
+  ResidentFields fd;
+};
+struct ResidentBatchFieldsArgs : ResidentBatchArgs {
+  const ResidentFields* fields;  // [this launch's members], as members
+};
 #ifdef LBM_RESIDENT_PROFILE
 __device__ __forceinline__ long long prof_clock() {
   long long t;
@@ -1730,6 +1751,57 @@ __device__ __forceinline__ granule_vec granule_load(__amdgpu_buffer_rsrc_t rsrc,
   return __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)byte_off, 0, 16);
 }
 
+// field frames (resident_band<..., REC = kRecFields>): the selected values of a band's post-step cells inside the window --
+// edge pair `pe` (band rows 0 and ROWS - 1), interior pair `ri` (rows 1 and 2 of four) -- into the slot, then the deferred
+// accelerate_flow of the next step on `lidp`, the pair that holds the lid row (see take_frame), and the frames' count of
+// f_next and f_slot.  band_row0 is the slab row of the band's row 0, x the lane's column.
+template <int ROWS>
+__device__ __forceinline__ void take_fields(const ResidentFields& fd, int band_row0, int x, const f2 (&pe)[kQ], const f2 (&ri)[kQ],
+                                            f2 (&lidp)[kQ], unsigned blocked_e, unsigned blocked_i, unsigned lid, bool accel_next,
+                                            float a1, float a2, unsigned& f_next, int& f_slot) {
+  constexpr int TOP = ROWS - 1;
+  // the band's rows against the window's: wave-uniform (a band without rows of the window stores nothing)
+  const int row0 = __builtin_amdgcn_readfirstlane(band_row0) - fd.wy0;  // window row of band row 0
+  if (row0 + ROWS > 0 && row0 < fd.wny) {
+    // the slot as a buffer (scalar base, 32-bit lane offset): no 64-bit address stays live in VGPRs
+    const unsigned row_bytes = (unsigned)fd.wnx * 4u, plane_bytes = row_bytes * (unsigned)fd.wny;
+    const int planes = __builtin_popcount((unsigned)fd.fields);
+    const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(fd.base + (long)f_slot * planes * fd.wny * fd.wnx, 0,
+                                                                           (int)((unsigned)planes * plane_bytes), 0x00020000);
+    const int col = x - fd.wx0;
+    const int lane_off = col * 4;
+    auto store_cell = [&](const f2 (&p)[kQ], int c, bool blocked, int rb) {
+      const int wrow = row0 + rb;
+      if (wrow < 0 || wrow >= fd.wny) return;  // wave-uniform
+      float f[kQ];
+#pragma unroll
+      for (int k = 0; k < kQ; k++) f[k] = p[k][c];
+      const probe_vec v = probe_sample(f, blocked, fd.density);
+      unsigned soff = (unsigned)wrow * row_bytes;
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        if (((unsigned)fd.fields >> j) & 1u) {  // wave-uniform
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[j]), srsrc, lane_off, (int)soff, 2);  // aux 2 = nt
+          soff += plane_bytes;
+        }
+      }
+    };
+    if (col >= 0 && col < fd.wnx) {
+      store_cell(pe, 0, (blocked_e & 0xffu) != 0, 0);
+      store_cell(pe, 1, (blocked_e & 0xff00u) != 0, TOP);
+      if constexpr (ROWS == 4) {
+        store_cell(ri, 0, (blocked_i & 0xffu) != 0, 1);
+        store_cell(ri, 1, (blocked_i & 0xff00u) != 0, 2);
+      }
+    }
+  }
+  const unsigned blk = (ROWS == 4) ? blocked_i : blocked_e;
+  if (accel_next && lid != 0)
+    accelerate_select(lidp, (lid & 1u) != 0 && (blk & 0xffu) == 0, (lid & 2u) != 0 && (blk & 0xff00u) == 0, a1, a2);
+  f_next += (unsigned)fd.every;
+  f_slot = (f_slot + 1 == fd.slots) ? 0 : f_slot + 1;
+}
+
 // JOINT: wait for the halo first and relax both pairs as ONE block of independent work -- for narrow grids, whose few
 // waves sit alone on their SIMDs: there the step is the dependent-instruction latency of the two collisions one after
 // the other, and two independent chains interleave (issue-bound instead of latency-bound).  Wide grids (four waves
@@ -1756,10 +1828,13 @@ __device__ __forceinline__ granule_vec granule_load(__amdgpu_buffer_rsrc_t rsrc,
 // sums are not kept in registers across steps: the planes stay in L2 / Infinity Cache between samples.  At order 2
 // (ResidentMean::order, a scalar: the branch is wave-uniform and lies inside the sample branch) four more sums per cell,
 // of the products, are updated the same way through the same descriptor.
+// REC = kRecFields: also record field frames (ResidentFields).  A sample step is a frame step in every respect, as for the
+// mean fields; the four values of a cell are the mean fields' (probe_sample), stored instead of accumulated, and only by
+// the rows (a wave-uniform test) and lanes (their column) inside the window (take_fields).
 template <bool BATCH, int REC>
 using ResidentArgsOf = std::tuple_element_t<
-    REC, std::conditional_t<BATCH, std::tuple<ResidentBatchArgs, ResidentBatchFramesArgs, ResidentBatchProbesArgs, ResidentBatchMeanArgs>,
-                            std::tuple<ResidentArgs, ResidentFramesArgs, ResidentProbesArgs, ResidentMeanArgs>>>;
+    REC, std::conditional_t<BATCH, std::tuple<ResidentBatchArgs, ResidentBatchFramesArgs, ResidentBatchProbesArgs, ResidentBatchMeanArgs, ResidentBatchFieldsArgs>,
+                            std::tuple<ResidentArgs, ResidentFramesArgs, ResidentProbesArgs, ResidentMeanArgs, ResidentFieldsArgs>>>;
 template <int MAXT, bool JOINT = false, int ROWS = 4, bool BATCH = false, int REC = kRecNone>
 __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH, REC> a) {
   static_assert(ROWS == 4 || ROWS == 2, "bands of four or two rows");
@@ -1774,6 +1849,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
   ResidentFrames fr{};
   ResidentProbes pr{};
   ResidentMean mn{};
+  const ResidentFields* fdp = nullptr;  // read where it is (kernel arguments / the members' table) on sample steps: eleven words fewer to keep
   if constexpr (BATCH) {
     const int stride = (a.member_wgs + 7) & ~7;
     const int member = a.one_xcd ? (int)(blockIdx.x & 7) : (int)blockIdx.x / stride;
@@ -1783,10 +1859,12 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     if constexpr (REC == kRecFrames) fr = a.frames[member];
     if constexpr (REC == kRecProbes) pr = a.probes[member];
     if constexpr (REC == kRecMean) mn = a.means[member];
+    if constexpr (REC == kRecFields) fdp = a.fields + member;
   } else if (a.one_xcd && (blockIdx.x & 7) != 0) return;
   if constexpr (REC == kRecFrames && !BATCH) fr = a.fr;
   if constexpr (REC == kRecProbes && !BATCH) pr = a.pr;
   if constexpr (REC == kRecMean && !BATCH) mn = a.mn;
+  if constexpr (REC == kRecFields && !BATCH) fdp = &a.fd;
 #define RES_M(field) (BATCH ? mb.field : a.field)
   const int bands = n_wgs * a.group;
   // Workgroups are dealt to the 8 XCDs round-robin (observed, not promised): consecutive bands are given to
@@ -2002,6 +2080,16 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     f_next += (unsigned)mn.every;
   };
 
+  // field frames: the frames' bookkeeping (f_next, f_slot); the sample itself is take_fields (a function, not a lambda
+  // of this kernel: a closure defined here, used or not, reorders the scalar moves of the other forms' prologues)
+  if constexpr (REC == kRecFields) {
+    if (fdp->every > 0) {
+      const unsigned e = (unsigned)fdp->every, r = a.epoch0 % e;
+      f_next = r ? e - r : 0u;
+      f_slot = (int)(((a.epoch0 + f_next) / e - (unsigned)fdp->ord0) % (unsigned)fdp->slots);
+    }
+  }
+
   bool alive = true;
 #ifdef LBM_RESIDENT_PROFILE
   long long prof_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, prof_t = prof_clock();
@@ -2063,7 +2151,7 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     granule_vec sn = granule_load(grsrc, gn + x_side);
 
     bool frame_now = false;
-    if constexpr (REC == kRecFrames || REC == kRecMean) frame_now = ((unsigned)s == f_next);  // wave-uniform
+    if constexpr (REC == kRecFrames || REC == kRecMean || REC == kRecFields) frame_now = ((unsigned)s == f_next);  // wave-uniform
     // probes: a sample step; only a band with a probe on the lid row defers the lid's acceleration as a frame step does
     bool sample_now = false;
     if constexpr (REC == kRecProbes) {
@@ -2165,6 +2253,9 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     if constexpr (REC == kRecMean && ROWS == 2) {
       if (frame_now) take_mean(ne, ne, accel_next);
     }
+    if constexpr (REC == kRecFields && ROWS == 2) {
+      if (frame_now) take_fields<ROWS>(*fdp, ROWS * b, x, ne, ri, ne, blocked_e, blocked_i, lid_e, accel_next, RES_M(a1), RES_M(a2), f_next, f_slot);
+    }
 #pragma unroll
     for (int k = 0; k < kQ; k++) {
       re[k] = ne[k];
@@ -2185,6 +2276,9 @@ __global__ __launch_bounds__(MAXT) void resident_band(const ResidentArgsOf<BATCH
     }
     if constexpr (REC == kRecMean && ROWS == 4) {
       if (frame_now) take_mean(re, ri, accel_next);
+    }
+    if constexpr (REC == kRecFields && ROWS == 4) {
+      if (frame_now) take_fields<ROWS>(*fdp, ROWS * b, x, re, ri, ri, blocked_e, blocked_i, lid_i, accel_next, RES_M(a1), RES_M(a2), f_next, f_slot);
     }
     RESIDENT_PROF(6);  // publish, wave sum
     // (a wave that gave up leaves the loop alone: the hardware barrier counts only waves that have not ended, and
@@ -2589,6 +2683,27 @@ __global__ void mean_accumulate(const LatticeArgs a, int nrows, float density, d
 #pragma unroll
     for (int j = 0; j < 4; j++) sums[(4 + j) * plane + i] = sums[(4 + j) * plane + i] + prod[j];
   }
+}
+
+// one field frame of a stored lattice (lbm_set_field_frames, per-pass paths): final_state's values of the slab's cells of
+// the window -- columns [wx0, wx0 + wnx), slab rows [wy0, wy0 + wny) -- one thread per cell, the selected planes
+// (bits of `fields`, ascending) into out[F][wny][wnx]
+__global__ void field_frame(const LatticeArgs a, float density, int fields, int wx0, int wy0, int wnx, int wny, float* out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long n = (long)wnx * wny;
+  if (i >= n) return;
+  const int wr = (int)(i / wnx), wc = (int)(i - (long)wr * wnx);
+  const int r = wy0 + wr, x = wx0 + wc;
+  float f[kQ];
+  gather_cell(a, r, x, f);
+  const probe_vec v = probe_sample(f, cell_blocked(a, r, x), density);
+  long at = i;
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    if ((fields >> j) & 1) {
+      out[at] = v[j];
+      at += n;
+    }
 }
 
 // av_velocity() of a stored lattice (SerialCode/d2q9-bgk.c:409-458): per-workgroup partials of

@@ -137,6 +137,32 @@ static void parse_mean(const char* text, int* every, int* from)
   *from = (int)v[1];
 }
 
+/* LBM_STATES=<every>[:<x0>,<y0>,<nx>,<ny>] (the window defaults to the whole grid: nx = 0 here); plain decimal numbers
+   only; dies on anything else */
+static void parse_states(const char* text, int* every, lbm_window* window)
+{
+  const char* s = text;
+  long v[5] = {0, 0, 0, 0, 0};
+  int ok = 1, n = 0;
+  for (; ok && n < 5; n++) {
+    char* end = NULL;
+    ok = (*s >= '0' && *s <= '9');
+    if (!ok) break;
+    v[n] = strtol(s, &end, 10);
+    ok = v[n] <= 2147483647L;
+    s = end;
+    if (*s != (n == 0 ? ':' : ',') || n == 4) { n++; break; }
+    s++;
+  }
+  if (!ok || *s != '\0' || (n != 1 && n != 5) || v[0] < 1 || (n == 5 && (v[3] < 1 || v[4] < 1)))
+    lbm_die("could not read LBM_STATES: expected <every>[:<x0>,<y0>,<nx>,<ny>] with every >= 1, nx >= 1 and ny >= 1", __LINE__, __FILE__);
+  *every = (int)v[0];
+  window->x0 = (int)v[1];
+  window->y0 = (int)v[2];
+  window->nx = (int)v[3];
+  window->ny = (int)v[4];
+}
+
 /* LBM_PRECISION=double: the same program on the double engine (main() :132-205 with every float read as double) */
 static int main_double(const char* paramfile, const char* obstaclefile)
 {
@@ -211,6 +237,12 @@ int main(int argc, char* argv[])
   const char* obstaclefile = argv[2];
 
   const char* env;
+  const char* states_env = getenv("LBM_STATES");
+  int states_every = 0;
+  lbm_window states_window = {0, 0, 0, 0};
+  if (states_env && *states_env) parse_states(states_env, &states_every, &states_window);
+  if (states_every > 0 && (env = getenv("LBM_PRECISION")) && !strcmp(env, "double"))
+    lbm_die("LBM_PRECISION=double and LBM_STATES cannot be combined", __LINE__, __FILE__);
   if ((env = getenv("LBM_PRECISION")) && *env) {
     if (!strcmp(env, "double")) return main_double(paramfile, obstaclefile);
     if (strcmp(env, "single")) lbm_die("could not read LBM_PRECISION: expected single or double", __LINE__, __FILE__);
@@ -250,6 +282,11 @@ int main(int argc, char* argv[])
   if (mean_every > 0 && n_probes > 0) lbm_die("LBM_PROBES and LBM_MEAN cannot be combined", __LINE__, __FILE__);
   if (mean_every > 0 && (env = getenv("LBM_ANIMATION")) && *env && atoi(env) > 0)
     lbm_die("LBM_ANIMATION and LBM_MEAN cannot be combined", __LINE__, __FILE__);
+  if (states_every > 0 && until) lbm_die("LBM_STEADY and LBM_STATES cannot be combined", __LINE__, __FILE__);
+  if (states_every > 0 && n_probes > 0) lbm_die("LBM_PROBES and LBM_STATES cannot be combined", __LINE__, __FILE__);
+  if (states_every > 0 && mean_every > 0) lbm_die("LBM_MEAN and LBM_STATES cannot be combined", __LINE__, __FILE__);
+  if (states_every > 0 && (env = getenv("LBM_ANIMATION")) && *env && atoi(env) > 0)
+    lbm_die("LBM_ANIMATION and LBM_STATES cannot be combined", __LINE__, __FILE__);
 
   /* Total/init time starts here (SerialCode/d2q9-bgk.c:156-159) */
   const double tot_tic = wall_seconds();
@@ -268,7 +305,7 @@ int main(int argc, char* argv[])
     tile_params.ny = tile_ny;
     int* tile = lbm_read_obstacles(obstaclefile, &tile_params);
     ctx = lbm_create_tiled(&params, tile, tile_nx, tile_ny, NULL, n_gpus, math_mode);
-    if (write_text || mean_every > 0) obstacles = lbm_tile_obstacles(tile, tile_nx, tile_ny, params.nx, params.ny);
+    if (write_text || mean_every > 0 || states_every > 0) obstacles = lbm_tile_obstacles(tile, tile_nx, tile_ny, params.nx, params.ny);
     free(tile);
   } else {
     obstacles = lbm_read_obstacles(obstaclefile, &params);
@@ -331,6 +368,42 @@ int main(int argc, char* argv[])
       for (int i = 0; i < n_read; i++) {
         lbm_write_animation_frame("animation_data", params.nx, params.ny, steps[i], frames + (size_t)i * frame_cells);
         printf("Written animation data for timestep %d\n", steps[i]);
+      }
+      t += n;
+    }
+    free(frames);
+    free(steps);
+  } else if (states_every > 0) {
+    /* with field frames: segments whose frames fit 1 GiB of device memory, each drained and written after it */
+    if (states_window.nx == 0) {
+      states_window.nx = params.nx;
+      states_window.ny = params.ny;
+    }
+    const size_t plane_cells = (size_t)states_window.nx * (size_t)states_window.ny, frame_cells = 4 * plane_cells;
+    long cap = (long)((1UL << 30) / (frame_cells * sizeof(float)));
+    const long total_frames = params.max_iters > 0 ? (params.max_iters + states_every - 1) / states_every : 0;
+    if (cap > total_frames) cap = total_frames;
+    if (cap < 1) cap = 1;
+    if (lbm_set_field_frames(ctx, states_every, (int)cap, LBM_FIELD_ALL, &states_window) != LBM_SUCCESS)
+      lbm_die(lbm_last_error(), __LINE__, __FILE__);
+    if (mkdir("state_data", 0777) != 0) {
+      struct stat st;
+      if (stat("state_data", &st) != 0 || !S_ISDIR(st.st_mode)) lbm_die("could not create state_data", __LINE__, __FILE__);
+    }
+    float* frames = (float*)malloc(frame_cells * sizeof(float) * (size_t)cap);
+    int* steps = (int*)malloc(sizeof(int) * (size_t)cap);
+    if (frames == NULL || steps == NULL) lbm_die("cannot allocate memory for field frames", __LINE__, __FILE__);
+    const long seg = cap * (long)states_every;
+    for (long t = 0; t < params.max_iters;) {
+      const int n = (int)((params.max_iters - t < seg) ? params.max_iters - t : seg);
+      if (lbm_run(ctx, n) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+      int n_read = 0;
+      if (lbm_read_field_frames(ctx, (int)cap, frames, steps, &n_read) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+      for (int i = 0; i < n_read; i++) {
+        const float* f = frames + (size_t)i * frame_cells;
+        lbm_write_state_frame("state_data", &params, &states_window, steps[i], f, f + plane_cells, f + 2 * plane_cells,
+                              f + 3 * plane_cells, obstacles);
+        printf("Written state data for timestep %d\n", steps[i]);
       }
       t += n;
     }

@@ -202,6 +202,24 @@ void lbm_write_av_vels(const char* path, const float* av_vels, int n)
   fclose(fp);
 }
 
+void lbm_write_state_frame(const char* dir, const lbm_params* params, const lbm_window* window, int timestep,
+                           const float* u_x, const float* u_y, const float* u_mag, const float* pressure,
+                           const int* obstacles)
+{
+  char filename[4096];
+  snprintf(filename, sizeof(filename), "%s/final_state_%06d.dat", dir, timestep);
+  FILE* fp = fopen(filename, "w");
+  if (fp == NULL) lbm_die("could not open state data file", __LINE__, __FILE__);
+  for (int j = 0; j < window->ny; j++)
+    for (int i = 0; i < window->nx; i++) {
+      const size_t c = (size_t)j * (size_t)window->nx + (size_t)i;
+      const int ii = window->x0 + i, jj = window->y0 + j;
+      fprintf(fp, "%d %d %.12E %.12E %.12E %.12E %d\n", ii, jj, u_x[c], u_y[c], u_mag[c], pressure[c],
+              obstacles[(size_t)jj * (size_t)params->nx + (size_t)ii]);
+    }
+  fclose(fp);
+}
+
 void lbm_write_animation_frame(const char* dir, int nx, int ny, int timestep, const float* u_mag)
 {
   char filename[4096];

@@ -45,6 +45,13 @@ void lbm_write_final_state_rows(FILE* fp, const lbm_params* params, int row_firs
                                 const float* u_x, const float* u_y, const float* u_mag,
                                 const float* pressure, const int* obstacles);
 
+/* <dir>/final_state_%06d.dat (LBM_STATES, no counterpart): final_state.dat's line format for the cells of `window`
+ * (global ii jj, jj outer / ii inner) from the four planes [window->ny][window->nx] of one field frame; `obstacles` is
+ * the whole grid's map */
+void lbm_write_state_frame(const char* dir, const lbm_params* params, const lbm_window* window, int timestep,
+                           const float* u_x, const float* u_y, const float* u_mag, const float* pressure,
+                           const int* obstacles);
+
 /* animation_data/velocity_magnitude_%06d.dat of write_animation_data() (:802-849): "# nx=%d ny=%d timestep=%d",
  * then one "%.6E" line per cell of u_mag[ny*nx] (0 for blocked cells), jj outer / ii inner */
 void lbm_write_animation_frame(const char* dir, int nx, int ny, int timestep, const float* u_mag);
