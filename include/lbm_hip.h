@@ -473,6 +473,56 @@ typedef struct { int x0, y0, nx, ny; } lbm_window;   /* GLOBAL cells [x0, x0+nx)
 int lbm_set_field_frames(lbm_ctx* ctx, int every, int capacity, int fields, const lbm_window* window /* NULL: whole grid */);
 int lbm_read_field_frames(lbm_ctx* ctx, int max_frames, float* out, int* steps, int* n_read);
 
+/* ---- obstacle forces ---------------------------------------------------------------------------
+ * The force the fluid exerts on the obstacles -- drag, lift, the shedding frequency of a flow that oscillates (the
+ * 1024x1024 data set) -- by momentum exchange over the boundary links.  The reference has no counterpart; the definition
+ * rests on its lattice alone.  After a timestep the engine's lattice is bit-identical to the reference's, blocked cells
+ * included: a blocked cell b then holds in speeds[k] the population that arrived over the link from b + c_k and was
+ * turned round by rebound (SerialCode/d2q9-bgk.c, propagate + rebound, :239-301).  That population handed the solid the
+ * momentum (c_opp(k) - c_k) f = -2 c_k f.
+ * A BOUNDARY LINK is a pair (b, k), k in 1..8, with b blocked and b + c_k not blocked, the neighbour taken with both
+ * periodic wraps.  For a set of links L the force of the step that produced the lattice `cells` is
+ *     F_x = sum over (b,k) in L of (double)(-2 cx[k]) * (double)cells[b].speeds[k]
+ *     F_y = sum over (b,k) in L of (double)(-2 cy[k]) * (double)cells[b].speeds[k]
+ * Every term is exact in a double.  The sum is taken EXACTLY, in fixed point (csrc/lbm_exact_sum.h: integer additions of
+ * the floats' mantissas at their places), and rounded to a double once, to nearest-even: the value Python's math.fsum
+ * gives for the same terms.  It therefore has the same bits from run to run and from kernel path to kernel path -- a
+ * single lbm_run, split calls, resident launches, stream launches, 1, 2 or 3 slabs -- which no double sum in a fixed order
+ * can promise across slab counts (a slab's links are summed where the slab lives), and it differs from a double sum of
+ * the same terms in any order by that sum's rounding only.  A population that is not finite makes the force of its body
+ * NaN in that row.
+ * Bodies: body_of_cell is an int[ny*nx] (GLOBAL cells, y * nx + x); entries on fluid cells are ignored, those on blocked
+ * cells must lie in 0 .. n_bodies - 1.  A link belongs to the body of its blocked cell.  NULL: every blocked cell is body
+ * 0 (n_bodies must then be 1 or more; bodies 1.. have no links).  1 <= n_bodies <= LBM_MAX_BODIES.  A body without links
+ * reports 0, 0.
+ * lbm_set_forces(ctx, n_bodies, body_of_cell, every, capacity): from now on, after global timestep tt (0-based, counted
+ *   from the context's creation, the numbering of lbm_set_frames) with tt % every == 0, record one row: for each body
+ *   {double f_x, f_y} of the lattice after tt+1 timesteps.  Rows wait in a device ring of `capacity` rows (capacity *
+ *   n_bodies * 160 bytes per slab: the exact sums, rounded when read); an lbm_run call that would record more rows than are
+ *   free fails before issuing any work.  every == 0 disarms and frees; re-arming discards unread rows.
+ *   At arming each slab builds, on its device and from its uint8 mask (the neighbours of its first and last row are the
+ *   mask's halo rows) and the labels, the list of the boundary links of its blocked cells, ordered by body, then cell
+ *   index, then k: a context made by lbm_create_tiled needs no host map.  No step kernel records forces: every call runs
+ *   as the sub-calls that end at its sample steps, each followed by one force_gather launch per slab on the slab's
+ *   compute stream (every == 1: one-step passes -- correct, not fast).  On resident shapes the sub-calls of at least
+ *   resident_min_steps timesteps run the resident kernel.  Recording never changes the lattice or av_vels: they equal
+ *   those of the same run issued as calls split at the sample steps.
+ *   Works on lbm_create / lbm_create_tiled contexts of any number of slabs; a link belongs to the slab that owns its
+ *   blocked cell, and a row is the sum over the slabs.
+ *   Refused: negative every; capacity < 1; n_bodies outside [1, LBM_MAX_BODIES]; a blocked cell whose body lies outside
+ *   0 .. n_bodies - 1; a ring of 2 GiB or more; rank contexts (lbm_create_rank*); batch members; LBM_HALO_STALE /
+ *   LBM_HALO_FRESHEST (and lbm_set_halo_mode to those while armed); a context with another recorder armed (and the other
+ *   setters while this one is armed); lbm_run_until while armed; a slab of more than 2^29 cells.
+ *   Not offered: accumulation inside the resident or stream kernels, batches, rank contexts, the double engine, torque.
+ * lbm_read_forces: drains up to max_rows oldest rows into out[n][n_bodies][2] (f_x, f_y) and steps[n] (their tt, may be
+ *   NULL); out == NULL && steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers.
+ * lbm_forces_links: links_per_body[b] = boundary links of body b over all slabs, b < n_bodies; fails unless armed.
+ */
+#define LBM_MAX_BODIES 64
+int lbm_set_forces(lbm_ctx* ctx, int n_bodies, const int* body_of_cell /* or NULL */, int every, int capacity);
+int lbm_read_forces(lbm_ctx* ctx, int max_rows, double* out /* [n][n_bodies][2] */, int* steps, int* n_read);
+int lbm_forces_links(lbm_ctx* ctx, int* links_per_body /* [n_bodies] */);
+
 /* ---- steady-state runs ----------------------------------------------------------------------
  * The reference runs a fixed number of timesteps (maxIters, SerialCode/d2q9-bgk.c:166); none of its data sets has
  * stopped changing by then.  lbm_run_until advances the lattice until its average velocity has, with the decision taken

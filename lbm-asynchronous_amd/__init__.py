@@ -49,7 +49,8 @@ ABI_SYMBOLS = (
     "lbm_get_info", "lbm_set_halo_mode", "lbm_read_halo_log", "lbm_run", "lbm_sync", "lbm_run_timed", "lbm_read_av_vels", "lbm_read_cells",
     "lbm_read_final_state", "lbm_av_velocity", "lbm_total_density", "lbm_calc_reynolds",
     "lbm_set_frames", "lbm_read_frames", "lbm_set_probes", "lbm_read_probes", "lbm_set_mean", "lbm_read_mean", "lbm_set_mean_order",
-    "lbm_set_field_frames", "lbm_read_field_frames", "lbm_run_until", "lbm_batch_run_until",
+    "lbm_set_field_frames", "lbm_read_field_frames", "lbm_set_forces", "lbm_read_forces", "lbm_forces_links",
+    "lbm_run_until", "lbm_batch_run_until",
     "lbm_create_batch", "lbm_batch_member", "lbm_batch_run", "lbm_batch_sync", "lbm_batch_get_info", "lbm_destroy_batch",
     "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
     "lbm_double_sync", "lbm_double_read_av_vels", "lbm_double_read_cells", "lbm_double_read_final_state",
@@ -233,6 +234,9 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_read_mean2.argtypes = [P, P, P, P, P, ctypes.POINTER(ctypes.c_longlong)]; lib.lbm_read_mean2.restype = I
     lib.lbm_set_field_frames.argtypes = [P, I, I, I, ctypes.POINTER(_CWindow)]; lib.lbm_set_field_frames.restype = I
     lib.lbm_read_field_frames.argtypes = [P, I, P, P, PI]; lib.lbm_read_field_frames.restype = I
+    lib.lbm_set_forces.argtypes = [P, I, P, I, I]; lib.lbm_set_forces.restype = I
+    lib.lbm_read_forces.argtypes = [P, I, P, P, PI]; lib.lbm_read_forces.restype = I
+    lib.lbm_forces_links.argtypes = [P, P]; lib.lbm_forces_links.restype = I
     lib.lbm_run_until.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CSteadyResult)]
     lib.lbm_run_until.restype = I
     lib.lbm_batch_run_until.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CSteadyResult), PI]
@@ -624,6 +628,37 @@ class Engine:
             _check(self.lib, self.lib.lbm_read_field_frames(self.handle, int(max_frames), out.ctypes.data, steps.ctypes.data,
                                                             ctypes.byref(n)))
         return steps[:n.value].copy(), {k: out[:n.value, j].copy() for j, k in enumerate(names)}
+
+    # -- obstacle forces (lbm_set_forces / lbm_read_forces / lbm_forces_links) ---------------------
+    def set_forces(self, every: int, capacity: int = 4096, bodies=None, n_bodies: int | None = None) -> None:
+        """Record the force of the fluid on the obstacles -- the momentum exchanged over the boundary links, summed
+        exactly and rounded once -- after every global timestep tt with tt % every == 0, for the lattice after tt + 1
+        steps, into a device ring of `capacity` rows.  `bodies`: None (all blocked cells are body 0) or an integer array
+        of the grid's shape (ny, nx) with the body of every blocked cell in 0 .. n_bodies - 1 (entries on fluid cells are
+        ignored); n_bodies defaults to the largest label + 1.  every == 0 disarms; re-arming discards unread rows."""
+        every, capacity, n_bodies, labels = _forces_args(every, capacity, bodies, n_bodies, self.params.nx, self.params.ny)
+        _check(self.lib, self.lib.lbm_set_forces(self.handle, n_bodies, labels.ctypes.data if labels is not None else None,
+                                                 every, capacity))
+        self._n_bodies = n_bodies if every > 0 else 0
+
+    def forces(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], float64[n, n_bodies, 2]),
+        columns F_x, F_y."""
+        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
+            raise LbmError(f"forces: max_rows must be a non-negative integer or None (got {max_rows!r})")
+        n = ctypes.c_int()
+        _check(self.lib, self.lib.lbm_read_forces(self.handle, 0, None, None, ctypes.byref(n)))  # rows waiting
+        max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
+        rows = np.empty((int(max_rows), getattr(self, "_n_bodies", 0), 2), dtype=np.float64)
+        steps = np.empty(int(max_rows), dtype=np.int32)
+        _check(self.lib, self.lib.lbm_read_forces(self.handle, int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
+        return steps[:n.value].copy(), rows[:n.value].copy()
+
+    def force_links(self) -> np.ndarray:
+        """Boundary links of every body of the armed forces, int32[n_bodies] (lbm_forces_links)."""
+        out = np.zeros(max(1, getattr(self, "_n_bodies", 0)), dtype=np.int32)
+        _check(self.lib, self.lib.lbm_forces_links(self.handle, out.ctypes.data))
+        return out[:getattr(self, "_n_bodies", 0)].copy()
 
     # -- results -----------------------------------------------------------------------------
     def av_vels(self, n: int | None = None) -> np.ndarray:
@@ -1046,6 +1081,55 @@ def _probe_args(cells, every, capacity) -> tuple[list, int, int]:
     if flat and every > 0 and capacity < 1:
         raise LbmError(f"set_probes: capacity {capacity}, at least one row of samples is needed")
     return flat, int(every), int(capacity)
+
+
+LBM_MAX_BODIES = 64
+
+
+def _forces_args(every, capacity, bodies, n_bodies, nx, ny) -> tuple[int, int, int, np.ndarray | None]:
+    """Engine.set_forces' argument checks (no device needed): (every, capacity, n_bodies, int32 labels [ny*nx] or None).
+    Whether a blocked cell's label lies outside 0 .. n_bodies - 1 is the engine's check: it holds the obstacle mask."""
+    for name, v in (("every", every), ("capacity", capacity)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise LbmError(f"set_forces: {name} must be an integer (got {v!r})")
+        if not 0 <= int(v) <= 2147483647:
+            raise LbmError(f"set_forces: {name} must lie in [0, 2^31) (got {v})")
+    if every > 0 and capacity < 1:
+        raise LbmError(f"set_forces: capacity {capacity}, at least one row is needed")
+    labels = None
+    if bodies is not None:
+        try:
+            labels = np.asarray(bodies)
+        except (TypeError, ValueError):
+            raise LbmError(f"set_forces: bodies must be an integer array of shape ({ny}, {nx}) (got {bodies!r})"[:300]) from None
+        if labels.dtype.kind not in "iu" or labels.size != nx * ny or labels.shape not in ((ny, nx), (ny * nx,)):
+            raise LbmError(f"set_forces: bodies must be an integer array of shape ({ny}, {nx}) (got {bodies!r})"[:300])
+        if labels.size and (labels.min() < -2147483648 or labels.max() > 2147483647):
+            raise LbmError("set_forces: body labels must fit 32 bits")
+        labels = np.ascontiguousarray(labels.reshape(-1), dtype=np.int32)
+    if n_bodies is None:
+        n_bodies = 1 if labels is None or labels.size == 0 else max(1, int(labels.max()) + 1)
+    if isinstance(n_bodies, bool) or not isinstance(n_bodies, (int, np.integer)):
+        raise LbmError(f"set_forces: n_bodies must be an integer (got {n_bodies!r})")
+    if every > 0 and not 1 <= int(n_bodies) <= LBM_MAX_BODIES:
+        raise LbmError(f"set_forces: {int(n_bodies)} bodies, between 1 and LBM_MAX_BODIES = {LBM_MAX_BODIES} are possible")
+    return int(every), int(capacity), int(n_bodies), labels
+
+
+def write_forces(path: str, steps, rows) -> None:
+    """forces.dat of the command line (LBM_FORCES): '%d:\t%.12E\t%.12E\n' = tt, F_x, F_y, one line per sample, the forces
+    summed over the bodies in body order; `steps` int[n], `rows` float64 [n, n_bodies, 2] (Engine.forces)."""
+    rows = np.asarray(rows, dtype=np.float64)
+    steps = np.asarray(steps).ravel()
+    if rows.ndim != 3 or rows.shape[2] != 2 or rows.shape[0] != steps.size:
+        raise LbmError(f"write_forces: rows must be [{steps.size}, n_bodies, 2] (got shape {rows.shape})")
+    with open(path, "w") as fh:
+        for tt, row in zip(steps.tolist(), rows):
+            fx = fy = 0.0
+            for b in range(row.shape[0]):
+                fx += float(row[b, 0])
+                fy += float(row[b, 1])
+            fh.write("%d:\t%.12E\t%.12E\n" % (tt, fx, fy))
 
 
 def _mean_args(every) -> int:

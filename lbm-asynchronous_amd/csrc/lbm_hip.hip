@@ -250,6 +250,10 @@ struct Slab {
                                            // lbm_set_mean_order(.., 2): eight, then u_x u_x, u_y u_y, u_x u_y, pressure pressure
   DeviceBuf<float> field_ring;             // lbm_set_field_frames: [slots][F][field_ny][window nx], this slab's rows of the window
   int field_y0 = 0, field_ny = 0;          // ... those rows: slab rows [field_y0, field_y0 + field_ny); none: no ring
+  DeviceBuf<unsigned> force_links;         // lbm_set_forces: the boundary links of the owned blocked cells, by body, cell, k ...
+  DeviceBuf<unsigned> force_starts;        // ... [bodies + 1]: where each body's links start
+  DeviceBuf<long long> force_ring;         // ... [slots][bodies][lbm::kForceWords]: this slab's exact sums (lbm_exact_sum.h)
+  int force_groups = 0;                    // workgroups per body of force_gather (0: the slab has no links)
   // freshest-available mode (LBM_HALO_FRESHEST), allocated at its first use in this order: whole once ev_fresh[1] exists
   DeviceBuf<float> fresh_stage;          // [parity][side: 0 south halo, 1 north halo][row_pitch]: this pass's rows, if they make it
   DeviceBuf<unsigned> fresh_arrived;     // [parity][side]: id (global step + 1) of the step whose row the staging holds
@@ -397,8 +401,10 @@ struct GraphBuilder {
 // (tt / every - ord0) % slots of every slab's buffer of that kind.  The mean fields (lbm_set_mean) are the kind without
 // slots: their record is added to per-cell sums, `written` counts the samples, `read`, `slots` and `ord0` stay unused.
 // Field frames (lbm_set_field_frames) are slotted like the frames: chosen fields over a window instead of |u| everywhere.
+// Obstacle forces (lbm_set_forces) are slotted like the probes: a row of per-body sums over the boundary links.  The one
+// kind no kernel form records: every call runs as the sub-calls that end at its sample steps, each followed by force_gather.
 enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean,
-       kRecFields = lbm::kRecFields, kRecKinds = 5 };
+       kRecFields = lbm::kRecFields, kRecForces = 5, kRecKinds = 6 };
 struct Recorder {
   int kind = kRecNone;
   int every = 0;
@@ -429,7 +435,9 @@ constexpr RecorderKind kRecorderKinds[kRecKinds] = {
     {.name = "mean fields", .noun = "mean fields", .record = "sample", .setter = "lbm_set_mean",
      .reader = "lbm_read_mean", .disarm = "lbm_set_mean(ctx, 0)", .slotted = false},
     {.name = "field frames", .noun = "field frames", .record = "field frame", .setter = "lbm_set_field_frames",
-     .reader = "lbm_read_field_frames", .disarm = "lbm_set_field_frames(ctx, 0, 0, 0, NULL)"}};
+     .reader = "lbm_read_field_frames", .disarm = "lbm_set_field_frames(ctx, 0, 0, 0, NULL)"},
+    {.name = "obstacle forces", .noun = "forces", .record = "row", .setter = "lbm_set_forces",
+     .reader = "lbm_read_forces", .disarm = "lbm_set_forces(ctx, 0, NULL, 0, 0)"}};
 
 struct lbm_ctx {
   lbm_params p;
@@ -461,6 +469,7 @@ struct lbm_ctx {
   Recorder rec;                     // the one recorder: animation frames (lbm_set_frames), point probes (lbm_set_probes) or
                                     // mean fields (lbm_set_mean) or field frames (lbm_set_field_frames)
   std::vector<lbm_probe> probe_cells;  // the probed global cells, in the caller's order (a probes row has that many samples)
+  std::vector<int> force_link_counts;  // lbm_set_forces: boundary links of each body, all slabs (a forces row has that many bodies)
   // steady-state runs (lbm_run_until), allocated by the first such call in this order: whole once ev_steady[1] exists
   DeviceBuf<lbm::SteadyState> steady_state;  // device: what the checks of the current call have found
   PinnedBuf<int> steady_stop_host;  // pinned: its stop word after segment j, in slot j & 1 ...
@@ -487,7 +496,7 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentProbes> probe_table;  // device: [members], allocated when the first member arms probes
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
   DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
-  int armed[kRecKinds] = {0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
+  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
                                     // (a batch records one kind, so at most one count is non-zero)
   // steady-state runs (lbm_batch_run_until), allocated by the first such call; steady_state last: the set is whole once it exists
   DeviceBuf<lbm::SteadyMember> steady_members; // device: [members]
@@ -1310,9 +1319,9 @@ const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = f
   using Form = const void* (*)(int);
   static const Form forms[2][kRecKinds] = {
       {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>, resident_form<false, kRecMean>,
-       resident_form<false, kRecFields>},
+       resident_form<false, kRecFields>, resident_form<false, kRecNone>},  // (the forces run the plain form)
       {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>, resident_form<true, kRecMean>,
-       resident_form<true, kRecFields>}};
+       resident_form<true, kRecFields>, resident_form<true, kRecNone>}};
   return forms[batch][rec]((rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
 }
 
@@ -1522,6 +1531,14 @@ int take_record(lbm_ctx* c) {
             hipLaunchKernelGGL(lbm::field_frame, dim3(ceil_div(cells, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), c->p.density,
                                c->rec.fields, w.x0, sl.field_y0, w.nx, sl.field_ny,
                                sl.field_ring + slot * (size_t)__builtin_popcount((unsigned)c->rec.fields) * (size_t)cells);
+        } else if (c->rec.kind == kRecForces) {
+          // the row starts from zeros (force_gather adds into it); a slab without links records them
+          const size_t words = c->force_link_counts.size() * (size_t)lbm::kForceWords;
+          long long* row = sl.force_ring + slot * words;
+          HIP_TRY(LBM_FAILURE, hipMemsetAsync(row, 0, words * sizeof(long long), sl.compute));
+          if (sl.force_groups > 0)
+            hipLaunchKernelGGL(lbm::force_gather, dim3(sl.force_groups, (unsigned)c->force_link_counts.size()), dim3(lbm::kBlock), 0,
+                               sl.compute, lattice_args(c, sl), (const unsigned*)sl.force_links, (const unsigned*)sl.force_starts, row);
         } else if (c->rec.kind == kRecMean)
           hipLaunchKernelGGL(lbm::mean_accumulate, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              c->p.density, sl.mean_sums, n, c->rec.order);
@@ -1560,7 +1577,7 @@ int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
     const long long records = recorded_between(c->rec, c->steps_done, (long long)c->steps_done + n_steps);
     if (run_resident(c, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
     c->steps_done += n_steps;
-    c->rec.written += records;  // recorded by the kernel itself
+    if (c->rec.kind != kRecForces) c->rec.written += records;  // recorded by the kernel itself (forces: by the caller, behind it)
     return LBM_SUCCESS;
   }
 
@@ -1617,15 +1634,18 @@ int run_steps(lbm_ctx* c, int n_steps, float* kernel_ms) {
 
   // resident or per-pass: decided once per call, whether a recorder (frames or probes) is armed or not
   const bool resident = c->plan.resident && n_steps >= c->plan.resident_min_steps;
-  if (c->rec.kind != kRecNone && !resident) {
+  const bool forces = (c->rec.kind == kRecForces);
+  if (c->rec.kind != kRecNone && (!resident || forces)) {
     // per-pass kernels: the call runs as the sub-calls that end at its recorder steps, each followed by its frame or
-    // its sample row (the step kernels themselves record nothing)
+    // its sample row (the step kernels themselves record nothing).  The forces always run so, whatever kernels advance
+    // the lattice: a sub-call long enough for the resident kernel runs it (its plain form), as a call of that length would
     const int e = c->rec.every;
     for (int t = 0; t < n_steps;) {
       const int tt = c->steps_done, r = tt % e;
       const long long rec_tt = r ? (long long)tt + (e - r) : tt;  // next recorder step
       const int seg = (rec_tt - tt + 1 < n_steps - t) ? (int)(rec_tt - tt + 1) : n_steps - t;
-      if (run_passes(c, seg, false, kernel_ms && t == 0) != LBM_SUCCESS) return LBM_FAILURE;
+      const bool seg_resident = forces && c->plan.resident && seg >= c->plan.resident_min_steps;
+      if (run_passes(c, seg, seg_resident, kernel_ms && t == 0) != LBM_SUCCESS) return LBM_FAILURE;
       if (c->steps_done - 1 == rec_tt && take_record(c) != LBM_SUCCESS) return LBM_FAILURE;
       t += seg;
     }
@@ -2249,9 +2269,14 @@ void release_recorder(lbm_ctx* c) {
     sl.mean_sums.reset();
     sl.field_ring.reset();
     sl.field_y0 = sl.field_ny = 0;
+    sl.force_links.reset();
+    sl.force_starts.reset();
+    sl.force_ring.reset();
+    sl.force_groups = 0;
     sl.probe_count = 0;
   }
   c->probe_cells.clear();
+  c->force_link_counts.clear();
   c->rec = Recorder{};
 }
 
@@ -2279,7 +2304,7 @@ int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate alloc
         LBM_FAIL(LBM_FAILURE, "%s: a member of this batch has %s armed (%s); a batch records one kind: frames, probes, mean fields or field frames",
                  setter, o.name, o.setter);
     }
-    if (c->plan.resident) {
+    if (c->plan.resident && kind != kRecForces) {  // (the forces record behind the plain form, which every resident shape runs)
       // the recorder forms of four-row bands defer the acceleration of the interior pair only (lbm::resident_band): the lid
       // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form must run one workgroup per CU
       if (c->plan.resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
@@ -2805,6 +2830,145 @@ int lbm_read_field_frames(lbm_ctx* c, int max_frames, float* out, int* steps, in
     }
     return LBM_SUCCESS;
   });
+}
+
+int lbm_set_forces(lbm_ctx* c, int n_bodies, const int* body_of_cell, int every, int capacity) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_forces: null context");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_forces: negative interval %d", every);
+  // the labels of every slab's owned cells as bytes (255: outside 0 .. n_bodies - 1), on its device while the lists are built
+  std::vector<DeviceBuf<unsigned char>> labels((size_t)(every > 0 && body_of_cell ? c->n_slabs : 0));
+  if (every > 0) {
+    if (n_bodies < 1 || n_bodies > LBM_MAX_BODIES)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_forces: %d bodies, between 1 and LBM_MAX_BODIES = %d are possible", n_bodies, LBM_MAX_BODIES);
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_forces: capacity %d, at least one row is needed", capacity);
+    if ((long long)capacity * n_bodies * lbm::kForceWords * (long long)sizeof(long long) >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_set_forces: a ring of %d rows of %d bodies is 2 GiB or more (%d bytes per body and row)", capacity, n_bodies,
+               lbm::kForceWords * (int)sizeof(long long));
+    if (c->ranked || c->world > 1)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_forces: not available in a multi-process (rank) context: a body's links would be spread over the ranks");
+    if (c->batch)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_forces: not available on a member of a batch (lbm_create_batch): the batched launches have no sample steps to end at");
+    for (int s = 0; s < c->n_slabs; s++)
+      if ((long)c->slab[s].rows * c->p.nx > (1L << 29))
+        LBM_FAIL(LBM_FAILURE, "lbm_set_forces: a slab of %d x %d cells; a link is cell * 8 + k - 1 in 32 bits (at most 2^29 cells per slab)",
+                 c->p.nx, c->slab[s].rows);
+    for (size_t s = 0; s < labels.size(); s++) {
+      Slab& sl = c->slab[s];
+      const size_t n = (size_t)sl.rows * c->p.nx;
+      const int* src = body_of_cell + (size_t)(sl.row_first - c->row_first) * c->p.nx;
+      std::vector<unsigned char> bytes(n);
+      for (size_t i = 0; i < n; i++) bytes[i] = (src[i] < 0 || src[i] >= n_bodies) ? 255 : (unsigned char)src[i];
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      DeviceBuf<unsigned> bad;
+      const unsigned none = ~0u;
+      unsigned first_bad = none;
+      HIP_TRY(LBM_FAILURE, labels[s].alloc(n));
+      HIP_TRY(LBM_FAILURE, bad.alloc(1));
+      HIP_TRY(LBM_FAILURE, hipMemcpy(labels[s], bytes.data(), n, hipMemcpyHostToDevice));
+      HIP_TRY(LBM_FAILURE, hipMemcpy(bad, &none, sizeof(none), hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(lbm::label_check, dim3(ceil_div((long)n, 256)), dim3(256), 0, sl.compute, (const unsigned char*)sl.mask, c->pitch,
+                         c->p.nx, (const unsigned char*)labels[s], (long)n, bad.get());
+      HIP_TRY(LBM_FAILURE, hipGetLastError());
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(&first_bad, bad, sizeof(first_bad), hipMemcpyDeviceToHost, sl.compute));
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+      if (first_bad != none)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_forces: the blocked cell (%d, %d) has body %d, outside 0 .. %d", (int)(first_bad % (unsigned)c->p.nx),
+                 sl.row_first + (int)(first_bad / (unsigned)c->p.nx), src[first_bad], n_bodies - 1);
+    }
+  }
+  return rearm_recorder(c, kRecForces, every, capacity, [&]() -> int {
+    c->force_link_counts.assign((size_t)n_bodies, 0);
+    const size_t ring_bytes = (size_t)capacity * (size_t)n_bodies * lbm::kForceWords * sizeof(long long);
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      const long n = (long)sl.rows * c->p.nx;
+      const unsigned char* lab = labels.empty() ? nullptr : labels[s].get();
+      // the list: links per (body, workgroup of cells), their prefix sums, then the links themselves at those offsets
+      const int wgs = ceil_div(n, lbm::kLinkCells);
+      const long m = (long)wgs * n_bodies;
+      DeviceBuf<unsigned> counts;
+      DeviceBuf<unsigned long long> total_dev;
+      unsigned long long total = 0;
+      std::vector<unsigned> starts((size_t)n_bodies + 1);
+      if (counts.alloc((size_t)m) != hipSuccess || total_dev.alloc(1) != hipSuccess || sl.force_starts.alloc(starts.size()) != hipSuccess ||
+          sl.force_ring.alloc_bytes(ring_bytes) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_forces: cannot allocate %d rows of %d bodies (%.1f MiB per slab) and the link counts (%.1f MiB); forces stay off",
+                 capacity, n_bodies, (double)ring_bytes / 1048576.0, (double)m * sizeof(unsigned) / 1048576.0);
+      hipLaunchKernelGGL(lbm::link_count, dim3(wgs, n_bodies), dim3(lbm::kBlock), 0, sl.compute, (const unsigned char*)sl.mask, c->pitch,
+                         c->p.nx, lab, n, counts.get());
+      hipLaunchKernelGGL(lbm::link_scan, dim3(1), dim3(lbm::kBlock), 0, sl.compute, counts.get(), m, (long)wgs, sl.force_starts.get(),
+                         total_dev.get());
+      HIP_TRY(LBM_FAILURE, hipGetLastError());
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(&total, total_dev, sizeof(total), hipMemcpyDeviceToHost, sl.compute));
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(starts.data(), sl.force_starts, starts.size() * sizeof(unsigned), hipMemcpyDeviceToHost, sl.compute));
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+      if (total > 0x7fffffffull)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_forces: %llu boundary links in one slab, at most 2^31 - 1 are possible", total);
+      if (sl.force_links.alloc((size_t)(total ? total : 1)) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_forces: cannot allocate the list of %llu boundary links (%.1f MiB); forces stay off", total,
+                 (double)total * sizeof(unsigned) / 1048576.0);
+      if (total > 0) {
+        hipLaunchKernelGGL(lbm::link_fill, dim3(wgs, n_bodies), dim3(lbm::kBlock), 0, sl.compute, (const unsigned char*)sl.mask, c->pitch,
+                           c->p.nx, lab, n, (const unsigned*)counts.get(), sl.force_links.get(), (unsigned)total);
+        HIP_TRY(LBM_FAILURE, hipGetLastError());
+      }
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));  // counts and the labels are freed on return
+      unsigned most = 0;
+      for (int b = 0; b < n_bodies; b++) {
+        const unsigned links = starts[(size_t)b + 1] - starts[(size_t)b];
+        c->force_link_counts[(size_t)b] += (int)links;
+        if (links > most) most = links;
+      }
+      // four links per lane where there are that many, at most 256 workgroups per body
+      const int groups = ceil_div((long)most, 4 * lbm::kBlock);
+      sl.force_groups = most == 0 ? 0 : (groups > 256 ? 256 : groups);
+    }
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_read_forces(lbm_ctx* c, int max_rows, double* out, int* steps, int* n_read) {
+  return drain_recorder(c, kRecForces, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
+    constexpr int L = lbm_exact::kExactLimbs;
+    const size_t bodies = c->force_link_counts.size(), words = bodies * (size_t)lbm::kForceWords;
+    const size_t slots = (size_t)c->rec.slots;
+    // every slab's words of the n rows (they wait in at most two runs of its ring), added word by word -- integers: the
+    // order of the slabs does not matter -- then each body's two sums rounded once and doubled (-2 c_k f)
+    std::vector<long long> sum((size_t)n * words, 0), stage((size_t)n * words);
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      for (int i = 0; i < n;) {
+        const size_t slot = (size_t)((c->rec.read + i) % c->rec.slots);
+        const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
+        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, sl.force_ring + slot * words, (size_t)run * words * sizeof(long long),
+                                            hipMemcpyDeviceToHost, sl.compute));
+        i += run;
+      }
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+      for (size_t j = 0; j < sum.size(); j++) sum[j] += stage[j];
+    }
+    for (size_t j = 0; j < (size_t)n * bodies; j++) {
+      const long long* w = sum.data() + j * lbm::kForceWords;
+      long long fx[L], fy[L];
+      for (int i = 0; i < L; i++) {
+        fx[i] = w[i];
+        fy[i] = w[L + i];
+      }
+      const bool finite = (w[2 * L] == 0);  // a population that is not finite makes the body's force of that row NaN
+      out[2 * j] = finite ? 2.0 * lbm_exact::exact_sum_round(fx) : std::nan("");
+      out[2 * j + 1] = finite ? 2.0 * lbm_exact::exact_sum_round(fy) : std::nan("");
+    }
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_forces_links(lbm_ctx* c, int* links_per_body) {
+  if (!c || !links_per_body) LBM_FAIL(LBM_FAILURE, "lbm_forces_links: NULL argument");
+  if (c->rec.kind != kRecForces) LBM_FAIL(LBM_FAILURE, "lbm_forces_links: the obstacle forces are not armed (lbm_set_forces)");
+  for (size_t b = 0; b < c->force_link_counts.size(); b++) links_per_body[b] = c->force_link_counts[b];
+  return LBM_SUCCESS;
 }
 
 // the planes [first, first + 4) of every slab's sums, stitched by row_first; lbm_read_mean and lbm_read_mean2

@@ -34,6 +34,8 @@
 #include <tuple>
 #include <type_traits>
 
+#include "lbm_exact_sum.h"
+
 namespace lbm {
 
 constexpr int kBlock = 256;  // 4 waves of 64
@@ -41,6 +43,7 @@ constexpr int kQ = 9;
 constexpr int kNoRow = -1000000;  // "no such row in this slab"
 // what a context records while it runs, at most one at a time: the host's Recorder::kind and resident_band's REC
 constexpr int kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3, kRecFields = 4;
+// (the obstacle forces, lbm_set_forces, are a recorder kind of the host alone: force_gather runs behind the step kernels)
 
 // 1/3 rounded to fp32, and the two constant divisors of the equilibrium, folded in fp32
 // exactly as the reference's "2.f * c_sq" and "2.f * c_sq * c_sq" (SerialCode/d2q9-bgk.c:308,367-370)
@@ -2733,6 +2736,183 @@ __global__ __launch_bounds__(kBlock) void lattice_sums(const LatticeArgs a, int 
   if (threadIdx.x == 0) {
     speed_part[blockIdx.x] = sh_s[0];
     mass_part[blockIdx.x] = sh_m[0];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// obstacle forces (lbm_set_forces): the boundary links of a slab, and the momentum they handed over
+// ---------------------------------------------------------------------------------------------
+// A boundary link is (b, k), k in 1..8, with b blocked and b + c_k (both periodic wraps) not.  After a timestep
+// speeds[k] of b holds what arrived over that link and was turned round (SerialCode/d2q9-bgk.c, propagate + rebound):
+// the solid received -2 c_k f.  The list of a slab holds the links of its owned blocked cells as cell * 8 + (k - 1),
+// cell = row * nx + x slab-local, ordered by body, then cell, then k; starts[body] .. starts[body + 1] are a body's.
+// It is built once at arming, in three launches over (kLinkCells cells per workgroup) x (bodies): link_count, link_scan,
+// link_fill.  The neighbour rows of the slab's first and last row are the mask's halo rows.
+constexpr int kLinkCells = 4 * kBlock;  // cells per workgroup of link_count / link_fill: four consecutive cells per lane
+constexpr int kForceWords = 20;         // int64 words of a body in a ring row: F_x limbs 0..8, F_y limbs 9..17, 18 = terms
+                                        // that were not finite, 19 unused
+static_assert(2 * lbm_exact::kExactLimbs + 1 < kForceWords, "a body's words hold both accumulators and the count");
+
+// c_k of the reference's numbering (SerialCode/d2q9-bgk.c:224-232): 1 E, 2 N, 3 W, 4 S, 5 NE, 6 NW, 7 SW, 8 SE
+__device__ __forceinline__ int link_cx(int k) { return (int)((0x122u >> k) & 1u) - (int)((0x0c8u >> k) & 1u); }
+__device__ __forceinline__ int link_cy(int k) { return (int)((0x064u >> k) & 1u) - (int)((0x190u >> k) & 1u); }
+
+// bit k - 1 set: (cell, k) is a boundary link of body `body` (labels == nullptr: every blocked cell is body 0)
+__device__ __forceinline__ unsigned link_bits(const unsigned char* mask, int pitch, int nx, const unsigned char* labels, int body,
+                                              long cell) {
+  const int row = (int)(cell / nx), x = (int)(cell - (long)row * nx);
+  if (mask[(long)row * pitch + x] == 0) return 0u;
+  if ((labels ? (int)labels[cell] : 0) != body) return 0u;
+  unsigned bits = 0u;
+#pragma unroll
+  for (int k = 1; k < kQ; k++) {
+    int xn = x + link_cx(k);
+    xn = (xn < 0) ? nx - 1 : (xn == nx ? 0 : xn);
+    if (mask[(long)(row + link_cy(k)) * pitch + xn] == 0) bits |= 1u << (k - 1);
+  }
+  return bits;
+}
+
+// *bad = the lowest owned cell that is blocked and labelled 255 (the host's mark for "outside 0 .. n_bodies - 1")
+__global__ void label_check(const unsigned char* mask, int pitch, int nx, const unsigned char* labels, long n, unsigned* bad) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int row = (int)(i / nx), x = (int)(i - (long)row * nx);
+  if (mask[(long)row * pitch + x] != 0 && labels[i] == 255) atomicMin(bad, (unsigned)i);
+}
+
+// the links of a lane's four cells; n = owned cells of the slab
+__device__ __forceinline__ void lane_links(const unsigned char* mask, int pitch, int nx, const unsigned char* labels, long n,
+                                           unsigned (&bits)[4], int& count) {
+  const long cell0 = (long)blockIdx.x * kLinkCells + (long)threadIdx.x * 4;
+  count = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    bits[i] = (cell0 + i < n) ? link_bits(mask, pitch, nx, labels, (int)blockIdx.y, cell0 + i) : 0u;
+    count += __builtin_popcount(bits[i]);
+  }
+}
+
+// the workgroup's exclusive prefix of v in lane order and its total (kBlock lanes; sh: one word per wave + 1)
+__device__ __forceinline__ unsigned block_exclusive(unsigned v, unsigned* sh, unsigned& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+  unsigned inc = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned up = __shfl_up(inc, off, 64);
+    if (lane >= off) inc += up;
+  }
+  if (lane == 63) sh[wave] = inc;
+  __syncthreads();
+  unsigned before = 0u, all = 0u;
+  for (int w = 0; w < waves; w++) {
+    const unsigned t = sh[w];
+    if (w < wave) before += t;
+    all += t;
+  }
+  __syncthreads();  // sh may be reused
+  total = all;
+  return before + inc - v;
+}
+
+// counts[body * gridDim.x + workgroup] = links of that body among the workgroup's cells
+__global__ __launch_bounds__(kBlock) void link_count(const unsigned char* mask, int pitch, int nx, const unsigned char* labels, long n,
+                                                     unsigned* counts) {
+  __shared__ unsigned sh[kBlock / 64];
+  unsigned bits[4];
+  int count;
+  lane_links(mask, pitch, nx, labels, n, bits, count);
+  unsigned total;
+  (void)block_exclusive((unsigned)count, sh, total);
+  if (threadIdx.x == 0) counts[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
+}
+
+// one workgroup: counts[0 .. m) become their exclusive prefix sums (in place), starts[b] the prefix at b * per_body
+// (b < m / per_body), starts[m / per_body] and *total the sum of all
+__global__ __launch_bounds__(kBlock) void link_scan(unsigned* counts, long m, long per_body, unsigned* starts, unsigned long long* total) {
+  __shared__ unsigned sh[kBlock / 64];
+  unsigned long long carry = 0ull;
+  for (long base = 0; base < m; base += kBlock) {
+    const long i = base + threadIdx.x;
+    const unsigned v = (i < m) ? counts[i] : 0u;
+    unsigned chunk;
+    const unsigned ex = block_exclusive(v, sh, chunk);
+    if (i < m) {
+      const unsigned at = (unsigned)carry + ex;
+      counts[i] = at;
+      if (i % per_body == 0) starts[i / per_body] = at;
+    }
+    carry += chunk;
+  }
+  if (threadIdx.x == 0) {
+    starts[m / per_body] = (unsigned)carry;
+    *total = carry;
+  }
+}
+
+// links[offsets[body * gridDim.x + workgroup] ...] = the workgroup's links of that body, by cell, then k
+__global__ __launch_bounds__(kBlock) void link_fill(const unsigned char* mask, int pitch, int nx, const unsigned char* labels, long n,
+                                                    const unsigned* offsets, unsigned* links, unsigned n_links) {
+  __shared__ unsigned sh[kBlock / 64];
+  unsigned bits[4];
+  int count;
+  lane_links(mask, pitch, nx, labels, n, bits, count);
+  unsigned total;
+  unsigned at = offsets[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + block_exclusive((unsigned)count, sh, total);
+  const long cell0 = (long)blockIdx.x * kLinkCells + (long)threadIdx.x * 4;
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+    for (unsigned b = bits[i]; b != 0u; b &= b - 1u) {
+      if (at < n_links) links[at] = (unsigned)(cell0 + i) * 8u + (unsigned)__builtin_ctz(b);
+      at++;
+    }
+}
+
+// One sample of the forces on a stored lattice (per-pass and resident paths alike: launched behind the sub-call that
+// ends at the sample step).  Workgroup (g, body): its lanes walk the body's links g * kBlock + lane, + gridDim.x * kBlock,
+// ..., each adding -c_k f -- exactly, see lbm_exact_sum.h -- to its own pair of fixed-point accumulators; the pairs are
+// added across the wave by shuffles, across the workgroup's waves through LDS, and across workgroups by 64-bit INTEGER
+// atomics into the body's words of the ring row (zeroed by the host before the launch).  Every one of these additions
+// is exact and commutes, so the row does not depend on scheduling; no floating-point addition happens on the device.
+// The host rounds the sum once and doubles it (lbm_read_forces).
+__global__ __launch_bounds__(kBlock) void force_gather(const LatticeArgs a, const unsigned* links, const unsigned* starts, long long* row) {
+  constexpr int L = lbm_exact::kExactLimbs;
+  __shared__ long long sh[kBlock / 64][2 * L + 1];
+  const int body = blockIdx.y;
+  const unsigned first = starts[body], end = starts[body + 1];
+  if (first + (unsigned)blockIdx.x * kBlock >= end) return;  // (workgroup-uniform) nothing to add: the row keeps its zeros
+  long long fx[L], fy[L], bad = 0;
+#pragma unroll
+  for (int i = 0; i < L; i++) fx[i] = fy[i] = 0;
+  for (unsigned i = first + (unsigned)blockIdx.x * kBlock + threadIdx.x; i < end; i += gridDim.x * kBlock) {
+    const unsigned e = links[i];
+    const int k = (int)(e & 7u) + 1;
+    const long cell = (long)(e >> 3);
+    const int r = (int)(cell / a.nx), x = (int)(cell - (long)r * a.nx);
+    const unsigned bits = __float_as_uint(a.src[k * a.plane_stride + (long)r * a.row_pitch + x]);
+    if (lbm_exact::exact_sum_finite(bits)) {
+      lbm_exact::exact_sum_add(fx, bits, -link_cx(k));
+      lbm_exact::exact_sum_add(fy, bits, -link_cy(k));
+    } else {
+      bad++;
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  auto wave_total = [&](long long v, int word) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) sh[wave][word] = v;
+  };
+#pragma unroll
+  for (int i = 0; i < L; i++) {
+    wave_total(fx[i], i);
+    wave_total(fy[i], L + i);
+  }
+  wave_total(bad, 2 * L);
+  __syncthreads();
+  if (threadIdx.x < 2 * L + 1) {
+    long long v = 0;
+    for (int w = 0; w < kBlock / 64; w++) v += sh[w][threadIdx.x];
+    if (v != 0) atomicAdd(reinterpret_cast<unsigned long long*>(row + (size_t)body * kForceWords + threadIdx.x), (unsigned long long)v);
   }
 }
 

@@ -42,6 +42,11 @@
  *                         -- what the reference's golden files were computed in.  One GPU, plain runs only: dies together
  *                         with LBM_GPUS > 1, LBM_MATH=fast, LBM_TILE, LBM_ANIMATION, LBM_STEADY, LBM_PROBES, LBM_MEAN or
  *                         LBM_PRESSURE_BIN.  Unset or "single": everything above, unchanged.
+ *   LBM_FORCES=<every>    additionally write forces.dat: the force of the fluid on the obstacles (lbm_set_forces: momentum
+ *                         exchange over the boundary links, all blocked cells one body), one line "%d:\t%.12E\t%.12E" =
+ *                         tt, F_x, F_y after every step tt with tt % every == 0, in av_vels.dat's style.  final_state.dat
+ *                         is unchanged; av_vels.dat is that of the same run issued as calls split at the sample steps.  Not
+ *                         together with LBM_ANIMATION, LBM_STATES, LBM_PROBES, LBM_MEAN, LBM_STEADY or LBM_PRECISION=double.
  */
 #include <math.h>
 #include <stdio.h>
@@ -163,6 +168,16 @@ static void parse_states(const char* text, int* every, lbm_window* window)
   window->ny = (int)v[4];
 }
 
+/* LBM_FORCES=<every>: a plain decimal number >= 1, nothing else */
+static int parse_forces(const char* text)
+{
+  char* end = NULL;
+  const long v = strtol(text, &end, 10);
+  if (end == text || *end != '\0' || text[0] < '0' || text[0] > '9' || v < 1 || v > 2147483647L)
+    lbm_die("could not read LBM_FORCES: expected <every> with every >= 1", __LINE__, __FILE__);
+  return (int)v;
+}
+
 /* LBM_PRECISION=double: the same program on the double engine (main() :132-205 with every float read as double) */
 static int main_double(const char* paramfile, const char* obstaclefile)
 {
@@ -243,6 +258,10 @@ int main(int argc, char* argv[])
   if (states_env && *states_env) parse_states(states_env, &states_every, &states_window);
   if (states_every > 0 && (env = getenv("LBM_PRECISION")) && !strcmp(env, "double"))
     lbm_die("LBM_PRECISION=double and LBM_STATES cannot be combined", __LINE__, __FILE__);
+  const char* forces_env = getenv("LBM_FORCES");
+  const int forces_every = (forces_env && *forces_env) ? parse_forces(forces_env) : 0;
+  if (forces_every > 0 && (env = getenv("LBM_PRECISION")) && !strcmp(env, "double"))
+    lbm_die("LBM_PRECISION=double and LBM_FORCES cannot be combined", __LINE__, __FILE__);
   if ((env = getenv("LBM_PRECISION")) && *env) {
     if (!strcmp(env, "double")) return main_double(paramfile, obstaclefile);
     if (strcmp(env, "single")) lbm_die("could not read LBM_PRECISION: expected single or double", __LINE__, __FILE__);
@@ -287,6 +306,12 @@ int main(int argc, char* argv[])
   if (states_every > 0 && mean_every > 0) lbm_die("LBM_MEAN and LBM_STATES cannot be combined", __LINE__, __FILE__);
   if (states_every > 0 && (env = getenv("LBM_ANIMATION")) && *env && atoi(env) > 0)
     lbm_die("LBM_ANIMATION and LBM_STATES cannot be combined", __LINE__, __FILE__);
+  if (forces_every > 0 && until) lbm_die("LBM_STEADY and LBM_FORCES cannot be combined", __LINE__, __FILE__);
+  if (forces_every > 0 && n_probes > 0) lbm_die("LBM_PROBES and LBM_FORCES cannot be combined", __LINE__, __FILE__);
+  if (forces_every > 0 && mean_every > 0) lbm_die("LBM_MEAN and LBM_FORCES cannot be combined", __LINE__, __FILE__);
+  if (forces_every > 0 && states_every > 0) lbm_die("LBM_STATES and LBM_FORCES cannot be combined", __LINE__, __FILE__);
+  if (forces_every > 0 && (env = getenv("LBM_ANIMATION")) && *env && atoi(env) > 0)
+    lbm_die("LBM_ANIMATION and LBM_FORCES cannot be combined", __LINE__, __FILE__);
 
   /* Total/init time starts here (SerialCode/d2q9-bgk.c:156-159) */
   const double tot_tic = wall_seconds();
@@ -438,6 +463,30 @@ int main(int argc, char* argv[])
     }
     fclose(fp);
     free(samples);
+    free(steps);
+  } else if (forces_every > 0) {
+    /* with the forces: segments whose rows fit a ring of 4096, each drained and written after it */
+    const long total_rows = params.max_iters > 0 ? (params.max_iters + forces_every - 1) / forces_every : 0;
+    long cap = 4096;
+    if (cap > total_rows) cap = total_rows;
+    if (cap < 1) cap = 1;
+    if (lbm_set_forces(ctx, 1, NULL, forces_every, (int)cap) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+    double* rows = (double*)malloc(2 * sizeof(double) * (size_t)cap);
+    int* steps = (int*)malloc(sizeof(int) * (size_t)cap);
+    FILE* fp = fopen(LBM_FORCESFILE, "w");
+    if (rows == NULL || steps == NULL) lbm_die("cannot allocate memory for force rows", __LINE__, __FILE__);
+    if (fp == NULL) lbm_die("could not open file output file", __LINE__, __FILE__);
+    const long seg = cap * (long)forces_every;
+    for (long t = 0; t < params.max_iters;) {
+      const int n = (int)((params.max_iters - t < seg) ? params.max_iters - t : seg);
+      if (lbm_run(ctx, n) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+      int n_read = 0;
+      if (lbm_read_forces(ctx, (int)cap, rows, steps, &n_read) != LBM_SUCCESS) lbm_die(lbm_last_error(), __LINE__, __FILE__);
+      for (int i = 0; i < n_read; i++) fprintf(fp, "%d:\t%.12E\t%.12E\n", steps[i], rows[2 * i], rows[2 * i + 1]);
+      t += n;
+    }
+    fclose(fp);
+    free(rows);
     free(steps);
   } else if (mean_every > 0) {
     /* with the mean fields: <from> steps unarmed, then the rest armed */
