@@ -174,13 +174,18 @@ def test_guard_paths_stay_bit_exact(lbm, oracle, monkeypatch, kernel):
     with patches of populations scaled by 1e-22 and 1e+20 (densities 1e-23 and 1e+19) and a few cells with momenta
     far above their density drives every kernel family through those paths; results must still equal the oracle's
     bits (all values stay finite)."""
-    env = {"tile": {}, "one-step": {"LBM_FUSE2": "0"},
-           "two-cell packed": {"LBM_FUSE2": "1", "LBM_LANE_CELLS": "2"},
-           "four-step packed": {"LBM_FUSE2": "1", "LBM_LANE_CELLS": "4"},
-           "three-step scalar": {"LBM_FUSE2": "1", "LBM_LANE_CELLS": "4", "LBM_PACKED": "0", "LBM_PASS_STEPS": "3"}}[kernel]
+    # (steps_per_launch, lane_cells) as Engine.info() reports them.  Without LBM_TILE_STEPS the planner serves a call of 9
+    # steps at this size with the resident kernel (resident_min_steps is 8 below 48 Ki cells), not with step_tile
+    env, pin = {"tile": ({"LBM_TILE_STEPS": "4"}, (4, 0)), "one-step": ({"LBM_FUSE2": "0"}, (1, 0)),
+                "two-cell packed": ({"LBM_FUSE2": "1", "LBM_LANE_CELLS": "2"}, (3, 2)),
+                "four-step packed": ({"LBM_FUSE2": "1", "LBM_LANE_CELLS": "4"}, (4, 4)),
+                "three-step scalar": ({"LBM_FUSE2": "1", "LBM_LANE_CELLS": "4", "LBM_PACKED": "0", "LBM_PASS_STEPS": "3"}, (3, 4))}[kernel]
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     p, ob, cells = random_case(lbm, 256, 40, 4242, walls=False)
+    with lbm.Engine(p, ob, cells) as eng:
+        info = eng.info()
+        assert (info["steps_per_launch"], info["lane_cells"]) == pin and info["resident_steps"] == 0, info
     rng = np.random.default_rng(7)
     cells[5:9, 10:40] *= np.float32(1e-22)
     cells[20:23, 100:180] *= np.float32(1e20)
