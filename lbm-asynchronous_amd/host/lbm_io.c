@@ -25,7 +25,9 @@ void lbm_usage(const char* exe)
   exit(EXIT_FAILURE);
 }
 
-void lbm_read_params(const char* paramfile, lbm_params* params)
+/* seven values, one per line, in this order (SerialCode/d2q9-bgk.c:480-506); the last three scanned with real_fmt */
+static void read_params(const char* paramfile, int* nx, int* ny, int* max_iters, int* reynolds_dim, const char* real_fmt,
+                        void* density, void* accel, void* omega)
 {
   char message[1024];
   FILE* fp = fopen(paramfile, "r");
@@ -33,46 +35,29 @@ void lbm_read_params(const char* paramfile, lbm_params* params)
     snprintf(message, sizeof(message), "could not open input parameter file: %s", paramfile);
     lbm_die(message, __LINE__, __FILE__);
   }
-
-  /* seven values, one per line, in this order (SerialCode/d2q9-bgk.c:480-506) */
   struct { const char* fmt; void* dst; const char* what; } field[7] = {
-    { "%d\n", &params->nx,           "could not read param file: nx" },
-    { "%d\n", &params->ny,           "could not read param file: ny" },
-    { "%d\n", &params->max_iters,    "could not read param file: maxIters" },
-    { "%d\n", &params->reynolds_dim, "could not read param file: reynolds_dim" },
-    { "%f\n", &params->density,      "could not read param file: density" },
-    { "%f\n", &params->accel,        "could not read param file: accel" },
-    { "%f\n", &params->omega,        "could not read param file: omega" },
+    { "%d\n",    nx,           "could not read param file: nx" },
+    { "%d\n",    ny,           "could not read param file: ny" },
+    { "%d\n",    max_iters,    "could not read param file: maxIters" },
+    { "%d\n",    reynolds_dim, "could not read param file: reynolds_dim" },
+    { real_fmt,  density,      "could not read param file: density" },
+    { real_fmt,  accel,        "could not read param file: accel" },
+    { real_fmt,  omega,        "could not read param file: omega" },
   };
-  for (int i = 0; i < 7; i++) {
+  for (int i = 0; i < 7; i++)
     if (fscanf(fp, field[i].fmt, field[i].dst) != 1) lbm_die(field[i].what, __LINE__, __FILE__);
-  }
   fclose(fp);
 }
 
-void lbm_read_params_double(const char* paramfile, lbm_params_double* params)
+void lbm_read_params(const char* paramfile, lbm_params* p)
 {
-  char message[1024];
-  FILE* fp = fopen(paramfile, "r");
-  if (fp == NULL) {
-    snprintf(message, sizeof(message), "could not open input parameter file: %s", paramfile);
-    lbm_die(message, __LINE__, __FILE__);
-  }
+  read_params(paramfile, &p->nx, &p->ny, &p->max_iters, &p->reynolds_dim, "%f\n", &p->density, &p->accel, &p->omega);
+}
 
-  /* the same seven values; the last three scanned as doubles, so 1.85 is the double 1.85, not (double)1.85f */
-  struct { const char* fmt; void* dst; const char* what; } field[7] = {
-    { "%d\n",  &params->nx,           "could not read param file: nx" },
-    { "%d\n",  &params->ny,           "could not read param file: ny" },
-    { "%d\n",  &params->max_iters,    "could not read param file: maxIters" },
-    { "%d\n",  &params->reynolds_dim, "could not read param file: reynolds_dim" },
-    { "%lf\n", &params->density,      "could not read param file: density" },
-    { "%lf\n", &params->accel,        "could not read param file: accel" },
-    { "%lf\n", &params->omega,        "could not read param file: omega" },
-  };
-  for (int i = 0; i < 7; i++) {
-    if (fscanf(fp, field[i].fmt, field[i].dst) != 1) lbm_die(field[i].what, __LINE__, __FILE__);
-  }
-  fclose(fp);
+/* scanned as doubles, so 1.85 is the double 1.85, not (double)1.85f */
+void lbm_read_params_double(const char* paramfile, lbm_params_double* p)
+{
+  read_params(paramfile, &p->nx, &p->ny, &p->max_iters, &p->reynolds_dim, "%lf\n", &p->density, &p->accel, &p->omega);
 }
 
 int* lbm_read_obstacles(const char* obstaclefile, const lbm_params* params)
@@ -186,21 +171,17 @@ void lbm_write_final_state_rows_double(FILE* fp, const lbm_params_double* params
   write_final_state_rows(fp, params->nx, row_first, row_count, 1, u_x, u_y, u_mag, pressure, obstacles);
 }
 
-void lbm_write_av_vels_double(const char* path, const double* av_vels, int n)
+/* av_vels.dat from floats or from doubles */
+static void write_av_vels(const char* path, const void* av_vels, int is_double, int n)
 {
   FILE* fp = fopen(path, "w");
   if (fp == NULL) lbm_die("could not open file output file", __LINE__, __FILE__);
-  for (int ii = 0; ii < n; ii++) fprintf(fp, "%d:\t%.12E\n", ii, av_vels[ii]);
+  for (int ii = 0; ii < n; ii++) fprintf(fp, "%d:\t%.12E\n", ii, field_at(av_vels, is_double, (size_t)ii));
   fclose(fp);
 }
 
-void lbm_write_av_vels(const char* path, const float* av_vels, int n)
-{
-  FILE* fp = fopen(path, "w");
-  if (fp == NULL) lbm_die("could not open file output file", __LINE__, __FILE__);
-  for (int ii = 0; ii < n; ii++) fprintf(fp, "%d:\t%.12E\n", ii, av_vels[ii]);
-  fclose(fp);
-}
+void lbm_write_av_vels_double(const char* path, const double* av_vels, int n) { write_av_vels(path, av_vels, 1, n); }
+void lbm_write_av_vels(const char* path, const float* av_vels, int n) { write_av_vels(path, av_vels, 0, n); }
 
 void lbm_write_state_frame(const char* dir, const lbm_params* params, const lbm_window* window, int timestep,
                            const float* u_x, const float* u_y, const float* u_mag, const float* pressure,

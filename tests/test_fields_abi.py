@@ -6,12 +6,12 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import fields_model
+from cli_case import MALFORMED, run_cli
 from conftest import ROOT
 
 
@@ -115,24 +115,7 @@ def test_write_state_frame_of_the_whole_grid_is_write_final_state(lbm, tmp_path)
     assert (tmp_path / "a.dat").read_bytes() == (tmp_path / "b.dat").read_bytes()
 
 
-CLI_VARS = ("LBM_STATES", "LBM_MEAN", "LBM_ANIMATION", "LBM_PROBES", "LBM_STEADY", "LBM_PRECISION")
-
-
-def run_cli(lbm, tmp_path, **env):
-    if not os.path.exists(lbm.CLI_PATH):
-        lbm.build()
-    pf = tmp_path / "input.params"
-    pf.write_text("64\n16\n10\n16\n0.1\n0.005\n1.0\n")
-    of = tmp_path / "obstacles.dat"
-    of.write_text("".join("%d 0 1\n" % x for x in range(64)))
-    clean = {k: v for k, v in os.environ.items() if k not in CLI_VARS}
-    return subprocess.run([lbm.CLI_PATH, str(pf), str(of)], cwd=tmp_path, capture_output=True, text=True,
-                          env=dict(clean, **env), timeout=120)
-
-
-@pytest.mark.parametrize("value", ["", "abc", "0", "-5", "10:", "10:x", "10:-1", ":5", "10,5", "10:5:2", "10 ", " 10", "+10",
-                                   "1e2", "99999999999", "10:1,2,3", "10:1,2,0,4", "10:1,2,3,0", "10:a,b,c,d", "10:1,2,3,4,5",
-                                   "10:1,2,3,4:5", "10:1,2,3,", "10:1,-2,3,4", "10:1,2,3,99999999999", "10:1;2;3;4"])
+@pytest.mark.parametrize("value", [""] + MALFORMED["LBM_STATES"])
 def test_cli_dies_on_a_malformed_lbm_states(lbm, tmp_path, value):
     """As for a malformed LBM_MEAN: a message and exit(EXIT_FAILURE), before any device is touched.  (An empty value
     counts as unset, so the run goes on to its usual end: on a box without a device that is lbm_create's error.)"""

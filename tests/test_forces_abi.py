@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import forces_model
+from cli_case import run_cli
 from conftest import ROOT
 
 
@@ -194,15 +195,6 @@ def test_labelled_bodies_add_up_to_the_unlabelled_force(lbm, oracle):
 
 
 # ---- the command line ---------------------------------------------------------------------------------------------------
-def run_cli(lbm, env, tmp_path):
-    exe = os.path.join(os.path.dirname(lbm.LIB_PATH), "d2q9-bgk")
-    inputs = os.path.join(ROOT, "tests", "golden", "inputs")
-    full = dict(os.environ)
-    full.update(env)
-    return subprocess.run([exe, os.path.join(inputs, "input_128x128.params"), os.path.join(inputs, "obstacles_128x128.dat")],
-                          cwd=str(tmp_path), env=full, capture_output=True, text=True)
-
-
 @pytest.mark.parametrize("env,match", [
     ({"LBM_FORCES": "-5"}, "LBM_FORCES"), ({"LBM_FORCES": "ten"}, "LBM_FORCES"), ({"LBM_FORCES": "10x"}, "LBM_FORCES"),
     ({"LBM_FORCES": "50", "LBM_PRECISION": "double"}, "LBM_PRECISION=double"),
@@ -211,7 +203,7 @@ def run_cli(lbm, env, tmp_path):
     ({"LBM_FORCES": "50", "LBM_STEADY": "1e-6"}, "LBM_STEADY")])
 def test_command_line_refuses_bad_values_and_combinations(lbm, tmp_path, env, match):
     """Refused while the environment is read, before a device is looked for."""
-    out = run_cli(lbm, env, tmp_path)
+    out = run_cli(lbm, tmp_path, **env)
     assert out.returncode != 0
     assert match in out.stderr and "LBM_FORCES" in out.stderr, out.stderr
     assert not os.path.exists(tmp_path / "forces.dat")

@@ -13,6 +13,7 @@ import pytest
 
 import forces_model
 import test_frames_format as model
+from cli_case import obstacles_text, params_text, run_cli
 from conftest import GOLDEN
 from test_gpu_parity import random_case
 
@@ -383,3 +384,34 @@ def test_cli_writes_forces_dat(lbm, datasets, tmp_path):
     twin = tmp_path / "twin.dat"
     lbm.write_forces(str(twin), steps, rows)
     assert (outs["forces"] / "forces.dat").read_bytes() == twin.read_bytes()
+
+
+def test_cli_forces_across_segments(lbm, tmp_path):
+    """The segment loop of the command line over more than one segment: 64 x 16 with three blocked cells, 4 100 steps and
+    LBM_FORCES=1, so the ring of 4 096 rows is drained after 4 096 steps and a second segment of 4 steps follows.  forces.dat
+    holds the steps 0 .. 4 099 in order and is, as final_state.dat and av_vels.dat are, byte for byte what an Engine driven
+    the same way gives: set_forces(1, 4096), run(4096), drain, run(4), drain."""
+    p = lbm.Params(64, 16, 4100, 16, 0.1, 1e-5, 1.0)
+    ob = np.zeros((16, 64), dtype=np.int32)
+    ob[5, 20] = ob[6, 20] = ob[9, 41] = 1
+    d = tmp_path / "cli"
+    out = run_cli(lbm, d, params_text(p), obstacles_text(ob), LBM_FORCES="1")
+    assert out.returncode == 0, out.stderr
+    with lbm.Engine(p, ob) as eng:
+        eng.set_forces(1, 4096)
+        drained = []
+        for n in (4096, 4):
+            eng.run(n)
+            drained.append(eng.forces())
+        fields, av = eng.final_state(), eng.av_vels(4100)
+    assert [len(steps) for steps, _ in drained] == [4096, 4]
+    steps, rows = np.concatenate([s for s, _ in drained]), np.concatenate([r for _, r in drained])
+    lines = (d / "forces.dat").read_text().splitlines()
+    assert len(lines) == 4100
+    assert [int(line.split(":")[0]) for line in lines] == list(range(4100)) == steps.tolist()
+    assert rows[-1, 0, 0] != 0.0
+    lbm.write_forces(str(tmp_path / "forces.dat"), steps, rows)
+    lbm.write_final_state(str(tmp_path / "final_state.dat"), fields, ob)
+    lbm.write_av_vels(str(tmp_path / "av_vels.dat"), av)
+    for name in ("forces.dat", "final_state.dat", "av_vels.dat"):
+        assert (d / name).read_bytes() == (tmp_path / name).read_bytes(), name

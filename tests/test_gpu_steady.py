@@ -3,13 +3,12 @@ steps.  Each run stops where tests/steady_model.py says it must -- computed from
 kernels, deterministic sums) and from the oracle's series (tests/test_steady_model.py shows every decision of these
 cases is a factor >= 3 from tol) -- and leaves exactly the lattice, av_vels and steps_done of lbm_run(steps_run).
 "resident": 64x16, resident kernel, one segment of look-ahead (dropped after the stop); "per_pass": 100x16."""
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import steady_model as sm
+from cli_case import obstacles_text, params_text, run_cli
 from test_gpu_parity import AV_RTOL
 
 pytestmark = pytest.mark.gpu
@@ -248,26 +247,15 @@ def test_refusals_of_slabs_ranks_and_members(lbm):
         assert batch.run_until(64, 16, 1e30, 1)[1]["steps_run"] == 32
 
 
-def run_cli(lbm, d, p, ob, env):
-    if not os.path.exists(lbm.CLI_PATH):
-        lbm.build()
-    d.mkdir()
-    pf, of = d / "input.params", d / "obstacles.dat"
-    pf.write_text("%d\n%d\n%d\n%d\n%.9g\n%.9g\n%.9g\n" % (p.nx, p.ny, p.max_iters, p.reynolds_dim, p.density, p.accel, p.omega))
-    of.write_text("".join("%d %d 1\n" % (x, y) for y, x in zip(*np.nonzero(ob))))
-    out = subprocess.run([lbm.CLI_PATH, str(pf), str(of)], cwd=d, capture_output=True, text=True,
-                         env=dict(os.environ, **env), timeout=120)
-    assert out.returncode == 0, out.stderr
-    return out.stdout
-
-
 def test_cli_runs_to_the_steady_state(lbm, oracle, tmp_path):
     """Check 7: LBM_STEADY=1e-3:512:2 on the 64x16 case; without the variable the program runs maxIters steps as ever."""
     p, ob = sm.case_params(lbm, "resident")
     p.max_iters = 4096
     want_steps = {"steady": 2048, "plain": 4096}
     for label, env in (("steady", {"LBM_STEADY": "1e-3:512:2"}), ("plain", {})):
-        stdout = run_cli(lbm, tmp_path / label, p, ob, env)
+        out = run_cli(lbm, tmp_path / label, params_text(p), obstacles_text(ob), **env)
+        assert out.returncode == 0, out.stderr
+        stdout = out.stdout
         n = want_steps[label]
         cells, av, fields = oracle_after(lbm, oracle, p, ob, n)
         twin = tmp_path / (label + "_final_state.dat")
@@ -284,6 +272,8 @@ def test_cli_runs_to_the_steady_state(lbm, oracle, tmp_path):
             assert stdout.startswith("==done==\n")
     # the cap: not steady within maxIters
     p.max_iters = 1300
-    stdout = run_cli(lbm, tmp_path / "cap", p, ob, {"LBM_STEADY": "1e-9:512"})
+    out = run_cli(lbm, tmp_path / "cap", params_text(p), obstacles_text(ob), LBM_STEADY="1e-9:512")
+    assert out.returncode == 0, out.stderr
+    stdout = out.stdout
     assert "Not steady after 1300 steps (rel. change " in stdout
     assert len((tmp_path / "cap" / "av_vels.dat").read_text().splitlines()) == 1300

@@ -5,12 +5,12 @@ import ctypes
 import inspect
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import mean_model
+from cli_case import MALFORMED, run_cli
 from conftest import ROOT
 
 
@@ -75,20 +75,7 @@ def test_write_mean_state_matches_the_format(lbm, tmp_path):
     assert path.read_text() == want
 
 
-def run_cli(lbm, tmp_path, **env):
-    if not os.path.exists(lbm.CLI_PATH):
-        lbm.build()
-    pf = tmp_path / "input.params"
-    pf.write_text("64\n16\n10\n16\n0.1\n0.005\n1.0\n")
-    of = tmp_path / "obstacles.dat"
-    of.write_text("".join("%d 0 1\n" % x for x in range(64)))
-    clean = {k: v for k, v in os.environ.items() if k not in ("LBM_MEAN", "LBM_ANIMATION", "LBM_PROBES", "LBM_STEADY")}
-    return subprocess.run([lbm.CLI_PATH, str(pf), str(of)], cwd=tmp_path, capture_output=True, text=True,
-                          env=dict(clean, **env), timeout=120)
-
-
-@pytest.mark.parametrize("value", ["", "abc", "0", "-5", "10:", "10:x", "10:-1", ":5", "10,5", "10:5:2", "10 ", " 10", "+10",
-                                   "1e2", "99999999999"])
+@pytest.mark.parametrize("value", [""] + MALFORMED["LBM_MEAN"])
 def test_cli_dies_on_a_malformed_lbm_mean(lbm, tmp_path, value):
     """As for a malformed LBM_PROBES: a message and exit(EXIT_FAILURE), before any device is touched.  (An empty value
     counts as unset, so the run goes on to its usual end: on a box without a device that is lbm_create's error.)"""

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from cli_case import MALFORMED, run_cli
 from conftest import ROOT
 
 
@@ -109,18 +110,11 @@ def test_write_probes_matches_the_format(lbm, tmp_path):
         lbm.write_probes(str(path), cells, [0], samples)
 
 
-@pytest.mark.parametrize("value", ["", "abc", "1,2;", "1,2:0", "1,2:x", "1;2", "-1,2", "1,2 "])
+@pytest.mark.parametrize("value", [""] + MALFORMED["LBM_PROBES"])
 def test_cli_dies_on_a_malformed_lbm_probes(lbm, tmp_path, value):
     """As for a malformed LBM_STEADY: a message and exit(EXIT_FAILURE), before any device is touched.  (An empty value
     counts as unset, so the run goes on to its usual end: on a box without a device that is lbm_create's error.)"""
-    if not os.path.exists(lbm.CLI_PATH):
-        lbm.build()
-    pf = tmp_path / "input.params"
-    pf.write_text("64\n16\n10\n16\n0.1\n0.005\n1.0\n")
-    of = tmp_path / "obstacles.dat"
-    of.write_text("".join("%d 0 1\n" % x for x in range(64)))
-    out = subprocess.run([lbm.CLI_PATH, str(pf), str(of)], cwd=tmp_path, capture_output=True, text=True,
-                         env=dict(os.environ, LBM_PROBES=value), timeout=120)
+    out = run_cli(lbm, tmp_path, LBM_PROBES=value)
     if value == "":
         assert "LBM_PROBES" not in out.stderr
         return

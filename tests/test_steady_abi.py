@@ -4,11 +4,11 @@ Host-only: passes on a box without a GPU."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from cli_case import MALFORMED, run_cli
 from conftest import ROOT
 
 
@@ -75,18 +75,11 @@ def test_engine_classes_have_run_until(lbm):
         member.run_until(10)
 
 
-@pytest.mark.parametrize("value", ["", "abc", "1e-3:", "1e-3:0", "1e-3:512:0", "1e-3:512:2:9", "-1", "1e-3:x", "1e-3 "])
+@pytest.mark.parametrize("value", [""] + MALFORMED["LBM_STEADY"])
 def test_cli_dies_on_a_malformed_lbm_steady(lbm, tmp_path, value):
     """As for a malformed params file: a message and exit(EXIT_FAILURE), before any device is touched.  (An empty value
     counts as unset, so the run goes on to its usual end: on a box without a device that is lbm_create's error.)"""
-    if not os.path.exists(lbm.CLI_PATH):
-        lbm.build()
-    pf = tmp_path / "input.params"
-    pf.write_text("64\n16\n10\n16\n0.1\n0.005\n1.0\n")
-    of = tmp_path / "obstacles.dat"
-    of.write_text("".join("%d 0 1\n" % x for x in range(64)))
-    out = subprocess.run([lbm.CLI_PATH, str(pf), str(of)], cwd=tmp_path, capture_output=True, text=True,
-                         env=dict(os.environ, LBM_STEADY=value), timeout=120)
+    out = run_cli(lbm, tmp_path, LBM_STEADY=value)
     if value == "":
         assert "LBM_STEADY" not in out.stderr
         return
