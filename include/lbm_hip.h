@@ -510,10 +510,11 @@ int lbm_read_field_frames(lbm_ctx* ctx, int max_frames, float* out, int* steps, 
  *   Works on lbm_create / lbm_create_tiled contexts of any number of slabs; a link belongs to the slab that owns its
  *   blocked cell, and a row is the sum over the slabs.
  *   Refused: negative every; capacity < 1; n_bodies outside [1, LBM_MAX_BODIES]; a blocked cell whose body lies outside
- *   0 .. n_bodies - 1; a ring of 2 GiB or more; rank contexts (lbm_create_rank*); batch members; LBM_HALO_STALE /
+ *   0 .. n_bodies - 1; a ring of 2 GiB or more; rank contexts (lbm_create_rank*); batch members (a batch arms them
+ *   as a whole: lbm_batch_set_forces); LBM_HALO_STALE /
  *   LBM_HALO_FRESHEST (and lbm_set_halo_mode to those while armed); a context with another recorder armed (and the other
  *   setters while this one is armed); lbm_run_until while armed; a slab of more than 2^29 cells.
- *   Not offered: accumulation inside the resident or stream kernels, batches, rank contexts, the double engine, torque.
+ *   Not offered: accumulation inside the resident or stream kernels, rank contexts, the double engine, torque.
  * lbm_read_forces: drains up to max_rows oldest rows into out[n][n_bodies][2] (f_x, f_y) and steps[n] (their tt, may be
  *   NULL); out == NULL && steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers.
  * lbm_forces_links: links_per_body[b] = boundary links of body b over all slabs, b < n_bodies; fails unless armed.
@@ -594,6 +595,41 @@ int        lbm_batch_run_until(lbm_batch* batch, int max_steps, int check_every,
 int        lbm_batch_sync(lbm_batch* batch);
 int        lbm_batch_get_info(const lbm_batch* batch, lbm_batch_info* out);
 void       lbm_destroy_batch(lbm_batch* batch);
+
+/* ---- obstacle forces of a batch -------------------------------------------------------------
+ * A drag curve over omega or accel, or a comparison of obstacle shapes, as one engine: the forces of lbm_set_forces for
+ * every member of a batch.  They are armed on the BATCH, not on a member: the batched launches must end at common sample
+ * steps, so there is one `every` (and one n_bodies, one capacity) for all members.  The definition is lbm_set_forces',
+ * member by member: the boundary links of the member's own obstacle map and labels, F = sum of (-2 c_k) f over a body's
+ * links taken exactly and rounded once (math.fsum's value); a body of a member with a term that is not finite is NaN in
+ * that row and nothing else is; a body without links reports +0, +0.
+ * lbm_batch_set_forces(batch, n_bodies, body_of_cell, every, capacity): from now on, after global timestep tt (the
+ *   batch's steps_done, the numbering of lbm_set_frames) with tt % every == 0, record one row: {double f_x, f_y} for every
+ *   member and body.  body_of_cell is int[members][ny*nx], the labels of each member as lbm_set_forces takes them, or
+ *   NULL: in every member all blocked cells are body 0.  1 <= n_bodies <= LBM_MAX_BODIES.  Rows wait in ONE device ring
+ *   of `capacity` rows (capacity * members * n_bodies * 160 bytes); an lbm_batch_run that would record more rows than are
+ *   free fails before issuing any work, and no member's steps_done moves.  every == 0 disarms and frees; re-arming
+ *   discards unread rows.  At arming every member's list of links is built on the device as a slab's is.
+ *   While armed, lbm_batch_run runs as the sub-calls that end at the sample steps: one of at least resident_min_steps
+ *   timesteps on a resident shape is what lbm_batch_run of that length is otherwise (the batched resident kernel), a
+ *   shorter one, or any on another shape, advances the members one after another on the per-pass kernels.  Behind each
+ *   sub-call that ends at a sample step the batch's stream gets one memset of the row and ONE force_gather_batch launch for
+ *   all members, whatever their number (every == 1: correct, not fast).  Member i's lattice, av_vels and rows are
+ *   bit-identical to those of an lbm_create context with the same inputs, armed with lbm_set_forces(ctx, n_bodies, its
+ *   labels, every, ...) and advanced by the same calls; recording never changes the lattice.
+ *   Refused: negative every; capacity < 1; n_bodies outside [1, LBM_MAX_BODIES]; a blocked cell whose body lies outside
+ *   0 .. n_bodies - 1 (the message names member, x, y and the label); a ring of 2 GiB or more; a member with a recorder
+ *   armed (and every member-level setter while the batch's forces are armed: a batch records one kind);
+ *   lbm_batch_run_until while armed.  lbm_set_forces on a member handle stays refused.
+ * lbm_batch_read_forces: drains up to max_rows oldest rows into out[n][members][n_bodies][2] (f_x, f_y) and steps[n]
+ *   (their tt, may be NULL); out == NULL && steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises.
+ * lbm_batch_forces_links: links[m * n_bodies + b] = boundary links of body b of member m; fails unless armed.
+ */
+int lbm_batch_set_forces(lbm_batch* batch, int n_bodies, const int* body_of_cell /* [members][ny*nx] or NULL */,
+                         int every, int capacity);
+int lbm_batch_read_forces(lbm_batch* batch, int max_rows, double* out /* [n][members][n_bodies][2] */,
+                          int* steps, int* n_read);
+int lbm_batch_forces_links(lbm_batch* batch, int* links /* [members][n_bodies] */);
 
 /* ---- double precision -----------------------------------------------------------------------
  * The reference's programs are `float`, but its published golden results (the .dat files of check/) are its algorithm evaluated in

@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     "lbm_set_field_frames", "lbm_read_field_frames", "lbm_set_forces", "lbm_read_forces", "lbm_forces_links",
     "lbm_run_until", "lbm_batch_run_until",
     "lbm_create_batch", "lbm_batch_member", "lbm_batch_run", "lbm_batch_sync", "lbm_batch_get_info", "lbm_destroy_batch",
+    "lbm_batch_set_forces", "lbm_batch_read_forces", "lbm_batch_forces_links",
     "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
     "lbm_double_sync", "lbm_double_read_av_vels", "lbm_double_read_cells", "lbm_double_read_final_state",
     "lbm_double_av_velocity", "lbm_double_total_density", "lbm_double_calc_reynolds",
@@ -247,6 +248,9 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_batch_sync.argtypes = [P]; lib.lbm_batch_sync.restype = I
     lib.lbm_batch_get_info.argtypes = [P, ctypes.POINTER(_CBatchInfo)]; lib.lbm_batch_get_info.restype = I
     lib.lbm_destroy_batch.argtypes = [P]; lib.lbm_destroy_batch.restype = None
+    lib.lbm_batch_set_forces.argtypes = [P, I, P, I, I]; lib.lbm_batch_set_forces.restype = I
+    lib.lbm_batch_read_forces.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_forces.restype = I
+    lib.lbm_batch_forces_links.argtypes = [P, P]; lib.lbm_batch_forces_links.restype = I
     PD = ctypes.POINTER(ctypes.c_double)
     lib.lbm_double_create.argtypes = [ctypes.POINTER(_CParamsDouble), P, P]; lib.lbm_double_create.restype = P
     lib.lbm_double_destroy.argtypes = [P]; lib.lbm_double_destroy.restype = None
@@ -890,6 +894,39 @@ class Batch:
         _check(self.lib, self.lib.lbm_batch_get_info(self._live(), ctypes.byref(bi)))
         return {name: getattr(bi, name) for name, _ in _CBatchInfo._fields_}
 
+    # -- obstacle forces of all members (lbm_batch_set_forces / lbm_batch_read_forces / lbm_batch_forces_links) ------
+    def set_forces(self, every: int, capacity: int = 4096, bodies=None, n_bodies: int | None = None) -> None:
+        """Engine.set_forces for every member at once: one `every`, `capacity` and `n_bodies` for the batch, rows in one
+        device ring.  `bodies`: None (in every member all blocked cells are body 0) or one label map (ny, nx) per member,
+        as a sequence or stacked [members, ny, nx]; n_bodies defaults to the largest label of any member + 1.
+        every == 0 disarms; re-arming discards unread rows."""
+        p0 = self.params[0]
+        every, capacity, n_bodies, labels = _batch_forces_args(every, capacity, bodies, n_bodies, len(self), p0.nx, p0.ny)
+        _check(self.lib, self.lib.lbm_batch_set_forces(self._live(), n_bodies, labels.ctypes.data if labels is not None else None,
+                                                       every, capacity))
+        self._n_bodies = n_bodies if every > 0 else 0
+
+    def forces(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n],
+        float64[n, members, n_bodies, 2]), columns F_x, F_y."""
+        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
+            raise LbmError(f"forces: max_rows must be a non-negative integer or None (got {max_rows!r})")
+        n = ctypes.c_int()
+        _check(self.lib, self.lib.lbm_batch_read_forces(self._live(), 0, None, None, ctypes.byref(n)))  # rows waiting
+        max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
+        rows = np.empty((int(max_rows), len(self), getattr(self, "_n_bodies", 0), 2), dtype=np.float64)
+        steps = np.empty(int(max_rows), dtype=np.int32)
+        _check(self.lib, self.lib.lbm_batch_read_forces(self._live(), int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
+        return steps[:n.value].copy(), rows[:n.value].copy()
+
+    def force_links(self) -> np.ndarray:
+        """Boundary links of every body of every member of the armed forces, int32[members, n_bodies]
+        (lbm_batch_forces_links)."""
+        n_bodies = getattr(self, "_n_bodies", 0)
+        out = np.zeros(max(1, len(self) * n_bodies), dtype=np.int32)
+        _check(self.lib, self.lib.lbm_batch_forces_links(self._live(), out.ctypes.data))
+        return out[:len(self) * n_bodies].reshape(len(self), n_bodies).copy()
+
     def member(self, index: int) -> "BatchMember":
         """Read-only view of member `index` (lbm_batch_member)."""
         if not 0 <= index < len(self):
@@ -1114,6 +1151,23 @@ def _forces_args(every, capacity, bodies, n_bodies, nx, ny) -> tuple[int, int, i
     if every > 0 and not 1 <= int(n_bodies) <= LBM_MAX_BODIES:
         raise LbmError(f"set_forces: {int(n_bodies)} bodies, between 1 and LBM_MAX_BODIES = {LBM_MAX_BODIES} are possible")
     return int(every), int(capacity), int(n_bodies), labels
+
+
+def _batch_forces_args(every, capacity, bodies, n_bodies, members, nx, ny) -> tuple[int, int, int, np.ndarray | None]:
+    """Batch.set_forces' argument checks (no device needed): _forces_args for every member's label map; (every, capacity,
+    n_bodies, int32 labels [members, ny*nx] or None), n_bodies by default the largest any member needs."""
+    if bodies is None:
+        return _forces_args(every, capacity, None, n_bodies, nx, ny)
+    try:
+        maps = list(bodies)
+    except TypeError:
+        raise LbmError(f"set_forces: bodies must be one integer array of shape ({ny}, {nx}) per member (got {bodies!r})"[:300]) from None
+    if len(maps) != members:
+        raise LbmError(f"set_forces: {len(maps)} label maps for {members} members")
+    checked = [_forces_args(every, capacity, m, n_bodies, nx, ny) for m in maps]
+    every, capacity = checked[0][:2]
+    n_bodies = max(c[2] for c in checked)
+    return every, capacity, n_bodies, np.ascontiguousarray(np.stack([c[3] for c in checked]), dtype=np.int32)
 
 
 def write_forces(path: str, steps, rows) -> None:

@@ -497,7 +497,18 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
   DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
   int armed[kRecKinds] = {0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
-                                    // (a batch records one kind, so at most one count is non-zero)
+                                    // (a batch records one kind, so at most one count is non-zero; the forces are armed on
+                                    // the batch, lbm_batch_set_forces, and count as one)
+  // obstacle forces of all members (lbm_batch_set_forces): the members' own recorders stay off, the batch keeps the one
+  // recorder and the one ring; every lbm_batch_run runs as the sub-calls that end at its sample steps
+  Recorder force_rec;                            // kind kRecForces while armed
+  int force_bodies = 0;                          // bodies of every member
+  int force_groups = 0;                          // workgroups per (member, body) of force_gather_batch (0: no member has a link)
+  std::vector<int> force_link_counts;            // [members][bodies]
+  std::vector<DeviceBuf<unsigned>> force_links;  // [members]: the member's boundary links, by body, cell, k ...
+  std::vector<DeviceBuf<unsigned>> force_starts; // ... and [bodies + 1]: where each body's links start
+  DeviceBuf<lbm::ForceMember> force_lists;       // device: [members], those pointers
+  DeviceBuf<long long> force_ring;               // device: [slots][members][bodies][lbm::kForceWords]
   // steady-state runs (lbm_batch_run_until), allocated by the first such call; steady_state last: the set is whole once it exists
   DeviceBuf<lbm::SteadyMember> steady_members; // device: [members]
   DeviceBuf<lbm::SteadyBatch> steady_batch;    // device
@@ -1500,16 +1511,18 @@ long long recorded_between(const Recorder& r, long long from, long long to) {
 
 // lbm_run / lbm_batch_run refuse a call whose records would not fit the free slots, before any work is issued; a kind
 // that accumulates its records (the mean fields) has room for any call
-int recorder_fits(const lbm_ctx* c, int n_steps, const char* who) {
-  const Recorder& r = c->rec;
+int recorder_fits(const Recorder& r, int steps_done, int n_steps, const char* who, const char* reader) {
   const RecorderKind& k = kRecorderKinds[r.kind];
   if (!k.slotted) return LBM_SUCCESS;
-  const long long add = recorded_between(r, c->steps_done, (long long)c->steps_done + n_steps);
+  const long long add = recorded_between(r, steps_done, (long long)steps_done + n_steps);
   const long long waiting = r.written - r.read;
   if (waiting + add > r.slots)
     LBM_FAIL(LBM_FAILURE, "%s: %d steps would record %lld %ss, but the %s buffer holds %d and %lld %ss are waiting (%s drains them)",
-             who, n_steps, add, k.record, k.record, r.slots, waiting, k.record, k.reader);
+             who, n_steps, add, k.record, k.record, r.slots, waiting, k.record, reader);
   return LBM_SUCCESS;
+}
+int recorder_fits(const lbm_ctx* c, int n_steps, const char* who) {
+  return recorder_fits(c->rec, c->steps_done, n_steps, who, kRecorderKinds[c->rec.kind].reader);
 }
 
 // the record of the current (stored) lattice into the next slot, on every slab's compute stream: the frame of its rows,
@@ -2300,6 +2313,9 @@ int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate alloc
       if (c->rec.kind == other)
         LBM_FAIL(LBM_FAILURE, "%s: %s are armed (%s) and a context has one recorder -- disarm them with %s first", setter, o.name,
                  o.setter, o.disarm);
+      if (bt && other == kRecForces && bt->armed[other] > 0)  // (no member arms them: the batch does)
+        LBM_FAIL(LBM_FAILURE, "%s: this batch has %s armed (lbm_batch_set_forces); a batch records one kind -- disarm them with "
+                 "lbm_batch_set_forces(batch, 0, NULL, 0, 0) first", setter, o.name);
       if (bt && bt->armed[other] > 0)
         LBM_FAIL(LBM_FAILURE, "%s: a member of this batch has %s armed (%s); a batch records one kind: frames, probes, mean fields or field frames",
                  setter, o.name, o.setter);
@@ -2367,6 +2383,88 @@ int drain_recorder(lbm_ctx* c, int kind, int max_records, bool has_out, int* ste
   r.read += n;
   *n_read = n;
   return LBM_SUCCESS;
+}
+
+// ---- obstacle forces: what lbm_set_forces (per slab) and lbm_batch_set_forces (per member) share ------------------
+// the labels of a slab's owned cells (src: those of its first owned cell on) as bytes on its device, 255: outside
+// 0 .. n_bodies - 1; *first_bad = the lowest blocked cell so marked, ~0u where there is none
+constexpr unsigned kNoBadLabel = ~0u;
+int upload_labels(lbm_ctx* c, Slab& sl, const int* src, int n_bodies, DeviceBuf<unsigned char>& labels, unsigned* first_bad) {
+  const size_t n = (size_t)sl.rows * c->p.nx;
+  std::vector<unsigned char> bytes(n);
+  for (size_t i = 0; i < n; i++) bytes[i] = (src[i] < 0 || src[i] >= n_bodies) ? 255 : (unsigned char)src[i];
+  HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+  DeviceBuf<unsigned> bad;
+  *first_bad = kNoBadLabel;
+  HIP_TRY(LBM_FAILURE, labels.alloc(n));
+  HIP_TRY(LBM_FAILURE, bad.alloc(1));
+  HIP_TRY(LBM_FAILURE, hipMemcpy(labels, bytes.data(), n, hipMemcpyHostToDevice));
+  HIP_TRY(LBM_FAILURE, hipMemcpy(bad, first_bad, sizeof(*first_bad), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(lbm::label_check, dim3(ceil_div((long)n, 256)), dim3(256), 0, sl.compute, (const unsigned char*)sl.mask, c->pitch,
+                     c->p.nx, (const unsigned char*)labels, (long)n, bad.get());
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(first_bad, bad, sizeof(*first_bad), hipMemcpyDeviceToHost, sl.compute));
+  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+  return LBM_SUCCESS;
+}
+
+// A slab's list of boundary links from its mask and the labels (nullptr: every blocked cell is body 0), on its device:
+// links per (body, workgroup of cells), their prefix sums, then the links themselves at those offsets.  `starts` is the
+// host's copy of starts_dev, [n_bodies + 1].
+int build_link_list(const char* who, lbm_ctx* c, Slab& sl, const unsigned char* lab, int n_bodies, DeviceBuf<unsigned>& links,
+                    DeviceBuf<unsigned>& starts_dev, std::vector<unsigned>& starts) {
+  HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+  const long n = (long)sl.rows * c->p.nx;
+  const int wgs = ceil_div(n, lbm::kLinkCells);
+  const long m = (long)wgs * n_bodies;
+  DeviceBuf<unsigned> counts;
+  DeviceBuf<unsigned long long> total_dev;
+  unsigned long long total = 0;
+  starts.assign((size_t)n_bodies + 1, 0u);
+  if (counts.alloc((size_t)m) != hipSuccess || total_dev.alloc(1) != hipSuccess || starts_dev.alloc(starts.size()) != hipSuccess)
+    LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the link counts (%.1f MiB); forces stay off", who, (double)m * sizeof(unsigned) / 1048576.0);
+  hipLaunchKernelGGL(lbm::link_count, dim3(wgs, n_bodies), dim3(lbm::kBlock), 0, sl.compute, (const unsigned char*)sl.mask, c->pitch,
+                     c->p.nx, lab, n, counts.get());
+  hipLaunchKernelGGL(lbm::link_scan, dim3(1), dim3(lbm::kBlock), 0, sl.compute, counts.get(), m, (long)wgs, starts_dev.get(),
+                     total_dev.get());
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(&total, total_dev, sizeof(total), hipMemcpyDeviceToHost, sl.compute));
+  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(starts.data(), starts_dev, starts.size() * sizeof(unsigned), hipMemcpyDeviceToHost, sl.compute));
+  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+  if (total > 0x7fffffffull) LBM_FAIL(LBM_FAILURE, "%s: %llu boundary links in one slab, at most 2^31 - 1 are possible", who, total);
+  if (links.alloc((size_t)(total ? total : 1)) != hipSuccess)
+    LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the list of %llu boundary links (%.1f MiB); forces stay off", who, total,
+             (double)total * sizeof(unsigned) / 1048576.0);
+  if (total > 0) {
+    hipLaunchKernelGGL(lbm::link_fill, dim3(wgs, n_bodies), dim3(lbm::kBlock), 0, sl.compute, (const unsigned char*)sl.mask, c->pitch,
+                       c->p.nx, lab, n, (const unsigned*)counts.get(), links.get(), (unsigned)total);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+  }
+  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));  // counts (and the caller's labels) may be freed on return
+  return LBM_SUCCESS;
+}
+
+// workgroups per body of force_gather / force_gather_batch where the largest body has `most` links: four links per lane
+// where there are that many, at most 256 (0: no links at all)
+int gather_groups(unsigned most) {
+  const int groups = ceil_div((long)most, 4 * lbm::kBlock);
+  return most == 0 ? 0 : (groups > 256 ? 256 : groups);
+}
+
+// n bodies' words of ring rows -> out[n][2]: each body's two exact sums rounded once and doubled (-2 c_k f)
+void round_forces(const long long* words, size_t n, double* out) {
+  constexpr int L = lbm_exact::kExactLimbs;
+  for (size_t j = 0; j < n; j++) {
+    const long long* w = words + j * lbm::kForceWords;
+    long long fx[L], fy[L];
+    for (int i = 0; i < L; i++) {
+      fx[i] = w[i];
+      fy[i] = w[L + i];
+    }
+    const bool finite = (w[2 * L] == 0);  // a population that is not finite makes the body's force of that row NaN
+    out[2 * j] = finite ? 2.0 * lbm_exact::exact_sum_round(fx) : std::nan("");
+    out[2 * j + 1] = finite ? 2.0 * lbm_exact::exact_sum_round(fy) : std::nan("");
+  }
 }
 
 }  // namespace
@@ -2847,31 +2945,18 @@ int lbm_set_forces(lbm_ctx* c, int n_bodies, const int* body_of_cell, int every,
     if (c->ranked || c->world > 1)
       LBM_FAIL(LBM_FAILURE, "lbm_set_forces: not available in a multi-process (rank) context: a body's links would be spread over the ranks");
     if (c->batch)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_forces: not available on a member of a batch (lbm_create_batch): the batched launches have no sample steps to end at");
+      LBM_FAIL(LBM_FAILURE, "lbm_set_forces: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
+               "end at, so the forces of a batch are armed on the batch, with one `every` for all members (lbm_batch_set_forces)");
     for (int s = 0; s < c->n_slabs; s++)
       if ((long)c->slab[s].rows * c->p.nx > (1L << 29))
         LBM_FAIL(LBM_FAILURE, "lbm_set_forces: a slab of %d x %d cells; a link is cell * 8 + k - 1 in 32 bits (at most 2^29 cells per slab)",
                  c->p.nx, c->slab[s].rows);
     for (size_t s = 0; s < labels.size(); s++) {
       Slab& sl = c->slab[s];
-      const size_t n = (size_t)sl.rows * c->p.nx;
       const int* src = body_of_cell + (size_t)(sl.row_first - c->row_first) * c->p.nx;
-      std::vector<unsigned char> bytes(n);
-      for (size_t i = 0; i < n; i++) bytes[i] = (src[i] < 0 || src[i] >= n_bodies) ? 255 : (unsigned char)src[i];
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      DeviceBuf<unsigned> bad;
-      const unsigned none = ~0u;
-      unsigned first_bad = none;
-      HIP_TRY(LBM_FAILURE, labels[s].alloc(n));
-      HIP_TRY(LBM_FAILURE, bad.alloc(1));
-      HIP_TRY(LBM_FAILURE, hipMemcpy(labels[s], bytes.data(), n, hipMemcpyHostToDevice));
-      HIP_TRY(LBM_FAILURE, hipMemcpy(bad, &none, sizeof(none), hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(lbm::label_check, dim3(ceil_div((long)n, 256)), dim3(256), 0, sl.compute, (const unsigned char*)sl.mask, c->pitch,
-                         c->p.nx, (const unsigned char*)labels[s], (long)n, bad.get());
-      HIP_TRY(LBM_FAILURE, hipGetLastError());
-      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(&first_bad, bad, sizeof(first_bad), hipMemcpyDeviceToHost, sl.compute));
-      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
-      if (first_bad != none)
+      unsigned first_bad;
+      if (upload_labels(c, sl, src, n_bodies, labels[s], &first_bad) != LBM_SUCCESS) return LBM_FAILURE;
+      if (first_bad != kNoBadLabel)
         LBM_FAIL(LBM_FAILURE, "lbm_set_forces: the blocked cell (%d, %d) has body %d, outside 0 .. %d", (int)(first_bad % (unsigned)c->p.nx),
                  sl.row_first + (int)(first_bad / (unsigned)c->p.nx), src[first_bad], n_bodies - 1);
     }
@@ -2882,47 +2967,20 @@ int lbm_set_forces(lbm_ctx* c, int n_bodies, const int* body_of_cell, int every,
     for (int s = 0; s < c->n_slabs; s++) {
       Slab& sl = c->slab[s];
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      const long n = (long)sl.rows * c->p.nx;
-      const unsigned char* lab = labels.empty() ? nullptr : labels[s].get();
-      // the list: links per (body, workgroup of cells), their prefix sums, then the links themselves at those offsets
-      const int wgs = ceil_div(n, lbm::kLinkCells);
-      const long m = (long)wgs * n_bodies;
-      DeviceBuf<unsigned> counts;
-      DeviceBuf<unsigned long long> total_dev;
-      unsigned long long total = 0;
-      std::vector<unsigned> starts((size_t)n_bodies + 1);
-      if (counts.alloc((size_t)m) != hipSuccess || total_dev.alloc(1) != hipSuccess || sl.force_starts.alloc(starts.size()) != hipSuccess ||
-          sl.force_ring.alloc_bytes(ring_bytes) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_set_forces: cannot allocate %d rows of %d bodies (%.1f MiB per slab) and the link counts (%.1f MiB); forces stay off",
-                 capacity, n_bodies, (double)ring_bytes / 1048576.0, (double)m * sizeof(unsigned) / 1048576.0);
-      hipLaunchKernelGGL(lbm::link_count, dim3(wgs, n_bodies), dim3(lbm::kBlock), 0, sl.compute, (const unsigned char*)sl.mask, c->pitch,
-                         c->p.nx, lab, n, counts.get());
-      hipLaunchKernelGGL(lbm::link_scan, dim3(1), dim3(lbm::kBlock), 0, sl.compute, counts.get(), m, (long)wgs, sl.force_starts.get(),
-                         total_dev.get());
-      HIP_TRY(LBM_FAILURE, hipGetLastError());
-      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(&total, total_dev, sizeof(total), hipMemcpyDeviceToHost, sl.compute));
-      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(starts.data(), sl.force_starts, starts.size() * sizeof(unsigned), hipMemcpyDeviceToHost, sl.compute));
-      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
-      if (total > 0x7fffffffull)
-        LBM_FAIL(LBM_FAILURE, "lbm_set_forces: %llu boundary links in one slab, at most 2^31 - 1 are possible", total);
-      if (sl.force_links.alloc((size_t)(total ? total : 1)) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_set_forces: cannot allocate the list of %llu boundary links (%.1f MiB); forces stay off", total,
-                 (double)total * sizeof(unsigned) / 1048576.0);
-      if (total > 0) {
-        hipLaunchKernelGGL(lbm::link_fill, dim3(wgs, n_bodies), dim3(lbm::kBlock), 0, sl.compute, (const unsigned char*)sl.mask, c->pitch,
-                           c->p.nx, lab, n, (const unsigned*)counts.get(), sl.force_links.get(), (unsigned)total);
-        HIP_TRY(LBM_FAILURE, hipGetLastError());
-      }
-      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));  // counts and the labels are freed on return
+      if (sl.force_ring.alloc_bytes(ring_bytes) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_forces: cannot allocate %d rows of %d bodies (%.1f MiB per slab); forces stay off", capacity, n_bodies,
+                 (double)ring_bytes / 1048576.0);
+      std::vector<unsigned> starts;
+      if (build_link_list("lbm_set_forces", c, sl, labels.empty() ? nullptr : labels[s].get(), n_bodies, sl.force_links, sl.force_starts,
+                          starts) != LBM_SUCCESS)
+        return LBM_FAILURE;
       unsigned most = 0;
       for (int b = 0; b < n_bodies; b++) {
         const unsigned links = starts[(size_t)b + 1] - starts[(size_t)b];
         c->force_link_counts[(size_t)b] += (int)links;
         if (links > most) most = links;
       }
-      // four links per lane where there are that many, at most 256 workgroups per body
-      const int groups = ceil_div((long)most, 4 * lbm::kBlock);
-      sl.force_groups = most == 0 ? 0 : (groups > 256 ? 256 : groups);
+      sl.force_groups = gather_groups(most);
     }
     return LBM_SUCCESS;
   });
@@ -2930,7 +2988,6 @@ int lbm_set_forces(lbm_ctx* c, int n_bodies, const int* body_of_cell, int every,
 
 int lbm_read_forces(lbm_ctx* c, int max_rows, double* out, int* steps, int* n_read) {
   return drain_recorder(c, kRecForces, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
-    constexpr int L = lbm_exact::kExactLimbs;
     const size_t bodies = c->force_link_counts.size(), words = bodies * (size_t)lbm::kForceWords;
     const size_t slots = (size_t)c->rec.slots;
     // every slab's words of the n rows (they wait in at most two runs of its ring), added word by word -- integers: the
@@ -2949,17 +3006,7 @@ int lbm_read_forces(lbm_ctx* c, int max_rows, double* out, int* steps, int* n_re
       HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
       for (size_t j = 0; j < sum.size(); j++) sum[j] += stage[j];
     }
-    for (size_t j = 0; j < (size_t)n * bodies; j++) {
-      const long long* w = sum.data() + j * lbm::kForceWords;
-      long long fx[L], fy[L];
-      for (int i = 0; i < L; i++) {
-        fx[i] = w[i];
-        fy[i] = w[L + i];
-      }
-      const bool finite = (w[2 * L] == 0);  // a population that is not finite makes the body's force of that row NaN
-      out[2 * j] = finite ? 2.0 * lbm_exact::exact_sum_round(fx) : std::nan("");
-      out[2 * j + 1] = finite ? 2.0 * lbm_exact::exact_sum_round(fy) : std::nan("");
-    }
+    round_forces(sum.data(), (size_t)n * bodies, out);
     return LBM_SUCCESS;
   });
 }
@@ -3222,6 +3269,27 @@ void lbm_destroy_batch(lbm_batch* bt) {
   delete bt;  // the batch's own tables go with it
 }
 
+// what the batched kernels read of every member, [parity of cur][members]
+static std::vector<lbm::ResidentMember> member_table(const lbm_batch* bt) {
+  const size_t n_members = bt->members.size();
+  std::vector<lbm::ResidentMember> h(2 * n_members);
+  for (int par = 0; par < 2; par++)
+    for (size_t i = 0; i < n_members; i++) {
+      const lbm_ctx* c = bt->members[i];
+      const Slab& sl = c->slab[0];
+      lbm::ResidentMember& m = h[(size_t)par * n_members + i];
+      m.src = sl.lat[par];
+      m.dst = sl.lat[par ^ 1];
+      m.mask = sl.mask;
+      m.gran = sl.res_gran;
+      m.partials = sl.res_part;
+      m.tot_u = sl.tot_u;
+      m.omega = c->p.omega;
+      set_accel_weights(m, c->p);  // as run_steps / run_resident
+    }
+  return h;
+}
+
 lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* obstacles, const float* cells_aos,
                             int math_mode) {
   // everything that can be checked without a device is checked first
@@ -3292,21 +3360,7 @@ lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* 
     }
     bt->members_per_launch = mpl;
     bt->launches = ceil_div(n_members, mpl);
-    std::vector<lbm::ResidentMember> h(2 * (size_t)n_members);
-    for (int par = 0; par < 2; par++)
-      for (int i = 0; i < n_members; i++) {
-        const lbm_ctx* c = bt->members[i];
-        const Slab& sl = c->slab[0];
-        lbm::ResidentMember& m = h[(size_t)par * n_members + i];
-        m.src = sl.lat[par];
-        m.dst = sl.lat[par ^ 1];
-        m.mask = sl.mask;
-        m.gran = sl.res_gran;
-        m.partials = sl.res_part;
-        m.tot_u = sl.tot_u;
-        m.omega = c->p.omega;
-        set_accel_weights(m, c->p);  // as run_steps / run_resident
-      }
+    const std::vector<lbm::ResidentMember> h = member_table(bt);
     if (bt->table.alloc(h.size()) != hipSuccess ||
         hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess ||
         bt->status.alloc(1) != hipSuccess || hipMemset(bt->status, 0, sizeof(int)) != hipSuccess ||
@@ -3326,16 +3380,9 @@ lbm_ctx* lbm_batch_member(lbm_batch* bt, int index) {
   return bt->members[(size_t)index];
 }
 
-int lbm_batch_run(lbm_batch* bt, int n_steps) {
-  if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: null batch");
-  if (n_steps < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: negative step count");
-  if (n_steps == 0) return LBM_SUCCESS;
+// n_steps timesteps of every member, as one call: batched on the resident kernel where the call is long enough for it
+static int batch_advance(lbm_batch* bt, int n_steps) {
   lbm_ctx* c0 = bt->members[0];
-  if (bt->steps_done + n_steps > c0->capacity)
-    LBM_FAIL(LBM_FAILURE, "lbm_batch_run: %d steps requested but the av_vels record holds %d (maxIters)",
-             bt->steps_done + n_steps, c0->capacity);
-  for (lbm_ctx* c : bt->members)  // every member's records must fit before any member runs
-    if (recorder_fits(c, n_steps, "lbm_batch_run") != LBM_SUCCESS) return LBM_FAILURE;
   if (bt->resident && n_steps >= c0->plan.resident_min_steps) {
     if (run_batch_resident(bt, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
     for (lbm_ctx* c : bt->members) {
@@ -3364,6 +3411,51 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
   return LBM_SUCCESS;
 }
 
+// the forces row of the members' current (stored) lattices into the next slot: the row's words of all members zeroed at
+// once, then one force_gather_batch for all of them, on the batch's stream
+static int take_batch_forces(lbm_batch* bt) {
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  const size_t words = n_members * (size_t)bt->force_bodies * lbm::kForceWords;
+  long long* row = bt->force_ring + (size_t)(bt->force_rec.written % bt->force_rec.slots) * words;
+  HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
+  HIP_TRY(LBM_FAILURE, hipMemsetAsync(row, 0, words * sizeof(long long), bt->stream));
+  if (bt->force_groups > 0) {
+    hipLaunchKernelGGL(lbm::force_gather_batch, dim3((unsigned)bt->force_groups, (unsigned)bt->force_bodies, (unsigned)n_members),
+                       dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, c0->slab[0]),
+                       (const lbm::ResidentMember*)(bt->table + (size_t)bt->cur * n_members), (const lbm::ForceMember*)bt->force_lists, row);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+  }
+  bt->force_rec.written++;
+  return LBM_SUCCESS;
+}
+
+int lbm_batch_run(lbm_batch* bt, int n_steps) {
+  if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: null batch");
+  if (n_steps < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: negative step count");
+  if (n_steps == 0) return LBM_SUCCESS;
+  lbm_ctx* c0 = bt->members[0];
+  if (bt->steps_done + n_steps > c0->capacity)
+    LBM_FAIL(LBM_FAILURE, "lbm_batch_run: %d steps requested but the av_vels record holds %d (maxIters)",
+             bt->steps_done + n_steps, c0->capacity);
+  for (lbm_ctx* c : bt->members)  // every member's records must fit before any member runs
+    if (recorder_fits(c, n_steps, "lbm_batch_run") != LBM_SUCCESS) return LBM_FAILURE;
+  if (bt->force_rec.kind != kRecForces) return batch_advance(bt, n_steps);
+  // forces armed: the call runs as the sub-calls that end at the sample steps, each advanced as a call of its length
+  // would be and followed by the row of all members (lbm_run does the same for one context, run_steps)
+  if (recorder_fits(bt->force_rec, bt->steps_done, n_steps, "lbm_batch_run", "lbm_batch_read_forces") != LBM_SUCCESS) return LBM_FAILURE;
+  const int e = bt->force_rec.every;
+  for (int t = 0; t < n_steps;) {
+    const int tt = bt->steps_done, r = tt % e;
+    const long long rec_tt = r ? (long long)tt + (e - r) : tt;  // next sample step
+    const int seg = (rec_tt - tt + 1 < n_steps - t) ? (int)(rec_tt - tt + 1) : n_steps - t;
+    if (batch_advance(bt, seg) != LBM_SUCCESS) return LBM_FAILURE;
+    if (bt->steps_done - 1 == rec_tt && take_batch_forces(bt) != LBM_SUCCESS) return LBM_FAILURE;
+    t += seg;
+  }
+  return LBM_SUCCESS;
+}
+
 int lbm_batch_sync(lbm_batch* bt) {
   if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_sync: null batch");
   int rc = LBM_SUCCESS;
@@ -3381,6 +3473,150 @@ int lbm_batch_get_info(const lbm_batch* bt, lbm_batch_info* out) {
   out->resident_steps = bt->resident ? kResidentChunk : 0;
   out->resident_min_steps = bt->resident ? c0->plan.resident_min_steps : 0;
   out->steps_done = bt->steps_done;
+  return LBM_SUCCESS;
+}
+
+// ---- obstacle forces of a batch ------------------------------------------------------------------------------------
+static void release_batch_forces(lbm_batch* bt) {
+  (void)hipSetDevice(bt->members[0]->slab[0].device);
+  bt->force_ring.reset();
+  bt->force_lists.reset();
+  bt->force_links.clear();
+  bt->force_starts.clear();
+  bt->force_link_counts.clear();
+  bt->force_bodies = bt->force_groups = 0;
+  bt->force_rec = Recorder{};
+  bt->armed[kRecForces] = 0;
+}
+
+int lbm_batch_set_forces(lbm_batch* bt, int n_bodies, const int* body_of_cell, int every, int capacity) {
+  if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: null batch");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: negative interval %d", every);
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size(), cells = (size_t)c0->p.nx * c0->p.ny;
+  // every member's labels as bytes (255: outside 0 .. n_bodies - 1), on the device while the lists are built
+  std::vector<DeviceBuf<unsigned char>> labels(every > 0 && body_of_cell ? n_members : 0);
+  if (every > 0) {
+    if (n_bodies < 1 || n_bodies > LBM_MAX_BODIES)
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: %d bodies, between 1 and LBM_MAX_BODIES = %d are possible", n_bodies, LBM_MAX_BODIES);
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: capacity %d, at least one row is needed", capacity);
+    if ((long long)capacity * (long long)n_members * n_bodies * lbm::kForceWords * (long long)sizeof(long long) >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: a ring of %d rows of %d members of %d bodies is %.2f GiB, 2 GiB or more (%d bytes per body and row)",
+               capacity, (int)n_members, n_bodies,
+               (double)capacity * (double)n_members * n_bodies * lbm::kForceWords * sizeof(long long) / 1073741824.0,
+               lbm::kForceWords * (int)sizeof(long long));
+    if (cells > ((size_t)1 << 29))
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: members of %d x %d cells; a link is cell * 8 + k - 1 in 32 bits (at most 2^29 cells)",
+               c0->p.nx, c0->p.ny);
+    for (size_t i = 0; i < n_members; i++) {
+      const Recorder& r = bt->members[i]->rec;
+      if (r.kind != kRecNone)
+        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: member %d has %s armed (%s); a batch records one kind -- disarm them with %s first", (int)i,
+                 kRecorderKinds[r.kind].name, kRecorderKinds[r.kind].setter, kRecorderKinds[r.kind].disarm);
+    }
+    for (size_t i = 0; i < labels.size(); i++) {
+      lbm_ctx* c = bt->members[i];
+      const int* src = body_of_cell + i * cells;
+      unsigned first_bad;
+      if (upload_labels(c, c->slab[0], src, n_bodies, labels[i], &first_bad) != LBM_SUCCESS) return LBM_FAILURE;
+      if (first_bad != kNoBadLabel)
+        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: member %d: the blocked cell (%d, %d) has body %d, outside 0 .. %d", (int)i,
+                 (int)(first_bad % (unsigned)c->p.nx), (int)(first_bad / (unsigned)c->p.nx), src[first_bad], n_bodies - 1);
+    }
+  }
+  // the ring may still be written by launches in flight
+  HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
+  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
+  release_batch_forces(bt);
+  if (every == 0) return LBM_SUCCESS;
+
+  auto allocate = [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * n_members * (size_t)n_bodies * lbm::kForceWords * sizeof(long long);
+    if (bt->force_ring.alloc_bytes(ring_bytes) != hipSuccess || bt->force_lists.alloc(n_members) != hipSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: cannot allocate %d rows of %d members of %d bodies (%.1f MiB); forces stay off", capacity,
+               (int)n_members, n_bodies, (double)ring_bytes / 1048576.0);
+    if (!bt->table) {  // a shape the resident kernel does not take: the gather still reads the members' lattices from the table
+      const std::vector<lbm::ResidentMember> h = member_table(bt);
+      if (bt->table.alloc(h.size()) != hipSuccess || hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: cannot allocate the member table; forces stay off");
+    }
+    bt->force_links.resize(n_members);
+    bt->force_starts.resize(n_members);
+    bt->force_link_counts.assign(n_members * (size_t)n_bodies, 0);
+    std::vector<lbm::ForceMember> lists(n_members);
+    unsigned most = 0;
+    for (size_t i = 0; i < n_members; i++) {
+      lbm_ctx* c = bt->members[i];
+      std::vector<unsigned> starts;
+      if (build_link_list("lbm_batch_set_forces", c, c->slab[0], labels.empty() ? nullptr : labels[i].get(), n_bodies, bt->force_links[i],
+                          bt->force_starts[i], starts) != LBM_SUCCESS)
+        return LBM_FAILURE;
+      for (int b = 0; b < n_bodies; b++) {
+        const unsigned links = starts[(size_t)b + 1] - starts[(size_t)b];
+        bt->force_link_counts[i * (size_t)n_bodies + (size_t)b] = (int)links;
+        if (links > most) most = links;
+      }
+      lists[i] = {bt->force_links[i].get(), bt->force_starts[i].get()};
+    }
+    HIP_TRY(LBM_FAILURE, hipMemcpy(bt->force_lists, lists.data(), lists.size() * sizeof(lists[0]), hipMemcpyHostToDevice));
+    bt->force_groups = gather_groups(most);  // the x-extent suits the largest body of any member
+    return LBM_SUCCESS;
+  };
+  if (allocate() != LBM_SUCCESS) {
+    (void)hipGetLastError();  // a failed allocation must not surface at the next launch
+    release_batch_forces(bt);
+    return LBM_FAILURE;
+  }
+  bt->force_bodies = n_bodies;
+  bt->force_rec.kind = kRecForces;
+  bt->force_rec.every = every;
+  bt->force_rec.slots = capacity;
+  bt->force_rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
+  bt->armed[kRecForces] = 1;
+  return LBM_SUCCESS;
+}
+
+int lbm_batch_read_forces(lbm_batch* bt, int max_rows, double* out, int* steps, int* n_read) {
+  if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_forces: NULL argument");
+  *n_read = 0;
+  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
+  Recorder& r = bt->force_rec;
+  const long long waiting = (r.kind == kRecForces) ? r.written - r.read : 0;
+  if (!out && !steps) {
+    *n_read = (int)waiting;
+    return LBM_SUCCESS;
+  }
+  if (!out) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_forces: NULL row output");
+  if (max_rows < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_forces: negative max_rows %d", max_rows);
+  const int n = (waiting < max_rows) ? (int)waiting : max_rows;
+  if (n > 0) {
+    // the n oldest rows wait in at most two runs of the ring; each body's two sums are rounded once and doubled
+    const size_t bodies = bt->members.size() * (size_t)bt->force_bodies, words = bodies * (size_t)lbm::kForceWords;
+    const size_t slots = (size_t)r.slots;
+    std::vector<long long> stage((size_t)n * words);
+    HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
+    for (int i = 0; i < n;) {
+      const size_t slot = (size_t)((r.read + i) % r.slots);
+      const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, bt->force_ring + slot * words, (size_t)run * words * sizeof(long long),
+                                          hipMemcpyDeviceToHost, bt->stream));
+      i += run;
+    }
+    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
+    round_forces(stage.data(), (size_t)n * bodies, out);
+  }
+  if (steps)
+    for (int i = 0; i < n; i++) steps[i] = (int)((r.ord0 + r.read + i) * r.every);
+  r.read += n;
+  *n_read = n;
+  return LBM_SUCCESS;
+}
+
+int lbm_batch_forces_links(lbm_batch* bt, int* links) {
+  if (!bt || !links) LBM_FAIL(LBM_FAILURE, "lbm_batch_forces_links: NULL argument");
+  if (bt->force_rec.kind != kRecForces)
+    LBM_FAIL(LBM_FAILURE, "lbm_batch_forces_links: the obstacle forces are not armed (lbm_batch_set_forces)");
+  for (size_t j = 0; j < bt->force_link_counts.size(); j++) links[j] = bt->force_link_counts[j];
   return LBM_SUCCESS;
 }
 
@@ -3517,6 +3753,9 @@ int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double to
       LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_batch_run_until", k.name, k.setter, k.noun);
     }
   }
+  if (bt->force_rec.kind == kRecForces)
+    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_batch_run_until", kRecorderKinds[kRecForces].name, "lbm_batch_set_forces",
+             kRecorderKinds[kRecForces].noun);
 
   HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
   if (!bt->steady_state) {  // allocated last: the set is whole (an attempt that failed half-way starts again)

@@ -43,7 +43,8 @@ constexpr int kQ = 9;
 constexpr int kNoRow = -1000000;  // "no such row in this slab"
 // what a context records while it runs, at most one at a time: the host's Recorder::kind and resident_band's REC
 constexpr int kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3, kRecFields = 4;
-// (the obstacle forces, lbm_set_forces, are a recorder kind of the host alone: force_gather runs behind the step kernels)
+// (the obstacle forces, lbm_set_forces / lbm_batch_set_forces, are a recorder kind of the host alone: force_gather and
+// force_gather_batch run behind the step kernels)
 
 // 1/3 rounded to fp32, and the two constant divisors of the equilibrium, folded in fp32
 // exactly as the reference's "2.f * c_sq" and "2.f * c_sq * c_sq" (SerialCode/d2q9-bgk.c:308,367-370)
@@ -2913,6 +2914,63 @@ __global__ __launch_bounds__(kBlock) void force_gather(const LatticeArgs a, cons
     long long v = 0;
     for (int w = 0; w < kBlock / 64; w++) v += sh[w][threadIdx.x];
     if (v != 0) atomicAdd(reinterpret_cast<unsigned long long*>(row + (size_t)body * kForceWords + threadIdx.x), (unsigned long long)v);
+  }
+}
+
+// a batch member's list of boundary links (lbm_batch_set_forces): built like a slab's, from the member's own mask and labels
+struct ForceMember {
+  const unsigned* links;
+  const unsigned* starts;  // [bodies + 1]
+};
+
+// force_gather's twin for a batch: one sample of every member, in one launch behind the sub-call that ends at the sample
+// step.  Workgroup (g, body, member) walks that member's links of that body on the member's current lattice
+// (members[member].src; `a` carries the strides all members share) exactly as force_gather does, and adds into the
+// member's and body's words of the row, [members][bodies][kForceWords] (zeroed by the host before the launch).  The
+// x-extent of the grid suits the largest body of any member: a workgroup whose (member, body) has nothing left returns
+// before the barrier, all of it.
+__global__ __launch_bounds__(kBlock) void force_gather_batch(const LatticeArgs a, const ResidentMember* members, const ForceMember* lists,
+                                                             long long* row) {
+  constexpr int L = lbm_exact::kExactLimbs;
+  __shared__ long long sh[kBlock / 64][2 * L + 1];
+  const int body = blockIdx.y, member = blockIdx.z;
+  const ForceMember list = lists[member];
+  const unsigned first = list.starts[body], end = list.starts[body + 1];
+  if (first + (unsigned)blockIdx.x * kBlock >= end) return;  // (workgroup-uniform) nothing to add: the words keep their zeros
+  const float* src = members[member].src;
+  long long fx[L], fy[L], bad = 0;
+#pragma unroll
+  for (int i = 0; i < L; i++) fx[i] = fy[i] = 0;
+  for (unsigned i = first + (unsigned)blockIdx.x * kBlock + threadIdx.x; i < end; i += gridDim.x * kBlock) {
+    const unsigned e = list.links[i];
+    const int k = (int)(e & 7u) + 1;
+    const long cell = (long)(e >> 3);
+    const int r = (int)(cell / a.nx), x = (int)(cell - (long)r * a.nx);
+    const unsigned bits = __float_as_uint(src[k * a.plane_stride + (long)r * a.row_pitch + x]);
+    if (lbm_exact::exact_sum_finite(bits)) {
+      lbm_exact::exact_sum_add(fx, bits, -link_cx(k));
+      lbm_exact::exact_sum_add(fy, bits, -link_cy(k));
+    } else {
+      bad++;
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  auto wave_total = [&](long long v, int word) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) sh[wave][word] = v;
+  };
+#pragma unroll
+  for (int i = 0; i < L; i++) {
+    wave_total(fx[i], i);
+    wave_total(fy[i], L + i);
+  }
+  wave_total(bad, 2 * L);
+  __syncthreads();
+  if (threadIdx.x < 2 * L + 1) {
+    long long v = 0;
+    for (int w = 0; w < kBlock / 64; w++) v += sh[w][threadIdx.x];
+    long long* words = row + ((size_t)member * gridDim.y + body) * kForceWords;
+    if (v != 0) atomicAdd(reinterpret_cast<unsigned long long*>(words + threadIdx.x), (unsigned long long)v);
   }
 }
 
