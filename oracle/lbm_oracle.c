@@ -214,6 +214,67 @@ void lbm_oracle_run(const lbm_oracle_params* p, float* cells, float* tmp_cells,
   }
 }
 
+/* ------------------------------------------------------------------------------------------
+ * the FAST collision (math="fast"): this project's own arithmetic, not the reference's
+ * ---------------------------------------------------------------------------------------- */
+
+float lbm_oracle_fmaf(float a, float b, float c) { return fmaf(a, b, c); }
+
+/* collide<false> of lbm-asynchronous_amd/csrc/lbm_kernels.hip.h:279-306, operation for operation: the pairwise
+ * density sum, one IEEE reciprocal, fmaf exactly where the kernel has __fmaf_rn, everything else one unfused
+ * fp32 operation in the kernel's order (the file is built with -ffp-contract=off).  Returns u_sq, the value
+ * whose native square root the kernel adds to av_vels. */
+static inline float fast_collide(const float t[Q], float omega, float r[Q])
+{
+  const float w0 = 4.f / 9.f, w1 = 1.f / 9.f, w2 = 1.f / 36.f;
+  const float rho = ((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7])) + t[8];
+  const float inv = 1.f / rho;
+  const float ux = ((t[1] + t[5] + t[8]) - (t[3] + t[6] + t[7])) * inv;
+  const float uy = ((t[2] + t[5] + t[6]) - (t[4] + t[7] + t[8])) * inv;
+  const float u_sq = fmaf(ux, ux, uy * uy);
+  const float base = fmaf(-1.5f, u_sq, 1.f);
+  const float w0r = omega * w0 * rho, w1r = omega * w1 * rho, w2r = omega * w2 * rho;
+  const float keep = 1.f - omega;
+  const float wr[Q] = { w0r, w1r, w1r, w1r, w1r, w2r, w2r, w2r, w2r };
+  float u[Q];
+  u[1] = ux;        u[2] = uy;
+  u[3] = -ux;       u[4] = -uy;
+  u[5] = ux + uy;   u[6] = uy - ux;
+  u[7] = -ux - uy;  u[8] = ux - uy;
+  r[0] = fmaf(w0r, base, keep * t[0]);
+  for (int k = 1; k < Q; k++) {
+    const float poly = fmaf(u[k], fmaf(4.5f, u[k], 3.f), base);
+    r[k] = fmaf(wr[k], poly, keep * t[k]);
+  }
+  return u_sq;
+}
+
+void lbm_oracle_collision_fast(const lbm_oracle_params* p, float* cells, const float* tmp_cells,
+                               const int* obstacles, float* usq_out)
+{
+  const size_t n = (size_t)p->nx * (size_t)p->ny;
+  for (size_t c = 0; c < n; c++) {
+    float usq = 0.f;
+    if (!obstacles[c]) usq = fast_collide(tmp_cells + Q * c, p->omega, cells + Q * c);
+    if (usq_out) usq_out[c] = usq;
+  }
+}
+
+void lbm_oracle_run_fast(const lbm_oracle_params* p, float* cells, float* tmp_cells,
+                         const int* obstacles, float* usq_maps, int n_steps)
+{
+  /* The kernels accelerate the relaxed lid row for the NEXT step and a call's first step runs accelerate_row
+   * (lbm_hip.hip:1575-1583): between two collisions the lid row is accelerated exactly once either way, so the
+   * four-sweep order gives the same lattice. */
+  const size_t n = (size_t)p->nx * (size_t)p->ny;
+  for (int tt = 0; tt < n_steps; tt++) {
+    lbm_oracle_accelerate_flow(p, cells, obstacles);
+    lbm_oracle_propagate(p, cells, tmp_cells);
+    lbm_oracle_rebound(p, cells, tmp_cells, obstacles);
+    lbm_oracle_collision_fast(p, cells, tmp_cells, obstacles, usq_maps ? usq_maps + (size_t)tt * n : NULL);
+  }
+}
+
 float lbm_oracle_calc_reynolds(const lbm_oracle_params* p, const float* cells, const int* obstacles)
 {
   /* SerialCode/d2q9-bgk.c:639-641 */

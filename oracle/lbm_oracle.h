@@ -14,7 +14,9 @@
  * into oracle/_ref/ and tests/test_oracle_vs_ref.py pins the equality.
  *
  * PARITY PINNED BY: (1) oracle/_ref/d2q9-bgk-serial (the reference itself, compiled here)
- * producing byte-identical final_state.dat on the reference's four data sets; (2) the
+ * producing byte-identical final_state.dat on the reference's four data sets (the one exception
+ * to "the reference's arithmetic" is marked as such below: the fast collision, which restates
+ * this project's own fast-math kernel and calls fmaf() where that kernel fuses); (2) the
  * reference's double-precision goldens check/ *.dat through the check.py rule (<= 1 %);
  * (3) the known-answer table of SURVEY.md section 8c.  See tests/golden/README.md.
  */
@@ -73,6 +75,24 @@ float lbm_oracle_total_density(const lbm_oracle_params* p, const float* cells);
  * (u_x, u_y, |u|, pressure); each output is nx*ny floats, row-major */
 void  lbm_oracle_final_state(const lbm_oracle_params* p, const float* cells, const int* obstacles,
                              float* u_x, float* u_y, float* u_mag, float* pressure);
+
+/* ---- The fast collision (math="fast") ----
+ * NOT the reference's arithmetic: a restatement, operation for operation, of this project's own collide<false>
+ * (lbm-asynchronous_amd/csrc/lbm_kernels.hip.h:279-306) -- pairwise density sum, one IEEE reciprocal, fmaf()
+ * exactly where the kernel spells __fmaf_rn, every other operation one unfused fp32 operation.  A fast-mode
+ * lattice has one right answer bit for bit; tests/test_fast_model.py holds this sweep to the float64 / rational
+ * BGK collision, tests/test_gpu_fast.py holds every fast kernel to this sweep.
+ *
+ * Fluid cells of `cells` receive the relaxed tmp_cells; blocked cells are untouched (lbm_oracle_rebound serves
+ * them).  usq_out (may be NULL, else nx*ny floats) receives the fp32 u_sq of every fluid cell, the value whose
+ * native square root the kernels add to av_vels; blocked cells get 0. */
+void  lbm_oracle_collision_fast(const lbm_oracle_params* p, float* cells, const float* tmp_cells,
+                                const int* obstacles, float* usq_out);
+/* n_steps x (accelerate_flow, propagate, rebound, collision_fast); usq_maps: NULL or n_steps*nx*ny floats */
+void  lbm_oracle_run_fast(const lbm_oracle_params* p, float* cells, float* tmp_cells,
+                          const int* obstacles, float* usq_maps, int n_steps);
+/* C99 fmaf, as this library was compiled: tests show that it rounds once */
+float lbm_oracle_fmaf(float a, float b, float c);
 
 /* ---- Structure-of-arrays, two-lattice, fused pull form ----
  * The reference's own fast formulation: fusion_more(), OpenMP/d2q9-bgk.c:260-498, and its

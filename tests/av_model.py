@@ -173,14 +173,18 @@ def depth(info, tile=None, packed=None):
     return max(DEPTH_TABLE[name][0](geom) for name, geom in fams)
 
 
-def speed_mode(info, tile=None):
-    """s of bound(): 1 where the engine's long passes run a SPEED = 1 kernel (stream kernels, resident_band)."""
-    return 1 if (info["lane_cells"] > 0 or info.get("resident_steps", 0) > 0) else 0
+def speed_mode(info, tile=None, fast=False):
+    """s of bound(): 1 where the engine's long passes run a SPEED = 1 kernel (stream kernels, resident_band).
+    fast: the engine was created with math="fast" and runs the scalar fast kernels, whose collide<false> takes |u| from
+    the pre-collision moments with the native sqrt in EVERY family (lbm_kernels.hip.h:305): s = 1 also for step_vec4,
+    step_scalar and step_tile."""
+    return 1 if (fast or info["lane_cells"] > 0 or info.get("resident_steps", 0) > 0) else 0
 
 
-def bound(info, tile=None, packed=None):
-    """Relative bound of |av_vels[t] - want_av(map_t)|: (depth + R) 2^-24 + s 2^-23."""
-    return (depth(info, tile, packed) + READ_ROUNDINGS) * U + speed_mode(info, tile) * ULP
+def bound(info, tile=None, packed=None, fast=False):
+    """Relative bound of |av_vels[t] - want_av(map_t)|: (depth + R) 2^-24 + s 2^-23.  The sums are the same code in
+    both math modes, so depth does not depend on `fast`; s does (speed_mode)."""
+    return (depth(info, tile, packed) + READ_ROUNDINGS) * U + speed_mode(info, tile, fast) * ULP
 
 
 # absolute allowance on av_vels[t]: cells whose u_sq is below FLT_MIN (|u| < 2^-63) may be flushed by the native sqrt;

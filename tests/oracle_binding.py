@@ -50,6 +50,9 @@ class Oracle:
         lib.lbm_oracle_fused_step_periodic.restype = F
         lib.lbm_oracle_aos_to_soa.argtypes = [I, P, P, L]
         lib.lbm_oracle_soa_to_aos.argtypes = [I, P, L, P]
+        lib.lbm_oracle_collision_fast.argtypes = [PP, P, P, P, P]
+        lib.lbm_oracle_run_fast.argtypes = [PP, P, P, P, P, I]
+        lib.lbm_oracle_fmaf.argtypes = [F, F, F]; lib.lbm_oracle_fmaf.restype = F
 
     @staticmethod
     def cparams(p):
@@ -91,6 +94,32 @@ class Oracle:
                                         f["u_x"].ctypes.data, f["u_y"].ctypes.data, f["u"].ctypes.data,
                                         f["pressure"].ctypes.data)
         return f
+
+    # ---- the fast collision (math="fast": the project's own collide<false>) ----
+    def collision_fast(self, p, tmp_cells, obstacles, cells=None):
+        """One sweep over post-propagate populations `tmp_cells` (ny,nx,9 float32): returns (relaxed cells, u_sq map).
+        Blocked cells keep what `cells` holds (default: a copy of tmp_cells)."""
+        assert tmp_cells.dtype == np.float32 and tmp_cells.flags.c_contiguous
+        ob = np.ascontiguousarray(obstacles, dtype=np.int32)
+        out = tmp_cells.copy() if cells is None else cells
+        usq = np.empty((p.ny, p.nx), dtype=np.float32)
+        self.lib.lbm_oracle_collision_fast(ctypes.byref(self.cparams(p)), out.ctypes.data, tmp_cells.ctypes.data,
+                                           ob.ctypes.data, usq.ctypes.data)
+        return out, usq
+
+    def run_fast(self, p, cells, obstacles, n_steps, want_usq=False):
+        """Advance `cells` (in place) n_steps with the fast collision; with want_usq returns the per-step u_sq maps
+        (n_steps, ny, nx float32: the pre-collision |u|^2 whose native sqrt the fast kernels add to av_vels)."""
+        assert cells.dtype == np.float32 and cells.flags.c_contiguous
+        ob = np.ascontiguousarray(obstacles, dtype=np.int32)
+        tmp = np.empty_like(cells)
+        usq = np.empty((n_steps, p.ny, p.nx), dtype=np.float32) if want_usq else None
+        self.lib.lbm_oracle_run_fast(ctypes.byref(self.cparams(p)), cells.ctypes.data, tmp.ctypes.data, ob.ctypes.data,
+                                     usq.ctypes.data if want_usq else None, n_steps)
+        return usq
+
+    def fmaf(self, a, b, c):
+        return np.float32(self.lib.lbm_oracle_fmaf(float(a), float(b), float(c)))
 
     # ---- SoA fused forms ----
     def fused_step_periodic(self, p, src, dst, obstacles):
