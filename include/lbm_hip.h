@@ -631,6 +631,61 @@ int lbm_batch_read_forces(lbm_batch* batch, int max_rows, double* out /* [n][mem
                           int* steps, int* n_read);
 int lbm_batch_forces_links(lbm_batch* batch, int* links /* [members][n_bodies] */);
 
+/* ---- lattice statistics ---------------------------------------------------------------------
+ * Whether the lattice is still healthy, as a series: its mass (conserved by every step but accelerate_flow's rounding),
+ * its momentum, the sum of |u|^2 (the distance from the low-Mach limit), the largest speed and where it is, and how
+ * many cells have stopped being numbers.  The reference has av_vels and one end-of-run total_density (:644-660), a
+ * double sum in one fixed order; a run that diverges tells neither when nor where.
+ * One row describes a whole lattice.  For a cell with populations f[0..8], in fp32 without contraction, exactly as
+ * lbm_read_final_state computes them (SerialCode/d2q9-bgk.c:684-719):
+ *     rho  = ((((((((f0+f1)+f2)+f3)+f4)+f5)+f6)+f7)+f8)
+ *     jx   = ((f1+f5)+f8) - ((f3+f6)+f7)        jy = ((f2+f5)+f6) - ((f4+f7)+f8)
+ *     ux   = jx/rho    uy = jy/rho    usq = (ux*ux)+(uy*uy)    umag = sqrtf(usq)
+ * A blocked cell contributes rho alone (it holds the populations rebound turned round, which are part of the mass); a
+ * fluid cell contributes rho, jx, jy, usq and umag.  A cell is NON-FINITE when one of rho, jx, jy, usq is not finite
+ * (a blocked cell: rho alone); such a cell contributes to nothing and is counted in `nonfinite`.
+ *     mass = sum of rho over the finite cells;  mom_x, mom_y = sums of jx, jy over the finite fluid cells;
+ *     sum_u_sq = sum of usq over them;  max_u = the largest umag among them, at the GLOBAL cell (max_x, max_y) -- of
+ *     several cells with that umag the one with the smallest y*nx+x; 0 at -1, -1 when there is no finite fluid cell.
+ * Every sum is taken EXACTLY (csrc/lbm_exact_sum.h, one float per cell and sum) and rounded to a double once: the value
+ * math.fsum gives for the same terms.  The maximum does not depend on order either.  A row therefore has the same bits
+ * from a single call, split calls, resident or per-pass kernels, 1, 2 or 3 slabs, a tiled context, a batch member, and
+ * from run to run; `mass` differs from lbm_total_density by that function's double-sum rounding only.
+ * lbm_set_stats(ctx, every, capacity): from now on, after global timestep tt (0-based, the numbering of lbm_set_frames)
+ *   with tt % every == 0, record one row of the lattice after tt+1 timesteps.  Rows wait in a device ring of `capacity`
+ *   rows (320 bytes per row and slab: the exact sums, rounded when read); an lbm_run that would record more rows than
+ *   are free fails before issuing any work.  every == 0 disarms and frees; re-arming discards unread rows.  No step
+ *   kernel records statistics: as with the forces every call runs as the sub-calls that end at its sample steps, each
+ *   followed by one memset of the row and one stats_gather launch per slab (every == 1: correct, not fast).  Recording
+ *   never changes the lattice or av_vels: they equal those of the same run issued as calls split at the sample steps.
+ *   Refused: negative every; capacity < 1; a ring of 2 GiB or more; rank contexts (lbm_create_rank*); batch members (a
+ *   batch arms them as a whole: lbm_batch_set_stats); LBM_HALO_STALE / LBM_HALO_FRESHEST (and lbm_set_halo_mode to
+ *   those while armed); a context with another recorder armed (and the other setters while this one is armed);
+ *   lbm_run_until while armed.  Not offered: the double engine, statistics inside the resident or stream kernels.
+ * lbm_read_stats: drains up to max_rows oldest rows into out[n] and steps[n] (their tt, may be NULL); out == NULL &&
+ *   steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers.
+ * lbm_batch_set_stats / lbm_batch_read_stats: the same for every member of a batch, armed on the BATCH with one `every`
+ *   and ONE ring (capacity * members * 320 bytes); rows are out[n][members].  Behind each sub-call that ends at a sample
+ *   step the batch's stream gets one memset of the row and ONE stats_gather_batch launch for all members.  Member i's
+ *   rows, lattice and av_vels are bit-identical to those of an lbm_create context armed with lbm_set_stats and advanced
+ *   by the same calls.  An lbm_batch_run without room fails before any work and moves no member's steps_done.  Refused
+ *   as lbm_batch_set_forces refuses: a member with a recorder armed, the batch's forces armed (and every member-level
+ *   setter and lbm_batch_set_forces while the statistics are armed); lbm_batch_run_until while armed.
+ */
+typedef struct {
+  double    mass;         /* exact sum, rounded once */
+  double    mom_x, mom_y;
+  double    sum_u_sq;
+  long long nonfinite;    /* cells left out of everything above and below */
+  float     max_u;        /* largest |u| of a finite fluid cell; 0 when there is none */
+  int       max_x, max_y; /* its GLOBAL cell; ties: the smallest y*nx+x; -1,-1 when there is none */
+  int       reserved;     /* 0 */
+} lbm_stats_row;          /* 56 bytes */
+int lbm_set_stats(lbm_ctx* ctx, int every, int capacity);
+int lbm_read_stats(lbm_ctx* ctx, int max_rows, lbm_stats_row* out, int* steps, int* n_read);
+int lbm_batch_set_stats(lbm_batch* batch, int every, int capacity);
+int lbm_batch_read_stats(lbm_batch* batch, int max_rows, lbm_stats_row* out /* [n][members] */, int* steps, int* n_read);
+
 /* ---- double precision -----------------------------------------------------------------------
  * The reference's programs are `float`, but its published golden results (the .dat files of check/) are its algorithm evaluated in
  * IEEE double.  A double context computes exactly that: the driver loop of SerialCode/d2q9-bgk.c:166-170 with every

@@ -53,6 +53,7 @@ ABI_SYMBOLS = (
     "lbm_run_until", "lbm_batch_run_until",
     "lbm_create_batch", "lbm_batch_member", "lbm_batch_run", "lbm_batch_sync", "lbm_batch_get_info", "lbm_destroy_batch",
     "lbm_batch_set_forces", "lbm_batch_read_forces", "lbm_batch_forces_links",
+    "lbm_set_stats", "lbm_read_stats", "lbm_batch_set_stats", "lbm_batch_read_stats",
     "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
     "lbm_double_sync", "lbm_double_read_av_vels", "lbm_double_read_cells", "lbm_double_read_final_state",
     "lbm_double_av_velocity", "lbm_double_total_density", "lbm_double_calc_reynolds",
@@ -251,6 +252,10 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_batch_set_forces.argtypes = [P, I, P, I, I]; lib.lbm_batch_set_forces.restype = I
     lib.lbm_batch_read_forces.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_forces.restype = I
     lib.lbm_batch_forces_links.argtypes = [P, P]; lib.lbm_batch_forces_links.restype = I
+    lib.lbm_set_stats.argtypes = [P, I, I]; lib.lbm_set_stats.restype = I
+    lib.lbm_read_stats.argtypes = [P, I, P, P, PI]; lib.lbm_read_stats.restype = I
+    lib.lbm_batch_set_stats.argtypes = [P, I, I]; lib.lbm_batch_set_stats.restype = I
+    lib.lbm_batch_read_stats.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_stats.restype = I
     PD = ctypes.POINTER(ctypes.c_double)
     lib.lbm_double_create.argtypes = [ctypes.POINTER(_CParamsDouble), P, P]; lib.lbm_double_create.restype = P
     lib.lbm_double_destroy.argtypes = [P]; lib.lbm_double_destroy.restype = None
@@ -664,6 +669,27 @@ class Engine:
         _check(self.lib, self.lib.lbm_forces_links(self.handle, out.ctypes.data))
         return out[:getattr(self, "_n_bodies", 0)].copy()
 
+    # -- lattice statistics (lbm_set_stats / lbm_read_stats) ---------------------------------------
+    def set_stats(self, every: int, capacity: int = 4096) -> None:
+        """Record one row of whole-lattice statistics -- mass, momentum and the sum of |u|^2 summed exactly and rounded
+        once, the largest |u| and its cell, the cells that are not finite -- after every global timestep tt with
+        tt % every == 0, for the lattice after tt + 1 steps, into a device ring of `capacity` rows.  every == 0 disarms;
+        re-arming discards unread rows."""
+        every, capacity = _stats_args(every, capacity)
+        _check(self.lib, self.lib.lbm_set_stats(self.handle, every, capacity))
+
+    def stats(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], STATS_DTYPE[n])."""
+        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
+            raise LbmError(f"stats: max_rows must be a non-negative integer or None (got {max_rows!r})")
+        n = ctypes.c_int()
+        _check(self.lib, self.lib.lbm_read_stats(self.handle, 0, None, None, ctypes.byref(n)))  # rows waiting
+        max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
+        rows = np.zeros(int(max_rows), dtype=STATS_DTYPE)
+        steps = np.empty(int(max_rows), dtype=np.int32)
+        _check(self.lib, self.lib.lbm_read_stats(self.handle, int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
+        return steps[:n.value].copy(), rows[:n.value].copy()
+
     # -- results -----------------------------------------------------------------------------
     def av_vels(self, n: int | None = None) -> np.ndarray:
         n = self.info()["steps_done"] if n is None else n
@@ -917,6 +943,25 @@ class Batch:
         rows = np.empty((int(max_rows), len(self), getattr(self, "_n_bodies", 0), 2), dtype=np.float64)
         steps = np.empty(int(max_rows), dtype=np.int32)
         _check(self.lib, self.lib.lbm_batch_read_forces(self._live(), int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
+        return steps[:n.value].copy(), rows[:n.value].copy()
+
+    # -- lattice statistics of all members (lbm_batch_set_stats / lbm_batch_read_stats) -----------------------------
+    def set_stats(self, every: int, capacity: int = 4096) -> None:
+        """Engine.set_stats for every member at once: one `every` and `capacity` for the batch, rows in one device ring,
+        one gather launch per sample whatever the number of members."""
+        every, capacity = _stats_args(every, capacity)
+        _check(self.lib, self.lib.lbm_batch_set_stats(self._live(), every, capacity))
+
+    def stats(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], STATS_DTYPE[n, members])."""
+        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
+            raise LbmError(f"stats: max_rows must be a non-negative integer or None (got {max_rows!r})")
+        n = ctypes.c_int()
+        _check(self.lib, self.lib.lbm_batch_read_stats(self._live(), 0, None, None, ctypes.byref(n)))  # rows waiting
+        max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
+        rows = np.zeros((int(max_rows), len(self)), dtype=STATS_DTYPE)
+        steps = np.empty(int(max_rows), dtype=np.int32)
+        _check(self.lib, self.lib.lbm_batch_read_stats(self._live(), int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
         return steps[:n.value].copy(), rows[:n.value].copy()
 
     def force_links(self) -> np.ndarray:
@@ -1184,6 +1229,38 @@ def write_forces(path: str, steps, rows) -> None:
                 fx += float(row[b, 0])
                 fy += float(row[b, 1])
             fh.write("%d:\t%.12E\t%.12E\n" % (tt, fx, fy))
+
+
+# lbm_stats_row of include/lbm_hip.h, 56 bytes
+STATS_DTYPE = np.dtype([("mass", "<f8"), ("mom_x", "<f8"), ("mom_y", "<f8"), ("sum_u_sq", "<f8"), ("nonfinite", "<i8"),
+                        ("max_u", "<f4"), ("max_x", "<i4"), ("max_y", "<i4"), ("reserved", "<i4")])
+
+
+def _stats_args(every, capacity) -> tuple[int, int]:
+    """Engine.set_stats' argument checks (no device needed): (every, capacity)."""
+    for name, v in (("every", every), ("capacity", capacity)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise LbmError(f"set_stats: {name} must be an integer (got {v!r})")
+        if not 0 <= int(v) <= 2147483647:
+            raise LbmError(f"set_stats: {name} must lie in [0, 2^31) (got {v})")
+    if every > 0 and capacity < 1:
+        raise LbmError(f"set_stats: capacity {capacity}, at least one row is needed")
+    return int(every), int(capacity)
+
+
+def write_stats(path: str, steps, rows) -> None:
+    """stats.dat of the command line (LBM_STATS): one line per row, tt, a colon, then tab-separated mass, mom_x, mom_y,
+    sum_u_sq and max_u as '%.12E' and max_x, max_y and nonfinite as '%d'; `steps` int[n], `rows` STATS_DTYPE[n]
+    (Engine.stats)."""
+    rows = np.asarray(rows)
+    steps = np.asarray(steps).ravel()
+    if rows.dtype != STATS_DTYPE or rows.ndim != 1 or rows.shape[0] != steps.size:
+        raise LbmError(f"write_stats: rows must be {steps.size} rows of STATS_DTYPE (got shape {rows.shape}, dtype {rows.dtype})")
+    with open(path, "w") as fh:
+        for tt, r in zip(steps.tolist(), rows):
+            fh.write("%d:\t%.12E\t%.12E\t%.12E\t%.12E\t%.12E\t%d\t%d\t%d\n" % (
+                tt, float(r["mass"]), float(r["mom_x"]), float(r["mom_y"]), float(r["sum_u_sq"]), float(r["max_u"]),
+                int(r["max_x"]), int(r["max_y"]), int(r["nonfinite"])))
 
 
 def _mean_args(every) -> int:

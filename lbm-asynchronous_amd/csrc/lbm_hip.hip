@@ -254,6 +254,7 @@ struct Slab {
   DeviceBuf<unsigned> force_starts;        // ... [bodies + 1]: where each body's links start
   DeviceBuf<long long> force_ring;         // ... [slots][bodies][lbm::kForceWords]: this slab's exact sums (lbm_exact_sum.h)
   int force_groups = 0;                    // workgroups per body of force_gather (0: the slab has no links)
+  DeviceBuf<long long> stats_ring;         // lbm_set_stats: [slots][lbm_stats::kStatsWords]: this slab's exact sums, count and max key
   // freshest-available mode (LBM_HALO_FRESHEST), allocated at its first use in this order: whole once ev_fresh[1] exists
   DeviceBuf<float> fresh_stage;          // [parity][side: 0 south halo, 1 north halo][row_pitch]: this pass's rows, if they make it
   DeviceBuf<unsigned> fresh_arrived;     // [parity][side]: id (global step + 1) of the step whose row the staging holds
@@ -403,8 +404,11 @@ struct GraphBuilder {
 // Field frames (lbm_set_field_frames) are slotted like the frames: chosen fields over a window instead of |u| everywhere.
 // Obstacle forces (lbm_set_forces) are slotted like the probes: a row of per-body sums over the boundary links.  The one
 // kind no kernel form records: every call runs as the sub-calls that end at its sample steps, each followed by force_gather.
+// Lattice statistics (lbm_set_stats) are recorded the same way, by stats_gather: a row of whole-lattice sums.
 enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean,
-       kRecFields = lbm::kRecFields, kRecForces = 5, kRecKinds = 6 };
+       kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecKinds = 7 };
+// the kinds recorded by a gather launch behind the sub-call that ends at a sample step, whatever kernels advance the lattice
+constexpr bool records_behind(int kind) { return kind == kRecForces || kind == kRecStats; }
 struct Recorder {
   int kind = kRecNone;
   int every = 0;
@@ -437,7 +441,9 @@ constexpr RecorderKind kRecorderKinds[kRecKinds] = {
     {.name = "field frames", .noun = "field frames", .record = "field frame", .setter = "lbm_set_field_frames",
      .reader = "lbm_read_field_frames", .disarm = "lbm_set_field_frames(ctx, 0, 0, 0, NULL)"},
     {.name = "obstacle forces", .noun = "forces", .record = "row", .setter = "lbm_set_forces",
-     .reader = "lbm_read_forces", .disarm = "lbm_set_forces(ctx, 0, NULL, 0, 0)"}};
+     .reader = "lbm_read_forces", .disarm = "lbm_set_forces(ctx, 0, NULL, 0, 0)"},
+    {.name = "lattice statistics", .noun = "statistics", .record = "row", .setter = "lbm_set_stats",
+     .reader = "lbm_read_stats", .disarm = "lbm_set_stats(ctx, 0, 0)"}};
 
 struct lbm_ctx {
   lbm_params p;
@@ -496,12 +502,15 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentProbes> probe_table;  // device: [members], allocated when the first member arms probes
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
   DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
-  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
-                                    // (a batch records one kind, so at most one count is non-zero; the forces are armed on
-                                    // the batch, lbm_batch_set_forces, and count as one)
-  // obstacle forces of all members (lbm_batch_set_forces): the members' own recorders stay off, the batch keeps the one
-  // recorder and the one ring; every lbm_batch_run runs as the sub-calls that end at its sample steps
-  Recorder force_rec;                            // kind kRecForces while armed
+  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
+                                    // (a batch records one kind, so at most one count is non-zero; the forces and the
+                                    // statistics are armed on the batch, lbm_batch_set_forces / lbm_batch_set_stats, and
+                                    // count as one)
+  // obstacle forces or lattice statistics of all members (lbm_batch_set_forces, lbm_batch_set_stats): the members' own
+  // recorders stay off, the batch keeps the one recorder and the one ring; every lbm_batch_run runs as the sub-calls that
+  // end at its sample steps
+  Recorder rec;                                  // kind kRecForces or kRecStats while armed
+  DeviceBuf<long long> stats_ring;               // lbm_batch_set_stats: device: [slots][members][lbm_stats::kStatsWords]
   int force_bodies = 0;                          // bodies of every member
   int force_groups = 0;                          // workgroups per (member, body) of force_gather_batch (0: no member has a link)
   std::vector<int> force_link_counts;            // [members][bodies]
@@ -1330,9 +1339,10 @@ const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = f
   using Form = const void* (*)(int);
   static const Form forms[2][kRecKinds] = {
       {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>, resident_form<false, kRecMean>,
-       resident_form<false, kRecFields>, resident_form<false, kRecNone>},  // (the forces run the plain form)
+       resident_form<false, kRecFields>, resident_form<false, kRecNone>, resident_form<false, kRecNone>},  // (the forces and the statistics
+                                                                                                           // run the plain form)
       {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>, resident_form<true, kRecMean>,
-       resident_form<true, kRecFields>, resident_form<true, kRecNone>}};
+       resident_form<true, kRecFields>, resident_form<true, kRecNone>, resident_form<true, kRecNone>}};
   return forms[batch][rec]((rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
 }
 
@@ -1525,6 +1535,26 @@ int recorder_fits(const lbm_ctx* c, int n_steps, const char* who) {
   return recorder_fits(c->rec, c->steps_done, n_steps, who, kRecorderKinds[c->rec.kind].reader);
 }
 
+// workgroups of stats_gather / stats_gather_batch for `cells` cells of a slab or member, V at a time per lane: one unit
+// per lane where the cap allows, the lanes striding over the rest
+int stats_groups(long cells, int v) {
+  const long groups = ceil_div(cells / v, lbm::kBlock);
+  return groups > lbm::kStatsMaxGroups ? lbm::kStatsMaxGroups : (int)groups;
+}
+// cells per lane and unit: four (16-byte loads) where the rows allow it
+int stats_vector(int nx) { return nx % 4 == 0 ? 4 : 1; }
+
+// one statistics sample of a slab's current lattice into `words` (zeroed in front, on the same stream)
+void launch_stats_gather(const lbm_ctx* c, const Slab& sl, long long* words) {
+  const int v = stats_vector(c->p.nx);
+  const dim3 grid(stats_groups((long)sl.rows * c->p.nx, v));
+  const unsigned cell_first = (unsigned)sl.row_first * (unsigned)c->p.nx;
+  if (v == 4)
+    hipLaunchKernelGGL(lbm::stats_gather<4>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, words);
+  else
+    hipLaunchKernelGGL(lbm::stats_gather<1>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, words);
+}
+
 // the record of the current (stored) lattice into the next slot, on every slab's compute stream: the frame of its rows,
 // or the gathered samples of the probes in its rows; or, for the mean fields, the sample of its rows added to their sums
 int take_record(lbm_ctx* c) {
@@ -1552,6 +1582,11 @@ int take_record(lbm_ctx* c) {
           if (sl.force_groups > 0)
             hipLaunchKernelGGL(lbm::force_gather, dim3(sl.force_groups, (unsigned)c->force_link_counts.size()), dim3(lbm::kBlock), 0,
                                sl.compute, lattice_args(c, sl), (const unsigned*)sl.force_links, (const unsigned*)sl.force_starts, row);
+        } else if (c->rec.kind == kRecStats) {
+          // the slab's words start from zeros (stats_gather adds into them)
+          long long* words = sl.stats_ring + slot * (size_t)lbm_stats::kStatsWords;
+          HIP_TRY(LBM_FAILURE, hipMemsetAsync(words, 0, lbm_stats::kStatsWords * sizeof(long long), sl.compute));
+          launch_stats_gather(c, sl, words);
         } else if (c->rec.kind == kRecMean)
           hipLaunchKernelGGL(lbm::mean_accumulate, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              c->p.density, sl.mean_sums, n, c->rec.order);
@@ -1590,7 +1625,7 @@ int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
     const long long records = recorded_between(c->rec, c->steps_done, (long long)c->steps_done + n_steps);
     if (run_resident(c, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
     c->steps_done += n_steps;
-    if (c->rec.kind != kRecForces) c->rec.written += records;  // recorded by the kernel itself (forces: by the caller, behind it)
+    if (!records_behind(c->rec.kind)) c->rec.written += records;  // recorded by the kernel itself (forces, statistics: by the caller, behind it)
     return LBM_SUCCESS;
   }
 
@@ -1647,17 +1682,17 @@ int run_steps(lbm_ctx* c, int n_steps, float* kernel_ms) {
 
   // resident or per-pass: decided once per call, whether a recorder (frames or probes) is armed or not
   const bool resident = c->plan.resident && n_steps >= c->plan.resident_min_steps;
-  const bool forces = (c->rec.kind == kRecForces);
-  if (c->rec.kind != kRecNone && (!resident || forces)) {
+  const bool behind = records_behind(c->rec.kind);
+  if (c->rec.kind != kRecNone && (!resident || behind)) {
     // per-pass kernels: the call runs as the sub-calls that end at its recorder steps, each followed by its frame or
-    // its sample row (the step kernels themselves record nothing).  The forces always run so, whatever kernels advance
+    // its sample row (the step kernels themselves record nothing).  The forces and the statistics always run so, whatever kernels advance
     // the lattice: a sub-call long enough for the resident kernel runs it (its plain form), as a call of that length would
     const int e = c->rec.every;
     for (int t = 0; t < n_steps;) {
       const int tt = c->steps_done, r = tt % e;
       const long long rec_tt = r ? (long long)tt + (e - r) : tt;  // next recorder step
       const int seg = (rec_tt - tt + 1 < n_steps - t) ? (int)(rec_tt - tt + 1) : n_steps - t;
-      const bool seg_resident = forces && c->plan.resident && seg >= c->plan.resident_min_steps;
+      const bool seg_resident = behind && c->plan.resident && seg >= c->plan.resident_min_steps;
       if (run_passes(c, seg, seg_resident, kernel_ms && t == 0) != LBM_SUCCESS) return LBM_FAILURE;
       if (c->steps_done - 1 == rec_tt && take_record(c) != LBM_SUCCESS) return LBM_FAILURE;
       t += seg;
@@ -2286,6 +2321,7 @@ void release_recorder(lbm_ctx* c) {
     sl.force_starts.reset();
     sl.force_ring.reset();
     sl.force_groups = 0;
+    sl.stats_ring.reset();
     sl.probe_count = 0;
   }
   c->probe_cells.clear();
@@ -2316,11 +2352,14 @@ int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate alloc
       if (bt && other == kRecForces && bt->armed[other] > 0)  // (no member arms them: the batch does)
         LBM_FAIL(LBM_FAILURE, "%s: this batch has %s armed (lbm_batch_set_forces); a batch records one kind -- disarm them with "
                  "lbm_batch_set_forces(batch, 0, NULL, 0, 0) first", setter, o.name);
+      if (bt && other == kRecStats && bt->armed[other] > 0)  // (likewise)
+        LBM_FAIL(LBM_FAILURE, "%s: this batch has %s armed (lbm_batch_set_stats); a batch records one kind -- disarm them with "
+                 "lbm_batch_set_stats(batch, 0, 0) first", setter, o.name);
       if (bt && bt->armed[other] > 0)
         LBM_FAIL(LBM_FAILURE, "%s: a member of this batch has %s armed (%s); a batch records one kind: frames, probes, mean fields or field frames",
                  setter, o.name, o.setter);
     }
-    if (c->plan.resident && kind != kRecForces) {  // (the forces record behind the plain form, which every resident shape runs)
+    if (c->plan.resident && !records_behind(kind)) {  // (the forces and the statistics record behind the plain form, which every resident shape runs)
       // the recorder forms of four-row bands defer the acceleration of the interior pair only (lbm::resident_band): the lid
       // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form must run one workgroup per CU
       if (c->plan.resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
@@ -3018,6 +3057,58 @@ int lbm_forces_links(lbm_ctx* c, int* links_per_body) {
   return LBM_SUCCESS;
 }
 
+int lbm_set_stats(lbm_ctx* c, int every, int capacity) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_stats: null context");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_stats: negative interval %d", every);
+  constexpr long long kRowBytes = lbm_stats::kStatsWords * (long long)sizeof(long long);
+  if (every > 0) {
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_stats: capacity %d, at least one row is needed", capacity);
+    if ((long long)capacity * kRowBytes >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_set_stats: a ring of %d rows is 2 GiB or more (%d bytes per row)", capacity, (int)kRowBytes);
+    if (c->ranked || c->world > 1)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_stats: not available in a multi-process (rank) context: a row's sums would be spread over the ranks");
+    if (c->batch)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_stats: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
+               "end at, so the statistics of a batch are armed on the batch, with one `every` for all members (lbm_batch_set_stats)");
+  }
+  return rearm_recorder(c, kRecStats, every, capacity, [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * (size_t)kRowBytes;
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      if (sl.stats_ring.alloc_bytes(ring_bytes) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_stats: cannot allocate %d rows (%.1f MiB per slab); statistics stay off", capacity,
+                 (double)ring_bytes / 1048576.0);
+    }
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_read_stats(lbm_ctx* c, int max_rows, lbm_stats_row* out, int* steps, int* n_read) {
+  return drain_recorder(c, kRecStats, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
+    constexpr size_t words = lbm_stats::kStatsWords;
+    const size_t slots = (size_t)c->rec.slots, n_slabs = (size_t)c->n_slabs;
+    // every slab's words of the n rows (they wait in at most two runs of its ring), gathered as rows[row][slab][words];
+    // the slabs of a row are merged and rounded by stats_row_from_words
+    std::vector<long long> rows((size_t)n * n_slabs * words), stage((size_t)n * words);
+    for (size_t s = 0; s < n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      for (int i = 0; i < n;) {
+        const size_t slot = (size_t)((c->rec.read + i) % c->rec.slots);
+        const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
+        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, sl.stats_ring + slot * words, (size_t)run * words * sizeof(long long),
+                                            hipMemcpyDeviceToHost, sl.compute));
+        i += run;
+      }
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+      for (size_t i = 0; i < (size_t)n; i++) memcpy(&rows[(i * n_slabs + s) * words], &stage[i * words], words * sizeof(long long));
+    }
+    for (int i = 0; i < n; i++) out[i] = lbm_stats::stats_row_from_words(rows.data() + (size_t)i * n_slabs * words, (int)n_slabs, c->p.nx);
+    return LBM_SUCCESS;
+  });
+}
+
 // the planes [first, first + 4) of every slab's sums, stitched by row_first; lbm_read_mean and lbm_read_mean2
 static int read_mean_planes(lbm_ctx* c, int first, double* const (&out)[4], long long* n_samples) {
   for (int s = 0; s < c->n_slabs; s++) {
@@ -3417,7 +3508,7 @@ static int take_batch_forces(lbm_batch* bt) {
   lbm_ctx* c0 = bt->members[0];
   const size_t n_members = bt->members.size();
   const size_t words = n_members * (size_t)bt->force_bodies * lbm::kForceWords;
-  long long* row = bt->force_ring + (size_t)(bt->force_rec.written % bt->force_rec.slots) * words;
+  long long* row = bt->force_ring + (size_t)(bt->rec.written % bt->rec.slots) * words;
   HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
   HIP_TRY(LBM_FAILURE, hipMemsetAsync(row, 0, words * sizeof(long long), bt->stream));
   if (bt->force_groups > 0) {
@@ -3426,7 +3517,29 @@ static int take_batch_forces(lbm_batch* bt) {
                        (const lbm::ResidentMember*)(bt->table + (size_t)bt->cur * n_members), (const lbm::ForceMember*)bt->force_lists, row);
     HIP_TRY(LBM_FAILURE, hipGetLastError());
   }
-  bt->force_rec.written++;
+  bt->rec.written++;
+  return LBM_SUCCESS;
+}
+
+// the statistics row of the members' current (stored) lattices into the next slot: the row's words of all members zeroed
+// at once, then one stats_gather_batch for all of them, on the batch's stream
+static int take_batch_stats(lbm_batch* bt) {
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  const size_t words = n_members * (size_t)lbm_stats::kStatsWords;
+  long long* row = bt->stats_ring + (size_t)(bt->rec.written % bt->rec.slots) * words;
+  const Slab& sl0 = c0->slab[0];
+  const int v = stats_vector(c0->p.nx);
+  const dim3 grid((unsigned)stats_groups((long)sl0.rows * c0->p.nx, v), 1, (unsigned)n_members);
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
+  HIP_TRY(LBM_FAILURE, hipMemsetAsync(row, 0, words * sizeof(long long), bt->stream));
+  if (v == 4)
+    hipLaunchKernelGGL(lbm::stats_gather_batch<4>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, row);
+  else
+    hipLaunchKernelGGL(lbm::stats_gather_batch<1>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, row);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  bt->rec.written++;
   return LBM_SUCCESS;
 }
 
@@ -3440,17 +3553,19 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
              bt->steps_done + n_steps, c0->capacity);
   for (lbm_ctx* c : bt->members)  // every member's records must fit before any member runs
     if (recorder_fits(c, n_steps, "lbm_batch_run") != LBM_SUCCESS) return LBM_FAILURE;
-  if (bt->force_rec.kind != kRecForces) return batch_advance(bt, n_steps);
-  // forces armed: the call runs as the sub-calls that end at the sample steps, each advanced as a call of its length
-  // would be and followed by the row of all members (lbm_run does the same for one context, run_steps)
-  if (recorder_fits(bt->force_rec, bt->steps_done, n_steps, "lbm_batch_run", "lbm_batch_read_forces") != LBM_SUCCESS) return LBM_FAILURE;
-  const int e = bt->force_rec.every;
+  if (bt->rec.kind == kRecNone) return batch_advance(bt, n_steps);
+  // forces or statistics armed: the call runs as the sub-calls that end at the sample steps, each advanced as a call of its
+  // length would be and followed by the row of all members (lbm_run does the same for one context, run_steps)
+  const bool stats = (bt->rec.kind == kRecStats);
+  if (recorder_fits(bt->rec, bt->steps_done, n_steps, "lbm_batch_run", stats ? "lbm_batch_read_stats" : "lbm_batch_read_forces") != LBM_SUCCESS)
+    return LBM_FAILURE;
+  const int e = bt->rec.every;
   for (int t = 0; t < n_steps;) {
     const int tt = bt->steps_done, r = tt % e;
     const long long rec_tt = r ? (long long)tt + (e - r) : tt;  // next sample step
     const int seg = (rec_tt - tt + 1 < n_steps - t) ? (int)(rec_tt - tt + 1) : n_steps - t;
     if (batch_advance(bt, seg) != LBM_SUCCESS) return LBM_FAILURE;
-    if (bt->steps_done - 1 == rec_tt && take_batch_forces(bt) != LBM_SUCCESS) return LBM_FAILURE;
+    if (bt->steps_done - 1 == rec_tt && (stats ? take_batch_stats(bt) : take_batch_forces(bt)) != LBM_SUCCESS) return LBM_FAILURE;
     t += seg;
   }
   return LBM_SUCCESS;
@@ -3485,7 +3600,7 @@ static void release_batch_forces(lbm_batch* bt) {
   bt->force_starts.clear();
   bt->force_link_counts.clear();
   bt->force_bodies = bt->force_groups = 0;
-  bt->force_rec = Recorder{};
+  bt->rec = Recorder{};
   bt->armed[kRecForces] = 0;
 }
 
@@ -3496,6 +3611,11 @@ int lbm_batch_set_forces(lbm_batch* bt, int n_bodies, const int* body_of_cell, i
   const size_t n_members = bt->members.size(), cells = (size_t)c0->p.nx * c0->p.ny;
   // every member's labels as bytes (255: outside 0 .. n_bodies - 1), on the device while the lists are built
   std::vector<DeviceBuf<unsigned char>> labels(every > 0 && body_of_cell ? n_members : 0);
+  if (bt->rec.kind == kRecStats) {  // the batch's one recorder is taken
+    if (every == 0) return LBM_SUCCESS;
+    LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: this batch has %s armed (lbm_batch_set_stats); a batch records one kind -- disarm them with "
+             "lbm_batch_set_stats(batch, 0, 0) first", kRecorderKinds[kRecStats].name);
+  }
   if (every > 0) {
     if (n_bodies < 1 || n_bodies > LBM_MAX_BODIES)
       LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: %d bodies, between 1 and LBM_MAX_BODIES = %d are possible", n_bodies, LBM_MAX_BODIES);
@@ -3568,10 +3688,10 @@ int lbm_batch_set_forces(lbm_batch* bt, int n_bodies, const int* body_of_cell, i
     return LBM_FAILURE;
   }
   bt->force_bodies = n_bodies;
-  bt->force_rec.kind = kRecForces;
-  bt->force_rec.every = every;
-  bt->force_rec.slots = capacity;
-  bt->force_rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
+  bt->rec.kind = kRecForces;
+  bt->rec.every = every;
+  bt->rec.slots = capacity;
+  bt->rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
   bt->armed[kRecForces] = 1;
   return LBM_SUCCESS;
 }
@@ -3580,7 +3700,7 @@ int lbm_batch_read_forces(lbm_batch* bt, int max_rows, double* out, int* steps, 
   if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_forces: NULL argument");
   *n_read = 0;
   if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
-  Recorder& r = bt->force_rec;
+  Recorder& r = bt->rec;
   const long long waiting = (r.kind == kRecForces) ? r.written - r.read : 0;
   if (!out && !steps) {
     *n_read = (int)waiting;
@@ -3614,9 +3734,109 @@ int lbm_batch_read_forces(lbm_batch* bt, int max_rows, double* out, int* steps, 
 
 int lbm_batch_forces_links(lbm_batch* bt, int* links) {
   if (!bt || !links) LBM_FAIL(LBM_FAILURE, "lbm_batch_forces_links: NULL argument");
-  if (bt->force_rec.kind != kRecForces)
+  if (bt->rec.kind != kRecForces)
     LBM_FAIL(LBM_FAILURE, "lbm_batch_forces_links: the obstacle forces are not armed (lbm_batch_set_forces)");
   for (size_t j = 0; j < bt->force_link_counts.size(); j++) links[j] = bt->force_link_counts[j];
+  return LBM_SUCCESS;
+}
+
+// ---- lattice statistics of a batch ---------------------------------------------------------------------------------
+static void release_batch_stats(lbm_batch* bt) {
+  (void)hipSetDevice(bt->members[0]->slab[0].device);
+  bt->stats_ring.reset();
+  bt->rec = Recorder{};
+  bt->armed[kRecStats] = 0;
+}
+
+int lbm_batch_set_stats(lbm_batch* bt, int every, int capacity) {
+  if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: null batch");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: negative interval %d", every);
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  const size_t row_bytes = n_members * lbm_stats::kStatsWords * sizeof(long long);
+  if (bt->rec.kind == kRecForces) {  // the batch's one recorder is taken
+    if (every == 0) return LBM_SUCCESS;
+    LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: this batch has %s armed (lbm_batch_set_forces); a batch records one kind -- disarm them with "
+             "lbm_batch_set_forces(batch, 0, NULL, 0, 0) first", kRecorderKinds[kRecForces].name);
+  }
+  if (every > 0) {
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: capacity %d, at least one row is needed", capacity);
+    if ((long long)capacity * (long long)row_bytes >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: a ring of %d rows of %d members is %.2f GiB, 2 GiB or more (%d bytes per member and row)",
+               capacity, (int)n_members, (double)capacity * (double)row_bytes / 1073741824.0,
+               lbm_stats::kStatsWords * (int)sizeof(long long));
+    for (size_t i = 0; i < n_members; i++) {
+      const Recorder& r = bt->members[i]->rec;
+      if (r.kind != kRecNone)
+        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: member %d has %s armed (%s); a batch records one kind -- disarm them with %s first", (int)i,
+                 kRecorderKinds[r.kind].name, kRecorderKinds[r.kind].setter, kRecorderKinds[r.kind].disarm);
+    }
+  }
+  // the ring may still be written by launches in flight
+  HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
+  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
+  release_batch_stats(bt);
+  if (every == 0) return LBM_SUCCESS;
+
+  auto allocate = [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * row_bytes;
+    if (bt->stats_ring.alloc_bytes(ring_bytes) != hipSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: cannot allocate %d rows of %d members (%.1f MiB); statistics stay off", capacity,
+               (int)n_members, (double)ring_bytes / 1048576.0);
+    if (!bt->table) {  // a shape the resident kernel does not take: the gather still reads the members' lattices from the table
+      const std::vector<lbm::ResidentMember> h = member_table(bt);
+      if (bt->table.alloc(h.size()) != hipSuccess || hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: cannot allocate the member table; statistics stay off");
+    }
+    return LBM_SUCCESS;
+  };
+  if (allocate() != LBM_SUCCESS) {
+    (void)hipGetLastError();  // a failed allocation must not surface at the next launch
+    release_batch_stats(bt);
+    return LBM_FAILURE;
+  }
+  bt->rec.kind = kRecStats;
+  bt->rec.every = every;
+  bt->rec.slots = capacity;
+  bt->rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
+  bt->armed[kRecStats] = 1;
+  return LBM_SUCCESS;
+}
+
+int lbm_batch_read_stats(lbm_batch* bt, int max_rows, lbm_stats_row* out, int* steps, int* n_read) {
+  if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_stats: NULL argument");
+  *n_read = 0;
+  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
+  Recorder& r = bt->rec;
+  const long long waiting = (r.kind == kRecStats) ? r.written - r.read : 0;
+  if (!out && !steps) {
+    *n_read = (int)waiting;
+    return LBM_SUCCESS;
+  }
+  if (!out) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_stats: NULL row output");
+  if (max_rows < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_stats: negative max_rows %d", max_rows);
+  const int n = (waiting < max_rows) ? (int)waiting : max_rows;
+  if (n > 0) {
+    // the n oldest rows wait in at most two runs of the ring; every member's words become its row
+    const size_t n_members = bt->members.size(), words = n_members * (size_t)lbm_stats::kStatsWords;
+    const size_t slots = (size_t)r.slots;
+    std::vector<long long> stage((size_t)n * words);
+    HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
+    for (int i = 0; i < n;) {
+      const size_t slot = (size_t)((r.read + i) % r.slots);
+      const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, bt->stats_ring + slot * words, (size_t)run * words * sizeof(long long),
+                                          hipMemcpyDeviceToHost, bt->stream));
+      i += run;
+    }
+    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
+    for (size_t j = 0; j < (size_t)n * n_members; j++)
+      out[j] = lbm_stats::stats_row_from_words(stage.data() + j * lbm_stats::kStatsWords, 1, bt->members[0]->p.nx);
+  }
+  if (steps)
+    for (int i = 0; i < n; i++) steps[i] = (int)((r.ord0 + r.read + i) * r.every);
+  r.read += n;
+  *n_read = n;
   return LBM_SUCCESS;
 }
 
@@ -3753,9 +3973,12 @@ int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double to
       LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_batch_run_until", k.name, k.setter, k.noun);
     }
   }
-  if (bt->force_rec.kind == kRecForces)
+  if (bt->rec.kind == kRecForces)
     LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_batch_run_until", kRecorderKinds[kRecForces].name, "lbm_batch_set_forces",
              kRecorderKinds[kRecForces].noun);
+  if (bt->rec.kind == kRecStats)
+    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_batch_run_until", kRecorderKinds[kRecStats].name, "lbm_batch_set_stats",
+             kRecorderKinds[kRecStats].noun);
 
   HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
   if (!bt->steady_state) {  // allocated last: the set is whole (an attempt that failed half-way starts again)

@@ -35,6 +35,7 @@
 #include <type_traits>
 
 #include "lbm_exact_sum.h"
+#include "lbm_stats_row.h"
 
 namespace lbm {
 
@@ -43,8 +44,9 @@ constexpr int kQ = 9;
 constexpr int kNoRow = -1000000;  // "no such row in this slab"
 // what a context records while it runs, at most one at a time: the host's Recorder::kind and resident_band's REC
 constexpr int kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3, kRecFields = 4;
-// (the obstacle forces, lbm_set_forces / lbm_batch_set_forces, are a recorder kind of the host alone: force_gather and
-// force_gather_batch run behind the step kernels)
+// (the obstacle forces, lbm_set_forces / lbm_batch_set_forces, and the lattice statistics, lbm_set_stats /
+// lbm_batch_set_stats, are recorder kinds of the host alone: force_gather, stats_gather and their batch twins run behind
+// the step kernels)
 
 // 1/3 rounded to fp32, and the two constant divisors of the equilibrium, folded in fp32
 // exactly as the reference's "2.f * c_sq" and "2.f * c_sq * c_sq" (SerialCode/d2q9-bgk.c:308,367-370)
@@ -2972,6 +2974,120 @@ __global__ __launch_bounds__(kBlock) void force_gather_batch(const LatticeArgs a
     long long* words = row + ((size_t)member * gridDim.y + body) * kForceWords;
     if (v != 0) atomicAdd(reinterpret_cast<unsigned long long*>(words + threadIdx.x), (unsigned long long)v);
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// lattice statistics (lbm_set_stats): exact mass, momentum and sum of |u|^2, the largest |u| and the cells that are
+// not finite, of a whole stored lattice
+// ---------------------------------------------------------------------------------------------
+// One sample (launched behind the sub-call that ends at the sample step, like force_gather).  The owned cells are dealt
+// out V at a time along x -- V = 4 where nx % 4 == 0: each of the nine planes is read with one 16-byte load per lane, the
+// mask with one 4-byte load; V = 1 otherwise -- to the lanes of a capped grid, unit g * kBlock + lane, + gridDim.x * kBlock,
+// ...: consecutive lanes read consecutive addresses of a row, and no unit reaches into the pitch padding (x + V <= nx).
+// A lane keeps four fixed-point accumulators (rho, jx, jy, usq: lbm_exact_sum.h), its count of non-finite cells and its
+// max key (lbm_stats_row.h); a cell that does not contribute is added with sign 0, so the lanes of a wave do not diverge.
+// Per cell the arithmetic is final_state's (moments_exact, IEEE divide and sqrt, no contraction).  The lanes' values are
+// combined across the wave by shuffles, across the waves through LDS, and across workgroups by 64-bit integer atomicAdd /
+// atomicMax into `words` (kStatsWords of them, zeroed by the host before the launch): every combination is exact and
+// commutes, so the words do not depend on scheduling or on the grid; no floating-point addition happens on the device.
+constexpr int kStatsMaxGroups = 512;  // two workgroups per CU: a few thousand atomics per sample (words that stay 0 send none)
+
+template <int V>
+__device__ __forceinline__ void stats_cells(const LatticeArgs& a, const float* src, const unsigned char* mask, int rows, unsigned cell_first,
+                                            long long* words) {
+  constexpr int L = lbm_exact::kExactLimbs, S = lbm_stats::kStatsSums, W = lbm_stats::kStatsKeyWord + 1;
+  __shared__ long long sh[kBlock / 64][W];
+  long long acc[S][L], bad = 0;
+  unsigned long long key = 0ull;
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int i = 0; i < L; i++) acc[j][i] = 0;
+  const long per_row = a.nx / V, n_units = (long)rows * per_row;
+  for (long u = (long)blockIdx.x * kBlock + threadIdx.x; u < n_units; u += (long)gridDim.x * kBlock) {
+    const int r = (int)(u / per_row), x = (int)(u - (long)r * per_row) * V;
+    const float* p = src + (long)r * a.row_pitch + x;
+    float f[V][kQ];
+    unsigned blocked;  // byte v: the mask of cell x + v
+    if constexpr (V == 4) {
+#pragma unroll
+      for (int k = 0; k < kQ; k++) {
+        const float4 q = *reinterpret_cast<const float4*>(p + k * a.plane_stride);
+        f[0][k] = q.x;  f[1][k] = q.y;  f[2][k] = q.z;  f[3][k] = q.w;
+      }
+      blocked = *reinterpret_cast<const unsigned*>(mask + (long)r * a.pitch + x);
+    } else {
+#pragma unroll
+      for (int k = 0; k < kQ; k++) f[0][k] = p[k * a.plane_stride];
+      blocked = mask[(long)r * a.pitch + x];
+    }
+    const unsigned cell = cell_first + (unsigned)r * (unsigned)a.nx + (unsigned)x;
+#pragma unroll
+    for (int v = 0; v < V; v++) {
+      const float(&g)[kQ] = f[v];
+      float rho, ux, uy;
+      moments_exact(g, rho, ux, uy);
+      const float jx = g[1] + g[5] + g[8] - (g[3] + g[6] + g[7]);
+      const float jy = g[2] + g[5] + g[6] - (g[4] + g[7] + g[8]);
+      const float usq = (ux * ux) + (uy * uy);
+      const float umag = sqrtf(usq);
+      const unsigned b_rho = __float_as_uint(rho), b_jx = __float_as_uint(jx), b_jy = __float_as_uint(jy), b_usq = __float_as_uint(usq);
+      const bool fluid = ((blocked >> (8 * v)) & 0xffu) == 0u;
+      const bool finite = lbm_exact::exact_sum_finite(b_rho) && (!fluid || (lbm_exact::exact_sum_finite(b_jx) && lbm_exact::exact_sum_finite(b_jy) &&
+                                                                            lbm_exact::exact_sum_finite(b_usq)));
+      const int s_all = finite ? 1 : 0, s_fluid = (finite && fluid) ? 1 : 0;
+      lbm_exact::exact_sum_add(acc[0], b_rho, s_all);
+      lbm_exact::exact_sum_add(acc[1], b_jx, s_fluid);
+      lbm_exact::exact_sum_add(acc[2], b_jy, s_fluid);
+      lbm_exact::exact_sum_add(acc[3], b_usq, s_fluid);
+      bad += finite ? 0 : 1;
+      const unsigned long long cell_key = lbm_stats::stats_key(__float_as_uint(umag), cell + (unsigned)v);
+      key = (s_fluid && cell_key > key) ? cell_key : key;
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  auto wave_total = [&](long long t, int word) {
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+    if (lane == 0) sh[wave][word] = t;
+  };
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int i = 0; i < L; i++) wave_total(acc[j][i], j * L + i);
+  wave_total(bad, lbm_stats::kStatsBadWord);
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long other = (unsigned long long)__shfl_down((long long)key, off, 64);
+    key = other > key ? other : key;
+  }
+  if (lane == 0) sh[wave][lbm_stats::kStatsKeyWord] = (long long)key;
+  __syncthreads();
+  if (threadIdx.x < W) {
+    unsigned long long* word = reinterpret_cast<unsigned long long*>(words + threadIdx.x);
+    if (threadIdx.x == lbm_stats::kStatsKeyWord) {
+      unsigned long long m = 0ull;
+      for (int w = 0; w < kBlock / 64; w++) m = (unsigned long long)sh[w][threadIdx.x] > m ? (unsigned long long)sh[w][threadIdx.x] : m;
+      if (m != 0ull) atomicMax(word, m);
+    } else {
+      long long t = 0;
+      for (int w = 0; w < kBlock / 64; w++) t += sh[w][threadIdx.x];
+      if (t != 0) atomicAdd(word, (unsigned long long)t);
+    }
+  }
+}
+
+// a slab's owned rows into its words of the ring row; cell_first: the GLOBAL index of its first owned cell
+template <int V>
+__global__ __launch_bounds__(kBlock) void stats_gather(const LatticeArgs a, int rows, unsigned cell_first, long long* words) {
+  stats_cells<V>(a, a.src, a.mask, rows, cell_first, words);
+}
+
+// stats_gather's twin for a batch: one sample of every member in one launch, workgroup (g, 0, member) on the member's
+// current lattice and mask (members[member]; `a` carries the strides all members share), into the member's words of the
+// row, [members][kStatsWords]
+template <int V>
+__global__ __launch_bounds__(kBlock) void stats_gather_batch(const LatticeArgs a, const ResidentMember* members, int rows, long long* row) {
+  const int member = blockIdx.z;
+  stats_cells<V>(a, members[member].src, members[member].mask, rows, 0u, row + (size_t)member * lbm_stats::kStatsWords);
 }
 
 }  // namespace lbm

@@ -21,10 +21,10 @@
  *                         -- what the reference's golden files were computed in.  One GPU, plain runs only: with none of
  *                         the modes below, nor LBM_GPUS other than 1, LBM_MATH=fast, LBM_TILE or LBM_PRESSURE_BIN.
  *
- * Modes: at most one of LBM_STEADY, LBM_PROBES, LBM_ANIMATION, LBM_MEAN, LBM_STATES and LBM_FORCES; the numbers in their
+ * Modes: at most one of LBM_STEADY, LBM_PROBES, LBM_ANIMATION, LBM_MEAN, LBM_STATES, LBM_FORCES and LBM_STATS; the numbers in their
  * values are plain decimal, digits only.  Every mode leaves final_state.dat unchanged.  All but LBM_STEADY leave
  * av_vels.dat unchanged where the run is resident (all four reference data sets); elsewhere it is that of the same run
- * issued as calls split at the sample steps.  LBM_PROBES, LBM_ANIMATION, LBM_STATES and LBM_FORCES record on the device
+ * issued as calls split at the sample steps.  LBM_PROBES, LBM_ANIMATION, LBM_STATES, LBM_FORCES and LBM_STATS record on the device
  * into a ring; the loop runs in segments that fill it (run_in_segments), each drained and written after it.
  *   LBM_STEADY=<tol>[:<check_every>[:<patience>]]
  *                         run to the steady state instead of for maxIters steps (lbm_run_until; check_every defaults to
@@ -53,6 +53,10 @@
  *   LBM_FORCES=<every>    write forces.dat: the force of the fluid on the obstacles (momentum exchange over the boundary
  *                         links, all blocked cells one body), one line "%d:\t%.12E\t%.12E" = tt, F_x, F_y after every step
  *                         tt with tt % every == 0, in av_vels.dat's style; lbm_set_forces, a ring of 4096 rows.
+ *   LBM_STATS=<every>     write stats.dat: the statistics of the whole lattice (lbm_set_stats, a ring of 4096 rows), one line
+ *                         "tt:\tmass\tmom_x\tmom_y\tsum_u_sq\tmax_u\tmax_x\tmax_y\tnonfinite" after every step tt with
+ *                         tt % every == 0, the reals as %.12E.  If the last row counts cells that are not finite, one line on
+ *                         stderr names the first sampled step that did.
  */
 #include <math.h>
 #include <stdio.h>
@@ -116,7 +120,9 @@ typedef struct {
   const lbm_options* opt;    /* LBM_STATES: its window is set */
   const int* obstacles;
   void* records; int* steps; /* the host copy of the ring: cap records and their timesteps */
-  FILE* fp;                  /* probes.dat, forces.dat */
+  FILE* fp;                  /* probes.dat, forces.dat, stats.dat */
+  int bad_step;              /* LBM_STATS: the first sampled step with cells that are not finite (-1: none so far) ... */
+  long long bad_last;        /* ... and how many the last row counted */
 } recording;
 
 /* the timestep loop of the recording modes: segments of cap samples, the ring drained after each */
@@ -176,6 +182,20 @@ static void drain_forces(recording* r, int cap)
   for (int i = 0; i < n_read; i++) fprintf(r->fp, "%d:\t%.12E\t%.12E\n", r->steps[i], rows[2 * i], rows[2 * i + 1]);
 }
 
+static void drain_stats(recording* r, int cap)
+{
+  const lbm_stats_row* rows = (const lbm_stats_row*)r->records;
+  int n_read = 0;
+  must(lbm_read_stats(r->ctx, cap, (lbm_stats_row*)r->records, r->steps, &n_read));
+  for (int i = 0; i < n_read; i++) {
+    const lbm_stats_row* v = rows + i;
+    fprintf(r->fp, "%d:\t%.12E\t%.12E\t%.12E\t%.12E\t%.12E\t%d\t%d\t%lld\n", r->steps[i], v->mass, v->mom_x, v->mom_y, v->sum_u_sq,
+            (double)v->max_u, v->max_x, v->max_y, v->nonfinite);
+    if (v->nonfinite > 0 && r->bad_step < 0) r->bad_step = r->steps[i];
+    r->bad_last = v->nonfinite;
+  }
+}
+
 /* the rest of a recording run once the device's ring is armed: allocate its host copy, open the file, run in segments */
 static void record(recording* r, int cap, size_t record_bytes, const char* no_memory, const char* file, void (*drain)(recording*, int))
 {
@@ -191,7 +211,7 @@ static void record(recording* r, int cap, size_t record_bytes, const char* no_me
 /* the recording modes: each case holds what differs -- record size, ring budget, arming call, output and drain function */
 static void run_recording(lbm_ctx* ctx, const lbm_params* params, const lbm_options* opt, const int* obstacles)
 {
-  recording r = {ctx, params, opt, obstacles, NULL, NULL, NULL};
+  recording r = {ctx, params, opt, obstacles, NULL, NULL, NULL, -1, 0};
   const int every = opt->every, max_iters = params->max_iters;
   size_t record_bytes;
   int cap;
@@ -215,6 +235,14 @@ static void run_recording(lbm_ctx* ctx, const lbm_params* params, const lbm_opti
       cap = ring_capacity(64UL << 20, record_bytes, max_iters, every);
       must(lbm_set_probes(ctx, opt->n_probes, opt->probes, every, cap));
       record(&r, cap, record_bytes, "cannot allocate memory for probe samples", LBM_PROBESFILE, drain_probes);
+      break;
+    case LBM_MODE_STATS: /* a ring of 4096 rows */
+      record_bytes = sizeof(lbm_stats_row);
+      cap = ring_capacity(4096 * record_bytes, record_bytes, max_iters, every);
+      must(lbm_set_stats(ctx, every, cap));
+      record(&r, cap, record_bytes, "cannot allocate memory for statistics rows", LBM_STATSFILE, drain_stats);
+      if (r.bad_last > 0)
+        fprintf(stderr, "%lld cells of the lattice are not finite; the first sampled step with such cells was %d\n", r.bad_last, r.bad_step);
       break;
     default: /* LBM_MODE_FORCES: a ring of 4096 rows */
       record_bytes = 2 * sizeof(double);

@@ -19,6 +19,7 @@
 #define LBM_PROBESFILE     "probes.dat"      /* LBM_PROBES: the time series at the probed cells (no counterpart) */
 #define LBM_MEANSTATEFILE  "mean_state.dat"  /* LBM_MEAN: final_state.dat's format with the time-averaged fields (no counterpart) */
 #define LBM_FORCESFILE     "forces.dat"      /* LBM_FORCES: the force on the obstacles at the sample steps (no counterpart) */
+#define LBM_STATSFILE      "stats.dat"       /* LBM_STATS: the lattice statistics at the sample steps (no counterpart) */
 #define LBM_RMSSTATEFILE   "rms_state.dat"   /* LBM_MEAN_ORDER=2: the same format with rms u_x, rms u_y, <u'v'>, rms pressure */
 
 /* message to stderr + exit(EXIT_FAILURE), the reference's die() (:745-751) */

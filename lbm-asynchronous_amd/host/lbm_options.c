@@ -13,7 +13,7 @@
 enum { ROW_DOUBLE = 0, ROW_TILE = LBM_N_MODES, ROW_MEAN_ORDER, ROW_PRESSURE_BIN, ROW_GPUS, ROW_MATH_FAST, N_ROWS };
 static const struct { const char* name; int not_offered; } rows[N_ROWS] = {
   {"LBM_PRECISION=double", 0}, {"LBM_STEADY", 1}, {"LBM_PROBES", 1}, {"LBM_ANIMATION", 1}, {"LBM_MEAN", 1},
-  {"LBM_STATES", 0}, {"LBM_FORCES", 0},
+  {"LBM_STATES", 0}, {"LBM_FORCES", 0}, {"LBM_STATS", 1},
   {"LBM_TILE", 1}, {"LBM_MEAN_ORDER", 1}, {"LBM_PRESSURE_BIN", 1}, {"LBM_GPUS", 1}, {"LBM_MATH=fast", 1},
 };
 
@@ -27,8 +27,8 @@ static void refuse(int earlier, int later)
   lbm_die(message, __LINE__, __FILE__);
 }
 
-/* The one number format of LBM_PROBES, LBM_MEAN, LBM_MEAN_ORDER, LBM_STATES and LBM_FORCES: decimal digits only (no sign,
-   no space, no exponent), at most 2147483647.  Reads one at *s and returns the character after it, which the caller
+/* The one number format of LBM_PROBES, LBM_MEAN, LBM_MEAN_ORDER, LBM_STATES, LBM_FORCES and LBM_STATS: decimal digits only (no
+   sign, no space, no exponent), at most 2147483647.  Reads one at *s and returns the character after it, which the caller
    compares with the separator it expects: that character is skipped, unless it is the '\0' at the end.  -1: no such
    number here. */
 static int scan_number(const char** s, int* value)
@@ -112,6 +112,8 @@ void lbm_parse_options(const char* (*lookup)(const char*), lbm_options* out)
   if ((v = value[LBM_MODE_STATES])) parse_states(v, &every[LBM_MODE_STATES], &out->window);
   if ((v = value[LBM_MODE_FORCES]) && (scan_number(&v, &every[LBM_MODE_FORCES]) != '\0' || every[LBM_MODE_FORCES] < 1))
     lbm_die("could not read LBM_FORCES: expected <every> with every >= 1", __LINE__, __FILE__);
+  if ((v = value[LBM_MODE_STATS]) && (scan_number(&v, &every[LBM_MODE_STATS]) != '\0' || every[LBM_MODE_STATS] < 1))
+    lbm_die("could not read LBM_STATS: expected <every> with every >= 1", __LINE__, __FILE__);
   out->is_double = (v = value[ROW_DOUBLE]) && !strcmp(v, "double");
   if (v && !out->is_double && strcmp(v, "single")) lbm_die("could not read LBM_PRECISION: expected single or double", __LINE__, __FILE__);
   out->n_gpus = value[ROW_GPUS] ? atoi(value[ROW_GPUS]) : 1;

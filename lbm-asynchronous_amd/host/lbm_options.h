@@ -11,7 +11,7 @@
    lbm_options.c, whose row 0 is LBM_PRECISION=double. */
 typedef enum {
   LBM_MODE_PLAIN = 0, LBM_MODE_STEADY, LBM_MODE_PROBES, LBM_MODE_ANIMATION, LBM_MODE_MEAN, LBM_MODE_STATES, LBM_MODE_FORCES,
-  LBM_N_MODES
+  LBM_MODE_STATS, LBM_N_MODES
 } lbm_mode;
 
 typedef struct {
