@@ -686,6 +686,67 @@ int lbm_read_stats(lbm_ctx* ctx, int max_rows, lbm_stats_row* out, int* steps, i
 int lbm_batch_set_stats(lbm_batch* batch, int every, int capacity);
 int lbm_batch_read_stats(lbm_batch* batch, int max_rows, lbm_stats_row* out /* [n][members] */, int* steps, int* n_read);
 
+/* ---- velocity residuals ---------------------------------------------------------------------
+ * How much the velocity field changed since it was last looked at, and where it still changes: the residual every CFD
+ * code reports.  lbm_run_until decides on the change of ONE number, the mean of av_vels, in which local motion can
+ * cancel; lbm_set_stats gives the sum of |u|^2 of an instant, not a change.
+ * The REMEMBERED FIELD of a cell is the pair (u_x, u_y) that lbm_read_final_state gives for it: a fluid cell jx/rho,
+ * jy/rho in fp32 with IEEE divide and no contraction (rho, jx, jy as in the statistics' text above), a blocked cell 0, 0.
+ * lbm_set_residual(ctx, every, capacity) with every >= 1 takes the BASELINE: the field of the current lattice, after
+ *   steps_done steps, stored in two planes float[rows][nx] per slab (8 bytes per owned cell).  From then on, after global
+ *   timestep tt (0-based, the numbering of lbm_set_frames) with tt % every == 0, one row of the lattice after tt+1
+ *   timesteps is recorded.  For every fluid cell, in fp32, no contraction, with (pux, puy) the remembered field:
+ *       dux = ux - pux      duy = uy - puy      dsq = (dux*dux) + (duy*duy)      dmag = sqrtf(dsq)
+ *       usq = (ux*ux) + (uy*uy)
+ *   A fluid cell is NON-FINITE when one of rho, jx, jy, usq (the statistics' rule) or dsq is not finite; such a cell
+ *   contributes to nothing and is counted in `nonfinite`.  Blocked cells contribute to nothing and are never counted.
+ *   After the row is taken, the remembered field of every owned cell becomes the current (u_x, u_y), whatever its value.
+ *       sum_du_sq, sum_u_sq = the sums of dsq and of usq over the finite fluid cells;  max_du = the largest dmag among
+ *       them, at the GLOBAL cell (max_x, max_y) -- of several cells with that dmag the one with the smallest y*nx+x; 0 at
+ *       -1, -1 when there is no finite fluid cell;  span = the timesteps between the remembered field and this sample:
+ *       tt + 1 - (steps_done at arming) for the first row after arming, `every` afterwards.
+ *   The relative L2 residual a user plots is sqrt(sum_du_sq / sum_u_sq), taken on the host in double.
+ *   Every sum is taken EXACTLY (csrc/lbm_exact_sum.h) and rounded to a double once -- the value math.fsum gives for the
+ *   same terms -- and the maximum does not depend on order.  A row therefore has the same bits from a single call, split
+ *   calls, resident or per-pass sub-calls, 1, 2 or 3 slabs, a tiled context, a batch member, and from run to run.  With
+ *   nonfinite == 0, sum_u_sq has the bits of lbm_stats_row.sum_u_sq at the same step.
+ *   Rows wait in a device ring of `capacity` rows (160 bytes per row and slab: 2 x 9 limbs, the count, the key); an
+ *   lbm_run that would record more rows than are free fails before issuing any work.  every == 0 disarms and frees the
+ *   planes and the ring; arming again takes a new baseline and discards unread rows.  No step kernel records residuals:
+ *   as with the statistics every call runs as the sub-calls that end at its sample steps, each followed by one memset of
+ *   the row and one residual_gather launch per slab (every == 1: correct, not fast).  Recording never changes the lattice
+ *   or av_vels: they equal those of the same run issued as calls split at the sample steps.  A failed allocation of the
+ *   planes says their size and leaves the context disarmed.
+ *   Refused, as lbm_set_stats refuses: negative every; capacity < 1; a ring of 2 GiB or more; rank contexts
+ *   (lbm_create_rank*); batch members (a batch arms them as a whole: lbm_batch_set_residual); LBM_HALO_STALE /
+ *   LBM_HALO_FRESHEST (and lbm_set_halo_mode to those while armed); a context with another recorder armed (and the other
+ *   setters while this one is armed); lbm_run_until while armed.  Not offered: density or pressure residuals, the double
+ *   engine, a residual criterion for lbm_run_until, recording inside the resident or stream kernels.
+ * lbm_read_residual: drains up to max_rows oldest rows into out[n] and steps[n] (their tt, may be NULL); out == NULL &&
+ *   steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers.
+ * lbm_batch_set_residual / lbm_batch_read_residual: the same for every member of a batch, armed on the BATCH with one
+ *   `every`, ONE ring (capacity * members * 160 bytes) and the planes of all members in one allocation; rows are
+ *   out[n][members].  Arming takes ONE residual_gather_batch launch for the baselines of all members, and behind each
+ *   sub-call that ends at a sample step the batch's stream gets one memset of the row and ONE launch for all members.
+ *   Member i's rows, lattice and av_vels are bit-identical to those of an lbm_create context armed with lbm_set_residual
+ *   and advanced by the same calls.  An lbm_batch_run without room fails before any work and moves no member's
+ *   steps_done.  Refused as lbm_batch_set_stats refuses: a member with a recorder armed, the batch's forces or statistics
+ *   armed (and every member-level setter, lbm_batch_set_forces and lbm_batch_set_stats while the residuals are armed);
+ *   lbm_batch_run_until while armed.
+ */
+typedef struct {
+  double    sum_du_sq;    /* exact sum of dsq over the finite fluid cells, rounded once (math.fsum's value) */
+  double    sum_u_sq;     /* exact sum of usq over the same cells */
+  long long nonfinite;
+  float     max_du;       /* largest dmag of a finite fluid cell; 0 when there is none */
+  int       max_x, max_y; /* its GLOBAL cell; ties: the smallest y*nx+x; -1,-1 when there is none */
+  int       span;         /* timesteps between the remembered field and this sample */
+} lbm_residual_row;       /* 40 bytes; offsets 0 8 16 24 28 32 36 */
+int lbm_set_residual(lbm_ctx* ctx, int every, int capacity);
+int lbm_read_residual(lbm_ctx* ctx, int max_rows, lbm_residual_row* out, int* steps, int* n_read);
+int lbm_batch_set_residual(lbm_batch* batch, int every, int capacity);
+int lbm_batch_read_residual(lbm_batch* batch, int max_rows, lbm_residual_row* out /* [n][members] */, int* steps, int* n_read);
+
 /* ---- double precision -----------------------------------------------------------------------
  * The reference's programs are `float`, but its published golden results (the .dat files of check/) are its algorithm evaluated in
  * IEEE double.  A double context computes exactly that: the driver loop of SerialCode/d2q9-bgk.c:166-170 with every

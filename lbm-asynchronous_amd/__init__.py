@@ -54,6 +54,7 @@ ABI_SYMBOLS = (
     "lbm_create_batch", "lbm_batch_member", "lbm_batch_run", "lbm_batch_sync", "lbm_batch_get_info", "lbm_destroy_batch",
     "lbm_batch_set_forces", "lbm_batch_read_forces", "lbm_batch_forces_links",
     "lbm_set_stats", "lbm_read_stats", "lbm_batch_set_stats", "lbm_batch_read_stats",
+    "lbm_set_residual", "lbm_read_residual", "lbm_batch_set_residual", "lbm_batch_read_residual",
     "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
     "lbm_double_sync", "lbm_double_read_av_vels", "lbm_double_read_cells", "lbm_double_read_final_state",
     "lbm_double_av_velocity", "lbm_double_total_density", "lbm_double_calc_reynolds",
@@ -256,6 +257,10 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_read_stats.argtypes = [P, I, P, P, PI]; lib.lbm_read_stats.restype = I
     lib.lbm_batch_set_stats.argtypes = [P, I, I]; lib.lbm_batch_set_stats.restype = I
     lib.lbm_batch_read_stats.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_stats.restype = I
+    lib.lbm_set_residual.argtypes = [P, I, I]; lib.lbm_set_residual.restype = I
+    lib.lbm_read_residual.argtypes = [P, I, P, P, PI]; lib.lbm_read_residual.restype = I
+    lib.lbm_batch_set_residual.argtypes = [P, I, I]; lib.lbm_batch_set_residual.restype = I
+    lib.lbm_batch_read_residual.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_residual.restype = I
     PD = ctypes.POINTER(ctypes.c_double)
     lib.lbm_double_create.argtypes = [ctypes.POINTER(_CParamsDouble), P, P]; lib.lbm_double_create.restype = P
     lib.lbm_double_destroy.argtypes = [P]; lib.lbm_double_destroy.restype = None
@@ -690,6 +695,28 @@ class Engine:
         _check(self.lib, self.lib.lbm_read_stats(self.handle, int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
         return steps[:n.value].copy(), rows[:n.value].copy()
 
+    # -- velocity residuals (lbm_set_residual / lbm_read_residual) ---------------------------------
+    def set_residual(self, every: int, capacity: int = 4096) -> None:
+        """Remember the velocity field of the current lattice (the baseline) and, after every global timestep tt with
+        tt % every == 0, record one row for the lattice after tt + 1 steps: the exact sums of |u - u_remembered|^2 and of
+        |u|^2 over the finite fluid cells, the largest |u - u_remembered| and its cell, the fluid cells that are not
+        finite, and the steps the comparison spans; the sample then becomes the remembered field.  Rows wait in a device
+        ring of `capacity` rows.  every == 0 disarms; re-arming takes a new baseline and discards unread rows."""
+        every, capacity = _residual_args(every, capacity)
+        _check(self.lib, self.lib.lbm_set_residual(self.handle, every, capacity))
+
+    def residuals(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], RESIDUAL_DTYPE[n])."""
+        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
+            raise LbmError(f"residuals: max_rows must be a non-negative integer or None (got {max_rows!r})")
+        n = ctypes.c_int()
+        _check(self.lib, self.lib.lbm_read_residual(self.handle, 0, None, None, ctypes.byref(n)))  # rows waiting
+        max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
+        rows = np.zeros(int(max_rows), dtype=RESIDUAL_DTYPE)
+        steps = np.empty(int(max_rows), dtype=np.int32)
+        _check(self.lib, self.lib.lbm_read_residual(self.handle, int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
+        return steps[:n.value].copy(), rows[:n.value].copy()
+
     # -- results -----------------------------------------------------------------------------
     def av_vels(self, n: int | None = None) -> np.ndarray:
         n = self.info()["steps_done"] if n is None else n
@@ -962,6 +989,25 @@ class Batch:
         rows = np.zeros((int(max_rows), len(self)), dtype=STATS_DTYPE)
         steps = np.empty(int(max_rows), dtype=np.int32)
         _check(self.lib, self.lib.lbm_batch_read_stats(self._live(), int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
+        return steps[:n.value].copy(), rows[:n.value].copy()
+
+    # -- velocity residuals of all members (lbm_batch_set_residual / lbm_batch_read_residual) ------------------------
+    def set_residual(self, every: int, capacity: int = 4096) -> None:
+        """Engine.set_residual for every member at once: one `every` and `capacity` for the batch, rows in one device
+        ring, one gather launch for the baselines and one per sample whatever the number of members."""
+        every, capacity = _residual_args(every, capacity)
+        _check(self.lib, self.lib.lbm_batch_set_residual(self._live(), every, capacity))
+
+    def residuals(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], RESIDUAL_DTYPE[n, members])."""
+        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
+            raise LbmError(f"residuals: max_rows must be a non-negative integer or None (got {max_rows!r})")
+        n = ctypes.c_int()
+        _check(self.lib, self.lib.lbm_batch_read_residual(self._live(), 0, None, None, ctypes.byref(n)))  # rows waiting
+        max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
+        rows = np.zeros((int(max_rows), len(self)), dtype=RESIDUAL_DTYPE)
+        steps = np.empty(int(max_rows), dtype=np.int32)
+        _check(self.lib, self.lib.lbm_batch_read_residual(self._live(), int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
         return steps[:n.value].copy(), rows[:n.value].copy()
 
     def force_links(self) -> np.ndarray:
@@ -1261,6 +1307,50 @@ def write_stats(path: str, steps, rows) -> None:
             fh.write("%d:\t%.12E\t%.12E\t%.12E\t%.12E\t%.12E\t%d\t%d\t%d\n" % (
                 tt, float(r["mass"]), float(r["mom_x"]), float(r["mom_y"]), float(r["sum_u_sq"]), float(r["max_u"]),
                 int(r["max_x"]), int(r["max_y"]), int(r["nonfinite"])))
+
+
+# lbm_residual_row of include/lbm_hip.h, 40 bytes
+RESIDUAL_DTYPE = np.dtype([("sum_du_sq", "<f8"), ("sum_u_sq", "<f8"), ("nonfinite", "<i8"), ("max_du", "<f4"), ("max_x", "<i4"),
+                           ("max_y", "<i4"), ("span", "<i4")])
+
+
+def _residual_args(every, capacity) -> tuple[int, int]:
+    """Engine.set_residual's argument checks (no device needed): (every, capacity)."""
+    for name, v in (("every", every), ("capacity", capacity)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise LbmError(f"set_residual: {name} must be an integer (got {v!r})")
+        if not 0 <= int(v) <= 2147483647:
+            raise LbmError(f"set_residual: {name} must lie in [0, 2^31) (got {v})")
+    if every > 0 and capacity < 1:
+        raise LbmError(f"set_residual: capacity {capacity}, at least one row is needed")
+    return int(every), int(capacity)
+
+
+def residual_l2(rows) -> np.ndarray:
+    """The relative L2 residual of rows of RESIDUAL_DTYPE (any shape), sqrt(sum_du_sq / sum_u_sq) in float64: 0.0 where
+    both sums are 0 (a fluid at rest that stays at rest), inf where only sum_u_sq is."""
+    rows = np.asarray(rows)
+    du = np.asarray(rows["sum_du_sq"], dtype=np.float64)
+    u = np.asarray(rows["sum_u_sq"], dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where((du == 0.0) & (u == 0.0), 0.0, du / u)
+    return np.sqrt(ratio)
+
+
+def write_residuals(path: str, steps, rows) -> None:
+    """One line per row in write_stats' style: tt, a colon, then tab-separated the relative L2 residual (residual_l2),
+    sum_du_sq, sum_u_sq and max_du as '%.12E' and max_x, max_y, span and nonfinite as '%d'; `steps` int[n], `rows`
+    RESIDUAL_DTYPE[n] (Engine.residuals)."""
+    rows = np.asarray(rows)
+    steps = np.asarray(steps).ravel()
+    if rows.dtype != RESIDUAL_DTYPE or rows.ndim != 1 or rows.shape[0] != steps.size:
+        raise LbmError(f"write_residuals: rows must be {steps.size} rows of RESIDUAL_DTYPE (got shape {rows.shape}, dtype {rows.dtype})")
+    l2 = residual_l2(rows)
+    with open(path, "w") as fh:
+        for tt, r, v in zip(steps.tolist(), rows, l2.tolist()):
+            fh.write("%d:\t%.12E\t%.12E\t%.12E\t%.12E\t%d\t%d\t%d\t%d\n" % (
+                tt, v, float(r["sum_du_sq"]), float(r["sum_u_sq"]), float(r["max_du"]),
+                int(r["max_x"]), int(r["max_y"]), int(r["span"]), int(r["nonfinite"])))
 
 
 def _mean_args(every) -> int:

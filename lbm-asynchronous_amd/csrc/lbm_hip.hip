@@ -255,6 +255,8 @@ struct Slab {
   DeviceBuf<long long> force_ring;         // ... [slots][bodies][lbm::kForceWords]: this slab's exact sums (lbm_exact_sum.h)
   int force_groups = 0;                    // workgroups per body of force_gather (0: the slab has no links)
   DeviceBuf<long long> stats_ring;         // lbm_set_stats: [slots][lbm_stats::kStatsWords]: this slab's exact sums, count and max key
+  DeviceBuf<long long> residual_ring;      // lbm_set_residual: [slots][lbm_residual::kResidualWords]: likewise
+  DeviceBuf<float> residual_planes;        // ... [2][rows][nx]: the remembered u_x and u_y of this slab's owned cells
   // freshest-available mode (LBM_HALO_FRESHEST), allocated at its first use in this order: whole once ev_fresh[1] exists
   DeviceBuf<float> fresh_stage;          // [parity][side: 0 south halo, 1 north halo][row_pitch]: this pass's rows, if they make it
   DeviceBuf<unsigned> fresh_arrived;     // [parity][side]: id (global step + 1) of the step whose row the staging holds
@@ -405,10 +407,12 @@ struct GraphBuilder {
 // Obstacle forces (lbm_set_forces) are slotted like the probes: a row of per-body sums over the boundary links.  The one
 // kind no kernel form records: every call runs as the sub-calls that end at its sample steps, each followed by force_gather.
 // Lattice statistics (lbm_set_stats) are recorded the same way, by stats_gather: a row of whole-lattice sums.
+// Velocity residuals (lbm_set_residual) likewise, by residual_gather, which also keeps a field between the samples: the
+// velocities of the last sample (at first: of arming), which every sample compares with and replaces.
 enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean,
-       kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecKinds = 7 };
+       kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecResidual = 7, kRecKinds = 8 };
 // the kinds recorded by a gather launch behind the sub-call that ends at a sample step, whatever kernels advance the lattice
-constexpr bool records_behind(int kind) { return kind == kRecForces || kind == kRecStats; }
+constexpr bool records_behind(int kind) { return kind == kRecForces || kind == kRecStats || kind == kRecResidual; }
 struct Recorder {
   int kind = kRecNone;
   int every = 0;
@@ -419,6 +423,7 @@ struct Recorder {
   int order = 0;            // mean fields: 1 = the four sums, 2 = also the four sums of products (lbm_set_mean_order)
   int fields = 0;           // field frames: the LBM_FIELD_* bits ...
   lbm_window window = {0, 0, 0, 0};  // ... and the window, global cells
+  int base_steps = 0;       // velocity residuals: steps_done at arming, the step of the baseline (the first row's span)
 };
 // what differs between the kinds in the host's messages (indexed by kind; kRecNone keeps the empty defaults)
 struct RecorderKind {
@@ -443,7 +448,9 @@ constexpr RecorderKind kRecorderKinds[kRecKinds] = {
     {.name = "obstacle forces", .noun = "forces", .record = "row", .setter = "lbm_set_forces",
      .reader = "lbm_read_forces", .disarm = "lbm_set_forces(ctx, 0, NULL, 0, 0)"},
     {.name = "lattice statistics", .noun = "statistics", .record = "row", .setter = "lbm_set_stats",
-     .reader = "lbm_read_stats", .disarm = "lbm_set_stats(ctx, 0, 0)"}};
+     .reader = "lbm_read_stats", .disarm = "lbm_set_stats(ctx, 0, 0)"},
+    {.name = "velocity residuals", .noun = "residuals", .record = "row", .setter = "lbm_set_residual",
+     .reader = "lbm_read_residual", .disarm = "lbm_set_residual(ctx, 0, 0)"}};
 
 struct lbm_ctx {
   lbm_params p;
@@ -502,15 +509,17 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentProbes> probe_table;  // device: [members], allocated when the first member arms probes
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
   DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
-  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
-                                    // (a batch records one kind, so at most one count is non-zero; the forces and the
-                                    // statistics are armed on the batch, lbm_batch_set_forces / lbm_batch_set_stats, and
-                                    // count as one)
-  // obstacle forces or lattice statistics of all members (lbm_batch_set_forces, lbm_batch_set_stats): the members' own
-  // recorders stay off, the batch keeps the one recorder and the one ring; every lbm_batch_run runs as the sub-calls that
-  // end at its sample steps
-  Recorder rec;                                  // kind kRecForces or kRecStats while armed
+  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
+                                    // (a batch records one kind, so at most one count is non-zero; the forces, the
+                                    // statistics and the residuals are armed on the batch, lbm_batch_set_forces /
+                                    // lbm_batch_set_stats / lbm_batch_set_residual, and count as one)
+  // obstacle forces, lattice statistics or velocity residuals of all members (lbm_batch_set_forces, lbm_batch_set_stats,
+  // lbm_batch_set_residual): the members' own recorders stay off, the batch keeps the one recorder and the one ring; every
+  // lbm_batch_run runs as the sub-calls that end at its sample steps
+  Recorder rec;                                  // kind kRecForces, kRecStats or kRecResidual while armed
   DeviceBuf<long long> stats_ring;               // lbm_batch_set_stats: device: [slots][members][lbm_stats::kStatsWords]
+  DeviceBuf<long long> residual_ring;            // lbm_batch_set_residual: device: [slots][members][lbm_residual::kResidualWords]
+  DeviceBuf<float> residual_planes;              // ... device: [members][2][rows][nx]: the members' remembered u_x and u_y
   int force_bodies = 0;                          // bodies of every member
   int force_groups = 0;                          // workgroups per (member, body) of force_gather_batch (0: no member has a link)
   std::vector<int> force_link_counts;            // [members][bodies]
@@ -525,6 +534,28 @@ struct lbm_batch {
   Event ev_steady;                  // ... behind this event
   DeviceBuf<lbm::SteadyState> steady_state;    // device: [members]
 };
+
+// The kinds armed on a batch as a whole (lbm_batch::rec): what differs between them in the messages and in lbm_batch_run,
+// where take() records the row of all members behind a sub-call that ends at a sample step
+static int take_batch_forces(lbm_batch* bt);
+static int take_batch_stats(lbm_batch* bt);
+static int take_batch_residual(lbm_batch* bt);
+struct BatchKind {
+  int kind;
+  const char* setter;
+  const char* reader;
+  const char* disarm;
+  int (*take)(lbm_batch*);
+};
+static const BatchKind kBatchKinds[] = {
+    {kRecForces, "lbm_batch_set_forces", "lbm_batch_read_forces", "lbm_batch_set_forces(batch, 0, NULL, 0, 0)", take_batch_forces},
+    {kRecStats, "lbm_batch_set_stats", "lbm_batch_read_stats", "lbm_batch_set_stats(batch, 0, 0)", take_batch_stats},
+    {kRecResidual, "lbm_batch_set_residual", "lbm_batch_read_residual", "lbm_batch_set_residual(batch, 0, 0)", take_batch_residual}};
+static const BatchKind* batch_kind(int kind) {
+  for (const BatchKind& k : kBatchKinds)
+    if (k.kind == kind) return &k;
+  return nullptr;
+}
 
 namespace {
 
@@ -1339,10 +1370,10 @@ const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = f
   using Form = const void* (*)(int);
   static const Form forms[2][kRecKinds] = {
       {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>, resident_form<false, kRecMean>,
-       resident_form<false, kRecFields>, resident_form<false, kRecNone>, resident_form<false, kRecNone>},  // (the forces and the statistics
-                                                                                                           // run the plain form)
+       resident_form<false, kRecFields>, resident_form<false, kRecNone>, resident_form<false, kRecNone>,
+       resident_form<false, kRecNone>},  // (the forces, the statistics and the residuals run the plain form)
       {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>, resident_form<true, kRecMean>,
-       resident_form<true, kRecFields>, resident_form<true, kRecNone>, resident_form<true, kRecNone>}};
+       resident_form<true, kRecFields>, resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>}};
   return forms[batch][rec]((rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
 }
 
@@ -1555,6 +1586,22 @@ void launch_stats_gather(const lbm_ctx* c, const Slab& sl, long long* words) {
     hipLaunchKernelGGL(lbm::stats_gather<1>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, words);
 }
 
+// one residual sample of a slab's current lattice against its planes into `words` (zeroed in front, on the same stream);
+// baseline: the planes are filled from the lattice and nothing is reduced (arming)
+void launch_residual_gather(const lbm_ctx* c, const Slab& sl, long long* words, bool baseline) {
+  const int v = stats_vector(c->p.nx);
+  const dim3 grid(stats_groups((long)sl.rows * c->p.nx, v));
+  const unsigned cell_first = (unsigned)sl.row_first * (unsigned)c->p.nx;
+  float* px = sl.residual_planes;
+  float* py = px + (size_t)sl.rows * c->p.nx;
+  if (v == 4)
+    hipLaunchKernelGGL(lbm::residual_gather<4>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, px, py, words,
+                       (int)baseline);
+  else
+    hipLaunchKernelGGL(lbm::residual_gather<1>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, px, py, words,
+                       (int)baseline);
+}
+
 // the record of the current (stored) lattice into the next slot, on every slab's compute stream: the frame of its rows,
 // or the gathered samples of the probes in its rows; or, for the mean fields, the sample of its rows added to their sums
 int take_record(lbm_ctx* c) {
@@ -1587,6 +1634,11 @@ int take_record(lbm_ctx* c) {
           long long* words = sl.stats_ring + slot * (size_t)lbm_stats::kStatsWords;
           HIP_TRY(LBM_FAILURE, hipMemsetAsync(words, 0, lbm_stats::kStatsWords * sizeof(long long), sl.compute));
           launch_stats_gather(c, sl, words);
+        } else if (c->rec.kind == kRecResidual) {
+          // likewise; the gather also replaces the slab's remembered field by this lattice's
+          long long* words = sl.residual_ring + slot * (size_t)lbm_residual::kResidualWords;
+          HIP_TRY(LBM_FAILURE, hipMemsetAsync(words, 0, lbm_residual::kResidualWords * sizeof(long long), sl.compute));
+          launch_residual_gather(c, sl, words, false);
         } else if (c->rec.kind == kRecMean)
           hipLaunchKernelGGL(lbm::mean_accumulate, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              c->p.density, sl.mean_sums, n, c->rec.order);
@@ -1625,7 +1677,7 @@ int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
     const long long records = recorded_between(c->rec, c->steps_done, (long long)c->steps_done + n_steps);
     if (run_resident(c, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
     c->steps_done += n_steps;
-    if (!records_behind(c->rec.kind)) c->rec.written += records;  // recorded by the kernel itself (forces, statistics: by the caller, behind it)
+    if (!records_behind(c->rec.kind)) c->rec.written += records;  // recorded by the kernel itself (forces, statistics, residuals: by the caller, behind it)
     return LBM_SUCCESS;
   }
 
@@ -2322,6 +2374,8 @@ void release_recorder(lbm_ctx* c) {
     sl.force_ring.reset();
     sl.force_groups = 0;
     sl.stats_ring.reset();
+    sl.residual_ring.reset();
+    sl.residual_planes.reset();
     sl.probe_count = 0;
   }
   c->probe_cells.clear();
@@ -2349,17 +2403,14 @@ int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate alloc
       if (c->rec.kind == other)
         LBM_FAIL(LBM_FAILURE, "%s: %s are armed (%s) and a context has one recorder -- disarm them with %s first", setter, o.name,
                  o.setter, o.disarm);
-      if (bt && other == kRecForces && bt->armed[other] > 0)  // (no member arms them: the batch does)
-        LBM_FAIL(LBM_FAILURE, "%s: this batch has %s armed (lbm_batch_set_forces); a batch records one kind -- disarm them with "
-                 "lbm_batch_set_forces(batch, 0, NULL, 0, 0) first", setter, o.name);
-      if (bt && other == kRecStats && bt->armed[other] > 0)  // (likewise)
-        LBM_FAIL(LBM_FAILURE, "%s: this batch has %s armed (lbm_batch_set_stats); a batch records one kind -- disarm them with "
-                 "lbm_batch_set_stats(batch, 0, 0) first", setter, o.name);
+      if (bt && bt->rec.kind == other)  // (a kind no member arms: the batch does)
+        LBM_FAIL(LBM_FAILURE, "%s: this batch has %s armed (%s); a batch records one kind -- disarm them with %s first", setter, o.name,
+                 batch_kind(other)->setter, batch_kind(other)->disarm);
       if (bt && bt->armed[other] > 0)
         LBM_FAIL(LBM_FAILURE, "%s: a member of this batch has %s armed (%s); a batch records one kind: frames, probes, mean fields or field frames",
                  setter, o.name, o.setter);
     }
-    if (c->plan.resident && !records_behind(kind)) {  // (the forces and the statistics record behind the plain form, which every resident shape runs)
+    if (c->plan.resident && !records_behind(kind)) {  // (the forces, the statistics and the residuals record behind the plain form, which every resident shape runs)
       // the recorder forms of four-row bands defer the acceleration of the interior pair only (lbm::resident_band): the lid
       // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form must run one workgroup per CU
       if (c->plan.resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
@@ -3109,6 +3160,78 @@ int lbm_read_stats(lbm_ctx* c, int max_rows, lbm_stats_row* out, int* steps, int
   });
 }
 
+// the span of the row with ordinal `ord` since arming: from the baseline to the first sample, then `every`
+static int residual_span(const Recorder& r, long long ord) {
+  return ord == 0 ? (int)((long long)r.ord0 * r.every + 1 - r.base_steps) : r.every;
+}
+
+int lbm_set_residual(lbm_ctx* c, int every, int capacity) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_residual: null context");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_residual: negative interval %d", every);
+  constexpr long long kRowBytes = lbm_residual::kResidualWords * (long long)sizeof(long long);
+  if (every > 0) {
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_residual: capacity %d, at least one row is needed", capacity);
+    if ((long long)capacity * kRowBytes >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_set_residual: a ring of %d rows is 2 GiB or more (%d bytes per row)", capacity, (int)kRowBytes);
+    if (c->ranked || c->world > 1)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_residual: not available in a multi-process (rank) context: a row's sums would be spread over the ranks");
+    if (c->batch)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_residual: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
+               "end at, so the residuals of a batch are armed on the batch, with one `every` for all members (lbm_batch_set_residual)");
+  }
+  const int status = rearm_recorder(c, kRecResidual, every, capacity, [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * (size_t)kRowBytes;
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      const size_t cells = (size_t)sl.rows * c->p.nx;
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      if (sl.residual_planes.alloc(2 * cells) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_residual: cannot allocate the remembered field of slab %d (%zu cells, %.1f MiB); residuals stay off", s, cells,
+                 (double)(2 * cells * sizeof(float)) / 1048576.0);
+      if (sl.residual_ring.alloc_bytes(ring_bytes) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_residual: cannot allocate %d rows (%.1f MiB per slab); residuals stay off", capacity,
+                 (double)ring_bytes / 1048576.0);
+    }
+    // the baseline: the field of the current lattice (the streams are idle: rearm_recorder waited for them)
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      launch_residual_gather(c, sl, nullptr, true);
+      HIP_TRY(LBM_FAILURE, hipGetLastError());
+    }
+    return LBM_SUCCESS;
+  });
+  if (status == LBM_SUCCESS && every > 0) c->rec.base_steps = c->steps_done;
+  return status;
+}
+
+int lbm_read_residual(lbm_ctx* c, int max_rows, lbm_residual_row* out, int* steps, int* n_read) {
+  return drain_recorder(c, kRecResidual, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
+    constexpr size_t words = lbm_residual::kResidualWords;
+    const size_t slots = (size_t)c->rec.slots, n_slabs = (size_t)c->n_slabs;
+    // every slab's words of the n rows (they wait in at most two runs of its ring), gathered as rows[row][slab][words];
+    // the slabs of a row are merged and rounded by residual_row_from_words
+    std::vector<long long> rows((size_t)n * n_slabs * words), stage((size_t)n * words);
+    for (size_t s = 0; s < n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      for (int i = 0; i < n;) {
+        const size_t slot = (size_t)((c->rec.read + i) % c->rec.slots);
+        const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
+        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, sl.residual_ring + slot * words, (size_t)run * words * sizeof(long long),
+                                            hipMemcpyDeviceToHost, sl.compute));
+        i += run;
+      }
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+      for (size_t i = 0; i < (size_t)n; i++) memcpy(&rows[(i * n_slabs + s) * words], &stage[i * words], words * sizeof(long long));
+    }
+    for (int i = 0; i < n; i++)
+      out[i] = lbm_residual::residual_row_from_words(rows.data() + (size_t)i * n_slabs * words, (int)n_slabs, c->p.nx,
+                                                     residual_span(c->rec, c->rec.read + i));
+    return LBM_SUCCESS;
+  });
+}
+
 // the planes [first, first + 4) of every slab's sums, stitched by row_first; lbm_read_mean and lbm_read_mean2
 static int read_mean_planes(lbm_ctx* c, int first, double* const (&out)[4], long long* n_samples) {
   for (int s = 0; s < c->n_slabs; s++) {
@@ -3543,6 +3666,45 @@ static int take_batch_stats(lbm_batch* bt) {
   return LBM_SUCCESS;
 }
 
+// ONE residual_gather_batch launch over all members' current (stored) lattices and planes, on the batch's stream:
+// the baseline (the planes filled, `row` unused) or a sample into `row`, [members][kResidualWords], zeroed in front
+static int launch_batch_residual(lbm_batch* bt, long long* row, bool baseline) {
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  const Slab& sl0 = c0->slab[0];
+  const int v = stats_vector(c0->p.nx);
+  const dim3 grid((unsigned)stats_groups((long)sl0.rows * c0->p.nx, v), 1, (unsigned)n_members);
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
+  if (!baseline) HIP_TRY(LBM_FAILURE, hipMemsetAsync(row, 0, n_members * lbm_residual::kResidualWords * sizeof(long long), bt->stream));
+  if (v == 4)
+    hipLaunchKernelGGL(lbm::residual_gather_batch<4>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows,
+                       bt->residual_planes.get(), row, (int)baseline);
+  else
+    hipLaunchKernelGGL(lbm::residual_gather_batch<1>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows,
+                       bt->residual_planes.get(), row, (int)baseline);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+
+// the residual row of all members into the next slot
+static int take_batch_residual(lbm_batch* bt) {
+  const size_t words = bt->members.size() * (size_t)lbm_residual::kResidualWords;
+  if (launch_batch_residual(bt, bt->residual_ring + (size_t)(bt->rec.written % bt->rec.slots) * words, false) != LBM_SUCCESS) return LBM_FAILURE;
+  bt->rec.written++;
+  return LBM_SUCCESS;
+}
+
+// a batch-level setter of `kind` called while the batch's one recorder holds another kind: disarming is a no-op
+// (*taken = true, success), arming is refused
+static int batch_recorder_taken(const lbm_batch* bt, int kind, const char* who, int every, bool* taken) {
+  *taken = (bt->rec.kind != kRecNone && bt->rec.kind != kind);
+  if (!*taken || every == 0) return LBM_SUCCESS;
+  const BatchKind* k = batch_kind(bt->rec.kind);
+  LBM_FAIL(LBM_FAILURE, "%s: this batch has %s armed (%s); a batch records one kind -- disarm them with %s first", who,
+           kRecorderKinds[bt->rec.kind].name, k->setter, k->disarm);
+}
+
 int lbm_batch_run(lbm_batch* bt, int n_steps) {
   if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: null batch");
   if (n_steps < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: negative step count");
@@ -3554,18 +3716,17 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
   for (lbm_ctx* c : bt->members)  // every member's records must fit before any member runs
     if (recorder_fits(c, n_steps, "lbm_batch_run") != LBM_SUCCESS) return LBM_FAILURE;
   if (bt->rec.kind == kRecNone) return batch_advance(bt, n_steps);
-  // forces or statistics armed: the call runs as the sub-calls that end at the sample steps, each advanced as a call of its
-  // length would be and followed by the row of all members (lbm_run does the same for one context, run_steps)
-  const bool stats = (bt->rec.kind == kRecStats);
-  if (recorder_fits(bt->rec, bt->steps_done, n_steps, "lbm_batch_run", stats ? "lbm_batch_read_stats" : "lbm_batch_read_forces") != LBM_SUCCESS)
-    return LBM_FAILURE;
+  // forces, statistics or residuals armed: the call runs as the sub-calls that end at the sample steps, each advanced as a
+  // call of its length would be and followed by the row of all members (lbm_run does the same for one context, run_steps)
+  const BatchKind* kind = batch_kind(bt->rec.kind);
+  if (recorder_fits(bt->rec, bt->steps_done, n_steps, "lbm_batch_run", kind->reader) != LBM_SUCCESS) return LBM_FAILURE;
   const int e = bt->rec.every;
   for (int t = 0; t < n_steps;) {
     const int tt = bt->steps_done, r = tt % e;
     const long long rec_tt = r ? (long long)tt + (e - r) : tt;  // next sample step
     const int seg = (rec_tt - tt + 1 < n_steps - t) ? (int)(rec_tt - tt + 1) : n_steps - t;
     if (batch_advance(bt, seg) != LBM_SUCCESS) return LBM_FAILURE;
-    if (bt->steps_done - 1 == rec_tt && (stats ? take_batch_stats(bt) : take_batch_forces(bt)) != LBM_SUCCESS) return LBM_FAILURE;
+    if (bt->steps_done - 1 == rec_tt && kind->take(bt) != LBM_SUCCESS) return LBM_FAILURE;
     t += seg;
   }
   return LBM_SUCCESS;
@@ -3611,11 +3772,9 @@ int lbm_batch_set_forces(lbm_batch* bt, int n_bodies, const int* body_of_cell, i
   const size_t n_members = bt->members.size(), cells = (size_t)c0->p.nx * c0->p.ny;
   // every member's labels as bytes (255: outside 0 .. n_bodies - 1), on the device while the lists are built
   std::vector<DeviceBuf<unsigned char>> labels(every > 0 && body_of_cell ? n_members : 0);
-  if (bt->rec.kind == kRecStats) {  // the batch's one recorder is taken
-    if (every == 0) return LBM_SUCCESS;
-    LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: this batch has %s armed (lbm_batch_set_stats); a batch records one kind -- disarm them with "
-             "lbm_batch_set_stats(batch, 0, 0) first", kRecorderKinds[kRecStats].name);
-  }
+  bool taken;  // the batch's one recorder holds another kind
+  if (batch_recorder_taken(bt, kRecForces, "lbm_batch_set_forces", every, &taken) != LBM_SUCCESS) return LBM_FAILURE;
+  if (taken) return LBM_SUCCESS;
   if (every > 0) {
     if (n_bodies < 1 || n_bodies > LBM_MAX_BODIES)
       LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: %d bodies, between 1 and LBM_MAX_BODIES = %d are possible", n_bodies, LBM_MAX_BODIES);
@@ -3754,11 +3913,9 @@ int lbm_batch_set_stats(lbm_batch* bt, int every, int capacity) {
   lbm_ctx* c0 = bt->members[0];
   const size_t n_members = bt->members.size();
   const size_t row_bytes = n_members * lbm_stats::kStatsWords * sizeof(long long);
-  if (bt->rec.kind == kRecForces) {  // the batch's one recorder is taken
-    if (every == 0) return LBM_SUCCESS;
-    LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: this batch has %s armed (lbm_batch_set_forces); a batch records one kind -- disarm them with "
-             "lbm_batch_set_forces(batch, 0, NULL, 0, 0) first", kRecorderKinds[kRecForces].name);
-  }
+  bool taken;  // the batch's one recorder holds another kind
+  if (batch_recorder_taken(bt, kRecStats, "lbm_batch_set_stats", every, &taken) != LBM_SUCCESS) return LBM_FAILURE;
+  if (taken) return LBM_SUCCESS;
   if (every > 0) {
     if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: capacity %d, at least one row is needed", capacity);
     if ((long long)capacity * (long long)row_bytes >= (1LL << 31))
@@ -3832,6 +3989,111 @@ int lbm_batch_read_stats(lbm_batch* bt, int max_rows, lbm_stats_row* out, int* s
     HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
     for (size_t j = 0; j < (size_t)n * n_members; j++)
       out[j] = lbm_stats::stats_row_from_words(stage.data() + j * lbm_stats::kStatsWords, 1, bt->members[0]->p.nx);
+  }
+  if (steps)
+    for (int i = 0; i < n; i++) steps[i] = (int)((r.ord0 + r.read + i) * r.every);
+  r.read += n;
+  *n_read = n;
+  return LBM_SUCCESS;
+}
+
+// ---- velocity residuals of a batch ---------------------------------------------------------------------------------
+static void release_batch_residual(lbm_batch* bt) {
+  (void)hipSetDevice(bt->members[0]->slab[0].device);
+  bt->residual_ring.reset();
+  bt->residual_planes.reset();
+  bt->rec = Recorder{};
+  bt->armed[kRecResidual] = 0;
+}
+
+int lbm_batch_set_residual(lbm_batch* bt, int every, int capacity) {
+  if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: null batch");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: negative interval %d", every);
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  const size_t row_bytes = n_members * lbm_residual::kResidualWords * sizeof(long long);
+  bool taken;  // the batch's one recorder holds another kind
+  if (batch_recorder_taken(bt, kRecResidual, "lbm_batch_set_residual", every, &taken) != LBM_SUCCESS) return LBM_FAILURE;
+  if (taken) return LBM_SUCCESS;
+  if (every > 0) {
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: capacity %d, at least one row is needed", capacity);
+    if ((long long)capacity * (long long)row_bytes >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: a ring of %d rows of %d members is %.2f GiB, 2 GiB or more (%d bytes per member and row)",
+               capacity, (int)n_members, (double)capacity * (double)row_bytes / 1073741824.0,
+               lbm_residual::kResidualWords * (int)sizeof(long long));
+    for (size_t i = 0; i < n_members; i++) {
+      const Recorder& r = bt->members[i]->rec;
+      if (r.kind != kRecNone)
+        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: member %d has %s armed (%s); a batch records one kind -- disarm them with %s first", (int)i,
+                 kRecorderKinds[r.kind].name, kRecorderKinds[r.kind].setter, kRecorderKinds[r.kind].disarm);
+    }
+  }
+  // the ring and the planes may still be written by launches in flight
+  HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
+  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
+  release_batch_residual(bt);
+  if (every == 0) return LBM_SUCCESS;
+
+  auto allocate = [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * row_bytes;
+    const size_t cells = (size_t)c0->slab[0].rows * c0->p.nx;
+    if (bt->residual_planes.alloc(n_members * 2 * cells) != hipSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: cannot allocate the remembered fields of %d members (%zu cells each, %.1f MiB); residuals stay off",
+               (int)n_members, cells, (double)(n_members * 2 * cells * sizeof(float)) / 1048576.0);
+    if (bt->residual_ring.alloc_bytes(ring_bytes) != hipSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: cannot allocate %d rows of %d members (%.1f MiB); residuals stay off", capacity,
+               (int)n_members, (double)ring_bytes / 1048576.0);
+    if (!bt->table) {  // a shape the resident kernel does not take: the gather still reads the members' lattices from the table
+      const std::vector<lbm::ResidentMember> h = member_table(bt);
+      if (bt->table.alloc(h.size()) != hipSuccess || hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: cannot allocate the member table; residuals stay off");
+    }
+    return launch_batch_residual(bt, nullptr, true);  // the baselines of all members: one launch
+  };
+  if (allocate() != LBM_SUCCESS) {
+    (void)hipGetLastError();  // a failed allocation must not surface at the next launch
+    release_batch_residual(bt);
+    return LBM_FAILURE;
+  }
+  bt->rec.kind = kRecResidual;
+  bt->rec.every = every;
+  bt->rec.slots = capacity;
+  bt->rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
+  bt->rec.base_steps = bt->steps_done;
+  bt->armed[kRecResidual] = 1;
+  return LBM_SUCCESS;
+}
+
+int lbm_batch_read_residual(lbm_batch* bt, int max_rows, lbm_residual_row* out, int* steps, int* n_read) {
+  if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_residual: NULL argument");
+  *n_read = 0;
+  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
+  Recorder& r = bt->rec;
+  const long long waiting = (r.kind == kRecResidual) ? r.written - r.read : 0;
+  if (!out && !steps) {
+    *n_read = (int)waiting;
+    return LBM_SUCCESS;
+  }
+  if (!out) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_residual: NULL row output");
+  if (max_rows < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_residual: negative max_rows %d", max_rows);
+  const int n = (waiting < max_rows) ? (int)waiting : max_rows;
+  if (n > 0) {
+    // the n oldest rows wait in at most two runs of the ring; every member's words become its row
+    const size_t n_members = bt->members.size(), words = n_members * (size_t)lbm_residual::kResidualWords;
+    const size_t slots = (size_t)r.slots;
+    std::vector<long long> stage((size_t)n * words);
+    HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
+    for (int i = 0; i < n;) {
+      const size_t slot = (size_t)((r.read + i) % r.slots);
+      const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, bt->residual_ring + slot * words, (size_t)run * words * sizeof(long long),
+                                          hipMemcpyDeviceToHost, bt->stream));
+      i += run;
+    }
+    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
+    for (size_t j = 0; j < (size_t)n * n_members; j++)
+      out[j] = lbm_residual::residual_row_from_words(stage.data() + j * lbm_residual::kResidualWords, 1, bt->members[0]->p.nx,
+                                                     residual_span(r, r.read + (long long)(j / n_members)));
   }
   if (steps)
     for (int i = 0; i < n; i++) steps[i] = (int)((r.ord0 + r.read + i) * r.every);
@@ -3973,12 +4235,9 @@ int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double to
       LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_batch_run_until", k.name, k.setter, k.noun);
     }
   }
-  if (bt->rec.kind == kRecForces)
-    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_batch_run_until", kRecorderKinds[kRecForces].name, "lbm_batch_set_forces",
-             kRecorderKinds[kRecForces].noun);
-  if (bt->rec.kind == kRecStats)
-    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_batch_run_until", kRecorderKinds[kRecStats].name, "lbm_batch_set_stats",
-             kRecorderKinds[kRecStats].noun);
+  if (bt->rec.kind != kRecNone)  // forces, statistics or residuals armed on the batch
+    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_batch_run_until", kRecorderKinds[bt->rec.kind].name, batch_kind(bt->rec.kind)->setter,
+             kRecorderKinds[bt->rec.kind].noun);
 
   HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
   if (!bt->steady_state) {  // allocated last: the set is whole (an attempt that failed half-way starts again)

@@ -36,6 +36,7 @@
 
 #include "lbm_exact_sum.h"
 #include "lbm_stats_row.h"
+#include "lbm_residual_row.h"
 
 namespace lbm {
 
@@ -44,9 +45,9 @@ constexpr int kQ = 9;
 constexpr int kNoRow = -1000000;  // "no such row in this slab"
 // what a context records while it runs, at most one at a time: the host's Recorder::kind and resident_band's REC
 constexpr int kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3, kRecFields = 4;
-// (the obstacle forces, lbm_set_forces / lbm_batch_set_forces, and the lattice statistics, lbm_set_stats /
-// lbm_batch_set_stats, are recorder kinds of the host alone: force_gather, stats_gather and their batch twins run behind
-// the step kernels)
+// (the obstacle forces, lbm_set_forces / lbm_batch_set_forces, the lattice statistics, lbm_set_stats /
+// lbm_batch_set_stats, and the velocity residuals, lbm_set_residual / lbm_batch_set_residual, are recorder kinds of the
+// host alone: force_gather, stats_gather, residual_gather and their batch twins run behind the step kernels)
 
 // 1/3 rounded to fp32, and the two constant divisors of the equilibrium, folded in fp32
 // exactly as the reference's "2.f * c_sq" and "2.f * c_sq * c_sq" (SerialCode/d2q9-bgk.c:308,367-370)
@@ -3088,6 +3089,152 @@ template <int V>
 __global__ __launch_bounds__(kBlock) void stats_gather_batch(const LatticeArgs a, const ResidentMember* members, int rows, long long* row) {
   const int member = blockIdx.z;
   stats_cells<V>(a, members[member].src, members[member].mask, rows, 0u, row + (size_t)member * lbm_stats::kStatsWords);
+}
+
+// ---------------------------------------------------------------------------------------------
+// velocity residuals (lbm_set_residual): the exact sums of |u - u_remembered|^2 and of |u|^2 over the finite fluid cells,
+// the largest |u - u_remembered| with its cell and the fluid cells that are not finite, of a whole stored lattice
+// ---------------------------------------------------------------------------------------------
+// One sample, built the way stats_cells is: the same deal of the owned cells (V at a time along x, a capped grid that
+// strides), the same reduction (shuffles, LDS, 64-bit integer atomics into `words`, kResidualWords of them, zeroed by
+// the host; no floating-point addition on the device).  Besides the lattice a lane reads the remembered field of its
+// cells from the dense planes px, py ([rows][nx]: a V = 4 unit is 16-byte aligned where nx % 4 == 0) and writes the
+// current (u_x, u_y) back to them -- blocked cells 0, 0 -- with one 16-byte load and one 16-byte store per plane and unit.
+// Each cell is read and written by one lane only, so there is no race.  A lane keeps two fixed-point accumulators (dsq,
+// usq), its count and its key, stats_key(bits of dmag, global cell); a cell that does not contribute is added with sign
+// 0.  BASELINE: the field is stored and nothing else happens (arming; `words` is not touched).
+template <int V, bool BASELINE>
+__device__ __forceinline__ void residual_cells(const LatticeArgs& a, const float* src, const unsigned char* mask, int rows, unsigned cell_first,
+                                               float* px, float* py, long long* words) {
+  constexpr int L = lbm_exact::kExactLimbs, S = lbm_residual::kResidualSums, W = lbm_residual::kResidualKeyWord + 1;
+  long long acc[S][L], bad = 0;
+  unsigned long long key = 0ull;
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int i = 0; i < L; i++) acc[j][i] = 0;
+  const long per_row = a.nx / V, n_units = (long)rows * per_row;
+  for (long u = (long)blockIdx.x * kBlock + threadIdx.x; u < n_units; u += (long)gridDim.x * kBlock) {
+    const int r = (int)(u / per_row), x = (int)(u - (long)r * per_row) * V;
+    const float* p = src + (long)r * a.row_pitch + x;
+    const long at = (long)r * a.nx + x;  // in the planes
+    float f[V][kQ], pux[V], puy[V], nux[V], nuy[V];
+    unsigned blocked;  // byte v: the mask of cell x + v
+    if constexpr (V == 4) {
+#pragma unroll
+      for (int k = 0; k < kQ; k++) {
+        const float4 q = *reinterpret_cast<const float4*>(p + k * a.plane_stride);
+        f[0][k] = q.x;  f[1][k] = q.y;  f[2][k] = q.z;  f[3][k] = q.w;
+      }
+      blocked = *reinterpret_cast<const unsigned*>(mask + (long)r * a.pitch + x);
+      if constexpr (!BASELINE) {
+        const float4 qx = *reinterpret_cast<const float4*>(px + at), qy = *reinterpret_cast<const float4*>(py + at);
+        pux[0] = qx.x;  pux[1] = qx.y;  pux[2] = qx.z;  pux[3] = qx.w;
+        puy[0] = qy.x;  puy[1] = qy.y;  puy[2] = qy.z;  puy[3] = qy.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < kQ; k++) f[0][k] = p[k * a.plane_stride];
+      blocked = mask[(long)r * a.pitch + x];
+      if constexpr (!BASELINE) {
+        pux[0] = px[at];
+        puy[0] = py[at];
+      }
+    }
+    const unsigned cell = cell_first + (unsigned)r * (unsigned)a.nx + (unsigned)x;
+#pragma unroll
+    for (int v = 0; v < V; v++) {
+      const float(&g)[kQ] = f[v];
+      float rho, ux, uy;
+      moments_exact(g, rho, ux, uy);
+      const bool fluid = ((blocked >> (8 * v)) & 0xffu) == 0u;
+      nux[v] = fluid ? ux : 0.f;
+      nuy[v] = fluid ? uy : 0.f;
+      if constexpr (!BASELINE) {
+        const float jx = g[1] + g[5] + g[8] - (g[3] + g[6] + g[7]);
+        const float jy = g[2] + g[5] + g[6] - (g[4] + g[7] + g[8]);
+        const float usq = (ux * ux) + (uy * uy);
+        const float dux = ux - pux[v], duy = uy - puy[v];
+        const float dsq = (dux * dux) + (duy * duy);
+        const float dmag = sqrtf(dsq);
+        const unsigned b_usq = __float_as_uint(usq), b_dsq = __float_as_uint(dsq);
+        const bool finite = lbm_exact::exact_sum_finite(__float_as_uint(rho)) && lbm_exact::exact_sum_finite(__float_as_uint(jx)) &&
+                            lbm_exact::exact_sum_finite(__float_as_uint(jy)) && lbm_exact::exact_sum_finite(b_usq) &&
+                            lbm_exact::exact_sum_finite(b_dsq);
+        const int s = (finite && fluid) ? 1 : 0;
+        lbm_exact::exact_sum_add(acc[0], b_dsq, s);
+        lbm_exact::exact_sum_add(acc[1], b_usq, s);
+        bad += (fluid && !finite) ? 1 : 0;
+        const unsigned long long cell_key = lbm_stats::stats_key(__float_as_uint(dmag), cell + (unsigned)v);
+        key = (s && cell_key > key) ? cell_key : key;
+      }
+    }
+    if constexpr (V == 4) {
+      *reinterpret_cast<float4*>(px + at) = make_float4(nux[0], nux[1], nux[2], nux[3]);
+      *reinterpret_cast<float4*>(py + at) = make_float4(nuy[0], nuy[1], nuy[2], nuy[3]);
+    } else {
+      px[at] = nux[0];
+      py[at] = nuy[0];
+    }
+  }
+  if constexpr (!BASELINE) {
+    __shared__ long long sh[kBlock / 64][W];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    auto wave_total = [&](long long t, int word) {
+      for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+      if (lane == 0) sh[wave][word] = t;
+    };
+#pragma unroll
+    for (int j = 0; j < S; j++)
+#pragma unroll
+      for (int i = 0; i < L; i++) wave_total(acc[j][i], j * L + i);
+    wave_total(bad, lbm_residual::kResidualBadWord);
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long other = (unsigned long long)__shfl_down((long long)key, off, 64);
+      key = other > key ? other : key;
+    }
+    if (lane == 0) sh[wave][lbm_residual::kResidualKeyWord] = (long long)key;
+    __syncthreads();
+    if (threadIdx.x < W) {
+      unsigned long long* word = reinterpret_cast<unsigned long long*>(words + threadIdx.x);
+      if (threadIdx.x == lbm_residual::kResidualKeyWord) {
+        unsigned long long m = 0ull;
+        for (int w = 0; w < kBlock / 64; w++) m = (unsigned long long)sh[w][threadIdx.x] > m ? (unsigned long long)sh[w][threadIdx.x] : m;
+        if (m != 0ull) atomicMax(word, m);
+      } else {
+        long long t = 0;
+        for (int w = 0; w < kBlock / 64; w++) t += sh[w][threadIdx.x];
+        if (t != 0) atomicAdd(word, (unsigned long long)t);
+      }
+    }
+  }
+}
+
+// a slab's owned rows against its planes (px, py: [rows][nx]) into its words of the ring row; cell_first: the GLOBAL
+// index of its first owned cell.  baseline != 0: the planes are filled and `words` is not read (arming)
+template <int V>
+__global__ __launch_bounds__(kBlock) void residual_gather(const LatticeArgs a, int rows, unsigned cell_first, float* px, float* py,
+                                                          long long* words, int baseline) {
+  if (baseline)
+    residual_cells<V, true>(a, a.src, a.mask, rows, cell_first, px, py, words);
+  else
+    residual_cells<V, false>(a, a.src, a.mask, rows, cell_first, px, py, words);
+}
+
+// residual_gather's twin for a batch: one sample (or the baseline) of every member in one launch, workgroup (g, 0, member)
+// on the member's current lattice and mask (members[member]; `a` carries the strides all members share), the member's
+// planes -- planes[member][2][rows][nx] -- and the member's words of the row, [members][kResidualWords]
+template <int V>
+__global__ __launch_bounds__(kBlock) void residual_gather_batch(const LatticeArgs a, const ResidentMember* members, int rows, float* planes,
+                                                                long long* row, int baseline) {
+  const int member = blockIdx.z;
+  const size_t n = (size_t)rows * a.nx;
+  float* px = planes + (size_t)member * 2 * n;
+  if (baseline)
+    residual_cells<V, true>(a, members[member].src, members[member].mask, rows, 0u, px, px + n, row);
+  else
+    residual_cells<V, false>(a, members[member].src, members[member].mask, rows, 0u, px, px + n,
+                             row + (size_t)member * lbm_residual::kResidualWords);
 }
 
 }  // namespace lbm
