@@ -720,8 +720,9 @@ int lbm_batch_read_stats(lbm_batch* batch, int max_rows, lbm_stats_row* out /* [
  *   Refused, as lbm_set_stats refuses: negative every; capacity < 1; a ring of 2 GiB or more; rank contexts
  *   (lbm_create_rank*); batch members (a batch arms them as a whole: lbm_batch_set_residual); LBM_HALO_STALE /
  *   LBM_HALO_FRESHEST (and lbm_set_halo_mode to those while armed); a context with another recorder armed (and the other
- *   setters while this one is armed); lbm_run_until while armed.  Not offered: density or pressure residuals, the double
- *   engine, a residual criterion for lbm_run_until, recording inside the resident or stream kernels.
+ *   setters while this one is armed); lbm_run_until and lbm_run_until_residual while armed (the latter takes its own
+ *   baseline and rows, see below).  Not offered: density or pressure residuals, the double engine, recording inside the
+ *   resident or stream kernels.
  * lbm_read_residual: drains up to max_rows oldest rows into out[n] and steps[n] (their tt, may be NULL); out == NULL &&
  *   steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers.
  * lbm_batch_set_residual / lbm_batch_read_residual: the same for every member of a batch, armed on the BATCH with one
@@ -746,6 +747,70 @@ int lbm_set_residual(lbm_ctx* ctx, int every, int capacity);
 int lbm_read_residual(lbm_ctx* ctx, int max_rows, lbm_residual_row* out, int* steps, int* n_read);
 int lbm_batch_set_residual(lbm_batch* batch, int every, int capacity);
 int lbm_batch_read_residual(lbm_batch* batch, int max_rows, lbm_residual_row* out /* [n][members] */, int* steps, int* n_read);
+
+/* ---- steady-state runs on the velocity residual ---------------------------------------------
+ * lbm_run_until with the criterion every CFD code uses: the run is steady when the whole velocity field has stopped
+ * changing, not when one number has (the mean of av_vels, in which local motion can cancel).  The quantity is the row of
+ * lbm_set_residual, taken exactly, so a run stops at the same step and reports the same bits on every kernel path.  The
+ * verdict is taken on the device (four bytes come back per check).  A run that blows up ends at the first check that
+ * sees a fluid cell that is not finite, instead of stepping NaNs until max_steps.
+ * With check_every = E >= 1, tol >= 0, patience = P >= 1, max_steps = N >= 0:
+ *   BASELINE.  At its start the call takes the baseline: the remembered field (u_x, u_y) of the current lattice, exactly
+ *     as lbm_set_residual defines it, into planes the call owns (8 bytes per cell, allocated by the first such call and
+ *     kept with the context).  The recorder never sees them; nothing is armed before or after the call.
+ *   ROW OF A CHECK.  The call runs segments of E timesteps counted from its start.  After segment j = 1, 2, ... one row is
+ *     taken, precisely lbm_residual_row as lbm_set_residual defines it, with span = E; the sample then becomes the
+ *     remembered field.  Because there is a baseline, segment 1 is already a check (unlike lbm_run_until): `checks`
+ *     counts the segments judged.
+ *   RESIDUAL.  r_j = sqrt(sum_du_sq / sum_u_sq) in IEEE double from the two exactly rounded sums, the division and the
+ *     square root correctly rounded; both sums 0: r_j = 0; sum_u_sq == 0 < sum_du_sq: r_j = +inf (residual_l2's corners).
+ *   VERDICT OF A CHECK.  nonfinite > 0: the check is not met, streak = 0, diverged = 1, and the call ends with this
+ *     segment.  Otherwise the check is met iff r_j <= tol; `streak` counts consecutive checks met; the run is steady
+ *     when streak == P, and the call ends with that segment, after j*E steps.
+ *   CAP.  If N comes first the call ends there, not steady; a last segment shorter than E is run and not checked.
+ *   WHAT THE CALL LEAVES.  The call is synchronous; lattice, av_vels and steps_done are exactly those of
+ *     lbm_run(steps_run).
+ *   HISTORY.  history[i], i < min(checks, history_capacity): the row of check i+1, taken after (i+1)*E steps of the call.
+ *     history == NULL or history_capacity == 0: none.  The words of the rows stay on the device during the run (160
+ *     bytes per row) and the rows are formed after it; the traffic per check stays the one stop word (0: go on, 1:
+ *     steady, 2: diverged).
+ *   Single periodic slabs that run the resident kernel keep one segment in flight as lbm_run_until does; everything a
+ *   segment enqueued behind a "stop" would have done -- its acceleration, its sample, its check -- reads the stop word
+ *   first, so it is dropped without a trace: no reported row, no state and no remembered cell moves.  Other shapes wait
+ *   for each verdict.
+ *   PRECISION.  In fp32 the residual does not fall to zero: on channel flows like the reference's it falls by four
+ *   orders of magnitude and then sits on the rounding floor, r_j near 1e-5 (64x16 and 100x16, E = 512:
+ *   1.0, 2.5e-4, 1.9e-5, 1.5e-5, 1.6e-5, ...).  A tol below that floor is never met.  r_j measures the change over E
+ *   steps: above the floor it grows with E (a slowly drifting flow changes E times as much over E steps), so tol
+ *   belongs to an E.
+ *   Refused before any work is issued, everything lbm_run_until refuses: steps_done + max_steps beyond the av_vels
+ *   record, E < 1, P < 1, tol negative or NaN, any recorder armed, halo modes other than LBM_HALO_SYNC, rank contexts,
+ *   contexts of several slabs, batch members; also a negative history_capacity, a device history of 2 GiB or more, and
+ *   planes or a history that cannot be allocated (the message says the size; the context stays usable).
+ * lbm_batch_run_until_residual: the same for every member of a batch.  Every member has its own baseline, rows and
+ *   verdict, taken by ONE residual_gather_batch launch and ONE check launch per segment whatever the number of members.
+ *   A member's verdict freezes once it is steady or diverged; it keeps stepping with the others, so each member stays
+ *   bit-identical to an lbm_create context advanced by *steps_run.  The batch ends when every member is steady or
+ *   diverged, or at N.  history is [n][members], n = min(segments judged, history_capacity); a frozen member's later rows
+ *   are still real rows (its out[i].last and last_rel are those of its own last check).  Refused: what
+ *   lbm_batch_run_until refuses (a member or the batch with a recorder armed), and the history refusals above.
+ */
+typedef struct {
+  int    steps_run;    /* timesteps this call advanced */
+  int    steady;       /* 1: the criterion was met */
+  int    steady_step;  /* steps of this call after which it was first met (-1: never) */
+  int    checks;       /* checks made */
+  int    diverged;     /* 1: the call ended at a check whose row has nonfinite > 0 */
+  int    reserved;     /* 0 */
+  double last_rel;     /* r_j of the last check (+inf when none was made) */
+  lbm_residual_row last; /* the row of the last check (zeros, max_x = max_y = -1 when none) */
+} lbm_residual_steady_result;   /* 72 bytes; offsets 0 4 8 12 16 20 24 32 */
+int lbm_run_until_residual(lbm_ctx* ctx, int max_steps, int check_every, double tol, int patience,
+                           lbm_residual_steady_result* out,
+                           lbm_residual_row* history /* or NULL */, int history_capacity);
+int lbm_batch_run_until_residual(lbm_batch* batch, int max_steps, int check_every, double tol, int patience,
+                                 lbm_residual_steady_result* out /* [members] */, int* steps_run,
+                                 lbm_residual_row* history /* [n][members] or NULL */, int history_capacity);
 
 /* ---- double precision -----------------------------------------------------------------------
  * The reference's programs are `float`, but its published golden results (the .dat files of check/) are its algorithm evaluated in

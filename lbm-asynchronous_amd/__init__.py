@@ -55,6 +55,7 @@ ABI_SYMBOLS = (
     "lbm_batch_set_forces", "lbm_batch_read_forces", "lbm_batch_forces_links",
     "lbm_set_stats", "lbm_read_stats", "lbm_batch_set_stats", "lbm_batch_read_stats",
     "lbm_set_residual", "lbm_read_residual", "lbm_batch_set_residual", "lbm_batch_read_residual",
+    "lbm_run_until_residual", "lbm_batch_run_until_residual",
     "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
     "lbm_double_sync", "lbm_double_read_av_vels", "lbm_double_read_cells", "lbm_double_read_final_state",
     "lbm_double_av_velocity", "lbm_double_total_density", "lbm_double_calc_reynolds",
@@ -109,6 +110,22 @@ class _CSteadyResult(ctypes.Structure):
     def as_dict(self) -> dict:
         return {"steps_run": self.steps_run, "steady": bool(self.steady), "steady_step": self.steady_step,
                 "checks": self.checks, "last_rel": self.last_rel, "last_mean": self.last_mean}
+
+
+class _CResidualRow(ctypes.Structure):      # lbm_residual_row, 40 bytes (RESIDUAL_DTYPE)
+    _fields_ = [("sum_du_sq", ctypes.c_double), ("sum_u_sq", ctypes.c_double), ("nonfinite", ctypes.c_longlong),
+                ("max_du", ctypes.c_float), ("max_x", ctypes.c_int), ("max_y", ctypes.c_int), ("span", ctypes.c_int)]
+
+
+class _CResidualSteadyResult(ctypes.Structure):      # lbm_residual_steady_result, 72 bytes
+    _fields_ = [("steps_run", ctypes.c_int), ("steady", ctypes.c_int), ("steady_step", ctypes.c_int),
+                ("checks", ctypes.c_int), ("diverged", ctypes.c_int), ("reserved", ctypes.c_int),
+                ("last_rel", ctypes.c_double), ("last", _CResidualRow)]
+
+    def as_dict(self) -> dict:
+        last = np.frombuffer(bytes(self.last), dtype=RESIDUAL_DTYPE)[0]
+        return {"steps_run": self.steps_run, "steady": bool(self.steady), "steady_step": self.steady_step,
+                "checks": self.checks, "diverged": bool(self.diverged), "last_rel": self.last_rel, "last": last}
 
 
 class _CRcclStatus(ctypes.Structure):
@@ -261,6 +278,10 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_read_residual.argtypes = [P, I, P, P, PI]; lib.lbm_read_residual.restype = I
     lib.lbm_batch_set_residual.argtypes = [P, I, I]; lib.lbm_batch_set_residual.restype = I
     lib.lbm_batch_read_residual.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_residual.restype = I
+    lib.lbm_run_until_residual.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CResidualSteadyResult), P, I]
+    lib.lbm_run_until_residual.restype = I
+    lib.lbm_batch_run_until_residual.argtypes = [P, I, I, ctypes.c_double, I, ctypes.POINTER(_CResidualSteadyResult), PI, P, I]
+    lib.lbm_batch_run_until_residual.restype = I
     PD = ctypes.POINTER(ctypes.c_double)
     lib.lbm_double_create.argtypes = [ctypes.POINTER(_CParamsDouble), P, P]; lib.lbm_double_create.restype = P
     lib.lbm_double_destroy.argtypes = [P]; lib.lbm_double_destroy.restype = None
@@ -512,6 +533,24 @@ class Engine:
         return res.as_dict()
 
     # -- animation frames (lbm_set_frames / lbm_read_frames) ---------------------------------
+    def run_until_residual(self, max_steps: int, check_every: int = 1024, tol: float = 1e-4, patience: int = 2, history=None) -> dict:
+        """Advance until the velocity field has stopped changing, or by max_steps (lbm_run_until_residual): after every
+        check_every steps the relative L2 residual sqrt(sum_du_sq / sum_u_sq) against the field of the check before (the
+        first: of the start of the call) is compared with tol on the device; steady after `patience` consecutive checks
+        met; a check that finds a non-finite fluid cell ends the call (diverged).  In fp32 the residual floors near 1e-5,
+        and it scales with check_every.  history: None keeps the rows of all checks, an int that many.  Returns
+        {steps_run, steady, steady_step, checks, diverged, last_rel, last (a RESIDUAL_DTYPE record),
+        history: (steps int32[n], RESIDUAL_DTYPE[n])}, steps counted from the start of the call."""
+        args = _steady_args(max_steps, check_every, tol, patience)
+        capacity = _until_history_arg(history, args[0], args[1])
+        res = _CResidualSteadyResult()
+        rows = np.zeros(capacity, dtype=RESIDUAL_DTYPE)
+        _check(self.lib, self.lib.lbm_run_until_residual(self.handle, *args, ctypes.byref(res), rows.ctypes.data, capacity))
+        out = res.as_dict()
+        n = min(res.checks, capacity)
+        out["history"] = (np.arange(1, n + 1, dtype=np.int32) * np.int32(args[1]), rows[:n])
+        return out
+
     def set_frames(self, every: int, capacity: int = 0) -> None:
         """Record |u| of the owned rows after every global timestep tt with tt % every == 0 (the reference's
         write_animation_data hook, SerialCode/d2q9-bgk.c:171-173) into a device buffer of `capacity` frames.
@@ -942,6 +981,23 @@ class Batch:
         _check(self.lib, self.lib.lbm_batch_run_until(self._live(), *args, res, ctypes.byref(steps)))
         return [r.as_dict() for r in res]
 
+    def run_until_residual(self, max_steps: int, check_every: int = 1024, tol: float = 1e-4, patience: int = 2, history=None) -> list[dict]:
+        """Engine.run_until_residual for every member at once (lbm_batch_run_until_residual): every member its own
+        baseline, rows and verdict, frozen once it is steady or diverged; the batch ends when every member is, or at
+        max_steps.  A list of one dict per member as Engine.run_until_residual's without "history" (steps_run is the
+        batch's); the history of the batch is attached once, to the list: its attribute `history` is
+        (steps int32[n], RESIDUAL_DTYPE[n, members])."""
+        args = _steady_args(max_steps, check_every, tol, patience)
+        capacity = _until_history_arg(history, args[0], args[1])
+        res = (_CResidualSteadyResult * len(self))()
+        steps = ctypes.c_int()
+        rows = np.zeros((capacity, len(self)), dtype=RESIDUAL_DTYPE)
+        _check(self.lib, self.lib.lbm_batch_run_until_residual(self._live(), *args, res, ctypes.byref(steps), rows.ctypes.data, capacity))
+        out = _BatchResidualSteady(r.as_dict() for r in res)
+        n = min(steps.value // args[1], capacity)      # segments judged: the call ends with a checked segment or at the cap
+        out.history = (np.arange(1, n + 1, dtype=np.int32) * np.int32(args[1]), rows[:n])
+        return out
+
     def info(self) -> dict:
         bi = _CBatchInfo()
         _check(self.lib, self.lib.lbm_batch_get_info(self._live(), ctypes.byref(bi)))
@@ -1051,6 +1107,9 @@ class BatchMember(Engine):
 
     def run_until(self, *args, **kwargs):
         raise LbmError("run_until: this engine is a member of a batch; Batch.run_until advances all its members")
+
+    def run_until_residual(self, *args, **kwargs):
+        raise LbmError("run_until_residual: this engine is a member of a batch; Batch.run_until_residual advances all its members")
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1436,6 +1495,22 @@ def _steady_args(max_steps, check_every, tol, patience) -> tuple[int, int, float
     if not float(tol) >= 0.0:
         raise LbmError(f"run_until: tol must be a non-negative number (got {tol})")
     return int(max_steps), int(check_every), float(tol), int(patience)
+
+
+def _until_history_arg(history, max_steps: int, check_every: int) -> int:
+    """run_until_residual's history argument (no device needed): the capacity in rows; None: one per possible check."""
+    if history is None:
+        return max_steps // check_every
+    if isinstance(history, bool) or not isinstance(history, (int, np.integer)):
+        raise LbmError(f"run_until: history must be an integer or None (got {history!r})")
+    if not 0 <= int(history) <= 2147483647:
+        raise LbmError(f"run_until: history must lie in [0, 2^31) (got {history})")
+    return min(int(history), max_steps // check_every)
+
+
+class _BatchResidualSteady(list):
+    """Batch.run_until_residual's result: the members' dicts, with the batch's `history` attached once."""
+    history = None
 
 
 def write_animation_frame(path: str, frame: np.ndarray, tt: int) -> None:

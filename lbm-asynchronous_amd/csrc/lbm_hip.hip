@@ -487,6 +487,13 @@ struct lbm_ctx {
   DeviceBuf<lbm::SteadyState> steady_state;  // device: what the checks of the current call have found
   PinnedBuf<int> steady_stop_host;  // pinned: its stop word after segment j, in slot j & 1 ...
   Event ev_steady[2];               // ... behind these events
+  // residual-steady runs (lbm_run_until_residual), allocated by the first such call and kept; the stop word, its pinned
+  // pair and the events are those above.  The planes are the call's own: the recorder never sees them.
+  DeviceBuf<float> until_planes;                    // device: [2][rows][nx]: the remembered u_x and u_y of slab 0
+  DeviceBuf<long long> until_words;                 // device: [lbm_residual::kResidualWords]: the sample of the current segment
+  DeviceBuf<lbm_residual::UntilState> until_state;  // device: what the checks of the current call have found (allocated last)
+  DeviceBuf<long long> until_history;               // device: [until_history_rows][kResidualWords]: the words of the first checks
+  size_t until_history_rows = 0;
 };
 
 // B independent single-slab lattices of one shape on one device, advanced together (lbm_create_batch).  The members
@@ -533,6 +540,15 @@ struct lbm_batch {
   PinnedBuf<int> steady_stop_host;  // pinned: all_steady after the last segment ...
   Event ev_steady;                  // ... behind this event
   DeviceBuf<lbm::SteadyState> steady_state;    // device: [members]
+  // residual-steady runs (lbm_batch_run_until_residual), allocated by the first such call and kept; until_state last
+  DeviceBuf<float> until_planes;                    // device: [members][2][rows][nx]
+  DeviceBuf<long long> until_words;                 // device: [members][lbm_residual::kResidualWords]
+  DeviceBuf<lbm::SteadyBatch> until_batch;          // device: the count of finished members
+  PinnedBuf<int> until_stop_host;                   // pinned: all_steady after the last segment ...
+  Event ev_until;                                   // ... behind this event
+  DeviceBuf<lbm_residual::UntilState> until_state;  // device: [members]
+  DeviceBuf<long long> until_history;               // device: [until_history_rows][members][kResidualWords]
+  size_t until_history_rows = 0;
 };
 
 // The kinds armed on a batch as a whole (lbm_batch::rec): what differs between them in the messages and in lbm_batch_run,
@@ -3667,8 +3683,9 @@ static int take_batch_stats(lbm_batch* bt) {
 }
 
 // ONE residual_gather_batch launch over all members' current (stored) lattices and planes, on the batch's stream:
-// the baseline (the planes filled, `row` unused) or a sample into `row`, [members][kResidualWords], zeroed in front
-static int launch_batch_residual(lbm_batch* bt, long long* row, bool baseline) {
+// the baseline (`planes` filled, `row` unused) or a sample against `planes` into `row`, [members][kResidualWords], zeroed
+// in front
+static int launch_batch_residual(lbm_batch* bt, float* planes, long long* row, bool baseline) {
   lbm_ctx* c0 = bt->members[0];
   const size_t n_members = bt->members.size();
   const Slab& sl0 = c0->slab[0];
@@ -3679,10 +3696,10 @@ static int launch_batch_residual(lbm_batch* bt, long long* row, bool baseline) {
   if (!baseline) HIP_TRY(LBM_FAILURE, hipMemsetAsync(row, 0, n_members * lbm_residual::kResidualWords * sizeof(long long), bt->stream));
   if (v == 4)
     hipLaunchKernelGGL(lbm::residual_gather_batch<4>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows,
-                       bt->residual_planes.get(), row, (int)baseline);
+                       planes, row, (int)baseline);
   else
     hipLaunchKernelGGL(lbm::residual_gather_batch<1>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows,
-                       bt->residual_planes.get(), row, (int)baseline);
+                       planes, row, (int)baseline);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
   return LBM_SUCCESS;
 }
@@ -3690,7 +3707,7 @@ static int launch_batch_residual(lbm_batch* bt, long long* row, bool baseline) {
 // the residual row of all members into the next slot
 static int take_batch_residual(lbm_batch* bt) {
   const size_t words = bt->members.size() * (size_t)lbm_residual::kResidualWords;
-  if (launch_batch_residual(bt, bt->residual_ring + (size_t)(bt->rec.written % bt->rec.slots) * words, false) != LBM_SUCCESS) return LBM_FAILURE;
+  if (launch_batch_residual(bt, bt->residual_planes, bt->residual_ring + (size_t)(bt->rec.written % bt->rec.slots) * words, false) != LBM_SUCCESS) return LBM_FAILURE;
   bt->rec.written++;
   return LBM_SUCCESS;
 }
@@ -4048,7 +4065,7 @@ int lbm_batch_set_residual(lbm_batch* bt, int every, int capacity) {
       if (bt->table.alloc(h.size()) != hipSuccess || hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess)
         LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: cannot allocate the member table; residuals stay off");
     }
-    return launch_batch_residual(bt, nullptr, true);  // the baselines of all members: one launch
+    return launch_batch_residual(bt, bt->residual_planes, nullptr, true);  // the baselines of all members: one launch
   };
   if (allocate() != LBM_SUCCESS) {
     (void)hipGetLastError();  // a failed allocation must not surface at the next launch
@@ -4125,6 +4142,15 @@ static void steady_fill(lbm_steady_result* out, const lbm::SteadyState& st, int 
   out->last_mean = st.prev_mean;
 }
 
+// the stop word of a checked run, its pinned pair and their events (slab 0's device is current)
+static int steady_buffers(lbm_ctx* c) {
+  if (c->ev_steady[1]) return LBM_SUCCESS;  // created last: the set is whole (an attempt that failed half-way starts again)
+  HIP_TRY(LBM_FAILURE, c->steady_state.alloc(1));
+  HIP_TRY(LBM_FAILURE, c->steady_stop_host.alloc(2));
+  for (int i = 0; i < 2; i++) HIP_TRY(LBM_FAILURE, c->ev_steady[i].create(hipEventDisableTiming));
+  return LBM_SUCCESS;
+}
+
 // One segment of a resident lbm_run_until call: what lbm_run issues for `n` steps (first-step acceleration, the launches
 // of run_resident with accel_last = 0 on the last one), except that the acceleration stands back once the checks have
 // said "stop"; then the check of the segment and its stop word on the way to slot `slot` of the pinned pair.
@@ -4163,11 +4189,7 @@ int lbm_run_until(lbm_ctx* c, int max_steps, int check_every, double tol, int pa
 
   Slab& sl = c->slab[0];
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-  if (!c->ev_steady[1]) {  // created last: the set is whole (an attempt that failed half-way starts again)
-    HIP_TRY(LBM_FAILURE, c->steady_state.alloc(1));
-    HIP_TRY(LBM_FAILURE, c->steady_stop_host.alloc(2));
-    for (int i = 0; i < 2; i++) HIP_TRY(LBM_FAILURE, c->ev_steady[i].create(hipEventDisableTiming));
-  }
+  if (steady_buffers(c) != LBM_SUCCESS) return LBM_FAILURE;
   hipLaunchKernelGGL(lbm::steady_reset, dim3(1), dim3(64), 0, sl.compute, c->steady_state, 1, (lbm::SteadyBatch*)nullptr);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
 
@@ -4277,6 +4299,255 @@ int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double to
   HIP_TRY(LBM_FAILURE, hipMemcpy(st.data(), bt->steady_state, st.size() * sizeof(st[0]), hipMemcpyDeviceToHost));
   *steps_run = bt->steps_done - start;
   for (int i = 0; i < n_members; i++) steady_fill(&out[i], st[(size_t)i], *steps_run);
+  return LBM_SUCCESS;
+}
+
+// ---- residual-steady runs ------------------------------------------------------------------------------------------
+// the history arguments of lbm_run_until_residual and its batch twin (no device needed): *rows = rows kept on the device
+static int until_history_ok(const char* who, const void* history, int history_capacity, int n_seg, size_t n_members, size_t* rows) {
+  if (history_capacity < 0) LBM_FAIL(LBM_FAILURE, "%s: negative history capacity %d", who, history_capacity);
+  *rows = history ? (size_t)(history_capacity < n_seg ? history_capacity : n_seg) : 0;
+  constexpr size_t kRowBytes = lbm_residual::kResidualWords * sizeof(long long);
+  if (*rows * n_members * kRowBytes >= ((size_t)1 << 31))
+    LBM_FAIL(LBM_FAILURE, "%s: a history of %zu rows of %zu lattices is %.2f GiB on the device, 2 GiB or more (%d bytes per lattice and row)", who,
+             *rows, n_members, (double)(*rows * n_members * kRowBytes) / 1073741824.0, (int)kRowBytes);
+  return LBM_SUCCESS;
+}
+
+static void until_fill(lbm_residual_steady_result* out, const lbm_residual::UntilState& st, int steps_run, int nx, int span) {
+  std::memset(out, 0, sizeof(*out));
+  out->steps_run = steps_run;
+  out->steady = st.stop == lbm_residual::kUntilSteady ? 1 : 0;
+  out->steady_step = st.steady_step;
+  out->checks = st.checks;
+  out->diverged = st.stop == lbm_residual::kUntilDiverged ? 1 : 0;
+  out->last_rel = st.last_rel;
+  out->last = lbm_residual::residual_row_from_words(st.last, 1, nx, st.checks > 0 ? span : 0);  // (no check: zeros at -1, -1)
+}
+
+// slab 0's current lattice against the call's planes: the baseline (residual_gather: the planes are filled), or a sample
+// into until_words that stands back once the stop word is set (residual_gather_unless)
+static void launch_until_gather(const lbm_ctx* c, const Slab& sl, bool baseline) {
+  const int v = stats_vector(c->p.nx);
+  const dim3 grid(stats_groups((long)sl.rows * c->p.nx, v)), block(lbm::kBlock);
+  const unsigned cell_first = (unsigned)sl.row_first * (unsigned)c->p.nx;
+  float* px = c->until_planes;
+  float* py = px + (size_t)sl.rows * c->p.nx;
+  long long* words = c->until_words;
+  const lbm::SteadyState* gate = c->steady_state;
+  if (baseline && v == 4)
+    hipLaunchKernelGGL(lbm::residual_gather<4>, grid, block, 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, px, py, words, 1);
+  else if (baseline)
+    hipLaunchKernelGGL(lbm::residual_gather<1>, grid, block, 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, px, py, words, 1);
+  else if (v == 4)
+    hipLaunchKernelGGL(lbm::residual_gather_unless<4>, grid, block, 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, px, py, words, gate);
+  else
+    hipLaunchKernelGGL(lbm::residual_gather_unless<1>, grid, block, 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, px, py, words, gate);
+}
+
+// One segment of an lbm_run_until_residual call, the `index`-th: its E steps -- on a resident shape as
+// steady_segment_resident issues them, with the acceleration standing back behind a stop; else as lbm_run does -- then
+// the sample of the lattice it left (standing back likewise), the check, and the stop word on its way to the pinned pair.
+static int until_segment(lbm_ctx* c, bool resident, int E, int index, size_t hist_rows, double tol, int patience) {
+  Slab& sl = c->slab[0];
+  const lbm::SteadyState* gate = c->steady_state;
+  if (resident) {
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    const AccelWeights w = accel_weights(c->p);
+    hipLaunchKernelGGL(lbm::accelerate_row_unless, dim3(ceil_div(c->p.nx, 256)), dim3(256), 0, sl.compute,
+                       lattice_args(c, sl, c->cur, c->cur), sl.accel_row, w.a1, w.a2, gate);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    if (run_resident(c, E) != LBM_SUCCESS) return LBM_FAILURE;
+    c->steps_done += E;
+  } else {
+    if (run_passes(c, E, false, false) != LBM_SUCCESS) return LBM_FAILURE;
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+  }
+  launch_until_gather(c, sl, false);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  long long* hist = (size_t)index < hist_rows ? c->until_history + (size_t)index * lbm_residual::kResidualWords : nullptr;
+  hipLaunchKernelGGL(lbm::residual_check, dim3(1), dim3(64), 0, sl.compute, c->until_words.get(), hist, tol, patience, (index + 1) * E,
+                     c->until_state.get(), c->steady_state.get());
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(c->steady_stop_host + (index & 1), &c->steady_state.get()->stop, sizeof(int), hipMemcpyDeviceToHost, sl.compute));
+  HIP_TRY(LBM_FAILURE, hipEventRecord(c->ev_steady[index & 1], sl.compute));
+  return LBM_SUCCESS;
+}
+
+int lbm_run_until_residual(lbm_ctx* c, int max_steps, int check_every, double tol, int patience, lbm_residual_steady_result* out,
+                           lbm_residual_row* history, int history_capacity) {
+  static const char who[] = "lbm_run_until_residual";
+  if (!c || !out) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", who);
+  if (c->batch) LBM_FAIL(LBM_FAILURE, kMemberRun, who);
+  if (steady_args_ok(who, c->steps_done, c->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
+  if (c->rec.kind != kRecNone) {
+    const RecorderKind& k = kRecorderKinds[c->rec.kind];
+    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, who, k.name, k.setter, k.noun);
+  }
+  if (c->halo_mode != LBM_HALO_SYNC) LBM_FAIL(LBM_FAILURE, "%s: only LBM_HALO_SYNC runs can be checked (the halo mode is %d)", who, c->halo_mode);
+  if (c->ranked || c->world > 1)
+    LBM_FAIL(LBM_FAILURE, "%s: not available in a multi-process context (every rank would have to take the same decision)", who);
+  if (c->n_slabs != 1)
+    LBM_FAIL(LBM_FAILURE, "%s: the context has %d slabs; the check reads one slab's words (single-slab contexts only)", who, c->n_slabs);
+  const int E = check_every, n_seg = max_steps / E, start = c->steps_done;
+  size_t hist_rows = 0;
+  if (until_history_ok(who, history, history_capacity, n_seg, 1, &hist_rows) != LBM_SUCCESS) return LBM_FAILURE;
+
+  Slab& sl = c->slab[0];
+  constexpr size_t kWords = lbm_residual::kResidualWords;
+  HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+  if (steady_buffers(c) != LBM_SUCCESS) return LBM_FAILURE;
+  if (!c->until_state) {  // allocated last: the set is whole
+    const size_t cells = (size_t)sl.rows * c->p.nx;
+    if (c->until_planes.alloc(2 * cells) != hipSuccess) {
+      (void)hipGetLastError();
+      LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the remembered field (%zu cells, %.1f MiB); nothing was run", who, cells,
+               (double)(2 * cells * sizeof(float)) / 1048576.0);
+    }
+    HIP_TRY(LBM_FAILURE, c->until_words.alloc(kWords));
+    HIP_TRY(LBM_FAILURE, c->until_state.alloc(1));
+  }
+  if (hist_rows > c->until_history_rows) {
+    c->until_history_rows = 0;
+    if (c->until_history.alloc(hist_rows * kWords) != hipSuccess) {
+      (void)hipGetLastError();
+      LBM_FAIL(LBM_FAILURE, "%s: cannot allocate a history of %zu rows (%.1f MiB); nothing was run", who, hist_rows,
+               (double)(hist_rows * kWords * sizeof(long long)) / 1048576.0);
+    }
+    c->until_history_rows = hist_rows;
+  }
+  hipLaunchKernelGGL(lbm::steady_reset, dim3(1), dim3(64), 0, sl.compute, c->steady_state, 1, (lbm::SteadyBatch*)nullptr);
+  hipLaunchKernelGGL(lbm::residual_until_reset, dim3(1), dim3(64), 0, sl.compute, c->until_state.get(), c->until_words.get(), 1,
+                     (lbm::SteadyBatch*)nullptr);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  launch_until_gather(c, sl, true);  // the baseline: the field of the current lattice into the call's planes
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+
+  // the segment loop of lbm_run_until, with its look-ahead (see there): everything a dropped segment enqueued behind its
+  // one launch -- the sample, the check -- reads the stop word first and changes nothing
+  const bool resident = c->plan.resident && E >= c->plan.resident_min_steps;
+  const int depth = (resident && E <= kResidentChunk) ? 2 : 1;
+  int issued = 0, judged = 0;
+  bool stop = false;
+  while (judged < n_seg && !stop) {
+    while (issued < n_seg && issued - judged < depth) {
+      if (until_segment(c, resident, E, issued, hist_rows, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
+      issued++;
+    }
+    HIP_TRY(LBM_FAILURE, hipEventSynchronize(c->ev_steady[judged & 1]));
+    stop = c->steady_stop_host[judged & 1] != 0;
+    judged++;
+    if (resident && *sl.res_status_host != 0) break;  // a launch gave up: lbm_sync below reports it
+  }
+  if (issued > judged) {  // the look-ahead segment is dropped, as in lbm_run_until
+    c->cur ^= 1;
+    c->steps_done -= E;
+    HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.res_gran, 0, resident_gran_bytes(c), sl.compute));
+  }
+  if (!stop && max_steps - n_seg * E > 0) {
+    const int rest = max_steps - n_seg * E;  // shorter than a segment: run as lbm_run runs it, not checked
+    if (run_passes(c, rest, c->plan.resident && rest >= c->plan.resident_min_steps, false) != LBM_SUCCESS) return LBM_FAILURE;
+  }
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;  // also reports a resident give-up
+  lbm_residual::UntilState st;
+  HIP_TRY(LBM_FAILURE, hipMemcpy(&st, c->until_state, sizeof(st), hipMemcpyDeviceToHost));
+  until_fill(out, st, c->steps_done - start, c->p.nx, E);
+  const size_t n_rows = (size_t)st.checks < hist_rows ? (size_t)st.checks : hist_rows;
+  if (n_rows > 0) {
+    std::vector<long long> words(n_rows * kWords);
+    HIP_TRY(LBM_FAILURE, hipMemcpy(words.data(), c->until_history, words.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n_rows; i++) history[i] = lbm_residual::residual_row_from_words(words.data() + i * kWords, 1, c->p.nx, E);
+  }
+  return LBM_SUCCESS;
+}
+
+int lbm_batch_run_until_residual(lbm_batch* bt, int max_steps, int check_every, double tol, int patience, lbm_residual_steady_result* out,
+                                 int* steps_run, lbm_residual_row* history, int history_capacity) {
+  static const char who[] = "lbm_batch_run_until_residual";
+  if (!bt || !out || !steps_run) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", who);
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  if (steady_args_ok(who, bt->steps_done, c0->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
+  for (const lbm_ctx* c : bt->members) {
+    if (c->rec.kind != kRecNone) {
+      const RecorderKind& k = kRecorderKinds[c->rec.kind];
+      LBM_FAIL(LBM_FAILURE, kSteadyRecorder, who, k.name, k.setter, k.noun);
+    }
+  }
+  if (bt->rec.kind != kRecNone)  // forces, statistics or residuals armed on the batch
+    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, who, kRecorderKinds[bt->rec.kind].name, batch_kind(bt->rec.kind)->setter,
+             kRecorderKinds[bt->rec.kind].noun);
+  const int E = check_every, n_seg = max_steps / E, start = bt->steps_done;
+  size_t hist_rows = 0;
+  if (until_history_ok(who, history, history_capacity, n_seg, n_members, &hist_rows) != LBM_SUCCESS) return LBM_FAILURE;
+
+  const Slab& sl0 = c0->slab[0];
+  const size_t row_words = n_members * (size_t)lbm_residual::kResidualWords;
+  HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
+  if (!bt->table) {  // a shape the resident kernel does not take: the gather still reads the members' lattices from the table
+    const std::vector<lbm::ResidentMember> h = member_table(bt);
+    if (bt->table.alloc(h.size()) != hipSuccess || hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      bt->table.reset();
+      LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the member table; nothing was run", who);
+    }
+  }
+  if (!bt->until_state) {  // allocated last: the set is whole
+    const size_t cells = (size_t)sl0.rows * c0->p.nx;
+    if (bt->until_planes.alloc(n_members * 2 * cells) != hipSuccess) {
+      (void)hipGetLastError();
+      LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the remembered fields of %zu members (%zu cells each, %.1f MiB); nothing was run", who,
+               n_members, cells, (double)(n_members * 2 * cells * sizeof(float)) / 1048576.0);
+    }
+    HIP_TRY(LBM_FAILURE, bt->until_words.alloc(row_words));
+    HIP_TRY(LBM_FAILURE, bt->until_batch.alloc(1));
+    HIP_TRY(LBM_FAILURE, bt->until_stop_host.alloc(1));
+    HIP_TRY(LBM_FAILURE, bt->ev_until.create(hipEventDisableTiming));
+    HIP_TRY(LBM_FAILURE, bt->until_state.alloc(n_members));
+  }
+  if (hist_rows > bt->until_history_rows) {
+    bt->until_history_rows = 0;
+    if (bt->until_history.alloc(hist_rows * row_words) != hipSuccess) {
+      (void)hipGetLastError();
+      LBM_FAIL(LBM_FAILURE, "%s: cannot allocate a history of %zu rows of %zu members (%.1f MiB); nothing was run", who, hist_rows, n_members,
+               (double)(hist_rows * row_words * sizeof(long long)) / 1048576.0);
+    }
+    bt->until_history_rows = hist_rows;
+  }
+  hipLaunchKernelGGL(lbm::residual_until_reset, dim3(ceil_div((long)n_members, 64)), dim3(64), 0, bt->stream, bt->until_state.get(),
+                     bt->until_words.get(), (int)n_members, bt->until_batch.get());
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  if (launch_batch_residual(bt, bt->until_planes, nullptr, true) != LBM_SUCCESS) return LBM_FAILURE;  // the baselines: one launch
+
+  // per segment the launches of lbm_batch_run, ONE sample launch and ONE check launch for all members; the host waits for
+  // each verdict, as lbm_batch_run_until does.  Finished members keep stepping -- and being sampled -- with the others.
+  bool stop = false;
+  int judged = 0;
+  for (; judged < n_seg && !stop; judged++) {
+    if (lbm_batch_run(bt, E) != LBM_SUCCESS) return LBM_FAILURE;
+    if (launch_batch_residual(bt, bt->until_planes, bt->until_words, false) != LBM_SUCCESS) return LBM_FAILURE;
+    long long* hist = (size_t)judged < hist_rows ? bt->until_history + (size_t)judged * row_words : nullptr;
+    hipLaunchKernelGGL(lbm::residual_check_batch, dim3((unsigned)n_members), dim3(64), 0, bt->stream, bt->until_words.get(), hist,
+                       (int)n_members, tol, patience, (judged + 1) * E, bt->until_state.get(), bt->until_batch.get());
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    HIP_TRY(LBM_FAILURE, hipMemcpyAsync(bt->until_stop_host, &bt->until_batch.get()->all_steady, sizeof(int), hipMemcpyDeviceToHost, bt->stream));
+    HIP_TRY(LBM_FAILURE, hipEventRecord(bt->ev_until, bt->stream));
+    HIP_TRY(LBM_FAILURE, hipEventSynchronize(bt->ev_until));
+    stop = *bt->until_stop_host != 0;
+  }
+  if (!stop && max_steps - n_seg * E > 0 && lbm_batch_run(bt, max_steps - n_seg * E) != LBM_SUCCESS) return LBM_FAILURE;
+  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
+  std::vector<lbm_residual::UntilState> st(n_members);
+  HIP_TRY(LBM_FAILURE, hipMemcpy(st.data(), bt->until_state, st.size() * sizeof(st[0]), hipMemcpyDeviceToHost));
+  *steps_run = bt->steps_done - start;
+  for (size_t i = 0; i < n_members; i++) until_fill(&out[i], st[i], *steps_run, c0->p.nx, E);
+  const size_t n_rows = (size_t)judged < hist_rows ? (size_t)judged : hist_rows;
+  if (n_rows > 0) {
+    std::vector<long long> words(n_rows * row_words);
+    HIP_TRY(LBM_FAILURE, hipMemcpy(words.data(), bt->until_history, words.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    for (size_t j = 0; j < n_rows * n_members; j++)
+      history[j] = lbm_residual::residual_row_from_words(words.data() + j * lbm_residual::kResidualWords, 1, c0->p.nx, E);
+  }
   return LBM_SUCCESS;
 }
 

@@ -37,6 +37,7 @@
 #include "lbm_exact_sum.h"
 #include "lbm_stats_row.h"
 #include "lbm_residual_row.h"
+#include "lbm_residual_until.h"
 
 namespace lbm {
 
@@ -3235,6 +3236,74 @@ __global__ __launch_bounds__(kBlock) void residual_gather_batch(const LatticeArg
   else
     residual_cells<V, false>(a, members[member].src, members[member].mask, rows, 0u, px, px + n,
                              row + (size_t)member * lbm_residual::kResidualWords);
+}
+
+// ---------------------------------------------------------------------------------------------
+// residual-steady runs (lbm_run_until_residual): a sample of the residuals after every segment, judged on the device
+// ---------------------------------------------------------------------------------------------
+// residual_gather's sample for a segment that was enqueued before the verdict of the segment in front of it was known:
+// once that verdict is "stop" (gate->stop: the word accelerate_row_unless reads) neither the words nor the remembered
+// field move.  The words are not zeroed by the host: residual_check leaves them zero behind every sample it has read.
+template <int V>
+__global__ __launch_bounds__(kBlock) void residual_gather_unless(const LatticeArgs a, int rows, unsigned cell_first, float* px, float* py,
+                                                                 long long* words, const SteadyState* gate) {
+  if (gate->stop) return;  // one scalar load, uniform over the grid
+  residual_cells<V, false>(a, a.src, a.mask, rows, cell_first, px, py, words);
+}
+
+__global__ void residual_until_reset(lbm_residual::UntilState* st, long long* words, int n, SteadyBatch* batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    lbm_residual::until_reset(st[i]);
+    for (int k = 0; k < lbm_residual::kResidualWords; k++) words[(size_t)i * lbm_residual::kResidualWords + k] = 0;
+  }
+  if (i == 0 && batch) *batch = SteadyBatch{0, 0};
+}
+
+// One wave and one lattice: lanes 0 and 1 round the two sums (lbm_residual_until.h: exact_sum_round_hd), lane 0 takes
+// the verdict (until_verdict), the first kResidualWords lanes copy the words into the history row (hist: NULL beyond the
+// capacity) and leave them zero for the next sample.  FROZEN_ROWS: a lattice whose verdict stands still hands its words
+// on (a batch member steps on with the others, and its later rows are real rows); without it nothing at all happens
+// after a stop, which is what a dropped look-ahead segment needs.  Returns the stop word this check set (lane 0).
+template <bool FROZEN_ROWS>
+__device__ __forceinline__ int residual_check_at(long long* words, long long* hist, double tol, int patience, int steps_after,
+                                                 lbm_residual::UntilState* st) {
+  const bool stopped = st->stop != lbm_residual::kUntilGoOn;  // uniform
+  if (stopped && !FROZEN_ROWS) return lbm_residual::kUntilGoOn;
+  const int lane = threadIdx.x;
+  int code = lbm_residual::kUntilGoOn;
+  if (!stopped) {
+    double sum = 0.0;
+    if (lane < lbm_residual::kResidualSums) sum = lbm_residual::exact_sum_round_hd(words + lane * lbm_exact::kExactLimbs);
+    const double sum_u_sq = __shfl(sum, 1, 64);
+    if (lane == 0) code = lbm_residual::until_verdict(*st, words, sum, sum_u_sq, tol, patience, steps_after);
+  }
+  long long w = 0;
+  if (lane < lbm_residual::kResidualWords) {
+    w = words[lane];
+    if (hist) hist[lane] = w;
+  }
+  __syncthreads();  // lane 0 has read the words (until_verdict keeps them) before they are cleared
+  if (lane < lbm_residual::kResidualWords) words[lane] = 0;
+  return code;
+}
+// gate->stop takes the stop word: the look-ahead segment's accelerate_row_unless and residual_gather_unless read it, and
+// it is what travels back to the host
+__global__ __launch_bounds__(64) void residual_check(long long* words, long long* hist, double tol, int patience, int steps_after,
+                                                     lbm_residual::UntilState* st, SteadyState* gate) {
+  const int code = residual_check_at<false>(words, hist, tol, patience, steps_after, st);
+  if (threadIdx.x == 0 && code != lbm_residual::kUntilGoOn) gate->stop = code;
+}
+// every member of a batch at once, one wave per member: grid (members); words and hist are [members][kResidualWords].
+// The member that completes the set of finished (steady or diverged) members raises all_steady, as in steady_check_batch.
+__global__ __launch_bounds__(64) void residual_check_batch(long long* words, long long* hist, int n_members, double tol, int patience,
+                                                           int steps_after, lbm_residual::UntilState* st, SteadyBatch* batch) {
+  const size_t at = (size_t)blockIdx.x * lbm_residual::kResidualWords;
+  const int code = residual_check_at<true>(words + at, hist ? hist + at : nullptr, tol, patience, steps_after, st + blockIdx.x);
+  if (threadIdx.x == 0 && code != lbm_residual::kUntilGoOn) {
+    const int before = __hip_atomic_fetch_add(&batch->n_steady, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (before + 1 == n_members) __hip_atomic_store(&batch->all_steady, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
 }
 
 }  // namespace lbm
