@@ -812,6 +812,62 @@ int lbm_batch_run_until_residual(lbm_batch* batch, int max_steps, int check_ever
                                  lbm_residual_steady_result* out /* [members] */, int* steps_run,
                                  lbm_residual_row* history /* [n][members] or NULL */, int history_capacity);
 
+/* ---- line profiles --------------------------------------------------------------------------
+ * The statistics resolved along one axis: one line of sums per row y (sums along x: u_x(y), the profile across the
+ * channel) and one per column x (sums along y: the flow rate Q(x) = sum of jx, the mean density along the channel), every
+ * `every` steps, without leaving the device.
+ * Per fluid cell, in fp32 with IEEE divide and no contraction, rho, jx, jy, ux = jx/rho, uy = jy/rho and usq =
+ * (ux*ux)+(uy*uy) exactly as the statistics' text above defines them.  A fluid cell is NON-FINITE when one of rho, jx, jy,
+ * usq is not finite (the statistics' rule; usq finite implies ux and uy finite); such a cell adds to no sum and is
+ * counted in `nonfinite` of its row line and of its column line.  Blocked cells contribute to nothing and are counted
+ * nowhere.
+ *     sum_rho, sum_jx, sum_jy, sum_ux, sum_uy = the sums over the line's finite fluid cells;  fluid = their number (the
+ *     divisor of a mean);  nonfinite = the line's fluid cells left out.  fluid + nonfinite = the line's non-blocked cells.
+ * Every sum is taken EXACTLY (csrc/lbm_exact_sum.h, one float per cell and sum) and rounded to a double once: the value
+ * math.fsum gives for the same terms.  A line without finite fluid cells reports +0.0 five times and fluid == 0.  A
+ * line therefore has the same bits from a single call, split calls, resident or per-pass kernels, 1, 2 or 3 slabs, a
+ * tiled context, a batch member, and from run to run.
+ * lbm_set_profiles(ctx, every, capacity, axes): from now on, after global timestep tt (0-based, the numbering of
+ *   lbm_set_frames) with tt % every == 0, record one record of the lattice after tt+1 timesteps: ny row lines (line y,
+ *   GLOBAL row) if axes & LBM_PROFILE_ROWS, then nx column lines (line x) if axes & LBM_PROFILE_COLUMNS; `lines` is ny, nx
+ *   or ny + nx.  Records wait in a device ring of `capacity` slots.  A line occupies 48 int64 words (384 bytes: 5 x 9
+ *   limbs, the two counts, one spare word); per slab one slot is (owned rows [if ROWS] + nx [if COLUMNS]) * 384 bytes: a
+ *   slab's column lines hold its own rows' share, and the reader adds the slabs' limbs as integers before the one
+ *   rounding.  An lbm_run that would record more records than there are free slots fails before issuing any work.
+ *   every == 0 disarms and frees; re-arming discards unread records.  A failed allocation of the ring says its size and
+ *   leaves the context disarmed.  No step kernel records profiles: as with the statistics every call runs as the sub-calls
+ *   that end at its sample steps, each followed per slab by one memset of the record and one launch per selected axis
+ *   (profile_rows, profile_columns; every == 1: correct, not fast).  Recording never changes the lattice or av_vels:
+ *   they equal those of the same run issued as calls split at the sample steps.
+ *   Refused, as lbm_set_stats refuses: negative every; capacity < 1; axes outside 1..3; a ring of 2 GiB or more; rank
+ *   contexts (lbm_create_rank*); batch members (a batch arms them as a whole: lbm_batch_set_profiles); LBM_HALO_STALE /
+ *   LBM_HALO_FRESHEST (and lbm_set_halo_mode to those while armed); a context with another recorder armed (and the other
+ *   setters while this one is armed); lbm_run_until and lbm_run_until_residual while armed.  Not offered: the double
+ *   engine, profiles inside the resident or stream kernels, windows, lines other than whole rows and columns.
+ * lbm_read_profiles: drains up to max_records oldest records into out[n][lines] and steps[n] (their tt, may be NULL);
+ *   out == NULL && steps == NULL: *n_read = records waiting, nothing drained.  Synchronises like the other readers.
+ * lbm_batch_set_profiles / lbm_batch_read_profiles: the same for every member of a batch, armed on the BATCH with one
+ *   `every`, one `axes` and ONE ring [slots][members][lines][48 words]; records are out[n][members][lines].  Behind each
+ *   sub-call that ends at a sample step the batch's stream gets one memset of the record and ONE launch per selected axis
+ *   for all members (profile_rows_batch, profile_columns_batch: grid z is the member).  Member i's records, lattice and
+ *   av_vels are bit-identical to those of an lbm_create context armed with lbm_set_profiles and advanced by the same
+ *   calls.  An lbm_batch_run without room fails before any work and moves no member's steps_done.  Refused as
+ *   lbm_batch_set_stats refuses: a member with a recorder armed, the batch's forces, statistics or residuals armed (and
+ *   every member-level setter and the three other batch-level setters while the profiles are armed); lbm_batch_run_until
+ *   and lbm_batch_run_until_residual while armed.
+ */
+#define LBM_PROFILE_ROWS    1   /* one line per row y: sums along x -- u_x(y), the profile across the channel */
+#define LBM_PROFILE_COLUMNS 2   /* one line per column x: sums along y -- Q(x), the pressure along the channel */
+typedef struct {
+  double sum_rho, sum_jx, sum_jy, sum_ux, sum_uy; /* exact sums over the line's finite fluid cells, each rounded once */
+  int    fluid;      /* finite fluid cells on the line: the divisor of a mean */
+  int    nonfinite;  /* fluid cells on the line left out of everything above */
+} lbm_profile_line;  /* 48 bytes; offsets 0 8 16 24 32 40 44 */
+int lbm_set_profiles(lbm_ctx* ctx, int every, int capacity, int axes);
+int lbm_read_profiles(lbm_ctx* ctx, int max_records, lbm_profile_line* out /* [n][lines] */, int* steps, int* n_read);
+int lbm_batch_set_profiles(lbm_batch* batch, int every, int capacity, int axes);
+int lbm_batch_read_profiles(lbm_batch* batch, int max_records, lbm_profile_line* out /* [n][members][lines] */, int* steps, int* n_read);
+
 /* ---- double precision -----------------------------------------------------------------------
  * The reference's programs are `float`, but its published golden results (the .dat files of check/) are its algorithm evaluated in
  * IEEE double.  A double context computes exactly that: the driver loop of SerialCode/d2q9-bgk.c:166-170 with every

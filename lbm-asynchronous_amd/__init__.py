@@ -56,6 +56,7 @@ ABI_SYMBOLS = (
     "lbm_set_stats", "lbm_read_stats", "lbm_batch_set_stats", "lbm_batch_read_stats",
     "lbm_set_residual", "lbm_read_residual", "lbm_batch_set_residual", "lbm_batch_read_residual",
     "lbm_run_until_residual", "lbm_batch_run_until_residual",
+    "lbm_set_profiles", "lbm_read_profiles", "lbm_batch_set_profiles", "lbm_batch_read_profiles",
     "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
     "lbm_double_sync", "lbm_double_read_av_vels", "lbm_double_read_cells", "lbm_double_read_final_state",
     "lbm_double_av_velocity", "lbm_double_total_density", "lbm_double_calc_reynolds",
@@ -274,6 +275,10 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_read_stats.argtypes = [P, I, P, P, PI]; lib.lbm_read_stats.restype = I
     lib.lbm_batch_set_stats.argtypes = [P, I, I]; lib.lbm_batch_set_stats.restype = I
     lib.lbm_batch_read_stats.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_stats.restype = I
+    lib.lbm_set_profiles.argtypes = [P, I, I, I]; lib.lbm_set_profiles.restype = I
+    lib.lbm_read_profiles.argtypes = [P, I, P, P, PI]; lib.lbm_read_profiles.restype = I
+    lib.lbm_batch_set_profiles.argtypes = [P, I, I, I]; lib.lbm_batch_set_profiles.restype = I
+    lib.lbm_batch_read_profiles.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_profiles.restype = I
     lib.lbm_set_residual.argtypes = [P, I, I]; lib.lbm_set_residual.restype = I
     lib.lbm_read_residual.argtypes = [P, I, P, P, PI]; lib.lbm_read_residual.restype = I
     lib.lbm_batch_set_residual.argtypes = [P, I, I]; lib.lbm_batch_set_residual.restype = I
@@ -756,6 +761,23 @@ class Engine:
         _check(self.lib, self.lib.lbm_read_residual(self.handle, int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
         return steps[:n.value].copy(), rows[:n.value].copy()
 
+    # -- line profiles (lbm_set_profiles / lbm_read_profiles) ---------------------------------------
+    def set_profiles(self, every: int, capacity: int = 16, axes=("rows", "columns")) -> None:
+        """Record, after every global timestep tt with tt % every == 0, for the lattice after tt + 1 steps, one line of
+        exact sums (rho, jx, jy, ux, uy over the line's finite fluid cells, each rounded once) and two counts per row
+        ("rows": sums along x) and per column ("columns": sums along y), into a device ring of `capacity` records.
+        `axes`: an int of LBM_PROFILE_* bits or a subset of ("rows", "columns").  every == 0 disarms; re-arming
+        discards unread records."""
+        every, capacity, axes = _profile_args(every, capacity, axes)
+        _check(self.lib, self.lib.lbm_set_profiles(self.handle, every, capacity, axes))
+        self._profile_axes = axes if every > 0 else 0
+
+    def profiles(self, max_records: int | None = None) -> tuple[np.ndarray, dict]:
+        """Drain up to max_records (default: all) waiting records, oldest first: (steps int32[n], {"rows":
+        PROFILE_DTYPE[n, ny], "columns": PROFILE_DTYPE[n, nx]}), the selected keys only."""
+        return _read_profiles(self.lib.lbm_read_profiles, self.lib, self.handle, max_records, getattr(self, "_profile_axes", 0), (),
+                              self.params.nx, self.params.ny)
+
     # -- results -----------------------------------------------------------------------------
     def av_vels(self, n: int | None = None) -> np.ndarray:
         n = self.info()["steps_done"] if n is None else n
@@ -1066,6 +1088,20 @@ class Batch:
         _check(self.lib, self.lib.lbm_batch_read_residual(self._live(), int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
         return steps[:n.value].copy(), rows[:n.value].copy()
 
+    # -- line profiles of all members (lbm_batch_set_profiles / lbm_batch_read_profiles) ------------------------------
+    def set_profiles(self, every: int, capacity: int = 16, axes=("rows", "columns")) -> None:
+        """Engine.set_profiles for every member at once: one `every`, one `axes` and one `capacity` for the batch,
+        records in one device ring, one launch per selected axis and sample whatever the number of members."""
+        every, capacity, axes = _profile_args(every, capacity, axes)
+        _check(self.lib, self.lib.lbm_batch_set_profiles(self._live(), every, capacity, axes))
+        self._profile_axes = axes if every > 0 else 0
+
+    def profiles(self, max_records: int | None = None) -> tuple[np.ndarray, dict]:
+        """Drain up to max_records (default: all) waiting records, oldest first: (steps int32[n], {"rows":
+        PROFILE_DTYPE[n, members, ny], "columns": PROFILE_DTYPE[n, members, nx]}), the selected keys only."""
+        return _read_profiles(self.lib.lbm_batch_read_profiles, self.lib, self._live(), max_records, getattr(self, "_profile_axes", 0),
+                              (len(self),), self.params[0].nx, self.params[0].ny)
+
     def force_links(self) -> np.ndarray:
         """Boundary links of every body of every member of the armed forces, int32[members, n_bodies]
         (lbm_batch_forces_links)."""
@@ -1366,6 +1402,92 @@ def write_stats(path: str, steps, rows) -> None:
             fh.write("%d:\t%.12E\t%.12E\t%.12E\t%.12E\t%.12E\t%d\t%d\t%d\n" % (
                 tt, float(r["mass"]), float(r["mom_x"]), float(r["mom_y"]), float(r["sum_u_sq"]), float(r["max_u"]),
                 int(r["max_x"]), int(r["max_y"]), int(r["nonfinite"])))
+
+
+# lbm_profile_line of include/lbm_hip.h, 48 bytes
+PROFILE_DTYPE = np.dtype([("sum_rho", "<f8"), ("sum_jx", "<f8"), ("sum_jy", "<f8"), ("sum_ux", "<f8"), ("sum_uy", "<f8"),
+                          ("fluid", "<i4"), ("nonfinite", "<i4")])
+PROFILE_ROWS = 1          # LBM_PROFILE_ROWS
+PROFILE_COLUMNS = 2       # LBM_PROFILE_COLUMNS
+_PROFILE_AXES = {"rows": PROFILE_ROWS, "columns": PROFILE_COLUMNS}
+
+
+def _profile_args(every, capacity, axes) -> tuple[int, int, int]:
+    """Engine.set_profiles' argument checks (no device needed): (every, capacity, axes as LBM_PROFILE_* bits)."""
+    for name, v in (("every", every), ("capacity", capacity)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise LbmError(f"set_profiles: {name} must be an integer (got {v!r})")
+        if not 0 <= int(v) <= 2147483647:
+            raise LbmError(f"set_profiles: {name} must lie in [0, 2^31) (got {v})")
+    if every > 0 and capacity < 1:
+        raise LbmError(f"set_profiles: capacity {capacity}, at least one record is needed")
+    if isinstance(axes, bool):
+        raise LbmError(f"set_profiles: axes must be 1, 2, 3 or a subset of ('rows', 'columns') (got {axes!r})")
+    if isinstance(axes, (int, np.integer)):
+        bits = int(axes)
+    elif isinstance(axes, str):
+        raise LbmError(f"set_profiles: axes must be 1, 2, 3 or a subset of ('rows', 'columns') (got {axes!r}; a single axis is ('{axes}',))")
+    else:
+        try:
+            names = list(axes)
+        except TypeError:
+            raise LbmError(f"set_profiles: axes must be 1, 2, 3 or a subset of ('rows', 'columns') (got {axes!r})") from None
+        bits = 0
+        for a in names:
+            if not isinstance(a, str) or a not in _PROFILE_AXES:
+                raise LbmError(f"set_profiles: unknown axis {a!r}; the axes are 'rows' and 'columns'")
+            bits |= _PROFILE_AXES[a]
+    if not 1 <= bits <= 3:
+        raise LbmError(f"set_profiles: axes {axes!r} select nothing the engine records; 1 (rows), 2 (columns) or 3 (both) are possible")
+    return int(every), int(capacity), bits
+
+
+def _read_profiles(reader, lib, handle, max_records, axes, members, nx, ny) -> tuple[np.ndarray, dict]:
+    """What Engine.profiles and Batch.profiles share: the waiting records through `reader`, split into the selected axes;
+    members: () or (n_members,)."""
+    if max_records is not None and (isinstance(max_records, bool) or not isinstance(max_records, (int, np.integer)) or max_records < 0):
+        raise LbmError(f"profiles: max_records must be a non-negative integer or None (got {max_records!r})")
+    n = ctypes.c_int()
+    _check(lib, reader(handle, 0, None, None, ctypes.byref(n)))  # records waiting
+    max_records = n.value if max_records is None else min(int(max_records), n.value)
+    n_rows = ny if axes & PROFILE_ROWS else 0
+    n_columns = nx if axes & PROFILE_COLUMNS else 0
+    lines = np.zeros((int(max_records),) + tuple(members) + (max(1, n_rows + n_columns),), dtype=PROFILE_DTYPE)
+    steps = np.empty(int(max_records), dtype=np.int32)
+    _check(lib, reader(handle, int(max_records), lines.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
+    lines = lines[:n.value]
+    out = {}
+    if axes & PROFILE_ROWS:
+        out["rows"] = lines[..., :n_rows].copy()
+    if axes & PROFILE_COLUMNS:
+        out["columns"] = lines[..., n_rows:n_rows + n_columns].copy()
+    return steps[:n.value].copy(), out
+
+
+def profile_means(lines) -> dict:
+    """The means a profile is plotted as, of lines of PROFILE_DTYPE (any shape), in float64: u_x, u_y, rho and j_x as
+    sum / fluid, pressure as c_sq * rho (c_sq = 1/3); NaN where a line has no finite fluid cell (fluid == 0)."""
+    lines = np.asarray(lines)
+    fluid = np.asarray(lines["fluid"], dtype=np.float64)
+    out = {}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for key, field in (("u_x", "sum_ux"), ("u_y", "sum_uy"), ("rho", "sum_rho"), ("j_x", "sum_jx")):
+            out[key] = np.where(fluid == 0.0, np.nan, np.asarray(lines[field], dtype=np.float64) / fluid)
+    out["pressure"] = out["rho"] * (1.0 / 3.0)
+    return out
+
+
+def write_profile(path: str, lines) -> None:
+    """One text line per profile line of `lines` (PROFILE_DTYPE[n]: the rows or the columns of one record): its index,
+    then tab-separated sum_rho, sum_jx, sum_jy, sum_ux and sum_uy as '%.12E' and fluid and nonfinite as '%d'."""
+    lines = np.asarray(lines)
+    if lines.dtype != PROFILE_DTYPE or lines.ndim != 1:
+        raise LbmError(f"write_profile: lines must be one axis of one record, PROFILE_DTYPE[n] (got shape {lines.shape}, dtype {lines.dtype})")
+    with open(path, "w") as fh:
+        for i, r in enumerate(lines):
+            fh.write("%d\t%.12E\t%.12E\t%.12E\t%.12E\t%.12E\t%d\t%d\n" % (
+                i, float(r["sum_rho"]), float(r["sum_jx"]), float(r["sum_jy"]), float(r["sum_ux"]), float(r["sum_uy"]),
+                int(r["fluid"]), int(r["nonfinite"])))
 
 
 # lbm_residual_row of include/lbm_hip.h, 40 bytes

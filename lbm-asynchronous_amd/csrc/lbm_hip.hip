@@ -257,6 +257,8 @@ struct Slab {
   DeviceBuf<long long> stats_ring;         // lbm_set_stats: [slots][lbm_stats::kStatsWords]: this slab's exact sums, count and max key
   DeviceBuf<long long> residual_ring;      // lbm_set_residual: [slots][lbm_residual::kResidualWords]: likewise
   DeviceBuf<float> residual_planes;        // ... [2][rows][nx]: the remembered u_x and u_y of this slab's owned cells
+  DeviceBuf<long long> profile_ring;       // lbm_set_profiles: [slots][rows (if ROWS) + nx (if COLUMNS)][lbm_profile::kProfileWords]: this
+                                           // slab's row lines, then its rows' share of every column line
   // freshest-available mode (LBM_HALO_FRESHEST), allocated at its first use in this order: whole once ev_fresh[1] exists
   DeviceBuf<float> fresh_stage;          // [parity][side: 0 south halo, 1 north halo][row_pitch]: this pass's rows, if they make it
   DeviceBuf<unsigned> fresh_arrived;     // [parity][side]: id (global step + 1) of the step whose row the staging holds
@@ -409,10 +411,11 @@ struct GraphBuilder {
 // Lattice statistics (lbm_set_stats) are recorded the same way, by stats_gather: a row of whole-lattice sums.
 // Velocity residuals (lbm_set_residual) likewise, by residual_gather, which also keeps a field between the samples: the
 // velocities of the last sample (at first: of arming), which every sample compares with and replaces.
+// Line profiles (lbm_set_profiles) likewise, by profile_rows and profile_columns: a record of per-row and per-column sums.
 enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean,
-       kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecResidual = 7, kRecKinds = 8 };
+       kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecResidual = 7, kRecProfiles = 8, kRecKinds = 9 };
 // the kinds recorded by a gather launch behind the sub-call that ends at a sample step, whatever kernels advance the lattice
-constexpr bool records_behind(int kind) { return kind == kRecForces || kind == kRecStats || kind == kRecResidual; }
+constexpr bool records_behind(int kind) { return kind == kRecForces || kind == kRecStats || kind == kRecResidual || kind == kRecProfiles; }
 struct Recorder {
   int kind = kRecNone;
   int every = 0;
@@ -424,6 +427,7 @@ struct Recorder {
   int fields = 0;           // field frames: the LBM_FIELD_* bits ...
   lbm_window window = {0, 0, 0, 0};  // ... and the window, global cells
   int base_steps = 0;       // velocity residuals: steps_done at arming, the step of the baseline (the first row's span)
+  int axes = 0;             // line profiles: the LBM_PROFILE_* bits
 };
 // what differs between the kinds in the host's messages (indexed by kind; kRecNone keeps the empty defaults)
 struct RecorderKind {
@@ -450,7 +454,9 @@ constexpr RecorderKind kRecorderKinds[kRecKinds] = {
     {.name = "lattice statistics", .noun = "statistics", .record = "row", .setter = "lbm_set_stats",
      .reader = "lbm_read_stats", .disarm = "lbm_set_stats(ctx, 0, 0)"},
     {.name = "velocity residuals", .noun = "residuals", .record = "row", .setter = "lbm_set_residual",
-     .reader = "lbm_read_residual", .disarm = "lbm_set_residual(ctx, 0, 0)"}};
+     .reader = "lbm_read_residual", .disarm = "lbm_set_residual(ctx, 0, 0)"},
+    {.name = "line profiles", .noun = "profiles", .record = "record", .setter = "lbm_set_profiles",
+     .reader = "lbm_read_profiles", .disarm = "lbm_set_profiles(ctx, 0, 0, 0)"}};
 
 struct lbm_ctx {
   lbm_params p;
@@ -516,14 +522,15 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentProbes> probe_table;  // device: [members], allocated when the first member arms probes
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
   DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
-  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
+  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
                                     // (a batch records one kind, so at most one count is non-zero; the forces, the
-                                    // statistics and the residuals are armed on the batch, lbm_batch_set_forces /
-                                    // lbm_batch_set_stats / lbm_batch_set_residual, and count as one)
-  // obstacle forces, lattice statistics or velocity residuals of all members (lbm_batch_set_forces, lbm_batch_set_stats,
-  // lbm_batch_set_residual): the members' own recorders stay off, the batch keeps the one recorder and the one ring; every
-  // lbm_batch_run runs as the sub-calls that end at its sample steps
-  Recorder rec;                                  // kind kRecForces, kRecStats or kRecResidual while armed
+                                    // statistics, the residuals and the profiles are armed on the batch, lbm_batch_set_forces /
+                                    // lbm_batch_set_stats / lbm_batch_set_residual / lbm_batch_set_profiles, and count as one)
+  // obstacle forces, lattice statistics, velocity residuals or line profiles of all members (lbm_batch_set_forces,
+  // lbm_batch_set_stats, lbm_batch_set_residual, lbm_batch_set_profiles): the members' own recorders stay off, the batch
+  // keeps the one recorder and the one ring; every lbm_batch_run runs as the sub-calls that end at its sample steps
+  Recorder rec;                                  // kind kRecForces, kRecStats, kRecResidual or kRecProfiles while armed
+  DeviceBuf<long long> profile_ring;             // lbm_batch_set_profiles: device: [slots][members][lines][lbm_profile::kProfileWords]
   DeviceBuf<long long> stats_ring;               // lbm_batch_set_stats: device: [slots][members][lbm_stats::kStatsWords]
   DeviceBuf<long long> residual_ring;            // lbm_batch_set_residual: device: [slots][members][lbm_residual::kResidualWords]
   DeviceBuf<float> residual_planes;              // ... device: [members][2][rows][nx]: the members' remembered u_x and u_y
@@ -556,6 +563,7 @@ struct lbm_batch {
 static int take_batch_forces(lbm_batch* bt);
 static int take_batch_stats(lbm_batch* bt);
 static int take_batch_residual(lbm_batch* bt);
+static int take_batch_profiles(lbm_batch* bt);
 struct BatchKind {
   int kind;
   const char* setter;
@@ -566,7 +574,8 @@ struct BatchKind {
 static const BatchKind kBatchKinds[] = {
     {kRecForces, "lbm_batch_set_forces", "lbm_batch_read_forces", "lbm_batch_set_forces(batch, 0, NULL, 0, 0)", take_batch_forces},
     {kRecStats, "lbm_batch_set_stats", "lbm_batch_read_stats", "lbm_batch_set_stats(batch, 0, 0)", take_batch_stats},
-    {kRecResidual, "lbm_batch_set_residual", "lbm_batch_read_residual", "lbm_batch_set_residual(batch, 0, 0)", take_batch_residual}};
+    {kRecResidual, "lbm_batch_set_residual", "lbm_batch_read_residual", "lbm_batch_set_residual(batch, 0, 0)", take_batch_residual},
+    {kRecProfiles, "lbm_batch_set_profiles", "lbm_batch_read_profiles", "lbm_batch_set_profiles(batch, 0, 0, 0)", take_batch_profiles}};
 static const BatchKind* batch_kind(int kind) {
   for (const BatchKind& k : kBatchKinds)
     if (k.kind == kind) return &k;
@@ -1387,9 +1396,10 @@ const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = f
   static const Form forms[2][kRecKinds] = {
       {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>, resident_form<false, kRecMean>,
        resident_form<false, kRecFields>, resident_form<false, kRecNone>, resident_form<false, kRecNone>,
-       resident_form<false, kRecNone>},  // (the forces, the statistics and the residuals run the plain form)
+       resident_form<false, kRecNone>, resident_form<false, kRecNone>},  // (the forces, the statistics, the residuals and the profiles run the plain form)
       {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>, resident_form<true, kRecMean>,
-       resident_form<true, kRecFields>, resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>}};
+       resident_form<true, kRecFields>, resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>,
+       resident_form<true, kRecNone>}};
   return forms[batch][rec]((rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
 }
 
@@ -1618,6 +1628,35 @@ void launch_residual_gather(const lbm_ctx* c, const Slab& sl, long long* words, 
                        (int)baseline);
 }
 
+// rows of a band of profile_columns / profile_columns_batch for `rows` rows of nx cells: about kProfileTargetGroups
+// workgroups where the grid has that many bands of kProfileMinBand rows, so that small and large grids both fill the device
+constexpr int kProfileTargetGroups = 1024;  // four workgroups per CU
+int profile_band_rows(int rows, int nx) {
+  const int col_groups = ceil_div(nx, lbm::kProfileColumns);
+  const int bands = kProfileTargetGroups / col_groups > 1 ? kProfileTargetGroups / col_groups : 1;
+  const int band_rows = ceil_div(rows, bands);
+  return band_rows > lbm::kProfileMinBand ? band_rows : lbm::kProfileMinBand;
+}
+
+// one profile sample of a slab's current lattice into `lines` (zeroed in front, on the same stream): its row lines, then
+// its share of the column lines
+void launch_profiles(const lbm_ctx* c, const Slab& sl, long long* lines) {
+  const int nx = c->p.nx;
+  if (c->rec.axes & LBM_PROFILE_ROWS) {
+    const dim3 grid(ceil_div(sl.rows, lbm::kBlock / 64));
+    if (stats_vector(nx) == 4)
+      hipLaunchKernelGGL(lbm::profile_rows<4>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, lines);
+    else
+      hipLaunchKernelGGL(lbm::profile_rows<1>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, lines);
+    lines += (size_t)sl.rows * lbm_profile::kProfileWords;
+  }
+  if (c->rec.axes & LBM_PROFILE_COLUMNS) {
+    const int band_rows = profile_band_rows(sl.rows, nx);
+    hipLaunchKernelGGL(lbm::profile_columns, dim3(ceil_div(nx, lbm::kProfileColumns), ceil_div(sl.rows, band_rows)), dim3(lbm::kBlock), 0,
+                       sl.compute, lattice_args(c, sl), sl.rows, band_rows, lines);
+  }
+}
+
 // the record of the current (stored) lattice into the next slot, on every slab's compute stream: the frame of its rows,
 // or the gathered samples of the probes in its rows; or, for the mean fields, the sample of its rows added to their sums
 int take_record(lbm_ctx* c) {
@@ -1655,6 +1694,12 @@ int take_record(lbm_ctx* c) {
           long long* words = sl.residual_ring + slot * (size_t)lbm_residual::kResidualWords;
           HIP_TRY(LBM_FAILURE, hipMemsetAsync(words, 0, lbm_residual::kResidualWords * sizeof(long long), sl.compute));
           launch_residual_gather(c, sl, words, false);
+        } else if (c->rec.kind == kRecProfiles) {
+          // the slab's lines start from zeros (profile_columns adds into them, profile_rows leaves a line's spare word)
+          const size_t words = lbm_profile::profile_slab_lines(sl.rows, c->p.nx, c->rec.axes) * lbm_profile::kProfileWords;
+          long long* lines = sl.profile_ring + slot * words;
+          HIP_TRY(LBM_FAILURE, hipMemsetAsync(lines, 0, words * sizeof(long long), sl.compute));
+          launch_profiles(c, sl, lines);
         } else if (c->rec.kind == kRecMean)
           hipLaunchKernelGGL(lbm::mean_accumulate, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              c->p.density, sl.mean_sums, n, c->rec.order);
@@ -2392,6 +2437,7 @@ void release_recorder(lbm_ctx* c) {
     sl.stats_ring.reset();
     sl.residual_ring.reset();
     sl.residual_planes.reset();
+    sl.profile_ring.reset();
     sl.probe_count = 0;
   }
   c->probe_cells.clear();
@@ -3244,6 +3290,78 @@ int lbm_read_residual(lbm_ctx* c, int max_rows, lbm_residual_row* out, int* step
     for (int i = 0; i < n; i++)
       out[i] = lbm_residual::residual_row_from_words(rows.data() + (size_t)i * n_slabs * words, (int)n_slabs, c->p.nx,
                                                      residual_span(c->rec, c->rec.read + i));
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_set_profiles(lbm_ctx* c, int every, int capacity, int axes) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: null context");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: negative interval %d", every);
+  constexpr long long kLineBytes = lbm_profile::kProfileWords * (long long)sizeof(long long);
+  if (every > 0) {
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: capacity %d, at least one record is needed", capacity);
+    if (axes < 1 || axes > (LBM_PROFILE_ROWS | LBM_PROFILE_COLUMNS))
+      LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: axes %d, LBM_PROFILE_ROWS (1), LBM_PROFILE_COLUMNS (2) or both (3) are possible", axes);
+    for (int s = 0; s < c->n_slabs; s++) {
+      const long long slot_bytes = (long long)lbm_profile::profile_slab_lines(c->slab[s].rows, c->p.nx, axes) * kLineBytes;
+      if ((long long)capacity * slot_bytes >= (1LL << 31))
+        LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: a ring of %d records is 2 GiB or more (%lld bytes per record and slab)", capacity, slot_bytes);
+    }
+    if (c->ranked || c->world > 1)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: not available in a multi-process (rank) context: a column's sums would be spread over the ranks");
+    if (c->batch)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
+               "end at, so the profiles of a batch are armed on the batch, with one `every` for all members (lbm_batch_set_profiles)");
+  }
+  const int status = rearm_recorder(c, kRecProfiles, every, capacity, [&]() -> int {
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      const size_t ring_bytes = (size_t)capacity * lbm_profile::profile_slab_lines(sl.rows, c->p.nx, axes) * (size_t)kLineBytes;
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      if (sl.profile_ring.alloc_bytes(ring_bytes) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: cannot allocate %d records (%.1f MiB for slab %d); profiles stay off", capacity,
+                 (double)ring_bytes / 1048576.0, s);
+    }
+    return LBM_SUCCESS;
+  });
+  if (status == LBM_SUCCESS && every > 0) c->rec.axes = axes;
+  return status;
+}
+
+int lbm_read_profiles(lbm_ctx* c, int max_records, lbm_profile_line* out, int* steps, int* n_read) {
+  return drain_recorder(c, kRecProfiles, max_records, out != nullptr, steps, n_read, [&](int n) -> int {
+    const size_t slots = (size_t)c->rec.slots, n_slabs = (size_t)c->n_slabs;
+    const int nx = c->p.nx, ny = c->p.ny, axes = c->rec.axes;
+    // every slab's words of the n records (they wait in at most two runs of its ring), gathered as records[record][slab's
+    // share]; the shares of a record become its lines by profile_lines_from_words
+    int row_first[kMaxSlabs], row_count[kMaxSlabs];
+    size_t share_at[kMaxSlabs + 1] = {0};  // where slab s's words start in a record's
+    for (size_t s = 0; s < n_slabs; s++) {
+      row_first[s] = c->slab[s].row_first;
+      row_count[s] = c->slab[s].rows;
+      share_at[s + 1] = share_at[s] + lbm_profile::profile_slab_lines(row_count[s], nx, axes) * lbm_profile::kProfileWords;
+    }
+    const size_t record_words = share_at[n_slabs];
+    std::vector<long long> records((size_t)n * record_words), stage;
+    for (size_t s = 0; s < n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      const size_t words = share_at[s + 1] - share_at[s];
+      stage.resize((size_t)n * words);
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      for (int i = 0; i < n;) {
+        const size_t slot = (size_t)((c->rec.read + i) % c->rec.slots);
+        const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
+        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, sl.profile_ring + slot * words, (size_t)run * words * sizeof(long long),
+                                            hipMemcpyDeviceToHost, sl.compute));
+        i += run;
+      }
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+      for (size_t i = 0; i < (size_t)n; i++) memcpy(&records[i * record_words + share_at[s]], &stage[i * words], words * sizeof(long long));
+    }
+    const size_t lines = lbm_profile::profile_slab_lines(ny, nx, axes);
+    for (int i = 0; i < n; i++)
+      lbm_profile::profile_lines_from_words(records.data() + (size_t)i * record_words, (int)n_slabs, row_first, row_count, nx, ny, axes,
+                                            out + (size_t)i * lines);
     return LBM_SUCCESS;
   });
 }
@@ -4111,6 +4229,143 @@ int lbm_batch_read_residual(lbm_batch* bt, int max_rows, lbm_residual_row* out, 
     for (size_t j = 0; j < (size_t)n * n_members; j++)
       out[j] = lbm_residual::residual_row_from_words(stage.data() + j * lbm_residual::kResidualWords, 1, bt->members[0]->p.nx,
                                                      residual_span(r, r.read + (long long)(j / n_members)));
+  }
+  if (steps)
+    for (int i = 0; i < n; i++) steps[i] = (int)((r.ord0 + r.read + i) * r.every);
+  r.read += n;
+  *n_read = n;
+  return LBM_SUCCESS;
+}
+
+// ---- line profiles of a batch --------------------------------------------------------------------------------------
+// the profile record of the members' current (stored) lattices into the next slot: the record's words of all members
+// zeroed at once, then one launch per selected axis for all of them, on the batch's stream
+static int take_batch_profiles(lbm_batch* bt) {
+  lbm_ctx* c0 = bt->members[0];
+  const Slab& sl0 = c0->slab[0];
+  const size_t n_members = bt->members.size();
+  const int nx = c0->p.nx, axes = bt->rec.axes;
+  const long member_words = (long)(lbm_profile::profile_slab_lines(sl0.rows, nx, axes) * lbm_profile::kProfileWords);
+  long long* record = bt->profile_ring + (size_t)(bt->rec.written % bt->rec.slots) * n_members * (size_t)member_words;
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
+  HIP_TRY(LBM_FAILURE, hipMemsetAsync(record, 0, n_members * (size_t)member_words * sizeof(long long), bt->stream));
+  long long* lines = record;
+  if (axes & LBM_PROFILE_ROWS) {
+    const dim3 grid((unsigned)ceil_div(sl0.rows, lbm::kBlock / 64), 1, (unsigned)n_members);
+    if (stats_vector(nx) == 4)
+      hipLaunchKernelGGL(lbm::profile_rows_batch<4>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, lines, member_words);
+    else
+      hipLaunchKernelGGL(lbm::profile_rows_batch<1>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, lines, member_words);
+    lines += (size_t)sl0.rows * lbm_profile::kProfileWords;
+  }
+  if (axes & LBM_PROFILE_COLUMNS) {
+    const int band_rows = profile_band_rows(sl0.rows, nx);
+    const dim3 grid((unsigned)ceil_div(nx, lbm::kProfileColumns), (unsigned)ceil_div(sl0.rows, band_rows), (unsigned)n_members);
+    hipLaunchKernelGGL(lbm::profile_columns_batch, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, band_rows, lines,
+                       member_words);
+  }
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  bt->rec.written++;
+  return LBM_SUCCESS;
+}
+
+static void release_batch_profiles(lbm_batch* bt) {
+  (void)hipSetDevice(bt->members[0]->slab[0].device);
+  bt->profile_ring.reset();
+  bt->rec = Recorder{};
+  bt->armed[kRecProfiles] = 0;
+}
+
+int lbm_batch_set_profiles(lbm_batch* bt, int every, int capacity, int axes) {
+  if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: null batch");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: negative interval %d", every);
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  bool taken;  // the batch's one recorder holds another kind
+  if (batch_recorder_taken(bt, kRecProfiles, "lbm_batch_set_profiles", every, &taken) != LBM_SUCCESS) return LBM_FAILURE;
+  if (taken) return LBM_SUCCESS;
+  size_t record_bytes = 0;
+  if (every > 0) {
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: capacity %d, at least one record is needed", capacity);
+    if (axes < 1 || axes > (LBM_PROFILE_ROWS | LBM_PROFILE_COLUMNS))
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: axes %d, LBM_PROFILE_ROWS (1), LBM_PROFILE_COLUMNS (2) or both (3) are possible", axes);
+    const size_t member_bytes = lbm_profile::profile_slab_lines(c0->slab[0].rows, c0->p.nx, axes) * lbm_profile::kProfileWords * sizeof(long long);
+    record_bytes = n_members * member_bytes;
+    if ((long long)capacity * (long long)record_bytes >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: a ring of %d records of %d members is %.2f GiB, 2 GiB or more (%zu bytes per member and record)",
+               capacity, (int)n_members, (double)capacity * (double)record_bytes / 1073741824.0, member_bytes);
+    for (size_t i = 0; i < n_members; i++) {
+      const Recorder& r = bt->members[i]->rec;
+      if (r.kind != kRecNone)
+        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: member %d has %s armed (%s); a batch records one kind -- disarm them with %s first", (int)i,
+                 kRecorderKinds[r.kind].name, kRecorderKinds[r.kind].setter, kRecorderKinds[r.kind].disarm);
+    }
+  }
+  // the ring may still be written by launches in flight
+  HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
+  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
+  release_batch_profiles(bt);
+  if (every == 0) return LBM_SUCCESS;
+
+  auto allocate = [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * record_bytes;
+    if (bt->profile_ring.alloc_bytes(ring_bytes) != hipSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: cannot allocate %d records of %d members (%.1f MiB); profiles stay off", capacity,
+               (int)n_members, (double)ring_bytes / 1048576.0);
+    if (!bt->table) {  // a shape the resident kernel does not take: the kernels still read the members' lattices from the table
+      const std::vector<lbm::ResidentMember> h = member_table(bt);
+      if (bt->table.alloc(h.size()) != hipSuccess || hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: cannot allocate the member table; profiles stay off");
+    }
+    return LBM_SUCCESS;
+  };
+  if (allocate() != LBM_SUCCESS) {
+    (void)hipGetLastError();  // a failed allocation must not surface at the next launch
+    release_batch_profiles(bt);
+    return LBM_FAILURE;
+  }
+  bt->rec.kind = kRecProfiles;
+  bt->rec.every = every;
+  bt->rec.slots = capacity;
+  bt->rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
+  bt->rec.axes = axes;
+  bt->armed[kRecProfiles] = 1;
+  return LBM_SUCCESS;
+}
+
+int lbm_batch_read_profiles(lbm_batch* bt, int max_records, lbm_profile_line* out, int* steps, int* n_read) {
+  if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_profiles: NULL argument");
+  *n_read = 0;
+  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
+  Recorder& r = bt->rec;
+  const long long waiting = (r.kind == kRecProfiles) ? r.written - r.read : 0;
+  if (!out && !steps) {
+    *n_read = (int)waiting;
+    return LBM_SUCCESS;
+  }
+  if (!out) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_profiles: NULL record output");
+  if (max_records < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_profiles: negative max_records %d", max_records);
+  const int n = (waiting < max_records) ? (int)waiting : max_records;
+  if (n > 0) {
+    // the n oldest records wait in at most two runs of the ring; every member's words become its lines
+    const lbm_ctx* c0 = bt->members[0];
+    const int nx = c0->p.nx, ny = c0->slab[0].rows, row_first = 0;
+    const size_t n_members = bt->members.size(), lines = lbm_profile::profile_slab_lines(ny, nx, r.axes);
+    const size_t member_words = lines * lbm_profile::kProfileWords, words = n_members * member_words;
+    const size_t slots = (size_t)r.slots;
+    std::vector<long long> stage((size_t)n * words);
+    HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
+    for (int i = 0; i < n;) {
+      const size_t slot = (size_t)((r.read + i) % r.slots);
+      const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, bt->profile_ring + slot * words, (size_t)run * words * sizeof(long long),
+                                          hipMemcpyDeviceToHost, bt->stream));
+      i += run;
+    }
+    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
+    for (size_t j = 0; j < (size_t)n * n_members; j++)
+      lbm_profile::profile_lines_from_words(stage.data() + j * member_words, 1, &row_first, &ny, nx, ny, r.axes, out + j * lines);
   }
   if (steps)
     for (int i = 0; i < n; i++) steps[i] = (int)((r.ord0 + r.read + i) * r.every);

@@ -37,6 +37,7 @@
 #include "lbm_exact_sum.h"
 #include "lbm_stats_row.h"
 #include "lbm_residual_row.h"
+#include "lbm_profile_row.h"
 #include "lbm_residual_until.h"
 
 namespace lbm {
@@ -47,8 +48,9 @@ constexpr int kNoRow = -1000000;  // "no such row in this slab"
 // what a context records while it runs, at most one at a time: the host's Recorder::kind and resident_band's REC
 constexpr int kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3, kRecFields = 4;
 // (the obstacle forces, lbm_set_forces / lbm_batch_set_forces, the lattice statistics, lbm_set_stats /
-// lbm_batch_set_stats, and the velocity residuals, lbm_set_residual / lbm_batch_set_residual, are recorder kinds of the
-// host alone: force_gather, stats_gather, residual_gather and their batch twins run behind the step kernels)
+// lbm_batch_set_stats, the velocity residuals, lbm_set_residual / lbm_batch_set_residual, and the line profiles,
+// lbm_set_profiles / lbm_batch_set_profiles, are recorder kinds of the host alone: force_gather, stats_gather,
+// residual_gather, profile_rows, profile_columns and their batch twins run behind the step kernels)
 
 // 1/3 rounded to fp32, and the two constant divisors of the equilibrium, folded in fp32
 // exactly as the reference's "2.f * c_sq" and "2.f * c_sq * c_sq" (SerialCode/d2q9-bgk.c:308,367-370)
@@ -3304,6 +3306,169 @@ __global__ __launch_bounds__(64) void residual_check_batch(long long* words, lon
     const int before = __hip_atomic_fetch_add(&batch->n_steady, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (before + 1 == n_members) __hip_atomic_store(&batch->all_steady, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// line profiles (lbm_set_profiles): per row and per column the exact sums of rho, jx, jy, ux, uy over the line's finite
+// fluid cells, their number and the number of fluid cells that are not finite, of a whole stored lattice
+// ---------------------------------------------------------------------------------------------
+// One sample is one launch per selected axis (behind the sub-call that ends at the sample step, like stats_gather), into
+// the record's lines of kProfileWords words each (lbm_profile_row.h), zeroed by the host before the launches.  The two
+// axes reduce in different directions, so a lane owns different things in each: in profile_rows a wave owns a row and its
+// lanes stride along it; in profile_columns a lane owns a column and walks down it.  Both keep five fixed-point
+// accumulators per lane (lbm_exact_sum.h) and two counts; a cell that does not contribute (blocked or not finite) is
+// added with sign 0, so the lanes of a wave do not diverge.  Per cell the arithmetic is the statistics' (moments_exact,
+// IEEE divide, no contraction).  Every combination is an integer add: the words do not depend on the grid or on
+// scheduling, and no floating-point addition happens on the device.
+constexpr int kProfileColumns = 64;  // profile_columns: columns of a workgroup (one per lane of a wave; its waves share them)
+constexpr int kProfileMinBand = 8;   // ... and the fewest rows of a band: two per wave
+
+// one cell into a lane's accumulators
+__device__ __forceinline__ void profile_cell(const float (&g)[kQ], bool fluid, long long (&acc)[lbm_profile::kProfileSums][lbm_exact::kExactLimbs],
+                                             int& n_fluid, int& n_bad) {
+  float rho, ux, uy;
+  moments_exact(g, rho, ux, uy);
+  const float jx = g[1] + g[5] + g[8] - (g[3] + g[6] + g[7]);
+  const float jy = g[2] + g[5] + g[6] - (g[4] + g[7] + g[8]);
+  const float usq = (ux * ux) + (uy * uy);
+  const unsigned b_rho = __float_as_uint(rho), b_jx = __float_as_uint(jx), b_jy = __float_as_uint(jy);
+  const bool finite = lbm_exact::exact_sum_finite(b_rho) && lbm_exact::exact_sum_finite(b_jx) && lbm_exact::exact_sum_finite(b_jy) &&
+                      lbm_exact::exact_sum_finite(__float_as_uint(usq));
+  const int s = (fluid && finite) ? 1 : 0;
+  lbm_exact::exact_sum_add(acc[0], b_rho, s);
+  lbm_exact::exact_sum_add(acc[1], b_jx, s);
+  lbm_exact::exact_sum_add(acc[2], b_jy, s);
+  lbm_exact::exact_sum_add(acc[3], __float_as_uint(ux), s);  // (usq finite: ux and uy are)
+  lbm_exact::exact_sum_add(acc[4], __float_as_uint(uy), s);
+  n_fluid += s;
+  n_bad += (fluid && !finite) ? 1 : 0;
+}
+
+// Sums along x.  Wave w of workgroup g owns the owned row g * (kBlock / 64) + w; its lanes take the units lane, lane + 64,
+// ... of the row, a unit being V cells: V = 4 where nx % 4 == 0 (one 16-byte load per plane and lane, the mask with one
+// 4-byte load), else V = 1; no unit reaches into the pitch padding (x + V <= nx).  The accumulators are lane-private; one
+// butterfly of shuffles per word totals them across the wave, lane i keeps word i, and lanes 0 .. 46 store the line.
+// Nothing else writes a row line: no atomics.
+template <int V>
+__device__ __forceinline__ void profile_row_lines(const LatticeArgs& a, const float* src, const unsigned char* mask, int rows, long long* lines) {
+  constexpr int L = lbm_exact::kExactLimbs, S = lbm_profile::kProfileSums;
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  if (r >= rows) return;  // uniform over the wave
+  long long acc[S][L];
+  int n_fluid = 0, n_bad = 0;
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int i = 0; i < L; i++) acc[j][i] = 0;
+  const int per_row = a.nx / V;
+#pragma unroll 1
+  for (int u = lane; u < per_row; u += 64) {
+    const int x = u * V;
+    const float* p = src + (long)r * a.row_pitch + x;
+    float f[V][kQ];
+    unsigned blocked;  // byte v: the mask of cell x + v
+    if constexpr (V == 4) {
+#pragma unroll
+      for (int k = 0; k < kQ; k++) {
+        const float4 q = *reinterpret_cast<const float4*>(p + k * a.plane_stride);
+        f[0][k] = q.x;  f[1][k] = q.y;  f[2][k] = q.z;  f[3][k] = q.w;
+      }
+      blocked = *reinterpret_cast<const unsigned*>(mask + (long)r * a.pitch + x);
+    } else {
+#pragma unroll
+      for (int k = 0; k < kQ; k++) f[0][k] = p[k * a.plane_stride];
+      blocked = mask[(long)r * a.pitch + x];
+    }
+#pragma unroll
+    for (int v = 0; v < V; v++) profile_cell(f[v], ((blocked >> (8 * v)) & 0xffu) == 0u, acc, n_fluid, n_bad);
+  }
+  long long mine = 0;
+  auto wave_total = [&](long long t, int word) {
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+    mine = (lane == word) ? t : mine;
+  };
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int i = 0; i < L; i++) wave_total(acc[j][i], j * L + i);
+  wave_total((long long)n_fluid, lbm_profile::kProfileFluidWord);
+  wave_total((long long)n_bad, lbm_profile::kProfileBadWord);
+  if (lane <= lbm_profile::kProfileBadWord) lines[(size_t)r * lbm_profile::kProfileWords + lane] = mine;
+}
+
+// a slab's owned rows into its row lines of the record, [rows][kProfileWords]; grid: ceil(rows / (kBlock / 64))
+template <int V>
+__global__ __launch_bounds__(kBlock) void profile_rows(const LatticeArgs a, int rows, long long* lines) {
+  profile_row_lines<V>(a, a.src, a.mask, rows, lines);
+}
+
+// profile_rows' twin for a batch: workgroup (g, 0, member) on the member's current lattice and mask (members[member];
+// `a` carries the strides all members share), into the member's lines, member_words words apart
+template <int V>
+__global__ __launch_bounds__(kBlock) void profile_rows_batch(const LatticeArgs a, const ResidentMember* members, int rows, long long* lines,
+                                                             long member_words) {
+  const int member = blockIdx.z;
+  profile_row_lines<V>(a, members[member].src, members[member].mask, rows, lines + (size_t)member * member_words);
+}
+
+// Sums along y.  Workgroup (g, b) owns the columns [g * kProfileColumns, + kProfileColumns) of the rows of band b,
+// [b * band_rows, + band_rows): lane l of every wave owns column g * kProfileColumns + l -- consecutive lanes read
+// consecutive addresses of a row -- and wave w walks the band's rows w, w + kBlock / 64, ...  The waves of a workgroup
+// combine through LDS (integer atomics on words that start from zero), then the workgroup's lanes walk its
+// kProfileColumns lines word by word -- consecutive lanes, consecutive addresses -- and send every word that is not 0 by
+// one 64-bit atomicAdd into the column's words, where the bands meet.
+__device__ __forceinline__ void profile_column_lines(const LatticeArgs& a, const float* src, const unsigned char* mask, int rows, int band_rows,
+                                                     long long* lines) {
+  constexpr int L = lbm_exact::kExactLimbs, S = lbm_profile::kProfileSums, W = lbm_profile::kProfileWords;
+  __shared__ unsigned long long sh[kProfileColumns * W];  // [column][word], 24 KiB
+  for (int i = threadIdx.x; i < kProfileColumns * W; i += kBlock) sh[i] = 0ull;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int x0 = (int)blockIdx.x * kProfileColumns, x = x0 + lane;
+  const int r0 = (int)blockIdx.y * band_rows, r1 = (r0 + band_rows < rows) ? r0 + band_rows : rows;
+  long long acc[S][L];
+  int n_fluid = 0, n_bad = 0;
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int i = 0; i < L; i++) acc[j][i] = 0;
+  if (x < a.nx) {
+    for (int r = r0 + wave; r < r1; r += kBlock / 64) {
+      const float* p = src + (long)r * a.row_pitch + x;
+      float f[kQ];
+#pragma unroll
+      for (int k = 0; k < kQ; k++) f[k] = p[k * a.plane_stride];
+      profile_cell(f, mask[(long)r * a.pitch + x] == 0, acc, n_fluid, n_bad);
+    }
+  }
+  __syncthreads();
+  unsigned long long* mine = sh + lane * W;
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int i = 0; i < L; i++)
+      if (acc[j][i] != 0) atomicAdd(mine + j * L + i, (unsigned long long)acc[j][i]);
+  if (n_fluid != 0) atomicAdd(mine + lbm_profile::kProfileFluidWord, (unsigned long long)n_fluid);
+  if (n_bad != 0) atomicAdd(mine + lbm_profile::kProfileBadWord, (unsigned long long)n_bad);
+  __syncthreads();
+  const int columns = (a.nx - x0 < kProfileColumns) ? a.nx - x0 : kProfileColumns;
+  unsigned long long* out = reinterpret_cast<unsigned long long*>(lines) + (size_t)x0 * W;
+  for (int i = threadIdx.x; i < columns * W; i += kBlock) {
+    const unsigned long long t = sh[i];
+    if (t != 0ull) atomicAdd(out + i, t);
+  }
+}
+
+// a slab's owned rows into its column lines of the record, [nx][kProfileWords]; grid: (ceil(nx / kProfileColumns), bands)
+__global__ __launch_bounds__(kBlock) void profile_columns(const LatticeArgs a, int rows, int band_rows, long long* lines) {
+  profile_column_lines(a, a.src, a.mask, rows, band_rows, lines);
+}
+
+// profile_columns' twin for a batch: workgroup (g, b, member), as profile_rows_batch
+__global__ __launch_bounds__(kBlock) void profile_columns_batch(const LatticeArgs a, const ResidentMember* members, int rows, int band_rows,
+                                                                long long* lines, long member_words) {
+  const int member = blockIdx.z;
+  profile_column_lines(a, members[member].src, members[member].mask, rows, band_rows, lines + (size_t)member * member_words);
 }
 
 }  // namespace lbm
