@@ -702,15 +702,8 @@ class Engine:
     def forces(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], float64[n, n_bodies, 2]),
         columns F_x, F_y."""
-        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
-            raise LbmError(f"forces: max_rows must be a non-negative integer or None (got {max_rows!r})")
-        n = ctypes.c_int()
-        _check(self.lib, self.lib.lbm_read_forces(self.handle, 0, None, None, ctypes.byref(n)))  # rows waiting
-        max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
-        rows = np.empty((int(max_rows), getattr(self, "_n_bodies", 0), 2), dtype=np.float64)
-        steps = np.empty(int(max_rows), dtype=np.int32)
-        _check(self.lib, self.lib.lbm_read_forces(self.handle, int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
-        return steps[:n.value].copy(), rows[:n.value].copy()
+        return _drain_rows(self.lib.lbm_read_forces, self.lib, self.handle, "forces", max_rows, (getattr(self, "_n_bodies", 0), 2),
+                           np.float64, np.empty)
 
     def force_links(self) -> np.ndarray:
         """Boundary links of every body of the armed forces, int32[n_bodies] (lbm_forces_links)."""
@@ -729,15 +722,7 @@ class Engine:
 
     def stats(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], STATS_DTYPE[n])."""
-        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
-            raise LbmError(f"stats: max_rows must be a non-negative integer or None (got {max_rows!r})")
-        n = ctypes.c_int()
-        _check(self.lib, self.lib.lbm_read_stats(self.handle, 0, None, None, ctypes.byref(n)))  # rows waiting
-        max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
-        rows = np.zeros(int(max_rows), dtype=STATS_DTYPE)
-        steps = np.empty(int(max_rows), dtype=np.int32)
-        _check(self.lib, self.lib.lbm_read_stats(self.handle, int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
-        return steps[:n.value].copy(), rows[:n.value].copy()
+        return _drain_rows(self.lib.lbm_read_stats, self.lib, self.handle, "stats", max_rows, (), STATS_DTYPE, np.zeros)
 
     # -- velocity residuals (lbm_set_residual / lbm_read_residual) ---------------------------------
     def set_residual(self, every: int, capacity: int = 4096) -> None:
@@ -751,15 +736,7 @@ class Engine:
 
     def residuals(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], RESIDUAL_DTYPE[n])."""
-        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
-            raise LbmError(f"residuals: max_rows must be a non-negative integer or None (got {max_rows!r})")
-        n = ctypes.c_int()
-        _check(self.lib, self.lib.lbm_read_residual(self.handle, 0, None, None, ctypes.byref(n)))  # rows waiting
-        max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
-        rows = np.zeros(int(max_rows), dtype=RESIDUAL_DTYPE)
-        steps = np.empty(int(max_rows), dtype=np.int32)
-        _check(self.lib, self.lib.lbm_read_residual(self.handle, int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
-        return steps[:n.value].copy(), rows[:n.value].copy()
+        return _drain_rows(self.lib.lbm_read_residual, self.lib, self.handle, "residuals", max_rows, (), RESIDUAL_DTYPE, np.zeros)
 
     # -- line profiles (lbm_set_profiles / lbm_read_profiles) ---------------------------------------
     def set_profiles(self, every: int, capacity: int = 16, axes=("rows", "columns")) -> None:
@@ -1040,15 +1017,8 @@ class Batch:
     def forces(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n],
         float64[n, members, n_bodies, 2]), columns F_x, F_y."""
-        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
-            raise LbmError(f"forces: max_rows must be a non-negative integer or None (got {max_rows!r})")
-        n = ctypes.c_int()
-        _check(self.lib, self.lib.lbm_batch_read_forces(self._live(), 0, None, None, ctypes.byref(n)))  # rows waiting
-        max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
-        rows = np.empty((int(max_rows), len(self), getattr(self, "_n_bodies", 0), 2), dtype=np.float64)
-        steps = np.empty(int(max_rows), dtype=np.int32)
-        _check(self.lib, self.lib.lbm_batch_read_forces(self._live(), int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
-        return steps[:n.value].copy(), rows[:n.value].copy()
+        return _drain_rows(self.lib.lbm_batch_read_forces, self.lib, self._live(), "forces", max_rows,
+                           (len(self), getattr(self, "_n_bodies", 0), 2), np.float64, np.empty)
 
     # -- lattice statistics of all members (lbm_batch_set_stats / lbm_batch_read_stats) -----------------------------
     def set_stats(self, every: int, capacity: int = 4096) -> None:
@@ -1059,15 +1029,7 @@ class Batch:
 
     def stats(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], STATS_DTYPE[n, members])."""
-        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
-            raise LbmError(f"stats: max_rows must be a non-negative integer or None (got {max_rows!r})")
-        n = ctypes.c_int()
-        _check(self.lib, self.lib.lbm_batch_read_stats(self._live(), 0, None, None, ctypes.byref(n)))  # rows waiting
-        max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
-        rows = np.zeros((int(max_rows), len(self)), dtype=STATS_DTYPE)
-        steps = np.empty(int(max_rows), dtype=np.int32)
-        _check(self.lib, self.lib.lbm_batch_read_stats(self._live(), int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
-        return steps[:n.value].copy(), rows[:n.value].copy()
+        return _drain_rows(self.lib.lbm_batch_read_stats, self.lib, self._live(), "stats", max_rows, (len(self),), STATS_DTYPE, np.zeros)
 
     # -- velocity residuals of all members (lbm_batch_set_residual / lbm_batch_read_residual) ------------------------
     def set_residual(self, every: int, capacity: int = 4096) -> None:
@@ -1078,15 +1040,8 @@ class Batch:
 
     def residuals(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], RESIDUAL_DTYPE[n, members])."""
-        if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
-            raise LbmError(f"residuals: max_rows must be a non-negative integer or None (got {max_rows!r})")
-        n = ctypes.c_int()
-        _check(self.lib, self.lib.lbm_batch_read_residual(self._live(), 0, None, None, ctypes.byref(n)))  # rows waiting
-        max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
-        rows = np.zeros((int(max_rows), len(self)), dtype=RESIDUAL_DTYPE)
-        steps = np.empty(int(max_rows), dtype=np.int32)
-        _check(self.lib, self.lib.lbm_batch_read_residual(self._live(), int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
-        return steps[:n.value].copy(), rows[:n.value].copy()
+        return _drain_rows(self.lib.lbm_batch_read_residual, self.lib, self._live(), "residuals", max_rows, (len(self),), RESIDUAL_DTYPE,
+                           np.zeros)
 
     # -- line profiles of all members (lbm_batch_set_profiles / lbm_batch_read_profiles) ------------------------------
     def set_profiles(self, every: int, capacity: int = 16, axes=("rows", "columns")) -> None:
@@ -1210,16 +1165,36 @@ def write_av_vels(path: str, av_vels: np.ndarray) -> None:
             fh.write("%d:\t%.12E\n" % (i, float(v)))
 
 
-def _frame_args(every, capacity) -> tuple[int, int]:
-    """Engine.set_frames' argument checks (no device needed)."""
+def _every_capacity(setter, every, capacity, record) -> tuple[int, int]:
+    """What the recorders' argument checks begin with, under the setter's name: `every` and `capacity` are integers in
+    [0, 2^31) and an armed ring holds at least one `record` (None: the caller checks that itself)."""
     for name, v in (("every", every), ("capacity", capacity)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise LbmError(f"set_frames: {name} must be an integer (got {v!r})")
+            raise LbmError(f"{setter}: {name} must be an integer (got {v!r})")
         if not 0 <= int(v) <= 2147483647:
-            raise LbmError(f"set_frames: {name} must lie in [0, 2^31) (got {v})")
-    if every > 0 and capacity < 1:
-        raise LbmError(f"set_frames: capacity {capacity}, at least one frame slot is needed")
+            raise LbmError(f"{setter}: {name} must lie in [0, 2^31) (got {v})")
+    if record is not None and every > 0 and capacity < 1:
+        raise LbmError(f"{setter}: capacity {capacity}, at least one {record} is needed")
     return int(every), int(capacity)
+
+
+def _drain_rows(reader, lib, handle, method, max_rows, row_shape, dtype, alloc) -> tuple[np.ndarray, np.ndarray]:
+    """What the row readers of Engine and Batch (forces, stats, residuals) share: up to max_rows (None: all) waiting rows
+    through `reader`, oldest first, as (steps int32[n], dtype[n, *row_shape]); alloc: np.empty or np.zeros."""
+    if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or max_rows < 0):
+        raise LbmError(f"{method}: max_rows must be a non-negative integer or None (got {max_rows!r})")
+    n = ctypes.c_int()
+    _check(lib, reader(handle, 0, None, None, ctypes.byref(n)))  # rows waiting
+    max_rows = n.value if max_rows is None else min(int(max_rows), n.value)
+    rows = alloc((int(max_rows),) + tuple(row_shape), dtype=dtype)
+    steps = np.empty(int(max_rows), dtype=np.int32)
+    _check(lib, reader(handle, int(max_rows), rows.ctypes.data, steps.ctypes.data, ctypes.byref(n)))
+    return steps[:n.value].copy(), rows[:n.value].copy()
+
+
+def _frame_args(every, capacity) -> tuple[int, int]:
+    """Engine.set_frames' argument checks (no device needed)."""
+    return _every_capacity("set_frames", every, capacity, "frame slot")
 
 
 # the fields of a field frame under final_state()'s keys, in the order of their planes (LBM_FIELD_* of include/lbm_hip.h)
@@ -1229,13 +1204,7 @@ FIELD_BITS = {"u_x": 1, "u_y": 2, "u": 4, "pressure": 8}
 
 def _field_frame_args(every, capacity, fields, window) -> tuple[int, int, int, tuple | None]:
     """Engine.set_field_frames' argument checks (no device needed): (every, capacity, LBM_FIELD_* mask, window or None)."""
-    for name, v in (("every", every), ("capacity", capacity)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise LbmError(f"set_field_frames: {name} must be an integer (got {v!r})")
-        if not 0 <= int(v) <= 2147483647:
-            raise LbmError(f"set_field_frames: {name} must lie in [0, 2^31) (got {v})")
-    if every > 0 and capacity < 1:
-        raise LbmError(f"set_field_frames: capacity {capacity}, at least one frame slot is needed")
+    every, capacity = _every_capacity("set_field_frames", every, capacity, "frame slot")
     if isinstance(fields, str):
         fields = (fields,)
     try:
@@ -1279,11 +1248,7 @@ class _CProbeSample(ctypes.Structure):
 
 def _probe_args(cells, every, capacity) -> tuple[list, int, int]:
     """Engine.set_probes' argument checks (no device needed): ([(x, y), ...], every, capacity)."""
-    for name, v in (("every", every), ("capacity", capacity)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise LbmError(f"set_probes: {name} must be an integer (got {v!r})")
-        if not 0 <= int(v) <= 2147483647:
-            raise LbmError(f"set_probes: {name} must lie in [0, 2^31) (got {v})")
+    every, capacity = _every_capacity("set_probes", every, capacity, None)
     try:
         items = list(cells)
     except TypeError:
@@ -1312,13 +1277,7 @@ LBM_MAX_BODIES = 64
 def _forces_args(every, capacity, bodies, n_bodies, nx, ny) -> tuple[int, int, int, np.ndarray | None]:
     """Engine.set_forces' argument checks (no device needed): (every, capacity, n_bodies, int32 labels [ny*nx] or None).
     Whether a blocked cell's label lies outside 0 .. n_bodies - 1 is the engine's check: it holds the obstacle mask."""
-    for name, v in (("every", every), ("capacity", capacity)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise LbmError(f"set_forces: {name} must be an integer (got {v!r})")
-        if not 0 <= int(v) <= 2147483647:
-            raise LbmError(f"set_forces: {name} must lie in [0, 2^31) (got {v})")
-    if every > 0 and capacity < 1:
-        raise LbmError(f"set_forces: capacity {capacity}, at least one row is needed")
+    every, capacity = _every_capacity("set_forces", every, capacity, "row")
     labels = None
     if bodies is not None:
         try:
@@ -1379,14 +1338,7 @@ STATS_DTYPE = np.dtype([("mass", "<f8"), ("mom_x", "<f8"), ("mom_y", "<f8"), ("s
 
 def _stats_args(every, capacity) -> tuple[int, int]:
     """Engine.set_stats' argument checks (no device needed): (every, capacity)."""
-    for name, v in (("every", every), ("capacity", capacity)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise LbmError(f"set_stats: {name} must be an integer (got {v!r})")
-        if not 0 <= int(v) <= 2147483647:
-            raise LbmError(f"set_stats: {name} must lie in [0, 2^31) (got {v})")
-    if every > 0 and capacity < 1:
-        raise LbmError(f"set_stats: capacity {capacity}, at least one row is needed")
-    return int(every), int(capacity)
+    return _every_capacity("set_stats", every, capacity, "row")
 
 
 def write_stats(path: str, steps, rows) -> None:
@@ -1414,13 +1366,7 @@ _PROFILE_AXES = {"rows": PROFILE_ROWS, "columns": PROFILE_COLUMNS}
 
 def _profile_args(every, capacity, axes) -> tuple[int, int, int]:
     """Engine.set_profiles' argument checks (no device needed): (every, capacity, axes as LBM_PROFILE_* bits)."""
-    for name, v in (("every", every), ("capacity", capacity)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise LbmError(f"set_profiles: {name} must be an integer (got {v!r})")
-        if not 0 <= int(v) <= 2147483647:
-            raise LbmError(f"set_profiles: {name} must lie in [0, 2^31) (got {v})")
-    if every > 0 and capacity < 1:
-        raise LbmError(f"set_profiles: capacity {capacity}, at least one record is needed")
+    every, capacity = _every_capacity("set_profiles", every, capacity, "record")
     if isinstance(axes, bool):
         raise LbmError(f"set_profiles: axes must be 1, 2, 3 or a subset of ('rows', 'columns') (got {axes!r})")
     if isinstance(axes, (int, np.integer)):
@@ -1497,14 +1443,7 @@ RESIDUAL_DTYPE = np.dtype([("sum_du_sq", "<f8"), ("sum_u_sq", "<f8"), ("nonfinit
 
 def _residual_args(every, capacity) -> tuple[int, int]:
     """Engine.set_residual's argument checks (no device needed): (every, capacity)."""
-    for name, v in (("every", every), ("capacity", capacity)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise LbmError(f"set_residual: {name} must be an integer (got {v!r})")
-        if not 0 <= int(v) <= 2147483647:
-            raise LbmError(f"set_residual: {name} must lie in [0, 2^31) (got {v})")
-    if every > 0 and capacity < 1:
-        raise LbmError(f"set_residual: capacity {capacity}, at least one row is needed")
-    return int(every), int(capacity)
+    return _every_capacity("set_residual", every, capacity, "row")
 
 
 def residual_l2(rows) -> np.ndarray:

@@ -8,6 +8,7 @@
 #include "lbm_kernels.hip.h"
 #include "lbm_own.h"
 #include "lbm_plan.h"
+#include "lbm_ring.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -250,15 +251,16 @@ struct Slab {
                                            // lbm_set_mean_order(.., 2): eight, then u_x u_x, u_y u_y, u_x u_y, pressure pressure
   DeviceBuf<float> field_ring;             // lbm_set_field_frames: [slots][F][field_ny][window nx], this slab's rows of the window
   int field_y0 = 0, field_ny = 0;          // ... those rows: slab rows [field_y0, field_y0 + field_ny); none: no ring
+  DeviceBuf<long long> gather_ring;        // the gather kinds (records_behind): [slots][gather_slot_words]: this slab's exact sums
+                                           // (lbm_exact_sum.h) of a record.  lbm_set_forces: [bodies][lbm::kForceWords];
+                                           // lbm_set_stats: [lbm_stats::kStatsWords], the sums, a count and the max key;
+                                           // lbm_set_residual: [lbm_residual::kResidualWords], likewise; lbm_set_profiles:
+                                           // [rows (if ROWS) + nx (if COLUMNS)][lbm_profile::kProfileWords], this slab's row
+                                           // lines, then its rows' share of every column line
   DeviceBuf<unsigned> force_links;         // lbm_set_forces: the boundary links of the owned blocked cells, by body, cell, k ...
   DeviceBuf<unsigned> force_starts;        // ... [bodies + 1]: where each body's links start
-  DeviceBuf<long long> force_ring;         // ... [slots][bodies][lbm::kForceWords]: this slab's exact sums (lbm_exact_sum.h)
   int force_groups = 0;                    // workgroups per body of force_gather (0: the slab has no links)
-  DeviceBuf<long long> stats_ring;         // lbm_set_stats: [slots][lbm_stats::kStatsWords]: this slab's exact sums, count and max key
-  DeviceBuf<long long> residual_ring;      // lbm_set_residual: [slots][lbm_residual::kResidualWords]: likewise
-  DeviceBuf<float> residual_planes;        // ... [2][rows][nx]: the remembered u_x and u_y of this slab's owned cells
-  DeviceBuf<long long> profile_ring;       // lbm_set_profiles: [slots][rows (if ROWS) + nx (if COLUMNS)][lbm_profile::kProfileWords]: this
-                                           // slab's row lines, then its rows' share of every column line
+  DeviceBuf<float> residual_planes;        // lbm_set_residual: [2][rows][nx]: the remembered u_x and u_y of this slab's owned cells
   // freshest-available mode (LBM_HALO_FRESHEST), allocated at its first use in this order: whole once ev_fresh[1] exists
   DeviceBuf<float> fresh_stage;          // [parity][side: 0 south halo, 1 north halo][row_pitch]: this pass's rows, if they make it
   DeviceBuf<unsigned> fresh_arrived;     // [parity][side]: id (global step + 1) of the step whose row the staging holds
@@ -412,6 +414,8 @@ struct GraphBuilder {
 // Velocity residuals (lbm_set_residual) likewise, by residual_gather, which also keeps a field between the samples: the
 // velocities of the last sample (at first: of arming), which every sample compares with and replaces.
 // Line profiles (lbm_set_profiles) likewise, by profile_rows and profile_columns: a record of per-row and per-column sums.
+// These four gather kinds (records_behind) share one ring of int64 words per slab, Slab::gather_ring, whose slot holds
+// gather_slot_words words; a batch arms them on itself (lbm_batch::rec) with one ring for all members.
 enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean,
        kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecResidual = 7, kRecProfiles = 8, kRecKinds = 9 };
 // the kinds recorded by a gather launch behind the sub-call that ends at a sample step, whatever kernels advance the lattice
@@ -523,24 +527,20 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
   DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
   int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
-                                    // (a batch records one kind, so at most one count is non-zero; the forces, the
-                                    // statistics, the residuals and the profiles are armed on the batch, lbm_batch_set_forces /
-                                    // lbm_batch_set_stats / lbm_batch_set_residual / lbm_batch_set_profiles, and count as one)
-  // obstacle forces, lattice statistics, velocity residuals or line profiles of all members (lbm_batch_set_forces,
-  // lbm_batch_set_stats, lbm_batch_set_residual, lbm_batch_set_profiles): the members' own recorders stay off, the batch
-  // keeps the one recorder and the one ring; every lbm_batch_run runs as the sub-calls that end at its sample steps
-  Recorder rec;                                  // kind kRecForces, kRecStats, kRecResidual or kRecProfiles while armed
-  DeviceBuf<long long> profile_ring;             // lbm_batch_set_profiles: device: [slots][members][lines][lbm_profile::kProfileWords]
-  DeviceBuf<long long> stats_ring;               // lbm_batch_set_stats: device: [slots][members][lbm_stats::kStatsWords]
-  DeviceBuf<long long> residual_ring;            // lbm_batch_set_residual: device: [slots][members][lbm_residual::kResidualWords]
-  DeviceBuf<float> residual_planes;              // ... device: [members][2][rows][nx]: the members' remembered u_x and u_y
-  int force_bodies = 0;                          // bodies of every member
+                                    // (a batch records one kind, so at most one count is non-zero; a gather kind is armed
+                                    // on the batch, by its lbm_batch_set_* of kBatchKinds, and counts as one)
+  // the gather kinds (records_behind) of all members: the members' own recorders stay off, the batch keeps the one
+  // recorder and the one ring (rearm_batch_recorder, drain_batch_recorder, release_batch_recorder); every lbm_batch_run
+  // runs as the sub-calls that end at its sample steps
+  Recorder rec;                                  // one of kBatchKinds while armed
+  DeviceBuf<long long> gather_ring;              // device: [slots][members][a member's gather_slot_words]
+  DeviceBuf<float> residual_planes;              // lbm_batch_set_residual: device: [members][2][rows][nx]: the members' remembered u_x and u_y
+  int force_bodies = 0;                          // lbm_batch_set_forces: bodies of every member
   int force_groups = 0;                          // workgroups per (member, body) of force_gather_batch (0: no member has a link)
   std::vector<int> force_link_counts;            // [members][bodies]
   std::vector<DeviceBuf<unsigned>> force_links;  // [members]: the member's boundary links, by body, cell, k ...
   std::vector<DeviceBuf<unsigned>> force_starts; // ... and [bodies + 1]: where each body's links start
   DeviceBuf<lbm::ForceMember> force_lists;       // device: [members], those pointers
-  DeviceBuf<long long> force_ring;               // device: [slots][members][bodies][lbm::kForceWords]
   // steady-state runs (lbm_batch_run_until), allocated by the first such call; steady_state last: the set is whole once it exists
   DeviceBuf<lbm::SteadyMember> steady_members; // device: [members]
   DeviceBuf<lbm::SteadyBatch> steady_batch;    // device
@@ -559,17 +559,18 @@ struct lbm_batch {
 };
 
 // The kinds armed on a batch as a whole (lbm_batch::rec): what differs between them in the messages and in lbm_batch_run,
-// where take() records the row of all members behind a sub-call that ends at a sample step
-static int take_batch_forces(lbm_batch* bt);
-static int take_batch_stats(lbm_batch* bt);
-static int take_batch_residual(lbm_batch* bt);
-static int take_batch_profiles(lbm_batch* bt);
+// where take() launches the gather of all members into the record's zeroed slot behind a sub-call that ends at a sample
+// step.  The other words of the shared messages (noun, record) are the kind's of kRecorderKinds.
+static int take_batch_forces(lbm_batch* bt, long long* row);
+static int take_batch_stats(lbm_batch* bt, long long* row);
+static int take_batch_residual(lbm_batch* bt, long long* row);
+static int take_batch_profiles(lbm_batch* bt, long long* record);
 struct BatchKind {
   int kind;
   const char* setter;
   const char* reader;
   const char* disarm;
-  int (*take)(lbm_batch*);
+  int (*take)(lbm_batch*, long long*);
 };
 static const BatchKind kBatchKinds[] = {
     {kRecForces, "lbm_batch_set_forces", "lbm_batch_read_forces", "lbm_batch_set_forces(batch, 0, NULL, 0, 0)", take_batch_forces},
@@ -1657,8 +1658,53 @@ void launch_profiles(const lbm_ctx* c, const Slab& sl, long long* lines) {
   }
 }
 
+// int64 words a gather kind records per slab (or batch member) and sample: of `bodies` bodies (forces), of `rows` rows of
+// nx cells along `axes` (profiles).  The one place a slot's size is computed: the setters call it with what they are about
+// to arm, everything else through gather_slot_words with what is armed.
+size_t gather_words(int kind, size_t bodies = 0, int rows = 0, int nx = 0, int axes = 0) {
+  switch (kind) {
+    case kRecForces: return bodies * (size_t)lbm::kForceWords;
+    case kRecStats: return lbm_stats::kStatsWords;
+    case kRecResidual: return lbm_residual::kResidualWords;
+    case kRecProfiles: return lbm_profile::profile_slab_lines(rows, nx, axes) * lbm_profile::kProfileWords;
+    default: return 0;
+  }
+}
+// words of one slot of a slab's gather_ring: this slab's share of a record
+size_t gather_slot_words(const lbm_ctx* c, const Slab& sl) {
+  return gather_words(c->rec.kind, c->force_link_counts.size(), sl.rows, c->p.nx, c->rec.axes);
+}
+// ... and of a batch's: that of slab 0 for every member, one after the other
+size_t gather_slot_words(const lbm_batch* bt) {
+  const lbm_ctx* c0 = bt->members[0];
+  return bt->members.size() * gather_words(bt->rec.kind, (size_t)bt->force_bodies, c0->slab[0].rows, c0->p.nx, bt->rec.axes);
+}
+
+// the slot of the next record of a gather ring, zeroed on `stream` (the gather kernels add into it): nullptr where that failed
+long long* zeroed_slot(long long* ring, size_t slot_words, const Recorder& r, hipStream_t stream) {
+  long long* slot = ring + (size_t)(r.written % r.slots) * slot_words;
+  HIP_TRY(nullptr, hipMemsetAsync(slot, 0, slot_words * sizeof(long long), stream));
+  return slot;
+}
+
+// the n oldest waiting records of a ring of slot_words elements per slot into dst, record after record, over `stream` (of
+// the current device); they are on the host when this returns
+template <class T, class U>
+int fetch_ring(const T* ring, size_t slot_words, const Recorder& r, int n, hipStream_t stream, U* dst) {
+  static_assert(sizeof(T) == sizeof(U), "the host's element is the device's");
+  const lbm_ring::Runs runs = lbm_ring::oldest_runs(r.read, r.slots, n);
+  for (int j = 0; j < runs.n; j++) {
+    const lbm_ring::Run& run = runs.run[j];
+    HIP_TRY(LBM_FAILURE, hipMemcpyAsync(dst + (size_t)run.at * slot_words, ring + run.first * slot_words,
+                                        (size_t)run.count * slot_words * sizeof(T), hipMemcpyDeviceToHost, stream));
+  }
+  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(stream));
+  return LBM_SUCCESS;
+}
+
 // the record of the current (stored) lattice into the next slot, on every slab's compute stream: the frame of its rows,
-// or the gathered samples of the probes in its rows; or, for the mean fields, the sample of its rows added to their sums
+// or the gathered samples of the probes in its rows; or, for the mean fields, the sample of its rows added to their sums;
+// or, for a gather kind, the slab's share of the record added into its zeroed slot
 int take_record(lbm_ctx* c) {
   const size_t slot = kRecorderKinds[c->rec.kind].slotted ? (size_t)(c->rec.written % c->rec.slots) : 0;
   const size_t n_probes = c->probe_cells.size();
@@ -1666,6 +1712,9 @@ int take_record(lbm_ctx* c) {
         Slab& sl = c->slab[s];
         HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
         const long n = (long)sl.rows * c->p.nx;
+        long long* words = nullptr;
+        if (records_behind(c->rec.kind) && !(words = zeroed_slot(sl.gather_ring, gather_slot_words(c, sl), c->rec, sl.compute)))
+          return LBM_FAILURE;
         if (c->rec.kind == kRecFrames)
           hipLaunchKernelGGL(lbm::frame_umag, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              sl.frames + slot * n);
@@ -1677,30 +1726,17 @@ int take_record(lbm_ctx* c) {
                                c->rec.fields, w.x0, sl.field_y0, w.nx, sl.field_ny,
                                sl.field_ring + slot * (size_t)__builtin_popcount((unsigned)c->rec.fields) * (size_t)cells);
         } else if (c->rec.kind == kRecForces) {
-          // the row starts from zeros (force_gather adds into it); a slab without links records them
-          const size_t words = c->force_link_counts.size() * (size_t)lbm::kForceWords;
-          long long* row = sl.force_ring + slot * words;
-          HIP_TRY(LBM_FAILURE, hipMemsetAsync(row, 0, words * sizeof(long long), sl.compute));
+          // a slab without links records the zeros
           if (sl.force_groups > 0)
             hipLaunchKernelGGL(lbm::force_gather, dim3(sl.force_groups, (unsigned)c->force_link_counts.size()), dim3(lbm::kBlock), 0,
-                               sl.compute, lattice_args(c, sl), (const unsigned*)sl.force_links, (const unsigned*)sl.force_starts, row);
-        } else if (c->rec.kind == kRecStats) {
-          // the slab's words start from zeros (stats_gather adds into them)
-          long long* words = sl.stats_ring + slot * (size_t)lbm_stats::kStatsWords;
-          HIP_TRY(LBM_FAILURE, hipMemsetAsync(words, 0, lbm_stats::kStatsWords * sizeof(long long), sl.compute));
+                               sl.compute, lattice_args(c, sl), (const unsigned*)sl.force_links, (const unsigned*)sl.force_starts, words);
+        } else if (c->rec.kind == kRecStats)
           launch_stats_gather(c, sl, words);
-        } else if (c->rec.kind == kRecResidual) {
-          // likewise; the gather also replaces the slab's remembered field by this lattice's
-          long long* words = sl.residual_ring + slot * (size_t)lbm_residual::kResidualWords;
-          HIP_TRY(LBM_FAILURE, hipMemsetAsync(words, 0, lbm_residual::kResidualWords * sizeof(long long), sl.compute));
-          launch_residual_gather(c, sl, words, false);
-        } else if (c->rec.kind == kRecProfiles) {
-          // the slab's lines start from zeros (profile_columns adds into them, profile_rows leaves a line's spare word)
-          const size_t words = lbm_profile::profile_slab_lines(sl.rows, c->p.nx, c->rec.axes) * lbm_profile::kProfileWords;
-          long long* lines = sl.profile_ring + slot * words;
-          HIP_TRY(LBM_FAILURE, hipMemsetAsync(lines, 0, words * sizeof(long long), sl.compute));
-          launch_profiles(c, sl, lines);
-        } else if (c->rec.kind == kRecMean)
+        else if (c->rec.kind == kRecResidual)
+          launch_residual_gather(c, sl, words, false);  // also replaces the slab's remembered field by this lattice's
+        else if (c->rec.kind == kRecProfiles)
+          launch_profiles(c, sl, words);  // (profile_rows leaves a line's spare word as zeroed)
+        else if (c->rec.kind == kRecMean)
           hipLaunchKernelGGL(lbm::mean_accumulate, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              c->p.density, sl.mean_sums, n, c->rec.order);
         else if (sl.probe_count > 0)
@@ -2392,7 +2428,7 @@ lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, con
   return c;
 }
 
-// ---- the recorder: what lbm_set_frames / lbm_set_probes and their readers share ----------------------------------
+// ---- the recorder of a context: what the setters and the readers of kRecorderKinds share --------------------------
 // a batch member's entry of the table the batched launches of one kind read; the table is allocated, all zero, when the
 // first member arms that kind
 template <class Entry>
@@ -2430,14 +2466,11 @@ void release_recorder(lbm_ctx* c) {
     sl.mean_sums.reset();
     sl.field_ring.reset();
     sl.field_y0 = sl.field_ny = 0;
+    sl.gather_ring.reset();
     sl.force_links.reset();
     sl.force_starts.reset();
-    sl.force_ring.reset();
     sl.force_groups = 0;
-    sl.stats_ring.reset();
-    sl.residual_ring.reset();
     sl.residual_planes.reset();
-    sl.profile_ring.reset();
     sl.probe_count = 0;
   }
   c->probe_cells.clear();
@@ -2445,9 +2478,9 @@ void release_recorder(lbm_ctx* c) {
   c->rec = Recorder{};
 }
 
-// What lbm_set_frames, lbm_set_probes and set_mean_order (behind lbm_set_mean and lbm_set_mean_order) share behind
-// their own argument checks.  Arming (every > 0) is refused, with nothing touched, where this kind cannot record.  Then the launches in flight are awaited and a recorder of this kind is
-// disarmed; to arm, allocate() provides the kind's buffers of every slab (and says what it could not) before the
+// What the setters of every kind of kRecorderKinds (for the mean fields: set_mean_order, behind lbm_set_mean and
+// lbm_set_mean_order) share behind their own argument checks.  Arming (every > 0) is refused, with nothing touched,
+// where this kind cannot record.  Then the launches in flight are awaited and a recorder of this kind is disarmed; to arm, allocate() provides the kind's buffers of every slab (and says what it could not) before the
 // recorder's fields, the member's batch entry and the batch's count of armed members are set.
 template <class Allocate>
 int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate allocate, const char* who = nullptr) {
@@ -2512,22 +2545,19 @@ int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate alloc
   return LBM_SUCCESS;
 }
 
-// What lbm_read_frames and lbm_read_probes share: the work in flight is awaited; without outputs the call tells how many
-// records wait; else copy(n) fetches the n oldest (at most max_records) before their steps are told and they are retired.
+// What the readers of the slotted kinds share, a context's (drain_recorder) and a batch's (drain_batch_recorder), once
+// the work in flight has been awaited: without outputs the call tells how many records of `kind` wait in r; else copy(n)
+// fetches the n oldest (at most max_records) before their steps are told and they are retired.
 template <class Copy>
-int drain_recorder(lbm_ctx* c, int kind, int max_records, bool has_out, int* steps, int* n_read, Copy copy) {
+int drain_ring(Recorder& r, int kind, const char* reader, int max_records, bool has_out, int* steps, int* n_read, Copy copy) {
   const RecorderKind& k = kRecorderKinds[kind];
-  if (!c || !n_read) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", k.reader);
-  *n_read = 0;
-  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
-  Recorder& r = c->rec;
   const long long waiting = (r.kind == kind) ? r.written - r.read : 0;
   if (!has_out && !steps) {
     *n_read = (int)waiting;
     return LBM_SUCCESS;
   }
-  if (!has_out) LBM_FAIL(LBM_FAILURE, "%s: NULL %s output", k.reader, k.record);
-  if (max_records < 0) LBM_FAIL(LBM_FAILURE, "%s: negative max_%ss %d", k.reader, k.record, max_records);
+  if (!has_out) LBM_FAIL(LBM_FAILURE, "%s: NULL %s output", reader, k.record);
+  if (max_records < 0) LBM_FAIL(LBM_FAILURE, "%s: negative max_%ss %d", reader, k.record, max_records);
   const int n = (waiting < max_records) ? (int)waiting : max_records;
   if (n > 0 && copy(n) != LBM_SUCCESS) return LBM_FAILURE;
   if (steps)
@@ -2535,6 +2565,150 @@ int drain_recorder(lbm_ctx* c, int kind, int max_records, bool has_out, int* ste
   r.read += n;
   *n_read = n;
   return LBM_SUCCESS;
+}
+template <class Copy>
+int drain_recorder(lbm_ctx* c, int kind, int max_records, bool has_out, int* steps, int* n_read, Copy copy) {
+  const char* const reader = kRecorderKinds[kind].reader;
+  if (!c || !n_read) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", reader);
+  *n_read = 0;
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
+  return drain_ring(c->rec, kind, reader, max_records, has_out, steps, n_read, copy);
+}
+
+// every slab's share of the n oldest records of a gather kind, gathered as records[record][slab's share]; *record_words:
+// the words of one record, all shares.  The kind's words-to-row function merges the shares of a record.
+int fetch_gather_records(lbm_ctx* c, int n, std::vector<long long>& records, size_t* record_words) {
+  size_t share_at[kMaxSlabs + 1] = {0};  // where slab s's words start in a record's
+  for (int s = 0; s < c->n_slabs; s++) share_at[s + 1] = share_at[s] + gather_slot_words(c, c->slab[s]);
+  const size_t all = *record_words = share_at[c->n_slabs];
+  records.resize((size_t)n * all);
+  std::vector<long long> stage;
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    const size_t words = share_at[s + 1] - share_at[s];
+    stage.resize((size_t)n * words);
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    if (fetch_ring(sl.gather_ring.get(), words, c->rec, n, sl.compute, stage.data()) != LBM_SUCCESS) return LBM_FAILURE;
+    for (size_t i = 0; i < (size_t)n; i++) memcpy(&records[i * all + share_at[s]], &stage[i * words], words * sizeof(long long));
+  }
+  return LBM_SUCCESS;
+}
+
+// ---- the recorder of a batch: what the lbm_batch_set_* and lbm_batch_read_* of kBatchKinds share ---------------------
+// what the batched kernels read of every member, [parity of cur][members]
+std::vector<lbm::ResidentMember> member_table(const lbm_batch* bt) {
+  const size_t n_members = bt->members.size();
+  std::vector<lbm::ResidentMember> h(2 * n_members);
+  for (int par = 0; par < 2; par++)
+    for (size_t i = 0; i < n_members; i++) {
+      const lbm_ctx* c = bt->members[i];
+      const Slab& sl = c->slab[0];
+      lbm::ResidentMember& m = h[(size_t)par * n_members + i];
+      m.src = sl.lat[par];
+      m.dst = sl.lat[par ^ 1];
+      m.mask = sl.mask;
+      m.gran = sl.res_gran;
+      m.partials = sl.res_part;
+      m.tot_u = sl.tot_u;
+      m.omega = c->p.omega;
+      set_accel_weights(m, c->p);  // as run_steps / run_resident
+    }
+  return h;
+}
+// ... on the device (the current one); false, with no table left behind, where that fails
+bool upload_member_table(lbm_batch* bt) {
+  const std::vector<lbm::ResidentMember> h = member_table(bt);
+  if (bt->table.alloc(h.size()) == hipSuccess && hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) == hipSuccess)
+    return true;
+  (void)hipGetLastError();
+  bt->table.reset();
+  return false;
+}
+
+// frees the batch's record buffers, whatever gather kind they served, and leaves its recorder off (release_recorder does
+// so for a context)
+void release_batch_recorder(lbm_batch* bt) {
+  (void)hipSetDevice(bt->members[0]->slab[0].device);
+  bt->gather_ring.reset();
+  bt->residual_planes.reset();
+  bt->force_lists.reset();
+  bt->force_links.clear();
+  bt->force_starts.clear();
+  bt->force_link_counts.clear();
+  bt->force_bodies = bt->force_groups = 0;
+  if (bt->rec.kind != kRecNone) bt->armed[bt->rec.kind] = 0;
+  bt->rec = Recorder{};
+}
+
+// the batched gather kernels read the members' lattices from the member table: a batch of a shape the resident kernel
+// does not take has none until a kind is first armed
+int ensure_member_table(lbm_batch* bt, const char* who, const char* noun) {
+  if (!bt->table && !upload_member_table(bt)) LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the member table; %s stay off", who, noun);
+  return LBM_SUCCESS;
+}
+
+// a batch records one kind: no kind is armed on the batch while a member has its own recorder armed
+int batch_members_free(const lbm_batch* bt, const char* who) {
+  for (size_t i = 0; i < bt->members.size(); i++) {
+    const Recorder& r = bt->members[i]->rec;
+    if (r.kind != kRecNone)
+      LBM_FAIL(LBM_FAILURE, "%s: member %d has %s armed (%s); a batch records one kind -- disarm them with %s first", who, (int)i,
+               kRecorderKinds[r.kind].name, kRecorderKinds[r.kind].setter, kRecorderKinds[r.kind].disarm);
+  }
+  return LBM_SUCCESS;
+}
+
+// What the four lbm_batch_set_* share (rearm_recorder does so for a context).  Disarming while the batch's one recorder
+// holds another kind is a silent no-op, arming then is refused.  To arm, check() makes the kind's own checks of its
+// arguments; like every check here it runs, touching nothing of the recorder, before the launches in flight are awaited
+// and a recorder of this kind is released.  Then allocate() provides the kind's buffers (and says what it could not) and
+// sets the recorder's fields that only this kind has, before the common ones are set.
+template <class Check, class Allocate>
+int rearm_batch_recorder(lbm_batch* bt, int kind, int every, int capacity, Check check, Allocate allocate) {
+  const BatchKind& k = *batch_kind(kind);
+  if (!bt) LBM_FAIL(LBM_FAILURE, "%s: null batch", k.setter);
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "%s: negative interval %d", k.setter, every);
+  if (bt->rec.kind != kRecNone && bt->rec.kind != kind) {
+    if (every == 0) return LBM_SUCCESS;
+    const BatchKind* o = batch_kind(bt->rec.kind);
+    LBM_FAIL(LBM_FAILURE, "%s: this batch has %s armed (%s); a batch records one kind -- disarm them with %s first", k.setter,
+             kRecorderKinds[bt->rec.kind].name, o->setter, o->disarm);
+  }
+  if (every > 0 && (check() != LBM_SUCCESS || batch_members_free(bt, k.setter) != LBM_SUCCESS)) return LBM_FAILURE;
+  // the buffers may still be written by launches in flight
+  HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
+  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
+  release_batch_recorder(bt);
+  if (every == 0) return LBM_SUCCESS;
+  if (ensure_member_table(bt, k.setter, kRecorderKinds[kind].noun) != LBM_SUCCESS || allocate() != LBM_SUCCESS) {
+    (void)hipGetLastError();  // a failed allocation must not surface at the next launch
+    release_batch_recorder(bt);
+    return LBM_FAILURE;
+  }
+  bt->rec.kind = kind;
+  bt->rec.every = every;
+  bt->rec.slots = capacity;
+  bt->rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
+  bt->armed[kind] = 1;
+  return LBM_SUCCESS;
+}
+
+// What the four lbm_batch_read_* share (drain_recorder does so for a context): convert(n, words) turns the words of the n
+// oldest records, [record][member][a member's words], into the caller's rows.
+template <class Convert>
+int drain_batch_recorder(lbm_batch* bt, int kind, int max_records, bool has_out, int* steps, int* n_read, Convert convert) {
+  const char* const reader = batch_kind(kind)->reader;
+  if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", reader);
+  *n_read = 0;
+  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
+  return drain_ring(bt->rec, kind, reader, max_records, has_out, steps, n_read, [&](int n) -> int {
+    const size_t words = gather_slot_words(bt);
+    std::vector<long long> stage((size_t)n * words);
+    HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
+    if (fetch_ring(bt->gather_ring.get(), words, bt->rec, n, bt->stream, stage.data()) != LBM_SUCCESS) return LBM_FAILURE;
+    convert(n, stage.data());
+    return LBM_SUCCESS;
+  });
 }
 
 // ---- obstacle forces: what lbm_set_forces (per slab) and lbm_batch_set_forces (per member) share ------------------
@@ -2948,23 +3122,14 @@ int lbm_set_probes(lbm_ctx* c, int n_probes, const lbm_probe* cells, int every, 
 int lbm_read_probes(lbm_ctx* c, int max_samples, lbm_probe_sample* out, int* steps, int* n_read) {
   return drain_recorder(c, kRecProbes, max_samples, out != nullptr, steps, n_read, [&](int n) -> int {
     const size_t np = c->probe_cells.size();
-    const size_t slots = (size_t)c->rec.slots;
-    static_assert(sizeof(lbm_probe_sample) == sizeof(lbm::probe_vec), "a sample is one 16-byte store");
-    // the rows wait in at most two runs of the ring; one slab: straight into out, several: each slab's columns of a staged copy
+    // (a sample is one 16-byte store.)  One slab: straight into out, several: each slab's columns of a staged copy
     std::vector<lbm_probe_sample> stage(c->n_slabs > 1 ? (size_t)n * np : 0);
     for (int s = 0; s < c->n_slabs; s++) {
       Slab& sl = c->slab[s];
       if (sl.probe_count == 0 && c->n_slabs > 1) continue;
       lbm_probe_sample* dst = c->n_slabs > 1 ? stage.data() : out;
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      for (int i = 0; i < n;) {
-        const size_t slot = (size_t)((c->rec.read + i) % c->rec.slots);
-        const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
-        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(dst + (size_t)i * np, sl.probe_ring + slot * np, (size_t)run * np * sizeof(lbm_probe_sample),
-                                            hipMemcpyDeviceToHost, sl.compute));
-        i += run;
-      }
-      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+      if (fetch_ring(sl.probe_ring.get(), np, c->rec, n, sl.compute, dst) != LBM_SUCCESS) return LBM_FAILURE;
       if (c->n_slabs > 1)
         for (size_t p = 0; p < np; p++) {
           const int y = c->probe_cells[p].y;
@@ -3091,7 +3256,7 @@ int lbm_set_forces(lbm_ctx* c, int n_bodies, const int* body_of_cell, int every,
     if (n_bodies < 1 || n_bodies > LBM_MAX_BODIES)
       LBM_FAIL(LBM_FAILURE, "lbm_set_forces: %d bodies, between 1 and LBM_MAX_BODIES = %d are possible", n_bodies, LBM_MAX_BODIES);
     if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_forces: capacity %d, at least one row is needed", capacity);
-    if ((long long)capacity * n_bodies * lbm::kForceWords * (long long)sizeof(long long) >= (1LL << 31))
+    if ((long long)capacity * (long long)(gather_words(kRecForces, (size_t)n_bodies) * sizeof(long long)) >= (1LL << 31))
       LBM_FAIL(LBM_FAILURE, "lbm_set_forces: a ring of %d rows of %d bodies is 2 GiB or more (%d bytes per body and row)", capacity, n_bodies,
                lbm::kForceWords * (int)sizeof(long long));
     if (c->ranked || c->world > 1)
@@ -3115,11 +3280,11 @@ int lbm_set_forces(lbm_ctx* c, int n_bodies, const int* body_of_cell, int every,
   }
   return rearm_recorder(c, kRecForces, every, capacity, [&]() -> int {
     c->force_link_counts.assign((size_t)n_bodies, 0);
-    const size_t ring_bytes = (size_t)capacity * (size_t)n_bodies * lbm::kForceWords * sizeof(long long);
+    const size_t ring_bytes = (size_t)capacity * gather_words(kRecForces, (size_t)n_bodies) * sizeof(long long);
     for (int s = 0; s < c->n_slabs; s++) {
       Slab& sl = c->slab[s];
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      if (sl.force_ring.alloc_bytes(ring_bytes) != hipSuccess)
+      if (sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
         LBM_FAIL(LBM_FAILURE, "lbm_set_forces: cannot allocate %d rows of %d bodies (%.1f MiB per slab); forces stay off", capacity, n_bodies,
                  (double)ring_bytes / 1048576.0);
       std::vector<unsigned> starts;
@@ -3140,22 +3305,14 @@ int lbm_set_forces(lbm_ctx* c, int n_bodies, const int* body_of_cell, int every,
 
 int lbm_read_forces(lbm_ctx* c, int max_rows, double* out, int* steps, int* n_read) {
   return drain_recorder(c, kRecForces, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
-    const size_t bodies = c->force_link_counts.size(), words = bodies * (size_t)lbm::kForceWords;
-    const size_t slots = (size_t)c->rec.slots;
-    // every slab's words of the n rows (they wait in at most two runs of its ring), added word by word -- integers: the
-    // order of the slabs does not matter -- then each body's two sums rounded once and doubled (-2 c_k f)
+    const size_t bodies = c->force_link_counts.size(), words = gather_slot_words(c, c->slab[0]);
+    // every slab's words of the n rows, added word by word -- integers: the order of the slabs does not matter -- then
+    // each body's two sums rounded once and doubled (-2 c_k f)
     std::vector<long long> sum((size_t)n * words, 0), stage((size_t)n * words);
     for (int s = 0; s < c->n_slabs; s++) {
       Slab& sl = c->slab[s];
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      for (int i = 0; i < n;) {
-        const size_t slot = (size_t)((c->rec.read + i) % c->rec.slots);
-        const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
-        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, sl.force_ring + slot * words, (size_t)run * words * sizeof(long long),
-                                            hipMemcpyDeviceToHost, sl.compute));
-        i += run;
-      }
-      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+      if (fetch_ring(sl.gather_ring.get(), words, c->rec, n, sl.compute, stage.data()) != LBM_SUCCESS) return LBM_FAILURE;
       for (size_t j = 0; j < sum.size(); j++) sum[j] += stage[j];
     }
     round_forces(sum.data(), (size_t)n * bodies, out);
@@ -3173,7 +3330,7 @@ int lbm_forces_links(lbm_ctx* c, int* links_per_body) {
 int lbm_set_stats(lbm_ctx* c, int every, int capacity) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_stats: null context");
   if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_stats: negative interval %d", every);
-  constexpr long long kRowBytes = lbm_stats::kStatsWords * (long long)sizeof(long long);
+  const long long kRowBytes = (long long)(gather_words(kRecStats) * sizeof(long long));
   if (every > 0) {
     if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_stats: capacity %d, at least one row is needed", capacity);
     if ((long long)capacity * kRowBytes >= (1LL << 31))
@@ -3189,7 +3346,7 @@ int lbm_set_stats(lbm_ctx* c, int every, int capacity) {
     for (int s = 0; s < c->n_slabs; s++) {
       Slab& sl = c->slab[s];
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      if (sl.stats_ring.alloc_bytes(ring_bytes) != hipSuccess)
+      if (sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
         LBM_FAIL(LBM_FAILURE, "lbm_set_stats: cannot allocate %d rows (%.1f MiB per slab); statistics stay off", capacity,
                  (double)ring_bytes / 1048576.0);
     }
@@ -3199,25 +3356,11 @@ int lbm_set_stats(lbm_ctx* c, int every, int capacity) {
 
 int lbm_read_stats(lbm_ctx* c, int max_rows, lbm_stats_row* out, int* steps, int* n_read) {
   return drain_recorder(c, kRecStats, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
-    constexpr size_t words = lbm_stats::kStatsWords;
-    const size_t slots = (size_t)c->rec.slots, n_slabs = (size_t)c->n_slabs;
-    // every slab's words of the n rows (they wait in at most two runs of its ring), gathered as rows[row][slab][words];
-    // the slabs of a row are merged and rounded by stats_row_from_words
-    std::vector<long long> rows((size_t)n * n_slabs * words), stage((size_t)n * words);
-    for (size_t s = 0; s < n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      for (int i = 0; i < n;) {
-        const size_t slot = (size_t)((c->rec.read + i) % c->rec.slots);
-        const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
-        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, sl.stats_ring + slot * words, (size_t)run * words * sizeof(long long),
-                                            hipMemcpyDeviceToHost, sl.compute));
-        i += run;
-      }
-      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
-      for (size_t i = 0; i < (size_t)n; i++) memcpy(&rows[(i * n_slabs + s) * words], &stage[i * words], words * sizeof(long long));
-    }
-    for (int i = 0; i < n; i++) out[i] = lbm_stats::stats_row_from_words(rows.data() + (size_t)i * n_slabs * words, (int)n_slabs, c->p.nx);
+    // rows[row][slab][words]: the slabs of a row are merged and rounded by stats_row_from_words
+    std::vector<long long> rows;
+    size_t row_words;
+    if (fetch_gather_records(c, n, rows, &row_words) != LBM_SUCCESS) return LBM_FAILURE;
+    for (int i = 0; i < n; i++) out[i] = lbm_stats::stats_row_from_words(rows.data() + (size_t)i * row_words, c->n_slabs, c->p.nx);
     return LBM_SUCCESS;
   });
 }
@@ -3230,7 +3373,7 @@ static int residual_span(const Recorder& r, long long ord) {
 int lbm_set_residual(lbm_ctx* c, int every, int capacity) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_residual: null context");
   if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_residual: negative interval %d", every);
-  constexpr long long kRowBytes = lbm_residual::kResidualWords * (long long)sizeof(long long);
+  const long long kRowBytes = (long long)(gather_words(kRecResidual) * sizeof(long long));
   if (every > 0) {
     if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_residual: capacity %d, at least one row is needed", capacity);
     if ((long long)capacity * kRowBytes >= (1LL << 31))
@@ -3250,7 +3393,7 @@ int lbm_set_residual(lbm_ctx* c, int every, int capacity) {
       if (sl.residual_planes.alloc(2 * cells) != hipSuccess)
         LBM_FAIL(LBM_FAILURE, "lbm_set_residual: cannot allocate the remembered field of slab %d (%zu cells, %.1f MiB); residuals stay off", s, cells,
                  (double)(2 * cells * sizeof(float)) / 1048576.0);
-      if (sl.residual_ring.alloc_bytes(ring_bytes) != hipSuccess)
+      if (sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
         LBM_FAIL(LBM_FAILURE, "lbm_set_residual: cannot allocate %d rows (%.1f MiB per slab); residuals stay off", capacity,
                  (double)ring_bytes / 1048576.0);
     }
@@ -3269,26 +3412,12 @@ int lbm_set_residual(lbm_ctx* c, int every, int capacity) {
 
 int lbm_read_residual(lbm_ctx* c, int max_rows, lbm_residual_row* out, int* steps, int* n_read) {
   return drain_recorder(c, kRecResidual, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
-    constexpr size_t words = lbm_residual::kResidualWords;
-    const size_t slots = (size_t)c->rec.slots, n_slabs = (size_t)c->n_slabs;
-    // every slab's words of the n rows (they wait in at most two runs of its ring), gathered as rows[row][slab][words];
-    // the slabs of a row are merged and rounded by residual_row_from_words
-    std::vector<long long> rows((size_t)n * n_slabs * words), stage((size_t)n * words);
-    for (size_t s = 0; s < n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      for (int i = 0; i < n;) {
-        const size_t slot = (size_t)((c->rec.read + i) % c->rec.slots);
-        const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
-        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, sl.residual_ring + slot * words, (size_t)run * words * sizeof(long long),
-                                            hipMemcpyDeviceToHost, sl.compute));
-        i += run;
-      }
-      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
-      for (size_t i = 0; i < (size_t)n; i++) memcpy(&rows[(i * n_slabs + s) * words], &stage[i * words], words * sizeof(long long));
-    }
+    // rows[row][slab][words]: the slabs of a row are merged and rounded by residual_row_from_words
+    std::vector<long long> rows;
+    size_t row_words;
+    if (fetch_gather_records(c, n, rows, &row_words) != LBM_SUCCESS) return LBM_FAILURE;
     for (int i = 0; i < n; i++)
-      out[i] = lbm_residual::residual_row_from_words(rows.data() + (size_t)i * n_slabs * words, (int)n_slabs, c->p.nx,
+      out[i] = lbm_residual::residual_row_from_words(rows.data() + (size_t)i * row_words, c->n_slabs, c->p.nx,
                                                      residual_span(c->rec, c->rec.read + i));
     return LBM_SUCCESS;
   });
@@ -3297,13 +3426,12 @@ int lbm_read_residual(lbm_ctx* c, int max_rows, lbm_residual_row* out, int* step
 int lbm_set_profiles(lbm_ctx* c, int every, int capacity, int axes) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: null context");
   if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: negative interval %d", every);
-  constexpr long long kLineBytes = lbm_profile::kProfileWords * (long long)sizeof(long long);
   if (every > 0) {
     if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: capacity %d, at least one record is needed", capacity);
     if (axes < 1 || axes > (LBM_PROFILE_ROWS | LBM_PROFILE_COLUMNS))
       LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: axes %d, LBM_PROFILE_ROWS (1), LBM_PROFILE_COLUMNS (2) or both (3) are possible", axes);
     for (int s = 0; s < c->n_slabs; s++) {
-      const long long slot_bytes = (long long)lbm_profile::profile_slab_lines(c->slab[s].rows, c->p.nx, axes) * kLineBytes;
+      const long long slot_bytes = (long long)(gather_words(kRecProfiles, 0, c->slab[s].rows, c->p.nx, axes) * sizeof(long long));
       if ((long long)capacity * slot_bytes >= (1LL << 31))
         LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: a ring of %d records is 2 GiB or more (%lld bytes per record and slab)", capacity, slot_bytes);
     }
@@ -3316,9 +3444,9 @@ int lbm_set_profiles(lbm_ctx* c, int every, int capacity, int axes) {
   const int status = rearm_recorder(c, kRecProfiles, every, capacity, [&]() -> int {
     for (int s = 0; s < c->n_slabs; s++) {
       Slab& sl = c->slab[s];
-      const size_t ring_bytes = (size_t)capacity * lbm_profile::profile_slab_lines(sl.rows, c->p.nx, axes) * (size_t)kLineBytes;
+      const size_t ring_bytes = (size_t)capacity * gather_words(kRecProfiles, 0, sl.rows, c->p.nx, axes) * sizeof(long long);
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      if (sl.profile_ring.alloc_bytes(ring_bytes) != hipSuccess)
+      if (sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
         LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: cannot allocate %d records (%.1f MiB for slab %d); profiles stay off", capacity,
                  (double)ring_bytes / 1048576.0, s);
     }
@@ -3330,37 +3458,19 @@ int lbm_set_profiles(lbm_ctx* c, int every, int capacity, int axes) {
 
 int lbm_read_profiles(lbm_ctx* c, int max_records, lbm_profile_line* out, int* steps, int* n_read) {
   return drain_recorder(c, kRecProfiles, max_records, out != nullptr, steps, n_read, [&](int n) -> int {
-    const size_t slots = (size_t)c->rec.slots, n_slabs = (size_t)c->n_slabs;
     const int nx = c->p.nx, ny = c->p.ny, axes = c->rec.axes;
-    // every slab's words of the n records (they wait in at most two runs of its ring), gathered as records[record][slab's
-    // share]; the shares of a record become its lines by profile_lines_from_words
+    // records[record][slab's share]: the shares of a record become its lines by profile_lines_from_words
     int row_first[kMaxSlabs], row_count[kMaxSlabs];
-    size_t share_at[kMaxSlabs + 1] = {0};  // where slab s's words start in a record's
-    for (size_t s = 0; s < n_slabs; s++) {
+    for (int s = 0; s < c->n_slabs; s++) {
       row_first[s] = c->slab[s].row_first;
       row_count[s] = c->slab[s].rows;
-      share_at[s + 1] = share_at[s] + lbm_profile::profile_slab_lines(row_count[s], nx, axes) * lbm_profile::kProfileWords;
     }
-    const size_t record_words = share_at[n_slabs];
-    std::vector<long long> records((size_t)n * record_words), stage;
-    for (size_t s = 0; s < n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      const size_t words = share_at[s + 1] - share_at[s];
-      stage.resize((size_t)n * words);
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      for (int i = 0; i < n;) {
-        const size_t slot = (size_t)((c->rec.read + i) % c->rec.slots);
-        const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
-        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, sl.profile_ring + slot * words, (size_t)run * words * sizeof(long long),
-                                            hipMemcpyDeviceToHost, sl.compute));
-        i += run;
-      }
-      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
-      for (size_t i = 0; i < (size_t)n; i++) memcpy(&records[i * record_words + share_at[s]], &stage[i * words], words * sizeof(long long));
-    }
+    std::vector<long long> records;
+    size_t record_words;
+    if (fetch_gather_records(c, n, records, &record_words) != LBM_SUCCESS) return LBM_FAILURE;
     const size_t lines = lbm_profile::profile_slab_lines(ny, nx, axes);
     for (int i = 0; i < n; i++)
-      lbm_profile::profile_lines_from_words(records.data() + (size_t)i * record_words, (int)n_slabs, row_first, row_count, nx, ny, axes,
+      lbm_profile::profile_lines_from_words(records.data() + (size_t)i * record_words, c->n_slabs, row_first, row_count, nx, ny, axes,
                                             out + (size_t)i * lines);
     return LBM_SUCCESS;
   });
@@ -3617,27 +3727,6 @@ void lbm_destroy_batch(lbm_batch* bt) {
   delete bt;  // the batch's own tables go with it
 }
 
-// what the batched kernels read of every member, [parity of cur][members]
-static std::vector<lbm::ResidentMember> member_table(const lbm_batch* bt) {
-  const size_t n_members = bt->members.size();
-  std::vector<lbm::ResidentMember> h(2 * n_members);
-  for (int par = 0; par < 2; par++)
-    for (size_t i = 0; i < n_members; i++) {
-      const lbm_ctx* c = bt->members[i];
-      const Slab& sl = c->slab[0];
-      lbm::ResidentMember& m = h[(size_t)par * n_members + i];
-      m.src = sl.lat[par];
-      m.dst = sl.lat[par ^ 1];
-      m.mask = sl.mask;
-      m.gran = sl.res_gran;
-      m.partials = sl.res_part;
-      m.tot_u = sl.tot_u;
-      m.omega = c->p.omega;
-      set_accel_weights(m, c->p);  // as run_steps / run_resident
-    }
-  return h;
-}
-
 lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* obstacles, const float* cells_aos,
                             int math_mode) {
   // everything that can be checked without a device is checked first
@@ -3708,10 +3797,7 @@ lbm_batch* lbm_create_batch(int n_members, const lbm_params* params, const int* 
     }
     bt->members_per_launch = mpl;
     bt->launches = ceil_div(n_members, mpl);
-    const std::vector<lbm::ResidentMember> h = member_table(bt);
-    if (bt->table.alloc(h.size()) != hipSuccess ||
-        hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess ||
-        bt->status.alloc(1) != hipSuccess || hipMemset(bt->status, 0, sizeof(int)) != hipSuccess ||
+    if (!upload_member_table(bt) || bt->status.alloc(1) != hipSuccess || hipMemset(bt->status, 0, sizeof(int)) != hipSuccess ||
         bt->status_host.alloc(1) != hipSuccess) {
       lbm_destroy_batch(bt);
       LBM_FAIL(nullptr, "lbm_create_batch: cannot allocate the member table");
@@ -3759,50 +3845,40 @@ static int batch_advance(lbm_batch* bt, int n_steps) {
   return LBM_SUCCESS;
 }
 
-// the forces row of the members' current (stored) lattices into the next slot: the row's words of all members zeroed at
-// once, then one force_gather_batch for all of them, on the batch's stream
-static int take_batch_forces(lbm_batch* bt) {
+// The take() of each batch kind: the record of the members' current (stored) lattices into `row`, its slot, which
+// lbm_batch_run has zeroed for all members at once, on the batch's stream (the current device's).
+// the forces: one force_gather_batch for all members
+static int take_batch_forces(lbm_batch* bt, long long* row) {
   lbm_ctx* c0 = bt->members[0];
   const size_t n_members = bt->members.size();
-  const size_t words = n_members * (size_t)bt->force_bodies * lbm::kForceWords;
-  long long* row = bt->force_ring + (size_t)(bt->rec.written % bt->rec.slots) * words;
-  HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
-  HIP_TRY(LBM_FAILURE, hipMemsetAsync(row, 0, words * sizeof(long long), bt->stream));
   if (bt->force_groups > 0) {
     hipLaunchKernelGGL(lbm::force_gather_batch, dim3((unsigned)bt->force_groups, (unsigned)bt->force_bodies, (unsigned)n_members),
                        dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, c0->slab[0]),
                        (const lbm::ResidentMember*)(bt->table + (size_t)bt->cur * n_members), (const lbm::ForceMember*)bt->force_lists, row);
     HIP_TRY(LBM_FAILURE, hipGetLastError());
   }
-  bt->rec.written++;
   return LBM_SUCCESS;
 }
 
-// the statistics row of the members' current (stored) lattices into the next slot: the row's words of all members zeroed
-// at once, then one stats_gather_batch for all of them, on the batch's stream
-static int take_batch_stats(lbm_batch* bt) {
+// the statistics: one stats_gather_batch for all members
+static int take_batch_stats(lbm_batch* bt, long long* row) {
   lbm_ctx* c0 = bt->members[0];
   const size_t n_members = bt->members.size();
-  const size_t words = n_members * (size_t)lbm_stats::kStatsWords;
-  long long* row = bt->stats_ring + (size_t)(bt->rec.written % bt->rec.slots) * words;
   const Slab& sl0 = c0->slab[0];
   const int v = stats_vector(c0->p.nx);
   const dim3 grid((unsigned)stats_groups((long)sl0.rows * c0->p.nx, v), 1, (unsigned)n_members);
   const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
-  HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
-  HIP_TRY(LBM_FAILURE, hipMemsetAsync(row, 0, words * sizeof(long long), bt->stream));
   if (v == 4)
     hipLaunchKernelGGL(lbm::stats_gather_batch<4>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, row);
   else
     hipLaunchKernelGGL(lbm::stats_gather_batch<1>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, row);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
-  bt->rec.written++;
   return LBM_SUCCESS;
 }
 
 // ONE residual_gather_batch launch over all members' current (stored) lattices and planes, on the batch's stream:
-// the baseline (`planes` filled, `row` unused) or a sample against `planes` into `row`, [members][kResidualWords], zeroed
-// in front
+// the baseline (`planes` filled, `row` unused) or a sample against `planes` into `row`, [members][kResidualWords], which
+// the caller has zeroed in front
 static int launch_batch_residual(lbm_batch* bt, float* planes, long long* row, bool baseline) {
   lbm_ctx* c0 = bt->members[0];
   const size_t n_members = bt->members.size();
@@ -3811,7 +3887,6 @@ static int launch_batch_residual(lbm_batch* bt, float* planes, long long* row, b
   const dim3 grid((unsigned)stats_groups((long)sl0.rows * c0->p.nx, v), 1, (unsigned)n_members);
   const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
-  if (!baseline) HIP_TRY(LBM_FAILURE, hipMemsetAsync(row, 0, n_members * lbm_residual::kResidualWords * sizeof(long long), bt->stream));
   if (v == 4)
     hipLaunchKernelGGL(lbm::residual_gather_batch<4>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows,
                        planes, row, (int)baseline);
@@ -3822,23 +3897,8 @@ static int launch_batch_residual(lbm_batch* bt, float* planes, long long* row, b
   return LBM_SUCCESS;
 }
 
-// the residual row of all members into the next slot
-static int take_batch_residual(lbm_batch* bt) {
-  const size_t words = bt->members.size() * (size_t)lbm_residual::kResidualWords;
-  if (launch_batch_residual(bt, bt->residual_planes, bt->residual_ring + (size_t)(bt->rec.written % bt->rec.slots) * words, false) != LBM_SUCCESS) return LBM_FAILURE;
-  bt->rec.written++;
-  return LBM_SUCCESS;
-}
-
-// a batch-level setter of `kind` called while the batch's one recorder holds another kind: disarming is a no-op
-// (*taken = true, success), arming is refused
-static int batch_recorder_taken(const lbm_batch* bt, int kind, const char* who, int every, bool* taken) {
-  *taken = (bt->rec.kind != kRecNone && bt->rec.kind != kind);
-  if (!*taken || every == 0) return LBM_SUCCESS;
-  const BatchKind* k = batch_kind(bt->rec.kind);
-  LBM_FAIL(LBM_FAILURE, "%s: this batch has %s armed (%s); a batch records one kind -- disarm them with %s first", who,
-           kRecorderKinds[bt->rec.kind].name, k->setter, k->disarm);
-}
+// the residuals: one sample launch against the members' remembered fields
+static int take_batch_residual(lbm_batch* bt, long long* row) { return launch_batch_residual(bt, bt->residual_planes, row, false); }
 
 int lbm_batch_run(lbm_batch* bt, int n_steps) {
   if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: null batch");
@@ -3851,8 +3911,9 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
   for (lbm_ctx* c : bt->members)  // every member's records must fit before any member runs
     if (recorder_fits(c, n_steps, "lbm_batch_run") != LBM_SUCCESS) return LBM_FAILURE;
   if (bt->rec.kind == kRecNone) return batch_advance(bt, n_steps);
-  // forces, statistics or residuals armed: the call runs as the sub-calls that end at the sample steps, each advanced as a
-  // call of its length would be and followed by the row of all members (lbm_run does the same for one context, run_steps)
+  // a gather kind armed: the call runs as the sub-calls that end at the sample steps, each advanced as a call of its
+  // length would be and followed by the record of all members into its zeroed slot (lbm_run does the same for one context,
+  // run_steps and take_record)
   const BatchKind* kind = batch_kind(bt->rec.kind);
   if (recorder_fits(bt->rec, bt->steps_done, n_steps, "lbm_batch_run", kind->reader) != LBM_SUCCESS) return LBM_FAILURE;
   const int e = bt->rec.every;
@@ -3861,7 +3922,12 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
     const long long rec_tt = r ? (long long)tt + (e - r) : tt;  // next sample step
     const int seg = (rec_tt - tt + 1 < n_steps - t) ? (int)(rec_tt - tt + 1) : n_steps - t;
     if (batch_advance(bt, seg) != LBM_SUCCESS) return LBM_FAILURE;
-    if (bt->steps_done - 1 == rec_tt && kind->take(bt) != LBM_SUCCESS) return LBM_FAILURE;
+    if (bt->steps_done - 1 == rec_tt) {
+      HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
+      long long* slot = zeroed_slot(bt->gather_ring, gather_slot_words(bt), bt->rec, bt->stream);
+      if (!slot || kind->take(bt, slot) != LBM_SUCCESS) return LBM_FAILURE;
+      bt->rec.written++;
+    }
     t += seg;
   }
   return LBM_SUCCESS;
@@ -3888,46 +3954,25 @@ int lbm_batch_get_info(const lbm_batch* bt, lbm_batch_info* out) {
 }
 
 // ---- obstacle forces of a batch ------------------------------------------------------------------------------------
-static void release_batch_forces(lbm_batch* bt) {
-  (void)hipSetDevice(bt->members[0]->slab[0].device);
-  bt->force_ring.reset();
-  bt->force_lists.reset();
-  bt->force_links.clear();
-  bt->force_starts.clear();
-  bt->force_link_counts.clear();
-  bt->force_bodies = bt->force_groups = 0;
-  bt->rec = Recorder{};
-  bt->armed[kRecForces] = 0;
-}
-
 int lbm_batch_set_forces(lbm_batch* bt, int n_bodies, const int* body_of_cell, int every, int capacity) {
-  if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: null batch");
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: negative interval %d", every);
-  lbm_ctx* c0 = bt->members[0];
-  const size_t n_members = bt->members.size(), cells = (size_t)c0->p.nx * c0->p.ny;
   // every member's labels as bytes (255: outside 0 .. n_bodies - 1), on the device while the lists are built
-  std::vector<DeviceBuf<unsigned char>> labels(every > 0 && body_of_cell ? n_members : 0);
-  bool taken;  // the batch's one recorder holds another kind
-  if (batch_recorder_taken(bt, kRecForces, "lbm_batch_set_forces", every, &taken) != LBM_SUCCESS) return LBM_FAILURE;
-  if (taken) return LBM_SUCCESS;
-  if (every > 0) {
+  std::vector<DeviceBuf<unsigned char>> labels;
+  return rearm_batch_recorder(bt, kRecForces, every, capacity, [&]() -> int {
+    const lbm_ctx* c0 = bt->members[0];
+    const size_t n_members = bt->members.size(), cells = (size_t)c0->p.nx * c0->p.ny;
     if (n_bodies < 1 || n_bodies > LBM_MAX_BODIES)
       LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: %d bodies, between 1 and LBM_MAX_BODIES = %d are possible", n_bodies, LBM_MAX_BODIES);
     if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: capacity %d, at least one row is needed", capacity);
-    if ((long long)capacity * (long long)n_members * n_bodies * lbm::kForceWords * (long long)sizeof(long long) >= (1LL << 31))
+    const long long row_bytes = (long long)(n_members * gather_words(kRecForces, (size_t)n_bodies) * sizeof(long long));
+    if ((long long)capacity * row_bytes >= (1LL << 31))
       LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: a ring of %d rows of %d members of %d bodies is %.2f GiB, 2 GiB or more (%d bytes per body and row)",
-               capacity, (int)n_members, n_bodies,
-               (double)capacity * (double)n_members * n_bodies * lbm::kForceWords * sizeof(long long) / 1073741824.0,
-               lbm::kForceWords * (int)sizeof(long long));
+               capacity, (int)n_members, n_bodies, (double)capacity * (double)row_bytes / 1073741824.0, lbm::kForceWords * (int)sizeof(long long));
     if (cells > ((size_t)1 << 29))
       LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: members of %d x %d cells; a link is cell * 8 + k - 1 in 32 bits (at most 2^29 cells)",
                c0->p.nx, c0->p.ny);
-    for (size_t i = 0; i < n_members; i++) {
-      const Recorder& r = bt->members[i]->rec;
-      if (r.kind != kRecNone)
-        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: member %d has %s armed (%s); a batch records one kind -- disarm them with %s first", (int)i,
-                 kRecorderKinds[r.kind].name, kRecorderKinds[r.kind].setter, kRecorderKinds[r.kind].disarm);
-    }
+    // the labels go to the device only once no member is in the way: rearm_batch_recorder's next check, made here first
+    if (batch_members_free(bt, "lbm_batch_set_forces") != LBM_SUCCESS) return LBM_FAILURE;
+    labels.resize(body_of_cell ? n_members : 0);
     for (size_t i = 0; i < labels.size(); i++) {
       lbm_ctx* c = bt->members[i];
       const int* src = body_of_cell + i * cells;
@@ -3937,23 +3982,13 @@ int lbm_batch_set_forces(lbm_batch* bt, int n_bodies, const int* body_of_cell, i
         LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: member %d: the blocked cell (%d, %d) has body %d, outside 0 .. %d", (int)i,
                  (int)(first_bad % (unsigned)c->p.nx), (int)(first_bad / (unsigned)c->p.nx), src[first_bad], n_bodies - 1);
     }
-  }
-  // the ring may still be written by launches in flight
-  HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
-  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
-  release_batch_forces(bt);
-  if (every == 0) return LBM_SUCCESS;
-
-  auto allocate = [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * n_members * (size_t)n_bodies * lbm::kForceWords * sizeof(long long);
-    if (bt->force_ring.alloc_bytes(ring_bytes) != hipSuccess || bt->force_lists.alloc(n_members) != hipSuccess)
+    return LBM_SUCCESS;
+  }, [&]() -> int {
+    const size_t n_members = bt->members.size();
+    const size_t ring_bytes = (size_t)capacity * n_members * gather_words(kRecForces, (size_t)n_bodies) * sizeof(long long);
+    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess || bt->force_lists.alloc(n_members) != hipSuccess)
       LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: cannot allocate %d rows of %d members of %d bodies (%.1f MiB); forces stay off", capacity,
                (int)n_members, n_bodies, (double)ring_bytes / 1048576.0);
-    if (!bt->table) {  // a shape the resident kernel does not take: the gather still reads the members' lattices from the table
-      const std::vector<lbm::ResidentMember> h = member_table(bt);
-      if (bt->table.alloc(h.size()) != hipSuccess || hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: cannot allocate the member table; forces stay off");
-    }
     bt->force_links.resize(n_members);
     bt->force_starts.resize(n_members);
     bt->force_link_counts.assign(n_members * (size_t)n_bodies, 0);
@@ -3974,56 +4009,16 @@ int lbm_batch_set_forces(lbm_batch* bt, int n_bodies, const int* body_of_cell, i
     }
     HIP_TRY(LBM_FAILURE, hipMemcpy(bt->force_lists, lists.data(), lists.size() * sizeof(lists[0]), hipMemcpyHostToDevice));
     bt->force_groups = gather_groups(most);  // the x-extent suits the largest body of any member
+    bt->force_bodies = n_bodies;
     return LBM_SUCCESS;
-  };
-  if (allocate() != LBM_SUCCESS) {
-    (void)hipGetLastError();  // a failed allocation must not surface at the next launch
-    release_batch_forces(bt);
-    return LBM_FAILURE;
-  }
-  bt->force_bodies = n_bodies;
-  bt->rec.kind = kRecForces;
-  bt->rec.every = every;
-  bt->rec.slots = capacity;
-  bt->rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
-  bt->armed[kRecForces] = 1;
-  return LBM_SUCCESS;
+  });
 }
 
 int lbm_batch_read_forces(lbm_batch* bt, int max_rows, double* out, int* steps, int* n_read) {
-  if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_forces: NULL argument");
-  *n_read = 0;
-  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
-  Recorder& r = bt->rec;
-  const long long waiting = (r.kind == kRecForces) ? r.written - r.read : 0;
-  if (!out && !steps) {
-    *n_read = (int)waiting;
-    return LBM_SUCCESS;
-  }
-  if (!out) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_forces: NULL row output");
-  if (max_rows < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_forces: negative max_rows %d", max_rows);
-  const int n = (waiting < max_rows) ? (int)waiting : max_rows;
-  if (n > 0) {
-    // the n oldest rows wait in at most two runs of the ring; each body's two sums are rounded once and doubled
-    const size_t bodies = bt->members.size() * (size_t)bt->force_bodies, words = bodies * (size_t)lbm::kForceWords;
-    const size_t slots = (size_t)r.slots;
-    std::vector<long long> stage((size_t)n * words);
-    HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
-    for (int i = 0; i < n;) {
-      const size_t slot = (size_t)((r.read + i) % r.slots);
-      const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
-      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, bt->force_ring + slot * words, (size_t)run * words * sizeof(long long),
-                                          hipMemcpyDeviceToHost, bt->stream));
-      i += run;
-    }
-    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
-    round_forces(stage.data(), (size_t)n * bodies, out);
-  }
-  if (steps)
-    for (int i = 0; i < n; i++) steps[i] = (int)((r.ord0 + r.read + i) * r.every);
-  r.read += n;
-  *n_read = n;
-  return LBM_SUCCESS;
+  return drain_batch_recorder(bt, kRecForces, max_rows, out != nullptr, steps, n_read, [&](int n, const long long* words) {
+    // each body's two sums are rounded once and doubled
+    round_forces(words, (size_t)n * bt->members.size() * (size_t)bt->force_bodies, out);
+  });
 }
 
 int lbm_batch_forces_links(lbm_batch* bt, int* links) {
@@ -4035,221 +4030,80 @@ int lbm_batch_forces_links(lbm_batch* bt, int* links) {
 }
 
 // ---- lattice statistics of a batch ---------------------------------------------------------------------------------
-static void release_batch_stats(lbm_batch* bt) {
-  (void)hipSetDevice(bt->members[0]->slab[0].device);
-  bt->stats_ring.reset();
-  bt->rec = Recorder{};
-  bt->armed[kRecStats] = 0;
-}
-
 int lbm_batch_set_stats(lbm_batch* bt, int every, int capacity) {
-  if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: null batch");
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: negative interval %d", every);
-  lbm_ctx* c0 = bt->members[0];
-  const size_t n_members = bt->members.size();
-  const size_t row_bytes = n_members * lbm_stats::kStatsWords * sizeof(long long);
-  bool taken;  // the batch's one recorder holds another kind
-  if (batch_recorder_taken(bt, kRecStats, "lbm_batch_set_stats", every, &taken) != LBM_SUCCESS) return LBM_FAILURE;
-  if (taken) return LBM_SUCCESS;
-  if (every > 0) {
+  size_t row_bytes = 0;  // of all members
+  return rearm_batch_recorder(bt, kRecStats, every, capacity, [&]() -> int {
+    const size_t n_members = bt->members.size();
+    row_bytes = n_members * gather_words(kRecStats) * sizeof(long long);
     if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: capacity %d, at least one row is needed", capacity);
     if ((long long)capacity * (long long)row_bytes >= (1LL << 31))
       LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: a ring of %d rows of %d members is %.2f GiB, 2 GiB or more (%d bytes per member and row)",
                capacity, (int)n_members, (double)capacity * (double)row_bytes / 1073741824.0,
                lbm_stats::kStatsWords * (int)sizeof(long long));
-    for (size_t i = 0; i < n_members; i++) {
-      const Recorder& r = bt->members[i]->rec;
-      if (r.kind != kRecNone)
-        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: member %d has %s armed (%s); a batch records one kind -- disarm them with %s first", (int)i,
-                 kRecorderKinds[r.kind].name, kRecorderKinds[r.kind].setter, kRecorderKinds[r.kind].disarm);
-    }
-  }
-  // the ring may still be written by launches in flight
-  HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
-  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
-  release_batch_stats(bt);
-  if (every == 0) return LBM_SUCCESS;
-
-  auto allocate = [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * row_bytes;
-    if (bt->stats_ring.alloc_bytes(ring_bytes) != hipSuccess)
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: cannot allocate %d rows of %d members (%.1f MiB); statistics stay off", capacity,
-               (int)n_members, (double)ring_bytes / 1048576.0);
-    if (!bt->table) {  // a shape the resident kernel does not take: the gather still reads the members' lattices from the table
-      const std::vector<lbm::ResidentMember> h = member_table(bt);
-      if (bt->table.alloc(h.size()) != hipSuccess || hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: cannot allocate the member table; statistics stay off");
-    }
     return LBM_SUCCESS;
-  };
-  if (allocate() != LBM_SUCCESS) {
-    (void)hipGetLastError();  // a failed allocation must not surface at the next launch
-    release_batch_stats(bt);
-    return LBM_FAILURE;
-  }
-  bt->rec.kind = kRecStats;
-  bt->rec.every = every;
-  bt->rec.slots = capacity;
-  bt->rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
-  bt->armed[kRecStats] = 1;
-  return LBM_SUCCESS;
+  }, [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * row_bytes;
+    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: cannot allocate %d rows of %d members (%.1f MiB); statistics stay off", capacity,
+               (int)bt->members.size(), (double)ring_bytes / 1048576.0);
+    return LBM_SUCCESS;
+  });
 }
 
 int lbm_batch_read_stats(lbm_batch* bt, int max_rows, lbm_stats_row* out, int* steps, int* n_read) {
-  if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_stats: NULL argument");
-  *n_read = 0;
-  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
-  Recorder& r = bt->rec;
-  const long long waiting = (r.kind == kRecStats) ? r.written - r.read : 0;
-  if (!out && !steps) {
-    *n_read = (int)waiting;
-    return LBM_SUCCESS;
-  }
-  if (!out) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_stats: NULL row output");
-  if (max_rows < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_stats: negative max_rows %d", max_rows);
-  const int n = (waiting < max_rows) ? (int)waiting : max_rows;
-  if (n > 0) {
-    // the n oldest rows wait in at most two runs of the ring; every member's words become its row
-    const size_t n_members = bt->members.size(), words = n_members * (size_t)lbm_stats::kStatsWords;
-    const size_t slots = (size_t)r.slots;
-    std::vector<long long> stage((size_t)n * words);
-    HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
-    for (int i = 0; i < n;) {
-      const size_t slot = (size_t)((r.read + i) % r.slots);
-      const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
-      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, bt->stats_ring + slot * words, (size_t)run * words * sizeof(long long),
-                                          hipMemcpyDeviceToHost, bt->stream));
-      i += run;
-    }
-    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
-    for (size_t j = 0; j < (size_t)n * n_members; j++)
-      out[j] = lbm_stats::stats_row_from_words(stage.data() + j * lbm_stats::kStatsWords, 1, bt->members[0]->p.nx);
-  }
-  if (steps)
-    for (int i = 0; i < n; i++) steps[i] = (int)((r.ord0 + r.read + i) * r.every);
-  r.read += n;
-  *n_read = n;
-  return LBM_SUCCESS;
+  return drain_batch_recorder(bt, kRecStats, max_rows, out != nullptr, steps, n_read, [&](int n, const long long* words) {
+    // every member's words become its row
+    for (size_t j = 0; j < (size_t)n * bt->members.size(); j++)
+      out[j] = lbm_stats::stats_row_from_words(words + j * lbm_stats::kStatsWords, 1, bt->members[0]->p.nx);
+  });
 }
 
 // ---- velocity residuals of a batch ---------------------------------------------------------------------------------
-static void release_batch_residual(lbm_batch* bt) {
-  (void)hipSetDevice(bt->members[0]->slab[0].device);
-  bt->residual_ring.reset();
-  bt->residual_planes.reset();
-  bt->rec = Recorder{};
-  bt->armed[kRecResidual] = 0;
-}
-
 int lbm_batch_set_residual(lbm_batch* bt, int every, int capacity) {
-  if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: null batch");
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: negative interval %d", every);
-  lbm_ctx* c0 = bt->members[0];
-  const size_t n_members = bt->members.size();
-  const size_t row_bytes = n_members * lbm_residual::kResidualWords * sizeof(long long);
-  bool taken;  // the batch's one recorder holds another kind
-  if (batch_recorder_taken(bt, kRecResidual, "lbm_batch_set_residual", every, &taken) != LBM_SUCCESS) return LBM_FAILURE;
-  if (taken) return LBM_SUCCESS;
-  if (every > 0) {
+  size_t row_bytes = 0;  // of all members
+  return rearm_batch_recorder(bt, kRecResidual, every, capacity, [&]() -> int {
+    const size_t n_members = bt->members.size();
+    row_bytes = n_members * gather_words(kRecResidual) * sizeof(long long);
     if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: capacity %d, at least one row is needed", capacity);
     if ((long long)capacity * (long long)row_bytes >= (1LL << 31))
       LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: a ring of %d rows of %d members is %.2f GiB, 2 GiB or more (%d bytes per member and row)",
                capacity, (int)n_members, (double)capacity * (double)row_bytes / 1073741824.0,
                lbm_residual::kResidualWords * (int)sizeof(long long));
-    for (size_t i = 0; i < n_members; i++) {
-      const Recorder& r = bt->members[i]->rec;
-      if (r.kind != kRecNone)
-        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: member %d has %s armed (%s); a batch records one kind -- disarm them with %s first", (int)i,
-                 kRecorderKinds[r.kind].name, kRecorderKinds[r.kind].setter, kRecorderKinds[r.kind].disarm);
-    }
-  }
-  // the ring and the planes may still be written by launches in flight
-  HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
-  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
-  release_batch_residual(bt);
-  if (every == 0) return LBM_SUCCESS;
-
-  auto allocate = [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * row_bytes;
+    return LBM_SUCCESS;
+  }, [&]() -> int {
+    const lbm_ctx* c0 = bt->members[0];
+    const size_t n_members = bt->members.size(), ring_bytes = (size_t)capacity * row_bytes;
     const size_t cells = (size_t)c0->slab[0].rows * c0->p.nx;
     if (bt->residual_planes.alloc(n_members * 2 * cells) != hipSuccess)
       LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: cannot allocate the remembered fields of %d members (%zu cells each, %.1f MiB); residuals stay off",
                (int)n_members, cells, (double)(n_members * 2 * cells * sizeof(float)) / 1048576.0);
-    if (bt->residual_ring.alloc_bytes(ring_bytes) != hipSuccess)
+    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
       LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: cannot allocate %d rows of %d members (%.1f MiB); residuals stay off", capacity,
                (int)n_members, (double)ring_bytes / 1048576.0);
-    if (!bt->table) {  // a shape the resident kernel does not take: the gather still reads the members' lattices from the table
-      const std::vector<lbm::ResidentMember> h = member_table(bt);
-      if (bt->table.alloc(h.size()) != hipSuccess || hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: cannot allocate the member table; residuals stay off");
-    }
+    bt->rec.base_steps = bt->steps_done;
     return launch_batch_residual(bt, bt->residual_planes, nullptr, true);  // the baselines of all members: one launch
-  };
-  if (allocate() != LBM_SUCCESS) {
-    (void)hipGetLastError();  // a failed allocation must not surface at the next launch
-    release_batch_residual(bt);
-    return LBM_FAILURE;
-  }
-  bt->rec.kind = kRecResidual;
-  bt->rec.every = every;
-  bt->rec.slots = capacity;
-  bt->rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
-  bt->rec.base_steps = bt->steps_done;
-  bt->armed[kRecResidual] = 1;
-  return LBM_SUCCESS;
+  });
 }
 
 int lbm_batch_read_residual(lbm_batch* bt, int max_rows, lbm_residual_row* out, int* steps, int* n_read) {
-  if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_residual: NULL argument");
-  *n_read = 0;
-  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
-  Recorder& r = bt->rec;
-  const long long waiting = (r.kind == kRecResidual) ? r.written - r.read : 0;
-  if (!out && !steps) {
-    *n_read = (int)waiting;
-    return LBM_SUCCESS;
-  }
-  if (!out) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_residual: NULL row output");
-  if (max_rows < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_residual: negative max_rows %d", max_rows);
-  const int n = (waiting < max_rows) ? (int)waiting : max_rows;
-  if (n > 0) {
-    // the n oldest rows wait in at most two runs of the ring; every member's words become its row
-    const size_t n_members = bt->members.size(), words = n_members * (size_t)lbm_residual::kResidualWords;
-    const size_t slots = (size_t)r.slots;
-    std::vector<long long> stage((size_t)n * words);
-    HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
-    for (int i = 0; i < n;) {
-      const size_t slot = (size_t)((r.read + i) % r.slots);
-      const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
-      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, bt->residual_ring + slot * words, (size_t)run * words * sizeof(long long),
-                                          hipMemcpyDeviceToHost, bt->stream));
-      i += run;
-    }
-    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
+  return drain_batch_recorder(bt, kRecResidual, max_rows, out != nullptr, steps, n_read, [&](int n, const long long* words) {
+    // every member's words become its row
+    const size_t n_members = bt->members.size();
     for (size_t j = 0; j < (size_t)n * n_members; j++)
-      out[j] = lbm_residual::residual_row_from_words(stage.data() + j * lbm_residual::kResidualWords, 1, bt->members[0]->p.nx,
-                                                     residual_span(r, r.read + (long long)(j / n_members)));
-  }
-  if (steps)
-    for (int i = 0; i < n; i++) steps[i] = (int)((r.ord0 + r.read + i) * r.every);
-  r.read += n;
-  *n_read = n;
-  return LBM_SUCCESS;
+      out[j] = lbm_residual::residual_row_from_words(words + j * lbm_residual::kResidualWords, 1, bt->members[0]->p.nx,
+                                                     residual_span(bt->rec, bt->rec.read + (long long)(j / n_members)));
+  });
 }
 
 // ---- line profiles of a batch --------------------------------------------------------------------------------------
-// the profile record of the members' current (stored) lattices into the next slot: the record's words of all members
-// zeroed at once, then one launch per selected axis for all of them, on the batch's stream
-static int take_batch_profiles(lbm_batch* bt) {
+// the profiles: one launch per selected axis for all members
+static int take_batch_profiles(lbm_batch* bt, long long* record) {
   lbm_ctx* c0 = bt->members[0];
   const Slab& sl0 = c0->slab[0];
   const size_t n_members = bt->members.size();
   const int nx = c0->p.nx, axes = bt->rec.axes;
-  const long member_words = (long)(lbm_profile::profile_slab_lines(sl0.rows, nx, axes) * lbm_profile::kProfileWords);
-  long long* record = bt->profile_ring + (size_t)(bt->rec.written % bt->rec.slots) * n_members * (size_t)member_words;
+  const long member_words = (long)(gather_slot_words(bt) / n_members);
   const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
-  HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
-  HIP_TRY(LBM_FAILURE, hipMemsetAsync(record, 0, n_members * (size_t)member_words * sizeof(long long), bt->stream));
   long long* lines = record;
   if (axes & LBM_PROFILE_ROWS) {
     const dim3 grid((unsigned)ceil_div(sl0.rows, lbm::kBlock / 64), 1, (unsigned)n_members);
@@ -4266,112 +4120,43 @@ static int take_batch_profiles(lbm_batch* bt) {
                        member_words);
   }
   HIP_TRY(LBM_FAILURE, hipGetLastError());
-  bt->rec.written++;
   return LBM_SUCCESS;
 }
 
-static void release_batch_profiles(lbm_batch* bt) {
-  (void)hipSetDevice(bt->members[0]->slab[0].device);
-  bt->profile_ring.reset();
-  bt->rec = Recorder{};
-  bt->armed[kRecProfiles] = 0;
-}
-
 int lbm_batch_set_profiles(lbm_batch* bt, int every, int capacity, int axes) {
-  if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: null batch");
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: negative interval %d", every);
-  lbm_ctx* c0 = bt->members[0];
-  const size_t n_members = bt->members.size();
-  bool taken;  // the batch's one recorder holds another kind
-  if (batch_recorder_taken(bt, kRecProfiles, "lbm_batch_set_profiles", every, &taken) != LBM_SUCCESS) return LBM_FAILURE;
-  if (taken) return LBM_SUCCESS;
-  size_t record_bytes = 0;
-  if (every > 0) {
+  size_t record_bytes = 0;  // of all members
+  return rearm_batch_recorder(bt, kRecProfiles, every, capacity, [&]() -> int {
+    const lbm_ctx* c0 = bt->members[0];
+    const size_t n_members = bt->members.size();
     if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: capacity %d, at least one record is needed", capacity);
     if (axes < 1 || axes > (LBM_PROFILE_ROWS | LBM_PROFILE_COLUMNS))
       LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: axes %d, LBM_PROFILE_ROWS (1), LBM_PROFILE_COLUMNS (2) or both (3) are possible", axes);
-    const size_t member_bytes = lbm_profile::profile_slab_lines(c0->slab[0].rows, c0->p.nx, axes) * lbm_profile::kProfileWords * sizeof(long long);
+    const size_t member_bytes = gather_words(kRecProfiles, 0, c0->slab[0].rows, c0->p.nx, axes) * sizeof(long long);
     record_bytes = n_members * member_bytes;
     if ((long long)capacity * (long long)record_bytes >= (1LL << 31))
       LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: a ring of %d records of %d members is %.2f GiB, 2 GiB or more (%zu bytes per member and record)",
                capacity, (int)n_members, (double)capacity * (double)record_bytes / 1073741824.0, member_bytes);
-    for (size_t i = 0; i < n_members; i++) {
-      const Recorder& r = bt->members[i]->rec;
-      if (r.kind != kRecNone)
-        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: member %d has %s armed (%s); a batch records one kind -- disarm them with %s first", (int)i,
-                 kRecorderKinds[r.kind].name, kRecorderKinds[r.kind].setter, kRecorderKinds[r.kind].disarm);
-    }
-  }
-  // the ring may still be written by launches in flight
-  HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
-  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
-  release_batch_profiles(bt);
-  if (every == 0) return LBM_SUCCESS;
-
-  auto allocate = [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * record_bytes;
-    if (bt->profile_ring.alloc_bytes(ring_bytes) != hipSuccess)
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: cannot allocate %d records of %d members (%.1f MiB); profiles stay off", capacity,
-               (int)n_members, (double)ring_bytes / 1048576.0);
-    if (!bt->table) {  // a shape the resident kernel does not take: the kernels still read the members' lattices from the table
-      const std::vector<lbm::ResidentMember> h = member_table(bt);
-      if (bt->table.alloc(h.size()) != hipSuccess || hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: cannot allocate the member table; profiles stay off");
-    }
     return LBM_SUCCESS;
-  };
-  if (allocate() != LBM_SUCCESS) {
-    (void)hipGetLastError();  // a failed allocation must not surface at the next launch
-    release_batch_profiles(bt);
-    return LBM_FAILURE;
-  }
-  bt->rec.kind = kRecProfiles;
-  bt->rec.every = every;
-  bt->rec.slots = capacity;
-  bt->rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
-  bt->rec.axes = axes;
-  bt->armed[kRecProfiles] = 1;
-  return LBM_SUCCESS;
+  }, [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * record_bytes;
+    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: cannot allocate %d records of %d members (%.1f MiB); profiles stay off", capacity,
+               (int)bt->members.size(), (double)ring_bytes / 1048576.0);
+    bt->rec.axes = axes;
+    return LBM_SUCCESS;
+  });
 }
 
 int lbm_batch_read_profiles(lbm_batch* bt, int max_records, lbm_profile_line* out, int* steps, int* n_read) {
-  if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_profiles: NULL argument");
-  *n_read = 0;
-  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
-  Recorder& r = bt->rec;
-  const long long waiting = (r.kind == kRecProfiles) ? r.written - r.read : 0;
-  if (!out && !steps) {
-    *n_read = (int)waiting;
-    return LBM_SUCCESS;
-  }
-  if (!out) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_profiles: NULL record output");
-  if (max_records < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_read_profiles: negative max_records %d", max_records);
-  const int n = (waiting < max_records) ? (int)waiting : max_records;
-  if (n > 0) {
-    // the n oldest records wait in at most two runs of the ring; every member's words become its lines
+  return drain_batch_recorder(bt, kRecProfiles, max_records, out != nullptr, steps, n_read, [&](int n, const long long* words) {
+    // every member's words become its lines
     const lbm_ctx* c0 = bt->members[0];
-    const int nx = c0->p.nx, ny = c0->slab[0].rows, row_first = 0;
-    const size_t n_members = bt->members.size(), lines = lbm_profile::profile_slab_lines(ny, nx, r.axes);
-    const size_t member_words = lines * lbm_profile::kProfileWords, words = n_members * member_words;
-    const size_t slots = (size_t)r.slots;
-    std::vector<long long> stage((size_t)n * words);
-    HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
-    for (int i = 0; i < n;) {
-      const size_t slot = (size_t)((r.read + i) % r.slots);
-      const int run = ((size_t)(n - i) < slots - slot) ? n - i : (int)(slots - slot);
-      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(stage.data() + (size_t)i * words, bt->profile_ring + slot * words, (size_t)run * words * sizeof(long long),
-                                          hipMemcpyDeviceToHost, bt->stream));
-      i += run;
-    }
-    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
+    const int nx = c0->p.nx, ny = c0->slab[0].rows, row_first = 0, axes = bt->rec.axes;
+    const size_t n_members = bt->members.size(), lines = lbm_profile::profile_slab_lines(ny, nx, axes);
+    const size_t member_words = gather_slot_words(bt) / n_members;
     for (size_t j = 0; j < (size_t)n * n_members; j++)
-      lbm_profile::profile_lines_from_words(stage.data() + j * member_words, 1, &row_first, &ny, nx, ny, r.axes, out + j * lines);
-  }
-  if (steps)
-    for (int i = 0; i < n; i++) steps[i] = (int)((r.ord0 + r.read + i) * r.every);
-  r.read += n;
-  *n_read = n;
-  return LBM_SUCCESS;
+      lbm_profile::profile_lines_from_words(words + j * member_words, 1, &row_first, &ny, nx, ny, axes, out + j * lines);
+  });
 }
 
 // ---- steady-state runs ---------------------------------------------------------------------------------------------
@@ -4739,14 +4524,8 @@ int lbm_batch_run_until_residual(lbm_batch* bt, int max_steps, int check_every, 
   const Slab& sl0 = c0->slab[0];
   const size_t row_words = n_members * (size_t)lbm_residual::kResidualWords;
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
-  if (!bt->table) {  // a shape the resident kernel does not take: the gather still reads the members' lattices from the table
-    const std::vector<lbm::ResidentMember> h = member_table(bt);
-    if (bt->table.alloc(h.size()) != hipSuccess || hipMemcpy(bt->table, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipGetLastError();
-      bt->table.reset();
-      LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the member table; nothing was run", who);
-    }
-  }
+  // (a shape the resident kernel does not take: the gather still reads the members' lattices from the table)
+  if (!bt->table && !upload_member_table(bt)) LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the member table; nothing was run", who);
   if (!bt->until_state) {  // allocated last: the set is whole
     const size_t cells = (size_t)sl0.rows * c0->p.nx;
     if (bt->until_planes.alloc(n_members * 2 * cells) != hipSuccess) {
@@ -4780,6 +4559,7 @@ int lbm_batch_run_until_residual(lbm_batch* bt, int max_steps, int check_every, 
   int judged = 0;
   for (; judged < n_seg && !stop; judged++) {
     if (lbm_batch_run(bt, E) != LBM_SUCCESS) return LBM_FAILURE;
+    HIP_TRY(LBM_FAILURE, hipMemsetAsync(bt->until_words, 0, row_words * sizeof(long long), bt->stream));
     if (launch_batch_residual(bt, bt->until_planes, bt->until_words, false) != LBM_SUCCESS) return LBM_FAILURE;
     long long* hist = (size_t)judged < hist_rows ? bt->until_history + (size_t)judged * row_words : nullptr;
     hipLaunchKernelGGL(lbm::residual_check_batch, dim3((unsigned)n_members), dim3(64), 0, bt->stream, bt->until_words.get(), hist,
