@@ -703,7 +703,7 @@ int launch_step(lbm_ctx* c, int s, hipStream_t stream, int row_first, int row_st
 // two timesteps in one pass over the rows [row_first, row_end) of slab s, cut into band_count bands of
 // band_rows rows that start band_pitch rows apart; writes the partials of steps t and t+1 into
 // slots slot_fill and slot_fill+1
-int launch_step2(lbm_ctx* c, int s, hipStream_t stream, int row_first, int row_end, int band_rows,
+int launch_step2(lbm_ctx* c, int s, hipStream_t stream, const lbm_plan::StreamRow& row, int row_first, int row_end, int band_rows,
                  int band_pitch, int band_count, int part_offset, bool accel_after, hipEvent_t done = nullptr) {
   Slab& sl = c->slab[s];
   if (band_count <= 0) return LBM_SUCCESS;
@@ -730,14 +730,14 @@ int launch_step2(lbm_ctx* c, int s, hipStream_t stream, int row_first, int row_e
        {lbm::step2_stream<0, true, 4>, lbm::step2_stream<0, true, 2>}},
       {{lbm::step2_stream<1, false, 4>, lbm::step2_stream<1, false, 2>},
        {lbm::step2_stream<1, true, 4>, lbm::step2_stream<1, true, 2>}}};
-  const fn kernel = table[c->math_mode == LBM_MATH_EXACT ? 0 : 1][c->plan.nts][c->plan.lane_cells == 2 ? 1 : 0];
+  const fn kernel = table[row.math][row.nts][row.lane_cells == 2 ? 1 : 0];
   void* args[] = {&a};
   return q_kernel(c, stream, reinterpret_cast<const void*>(kernel), dim3(waves), dim3(64), args, done);
 }
 
-// k (2..4) timesteps in one pass over the rows [row_first, row_end) of slab s (4 cells per lane), cut into band_count
+// row.k (2..4) timesteps in one pass over the rows [row_first, row_end) of slab s (4 cells per lane), cut into band_count
 // bands of band_rows rows that start band_pitch rows apart; partials of step t+j go to slot slot_fill + j
-int launch_stepk(lbm_ctx* c, int s, hipStream_t stream, int k, int row_first, int row_end, int band_rows,
+int launch_stepk(lbm_ctx* c, int s, hipStream_t stream, const lbm_plan::StreamRow& row, int row_first, int row_end, int band_rows,
                  int band_pitch, int band_count, int part_offset, bool accel_after, hipEvent_t done = nullptr) {
   Slab& sl = c->slab[s];
   if (band_count <= 0) return LBM_SUCCESS;
@@ -791,22 +791,22 @@ int launch_stepk(lbm_ctx* c, int s, hipStream_t stream, int k, int row_first, in
   static const fn table_pk1[2][3][2][2] = {LBM_PK1_ROW(false), LBM_PK1_ROW(true)};
 #undef LBM_PK1_ROW
 #undef LBM_PK1
-  const int lds_windows = c->plan.lds_windows < k ? c->plan.lds_windows : k - 1;
-  const bool packed = c->plan.packed != 0;  // the packed kernels have one arithmetic (the exact one) and serve both math modes
-  const fn kernel = (packed && c->plan.lane_cells == 2) ? table_pk1[c->plan.nts][k - 2][c->plan.prefetch ? 1 : 0][lds_windows ? 1 : 0]
-                    : packed ? table_pk[c->plan.nts][k - 2][c->plan.prefetch ? 1 : 0][lds_windows]
-                           : table[c->math_mode == LBM_MATH_EXACT ? 0 : 1][c->plan.nts][k - 2][c->plan.prefetch ? 1 : 0];
+  // the packed kernels have one arithmetic (the exact one) and serve both math modes; lbm_plan::stream_row has folded
+  // the requests without a kernel of their own onto the entries that run instead
+  const fn kernel = row.family == lbm_plan::ROW_STEPK_PK1 ? table_pk1[row.nts][row.k - 2][row.prefetch][row.lds]
+                    : row.family == lbm_plan::ROW_STEPK_PK ? table_pk[row.nts][row.k - 2][row.prefetch][row.lds]
+                                                           : table[row.math][row.nts][row.k - 2][row.prefetch];
   void* args[] = {&a};
   return q_kernel(c, stream, reinterpret_cast<const void*>(kernel), dim3(waves), dim3(64), args, done);
 }
 
-// the stream kernel for a k-step pass: the 2-cells-per-lane form exists for k = 2 only (step2_stream)
+// the stream kernel for a k-step pass: which instantiation runs is the planner's arithmetic (lbm_plan::stream_row)
 int launch_pass(lbm_ctx* c, int s, hipStream_t stream, int k, int row_first, int row_end, int band_rows,
                 int band_pitch, int band_count, int part_offset, bool accel_after, hipEvent_t done = nullptr) {
-  if ((c->plan.lane_cells == 4 && (k > 2 || c->plan.prefetch || c->plan.xcd_chunk || c->plan.use_stepk || c->plan.packed)) ||
-      (c->plan.lane_cells == 2 && c->plan.packed))
-    return launch_stepk(c, s, stream, k, row_first, row_end, band_rows, band_pitch, band_count, part_offset, accel_after, done);
-  return launch_step2(c, s, stream, row_first, row_end, band_rows, band_pitch, band_count, part_offset, accel_after, done);
+  const lbm_plan::StreamRow row = lbm_plan::stream_row(c->plan, k, c->math_mode == LBM_MATH_EXACT);
+  if (row.family != lbm_plan::ROW_STEP2_STREAM)
+    return launch_stepk(c, s, stream, row, row_first, row_end, band_rows, band_pitch, band_count, part_offset, accel_after, done);
+  return launch_step2(c, s, stream, row, row_first, row_end, band_rows, band_pitch, band_count, part_offset, accel_after, done);
 }
 
 int tile_count(const lbm_ctx* c) { return lbm_plan::tile_count(c->p.nx, c->slab[0].rows, c->plan.tile_shape); }

@@ -478,4 +478,43 @@ inline KernelPlan plan_kernels(const PlanInput& in) {
   return pl;
 }
 
+// ---- which stream kernel a pass launches ----------------------------------------------------------------------------
+// The instantiation that advances k (2..4) timesteps in one pass under a plan: the kernel family and the template
+// arguments that differ between its instantiations, with every request that has no kernel of its own already folded
+// onto the one that runs instead.  lbm_hip.hip keeps the tables of function pointers and indexes them with this answer;
+// tests/plan_dump.cpp prints it, so what a forced environment launches is known without a device.
+//   step2_stream  <math, nts, lane_cells>             two steps, scalar arithmetic, four or two cells per lane
+//   stepk_stream  <math, nts, 4, k, prefetch>         scalar arithmetic, four cells per lane
+//   stepk_pk      <nts, k, prefetch, lds>             pairs of cells (exact arithmetic, both math modes), two pairs per lane
+//   stepk_pk1     <nts, k, prefetch, lds, false, 1>   ... one pair per lane
+enum StreamFamily { ROW_STEP2_STREAM = 0, ROW_STEPK_STREAM = 1, ROW_STEPK_PK = 2, ROW_STEPK_PK1 = 3 };
+struct StreamRow {
+  int family;      // StreamFamily
+  int math;        // 0 exact, 1 fast (the packed kernels have the exact arithmetic only: 0)
+  int nts;         // nontemporal stores
+  int lane_cells;  // 4 or 2
+  int k;           // timesteps of the pass
+  int prefetch;    // the next row is requested before the current one is relaxed
+  int lds;         // sliding windows kept in LDS (packed kernels)
+};
+inline StreamRow stream_row(const KernelPlan& pl, int k, bool exact) {
+  const int math = exact ? 0 : 1, pf = pl.prefetch ? 1 : 0;
+  if (pl.packed && pl.lane_cells == 2) {
+    // one pair per lane: at most one window in LDS; K = 4 prefetches only with that window there (else it spills)
+    const int lds = (pl.lds_windows < k ? pl.lds_windows : k - 1) ? 1 : 0;
+    return {ROW_STEPK_PK1, 0, pl.nts, 2, k, (k == 4 && !lds) ? 0 : pf, lds};
+  }
+  if (pl.packed && pl.lane_cells == 4) {
+    // a K-step pass has K - 1 sliding windows; K = 4 prefetches only with two of its three windows in LDS
+    const int lds = pl.lds_windows < k ? pl.lds_windows : k - 1;
+    return {ROW_STEPK_PK, 0, pl.nts, 4, k, (k == 4 && lds < 2) ? 0 : pf, lds};
+  }
+  // scalar arithmetic.  The two-cell form exists for two steps only (step2_stream); the four-cell form runs two steps
+  // through stepk_stream where something only that kernel has is asked for.  K = 4 with the next row prefetched does not
+  // fit the register file (112 bytes of scratch per lane), so that request runs the kernel without prefetch.
+  if (pl.lane_cells == 4 && (k > 2 || pl.prefetch || pl.xcd_chunk || pl.use_stepk))
+    return {ROW_STEPK_STREAM, math, pl.nts, 4, k, k == 4 ? 0 : pf, 0};
+  return {ROW_STEP2_STREAM, math, pl.nts, pl.lane_cells == 2 ? 2 : 4, 2, 0, 0};
+}
+
 }  // namespace lbm_plan

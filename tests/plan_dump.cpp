@@ -1,5 +1,6 @@
-// plan_dump: prints what lbm_plan.h decides for one context, as one JSON object -- the fields of
-// tests/golden/kernel_plans.json.  Host arithmetic only; the LBM_* knobs come from the environment.
+// plan_dump: prints what lbm_plan.h decides for one context, as one JSON object -- "plan" and "slabs", the fields of
+// tests/golden/kernel_plans.json, and "stream_rows", the stream-kernel instantiations an exact context with this plan
+// launches (tests/stream_rows.py).  Host arithmetic only; the LBM_* knobs come from the environment.
 //   plan_dump nx ny world rank n_slabs halo cus n_devices distinct_devices
 // halo: 0 none, 1 device copies, 2 RCCL, 3 the host's message passing (lbm_plan::HaloKind)
 #include "../lbm-asynchronous_amd/csrc/lbm_plan.h"
@@ -40,6 +41,19 @@ int main(int argc, char** argv) {
     const lbm_plan::SlabRows sl = lbm_plan::slab_rows(in, p.vec4, s);
     printf("%s{\"rows\":%d,\"accel_row\":%d,\"accel_row2\":%d,\"blocks_main\":%d,\"blocks_boundary\":%d}", s ? "," : "", sl.rows,
            sl.accel_row, sl.accel_row2, sl.blocks_main, sl.blocks_boundary);
+  }
+  // the stream kernels an exact context with this plan launches (lbm_plan::stream_row): the full pass at pass_steps,
+  // the two-step pass of a remainder of two or three, and -- not a stream kernel -- the one-step kernel of the odd last
+  // step.  Empty where no stream kernel runs (no fuse2, or LDS tiles on a periodic slab).
+  printf("],\"stream_rows\":[");
+  if (p.fuse2 && !(p.tile_steps && in.halo == lbm_plan::HALO_SELF)) {
+    static const char* const family[] = {"step2_stream", "stepk_stream", "stepk_pk", "stepk_pk1"};
+    for (int i = 0; i < 2; i++) {
+      const lbm_plan::StreamRow r = lbm_plan::stream_row(p, i == 0 ? p.pass_steps : 2, true);
+      printf("{\"family\":\"%s\",\"math\":%d,\"nts\":%d,\"lane_cells\":%d,\"k\":%d,\"prefetch\":%d,\"lds\":%d},", family[r.family],
+             r.math, r.nts, r.lane_cells, r.k, r.prefetch, r.lds);
+    }
+    printf("{\"family\":\"%s\",\"math\":0,\"nts\":%d,\"neigh\":%d}", p.vec4 ? "step_vec4" : "step_scalar", p.nts, p.neigh);
   }
   printf("]}\n");
   return 0;

@@ -1,6 +1,6 @@
 """tests/plan_dump.cpp as a stand-alone checked binary: what lbm_plan.h (plan_kernels, slab_rows) decides for one
 context, asked from Python.  Host arithmetic only -- shared by the CPU test that pins the plans
-(test_kernel_plan.py) and the GPU test that compares them with what a created context reports (test_gpu_plan.py).
+(test_kernel_plan.py), the CPU test that ties every exact stream-kernel row to a GPU case (test_stream_rows.py) and the GPU test that compares them with what a created context reports (test_gpu_plan.py).
 """
 import json
 import os
@@ -24,7 +24,8 @@ def build(directory) -> str:
 
 
 def run(exe, *, nx, ny, world=1, rank=0, n_slabs=1, halo=0, cus, n_devices=1, distinct_devices=0, env=None) -> dict:
-    """One plan, in a child process whose only LBM_* variables are `env`.  Returns {"plan": {...}, "slabs": [...]}."""
+    """One plan, in a child process whose only LBM_* variables are `env`.  Returns {"plan": {...}, "slabs": [...],
+    "stream_rows": [...]}."""
     child_env = {k: v for k, v in os.environ.items() if not k.startswith("LBM_")}
     child_env.update(env or {})
     args = [nx, ny, world, rank, n_slabs, halo, cus, n_devices, int(distinct_devices)]

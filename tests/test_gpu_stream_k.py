@@ -25,10 +25,23 @@ def force_stream(monkeypatch, k, band, prefetch=0, chunk=0, stepk=1, packed=None
 
 
 # (timesteps per pass, arithmetic: 0 scalar / 1 pairs / 11, 12 pairs with 1, 2 windows in LDS, band height, prefetch, XCD chunk)
-STREAM_VARIANTS = [(2, 0, 2, 0, 0), (2, 0, 7, 1, 3), (3, 0, 5, 0, 3), (3, 0, 64, 1, 1), (4, 0, 3, 0, 2), (4, 0, 7, 1, 0),
-                   (2, 1, 3, 1, 2), (2, 11, 5, 0, 0), (3, 1, 2, 0, 0), (3, 1, 7, 1, 0), (3, 12, 5, 0, 3), (3, 12, 64, 1, 1),
-                   (4, 1, 2, 0, 0), (4, 1, 5, 0, 3), (4, 11, 7, 1, 0), (4, 11, 3, 0, 2), (4, 12, 2, 1, 0), (4, 12, 7, 1, 0),
-                   (4, 12, 64, 1, 1), (4, 12, 5, 1, 3)]
+# The tuples say what runs.  The data set is 128 cells wide, one strip, and plan_kernels drops an XCD chunk larger than the
+# row's strips: the eight variants that once asked for chunks of 2 or 3 strips always ran with chunk 0 and now say so.
+# K = 4 prefetches only in the packed kernel with two windows in LDS, so the two K = 4 variants that asked for prefetch
+# without them say 0 as well.  The same kernels run as before; _variant keeps the test ids these cases have always had.
+# Chunks that are kept, several strips, ragged chunks and every row of the exact dispatch tables: tests/stream_rows.py,
+# tests/test_gpu_stream_rows.py.
+def _variant(k, packed, band, prefetch, chunk, asked=None):
+    return pytest.param(k, packed, band, prefetch, chunk, id="-".join(str(x) for x in (asked or (k, packed, band, prefetch, chunk))))
+
+
+STREAM_VARIANTS = [_variant(2, 0, 2, 0, 0), _variant(2, 0, 7, 1, 0, asked=(2, 0, 7, 1, 3)), _variant(3, 0, 5, 0, 0, asked=(3, 0, 5, 0, 3)),
+                   _variant(3, 0, 64, 1, 1), _variant(4, 0, 3, 0, 0, asked=(4, 0, 3, 0, 2)), _variant(4, 0, 7, 0, 0, asked=(4, 0, 7, 1, 0)),
+                   _variant(2, 1, 3, 1, 0, asked=(2, 1, 3, 1, 2)), _variant(2, 11, 5, 0, 0), _variant(3, 1, 2, 0, 0), _variant(3, 1, 7, 1, 0),
+                   _variant(3, 12, 5, 0, 0, asked=(3, 12, 5, 0, 3)), _variant(3, 12, 64, 1, 1), _variant(4, 1, 2, 0, 0),
+                   _variant(4, 1, 5, 0, 0, asked=(4, 1, 5, 0, 3)), _variant(4, 11, 7, 0, 0, asked=(4, 11, 7, 1, 0)),
+                   _variant(4, 11, 3, 0, 0, asked=(4, 11, 3, 0, 2)), _variant(4, 12, 2, 1, 0), _variant(4, 12, 7, 1, 0),
+                   _variant(4, 12, 64, 1, 1), _variant(4, 12, 5, 1, 0, asked=(4, 12, 5, 1, 3))]
 
 
 @pytest.mark.parametrize("k,packed,band,prefetch,chunk", STREAM_VARIANTS)
