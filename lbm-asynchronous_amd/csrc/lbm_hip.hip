@@ -9,6 +9,7 @@
 #include "lbm_own.h"
 #include "lbm_plan.h"
 #include "lbm_ring.h"
+#include "lbm_segments.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -493,17 +494,18 @@ struct lbm_ctx {
                                     // mean fields (lbm_set_mean) or field frames (lbm_set_field_frames)
   std::vector<lbm_probe> probe_cells;  // the probed global cells, in the caller's order (a probes row has that many samples)
   std::vector<int> force_link_counts;  // lbm_set_forces: boundary links of each body, all slabs (a forces row has that many bodies)
-  // steady-state runs (lbm_run_until), allocated by the first such call in this order: whole once ev_steady[1] exists
-  DeviceBuf<lbm::SteadyState> steady_state;  // device: what the checks of the current call have found
-  PinnedBuf<int> steady_stop_host;  // pinned: its stop word after segment j, in slot j & 1 ...
+  // checked runs (checked_run: lbm_run_until, lbm_run_until_residual), allocated by the first one in this order (steady_buffers):
+  // whole once ev_steady[1] exists
+  DeviceBuf<lbm::SteadyState> steady_state;  // device: the stop word of the current call (and what the average-velocity checks have found)
+  PinnedBuf<int> steady_stop_host;  // pinned: the stop word after segment j, in slot j & 1 ...
   Event ev_steady[2];               // ... behind these events
-  // residual-steady runs (lbm_run_until_residual), allocated by the first such call and kept; the stop word, its pinned
-  // pair and the events are those above.  The planes are the call's own: the recorder never sees them.
+  // the residual criterion's own set, allocated by the first lbm_run_until_residual and kept (until_state last: whole once
+  // it exists).  The planes are the call's own: the recorder never sees them.
   DeviceBuf<float> until_planes;                    // device: [2][rows][nx]: the remembered u_x and u_y of slab 0
   DeviceBuf<long long> until_words;                 // device: [lbm_residual::kResidualWords]: the sample of the current segment
-  DeviceBuf<lbm_residual::UntilState> until_state;  // device: what the checks of the current call have found (allocated last)
+  DeviceBuf<lbm_residual::UntilState> until_state;  // device: what the checks of the current call have found
   DeviceBuf<long long> until_history;               // device: [until_history_rows][kResidualWords]: the words of the first checks
-  size_t until_history_rows = 0;
+  size_t until_history_rows = 0;                    // (until_history_begin: kept from call to call while they suffice)
 };
 
 // B independent single-slab lattices of one shape on one device, advanced together (lbm_create_batch).  The members
@@ -541,18 +543,17 @@ struct lbm_batch {
   std::vector<DeviceBuf<unsigned>> force_links;  // [members]: the member's boundary links, by body, cell, k ...
   std::vector<DeviceBuf<unsigned>> force_starts; // ... and [bodies + 1]: where each body's links start
   DeviceBuf<lbm::ForceMember> force_lists;       // device: [members], those pointers
-  // steady-state runs (lbm_batch_run_until), allocated by the first such call; steady_state last: the set is whole once it exists
-  DeviceBuf<lbm::SteadyMember> steady_members; // device: [members]
-  DeviceBuf<lbm::SteadyBatch> steady_batch;    // device
+  // checked runs (checked_batch_run: lbm_batch_run_until, lbm_batch_run_until_residual), allocated by the first one in
+  // this order (steady_batch_buffers): whole once ev_steady exists
+  DeviceBuf<lbm::SteadyBatch> steady_batch;  // device: the count of finished members and all_steady, the stop word
   PinnedBuf<int> steady_stop_host;  // pinned: all_steady after the last segment ...
   Event ev_steady;                  // ... behind this event
-  DeviceBuf<lbm::SteadyState> steady_state;    // device: [members]
-  // residual-steady runs (lbm_batch_run_until_residual), allocated by the first such call and kept; until_state last
+  // the average-velocity criterion's own set (lbm_batch_run_until); steady_state last: whole once it exists
+  DeviceBuf<lbm::SteadyMember> steady_members;  // device: [members]
+  DeviceBuf<lbm::SteadyState> steady_state;     // device: [members]
+  // the residual criterion's own set (lbm_batch_run_until_residual), kept; until_state last: whole once it exists
   DeviceBuf<float> until_planes;                    // device: [members][2][rows][nx]
   DeviceBuf<long long> until_words;                 // device: [members][lbm_residual::kResidualWords]
-  DeviceBuf<lbm::SteadyBatch> until_batch;          // device: the count of finished members
-  PinnedBuf<int> until_stop_host;                   // pinned: all_steady after the last segment ...
-  Event ev_until;                                   // ... behind this event
   DeviceBuf<lbm_residual::UntilState> until_state;  // device: [members]
   DeviceBuf<long long> until_history;               // device: [until_history_rows][members][kResidualWords]
   size_t until_history_rows = 0;
@@ -1613,20 +1614,22 @@ void launch_stats_gather(const lbm_ctx* c, const Slab& sl, long long* words) {
     hipLaunchKernelGGL(lbm::stats_gather<1>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, words);
 }
 
-// one residual sample of a slab's current lattice against its planes into `words` (zeroed in front, on the same stream);
-// baseline: the planes are filled from the lattice and nothing is reduced (arming)
-void launch_residual_gather(const lbm_ctx* c, const Slab& sl, long long* words, bool baseline) {
+// one residual sample of a slab's current lattice against `planes` ([2][rows][nx]: the recorder's, or a checked run's
+// own) into `words` (zeroed in front, on the same stream); baseline: the planes are filled from the lattice and nothing
+// is reduced.  With a gate the sample stands back once the gate's stop word is set (residual_gather_unless).
+void launch_residual_gather(const lbm_ctx* c, const Slab& sl, float* planes, long long* words, bool baseline,
+                            const lbm::SteadyState* gate = nullptr) {
   const int v = stats_vector(c->p.nx);
-  const dim3 grid(stats_groups((long)sl.rows * c->p.nx, v));
+  const dim3 grid(stats_groups((long)sl.rows * c->p.nx, v)), block(lbm::kBlock);
   const unsigned cell_first = (unsigned)sl.row_first * (unsigned)c->p.nx;
-  float* px = sl.residual_planes;
+  float* px = planes;
   float* py = px + (size_t)sl.rows * c->p.nx;
-  if (v == 4)
-    hipLaunchKernelGGL(lbm::residual_gather<4>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, px, py, words,
-                       (int)baseline);
+  if (gate)
+    hipLaunchKernelGGL(v == 4 ? lbm::residual_gather_unless<4> : lbm::residual_gather_unless<1>, grid, block, 0, sl.compute, lattice_args(c, sl),
+                       sl.rows, cell_first, px, py, words, gate);
   else
-    hipLaunchKernelGGL(lbm::residual_gather<1>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, px, py, words,
-                       (int)baseline);
+    hipLaunchKernelGGL(v == 4 ? lbm::residual_gather<4> : lbm::residual_gather<1>, grid, block, 0, sl.compute, lattice_args(c, sl), sl.rows,
+                       cell_first, px, py, words, (int)baseline);
 }
 
 // rows of a band of profile_columns / profile_columns_batch for `rows` rows of nx cells: about kProfileTargetGroups
@@ -1733,7 +1736,7 @@ int take_record(lbm_ctx* c) {
         } else if (c->rec.kind == kRecStats)
           launch_stats_gather(c, sl, words);
         else if (c->rec.kind == kRecResidual)
-          launch_residual_gather(c, sl, words, false);  // also replaces the slab's remembered field by this lattice's
+          launch_residual_gather(c, sl, sl.residual_planes, words, false);  // also replaces the slab's remembered field by this lattice's
         else if (c->rec.kind == kRecProfiles)
           launch_profiles(c, sl, words);  // (profile_rows leaves a line's spare word as zeroed)
         else if (c->rec.kind == kRecMean)
@@ -3401,7 +3404,7 @@ int lbm_set_residual(lbm_ctx* c, int every, int capacity) {
     for (int s = 0; s < c->n_slabs; s++) {
       Slab& sl = c->slab[s];
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      launch_residual_gather(c, sl, nullptr, true);
+      launch_residual_gather(c, sl, sl.residual_planes, nullptr, true);
       HIP_TRY(LBM_FAILURE, hipGetLastError());
     }
     return LBM_SUCCESS;
@@ -4159,8 +4162,11 @@ int lbm_batch_read_profiles(lbm_batch* bt, int max_records, lbm_profile_line* ou
   });
 }
 
-// ---- steady-state runs ---------------------------------------------------------------------------------------------
-// argument checks shared by lbm_run_until and lbm_batch_run_until (no device needed)
+// ---- checked runs: to steady state on the average velocity (lbm_run_until) or the velocity residual (..._residual) ----
+// A checked run is segments of check_every steps, each followed by its criterion's check, which sets a stop word on the
+// device that travels to the host; checked_run drives a context, checked_batch_run a batch, and an entry point adds its
+// criterion: what starts a call (begin), the launches of one check, and the result.
+// argument checks shared by the four entry points (no device needed)
 static int steady_args_ok(const char* who, int steps_done, int capacity, int max_steps, int check_every, double tol, int patience) {
   if (max_steps < 0) LBM_FAIL(LBM_FAILURE, "%s: negative step count", who);
   if ((long long)steps_done + max_steps > capacity)
@@ -4191,93 +4197,167 @@ static int steady_buffers(lbm_ctx* c) {
   return LBM_SUCCESS;
 }
 
-// One segment of a resident lbm_run_until call: what lbm_run issues for `n` steps (first-step acceleration, the launches
-// of run_resident with accel_last = 0 on the last one), except that the acceleration stands back once the checks have
-// said "stop"; then the check of the segment and its stop word on the way to slot `slot` of the pinned pair.
-static int steady_segment_resident(lbm_ctx* c, int n, int slot, double tol, int patience, int steps_after) {
+// ... and of a batch: the finished-count with its stop word (all_steady), the pinned copy and its event
+static int steady_batch_buffers(lbm_batch* bt) {
+  if (bt->ev_steady) return LBM_SUCCESS;  // created last: the set is whole (an attempt that failed half-way starts again)
+  HIP_TRY(LBM_FAILURE, bt->steady_batch.alloc(1));
+  HIP_TRY(LBM_FAILURE, bt->steady_stop_host.alloc(1));
+  HIP_TRY(LBM_FAILURE, bt->ev_steady.create(hipEventDisableTiming));
+  return LBM_SUCCESS;
+}
+
+// the verdict of the runtime on the launches in front
+static int launched() {
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+
+// a stop word on its way to the host behind a check: 4 bytes into a pinned slot, and the event that says they are there
+static int post_stop_word(const int* word, int* slot, hipEvent_t ev, hipStream_t stream) {
+  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(slot, word, sizeof(int), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(LBM_FAILURE, hipEventRecord(ev, stream));
+  return LBM_SUCCESS;
+}
+static int wait_stop_word(hipEvent_t ev, const int* slot, bool* stop) {
+  HIP_TRY(LBM_FAILURE, hipEventSynchronize(ev));
+  *stop = *slot != 0;
+  return LBM_SUCCESS;
+}
+
+// no recorder of a context (or batch member) may be armed in a checked run
+static int steady_recorder_off(const lbm_ctx* c, const char* who) {
+  if (c->rec.kind == kRecNone) return LBM_SUCCESS;
+  const RecorderKind& k = kRecorderKinds[c->rec.kind];
+  LBM_FAIL(LBM_FAILURE, kSteadyRecorder, who, k.name, k.setter, k.noun);
+}
+
+// what `who` refuses of a context before any work (no device needed); `noun`: what its check reads of the one slab
+static int checked_ctx_ok(const lbm_ctx* c, const char* who, const char* noun, int max_steps, int check_every, double tol, int patience) {
+  if (c->batch) LBM_FAIL(LBM_FAILURE, kMemberRun, who);
+  if (steady_args_ok(who, c->steps_done, c->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
+  if (steady_recorder_off(c, who) != LBM_SUCCESS) return LBM_FAILURE;
+  if (c->halo_mode != LBM_HALO_SYNC) LBM_FAIL(LBM_FAILURE, "%s: only LBM_HALO_SYNC runs can be checked (the halo mode is %d)", who, c->halo_mode);
+  if (c->ranked || c->world > 1)
+    LBM_FAIL(LBM_FAILURE, "%s: not available in a multi-process context (every rank would have to take the same decision)", who);
+  if (c->n_slabs != 1)
+    LBM_FAIL(LBM_FAILURE, "%s: the context has %d slabs; the check reads one slab's %s (single-slab contexts only)", who, c->n_slabs, noun);
+  return LBM_SUCCESS;
+}
+// ... and of a batch
+static int checked_batch_ok(const lbm_batch* bt, const char* who, int max_steps, int check_every, double tol, int patience) {
+  if (steady_args_ok(who, bt->steps_done, bt->members[0]->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
+  for (const lbm_ctx* c : bt->members)
+    if (steady_recorder_off(c, who) != LBM_SUCCESS) return LBM_FAILURE;
+  if (bt->rec.kind != kRecNone)  // forces, statistics, residuals or profiles armed on the batch
+    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, who, kRecorderKinds[bt->rec.kind].name, batch_kind(bt->rec.kind)->setter,
+             kRecorderKinds[bt->rec.kind].noun);
+  return LBM_SUCCESS;
+}
+
+// The E steps of one segment of a context.  On the resident path what lbm_run issues for them (first-step acceleration, the
+// launches of run_resident with accel_last = 0 on the last one), except that the acceleration stands back once a check has
+// said "stop" (accelerate_row_unless); else the passes of lbm_run.  Slab 0's device is current afterwards.
+static int issue_segment(lbm_ctx* c, bool resident, int E) {
   Slab& sl = c->slab[0];
+  if (!resident && run_passes(c, E, false, false) != LBM_SUCCESS) return LBM_FAILURE;
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+  if (!resident) return LBM_SUCCESS;
   const AccelWeights w = accel_weights(c->p);
   hipLaunchKernelGGL(lbm::accelerate_row_unless, dim3(ceil_div(c->p.nx, 256)), dim3(256), 0, sl.compute,
                      lattice_args(c, sl, c->cur, c->cur), sl.accel_row, w.a1, w.a2, (const lbm::SteadyState*)c->steady_state);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
-  if (run_resident(c, n) != LBM_SUCCESS) return LBM_FAILURE;
-  hipLaunchKernelGGL(lbm::steady_check, dim3(1), dim3(64), 0, sl.compute, (const double*)sl.tot_u, c->steps_done, n,
-                     (float)c->fluid_cells, tol, patience, steps_after, c->steady_state);
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  c->steps_done += n;
-  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(c->steady_stop_host + slot, &c->steady_state.get()->stop, sizeof(int), hipMemcpyDeviceToHost, sl.compute));
-  HIP_TRY(LBM_FAILURE, hipEventRecord(c->ev_steady[slot], sl.compute));
+  if (run_resident(c, E) != LBM_SUCCESS) return LBM_FAILURE;
+  c->steps_done += E;
   return LBM_SUCCESS;
 }
 
-int lbm_run_until(lbm_ctx* c, int max_steps, int check_every, double tol, int patience, lbm_steady_result* out) {
-  if (!c || !out) LBM_FAIL(LBM_FAILURE, "lbm_run_until: NULL argument");
-  if (c->batch) LBM_FAIL(LBM_FAILURE, kMemberRun, "lbm_run_until");
-  if (steady_args_ok("lbm_run_until", c->steps_done, c->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS)
-    return LBM_FAILURE;
-  if (c->rec.kind != kRecNone) {
-    const RecorderKind& k = kRecorderKinds[c->rec.kind];
-    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_run_until", k.name, k.setter, k.noun);
-  }
-  if (c->halo_mode != LBM_HALO_SYNC)
-    LBM_FAIL(LBM_FAILURE, "lbm_run_until: only LBM_HALO_SYNC runs can be checked (the halo mode is %d)", c->halo_mode);
-  if (c->ranked || c->world > 1)
-    LBM_FAIL(LBM_FAILURE, "lbm_run_until: not available in a multi-process context (every rank would have to take the same decision)");
-  if (c->n_slabs != 1)
-    LBM_FAIL(LBM_FAILURE, "lbm_run_until: the context has %d slabs; the check reads one slab's sums (single-slab contexts only)", c->n_slabs);
-
+// One checked run of a context that checked_ctx_ok has passed: begin() starts the criterion (its buffers, its reset
+// launches behind steady_reset, its baseline), check(index, first) launches the check of segment `index`, whose steps
+// began at step `first`; the check sets SteadyState::stop when the run is to end.  The call's steps are run and waited for
+// when this returns; the caller reads its criterion's state.
+static int checked_run(lbm_ctx* c, int max_steps, int E, const std::function<int()>& begin, const std::function<int(int, int)>& check) {
   Slab& sl = c->slab[0];
   HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
   if (steady_buffers(c) != LBM_SUCCESS) return LBM_FAILURE;
   hipLaunchKernelGGL(lbm::steady_reset, dim3(1), dim3(64), 0, sl.compute, c->steady_state, 1, (lbm::SteadyBatch*)nullptr);
   HIP_TRY(LBM_FAILURE, hipGetLastError());
+  if (begin() != LBM_SUCCESS) return LBM_FAILURE;
 
-  const int E = check_every, n_seg = max_steps / E, start = c->steps_done;
+  const int n_seg = max_steps / E;
   const bool resident = c->plan.resident && E >= c->plan.resident_min_steps;
   // One segment of look-ahead where a segment is ONE launch of the resident kernel: it reads the lattice the segment in
-  // front left and writes the other one, so dropping it is `cur ^= 1`.  A longer segment (several launches, which would
-  // write both lattices) runs for milliseconds; there the host waits for each verdict first, as on the per-pass path.
+  // front left and writes the other one, so dropping it is one flip of `cur`.  A longer segment (several launches, which
+  // would write both lattices) runs for milliseconds; there the host waits for each verdict first, as on the per-pass path.
   const int depth = (resident && E <= kResidentChunk) ? 2 : 1;
-  int issued = 0, judged = 0;
-  bool steady = false;
-  while (judged < n_seg && !steady) {
-    while (issued < n_seg && issued - judged < depth) {
-      const int after = (issued + 1) * E;
-      if (resident) {
-        if (steady_segment_resident(c, E, issued & 1, tol, patience, after) != LBM_SUCCESS) return LBM_FAILURE;
-      } else {
-        const int first = c->steps_done;
-        if (run_passes(c, E, false, false) != LBM_SUCCESS) return LBM_FAILURE;
-        HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-        hipLaunchKernelGGL(lbm::steady_check, dim3(1), dim3(64), 0, sl.compute, (const double*)sl.tot_u, first, E,
-                           (float)c->fluid_cells, tol, patience, after, c->steady_state);
-        HIP_TRY(LBM_FAILURE, hipGetLastError());
-        HIP_TRY(LBM_FAILURE, hipMemcpyAsync(c->steady_stop_host + (issued & 1), &c->steady_state.get()->stop, sizeof(int),
-                                            hipMemcpyDeviceToHost, sl.compute));
-        HIP_TRY(LBM_FAILURE, hipEventRecord(c->ev_steady[issued & 1], sl.compute));
-      }
-      issued++;
-    }
-    HIP_TRY(LBM_FAILURE, hipEventSynchronize(c->ev_steady[judged & 1]));
-    steady = c->steady_stop_host[judged & 1] != 0;
-    judged++;
-    if (resident && *sl.res_status_host != 0) break;  // a launch gave up (its status travels in front of the stop word): lbm_sync below reports it
-  }
-  if (issued > judged) {
+  int waited = LBM_SUCCESS;
+  const auto issue = [&](int index) {  // the segment, its check, and the stop word on its way to slot index & 1 of the pinned pair
+    const int first = c->steps_done, slot = index & 1;
+    return issue_segment(c, resident, E) == LBM_SUCCESS && check(index, first) == LBM_SUCCESS &&
+           post_stop_word(&c->steady_state.get()->stop, c->steady_stop_host + slot, c->ev_steady[slot], sl.compute) == LBM_SUCCESS;
+  };
+  const auto judge = [&](int index) {
+    bool stop = false;
+    if ((waited = wait_stop_word(c->ev_steady[index & 1], c->steady_stop_host + (index & 1), &stop)) != LBM_SUCCESS) return lbm_segments::kBreak;
+    if (stop) return lbm_segments::kStop;
+    // a launch gave up (its status travels in front of the stop word): lbm_sync below reports it
+    return resident && *sl.res_status_host != 0 ? lbm_segments::kBreak : lbm_segments::kGoOn;
+  };
+  const lbm_segments::Outcome o = lbm_segments::run(n_seg, depth, issue, judge);
+  if (o.failed || waited != LBM_SUCCESS) return LBM_FAILURE;
+  if (o.issued > o.judged) {
     // The look-ahead segment is dropped: its acceleration did not happen (accelerate_row_unless), its one launch wrote
-    // the other lattice, its check changed nothing, and its tot_u entries lie beyond steps_done.  Its seam granules
-    // carry the tags of steps that will be run again, so they are cleared as at creation.
+    // the other lattice, everything enqueued behind that launch -- a sample, the check -- read the stop word first and
+    // changed nothing, and its tot_u entries lie beyond steps_done.  Its seam granules carry the tags of steps that will
+    // be run again, so they are cleared as at creation.
     c->cur ^= 1;
     c->steps_done -= E;
     HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.res_gran, 0, resident_gran_bytes(c), sl.compute));
   }
-  if (!steady && max_steps - n_seg * E > 0) {
+  if (!o.stopped && max_steps - n_seg * E > 0) {
     // the rest of the cap, shorter than a segment: run as lbm_run runs it, not checked
     const int rest = max_steps - n_seg * E;
     if (run_passes(c, rest, c->plan.resident && rest >= c->plan.resident_min_steps, false) != LBM_SUCCESS) return LBM_FAILURE;
   }
-  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;  // also reports a resident give-up
+  return lbm_sync(c);  // also reports a resident give-up
+}
+
+// One checked run of a batch that checked_batch_ok has passed, with begin() and check() as for a context; the checks set
+// SteadyBatch::all_steady once every member has finished.  Per segment the launches of lbm_batch_run, then the check; the
+// host waits for each verdict (a dropped segment of B lattices would cost more than the wait), which is the loop of
+// lbm_segments::run at depth 1.  Finished members keep stepping with the others, so every whole segment that ran was checked.
+static int checked_batch_run(lbm_batch* bt, int max_steps, int E, const std::function<int()>& begin, const std::function<int(int, int)>& check) {
+  const int device = bt->members[0]->slab[0].device;
+  HIP_TRY(LBM_FAILURE, hipSetDevice(device));
+  if (steady_batch_buffers(bt) != LBM_SUCCESS) return LBM_FAILURE;
+  if (begin() != LBM_SUCCESS) return LBM_FAILURE;
+  const int n_seg = max_steps / E;
+  bool stop = false;
+  for (int index = 0; index < n_seg && !stop; index++) {
+    const int first = bt->steps_done;
+    if (lbm_batch_run(bt, E) != LBM_SUCCESS) return LBM_FAILURE;
+    HIP_TRY(LBM_FAILURE, hipSetDevice(device));
+    if (check(index, first) != LBM_SUCCESS) return LBM_FAILURE;
+    if (post_stop_word(&bt->steady_batch.get()->all_steady, bt->steady_stop_host, bt->ev_steady, bt->stream) != LBM_SUCCESS) return LBM_FAILURE;
+    if (wait_stop_word(bt->ev_steady, bt->steady_stop_host, &stop) != LBM_SUCCESS) return LBM_FAILURE;
+  }
+  if (!stop && max_steps - n_seg * E > 0 && lbm_batch_run(bt, max_steps - n_seg * E) != LBM_SUCCESS) return LBM_FAILURE;
+  return lbm_batch_sync(bt);
+}
+
+// ---- ... on the average velocity: the check reads the segment's tot_u entries; SteadyState holds its state too
+int lbm_run_until(lbm_ctx* c, int max_steps, int check_every, double tol, int patience, lbm_steady_result* out) {
+  static const char who[] = "lbm_run_until";
+  if (!c || !out) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", who);
+  if (checked_ctx_ok(c, who, "sums", max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
+  const Slab& sl = c->slab[0];
+  const int E = check_every, start = c->steps_done;
+  const auto begin = [] { return LBM_SUCCESS; };  // steady_reset has done it
+  const auto check = [&](int index, int first) {
+    hipLaunchKernelGGL(lbm::steady_check, dim3(1), dim3(64), 0, sl.compute, (const double*)sl.tot_u, first, E, (float)c->fluid_cells, tol,
+                       patience, (index + 1) * E, c->steady_state);
+    return launched();
+  };
+  if (checked_run(c, max_steps, E, begin, check) != LBM_SUCCESS) return LBM_FAILURE;
   lbm::SteadyState st;
   HIP_TRY(LBM_FAILURE, hipMemcpy(&st, c->steady_state, sizeof(st), hipMemcpyDeviceToHost));
   steady_fill(out, st, c->steps_done - start);
@@ -4286,55 +4366,29 @@ int lbm_run_until(lbm_ctx* c, int max_steps, int check_every, double tol, int pa
 
 int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double tol, int patience, lbm_steady_result* out,
                         int* steps_run) {
-  if (!bt || !out || !steps_run) LBM_FAIL(LBM_FAILURE, "lbm_batch_run_until: NULL argument");
-  lbm_ctx* c0 = bt->members[0];
-  const int n_members = (int)bt->members.size();
-  if (steady_args_ok("lbm_batch_run_until", bt->steps_done, c0->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS)
-    return LBM_FAILURE;
-  for (const lbm_ctx* c : bt->members) {
-    if (c->rec.kind != kRecNone) {
-      const RecorderKind& k = kRecorderKinds[c->rec.kind];
-      LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_batch_run_until", k.name, k.setter, k.noun);
+  static const char who[] = "lbm_batch_run_until";
+  if (!bt || !out || !steps_run) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", who);
+  if (checked_batch_ok(bt, who, max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
+  const int n_members = (int)bt->members.size(), E = check_every, start = bt->steps_done;
+  const auto begin = [&]() -> int {
+    if (!bt->steady_state) {  // allocated last: the set is whole (an attempt that failed half-way starts again)
+      std::vector<lbm::SteadyMember> h((size_t)n_members);
+      for (int i = 0; i < n_members; i++) h[(size_t)i] = {bt->members[(size_t)i]->slab[0].tot_u, (float)bt->members[(size_t)i]->fluid_cells};
+      HIP_TRY(LBM_FAILURE, bt->steady_members.alloc(h.size()));
+      HIP_TRY(LBM_FAILURE, hipMemcpy(bt->steady_members, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice));
+      HIP_TRY(LBM_FAILURE, bt->steady_state.alloc((size_t)n_members));
     }
-  }
-  if (bt->rec.kind != kRecNone)  // forces, statistics or residuals armed on the batch
-    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, "lbm_batch_run_until", kRecorderKinds[bt->rec.kind].name, batch_kind(bt->rec.kind)->setter,
-             kRecorderKinds[bt->rec.kind].noun);
-
-  HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
-  if (!bt->steady_state) {  // allocated last: the set is whole (an attempt that failed half-way starts again)
-    std::vector<lbm::SteadyMember> h((size_t)n_members);
-    for (int i = 0; i < n_members; i++) h[(size_t)i] = {bt->members[(size_t)i]->slab[0].tot_u, (float)bt->members[(size_t)i]->fluid_cells};
-    HIP_TRY(LBM_FAILURE, bt->steady_members.alloc(h.size()));
-    HIP_TRY(LBM_FAILURE, hipMemcpy(bt->steady_members, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice));
-    HIP_TRY(LBM_FAILURE, bt->steady_batch.alloc(1));
-    HIP_TRY(LBM_FAILURE, bt->steady_stop_host.alloc(1));
-    HIP_TRY(LBM_FAILURE, bt->ev_steady.create(hipEventDisableTiming));
-    HIP_TRY(LBM_FAILURE, bt->steady_state.alloc((size_t)n_members));
-  }
-  hipLaunchKernelGGL(lbm::steady_reset, dim3(ceil_div(n_members, 64)), dim3(64), 0, bt->stream, bt->steady_state, n_members,
-                     bt->steady_batch);
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-
-  // the launches of lbm_batch_run per segment, then one check of every member; the host waits for each verdict (a
-  // dropped segment of B lattices would cost more than the wait).  Steady members keep stepping with the others.
-  const int E = check_every, n_seg = max_steps / E, start = bt->steps_done;
-  bool steady = false;
-  for (int j = 0; j < n_seg && !steady; j++) {
-    const int first = bt->steps_done;
-    if (lbm_batch_run(bt, E) != LBM_SUCCESS) return LBM_FAILURE;
-    HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
+    hipLaunchKernelGGL(lbm::steady_reset, dim3(ceil_div(n_members, 64)), dim3(64), 0, bt->stream, bt->steady_state, n_members,
+                       bt->steady_batch);
+    return launched();
+  };
+  const auto check = [&](int index, int first) {  // one check of every member
     hipLaunchKernelGGL(lbm::steady_check_batch, dim3(n_members), dim3(64), 0, bt->stream,
-                       (const lbm::SteadyMember*)bt->steady_members, n_members, first, E, tol, patience, (j + 1) * E,
+                       (const lbm::SteadyMember*)bt->steady_members, n_members, first, E, tol, patience, (index + 1) * E,
                        bt->steady_state, bt->steady_batch);
-    HIP_TRY(LBM_FAILURE, hipGetLastError());
-    HIP_TRY(LBM_FAILURE, hipMemcpyAsync(bt->steady_stop_host, &bt->steady_batch.get()->all_steady, sizeof(int), hipMemcpyDeviceToHost, bt->stream));
-    HIP_TRY(LBM_FAILURE, hipEventRecord(bt->ev_steady, bt->stream));
-    HIP_TRY(LBM_FAILURE, hipEventSynchronize(bt->ev_steady));
-    steady = *bt->steady_stop_host != 0;
-  }
-  if (!steady && max_steps - n_seg * E > 0 && lbm_batch_run(bt, max_steps - n_seg * E) != LBM_SUCCESS) return LBM_FAILURE;
-  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
+    return launched();
+  };
+  if (checked_batch_run(bt, max_steps, E, begin, check) != LBM_SUCCESS) return LBM_FAILURE;
   std::vector<lbm::SteadyState> st((size_t)n_members);
   HIP_TRY(LBM_FAILURE, hipMemcpy(st.data(), bt->steady_state, st.size() * sizeof(st[0]), hipMemcpyDeviceToHost));
   *steps_run = bt->steps_done - start;
@@ -4342,15 +4396,38 @@ int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double to
   return LBM_SUCCESS;
 }
 
-// ---- residual-steady runs ------------------------------------------------------------------------------------------
-// the history arguments of lbm_run_until_residual and its batch twin (no device needed): *rows = rows kept on the device
-static int until_history_ok(const char* who, const void* history, int history_capacity, int n_seg, size_t n_members, size_t* rows) {
+// ---- ... on the velocity residual: the check reads a sample of the lattice against the planes of the check before ----
+// The history of a call on a context (bt null: one lattice) or on a batch: its arguments (no device needed; *rows = rows
+// kept on the device), then room for them in `words` (`have` rows so far) on `device`, kept while it suffices.
+static int until_history_begin(const char* who, DeviceBuf<long long>& words, size_t& have, const void* history, int history_capacity,
+                               int n_seg, const lbm_batch* bt, int device, size_t* rows) {
   if (history_capacity < 0) LBM_FAIL(LBM_FAILURE, "%s: negative history capacity %d", who, history_capacity);
+  const size_t n_members = bt ? bt->members.size() : 1;
   *rows = history ? (size_t)(history_capacity < n_seg ? history_capacity : n_seg) : 0;
   constexpr size_t kRowBytes = lbm_residual::kResidualWords * sizeof(long long);
-  if (*rows * n_members * kRowBytes >= ((size_t)1 << 31))
+  const size_t bytes = *rows * n_members * kRowBytes;
+  if (bytes >= ((size_t)1 << 31))
     LBM_FAIL(LBM_FAILURE, "%s: a history of %zu rows of %zu lattices is %.2f GiB on the device, 2 GiB or more (%d bytes per lattice and row)", who,
-             *rows, n_members, (double)(*rows * n_members * kRowBytes) / 1073741824.0, (int)kRowBytes);
+             *rows, n_members, (double)bytes / 1073741824.0, (int)kRowBytes);
+  if (*rows <= have) return LBM_SUCCESS;
+  HIP_TRY(LBM_FAILURE, hipSetDevice(device));
+  have = 0;
+  if (words.alloc_bytes(bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    if (bt)
+      LBM_FAIL(LBM_FAILURE, "%s: cannot allocate a history of %zu rows of %zu members (%.1f MiB); nothing was run", who, *rows, n_members,
+               (double)bytes / 1048576.0);
+    LBM_FAIL(LBM_FAILURE, "%s: cannot allocate a history of %zu rows (%.1f MiB); nothing was run", who, *rows, (double)bytes / 1048576.0);
+  }
+  have = *rows;
+  return LBM_SUCCESS;
+}
+// its first n rows of one lattice each, formed from the words after the run
+static int until_history_read(const long long* device_words, size_t n, int nx, int span, lbm_residual_row* history) {
+  constexpr size_t kWords = lbm_residual::kResidualWords;
+  std::vector<long long> words(n * kWords);
+  if (n > 0) HIP_TRY(LBM_FAILURE, hipMemcpy(words.data(), device_words, words.size() * sizeof(long long), hipMemcpyDeviceToHost));
+  for (size_t j = 0; j < n; j++) history[j] = lbm_residual::residual_row_from_words(words.data() + j * kWords, 1, nx, span);
   return LBM_SUCCESS;
 }
 
@@ -4365,225 +4442,95 @@ static void until_fill(lbm_residual_steady_result* out, const lbm_residual::Unti
   out->last = lbm_residual::residual_row_from_words(st.last, 1, nx, st.checks > 0 ? span : 0);  // (no check: zeros at -1, -1)
 }
 
-// slab 0's current lattice against the call's planes: the baseline (residual_gather: the planes are filled), or a sample
-// into until_words that stands back once the stop word is set (residual_gather_unless)
-static void launch_until_gather(const lbm_ctx* c, const Slab& sl, bool baseline) {
-  const int v = stats_vector(c->p.nx);
-  const dim3 grid(stats_groups((long)sl.rows * c->p.nx, v)), block(lbm::kBlock);
-  const unsigned cell_first = (unsigned)sl.row_first * (unsigned)c->p.nx;
-  float* px = c->until_planes;
-  float* py = px + (size_t)sl.rows * c->p.nx;
-  long long* words = c->until_words;
-  const lbm::SteadyState* gate = c->steady_state;
-  if (baseline && v == 4)
-    hipLaunchKernelGGL(lbm::residual_gather<4>, grid, block, 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, px, py, words, 1);
-  else if (baseline)
-    hipLaunchKernelGGL(lbm::residual_gather<1>, grid, block, 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, px, py, words, 1);
-  else if (v == 4)
-    hipLaunchKernelGGL(lbm::residual_gather_unless<4>, grid, block, 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, px, py, words, gate);
-  else
-    hipLaunchKernelGGL(lbm::residual_gather_unless<1>, grid, block, 0, sl.compute, lattice_args(c, sl), sl.rows, cell_first, px, py, words, gate);
-}
-
-// One segment of an lbm_run_until_residual call, the `index`-th: its E steps -- on a resident shape as
-// steady_segment_resident issues them, with the acceleration standing back behind a stop; else as lbm_run does -- then
-// the sample of the lattice it left (standing back likewise), the check, and the stop word on its way to the pinned pair.
-static int until_segment(lbm_ctx* c, bool resident, int E, int index, size_t hist_rows, double tol, int patience) {
-  Slab& sl = c->slab[0];
-  const lbm::SteadyState* gate = c->steady_state;
-  if (resident) {
-    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-    const AccelWeights w = accel_weights(c->p);
-    hipLaunchKernelGGL(lbm::accelerate_row_unless, dim3(ceil_div(c->p.nx, 256)), dim3(256), 0, sl.compute,
-                       lattice_args(c, sl, c->cur, c->cur), sl.accel_row, w.a1, w.a2, gate);
-    HIP_TRY(LBM_FAILURE, hipGetLastError());
-    if (run_resident(c, E) != LBM_SUCCESS) return LBM_FAILURE;
-    c->steps_done += E;
-  } else {
-    if (run_passes(c, E, false, false) != LBM_SUCCESS) return LBM_FAILURE;
-    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-  }
-  launch_until_gather(c, sl, false);
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  long long* hist = (size_t)index < hist_rows ? c->until_history + (size_t)index * lbm_residual::kResidualWords : nullptr;
-  hipLaunchKernelGGL(lbm::residual_check, dim3(1), dim3(64), 0, sl.compute, c->until_words.get(), hist, tol, patience, (index + 1) * E,
-                     c->until_state.get(), c->steady_state.get());
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(c->steady_stop_host + (index & 1), &c->steady_state.get()->stop, sizeof(int), hipMemcpyDeviceToHost, sl.compute));
-  HIP_TRY(LBM_FAILURE, hipEventRecord(c->ev_steady[index & 1], sl.compute));
-  return LBM_SUCCESS;
-}
-
 int lbm_run_until_residual(lbm_ctx* c, int max_steps, int check_every, double tol, int patience, lbm_residual_steady_result* out,
                            lbm_residual_row* history, int history_capacity) {
   static const char who[] = "lbm_run_until_residual";
   if (!c || !out) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", who);
-  if (c->batch) LBM_FAIL(LBM_FAILURE, kMemberRun, who);
-  if (steady_args_ok(who, c->steps_done, c->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
-  if (c->rec.kind != kRecNone) {
-    const RecorderKind& k = kRecorderKinds[c->rec.kind];
-    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, who, k.name, k.setter, k.noun);
-  }
-  if (c->halo_mode != LBM_HALO_SYNC) LBM_FAIL(LBM_FAILURE, "%s: only LBM_HALO_SYNC runs can be checked (the halo mode is %d)", who, c->halo_mode);
-  if (c->ranked || c->world > 1)
-    LBM_FAIL(LBM_FAILURE, "%s: not available in a multi-process context (every rank would have to take the same decision)", who);
-  if (c->n_slabs != 1)
-    LBM_FAIL(LBM_FAILURE, "%s: the context has %d slabs; the check reads one slab's words (single-slab contexts only)", who, c->n_slabs);
-  const int E = check_every, n_seg = max_steps / E, start = c->steps_done;
+  if (checked_ctx_ok(c, who, "words", max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
+  const Slab& sl = c->slab[0];
+  const int E = check_every, start = c->steps_done;
   size_t hist_rows = 0;
-  if (until_history_ok(who, history, history_capacity, n_seg, 1, &hist_rows) != LBM_SUCCESS) return LBM_FAILURE;
-
-  Slab& sl = c->slab[0];
-  constexpr size_t kWords = lbm_residual::kResidualWords;
-  HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-  if (steady_buffers(c) != LBM_SUCCESS) return LBM_FAILURE;
-  if (!c->until_state) {  // allocated last: the set is whole
-    const size_t cells = (size_t)sl.rows * c->p.nx;
-    if (c->until_planes.alloc(2 * cells) != hipSuccess) {
-      (void)hipGetLastError();
-      LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the remembered field (%zu cells, %.1f MiB); nothing was run", who, cells,
-               (double)(2 * cells * sizeof(float)) / 1048576.0);
+  if (until_history_begin(who, c->until_history, c->until_history_rows, history, history_capacity, max_steps / E, nullptr, sl.device,
+                          &hist_rows) != LBM_SUCCESS)
+    return LBM_FAILURE;
+  const auto begin = [&]() -> int {
+    if (!c->until_state) {  // allocated last: the set is whole
+      const size_t cells = (size_t)sl.rows * c->p.nx;
+      if (c->until_planes.alloc(2 * cells) != hipSuccess) {
+        (void)hipGetLastError();
+        LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the remembered field (%zu cells, %.1f MiB); nothing was run", who, cells,
+                 (double)(2 * cells * sizeof(float)) / 1048576.0);
+      }
+      HIP_TRY(LBM_FAILURE, c->until_words.alloc(lbm_residual::kResidualWords));
+      HIP_TRY(LBM_FAILURE, c->until_state.alloc(1));
     }
-    HIP_TRY(LBM_FAILURE, c->until_words.alloc(kWords));
-    HIP_TRY(LBM_FAILURE, c->until_state.alloc(1));
-  }
-  if (hist_rows > c->until_history_rows) {
-    c->until_history_rows = 0;
-    if (c->until_history.alloc(hist_rows * kWords) != hipSuccess) {
-      (void)hipGetLastError();
-      LBM_FAIL(LBM_FAILURE, "%s: cannot allocate a history of %zu rows (%.1f MiB); nothing was run", who, hist_rows,
-               (double)(hist_rows * kWords * sizeof(long long)) / 1048576.0);
-    }
-    c->until_history_rows = hist_rows;
-  }
-  hipLaunchKernelGGL(lbm::steady_reset, dim3(1), dim3(64), 0, sl.compute, c->steady_state, 1, (lbm::SteadyBatch*)nullptr);
-  hipLaunchKernelGGL(lbm::residual_until_reset, dim3(1), dim3(64), 0, sl.compute, c->until_state.get(), c->until_words.get(), 1,
-                     (lbm::SteadyBatch*)nullptr);
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  launch_until_gather(c, sl, true);  // the baseline: the field of the current lattice into the call's planes
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-
-  // the segment loop of lbm_run_until, with its look-ahead (see there): everything a dropped segment enqueued behind its
-  // one launch -- the sample, the check -- reads the stop word first and changes nothing
-  const bool resident = c->plan.resident && E >= c->plan.resident_min_steps;
-  const int depth = (resident && E <= kResidentChunk) ? 2 : 1;
-  int issued = 0, judged = 0;
-  bool stop = false;
-  while (judged < n_seg && !stop) {
-    while (issued < n_seg && issued - judged < depth) {
-      if (until_segment(c, resident, E, issued, hist_rows, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
-      issued++;
-    }
-    HIP_TRY(LBM_FAILURE, hipEventSynchronize(c->ev_steady[judged & 1]));
-    stop = c->steady_stop_host[judged & 1] != 0;
-    judged++;
-    if (resident && *sl.res_status_host != 0) break;  // a launch gave up: lbm_sync below reports it
-  }
-  if (issued > judged) {  // the look-ahead segment is dropped, as in lbm_run_until
-    c->cur ^= 1;
-    c->steps_done -= E;
-    HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.res_gran, 0, resident_gran_bytes(c), sl.compute));
-  }
-  if (!stop && max_steps - n_seg * E > 0) {
-    const int rest = max_steps - n_seg * E;  // shorter than a segment: run as lbm_run runs it, not checked
-    if (run_passes(c, rest, c->plan.resident && rest >= c->plan.resident_min_steps, false) != LBM_SUCCESS) return LBM_FAILURE;
-  }
-  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;  // also reports a resident give-up
+    hipLaunchKernelGGL(lbm::residual_until_reset, dim3(1), dim3(64), 0, sl.compute, c->until_state.get(), c->until_words.get(), 1,
+                       (lbm::SteadyBatch*)nullptr);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    launch_residual_gather(c, sl, c->until_planes, c->until_words, true);  // the baseline: the field of the current lattice into the call's planes
+    return launched();
+  };
+  const auto check = [&](int index, int) -> int {  // the sample of the lattice the segment left, standing back behind a stop, and its check
+    launch_residual_gather(c, sl, c->until_planes, c->until_words, false, c->steady_state);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    long long* hist = (size_t)index < hist_rows ? c->until_history + (size_t)index * lbm_residual::kResidualWords : nullptr;
+    hipLaunchKernelGGL(lbm::residual_check, dim3(1), dim3(64), 0, sl.compute, c->until_words.get(), hist, tol, patience, (index + 1) * E,
+                       c->until_state.get(), c->steady_state.get());
+    return launched();
+  };
+  if (checked_run(c, max_steps, E, begin, check) != LBM_SUCCESS) return LBM_FAILURE;
   lbm_residual::UntilState st;
   HIP_TRY(LBM_FAILURE, hipMemcpy(&st, c->until_state, sizeof(st), hipMemcpyDeviceToHost));
   until_fill(out, st, c->steps_done - start, c->p.nx, E);
-  const size_t n_rows = (size_t)st.checks < hist_rows ? (size_t)st.checks : hist_rows;
-  if (n_rows > 0) {
-    std::vector<long long> words(n_rows * kWords);
-    HIP_TRY(LBM_FAILURE, hipMemcpy(words.data(), c->until_history, words.size() * sizeof(long long), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n_rows; i++) history[i] = lbm_residual::residual_row_from_words(words.data() + i * kWords, 1, c->p.nx, E);
-  }
-  return LBM_SUCCESS;
+  return until_history_read(c->until_history, std::min((size_t)st.checks, hist_rows), c->p.nx, E, history);
 }
 
 int lbm_batch_run_until_residual(lbm_batch* bt, int max_steps, int check_every, double tol, int patience, lbm_residual_steady_result* out,
                                  int* steps_run, lbm_residual_row* history, int history_capacity) {
   static const char who[] = "lbm_batch_run_until_residual";
   if (!bt || !out || !steps_run) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", who);
-  lbm_ctx* c0 = bt->members[0];
-  const size_t n_members = bt->members.size();
-  if (steady_args_ok(who, bt->steps_done, c0->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
-  for (const lbm_ctx* c : bt->members) {
-    if (c->rec.kind != kRecNone) {
-      const RecorderKind& k = kRecorderKinds[c->rec.kind];
-      LBM_FAIL(LBM_FAILURE, kSteadyRecorder, who, k.name, k.setter, k.noun);
-    }
-  }
-  if (bt->rec.kind != kRecNone)  // forces, statistics or residuals armed on the batch
-    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, who, kRecorderKinds[bt->rec.kind].name, batch_kind(bt->rec.kind)->setter,
-             kRecorderKinds[bt->rec.kind].noun);
-  const int E = check_every, n_seg = max_steps / E, start = bt->steps_done;
-  size_t hist_rows = 0;
-  if (until_history_ok(who, history, history_capacity, n_seg, n_members, &hist_rows) != LBM_SUCCESS) return LBM_FAILURE;
-
+  if (checked_batch_ok(bt, who, max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
+  const lbm_ctx* c0 = bt->members[0];
   const Slab& sl0 = c0->slab[0];
-  const size_t row_words = n_members * (size_t)lbm_residual::kResidualWords;
-  HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
-  // (a shape the resident kernel does not take: the gather still reads the members' lattices from the table)
-  if (!bt->table && !upload_member_table(bt)) LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the member table; nothing was run", who);
-  if (!bt->until_state) {  // allocated last: the set is whole
-    const size_t cells = (size_t)sl0.rows * c0->p.nx;
-    if (bt->until_planes.alloc(n_members * 2 * cells) != hipSuccess) {
-      (void)hipGetLastError();
-      LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the remembered fields of %zu members (%zu cells each, %.1f MiB); nothing was run", who,
-               n_members, cells, (double)(n_members * 2 * cells * sizeof(float)) / 1048576.0);
+  const size_t n_members = bt->members.size(), row_words = n_members * (size_t)lbm_residual::kResidualWords;
+  const int E = check_every, start = bt->steps_done;
+  size_t hist_rows = 0;
+  if (until_history_begin(who, bt->until_history, bt->until_history_rows, history, history_capacity, max_steps / E, bt, sl0.device,
+                          &hist_rows) != LBM_SUCCESS)
+    return LBM_FAILURE;
+  const auto begin = [&]() -> int {
+    // (a shape the resident kernel does not take: the gather still reads the members' lattices from the table)
+    if (!bt->table && !upload_member_table(bt)) LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the member table; nothing was run", who);
+    if (!bt->until_state) {  // allocated last: the set is whole
+      const size_t cells = (size_t)sl0.rows * c0->p.nx;
+      if (bt->until_planes.alloc(n_members * 2 * cells) != hipSuccess) {
+        (void)hipGetLastError();
+        LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the remembered fields of %zu members (%zu cells each, %.1f MiB); nothing was run", who,
+                 n_members, cells, (double)(n_members * 2 * cells * sizeof(float)) / 1048576.0);
+      }
+      HIP_TRY(LBM_FAILURE, bt->until_words.alloc(row_words));
+      HIP_TRY(LBM_FAILURE, bt->until_state.alloc(n_members));
     }
-    HIP_TRY(LBM_FAILURE, bt->until_words.alloc(row_words));
-    HIP_TRY(LBM_FAILURE, bt->until_batch.alloc(1));
-    HIP_TRY(LBM_FAILURE, bt->until_stop_host.alloc(1));
-    HIP_TRY(LBM_FAILURE, bt->ev_until.create(hipEventDisableTiming));
-    HIP_TRY(LBM_FAILURE, bt->until_state.alloc(n_members));
-  }
-  if (hist_rows > bt->until_history_rows) {
-    bt->until_history_rows = 0;
-    if (bt->until_history.alloc(hist_rows * row_words) != hipSuccess) {
-      (void)hipGetLastError();
-      LBM_FAIL(LBM_FAILURE, "%s: cannot allocate a history of %zu rows of %zu members (%.1f MiB); nothing was run", who, hist_rows, n_members,
-               (double)(hist_rows * row_words * sizeof(long long)) / 1048576.0);
-    }
-    bt->until_history_rows = hist_rows;
-  }
-  hipLaunchKernelGGL(lbm::residual_until_reset, dim3(ceil_div((long)n_members, 64)), dim3(64), 0, bt->stream, bt->until_state.get(),
-                     bt->until_words.get(), (int)n_members, bt->until_batch.get());
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  if (launch_batch_residual(bt, bt->until_planes, nullptr, true) != LBM_SUCCESS) return LBM_FAILURE;  // the baselines: one launch
-
-  // per segment the launches of lbm_batch_run, ONE sample launch and ONE check launch for all members; the host waits for
-  // each verdict, as lbm_batch_run_until does.  Finished members keep stepping -- and being sampled -- with the others.
-  bool stop = false;
-  int judged = 0;
-  for (; judged < n_seg && !stop; judged++) {
-    if (lbm_batch_run(bt, E) != LBM_SUCCESS) return LBM_FAILURE;
+    hipLaunchKernelGGL(lbm::residual_until_reset, dim3(ceil_div((long)n_members, 64)), dim3(64), 0, bt->stream, bt->until_state.get(),
+                       bt->until_words.get(), (int)n_members, bt->steady_batch.get());
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    return launch_batch_residual(bt, bt->until_planes, nullptr, true);  // the baselines: one launch
+  };
+  const auto check = [&](int index, int) -> int {  // ONE sample launch and ONE check launch for all members; finished members are still sampled
     HIP_TRY(LBM_FAILURE, hipMemsetAsync(bt->until_words, 0, row_words * sizeof(long long), bt->stream));
     if (launch_batch_residual(bt, bt->until_planes, bt->until_words, false) != LBM_SUCCESS) return LBM_FAILURE;
-    long long* hist = (size_t)judged < hist_rows ? bt->until_history + (size_t)judged * row_words : nullptr;
+    long long* hist = (size_t)index < hist_rows ? bt->until_history + (size_t)index * row_words : nullptr;
     hipLaunchKernelGGL(lbm::residual_check_batch, dim3((unsigned)n_members), dim3(64), 0, bt->stream, bt->until_words.get(), hist,
-                       (int)n_members, tol, patience, (judged + 1) * E, bt->until_state.get(), bt->until_batch.get());
-    HIP_TRY(LBM_FAILURE, hipGetLastError());
-    HIP_TRY(LBM_FAILURE, hipMemcpyAsync(bt->until_stop_host, &bt->until_batch.get()->all_steady, sizeof(int), hipMemcpyDeviceToHost, bt->stream));
-    HIP_TRY(LBM_FAILURE, hipEventRecord(bt->ev_until, bt->stream));
-    HIP_TRY(LBM_FAILURE, hipEventSynchronize(bt->ev_until));
-    stop = *bt->until_stop_host != 0;
-  }
-  if (!stop && max_steps - n_seg * E > 0 && lbm_batch_run(bt, max_steps - n_seg * E) != LBM_SUCCESS) return LBM_FAILURE;
-  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
+                       (int)n_members, tol, patience, (index + 1) * E, bt->until_state.get(), bt->steady_batch.get());
+    return launched();
+  };
+  if (checked_batch_run(bt, max_steps, E, begin, check) != LBM_SUCCESS) return LBM_FAILURE;
   std::vector<lbm_residual::UntilState> st(n_members);
   HIP_TRY(LBM_FAILURE, hipMemcpy(st.data(), bt->until_state, st.size() * sizeof(st[0]), hipMemcpyDeviceToHost));
   *steps_run = bt->steps_done - start;
   for (size_t i = 0; i < n_members; i++) until_fill(&out[i], st[i], *steps_run, c0->p.nx, E);
-  const size_t n_rows = (size_t)judged < hist_rows ? (size_t)judged : hist_rows;
-  if (n_rows > 0) {
-    std::vector<long long> words(n_rows * row_words);
-    HIP_TRY(LBM_FAILURE, hipMemcpy(words.data(), bt->until_history, words.size() * sizeof(long long), hipMemcpyDeviceToHost));
-    for (size_t j = 0; j < n_rows * n_members; j++)
-      history[j] = lbm_residual::residual_row_from_words(words.data() + j * lbm_residual::kResidualWords, 1, c0->p.nx, E);
-  }
-  return LBM_SUCCESS;
+  // (every whole segment that ran was checked, and the history holds a row of each while it has room)
+  return until_history_read(bt->until_history, std::min((size_t)(*steps_run / E), hist_rows) * n_members, c0->p.nx, E, history);
 }
 
 }  // extern "C"
