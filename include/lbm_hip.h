@@ -868,6 +868,70 @@ int lbm_read_profiles(lbm_ctx* ctx, int max_records, lbm_profile_line* out /* [n
 int lbm_batch_set_profiles(lbm_batch* batch, int every, int capacity, int axes);
 int lbm_batch_read_profiles(lbm_batch* batch, int max_records, lbm_profile_line* out /* [n][members][lines] */, int* steps, int* n_read);
 
+/* ---- vorticity and enstrophy ----------------------------------------------------------------
+ * The first field anyone draws of a lid-driven cavity or of a wake, and its integral: the series that tells whether a
+ * shear layer is rolling up or decaying.  The one diagnostic here that is not local to a cell.
+ * The velocity field U(x, y) = (u_x, u_y) is what lbm_read_final_state gives for the stored lattice: a fluid cell jx/rho,
+ * jy/rho in fp32 with IEEE divide and no contraction (rho, jx, jy as in the statistics' text above), a blocked cell 0, 0
+ * (the no-slip wall).  Neighbours are taken with both periodic wraps on the GLOBAL grid.  For every fluid cell, in fp32,
+ * no contraction, in exactly this order (central differences over two cells, lattice units):
+ *     dvdx = uy(x+1, y) - uy(x-1, y)        dudy = ux(x, y+1) - ux(x, y-1)
+ *     w    = 0.5f * (dvdx - dudy)           wsq  = w * w
+ * A blocked cell has w = 0 and contributes to nothing.  With nx == 1 or 2 the two x neighbours are the same cell and dvdx
+ * is exactly 0 (of finite velocities); likewise ny == 2 and dudy.  A fluid cell is NON-FINITE when one of its own rho, jx,
+ * jy, usq is not finite (the statistics' rule) or when w or wsq is not finite; such a cell adds to no sum and is counted
+ * in `nonfinite`.  A NaN in one cell therefore counts that cell and its (up to four) fluid neighbours.
+ *     enstrophy = sum of wsq over the finite fluid cells;  circulation = sum of w over them;  fluid = their number;
+ *     max_abs_w = the largest |w| among them, at the GLOBAL cell (max_x, max_y) -- of several cells with that |w| the one
+ *     with the smallest y*nx+x; 0 at -1, -1 when there is no finite fluid cell.
+ * Both sums are taken EXACTLY (csrc/lbm_exact_sum.h, one float per cell and sum) and rounded to a double once: the value
+ * math.fsum gives for the same terms.  The maximum is a 64-bit key (the bits of |w|, the cell) and does not depend on
+ * order either.  A row therefore has the same bits from a single call, split calls, resident or per-pass sub-calls, 1, 2,
+ * 3 or 8 slabs, a tiled context, a batch member, and from run to run.
+ * lbm_read_vorticity(ctx, w): the field of the current lattice, w[row_count * nx] row-major, w as above, 0 on blocked
+ *   cells; a non-finite w is stored as computed.  Synchronises like the other readers, needs nothing armed and changes
+ *   nothing.  Works on lbm_create / lbm_create_tiled contexts of any slab count and on batch member handles; refused on
+ *   rank contexts (lbm_create_rank*).
+ * lbm_set_enstrophy(ctx, every, capacity): from now on, after global timestep tt (0-based, the numbering of
+ *   lbm_set_frames) with tt % every == 0, record one row of the lattice after tt+1 timesteps.  Rows wait in a device ring
+ *   of `capacity` rows (192 bytes per row and slab: the exact sums, rounded when read); an lbm_run that would record more
+ *   rows than are free fails before issuing any work.  every == 0 disarms and frees; re-arming discards unread rows.  No
+ *   step kernel records the enstrophy: as with the statistics every call runs as the sub-calls that end at its sample
+ *   steps, each followed per slab by one memset of the row and one vorticity_gather launch (every == 1: correct, not
+ *   fast).  The kernel reads the rows around a slab: on several slabs each slab keeps an edge buffer of two lattice rows,
+ *   filled before every sample by device-to-device copies of its neighbours' boundary rows (behind their passes; their
+ *   later passes run behind the copies) -- the lattice's halo rows are not used.  Recording never changes the lattice or
+ *   av_vels: they equal those of the same run issued as calls split at the sample steps.
+ *   Refused, as lbm_set_stats refuses: negative every; capacity < 1; a ring of 2 GiB or more; rank contexts
+ *   (lbm_create_rank*); batch members (a batch arms it as a whole: lbm_batch_set_enstrophy); LBM_HALO_STALE /
+ *   LBM_HALO_FRESHEST (and lbm_set_halo_mode to those while armed); a context with another recorder armed (and the other
+ *   setters while this one is armed); lbm_run_until and lbm_run_until_residual while armed.  Not offered: the double
+ *   engine, recording inside the resident or stream kernels, higher-order stencils, the strain rate, a command-line mode.
+ * lbm_read_enstrophy: drains up to max_rows oldest rows into out[n] and steps[n] (their tt, may be NULL); out == NULL &&
+ *   steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers.
+ * lbm_batch_set_enstrophy / lbm_batch_read_enstrophy: the same for every member of a batch, armed on the BATCH with one
+ *   `every` and ONE ring [slots][members][24 words]; rows are out[n][members].  Behind each sub-call that ends at a sample
+ *   step the batch's stream gets one memset of the row and ONE vorticity_gather_batch launch for all members (grid z is
+ *   the member).  Member i's rows, lattice and av_vels are bit-identical to those of an lbm_create context armed with
+ *   lbm_set_enstrophy and advanced by the same calls.  An lbm_batch_run without room fails before any work and moves no
+ *   member's steps_done.  Refused as lbm_batch_set_stats refuses: a member with a recorder armed, another kind armed on
+ *   the batch (and every member-level setter and the four other batch-level setters while the enstrophy is armed);
+ *   lbm_batch_run_until and lbm_batch_run_until_residual while armed.
+ */
+typedef struct {
+  double    enstrophy;    /* exact sum of wsq over the finite fluid cells, rounded once (math.fsum's value) */
+  double    circulation;  /* exact sum of w over the same cells */
+  long long nonfinite;    /* fluid cells left out of everything above and below */
+  float     max_abs_w;    /* largest |w| of a finite fluid cell; 0 when there is none */
+  int       max_x, max_y; /* its GLOBAL cell; ties: the smallest y*nx+x; -1,-1 when there is none */
+  int       fluid;        /* finite fluid cells counted */
+} lbm_enstrophy_row;      /* 40 bytes; offsets 0 8 16 24 28 32 36 */
+int lbm_read_vorticity(lbm_ctx* ctx, float* w /* [row_count*nx] */);
+int lbm_set_enstrophy(lbm_ctx* ctx, int every, int capacity);
+int lbm_read_enstrophy(lbm_ctx* ctx, int max_rows, lbm_enstrophy_row* out, int* steps, int* n_read);
+int lbm_batch_set_enstrophy(lbm_batch* batch, int every, int capacity);
+int lbm_batch_read_enstrophy(lbm_batch* batch, int max_rows, lbm_enstrophy_row* out /* [n][members] */, int* steps, int* n_read);
+
 /* ---- double precision -----------------------------------------------------------------------
  * The reference's programs are `float`, but its published golden results (the .dat files of check/) are its algorithm evaluated in
  * IEEE double.  A double context computes exactly that: the driver loop of SerialCode/d2q9-bgk.c:166-170 with every

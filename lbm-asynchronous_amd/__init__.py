@@ -57,6 +57,7 @@ ABI_SYMBOLS = (
     "lbm_set_residual", "lbm_read_residual", "lbm_batch_set_residual", "lbm_batch_read_residual",
     "lbm_run_until_residual", "lbm_batch_run_until_residual",
     "lbm_set_profiles", "lbm_read_profiles", "lbm_batch_set_profiles", "lbm_batch_read_profiles",
+    "lbm_read_vorticity", "lbm_set_enstrophy", "lbm_read_enstrophy", "lbm_batch_set_enstrophy", "lbm_batch_read_enstrophy",
     "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
     "lbm_double_sync", "lbm_double_read_av_vels", "lbm_double_read_cells", "lbm_double_read_final_state",
     "lbm_double_av_velocity", "lbm_double_total_density", "lbm_double_calc_reynolds",
@@ -279,6 +280,11 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_read_profiles.argtypes = [P, I, P, P, PI]; lib.lbm_read_profiles.restype = I
     lib.lbm_batch_set_profiles.argtypes = [P, I, I, I]; lib.lbm_batch_set_profiles.restype = I
     lib.lbm_batch_read_profiles.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_profiles.restype = I
+    lib.lbm_read_vorticity.argtypes = [P, P]; lib.lbm_read_vorticity.restype = I
+    lib.lbm_set_enstrophy.argtypes = [P, I, I]; lib.lbm_set_enstrophy.restype = I
+    lib.lbm_read_enstrophy.argtypes = [P, I, P, P, PI]; lib.lbm_read_enstrophy.restype = I
+    lib.lbm_batch_set_enstrophy.argtypes = [P, I, I]; lib.lbm_batch_set_enstrophy.restype = I
+    lib.lbm_batch_read_enstrophy.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_enstrophy.restype = I
     lib.lbm_set_residual.argtypes = [P, I, I]; lib.lbm_set_residual.restype = I
     lib.lbm_read_residual.argtypes = [P, I, P, P, PI]; lib.lbm_read_residual.restype = I
     lib.lbm_batch_set_residual.argtypes = [P, I, I]; lib.lbm_batch_set_residual.restype = I
@@ -724,6 +730,27 @@ class Engine:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], STATS_DTYPE[n])."""
         return _drain_rows(self.lib.lbm_read_stats, self.lib, self.handle, "stats", max_rows, (), STATS_DTYPE, np.zeros)
 
+    # -- vorticity and enstrophy (lbm_read_vorticity / lbm_set_enstrophy / lbm_read_enstrophy) -------
+    def vorticity(self) -> np.ndarray:
+        """The vorticity of the current lattice, float32 (row_count, nx): w = 0.5 * ((u_y(x+1) - u_y(x-1)) - (u_x(y+1) -
+        u_x(y-1))) of final_state()'s velocities with both periodic wraps, blocked cells 0 (as neighbours too).  Needs
+        nothing armed and changes nothing."""
+        out = np.empty((self.info()["row_count"], self.params.nx), dtype=np.float32)
+        _check(self.lib, self.lib.lbm_read_vorticity(self.handle, out.ctypes.data))
+        return out
+
+    def set_enstrophy(self, every: int, capacity: int = 4096) -> None:
+        """Record one row of the vorticity's whole-lattice sums -- the enstrophy (sum of w^2) and the circulation (sum of
+        w) over the finite fluid cells, summed exactly and rounded once, the largest |w| and its cell, the counts --
+        after every global timestep tt with tt % every == 0, for the lattice after tt + 1 steps, into a device ring of
+        `capacity` rows.  every == 0 disarms; re-arming discards unread rows."""
+        every, capacity = _enstrophy_args(every, capacity)
+        _check(self.lib, self.lib.lbm_set_enstrophy(self.handle, every, capacity))
+
+    def enstrophy(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], ENSTROPHY_DTYPE[n])."""
+        return _drain_rows(self.lib.lbm_read_enstrophy, self.lib, self.handle, "enstrophy", max_rows, (), ENSTROPHY_DTYPE, np.zeros)
+
     # -- velocity residuals (lbm_set_residual / lbm_read_residual) ---------------------------------
     def set_residual(self, every: int, capacity: int = 4096) -> None:
         """Remember the velocity field of the current lattice (the baseline) and, after every global timestep tt with
@@ -1030,6 +1057,18 @@ class Batch:
     def stats(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], STATS_DTYPE[n, members])."""
         return _drain_rows(self.lib.lbm_batch_read_stats, self.lib, self._live(), "stats", max_rows, (len(self),), STATS_DTYPE, np.zeros)
+
+    # -- enstrophy of all members (lbm_batch_set_enstrophy / lbm_batch_read_enstrophy) -----------------------------------
+    def set_enstrophy(self, every: int, capacity: int = 4096) -> None:
+        """Engine.set_enstrophy for every member at once: one `every` and `capacity` for the batch, rows in one device
+        ring, one gather launch per sample for all members.  every == 0 disarms."""
+        every, capacity = _enstrophy_args(every, capacity)
+        _check(self.lib, self.lib.lbm_batch_set_enstrophy(self._live(), every, capacity))
+
+    def enstrophy(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], ENSTROPHY_DTYPE[n, members])."""
+        return _drain_rows(self.lib.lbm_batch_read_enstrophy, self.lib, self._live(), "enstrophy", max_rows, (len(self),),
+                           ENSTROPHY_DTYPE, np.zeros)
 
     # -- velocity residuals of all members (lbm_batch_set_residual / lbm_batch_read_residual) ------------------------
     def set_residual(self, every: int, capacity: int = 4096) -> None:
@@ -1354,6 +1393,30 @@ def write_stats(path: str, steps, rows) -> None:
             fh.write("%d:\t%.12E\t%.12E\t%.12E\t%.12E\t%.12E\t%d\t%d\t%d\n" % (
                 tt, float(r["mass"]), float(r["mom_x"]), float(r["mom_y"]), float(r["sum_u_sq"]), float(r["max_u"]),
                 int(r["max_x"]), int(r["max_y"]), int(r["nonfinite"])))
+
+
+# lbm_enstrophy_row of include/lbm_hip.h, 40 bytes
+ENSTROPHY_DTYPE = np.dtype([("enstrophy", "<f8"), ("circulation", "<f8"), ("nonfinite", "<i8"), ("max_abs_w", "<f4"),
+                            ("max_x", "<i4"), ("max_y", "<i4"), ("fluid", "<i4")])
+
+
+def _enstrophy_args(every, capacity) -> tuple[int, int]:
+    """Engine.set_enstrophy's argument checks (no device needed): (every, capacity)."""
+    return _every_capacity("set_enstrophy", every, capacity, "row")
+
+
+def write_enstrophy(path: str, steps, rows) -> None:
+    """One line per row in write_stats' style: tt, a colon, then tab-separated enstrophy, circulation and max_abs_w as
+    '%.12E' and max_x, max_y, fluid and nonfinite as '%d'; `steps` int[n], `rows` ENSTROPHY_DTYPE[n] (Engine.enstrophy)."""
+    rows = np.asarray(rows)
+    steps = np.asarray(steps).ravel()
+    if rows.dtype != ENSTROPHY_DTYPE or rows.ndim != 1 or rows.shape[0] != steps.size:
+        raise LbmError(f"write_enstrophy: rows must be {steps.size} rows of ENSTROPHY_DTYPE (got shape {rows.shape}, dtype {rows.dtype})")
+    with open(path, "w") as fh:
+        for tt, r in zip(steps.tolist(), rows):
+            fh.write("%d:\t%.12E\t%.12E\t%.12E\t%d\t%d\t%d\t%d\n" % (
+                tt, float(r["enstrophy"]), float(r["circulation"]), float(r["max_abs_w"]), int(r["max_x"]), int(r["max_y"]),
+                int(r["fluid"]), int(r["nonfinite"])))
 
 
 # lbm_profile_line of include/lbm_hip.h, 48 bytes

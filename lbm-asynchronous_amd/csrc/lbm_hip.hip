@@ -262,6 +262,9 @@ struct Slab {
   DeviceBuf<unsigned> force_starts;        // ... [bodies + 1]: where each body's links start
   int force_groups = 0;                    // workgroups per body of force_gather (0: the slab has no links)
   DeviceBuf<float> residual_planes;        // lbm_set_residual: [2][rows][nx]: the remembered u_x and u_y of this slab's owned cells
+  DeviceBuf<float> vort_edges;             // lbm_set_enstrophy, several slabs: [2][row_pitch]: the south and the north neighbour's
+                                           // boundary row of the current lattice, copied in front of every vorticity_gather
+  Event ev_vort_ready, ev_vort_done;       // ... this slab's rows may be copied / the copies of this slab's sample have been used
   // freshest-available mode (LBM_HALO_FRESHEST), allocated at its first use in this order: whole once ev_fresh[1] exists
   DeviceBuf<float> fresh_stage;          // [parity][side: 0 south halo, 1 north halo][row_pitch]: this pass's rows, if they make it
   DeviceBuf<unsigned> fresh_arrived;     // [parity][side]: id (global step + 1) of the step whose row the staging holds
@@ -415,12 +418,17 @@ struct GraphBuilder {
 // Velocity residuals (lbm_set_residual) likewise, by residual_gather, which also keeps a field between the samples: the
 // velocities of the last sample (at first: of arming), which every sample compares with and replaces.
 // Line profiles (lbm_set_profiles) likewise, by profile_rows and profile_columns: a record of per-row and per-column sums.
-// These four gather kinds (records_behind) share one ring of int64 words per slab, Slab::gather_ring, whose slot holds
+// The enstrophy (lbm_set_enstrophy) likewise, by vorticity_gather: a row of whole-lattice sums of the vorticity, the one
+// kind whose kernel reads rows a slab does not own (Slab::vort_edges).
+// These five gather kinds (records_behind) share one ring of int64 words per slab, Slab::gather_ring, whose slot holds
 // gather_slot_words words; a batch arms them on itself (lbm_batch::rec) with one ring for all members.
 enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean,
-       kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecResidual = 7, kRecProfiles = 8, kRecKinds = 9 };
+       kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecResidual = 7, kRecProfiles = 8, kRecEnstrophy = 9,
+       kRecKinds = 10 };
 // the kinds recorded by a gather launch behind the sub-call that ends at a sample step, whatever kernels advance the lattice
-constexpr bool records_behind(int kind) { return kind == kRecForces || kind == kRecStats || kind == kRecResidual || kind == kRecProfiles; }
+constexpr bool records_behind(int kind) {
+  return kind == kRecForces || kind == kRecStats || kind == kRecResidual || kind == kRecProfiles || kind == kRecEnstrophy;
+}
 struct Recorder {
   int kind = kRecNone;
   int every = 0;
@@ -461,7 +469,9 @@ constexpr RecorderKind kRecorderKinds[kRecKinds] = {
     {.name = "velocity residuals", .noun = "residuals", .record = "row", .setter = "lbm_set_residual",
      .reader = "lbm_read_residual", .disarm = "lbm_set_residual(ctx, 0, 0)"},
     {.name = "line profiles", .noun = "profiles", .record = "record", .setter = "lbm_set_profiles",
-     .reader = "lbm_read_profiles", .disarm = "lbm_set_profiles(ctx, 0, 0, 0)"}};
+     .reader = "lbm_read_profiles", .disarm = "lbm_set_profiles(ctx, 0, 0, 0)"},
+    {.name = "enstrophy rows", .noun = "enstrophy", .record = "row", .setter = "lbm_set_enstrophy",
+     .reader = "lbm_read_enstrophy", .disarm = "lbm_set_enstrophy(ctx, 0, 0)"}};
 
 struct lbm_ctx {
   lbm_params p;
@@ -528,7 +538,7 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentProbes> probe_table;  // device: [members], allocated when the first member arms probes
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
   DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
-  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
+  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
                                     // (a batch records one kind, so at most one count is non-zero; a gather kind is armed
                                     // on the batch, by its lbm_batch_set_* of kBatchKinds, and counts as one)
   // the gather kinds (records_behind) of all members: the members' own recorders stay off, the batch keeps the one
@@ -566,6 +576,7 @@ static int take_batch_forces(lbm_batch* bt, long long* row);
 static int take_batch_stats(lbm_batch* bt, long long* row);
 static int take_batch_residual(lbm_batch* bt, long long* row);
 static int take_batch_profiles(lbm_batch* bt, long long* record);
+static int take_batch_enstrophy(lbm_batch* bt, long long* row);
 struct BatchKind {
   int kind;
   const char* setter;
@@ -577,7 +588,8 @@ static const BatchKind kBatchKinds[] = {
     {kRecForces, "lbm_batch_set_forces", "lbm_batch_read_forces", "lbm_batch_set_forces(batch, 0, NULL, 0, 0)", take_batch_forces},
     {kRecStats, "lbm_batch_set_stats", "lbm_batch_read_stats", "lbm_batch_set_stats(batch, 0, 0)", take_batch_stats},
     {kRecResidual, "lbm_batch_set_residual", "lbm_batch_read_residual", "lbm_batch_set_residual(batch, 0, 0)", take_batch_residual},
-    {kRecProfiles, "lbm_batch_set_profiles", "lbm_batch_read_profiles", "lbm_batch_set_profiles(batch, 0, 0, 0)", take_batch_profiles}};
+    {kRecProfiles, "lbm_batch_set_profiles", "lbm_batch_read_profiles", "lbm_batch_set_profiles(batch, 0, 0, 0)", take_batch_profiles},
+    {kRecEnstrophy, "lbm_batch_set_enstrophy", "lbm_batch_read_enstrophy", "lbm_batch_set_enstrophy(batch, 0, 0)", take_batch_enstrophy}};
 static const BatchKind* batch_kind(int kind) {
   for (const BatchKind& k : kBatchKinds)
     if (k.kind == kind) return &k;
@@ -1398,10 +1410,10 @@ const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = f
   static const Form forms[2][kRecKinds] = {
       {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>, resident_form<false, kRecMean>,
        resident_form<false, kRecFields>, resident_form<false, kRecNone>, resident_form<false, kRecNone>,
-       resident_form<false, kRecNone>, resident_form<false, kRecNone>},  // (the forces, the statistics, the residuals and the profiles run the plain form)
+       resident_form<false, kRecNone>, resident_form<false, kRecNone>, resident_form<false, kRecNone>},  // (the gather kinds run the plain form)
       {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>, resident_form<true, kRecMean>,
        resident_form<true, kRecFields>, resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>,
-       resident_form<true, kRecNone>}};
+       resident_form<true, kRecNone>, resident_form<true, kRecNone>}};
   return forms[batch][rec]((rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
 }
 
@@ -1661,6 +1673,78 @@ void launch_profiles(const lbm_ctx* c, const Slab& sl, long long* lines) {
   }
 }
 
+// rows of a band of vorticity_gather / vorticity_gather_batch for `rows` rows of nx cells: about kVortTargetUnits units
+// (a wave's strip of 64 * V columns of a band) where the grid has that many bands of kVortMinBand rows, so that small and
+// large grids both fill the device and a large one reads few rows twice
+constexpr int kVortTargetUnits = 4096;  // four waves per SIMD
+int vorticity_strips(int nx) { return ceil_div(nx, 64 * stats_vector(nx)); }
+int vorticity_band_rows(int rows, int nx) {
+  const int strips = vorticity_strips(nx);
+  const int bands = kVortTargetUnits / strips > 1 ? kVortTargetUnits / strips : 1;
+  const int band_rows = ceil_div(rows, bands);
+  return band_rows > lbm::kVortMinBand ? band_rows : lbm::kVortMinBand;
+}
+// ... and its workgroups, a unit per wave where the cap allows
+int vorticity_groups(int rows, int nx, int band_rows) {
+  const long groups = ceil_div((long)vorticity_strips(nx) * ceil_div(rows, band_rows), lbm::kBlock / 64);
+  return groups > lbm::kVortMaxGroups ? lbm::kVortMaxGroups : (int)groups;
+}
+
+// the vorticity of a slab's rows [row_begin, row_end) of its current lattice on its compute stream: into `field` (dense,
+// row row_begin first) and / or `words` (zeroed in front, on the same stream).  edges: [2][row_pitch], the rows below and
+// above the slab; nullptr: the slab is the whole periodic grid and they are its own last and first row.
+void launch_vorticity_gather(const lbm_ctx* c, const Slab& sl, const float* edges, int row_begin, int row_end, float* field, long long* words) {
+  const int nx = c->p.nx, n = row_end - row_begin;
+  const int band_rows = vorticity_band_rows(n, nx);
+  const dim3 grid(vorticity_groups(n, nx, band_rows));
+  const float* south = edges ? edges : sl.lat[c->cur] + (long)(sl.rows - 1) * c->row_pitch;
+  const float* north = edges ? edges + c->row_pitch : sl.lat[c->cur];
+  const unsigned cell_first = (unsigned)sl.row_first * (unsigned)nx;
+  const bool v4 = stats_vector(nx) == 4;
+  const auto kernel = field ? (v4 ? lbm::vorticity_gather<4, true> : lbm::vorticity_gather<1, true>)
+                            : (v4 ? lbm::vorticity_gather<4, false> : lbm::vorticity_gather<1, false>);  // (the form without the field's store)
+  hipLaunchKernelGGL(kernel, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), south, north, sl.rows, row_begin, row_end, band_rows,
+                     cell_first, field, words);
+}
+
+// The rows a slab does not own, for vorticity_gather on several slabs: slab s's `edges` ([2][row_pitch]) get the last row
+// of its south neighbour's and the first row of its north neighbour's current lattice, by copies on s's compute stream
+// behind the neighbours' ev_vort_ready (recorded by the caller on their compute streams, behind the pass that wrote the
+// rows).  The lattice halo rows are not used: after a pass they are not defined to hold the neighbours' current rows.
+int copy_vorticity_edges(lbm_ctx* c, int s, float* edges) {
+  Slab& sl = c->slab[s];
+  const Slab& ss = c->slab[(s - 1 + c->n_slabs) % c->n_slabs];
+  const Slab& sn = c->slab[(s + 1) % c->n_slabs];
+  const size_t row_bytes = (size_t)c->row_pitch * sizeof(float);
+  HIP_TRY(LBM_FAILURE, hipStreamWaitEvent(sl.compute, ss.ev_vort_ready, 0));
+  HIP_TRY(LBM_FAILURE, hipStreamWaitEvent(sl.compute, sn.ev_vort_ready, 0));
+  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(edges, ss.lat[c->cur] + (long)(ss.rows - 1) * c->row_pitch, row_bytes, hipMemcpyDefault, sl.compute));
+  HIP_TRY(LBM_FAILURE, hipMemcpyAsync(edges + c->row_pitch, sn.lat[c->cur], row_bytes, hipMemcpyDefault, sl.compute));
+  return LBM_SUCCESS;
+}
+// every slab's compute stream marks "my rows of the current lattice are written" (several slabs)
+int mark_vorticity_ready(lbm_ctx* c) {
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    if (!sl.ev_vort_ready) HIP_TRY(LBM_FAILURE, sl.ev_vort_ready.create(hipEventDisableTiming));
+    if (!sl.ev_vort_done) HIP_TRY(LBM_FAILURE, sl.ev_vort_done.create(hipEventDisableTiming));
+    HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_vort_ready, sl.compute));
+  }
+  return LBM_SUCCESS;
+}
+// ... and, once every slab has recorded ev_vort_done behind its sample, waits for its neighbours': the later passes,
+// which overwrite the current lattice two passes on, run behind the copies of its rows
+int await_vorticity_done(lbm_ctx* c) {
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    HIP_TRY(LBM_FAILURE, hipStreamWaitEvent(sl.compute, c->slab[(s - 1 + c->n_slabs) % c->n_slabs].ev_vort_done, 0));
+    HIP_TRY(LBM_FAILURE, hipStreamWaitEvent(sl.compute, c->slab[(s + 1) % c->n_slabs].ev_vort_done, 0));
+  }
+  return LBM_SUCCESS;
+}
+
 // int64 words a gather kind records per slab (or batch member) and sample: of `bodies` bodies (forces), of `rows` rows of
 // nx cells along `axes` (profiles).  The one place a slot's size is computed: the setters call it with what they are about
 // to arm, everything else through gather_slot_words with what is armed.
@@ -1670,6 +1754,7 @@ size_t gather_words(int kind, size_t bodies = 0, int rows = 0, int nx = 0, int a
     case kRecStats: return lbm_stats::kStatsWords;
     case kRecResidual: return lbm_residual::kResidualWords;
     case kRecProfiles: return lbm_profile::profile_slab_lines(rows, nx, axes) * lbm_profile::kProfileWords;
+    case kRecEnstrophy: return lbm_enstrophy::kEnstrophyWords;
     default: return 0;
   }
 }
@@ -1711,6 +1796,8 @@ int fetch_ring(const T* ring, size_t slot_words, const Recorder& r, int n, hipSt
 int take_record(lbm_ctx* c) {
   const size_t slot = kRecorderKinds[c->rec.kind].slotted ? (size_t)(c->rec.written % c->rec.slots) : 0;
   const size_t n_probes = c->probe_cells.size();
+  const bool vort_edges = (c->rec.kind == kRecEnstrophy && c->n_slabs > 1);  // the sample reads the neighbours' boundary rows
+  if (vort_edges && mark_vorticity_ready(c) != LBM_SUCCESS) return LBM_FAILURE;
   if (for_slabs(c, [&](int s) -> int {
         Slab& sl = c->slab[s];
         HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
@@ -1739,7 +1826,11 @@ int take_record(lbm_ctx* c) {
           launch_residual_gather(c, sl, sl.residual_planes, words, false);  // also replaces the slab's remembered field by this lattice's
         else if (c->rec.kind == kRecProfiles)
           launch_profiles(c, sl, words);  // (profile_rows leaves a line's spare word as zeroed)
-        else if (c->rec.kind == kRecMean)
+        else if (c->rec.kind == kRecEnstrophy) {
+          if (vort_edges && copy_vorticity_edges(c, s, sl.vort_edges) != LBM_SUCCESS) return LBM_FAILURE;
+          launch_vorticity_gather(c, sl, vort_edges ? sl.vort_edges.get() : nullptr, 0, sl.rows, nullptr, words);
+          if (vort_edges) HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_vort_done, sl.compute));
+        } else if (c->rec.kind == kRecMean)
           hipLaunchKernelGGL(lbm::mean_accumulate, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              c->p.density, sl.mean_sums, n, c->rec.order);
         else if (sl.probe_count > 0)
@@ -1749,6 +1840,7 @@ int take_record(lbm_ctx* c) {
         return LBM_SUCCESS;
       }) != LBM_SUCCESS)
     return LBM_FAILURE;
+  if (vort_edges && await_vorticity_done(c) != LBM_SUCCESS) return LBM_FAILURE;
   c->rec.written++;
   return LBM_SUCCESS;
 }
@@ -2474,6 +2566,7 @@ void release_recorder(lbm_ctx* c) {
     sl.force_starts.reset();
     sl.force_groups = 0;
     sl.residual_planes.reset();
+    sl.vort_edges.reset();
     sl.probe_count = 0;
   }
   c->probe_cells.clear();
@@ -3368,6 +3461,79 @@ int lbm_read_stats(lbm_ctx* c, int max_rows, lbm_stats_row* out, int* steps, int
   });
 }
 
+// ---- vorticity and enstrophy -------------------------------------------------------------------------------------------
+int lbm_set_enstrophy(lbm_ctx* c, int every, int capacity) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: null context");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: negative interval %d", every);
+  const long long kRowBytes = (long long)(gather_words(kRecEnstrophy) * sizeof(long long));
+  if (every > 0) {
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: capacity %d, at least one row is needed", capacity);
+    if ((long long)capacity * kRowBytes >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: a ring of %d rows is 2 GiB or more (%d bytes per row)", capacity, (int)kRowBytes);
+    if (c->ranked || c->world > 1)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: not available in a multi-process (rank) context: a row's sums would be spread over the ranks");
+    if (c->batch)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
+               "end at, so the enstrophy of a batch is armed on the batch, with one `every` for all members (lbm_batch_set_enstrophy)");
+  }
+  return rearm_recorder(c, kRecEnstrophy, every, capacity, [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * (size_t)kRowBytes;
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      if (sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess || (c->n_slabs > 1 && sl.vort_edges.alloc(2 * (size_t)c->row_pitch) != hipSuccess))
+        LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: cannot allocate %d rows (%.1f MiB per slab); the enstrophy stays off", capacity,
+                 (double)ring_bytes / 1048576.0);
+    }
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_read_enstrophy(lbm_ctx* c, int max_rows, lbm_enstrophy_row* out, int* steps, int* n_read) {
+  return drain_recorder(c, kRecEnstrophy, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
+    // rows[row][slab][words]: the slabs of a row are merged and rounded by enstrophy_row_from_words
+    std::vector<long long> rows;
+    size_t row_words;
+    if (fetch_gather_records(c, n, rows, &row_words) != LBM_SUCCESS) return LBM_FAILURE;
+    for (int i = 0; i < n; i++) out[i] = lbm_enstrophy::enstrophy_row_from_words(rows.data() + (size_t)i * row_words, c->n_slabs, c->p.nx);
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_read_vorticity(lbm_ctx* c, float* w) {
+  if (!c || !w) LBM_FAIL(LBM_FAILURE, "lbm_read_vorticity: NULL argument");
+  if (c->ranked || c->world > 1)
+    LBM_FAIL(LBM_FAILURE, "lbm_read_vorticity: not available in a multi-process (rank) context: the rows around this rank's belong to other processes");
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
+  const int nx = c->p.nx;
+  long chunk_rows = (16L << 20) / ((long)nx * sizeof(float));
+  if (chunk_rows < 1) chunk_rows = 1;
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    DeviceBuf<float> stage, edges;  // the call's own: nothing armed is touched
+    HIP_TRY(LBM_FAILURE, stage.alloc((size_t)chunk_rows * nx));
+    if (c->n_slabs > 1) {
+      // every stream is idle (lbm_sync): the neighbours' boundary rows are copied in stream order, no events needed
+      const Slab& ss = c->slab[(s - 1 + c->n_slabs) % c->n_slabs];
+      const Slab& sn = c->slab[(s + 1) % c->n_slabs];
+      const size_t row_bytes = (size_t)c->row_pitch * sizeof(float);
+      HIP_TRY(LBM_FAILURE, edges.alloc(2 * (size_t)c->row_pitch));
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(edges, ss.lat[c->cur] + (long)(ss.rows - 1) * c->row_pitch, row_bytes, hipMemcpyDefault, sl.compute));
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(edges + c->row_pitch, sn.lat[c->cur], row_bytes, hipMemcpyDefault, sl.compute));
+    }
+    for (int r0 = 0; r0 < sl.rows; r0 += (int)chunk_rows) {
+      const int nr = (sl.rows - r0 < chunk_rows) ? sl.rows - r0 : (int)chunk_rows;
+      launch_vorticity_gather(c, sl, c->n_slabs > 1 ? edges.get() : nullptr, r0, r0 + nr, stage, nullptr);
+      HIP_TRY(LBM_FAILURE, hipGetLastError());
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(w + (size_t)(sl.row_first - c->row_first + r0) * nx, stage, (size_t)nr * nx * sizeof(float),
+                                          hipMemcpyDeviceToHost, sl.compute));
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+    }
+  }
+  return LBM_SUCCESS;
+}
+
 // the span of the row with ordinal `ord` since arming: from the baseline to the first sample, then `every`
 static int residual_span(const Recorder& r, long long ord) {
   return ord == 0 ? (int)((long long)r.ord0 * r.every + 1 - r.base_steps) : r.every;
@@ -3879,6 +4045,20 @@ static int take_batch_stats(lbm_batch* bt, long long* row) {
   return LBM_SUCCESS;
 }
 
+// the enstrophy: one vorticity_gather_batch for all members, each a periodic slab of its own
+static int take_batch_enstrophy(lbm_batch* bt, long long* row) {
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  const Slab& sl0 = c0->slab[0];
+  const int nx = c0->p.nx, band_rows = vorticity_band_rows(sl0.rows, nx);
+  const dim3 grid((unsigned)vorticity_groups(sl0.rows, nx, band_rows), 1, (unsigned)n_members);
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  hipLaunchKernelGGL(stats_vector(nx) == 4 ? lbm::vorticity_gather_batch<4> : lbm::vorticity_gather_batch<1>, grid, dim3(lbm::kBlock), 0,
+                     bt->stream, lattice_args(c0, sl0), tab, sl0.rows, band_rows, row);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+
 // ONE residual_gather_batch launch over all members' current (stored) lattices and planes, on the batch's stream:
 // the baseline (`planes` filled, `row` unused) or a sample against `planes` into `row`, [members][kResidualWords], which
 // the caller has zeroed in front
@@ -4058,6 +4238,35 @@ int lbm_batch_read_stats(lbm_batch* bt, int max_rows, lbm_stats_row* out, int* s
     // every member's words become its row
     for (size_t j = 0; j < (size_t)n * bt->members.size(); j++)
       out[j] = lbm_stats::stats_row_from_words(words + j * lbm_stats::kStatsWords, 1, bt->members[0]->p.nx);
+  });
+}
+
+// ---- enstrophy of a batch --------------------------------------------------------------------------------------------
+int lbm_batch_set_enstrophy(lbm_batch* bt, int every, int capacity) {
+  size_t row_bytes = 0;  // of all members
+  return rearm_batch_recorder(bt, kRecEnstrophy, every, capacity, [&]() -> int {
+    const size_t n_members = bt->members.size();
+    row_bytes = n_members * gather_words(kRecEnstrophy) * sizeof(long long);
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_enstrophy: capacity %d, at least one row is needed", capacity);
+    if ((long long)capacity * (long long)row_bytes >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_enstrophy: a ring of %d rows of %d members is %.2f GiB, 2 GiB or more (%d bytes per member and row)",
+               capacity, (int)n_members, (double)capacity * (double)row_bytes / 1073741824.0,
+               lbm_enstrophy::kEnstrophyWords * (int)sizeof(long long));
+    return LBM_SUCCESS;
+  }, [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * row_bytes;
+    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_enstrophy: cannot allocate %d rows of %d members (%.1f MiB); the enstrophy stays off", capacity,
+               (int)bt->members.size(), (double)ring_bytes / 1048576.0);
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_batch_read_enstrophy(lbm_batch* bt, int max_rows, lbm_enstrophy_row* out, int* steps, int* n_read) {
+  return drain_batch_recorder(bt, kRecEnstrophy, max_rows, out != nullptr, steps, n_read, [&](int n, const long long* words) {
+    // every member's words become its row
+    for (size_t j = 0; j < (size_t)n * bt->members.size(); j++)
+      out[j] = lbm_enstrophy::enstrophy_row_from_words(words + j * lbm_enstrophy::kEnstrophyWords, 1, bt->members[0]->p.nx);
   });
 }
 

@@ -38,6 +38,7 @@
 #include "lbm_stats_row.h"
 #include "lbm_residual_row.h"
 #include "lbm_profile_row.h"
+#include "lbm_enstrophy_row.h"
 #include "lbm_residual_until.h"
 
 namespace lbm {
@@ -50,7 +51,8 @@ constexpr int kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3, kRecFi
 // (the obstacle forces, lbm_set_forces / lbm_batch_set_forces, the lattice statistics, lbm_set_stats /
 // lbm_batch_set_stats, the velocity residuals, lbm_set_residual / lbm_batch_set_residual, and the line profiles,
 // lbm_set_profiles / lbm_batch_set_profiles, are recorder kinds of the host alone: force_gather, stats_gather,
-// residual_gather, profile_rows, profile_columns and their batch twins run behind the step kernels)
+// residual_gather, profile_rows, profile_columns and their batch twins run behind the step kernels; so does the
+// vorticity's vorticity_gather, lbm_set_enstrophy / lbm_batch_set_enstrophy)
 
 // 1/3 rounded to fp32, and the two constant divisors of the equilibrium, folded in fp32
 // exactly as the reference's "2.f * c_sq" and "2.f * c_sq * c_sq" (SerialCode/d2q9-bgk.c:308,367-370)
@@ -3469,6 +3471,217 @@ __global__ __launch_bounds__(kBlock) void profile_columns_batch(const LatticeArg
                                                                 long long* lines, long member_words) {
   const int member = blockIdx.z;
   profile_column_lines(a, members[member].src, members[member].mask, rows, band_rows, lines + (size_t)member * member_words);
+}
+
+// ---------------------------------------------------------------------------------------------
+// vorticity and enstrophy (lbm_read_vorticity, lbm_set_enstrophy): w = 0.5f * ((uy(x+1) - uy(x-1)) - (ux(y+1) - ux(y-1)))
+// of every fluid cell of a stored lattice, as a field and / or as the exact sums of w * w and w, the largest |w| with its
+// cell and the counts of a row (lbm_enstrophy_row.h)
+// ---------------------------------------------------------------------------------------------
+// The first gather that reads a cell's neighbours.  A wave owns a unit: a strip of 64 * V columns -- V = 4 where
+// nx % 4 == 0: each of the nine planes is read with one 16-byte load per lane, the mask with one 4-byte load; V = 1
+// otherwise; no lane reaches into the pitch padding (x + V <= nx, the other lanes load nothing) -- of a band of rows
+// [r0, r1).  It sweeps the rows r0 - 1 .. r1, computes (ux, uy) of its cells once per row (moments_exact, blocked: 0, 0)
+// and carries the three-row window in registers: a lattice row is read once per band, plus the two rows around the band.
+// The x neighbours inside the strip come from the adjacent lanes (shuffles); the two cells just outside it, x0 - 1 and
+// the cell behind the last VALID lane, both wrapped modulo nx, are gathered per owned row by lane 0 and by the last valid
+// lane as scalar nine-plane loads -- so a strip narrower than the wave (the ragged last strip, nx < 64 * V) takes cell 0's
+// velocity for the right neighbour of its last cell, not the next lane's.
+// Row -1 of a slab is `south`, row `rows` is `north`: each one whole lattice row (nine planes, plane_stride apart).  A
+// single periodic slab and a batch member pass their own rows rows - 1 and 0; a slab among several passes its edge
+// buffer, filled by the host from the neighbours' boundary rows -- the lattice halo rows are not read.  The mask rows -1
+// and `rows` are the mask's own halo rows.
+// The reduction is stats_cells': a cell that does not contribute is added with sign 0, the lanes are combined by
+// shuffles, the waves through LDS, the workgroups by 64-bit integer atomicAdd / atomicMax into `words`
+// (kEnstrophyWords, zeroed by the host before the launch; words that stayed 0 send nothing): no floating-point addition
+// happens on the device, and the words do not depend on the grid, the bands or scheduling.
+// Either of `field` (dense, row row_begin first, nx floats per row) and `words` may be null.  FIELD = false is the form
+// that never stores a field (`field` is not read): the recorder's; without the store's addresses it keeps two waves per
+// SIMD where the other form keeps one.
+constexpr int kVortMaxGroups = 512;   // two workgroups per CU; the waves stride over the units beyond
+constexpr int kVortMinBand = 8;       // the fewest rows of a band: at most 10 rows read for 8
+
+// uy of the cell x of a lattice row as lbm_read_final_state reports it: blocked -> 0
+__device__ __forceinline__ float vorticity_edge_uy(const float* row, const unsigned char* mrow, long plane_stride, int x) {
+  float f[kQ], rho, ux, uy;
+#pragma unroll
+  for (int k = 0; k < kQ; k++) f[k] = row[k * plane_stride + x];
+  moments_exact(f, rho, ux, uy);
+  return mrow[x] != 0 ? 0.f : uy;
+}
+
+template <int V, bool FIELD>
+__device__ __forceinline__ void vorticity_cells(const LatticeArgs& a, const float* src, const unsigned char* mask, const float* south,
+                                                const float* north, int rows, int row_begin, int row_end, int band_rows, unsigned cell_first,
+                                                float* field, long long* words) {
+  constexpr int L = lbm_exact::kExactLimbs, S = lbm_enstrophy::kEnstrophySums, W = lbm_enstrophy::kEnstrophyKeyWord + 1;
+  constexpr int kWaves = kBlock / 64, kSpan = 64 * V;
+  __shared__ long long sh[kWaves][W];
+  long long acc[S][L], bad = 0, n_fluid = 0;
+  unsigned long long key = 0ull;
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int i = 0; i < L; i++) acc[j][i] = 0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int strips = (a.nx + kSpan - 1) / kSpan;
+  const int bands = (row_end - row_begin + band_rows - 1) / band_rows;
+  const long n_units = (long)strips * bands;
+  for (long u = (long)blockIdx.x * kWaves + wave; u < n_units; u += (long)gridDim.x * kWaves) {  // (uniform over the wave)
+    const int band = (int)(u / strips), strip = (int)(u - (long)band * strips);
+    const int x0 = strip * kSpan, x = x0 + lane * V;
+    const bool valid = x < a.nx;  // (V == 4: nx % 4 == 0, so x + V <= nx)
+    const int n_valid = (a.nx - x0) / V < 64 ? (a.nx - x0) / V : 64;  // lanes of this strip with cells: 1 .. 64
+    const int last = n_valid - 1;
+    const int xl = x0 == 0 ? a.nx - 1 : x0 - 1;                        // the cell before the strip ...
+    const int xr = x0 + n_valid * V >= a.nx ? 0 : x0 + n_valid * V;    // ... and behind its last valid lane, both wrapped
+    const int r0 = row_begin + band * band_rows, r1 = (r0 + band_rows < row_end) ? r0 + band_rows : row_end;
+    // the window: ux of row rr - 2 (ux_a); ux, dvdx and the flags of row rr - 1 (_b); row rr is loaded (_c)
+    float ux_a[V], ux_b[V], dvdx_b[V];
+    unsigned fluid_b = 0u, fin_b = 0u;  // bit v: cell x + v is fluid / its own rho, jx, jy, usq are finite
+#pragma unroll
+    for (int v = 0; v < V; v++) ux_a[v] = ux_b[v] = dvdx_b[v] = 0.f;
+#pragma unroll 1
+    for (int rr = r0 - 1; rr <= r1; rr++) {
+      const float* row = rr < 0 ? south : (rr >= rows ? north : src + (long)rr * a.row_pitch);
+      const unsigned char* mrow = mask + (long)rr * a.pitch;
+      float f[V][kQ];
+      unsigned blocked = 0x01010101u;  // byte v: the mask of cell x + v; a lane without cells: blocked
+#pragma unroll
+      for (int v = 0; v < V; v++)
+#pragma unroll
+        for (int k = 0; k < kQ; k++) f[v][k] = 0.f;
+      if (valid) {
+        const float* p = row + x;
+        if constexpr (V == 4) {
+#pragma unroll
+          for (int k = 0; k < kQ; k++) {
+            const float4 q = *reinterpret_cast<const float4*>(p + k * a.plane_stride);
+            f[0][k] = q.x;  f[1][k] = q.y;  f[2][k] = q.z;  f[3][k] = q.w;
+          }
+          blocked = *reinterpret_cast<const unsigned*>(mrow + x);
+        } else {
+#pragma unroll
+          for (int k = 0; k < kQ; k++) f[0][k] = p[k * a.plane_stride];
+          blocked = mrow[x];
+        }
+      }
+      float ux_c[V], uy_c[V], dvdx_c[V];
+      unsigned fluid_c = 0u, fin_c = 0u;
+#pragma unroll
+      for (int v = 0; v < V; v++) {
+        const float(&g)[kQ] = f[v];
+        float rho, ux, uy;
+        moments_exact(g, rho, ux, uy);
+        const float jx = g[1] + g[5] + g[8] - (g[3] + g[6] + g[7]);
+        const float jy = g[2] + g[5] + g[6] - (g[4] + g[7] + g[8]);
+        const float usq = (ux * ux) + (uy * uy);
+        const bool fluid = ((blocked >> (8 * v)) & 0xffu) == 0u;
+        const bool finite = lbm_exact::exact_sum_finite(__float_as_uint(rho)) && lbm_exact::exact_sum_finite(__float_as_uint(jx)) &&
+                            lbm_exact::exact_sum_finite(__float_as_uint(jy)) && lbm_exact::exact_sum_finite(__float_as_uint(usq));
+        ux_c[v] = fluid ? ux : 0.f;
+        uy_c[v] = fluid ? uy : 0.f;
+        fluid_c |= (fluid ? 1u : 0u) << v;
+        fin_c |= (finite ? 1u : 0u) << v;
+        dvdx_c[v] = 0.f;
+      }
+      if (rr >= r0 && rr < r1) {  // (uniform) an owned row: its x differences; the rows around the band give ux alone
+        float west = __shfl_up(uy_c[V - 1], 1, 64), east = __shfl_down(uy_c[0], 1, 64);
+        if (lane == 0) west = vorticity_edge_uy(row, mrow, a.plane_stride, xl);
+        if (lane == last) east = vorticity_edge_uy(row, mrow, a.plane_stride, xr);
+#pragma unroll
+        for (int v = 0; v < V; v++) dvdx_c[v] = (v == V - 1 ? east : uy_c[v + 1 < V ? v + 1 : v]) - (v == 0 ? west : uy_c[v > 0 ? v - 1 : v]);
+      }
+      if (rr > r0) {  // (uniform) row e = rr - 1 is complete: ux_a is row e - 1's, ux_c row e + 1's
+        const int e = rr - 1;
+        const unsigned cell = cell_first + (unsigned)e * (unsigned)a.nx + (unsigned)x;
+        [[maybe_unused]] float w_out[V];
+#pragma unroll
+        for (int v = 0; v < V; v++) {
+          const bool fluid = ((fluid_b >> v) & 1u) != 0u;
+          const float dudy = ux_c[v] - ux_a[v];
+          const float w = fluid ? 0.5f * (dvdx_b[v] - dudy) : 0.f;
+          const float wsq = w * w;
+          if constexpr (FIELD) w_out[v] = w;
+          const unsigned b_w = __float_as_uint(w), b_wsq = __float_as_uint(wsq);
+          const bool finite = ((fin_b >> v) & 1u) != 0u && lbm_exact::exact_sum_finite(b_w) && lbm_exact::exact_sum_finite(b_wsq);
+          const int s = (fluid && finite) ? 1 : 0;
+          lbm_exact::exact_sum_add(acc[0], b_wsq, s);
+          lbm_exact::exact_sum_add(acc[1], b_w, s);
+          bad += (fluid && !finite) ? 1 : 0;
+          n_fluid += s;
+          const unsigned long long cell_key = lbm_stats::stats_key(__float_as_uint(fabsf(w)), cell + (unsigned)v);
+          key = (s && cell_key > key) ? cell_key : key;
+        }
+        if constexpr (FIELD) {
+          if (field && valid) {
+            float* out = field + (size_t)(e - row_begin) * a.nx + x;
+            if constexpr (V == 4)
+              *reinterpret_cast<float4*>(out) = make_float4(w_out[0], w_out[1], w_out[2], w_out[3]);
+            else
+              out[0] = w_out[0];
+          }
+        }
+      }
+#pragma unroll
+      for (int v = 0; v < V; v++) {
+        ux_a[v] = ux_b[v];
+        ux_b[v] = ux_c[v];
+        dvdx_b[v] = dvdx_c[v];
+      }
+      fluid_b = fluid_c;
+      fin_b = fin_c;
+    }
+  }
+  if (!words) return;  // (uniform) the field alone
+  auto wave_total = [&](long long t, int word) {
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+    if (lane == 0) sh[wave][word] = t;
+  };
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int i = 0; i < L; i++) wave_total(acc[j][i], j * L + i);
+  wave_total(bad, lbm_enstrophy::kEnstrophyBadWord);
+  wave_total(n_fluid, lbm_enstrophy::kEnstrophyFluidWord);
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long other = (unsigned long long)__shfl_down((long long)key, off, 64);
+    key = other > key ? other : key;
+  }
+  if (lane == 0) sh[wave][lbm_enstrophy::kEnstrophyKeyWord] = (long long)key;
+  __syncthreads();
+  if (threadIdx.x < W) {
+    unsigned long long* word = reinterpret_cast<unsigned long long*>(words + threadIdx.x);
+    if (threadIdx.x == lbm_enstrophy::kEnstrophyKeyWord) {
+      unsigned long long m = 0ull;
+      for (int w = 0; w < kWaves; w++) m = (unsigned long long)sh[w][threadIdx.x] > m ? (unsigned long long)sh[w][threadIdx.x] : m;
+      if (m != 0ull) atomicMax(word, m);
+    } else {
+      long long t = 0;
+      for (int w = 0; w < kWaves; w++) t += sh[w][threadIdx.x];
+      if (t != 0) atomicAdd(word, (unsigned long long)t);
+    }
+  }
+}
+
+// the rows [row_begin, row_end) of a slab's `rows` owned rows into `field` and / or its words of the ring row; cell_first:
+// the GLOBAL index of its first owned cell; grid: vorticity_groups (the host's rule) workgroups
+template <int V, bool FIELD>
+__global__ __launch_bounds__(kBlock) void vorticity_gather(const LatticeArgs a, const float* south, const float* north, int rows, int row_begin,
+                                                           int row_end, int band_rows, unsigned cell_first, float* field, long long* words) {
+  vorticity_cells<V, FIELD>(a, a.src, a.mask, south, north, rows, row_begin, row_end, band_rows, cell_first, field, words);
+}
+
+// vorticity_gather's twin for a batch: one sample of every member in one launch, workgroup (g, 0, member) on the member's
+// current lattice and mask (members[member]; `a` carries the strides all members share), a periodic slab each, into the
+// member's words of the row, [members][kEnstrophyWords]
+template <int V>
+__global__ __launch_bounds__(kBlock) void vorticity_gather_batch(const LatticeArgs a, const ResidentMember* members, int rows, int band_rows,
+                                                                 long long* row) {
+  const int member = blockIdx.z;
+  const float* src = members[member].src;
+  vorticity_cells<V, false>(a, src, members[member].mask, src + (long)(rows - 1) * a.row_pitch, src, rows, 0, rows, band_rows, 0u, nullptr,
+                     row + (size_t)member * lbm_enstrophy::kEnstrophyWords);
 }
 
 }  // namespace lbm
