@@ -932,6 +932,71 @@ int lbm_read_enstrophy(lbm_ctx* ctx, int max_rows, lbm_enstrophy_row* out, int* 
 int lbm_batch_set_enstrophy(lbm_batch* batch, int every, int capacity);
 int lbm_batch_read_enstrophy(lbm_batch* batch, int max_rows, lbm_enstrophy_row* out /* [n][members] */, int* steps, int* n_read);
 
+/* ---- stream function ------------------------------------------------------------------------
+ * The other field anyone draws of a lid-driven cavity, and the numbers it is validated by: the position of the primary
+ * and the secondary vortex centres and psi at them (Ghia et al.).  The one recorded quantity that is a PREFIX along an
+ * axis, not a total.
+ * Mass flux: per cell of the stored lattice, in fp32, no contraction, jx = g1 + g5 + g8 - (g3 + g6 + g7) -- the jx of the
+ * line profiles; rho, jy, ux, uy, usq as in the statistics' text above.  A fluid cell is NON-FINITE by the statistics'
+ * rule: one of its rho, jx, jy, usq is not finite.
+ * Term of a cell: t(x, y) = jx of a finite fluid cell; t(x, y) = 0 of a blocked cell and of a non-finite fluid cell.  (A
+ * blocked cell holds rebounded populations whose jx is not 0: it adds nothing.)
+ * The mass stream function is the inclusive prefix along y from the GLOBAL row 0:
+ *     psi(x, y) = round_to_double( exact sum of t(x, y') for y' = 0 .. y )
+ * The sum is taken EXACTLY (csrc/lbm_exact_sum.h) and rounded once, to nearest-even: math.fsum's value of the same terms.
+ * It is defined at every cell, blocked ones included: inside a wall psi is the wall's constant.  The exact sum never
+ * yields -0.0: a zero psi is +0.0.  Two ties to the rest, both bit for bit: psi(x, ny - 1) equals sum_jx of column line x
+ * of lbm_set_profiles on the same lattice; and no psi depends on the number of slabs, on the band height of the scan
+ * (LBM_PSI_BAND_ROWS), on the kernel family that advanced the lattice, or on how the calls were split.
+ * Extrema: over the finite fluid cells, compared as the rounded doubles (+0.0 and -0.0 are equal): psi_min at the GLOBAL
+ * cell (min_x, min_y), psi_max at (max_x, max_y); of several cells with that value the one with the smallest y*nx+x; 0 at
+ * -1, -1 when there is no finite fluid cell.
+ * lbm_read_psi(ctx, psi): the field of the current lattice, psi[row_count * nx] row-major.  Synchronises like the other
+ *   readers, needs nothing armed and changes nothing.  Works on lbm_create / lbm_create_tiled contexts of any slab count
+ *   and on batch member handles; refused on rank contexts (lbm_create_rank*).
+ * lbm_set_psi(ctx, every, capacity): from now on, after global timestep tt (0-based, the numbering of lbm_set_frames)
+ *   with tt % every == 0, record one row of the lattice after tt+1 timesteps.  Rows wait in a device ring of `capacity`
+ *   rows (64 bytes per row and slab); an lbm_run that would record more rows than are free fails before issuing any
+ *   work.  every == 0 disarms and frees; re-arming discards unread rows.  No step kernel records psi: as with the
+ *   statistics every call runs as the sub-calls that end at its sample steps, each followed per slab by a scan of three
+ *   sweeps over bands of rows -- psi_band_totals (a column's exact limbs per band), psi_band_bases (their exclusive
+ *   prefix over the bands), psi_scan (the band's rows again from its base, one rounding per cell, the extrema kept) -- and
+ *   psi_extrema (every == 1: correct, not fast).  On several slabs slab s+1 starts from the limbs of everything below
+ *   it: slab s leaves them in a buffer of its own, copied device to device behind an event; only these recorder-owned
+ *   buffers cross slabs -- the lattice's halo rows are not used.  The band height is chosen from the grid; LBM_PSI_BAND_ROWS
+ *   (read once per context, at its first scan) overrides it and never changes a bit.  Recording never changes the lattice
+ *   or av_vels: they equal those of the same run issued as calls split at the sample steps.
+ *   Refused, as lbm_set_enstrophy refuses: negative every; capacity < 1; a ring of 2 GiB or more; rank contexts
+ *   (lbm_create_rank*); batch members (a batch arms it as a whole: lbm_batch_set_psi); LBM_HALO_STALE /
+ *   LBM_HALO_FRESHEST (and lbm_set_halo_mode to those while armed); a context with another recorder armed (and the other
+ *   setters while this one is armed); lbm_run_until and lbm_run_until_residual while armed.  Not offered: psi of u
+ *   instead of j, trapezoid weights, the double engine, rank contexts, recording inside the resident or stream kernels,
+ *   a command-line (d2q9-bgk) mode.
+ * lbm_read_psi_rows: drains up to max_rows oldest rows into out[n] and steps[n] (their tt, may be NULL); out == NULL &&
+ *   steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers.
+ * lbm_batch_set_psi / lbm_batch_read_psi_rows: the same for every member of a batch, armed on the BATCH with one `every`
+ *   and ONE ring [slots][members][8 words]; rows are out[n][members].  Behind each sub-call that ends at a sample step the
+ *   batch's stream gets ONE launch of each of the four kernels for all members (grid z is the member).  Member i's rows,
+ *   lattice and av_vels are bit-identical to those of an lbm_create context armed with lbm_set_psi and advanced by the
+ *   same calls.  An lbm_batch_run without room fails before any work and moves no member's steps_done.  Refused as
+ *   lbm_batch_set_enstrophy refuses: a member with a recorder armed, another kind armed on the batch (and every
+ *   member-level setter and the five other batch-level setters while psi is armed); lbm_batch_run_until and
+ *   lbm_batch_run_until_residual while armed.
+ */
+typedef struct {
+  double    psi_min, psi_max;   /* over the finite fluid cells; 0, 0 when there is none */
+  long long nonfinite;          /* fluid cells that added nothing and were left out of the extrema */
+  int       min_x, min_y;       /* GLOBAL cell of psi_min; ties: smallest y*nx+x; -1,-1 when none */
+  int       max_x, max_y;
+  int       fluid;              /* finite fluid cells */
+  int       reserved;           /* 0 */
+} lbm_psi_row;                  /* 48 bytes; offsets 0 8 16 24 28 32 36 40 44 */
+int lbm_read_psi(lbm_ctx* ctx, double* psi /* [row_count*nx] */);
+int lbm_set_psi(lbm_ctx* ctx, int every, int capacity);
+int lbm_read_psi_rows(lbm_ctx* ctx, int max_rows, lbm_psi_row* out, int* steps, int* n_read);
+int lbm_batch_set_psi(lbm_batch* batch, int every, int capacity);
+int lbm_batch_read_psi_rows(lbm_batch* batch, int max_rows, lbm_psi_row* out /* [n][members] */, int* steps, int* n_read);
+
 /* ---- double precision -----------------------------------------------------------------------
  * The reference's programs are `float`, but its published golden results (the .dat files of check/) are its algorithm evaluated in
  * IEEE double.  A double context computes exactly that: the driver loop of SerialCode/d2q9-bgk.c:166-170 with every

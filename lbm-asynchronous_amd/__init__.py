@@ -58,6 +58,7 @@ ABI_SYMBOLS = (
     "lbm_run_until_residual", "lbm_batch_run_until_residual",
     "lbm_set_profiles", "lbm_read_profiles", "lbm_batch_set_profiles", "lbm_batch_read_profiles",
     "lbm_read_vorticity", "lbm_set_enstrophy", "lbm_read_enstrophy", "lbm_batch_set_enstrophy", "lbm_batch_read_enstrophy",
+    "lbm_read_psi", "lbm_set_psi", "lbm_read_psi_rows", "lbm_batch_set_psi", "lbm_batch_read_psi_rows",
     "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
     "lbm_double_sync", "lbm_double_read_av_vels", "lbm_double_read_cells", "lbm_double_read_final_state",
     "lbm_double_av_velocity", "lbm_double_total_density", "lbm_double_calc_reynolds",
@@ -285,6 +286,11 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_read_enstrophy.argtypes = [P, I, P, P, PI]; lib.lbm_read_enstrophy.restype = I
     lib.lbm_batch_set_enstrophy.argtypes = [P, I, I]; lib.lbm_batch_set_enstrophy.restype = I
     lib.lbm_batch_read_enstrophy.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_enstrophy.restype = I
+    lib.lbm_read_psi.argtypes = [P, P]; lib.lbm_read_psi.restype = I
+    lib.lbm_set_psi.argtypes = [P, I, I]; lib.lbm_set_psi.restype = I
+    lib.lbm_read_psi_rows.argtypes = [P, I, P, P, PI]; lib.lbm_read_psi_rows.restype = I
+    lib.lbm_batch_set_psi.argtypes = [P, I, I]; lib.lbm_batch_set_psi.restype = I
+    lib.lbm_batch_read_psi_rows.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_psi_rows.restype = I
     lib.lbm_set_residual.argtypes = [P, I, I]; lib.lbm_set_residual.restype = I
     lib.lbm_read_residual.argtypes = [P, I, P, P, PI]; lib.lbm_read_residual.restype = I
     lib.lbm_batch_set_residual.argtypes = [P, I, I]; lib.lbm_batch_set_residual.restype = I
@@ -751,6 +757,27 @@ class Engine:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], ENSTROPHY_DTYPE[n])."""
         return _drain_rows(self.lib.lbm_read_enstrophy, self.lib, self.handle, "enstrophy", max_rows, (), ENSTROPHY_DTYPE, np.zeros)
 
+    # -- stream function (lbm_read_psi / lbm_set_psi / lbm_read_psi_rows) ----------------------------
+    def psi(self) -> np.ndarray:
+        """The mass stream function of the current lattice, float64 (row_count, nx): psi[y, x] = the exact sum of j_x over
+        the finite fluid cells (x, 0 .. y), rounded once (math.fsum's value); blocked and non-finite cells add 0.  Needs
+        nothing armed and changes nothing."""
+        out = np.empty((self.info()["row_count"], self.params.nx), dtype=np.float64)
+        _check(self.lib, self.lib.lbm_read_psi(self.handle, out.ctypes.data))
+        return out
+
+    def set_psi(self, every: int, capacity: int = 4096) -> None:
+        """Record one row of the stream function's extrema over the finite fluid cells -- psi_min and psi_max with their
+        cells (the vortex centres), ties to the smallest y*nx+x, and the counts -- after every global timestep tt with
+        tt % every == 0, for the lattice after tt + 1 steps, into a device ring of `capacity` rows.  every == 0 disarms;
+        re-arming discards unread rows."""
+        every, capacity = _psi_args(every, capacity)
+        _check(self.lib, self.lib.lbm_set_psi(self.handle, every, capacity))
+
+    def psi_rows(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], PSI_DTYPE[n])."""
+        return _drain_rows(self.lib.lbm_read_psi_rows, self.lib, self.handle, "psi_rows", max_rows, (), PSI_DTYPE, np.zeros)
+
     # -- velocity residuals (lbm_set_residual / lbm_read_residual) ---------------------------------
     def set_residual(self, every: int, capacity: int = 4096) -> None:
         """Remember the velocity field of the current lattice (the baseline) and, after every global timestep tt with
@@ -1069,6 +1096,18 @@ class Batch:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], ENSTROPHY_DTYPE[n, members])."""
         return _drain_rows(self.lib.lbm_batch_read_enstrophy, self.lib, self._live(), "enstrophy", max_rows, (len(self),),
                            ENSTROPHY_DTYPE, np.zeros)
+
+    # -- stream function of all members (lbm_batch_set_psi / lbm_batch_read_psi_rows) ---------------------------------------
+    def set_psi(self, every: int, capacity: int = 4096) -> None:
+        """Engine.set_psi for every member at once: one `every` and `capacity` for the batch, rows in one device ring, one
+        launch of each of the scan's kernels per sample for all members.  every == 0 disarms."""
+        every, capacity = _psi_args(every, capacity)
+        _check(self.lib, self.lib.lbm_batch_set_psi(self._live(), every, capacity))
+
+    def psi_rows(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], PSI_DTYPE[n, members])."""
+        return _drain_rows(self.lib.lbm_batch_read_psi_rows, self.lib, self._live(), "psi_rows", max_rows, (len(self),),
+                           PSI_DTYPE, np.zeros)
 
     # -- velocity residuals of all members (lbm_batch_set_residual / lbm_batch_read_residual) ------------------------
     def set_residual(self, every: int, capacity: int = 4096) -> None:
@@ -1417,6 +1456,42 @@ def write_enstrophy(path: str, steps, rows) -> None:
             fh.write("%d:\t%.12E\t%.12E\t%.12E\t%d\t%d\t%d\t%d\n" % (
                 tt, float(r["enstrophy"]), float(r["circulation"]), float(r["max_abs_w"]), int(r["max_x"]), int(r["max_y"]),
                 int(r["fluid"]), int(r["nonfinite"])))
+
+
+# lbm_psi_row of include/lbm_hip.h, 48 bytes
+PSI_DTYPE = np.dtype([("psi_min", "<f8"), ("psi_max", "<f8"), ("nonfinite", "<i8"), ("min_x", "<i4"), ("min_y", "<i4"),
+                      ("max_x", "<i4"), ("max_y", "<i4"), ("fluid", "<i4"), ("reserved", "<i4")])
+
+
+def _psi_args(every, capacity) -> tuple[int, int]:
+    """Engine.set_psi's argument checks (no device needed): (every, capacity)."""
+    return _every_capacity("set_psi", every, capacity, "row")
+
+
+def write_psi_rows(path: str, steps, rows) -> None:
+    """One line per row in write_enstrophy's style: tt, a colon, then tab-separated psi_min and psi_max as '%.12E' and
+    min_x, min_y, max_x, max_y, fluid and nonfinite as '%d'; `steps` int[n], `rows` PSI_DTYPE[n] (Engine.psi_rows)."""
+    rows = np.asarray(rows)
+    steps = np.asarray(steps).ravel()
+    if rows.dtype != PSI_DTYPE or rows.ndim != 1 or rows.shape[0] != steps.size:
+        raise LbmError(f"write_psi_rows: rows must be {steps.size} rows of PSI_DTYPE (got shape {rows.shape}, dtype {rows.dtype})")
+    with open(path, "w") as fh:
+        for tt, r in zip(steps.tolist(), rows):
+            fh.write("%d:\t%.12E\t%.12E\t%d\t%d\t%d\t%d\t%d\t%d\n" % (
+                tt, float(r["psi_min"]), float(r["psi_max"]), int(r["min_x"]), int(r["min_y"]), int(r["max_x"]), int(r["max_y"]),
+                int(r["fluid"]), int(r["nonfinite"])))
+
+
+def write_psi(path: str, psi) -> None:
+    """The field Engine.psi() gives, one 'x y psi' line per cell, rows from y = 0, psi as '%.12E': the input a contour
+    plot needs."""
+    psi = np.asarray(psi)
+    if psi.dtype != np.float64 or psi.ndim != 2:
+        raise LbmError(f"write_psi: psi must be a float64 array of shape (ny, nx) (got shape {psi.shape}, dtype {psi.dtype})")
+    with open(path, "w") as fh:
+        for y in range(psi.shape[0]):
+            for x, v in enumerate(psi[y].tolist()):
+                fh.write("%d %d %.12E\n" % (x, y, v))
 
 
 # lbm_profile_line of include/lbm_hip.h, 48 bytes

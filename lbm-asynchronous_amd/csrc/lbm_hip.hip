@@ -265,6 +265,12 @@ struct Slab {
   DeviceBuf<float> vort_edges;             // lbm_set_enstrophy, several slabs: [2][row_pitch]: the south and the north neighbour's
                                            // boundary row of the current lattice, copied in front of every vorticity_gather
   Event ev_vort_ready, ev_vort_done;       // ... this slab's rows may be copied / the copies of this slab's sample have been used
+  DeviceBuf<long long> psi_totals;         // lbm_set_psi: [bands][nx][kExactLimbs]: the scan's band totals, then in place the bands' bases
+  DeviceBuf<lbm::PsiCandidate> psi_cand;   // ... [bands][column groups]: the workgroups' extrema of a sample
+  int psi_band_rows = 0;                   // ... rows of a band of this slab's scan
+  DeviceBuf<long long> psi_in, psi_out;    // ... several slabs: [nx][kExactLimbs]: the limbs of every column below this slab (a copy of
+                                           // the slab below's psi_out) and up to its last row
+  Event ev_psi_out, ev_psi_taken;          // ... psi_out is written / the slab above has copied it
   // freshest-available mode (LBM_HALO_FRESHEST), allocated at its first use in this order: whole once ev_fresh[1] exists
   DeviceBuf<float> fresh_stage;          // [parity][side: 0 south halo, 1 north halo][row_pitch]: this pass's rows, if they make it
   DeviceBuf<unsigned> fresh_arrived;     // [parity][side]: id (global step + 1) of the step whose row the staging holds
@@ -420,14 +426,17 @@ struct GraphBuilder {
 // Line profiles (lbm_set_profiles) likewise, by profile_rows and profile_columns: a record of per-row and per-column sums.
 // The enstrophy (lbm_set_enstrophy) likewise, by vorticity_gather: a row of whole-lattice sums of the vorticity, the one
 // kind whose kernel reads rows a slab does not own (Slab::vort_edges).
-// These five gather kinds (records_behind) share one ring of int64 words per slab, Slab::gather_ring, whose slot holds
+// The stream function (lbm_set_psi) likewise, by a scan of three sweeps and psi_extrema: a row of the extrema of psi, the
+// one kind whose slabs depend on each other (Slab::psi_in, psi_out).
+// These six gather kinds (records_behind) share one ring of int64 words per slab, Slab::gather_ring, whose slot holds
 // gather_slot_words words; a batch arms them on itself (lbm_batch::rec) with one ring for all members.
 enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean,
        kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecResidual = 7, kRecProfiles = 8, kRecEnstrophy = 9,
-       kRecKinds = 10 };
+       kRecPsi = 10, kRecKinds = 11 };
 // the kinds recorded by a gather launch behind the sub-call that ends at a sample step, whatever kernels advance the lattice
 constexpr bool records_behind(int kind) {
-  return kind == kRecForces || kind == kRecStats || kind == kRecResidual || kind == kRecProfiles || kind == kRecEnstrophy;
+  return kind == kRecForces || kind == kRecStats || kind == kRecResidual || kind == kRecProfiles || kind == kRecEnstrophy ||
+         kind == kRecPsi;
 }
 struct Recorder {
   int kind = kRecNone;
@@ -471,7 +480,9 @@ constexpr RecorderKind kRecorderKinds[kRecKinds] = {
     {.name = "line profiles", .noun = "profiles", .record = "record", .setter = "lbm_set_profiles",
      .reader = "lbm_read_profiles", .disarm = "lbm_set_profiles(ctx, 0, 0, 0)"},
     {.name = "enstrophy rows", .noun = "enstrophy", .record = "row", .setter = "lbm_set_enstrophy",
-     .reader = "lbm_read_enstrophy", .disarm = "lbm_set_enstrophy(ctx, 0, 0)"}};
+     .reader = "lbm_read_enstrophy", .disarm = "lbm_set_enstrophy(ctx, 0, 0)"},
+    {.name = "stream function rows", .noun = "the stream function", .record = "row", .setter = "lbm_set_psi",
+     .reader = "lbm_read_psi_rows", .disarm = "lbm_set_psi(ctx, 0, 0)"}};
 
 struct lbm_ctx {
   lbm_params p;
@@ -516,6 +527,7 @@ struct lbm_ctx {
   DeviceBuf<lbm_residual::UntilState> until_state;  // device: what the checks of the current call have found
   DeviceBuf<long long> until_history;               // device: [until_history_rows][kResidualWords]: the words of the first checks
   size_t until_history_rows = 0;                    // (until_history_begin: kept from call to call while they suffice)
+  int psi_band_env = -1;  // LBM_PSI_BAND_ROWS, read once at the context's first scan (psi_band_rows): 0: not set
 };
 
 // B independent single-slab lattices of one shape on one device, advanced together (lbm_create_batch).  The members
@@ -538,7 +550,7 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentProbes> probe_table;  // device: [members], allocated when the first member arms probes
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
   DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
-  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
+  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
                                     // (a batch records one kind, so at most one count is non-zero; a gather kind is armed
                                     // on the batch, by its lbm_batch_set_* of kBatchKinds, and counts as one)
   // the gather kinds (records_behind) of all members: the members' own recorders stay off, the batch keeps the one
@@ -547,6 +559,9 @@ struct lbm_batch {
   Recorder rec;                                  // one of kBatchKinds while armed
   DeviceBuf<long long> gather_ring;              // device: [slots][members][a member's gather_slot_words]
   DeviceBuf<float> residual_planes;              // lbm_batch_set_residual: device: [members][2][rows][nx]: the members' remembered u_x and u_y
+  DeviceBuf<long long> psi_totals;               // lbm_batch_set_psi: device: [members][bands][nx][kExactLimbs]: the scan's totals, then bases
+  DeviceBuf<lbm::PsiCandidate> psi_cand;         // ... [members][bands][column groups]
+  int psi_band_rows = 0;                         // ... rows of a band of every member's scan
   int force_bodies = 0;                          // lbm_batch_set_forces: bodies of every member
   int force_groups = 0;                          // workgroups per (member, body) of force_gather_batch (0: no member has a link)
   std::vector<int> force_link_counts;            // [members][bodies]
@@ -577,6 +592,7 @@ static int take_batch_stats(lbm_batch* bt, long long* row);
 static int take_batch_residual(lbm_batch* bt, long long* row);
 static int take_batch_profiles(lbm_batch* bt, long long* record);
 static int take_batch_enstrophy(lbm_batch* bt, long long* row);
+static int take_batch_psi(lbm_batch* bt, long long* row);
 struct BatchKind {
   int kind;
   const char* setter;
@@ -589,7 +605,8 @@ static const BatchKind kBatchKinds[] = {
     {kRecStats, "lbm_batch_set_stats", "lbm_batch_read_stats", "lbm_batch_set_stats(batch, 0, 0)", take_batch_stats},
     {kRecResidual, "lbm_batch_set_residual", "lbm_batch_read_residual", "lbm_batch_set_residual(batch, 0, 0)", take_batch_residual},
     {kRecProfiles, "lbm_batch_set_profiles", "lbm_batch_read_profiles", "lbm_batch_set_profiles(batch, 0, 0, 0)", take_batch_profiles},
-    {kRecEnstrophy, "lbm_batch_set_enstrophy", "lbm_batch_read_enstrophy", "lbm_batch_set_enstrophy(batch, 0, 0)", take_batch_enstrophy}};
+    {kRecEnstrophy, "lbm_batch_set_enstrophy", "lbm_batch_read_enstrophy", "lbm_batch_set_enstrophy(batch, 0, 0)", take_batch_enstrophy},
+    {kRecPsi, "lbm_batch_set_psi", "lbm_batch_read_psi_rows", "lbm_batch_set_psi(batch, 0, 0)", take_batch_psi}};
 static const BatchKind* batch_kind(int kind) {
   for (const BatchKind& k : kBatchKinds)
     if (k.kind == kind) return &k;
@@ -1410,10 +1427,11 @@ const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = f
   static const Form forms[2][kRecKinds] = {
       {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>, resident_form<false, kRecMean>,
        resident_form<false, kRecFields>, resident_form<false, kRecNone>, resident_form<false, kRecNone>,
-       resident_form<false, kRecNone>, resident_form<false, kRecNone>, resident_form<false, kRecNone>},  // (the gather kinds run the plain form)
+       resident_form<false, kRecNone>, resident_form<false, kRecNone>, resident_form<false, kRecNone>,
+       resident_form<false, kRecNone>},  // (the gather kinds run the plain form)
       {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>, resident_form<true, kRecMean>,
        resident_form<true, kRecFields>, resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>,
-       resident_form<true, kRecNone>, resident_form<true, kRecNone>}};
+       resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>}};
   return forms[batch][rec]((rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
 }
 
@@ -1745,6 +1763,83 @@ int await_vorticity_done(lbm_ctx* c) {
   return LBM_SUCCESS;
 }
 
+// rows of a band of the stream function's scan (psi_band_totals, psi_band_bases, psi_scan) for `rows` rows of nx cells:
+// LBM_PSI_BAND_ROWS where it is set (read once per context), else, as profile_band_rows, about kProfileTargetGroups
+// workgroups where the grid has that many bands of kPsiMinBand rows.  The height changes no bit of any psi.
+int psi_band_rows(lbm_ctx* c, int rows, int nx) {
+  if (c->psi_band_env < 0) {
+    const int env = lbm_plan::env_int("LBM_PSI_BAND_ROWS", 0);
+    c->psi_band_env = env > 0 ? env : 0;
+  }
+  if (c->psi_band_env > 0) return c->psi_band_env;
+  const int col_groups = ceil_div(nx, lbm::kPsiColumns);
+  const int bands = kProfileTargetGroups / col_groups > 1 ? kProfileTargetGroups / col_groups : 1;
+  const int band_rows = ceil_div(rows, bands);
+  return band_rows > lbm::kPsiMinBand ? band_rows : lbm::kPsiMinBand;
+}
+// elements of the scan's two scratch buffers for one slab or member
+size_t psi_total_words(int rows, int nx, int band_rows) { return (size_t)ceil_div(rows, band_rows) * nx * lbm_exact::kExactLimbs; }
+size_t psi_candidates(int rows, int nx, int band_rows) { return (size_t)ceil_div(rows, band_rows) * ceil_div(nx, lbm::kPsiColumns); }
+
+// the first two sweeps of a slab's scan on its compute stream: the band totals, then the bands' bases in place, from the
+// limbs below the slab (`incoming`, nullptr: it is the lowest) and with the limbs up to its last row left in `outgoing`
+// (nullptr: nobody asks)
+void launch_psi_totals(const lbm_ctx* c, const Slab& sl, int band_rows, long long* totals) {
+  const int nx = c->p.nx;
+  hipLaunchKernelGGL(lbm::psi_band_totals, dim3(ceil_div(nx, lbm::kPsiColumns), ceil_div(sl.rows, band_rows)), dim3(lbm::kBlock), 0,
+                     sl.compute, lattice_args(c, sl), sl.rows, band_rows, totals);
+}
+void launch_psi_bases(const lbm_ctx* c, const Slab& sl, int band_rows, long long* totals, const long long* incoming, long long* outgoing) {
+  const int nx = c->p.nx;
+  hipLaunchKernelGGL(lbm::psi_band_bases, dim3(ceil_div(nx * lbm_exact::kExactLimbs, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.compute, nx, ceil_div(sl.rows, band_rows),
+                     totals, incoming, outgoing);
+}
+
+// One stream-function sample of every slab into its zeroed slot of the ring.  The totals of all slabs run side by side;
+// then the slabs are chained from the lowest up: slab s copies slab s-1's psi_out (behind its ev_psi_out) into its own
+// psi_in, forms its bases and its psi_out, scans and reduces.  Slab s-1's next sample overwrites its psi_out only behind
+// slab s's copy (ev_psi_taken).  Issued by the calling thread, slab after slab: the chain has an order.
+size_t gather_slot_words(const lbm_ctx* c, const Slab& sl);
+long long* zeroed_slot(long long* ring, size_t slot_words, const Recorder& r, hipStream_t stream);
+int take_psi_record(lbm_ctx* c) {
+  const int nx = c->p.nx;
+  const size_t base_bytes = (size_t)nx * lbm_exact::kExactLimbs * sizeof(long long);
+  long long* words[kMaxSlabs];
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    if (!(words[s] = zeroed_slot(sl.gather_ring, gather_slot_words(c, sl), c->rec, sl.compute))) return LBM_FAILURE;
+    launch_psi_totals(c, sl, sl.psi_band_rows, sl.psi_totals);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+  }
+  const bool chain = c->n_slabs > 1;
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    if (chain && s > 0) {
+      HIP_TRY(LBM_FAILURE, hipStreamWaitEvent(sl.compute, c->slab[s - 1].ev_psi_out, 0));
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(sl.psi_in, c->slab[s - 1].psi_out, base_bytes, hipMemcpyDefault, sl.compute));
+      HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_psi_taken, sl.compute));
+    }
+    const bool hands_on = chain && s + 1 < c->n_slabs;
+    launch_psi_bases(c, sl, sl.psi_band_rows, sl.psi_totals, (chain && s > 0) ? sl.psi_in.get() : nullptr, hands_on ? sl.psi_out.get() : nullptr);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    if (hands_on) HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_psi_out, sl.compute));
+    const dim3 grid(ceil_div(nx, lbm::kPsiColumns), ceil_div(sl.rows, sl.psi_band_rows));
+    hipLaunchKernelGGL(lbm::psi_scan<false>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, sl.psi_band_rows, 0,
+                       (const long long*)sl.psi_totals, (unsigned)sl.row_first * (unsigned)nx, (double*)nullptr, sl.psi_cand.get());
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    hipLaunchKernelGGL(lbm::psi_extrema, dim3(1), dim3(64), 0, sl.compute, (const lbm::PsiCandidate*)sl.psi_cand, (int)(grid.x * grid.y), words[s]);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+  }
+  if (chain)
+    for (int s = 0; s + 1 < c->n_slabs; s++) {  // the next sample's psi_band_bases of slab s runs behind slab s+1's copy
+      HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
+      HIP_TRY(LBM_FAILURE, hipStreamWaitEvent(c->slab[s].compute, c->slab[s + 1].ev_psi_taken, 0));
+    }
+  return LBM_SUCCESS;
+}
+
 // int64 words a gather kind records per slab (or batch member) and sample: of `bodies` bodies (forces), of `rows` rows of
 // nx cells along `axes` (profiles).  The one place a slot's size is computed: the setters call it with what they are about
 // to arm, everything else through gather_slot_words with what is armed.
@@ -1755,6 +1850,7 @@ size_t gather_words(int kind, size_t bodies = 0, int rows = 0, int nx = 0, int a
     case kRecResidual: return lbm_residual::kResidualWords;
     case kRecProfiles: return lbm_profile::profile_slab_lines(rows, nx, axes) * lbm_profile::kProfileWords;
     case kRecEnstrophy: return lbm_enstrophy::kEnstrophyWords;
+    case kRecPsi: return lbm_psi::kPsiWords;
     default: return 0;
   }
 }
@@ -1798,6 +1894,11 @@ int take_record(lbm_ctx* c) {
   const size_t n_probes = c->probe_cells.size();
   const bool vort_edges = (c->rec.kind == kRecEnstrophy && c->n_slabs > 1);  // the sample reads the neighbours' boundary rows
   if (vort_edges && mark_vorticity_ready(c) != LBM_SUCCESS) return LBM_FAILURE;
+  if (c->rec.kind == kRecPsi) {  // the slabs depend on each other: issued in their order
+    if (take_psi_record(c) != LBM_SUCCESS) return LBM_FAILURE;
+    c->rec.written++;
+    return LBM_SUCCESS;
+  }
   if (for_slabs(c, [&](int s) -> int {
         Slab& sl = c->slab[s];
         HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
@@ -2567,6 +2668,11 @@ void release_recorder(lbm_ctx* c) {
     sl.force_groups = 0;
     sl.residual_planes.reset();
     sl.vort_edges.reset();
+    sl.psi_totals.reset();
+    sl.psi_cand.reset();
+    sl.psi_in.reset();
+    sl.psi_out.reset();
+    sl.psi_band_rows = 0;
     sl.probe_count = 0;
   }
   c->probe_cells.clear();
@@ -2727,6 +2833,9 @@ void release_batch_recorder(lbm_batch* bt) {
   (void)hipSetDevice(bt->members[0]->slab[0].device);
   bt->gather_ring.reset();
   bt->residual_planes.reset();
+  bt->psi_totals.reset();
+  bt->psi_cand.reset();
+  bt->psi_band_rows = 0;
   bt->force_lists.reset();
   bt->force_links.clear();
   bt->force_starts.clear();
@@ -3534,6 +3643,103 @@ int lbm_read_vorticity(lbm_ctx* c, float* w) {
   return LBM_SUCCESS;
 }
 
+// ---- stream function ---------------------------------------------------------------------------------------------------
+int lbm_set_psi(lbm_ctx* c, int every, int capacity) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_psi: null context");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_psi: negative interval %d", every);
+  const long long kRowBytes = (long long)(gather_words(kRecPsi) * sizeof(long long));
+  if (every > 0) {
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_psi: capacity %d, at least one row is needed", capacity);
+    if ((long long)capacity * kRowBytes >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_set_psi: a ring of %d rows is 2 GiB or more (%d bytes per row)", capacity, (int)kRowBytes);
+    if (c->ranked || c->world > 1)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_psi: not available in a multi-process (rank) context: a column's prefix would be spread over the ranks");
+    if (c->batch)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_psi: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
+               "end at, so the stream function of a batch is armed on the batch, with one `every` for all members (lbm_batch_set_psi)");
+  }
+  return rearm_recorder(c, kRecPsi, every, capacity, [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * (size_t)kRowBytes;
+    const int nx = c->p.nx;
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      sl.psi_band_rows = psi_band_rows(c, sl.rows, nx);
+      const size_t base_words = (size_t)nx * lbm_exact::kExactLimbs;
+      bool ok = sl.gather_ring.alloc_bytes(ring_bytes) == hipSuccess &&
+                sl.psi_totals.alloc(psi_total_words(sl.rows, nx, sl.psi_band_rows)) == hipSuccess &&
+                sl.psi_cand.alloc(psi_candidates(sl.rows, nx, sl.psi_band_rows)) == hipSuccess;
+      if (ok && c->n_slabs > 1) {
+        ok = sl.psi_in.alloc(base_words) == hipSuccess && sl.psi_out.alloc(base_words) == hipSuccess;
+        if (ok && !sl.ev_psi_out) ok = sl.ev_psi_out.create(hipEventDisableTiming) == hipSuccess;
+        if (ok && !sl.ev_psi_taken) ok = sl.ev_psi_taken.create(hipEventDisableTiming) == hipSuccess;
+      }
+      if (!ok)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_psi: cannot allocate %d rows (%.1f MiB per slab) and the scan's buffers; the stream function stays off",
+                 capacity, (double)ring_bytes / 1048576.0);
+    }
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_read_psi_rows(lbm_ctx* c, int max_rows, lbm_psi_row* out, int* steps, int* n_read) {
+  return drain_recorder(c, kRecPsi, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
+    // rows[row][slab][words]: the slabs' candidates of a row are merged by psi_row_from_words
+    std::vector<long long> rows;
+    size_t row_words;
+    if (fetch_gather_records(c, n, rows, &row_words) != LBM_SUCCESS) return LBM_FAILURE;
+    for (int i = 0; i < n; i++) out[i] = lbm_psi::psi_row_from_words(rows.data() + (size_t)i * row_words, c->n_slabs, c->p.nx);
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_read_psi(lbm_ctx* c, double* psi) {
+  if (!c || !psi) LBM_FAIL(LBM_FAILURE, "lbm_read_psi: NULL argument");
+  if (c->ranked || c->world > 1)
+    LBM_FAIL(LBM_FAILURE, "lbm_read_psi: not available in a multi-process (rank) context: the rows below this rank's belong to other processes");
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
+  const int nx = c->p.nx;
+  const size_t base_words = (size_t)nx * lbm_exact::kExactLimbs;
+  DeviceBuf<long long> below;  // the limbs up to the last row of the slab below, on that slab's device
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    // the call's own buffers: nothing armed is touched.  Every stream is idle (lbm_sync) and every slab is finished before
+    // the next begins: no events needed
+    const int band_rows = psi_band_rows(c, sl.rows, nx), bands = ceil_div(sl.rows, band_rows);
+    long chunk_bands = (256L << 20) / ((long)band_rows * nx * (long)sizeof(double));  // a staging buffer of at most 256 MiB, or one band
+    if (chunk_bands < 1) chunk_bands = 1;
+    if (chunk_bands > bands) chunk_bands = bands;
+    DeviceBuf<long long> totals, incoming, outgoing;
+    DeviceBuf<double> stage;
+    HIP_TRY(LBM_FAILURE, totals.alloc(psi_total_words(sl.rows, nx, band_rows)));
+    HIP_TRY(LBM_FAILURE, stage.alloc((size_t)chunk_bands * band_rows * nx));
+    if (s > 0) {
+      HIP_TRY(LBM_FAILURE, incoming.alloc(base_words));
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(incoming, below, base_words * sizeof(long long), hipMemcpyDefault, sl.compute));
+    }
+    if (s + 1 < c->n_slabs) HIP_TRY(LBM_FAILURE, outgoing.alloc(base_words));
+    launch_psi_totals(c, sl, band_rows, totals);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    launch_psi_bases(c, sl, band_rows, totals, s > 0 ? incoming.get() : nullptr, s + 1 < c->n_slabs ? outgoing.get() : nullptr);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    for (int b0 = 0; b0 < bands; b0 += (int)chunk_bands) {
+      const int nb = (bands - b0 < chunk_bands) ? bands - b0 : (int)chunk_bands;
+      const int r0 = b0 * band_rows, r1 = (b0 + nb) * band_rows < sl.rows ? (b0 + nb) * band_rows : sl.rows;
+      hipLaunchKernelGGL(lbm::psi_scan<true>, dim3(ceil_div(nx, lbm::kPsiColumns), nb), dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl),
+                         sl.rows, band_rows, b0, (const long long*)totals, (unsigned)sl.row_first * (unsigned)nx, stage.get(),
+                         (lbm::PsiCandidate*)nullptr);
+      HIP_TRY(LBM_FAILURE, hipGetLastError());
+      HIP_TRY(LBM_FAILURE, hipMemcpyAsync(psi + (size_t)(sl.row_first - c->row_first + r0) * nx, stage, (size_t)(r1 - r0) * nx * sizeof(double),
+                                          hipMemcpyDeviceToHost, sl.compute));
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+    }
+    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+    below = std::move(outgoing);
+  }
+  return LBM_SUCCESS;
+}
+
 // the span of the row with ordinal `ord` since arming: from the baseline to the first sample, then `every`
 static int residual_span(const Recorder& r, long long ord) {
   return ord == 0 ? (int)((long long)r.ord0 * r.every + 1 - r.base_steps) : r.every;
@@ -4059,6 +4265,29 @@ static int take_batch_enstrophy(lbm_batch* bt, long long* row) {
   return LBM_SUCCESS;
 }
 
+// the stream function: ONE launch of each of the scan's kernels for all members (grid z is the member; psi_extrema: grid x),
+// each member a grid of its own from row 0
+static int take_batch_psi(lbm_batch* bt, long long* row) {
+  lbm_ctx* c0 = bt->members[0];
+  const unsigned n_members = (unsigned)bt->members.size();
+  const Slab& sl0 = c0->slab[0];
+  const int nx = c0->p.nx, band_rows = bt->psi_band_rows, bands = ceil_div(sl0.rows, band_rows);
+  const dim3 grid((unsigned)ceil_div(nx, lbm::kPsiColumns), (unsigned)bands, n_members);
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  hipLaunchKernelGGL(lbm::psi_band_totals_batch, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, band_rows,
+                     bt->psi_totals.get());
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  hipLaunchKernelGGL(lbm::psi_band_bases, dim3((unsigned)ceil_div(nx * lbm_exact::kExactLimbs, lbm::kBlock), 1, n_members), dim3(lbm::kBlock), 0, bt->stream, nx, bands,
+                     bt->psi_totals.get(), (const long long*)nullptr, (long long*)nullptr);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  hipLaunchKernelGGL(lbm::psi_scan_batch, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, band_rows,
+                     (const long long*)bt->psi_totals, bt->psi_cand.get());
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  hipLaunchKernelGGL(lbm::psi_extrema, dim3(n_members), dim3(64), 0, bt->stream, (const lbm::PsiCandidate*)bt->psi_cand, (int)(grid.x * grid.y), row);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+
 // ONE residual_gather_batch launch over all members' current (stored) lattices and planes, on the batch's stream:
 // the baseline (`planes` filled, `row` unused) or a sample against `planes` into `row`, [members][kResidualWords], which
 // the caller has zeroed in front
@@ -4267,6 +4496,39 @@ int lbm_batch_read_enstrophy(lbm_batch* bt, int max_rows, lbm_enstrophy_row* out
     // every member's words become its row
     for (size_t j = 0; j < (size_t)n * bt->members.size(); j++)
       out[j] = lbm_enstrophy::enstrophy_row_from_words(words + j * lbm_enstrophy::kEnstrophyWords, 1, bt->members[0]->p.nx);
+  });
+}
+
+// ---- stream function of a batch ---------------------------------------------------------------------------------------
+int lbm_batch_set_psi(lbm_batch* bt, int every, int capacity) {
+  size_t row_bytes = 0;  // of all members
+  return rearm_batch_recorder(bt, kRecPsi, every, capacity, [&]() -> int {
+    const size_t n_members = bt->members.size();
+    row_bytes = n_members * gather_words(kRecPsi) * sizeof(long long);
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_psi: capacity %d, at least one row is needed", capacity);
+    if ((long long)capacity * (long long)row_bytes >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_psi: a ring of %d rows of %d members is %.2f GiB, 2 GiB or more (%d bytes per member and row)",
+               capacity, (int)n_members, (double)capacity * (double)row_bytes / 1073741824.0, lbm_psi::kPsiWords * (int)sizeof(long long));
+    return LBM_SUCCESS;
+  }, [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * row_bytes, n_members = bt->members.size();
+    lbm_ctx* c0 = bt->members[0];
+    const int rows = c0->slab[0].rows, nx = c0->p.nx;
+    bt->psi_band_rows = psi_band_rows(c0, rows, nx);
+    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess ||
+        bt->psi_totals.alloc(n_members * psi_total_words(rows, nx, bt->psi_band_rows)) != hipSuccess ||
+        bt->psi_cand.alloc(n_members * psi_candidates(rows, nx, bt->psi_band_rows)) != hipSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_psi: cannot allocate %d rows of %d members (%.1f MiB) and the scan's buffers; the stream function stays off",
+               capacity, (int)n_members, (double)ring_bytes / 1048576.0);
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_batch_read_psi_rows(lbm_batch* bt, int max_rows, lbm_psi_row* out, int* steps, int* n_read) {
+  return drain_batch_recorder(bt, kRecPsi, max_rows, out != nullptr, steps, n_read, [&](int n, const long long* words) {
+    // every member's words become its row
+    for (size_t j = 0; j < (size_t)n * bt->members.size(); j++)
+      out[j] = lbm_psi::psi_row_from_words(words + j * lbm_psi::kPsiWords, 1, bt->members[0]->p.nx);
   });
 }
 

@@ -39,6 +39,8 @@
 #include "lbm_residual_row.h"
 #include "lbm_profile_row.h"
 #include "lbm_enstrophy_row.h"
+#include "lbm_psi_row.h"
+#include "lbm_exact_round.h"
 #include "lbm_residual_until.h"
 
 namespace lbm {
@@ -52,7 +54,8 @@ constexpr int kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3, kRecFi
 // lbm_batch_set_stats, the velocity residuals, lbm_set_residual / lbm_batch_set_residual, and the line profiles,
 // lbm_set_profiles / lbm_batch_set_profiles, are recorder kinds of the host alone: force_gather, stats_gather,
 // residual_gather, profile_rows, profile_columns and their batch twins run behind the step kernels; so does the
-// vorticity's vorticity_gather, lbm_set_enstrophy / lbm_batch_set_enstrophy)
+// vorticity's vorticity_gather, lbm_set_enstrophy / lbm_batch_set_enstrophy, and the stream function's scan, psi_band_totals,
+// psi_band_bases, psi_scan and psi_extrema, lbm_set_psi / lbm_batch_set_psi)
 
 // 1/3 rounded to fp32, and the two constant divisors of the equilibrium, folded in fp32
 // exactly as the reference's "2.f * c_sq" and "2.f * c_sq * c_sq" (SerialCode/d2q9-bgk.c:308,367-370)
@@ -3682,6 +3685,249 @@ __global__ __launch_bounds__(kBlock) void vorticity_gather_batch(const LatticeAr
   const float* src = members[member].src;
   vorticity_cells<V, false>(a, src, members[member].mask, src + (long)(rows - 1) * a.row_pitch, src, rows, 0, rows, band_rows, 0u, nullptr,
                      row + (size_t)member * lbm_enstrophy::kEnstrophyWords);
+}
+
+// ---------------------------------------------------------------------------------------------
+// stream function (lbm_read_psi, lbm_set_psi): psi(x, y) = the exact sum of jx over the finite fluid cells (x, 0 .. y) of a
+// stored lattice, rounded once per cell, as a field and / or as its extrema with their cells and the counts of a row
+// (lbm_psi_row.h)
+// ---------------------------------------------------------------------------------------------
+// The one recorded quantity that is a PREFIX along an axis.  Totals meet in atomics, prefixes do not: the scan is blocked
+// into bands of band_rows rows whose partial results are fixed-point limbs (lbm_exact_sum.h).  Integer limb addition is
+// associative, so neither the band height, the slabs nor scheduling can change a bit of any psi.  As in profile_columns a
+// lane owns a column -- consecutive lanes read consecutive addresses of a row -- and walks down the rows of its band;
+// workgroup (g, b) owns the columns [g * kPsiColumns, + kPsiColumns) of band b.  Three sweeps:
+//   psi_band_totals  each lane adds the terms of its band's rows into one accumulator and stores the limbs to
+//                    totals[band][x][kExactLimbs] (plain stores, no atomics: a lane owns its limbs),
+//   psi_band_bases   a lane per limb of a column turns the totals, in place, into their exclusive prefix over the bands, starting
+//                    from the limbs of everything below the slab (`incoming`, null: nothing), and leaves the limbs of
+//                    everything up to the slab's last row in `outgoing` (null: nobody asks) -- the next slab's incoming,
+//   psi_scan         each lane starts from its band's base limbs, walks the band's rows again and, after adding a row's
+//                    term, rounds the running accumulator (exact_sum_round_hd, lbm_exact_round.h): the inclusive prefix.
+//                    FIELD = true stores the double; FIELD = false, the recorder's form, stores nothing per cell: a lane
+//                    keeps its running (smallest psi, cell) and (largest psi, cell) over the finite fluid cells -- values
+//                    compared as doubles, equal values by the smaller GLOBAL cell index -- the lanes are combined by
+//                    shuffles, the waves through LDS, and the workgroup leaves one PsiCandidate,
+//   psi_extrema      one wave per slab (or member) reduces the workgroups' candidates in the same order into the row's
+//                    words.  A double and a cell do not fit one 64-bit atomic key, so the candidates are reduced explicitly;
+//                    the order (value, then cell) is total, so the result does not depend on how they were grouped.
+// A term is jx of a finite fluid cell (profile_cell's jx and its rule for finite), 0 of every other cell: added with sign 0.
+constexpr int kPsiColumns = kBlock;  // columns of a workgroup: one per lane
+constexpr int kPsiMinBand = 8;       // the fewest rows of a band the host chooses by itself
+constexpr unsigned kPsiNoCell = 0xffffffffu;
+
+struct PsiCandidate {
+  double psi_min, psi_max;      // 0 with kPsiNoCell
+  unsigned min_cell, max_cell;  // GLOBAL cell index; kPsiNoCell: the workgroup saw no finite fluid cell
+  int fluid, bad;               // its finite fluid cells; its fluid cells that are not finite
+};
+static_assert(sizeof(PsiCandidate) == 32, "the host sizes the candidates' buffer");
+
+// the term of one cell: the bits of jx, the sign it is added with (1: a finite fluid cell) and whether it is a fluid cell
+// that is not finite
+__device__ __forceinline__ void psi_term(const float (&g)[kQ], bool fluid, unsigned& bits, int& s, int& bad) {
+  float rho, ux, uy;
+  moments_exact(g, rho, ux, uy);
+  const float jx = g[1] + g[5] + g[8] - (g[3] + g[6] + g[7]);
+  const float jy = g[2] + g[5] + g[6] - (g[4] + g[7] + g[8]);
+  const float usq = (ux * ux) + (uy * uy);
+  bits = __float_as_uint(jx);
+  const bool finite = lbm_exact::exact_sum_finite(__float_as_uint(rho)) && lbm_exact::exact_sum_finite(bits) &&
+                      lbm_exact::exact_sum_finite(__float_as_uint(jy)) && lbm_exact::exact_sum_finite(__float_as_uint(usq));
+  s = (fluid && finite) ? 1 : 0;
+  bad = (fluid && !finite) ? 1 : 0;
+}
+
+// is the candidate (v, cell) in front of (best, best_cell)?  sign < 0: the smaller value (the minimum), else the larger;
+// equal values (+0.0 == -0.0): the smaller cell (lbm_psi::psi_in_front is the host's)
+__device__ __forceinline__ bool psi_in_front(double v, unsigned cell, double best, unsigned best_cell, int sign) {
+  if (cell == kPsiNoCell) return false;
+  if (best_cell == kPsiNoCell) return true;
+  if (v != best) return sign < 0 ? v < best : v > best;
+  return cell < best_cell;
+}
+
+__device__ __forceinline__ void psi_band_totals_lines(const LatticeArgs& a, const float* src, const unsigned char* mask, int rows, int band_rows,
+                                                      long long* totals) {
+  constexpr int L = lbm_exact::kExactLimbs;
+  const int x = (int)blockIdx.x * kPsiColumns + (int)threadIdx.x;
+  if (x >= a.nx) return;
+  const int r0 = (int)blockIdx.y * band_rows, r1 = (r0 + band_rows < rows) ? r0 + band_rows : rows;
+  long long acc[L];
+#pragma unroll
+  for (int i = 0; i < L; i++) acc[i] = 0;
+  for (int r = r0; r < r1; r++) {
+    const float* p = src + (long)r * a.row_pitch + x;
+    float f[kQ];
+#pragma unroll
+    for (int k = 0; k < kQ; k++) f[k] = p[k * a.plane_stride];
+    unsigned bits;
+    int s, bad;
+    psi_term(f, mask[(long)r * a.pitch + x] == 0, bits, s, bad);
+    lbm_exact::exact_sum_add(acc, bits, s);
+  }
+  long long* out = totals + ((size_t)blockIdx.y * a.nx + x) * L;
+#pragma unroll
+  for (int i = 0; i < L; i++) out[i] = acc[i];
+}
+
+// a slab's owned rows into totals[bands][nx][kExactLimbs]; grid: (ceil(nx / kPsiColumns), bands)
+__global__ __launch_bounds__(kBlock) void psi_band_totals(const LatticeArgs a, int rows, int band_rows, long long* totals) {
+  psi_band_totals_lines(a, a.src, a.mask, rows, band_rows, totals);
+}
+// its twin for a batch: workgroup (g, b, member) on the member's current lattice and mask, into the member's totals
+__global__ __launch_bounds__(kBlock) void psi_band_totals_batch(const LatticeArgs a, const ResidentMember* members, int rows, int band_rows,
+                                                                long long* totals) {
+  const int member = blockIdx.z;
+  psi_band_totals_lines(a, members[member].src, members[member].mask, rows, band_rows,
+                        totals + (size_t)member * gridDim.y * a.nx * lbm_exact::kExactLimbs);
+}
+
+// totals[bands][nx][kExactLimbs] -> in place, the limbs of everything below each band.  Limbs do not carry into each other
+// (lbm_exact_sum.h), so a lane owns one WORD of a band, (column, limb) = (word / kExactLimbs, word % kExactLimbs) --
+// consecutive lanes, consecutive addresses -- and walks the bands, kPsiAhead loads in flight at a time: the walk is serial in
+// the bands and a grid of a few thousand columns has few lanes to hide it behind.  grid: (ceil(nx * kExactLimbs / kBlock),
+// 1, members), member m on totals + m * bands * nx * kExactLimbs (incoming and outgoing belong to a single slab: members == 1)
+constexpr int kPsiAhead = 8;
+__global__ __launch_bounds__(kBlock) void psi_band_bases(int nx, int bands, long long* totals, const long long* incoming, long long* outgoing) {
+  const size_t n_words = (size_t)nx * lbm_exact::kExactLimbs;
+  const size_t word = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (word >= n_words) return;
+  totals += (size_t)blockIdx.z * bands * n_words + word;
+  long long base = incoming ? incoming[word] : 0;
+  for (int b0 = 0; b0 < bands; b0 += kPsiAhead) {
+    long long t[kPsiAhead];
+#pragma unroll
+    for (int j = 0; j < kPsiAhead; j++) t[j] = (b0 + j < bands) ? totals[(size_t)(b0 + j) * n_words] : 0;
+#pragma unroll
+    for (int j = 0; j < kPsiAhead; j++) {
+      if (b0 + j < bands) totals[(size_t)(b0 + j) * n_words] = base;
+      base += t[j];
+    }
+  }
+  if (outgoing) outgoing[word] = base;
+}
+
+// the bands [band_first, band_first + gridDim.y) of a slab's `rows` owned rows from their bases.  FIELD: psi of their cells
+// into `field` (dense, the first row of band band_first first, nx doubles per row); else the workgroup's candidate into
+// cand[blockIdx.y * gridDim.x + blockIdx.x].  cell_first: the GLOBAL index of the slab's first owned cell.
+template <bool FIELD>
+__device__ __forceinline__ void psi_scan_cells(const LatticeArgs& a, const float* src, const unsigned char* mask, int rows, int band_rows,
+                                               int band_first, const long long* bases, unsigned cell_first, double* field, PsiCandidate* cand) {
+  constexpr int L = lbm_exact::kExactLimbs;
+  constexpr int kWaves = kBlock / 64;
+  const int band = band_first + (int)blockIdx.y;
+  const int x = (int)blockIdx.x * kPsiColumns + (int)threadIdx.x;
+  const int r0 = band * band_rows, r1 = (r0 + band_rows < rows) ? r0 + band_rows : rows;
+  double lo = 0.0, hi = 0.0;
+  unsigned lo_cell = kPsiNoCell, hi_cell = kPsiNoCell;
+  int n_fluid = 0, n_bad = 0;
+  if (x < a.nx) {
+    long long acc[L];
+    const long long* base = bases + ((size_t)band * a.nx + x) * L;
+#pragma unroll
+    for (int i = 0; i < L; i++) acc[i] = base[i];
+    for (int r = r0; r < r1; r++) {
+      const float* p = src + (long)r * a.row_pitch + x;
+      float f[kQ];
+#pragma unroll
+      for (int k = 0; k < kQ; k++) f[k] = p[k * a.plane_stride];
+      unsigned bits;
+      int s, bad;
+      psi_term(f, mask[(long)r * a.pitch + x] == 0, bits, s, bad);
+      lbm_exact::exact_sum_add(acc, bits, s);
+      const double psi = lbm_exact::exact_sum_round_hd(acc);  // (never -0.0)
+      if constexpr (FIELD) {
+        field[(size_t)(r - band_first * band_rows) * a.nx + x] = psi;
+      } else {
+        // rows ascend, so among a lane's equal values the first (the smallest cell) stays
+        const unsigned cell = s ? cell_first + (unsigned)r * (unsigned)a.nx + (unsigned)x : kPsiNoCell;
+        if (psi_in_front(psi, cell, lo, lo_cell, -1)) { lo = psi; lo_cell = cell; }
+        if (psi_in_front(psi, cell, hi, hi_cell, +1)) { hi = psi; hi_cell = cell; }
+        n_fluid += s;
+        n_bad += bad;
+      }
+    }
+  }
+  if constexpr (!FIELD) {
+    __shared__ double sh_v[2][kWaves];
+    __shared__ unsigned sh_c[2][kWaves];
+    __shared__ int sh_n[2][kWaves];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int off = 32; off > 0; off >>= 1) {
+      const double o_lo = __shfl_xor(lo, off, 64), o_hi = __shfl_xor(hi, off, 64);
+      const unsigned o_lo_cell = __shfl_xor(lo_cell, off, 64), o_hi_cell = __shfl_xor(hi_cell, off, 64);
+      if (psi_in_front(o_lo, o_lo_cell, lo, lo_cell, -1)) { lo = o_lo; lo_cell = o_lo_cell; }
+      if (psi_in_front(o_hi, o_hi_cell, hi, hi_cell, +1)) { hi = o_hi; hi_cell = o_hi_cell; }
+      n_fluid += __shfl_xor(n_fluid, off, 64);
+      n_bad += __shfl_xor(n_bad, off, 64);
+    }
+    if (lane == 0) {
+      sh_v[0][wave] = lo;  sh_v[1][wave] = hi;
+      sh_c[0][wave] = lo_cell;  sh_c[1][wave] = hi_cell;
+      sh_n[0][wave] = n_fluid;  sh_n[1][wave] = n_bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      PsiCandidate c = {0.0, 0.0, kPsiNoCell, kPsiNoCell, 0, 0};
+      for (int w = 0; w < kWaves; w++) {
+        if (psi_in_front(sh_v[0][w], sh_c[0][w], c.psi_min, c.min_cell, -1)) { c.psi_min = sh_v[0][w]; c.min_cell = sh_c[0][w]; }
+        if (psi_in_front(sh_v[1][w], sh_c[1][w], c.psi_max, c.max_cell, +1)) { c.psi_max = sh_v[1][w]; c.max_cell = sh_c[1][w]; }
+        c.fluid += sh_n[0][w];
+        c.bad += sh_n[1][w];
+      }
+      cand[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = c;
+    }
+  }
+}
+
+// grid: (ceil(nx / kPsiColumns), bands of this launch)
+template <bool FIELD>
+__global__ __launch_bounds__(kBlock) void psi_scan(const LatticeArgs a, int rows, int band_rows, int band_first, const long long* bases,
+                                                   unsigned cell_first, double* field, PsiCandidate* cand) {
+  psi_scan_cells<FIELD>(a, a.src, a.mask, rows, band_rows, band_first, bases, cell_first, field, cand);
+}
+// the recorder's form for a batch: workgroup (g, b, member), every member a grid of its own (cell_first 0), its bases and
+// candidates behind the members' before it
+__global__ __launch_bounds__(kBlock) void psi_scan_batch(const LatticeArgs a, const ResidentMember* members, int rows, int band_rows,
+                                                         const long long* bases, PsiCandidate* cand) {
+  const int member = blockIdx.z;
+  psi_scan_cells<false>(a, members[member].src, members[member].mask, rows, band_rows, 0,
+                        bases + (size_t)member * gridDim.y * a.nx * lbm_exact::kExactLimbs, 0u, nullptr,
+                        cand + (size_t)member * gridDim.y * gridDim.x);
+}
+
+// the n candidates of a slab (or of member blockIdx.x, n apart) into its kPsiWords words of the row; grid: (members), one
+// wave each.  Every word the readers use is stored: the row needs no zeroing.
+__global__ __launch_bounds__(64) void psi_extrema(const PsiCandidate* cand, int n, long long* words) {
+  cand += (size_t)blockIdx.x * n;
+  words += (size_t)blockIdx.x * lbm_psi::kPsiWords;
+  double lo = 0.0, hi = 0.0;
+  unsigned lo_cell = kPsiNoCell, hi_cell = kPsiNoCell;
+  long long n_fluid = 0, n_bad = 0;
+  for (int i = threadIdx.x; i < n; i += 64) {
+    const PsiCandidate c = cand[i];
+    if (psi_in_front(c.psi_min, c.min_cell, lo, lo_cell, -1)) { lo = c.psi_min; lo_cell = c.min_cell; }
+    if (psi_in_front(c.psi_max, c.max_cell, hi, hi_cell, +1)) { hi = c.psi_max; hi_cell = c.max_cell; }
+    n_fluid += c.fluid;
+    n_bad += c.bad;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const double o_lo = __shfl_xor(lo, off, 64), o_hi = __shfl_xor(hi, off, 64);
+    const unsigned o_lo_cell = __shfl_xor(lo_cell, off, 64), o_hi_cell = __shfl_xor(hi_cell, off, 64);
+    if (psi_in_front(o_lo, o_lo_cell, lo, lo_cell, -1)) { lo = o_lo; lo_cell = o_lo_cell; }
+    if (psi_in_front(o_hi, o_hi_cell, hi, hi_cell, +1)) { hi = o_hi; hi_cell = o_hi_cell; }
+    n_fluid += __shfl_xor(n_fluid, off, 64);
+    n_bad += __shfl_xor(n_bad, off, 64);
+  }
+  if (threadIdx.x == 0) {
+    words[lbm_psi::kPsiMinWord] = lo_cell == kPsiNoCell ? 0ll : (long long)__double_as_longlong(lo + 0.0);  // (+ 0.0: never -0.0)
+    words[lbm_psi::kPsiMaxWord] = hi_cell == kPsiNoCell ? 0ll : (long long)__double_as_longlong(hi + 0.0);
+    words[lbm_psi::kPsiMinCellWord] = lo_cell == kPsiNoCell ? -1ll : (long long)lo_cell;
+    words[lbm_psi::kPsiMaxCellWord] = hi_cell == kPsiNoCell ? -1ll : (long long)hi_cell;
+    words[lbm_psi::kPsiFluidWord] = n_fluid;
+    words[lbm_psi::kPsiBadWord] = n_bad;
+  }
 }
 
 }  // namespace lbm
