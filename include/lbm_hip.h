@@ -868,6 +868,64 @@ int lbm_read_profiles(lbm_ctx* ctx, int max_records, lbm_profile_line* out /* [n
 int lbm_batch_set_profiles(lbm_batch* batch, int every, int capacity, int axes);
 int lbm_batch_read_profiles(lbm_batch* batch, int max_records, lbm_profile_line* out /* [n][members][lines] */, int* steps, int* n_read);
 
+/* ---- coarse frames --------------------------------------------------------------------------
+ * The whole flow field at screen resolution: the line profiles' sums over the cells of a 2-D box instead of a line, so
+ * that a frame of a grid far too large for per-cell frames (8192^2: 1 GiB for four fields) is a few hundred by a few
+ * hundred lines that leave the device already rounded.
+ * A box size is (bx, by) with 1 <= bx <= min(nx, LBM_COARSE_MAX_BOX) and 1 <= by <= min(ny, LBM_COARSE_MAX_BOX).  The
+ * coarse grid has cx = ceil(nx / bx) by cy = ceil(ny / by) boxes; box (X, Y) covers the GLOBAL cells x in [X*bx,
+ * min(nx, (X+1)*bx)) and y in [Y*by, min(ny, (Y+1)*by)).  The last box of an axis may be ragged; nothing wraps.
+ * One box is one lbm_profile_line and holds exactly what a line of lbm_set_profiles holds, over the box's cells instead
+ * of a line's: sum_rho, sum_jx, sum_jy, sum_ux, sum_uy over the box's finite fluid cells -- the per-cell values and the
+ * rule for NON-FINITE cells are those of the line profiles' text above: the statistics' moments, IEEE divide, no
+ * contraction -- fluid = the number of those cells, nonfinite = the box's fluid cells left out; blocked cells are counted
+ * nowhere.  Every sum is taken EXACTLY and rounded to a double once: math.fsum's value, never -0.0; a box without finite
+ * fluid cells reports +0.0 five times.  One frame is lbm_profile_line[cy][cx], row-major.
+ * On the same lattice, bit for bit: with (bx, by) = (nx, 1) frame row Y is row line Y of lbm_set_profiles; with (1, ny)
+ * box X is column line X; with (nx, ny) and nonfinite == 0, sum_jx and sum_jy are lbm_stats_row.mom_x and mom_y; with
+ * (1, 1), on a finite fluid cell sum_ux and sum_uy are (double) of lbm_read_final_state's u_x and u_y, on a blocked cell
+ * +0.0.  No bit depends on the slab count, on the kernel family that advanced the lattice, on how calls were split, on
+ * batch membership, or on the run.
+ * lbm_read_coarse(ctx, bx, by, out): the frame of the current lattice into out[cy][cx].  Needs nothing armed, changes
+ *   nothing and works with any recorder armed (its slot is the call's own); synchronises like the other readers.  Works
+ *   on lbm_create / lbm_create_tiled contexts of any slab count and on batch member handles; refused on rank contexts
+ *   (lbm_create_rank*), whose boxes would be spread over the processes, and for a box outside the bounds above.
+ * lbm_set_coarse_frames(ctx, every, capacity, bx, by): a gather kind with the semantics of lbm_set_profiles: from now on,
+ *   after global timestep tt (0-based) with tt % every == 0, record one frame of the lattice after tt+1 timesteps into a
+ *   device ring of `capacity` slots.  An lbm_run that would record more frames than there are free slots fails before
+ *   issuing any work.  every == 0 disarms and frees; re-arming (with another box, too) discards unread frames.  No step
+ *   kernel records: every call runs as the sub-calls that end at its sample steps, each followed per slab by one memset
+ *   of the slot and ONE launch (coarse_gather); lattice and av_vels equal those of the same run issued as calls split at
+ *   the sample steps.  A finished box leaves the device as its 48-byte line, rounded there (five roundings per box), not
+ *   as its 48 limb words: a slab's slot is [its whole box rows][cx] lines, then -- only for its first and / or last box
+ *   row where it shares that row with a neighbouring slab (one row where by exceeds the slab's rows) -- [0, 1 or 2
+ *   partial box rows][cx] boxes of 48 int64 words (the line profiles' words), whose limbs the reader adds over the slabs
+ *   as integers before the one rounding.  A single slab and a batch member have no partial rows: 48 bytes per box.
+ *   Refused, as lbm_set_profiles refuses: negative every; capacity < 1; a ring of 2 GiB or more (the message gives the
+ *   bytes per frame and slab); rank contexts; batch members (lbm_batch_set_coarse_frames arms the batch); LBM_HALO_STALE /
+ *   LBM_HALO_FRESHEST (and lbm_set_halo_mode to those while armed); a context with another recorder armed (and every
+ *   other setter while this one is armed); lbm_run_until and lbm_run_until_residual while armed; and a box side below
+ *   1, above the grid's side, or above LBM_COARSE_MAX_BOX (the message names the side and the limit).  Not offered: the
+ *   double engine, windows, boxes above 256 per side, recording inside the resident or stream kernels.
+ * lbm_read_coarse_frames: drains up to max_frames oldest frames into out[n][cy][cx] and steps[n] (their tt, may be NULL);
+ *   out == NULL && steps == NULL: *n_read = frames waiting, nothing drained.  Synchronises like the other readers.
+ * lbm_batch_set_coarse_frames / lbm_batch_read_coarse_frames: the same for every member of a batch, armed on the BATCH
+ *   with one `every`, one box and ONE ring [slots][members][cy][cx] of lines; frames are out[n][members][cy][cx].  Behind
+ *   each sub-call that ends at a sample step the batch's stream gets one memset of the slot and ONE launch for all
+ *   members (coarse_gather_batch: grid z is the member).  Member i's frames, lattice and av_vels are bit-identical to
+ *   those of an lbm_create context armed with lbm_set_coarse_frames and advanced by the same calls.  An lbm_batch_run
+ *   without room fails before any work and moves no member's steps_done.  Refused as lbm_batch_set_profiles refuses: a
+ *   member with a recorder armed, another kind armed on the batch (and every member-level setter and the other
+ *   batch-level setters while the coarse frames are armed); lbm_batch_run_until and lbm_batch_run_until_residual while
+ *   armed.
+ */
+#define LBM_COARSE_MAX_BOX 256
+int lbm_read_coarse(lbm_ctx* ctx, int bx, int by, lbm_profile_line* out /* [cy][cx] */);
+int lbm_set_coarse_frames(lbm_ctx* ctx, int every, int capacity, int bx, int by);
+int lbm_read_coarse_frames(lbm_ctx* ctx, int max_frames, lbm_profile_line* out /* [n][cy][cx] */, int* steps, int* n_read);
+int lbm_batch_set_coarse_frames(lbm_batch* batch, int every, int capacity, int bx, int by);
+int lbm_batch_read_coarse_frames(lbm_batch* batch, int max_frames, lbm_profile_line* out /* [n][members][cy][cx] */, int* steps, int* n_read);
+
 /* ---- vorticity and enstrophy ----------------------------------------------------------------
  * The first field anyone draws of a lid-driven cavity or of a wake, and its integral: the series that tells whether a
  * shear layer is rolling up or decaying.  The one diagnostic here that is not local to a cell.

@@ -57,6 +57,7 @@ ABI_SYMBOLS = (
     "lbm_set_residual", "lbm_read_residual", "lbm_batch_set_residual", "lbm_batch_read_residual",
     "lbm_run_until_residual", "lbm_batch_run_until_residual",
     "lbm_set_profiles", "lbm_read_profiles", "lbm_batch_set_profiles", "lbm_batch_read_profiles",
+    "lbm_read_coarse", "lbm_set_coarse_frames", "lbm_read_coarse_frames", "lbm_batch_set_coarse_frames", "lbm_batch_read_coarse_frames",
     "lbm_read_vorticity", "lbm_set_enstrophy", "lbm_read_enstrophy", "lbm_batch_set_enstrophy", "lbm_batch_read_enstrophy",
     "lbm_read_psi", "lbm_set_psi", "lbm_read_psi_rows", "lbm_batch_set_psi", "lbm_batch_read_psi_rows",
     "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
@@ -281,6 +282,11 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_read_profiles.argtypes = [P, I, P, P, PI]; lib.lbm_read_profiles.restype = I
     lib.lbm_batch_set_profiles.argtypes = [P, I, I, I]; lib.lbm_batch_set_profiles.restype = I
     lib.lbm_batch_read_profiles.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_profiles.restype = I
+    lib.lbm_read_coarse.argtypes = [P, I, I, P]; lib.lbm_read_coarse.restype = I
+    lib.lbm_set_coarse_frames.argtypes = [P, I, I, I, I]; lib.lbm_set_coarse_frames.restype = I
+    lib.lbm_read_coarse_frames.argtypes = [P, I, P, P, PI]; lib.lbm_read_coarse_frames.restype = I
+    lib.lbm_batch_set_coarse_frames.argtypes = [P, I, I, I, I]; lib.lbm_batch_set_coarse_frames.restype = I
+    lib.lbm_batch_read_coarse_frames.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_coarse_frames.restype = I
     lib.lbm_read_vorticity.argtypes = [P, P]; lib.lbm_read_vorticity.restype = I
     lib.lbm_set_enstrophy.argtypes = [P, I, I]; lib.lbm_set_enstrophy.restype = I
     lib.lbm_read_enstrophy.argtypes = [P, I, P, P, PI]; lib.lbm_read_enstrophy.restype = I
@@ -809,6 +815,29 @@ class Engine:
         return _read_profiles(self.lib.lbm_read_profiles, self.lib, self.handle, max_records, getattr(self, "_profile_axes", 0), (),
                               self.params.nx, self.params.ny)
 
+    # -- coarse frames (lbm_read_coarse / lbm_set_coarse_frames / lbm_read_coarse_frames) -----------
+    def coarse(self, box) -> np.ndarray:
+        """The coarse frame of the current lattice, PROFILE_DTYPE (cy, cx): per box of `box` = (bx, by) cells (an int b:
+        (b, b)) what a line of set_profiles holds per line, over the box's cells; cx = ceil(nx / bx), cy = ceil(ny / by),
+        the last box of an axis may be ragged.  Needs nothing armed and changes nothing."""
+        _, _, bx, by = _coarse_args(0, 0, box, "coarse")
+        out = np.zeros(_coarse_shape(self.params.nx, self.params.ny, bx, by), dtype=PROFILE_DTYPE)
+        _check(self.lib, self.lib.lbm_read_coarse(self.handle, bx, by, out.ctypes.data))
+        return out
+
+    def set_coarse_frames(self, every: int, capacity: int = 16, box=(16, 16)) -> None:
+        """Record, after every global timestep tt with tt % every == 0, for the lattice after tt + 1 steps, one coarse
+        frame (Engine.coarse of `box`) into a device ring of `capacity` frames; a box leaves the device as its rounded
+        48-byte line.  every == 0 disarms; re-arming discards unread frames."""
+        every, capacity, bx, by = _coarse_args(every, capacity, box)
+        _check(self.lib, self.lib.lbm_set_coarse_frames(self.handle, every, capacity, bx, by))
+        self._coarse_box = (bx, by) if every > 0 else None
+
+    def coarse_frames(self, max_frames: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_frames (default: all) waiting frames, oldest first: (steps int32[n], PROFILE_DTYPE[n, cy, cx])."""
+        return _read_coarse_frames(self.lib.lbm_read_coarse_frames, self.lib, self.handle, max_frames, getattr(self, "_coarse_box", None), (),
+                                   self.params.nx, self.params.ny)
+
     # -- results -----------------------------------------------------------------------------
     def av_vels(self, n: int | None = None) -> np.ndarray:
         n = self.info()["steps_done"] if n is None else n
@@ -1134,6 +1163,20 @@ class Batch:
         PROFILE_DTYPE[n, members, ny], "columns": PROFILE_DTYPE[n, members, nx]}), the selected keys only."""
         return _read_profiles(self.lib.lbm_batch_read_profiles, self.lib, self._live(), max_records, getattr(self, "_profile_axes", 0),
                               (len(self),), self.params[0].nx, self.params[0].ny)
+
+    # -- coarse frames of all members (lbm_batch_set_coarse_frames / lbm_batch_read_coarse_frames) ---------------------
+    def set_coarse_frames(self, every: int, capacity: int = 16, box=(16, 16)) -> None:
+        """Engine.set_coarse_frames for every member at once: one `every`, one `box` and one `capacity` for the batch,
+        frames in one device ring, one launch per sample whatever the number of members."""
+        every, capacity, bx, by = _coarse_args(every, capacity, box)
+        _check(self.lib, self.lib.lbm_batch_set_coarse_frames(self._live(), every, capacity, bx, by))
+        self._coarse_box = (bx, by) if every > 0 else None
+
+    def coarse_frames(self, max_frames: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_frames (default: all) waiting frames, oldest first: (steps int32[n], PROFILE_DTYPE[n, members,
+        cy, cx])."""
+        return _read_coarse_frames(self.lib.lbm_batch_read_coarse_frames, self.lib, self._live(), max_frames, getattr(self, "_coarse_box", None),
+                                   (len(self),), self.params[0].nx, self.params[0].ny)
 
     def force_links(self) -> np.ndarray:
         """Boundary links of every body of every member of the armed forces, int32[members, n_bodies]
@@ -1549,8 +1592,9 @@ def _read_profiles(reader, lib, handle, max_records, axes, members, nx, ny) -> t
 
 
 def profile_means(lines) -> dict:
-    """The means a profile is plotted as, of lines of PROFILE_DTYPE (any shape), in float64: u_x, u_y, rho and j_x as
-    sum / fluid, pressure as c_sq * rho (c_sq = 1/3); NaN where a line has no finite fluid cell (fluid == 0)."""
+    """The means a profile is plotted as, of lines of PROFILE_DTYPE (any shape: one axis of a record, a stack of records,
+    or the [cy, cx] boxes of a coarse frame, Engine.coarse), in float64: u_x, u_y, rho and j_x as sum / fluid, pressure as
+    c_sq * rho (c_sq = 1/3); NaN where a line has no finite fluid cell (fluid == 0)."""
     lines = np.asarray(lines)
     fluid = np.asarray(lines["fluid"], dtype=np.float64)
     out = {}
@@ -1572,6 +1616,65 @@ def write_profile(path: str, lines) -> None:
             fh.write("%d\t%.12E\t%.12E\t%.12E\t%.12E\t%.12E\t%d\t%d\n" % (
                 i, float(r["sum_rho"]), float(r["sum_jx"]), float(r["sum_jy"]), float(r["sum_ux"]), float(r["sum_uy"]),
                 int(r["fluid"]), int(r["nonfinite"])))
+
+
+COARSE_MAX_BOX = 256      # LBM_COARSE_MAX_BOX
+
+
+def _coarse_args(every, capacity, box, setter="set_coarse_frames") -> tuple[int, int, int, int]:
+    """Engine.set_coarse_frames' argument checks (no device needed): (every, capacity, bx, by).  `box` is a pair of
+    integers (bx, by) or one integer b for (b, b), each side in [1, COARSE_MAX_BOX]; the grid's sides are the engine's to
+    check."""
+    every, capacity = _every_capacity(setter, every, capacity, "frame")
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)  # noqa: E731
+    if is_int(box):
+        sides = (box, box)
+    elif isinstance(box, (str, bytes)) or isinstance(box, bool):
+        raise LbmError(f"{setter}: box must be a pair of integers (bx, by) or one integer (got {box!r})")
+    else:
+        try:
+            sides = tuple(box)
+        except TypeError:
+            raise LbmError(f"{setter}: box must be a pair of integers (bx, by) or one integer (got {box!r})") from None
+        if len(sides) != 2:
+            raise LbmError(f"{setter}: box must be a pair of integers (bx, by) or one integer (got {box!r}: {len(sides)} values)")
+        if not all(is_int(v) for v in sides):
+            raise LbmError(f"{setter}: box must be a pair of integers (bx, by) or one integer (got {box!r})")
+    for name, v in zip(("bx", "by"), sides):
+        if not 1 <= int(v) <= COARSE_MAX_BOX:
+            raise LbmError(f"{setter}: box side {name} must lie in [1, {COARSE_MAX_BOX}] (got {v})")
+    return every, capacity, int(sides[0]), int(sides[1])
+
+
+def _coarse_shape(nx, ny, bx, by) -> tuple[int, int]:
+    """(cy, cx) of the coarse grid of bx x by boxes on nx x ny cells"""
+    return -(-ny // by), -(-nx // bx)
+
+
+def _read_coarse_frames(reader, lib, handle, max_frames, box, members, nx, ny) -> tuple[np.ndarray, np.ndarray]:
+    """What Engine.coarse_frames and Batch.coarse_frames share: the waiting frames through `reader`; members: () or
+    (n_members,); box: what this object armed, None: nothing (no frame waits)."""
+    if max_frames is not None and (isinstance(max_frames, bool) or not isinstance(max_frames, (int, np.integer)) or max_frames < 0):
+        raise LbmError(f"coarse_frames: max_frames must be a non-negative integer or None (got {max_frames!r})")
+    shape = _coarse_shape(nx, ny, *box) if box else (1, 1)
+    steps, frames = _drain_rows(reader, lib, handle, "coarse_frames", max_frames, tuple(members) + shape, PROFILE_DTYPE, np.zeros)
+    return steps, frames if box else frames[:0]
+
+
+def write_coarse_state(path: str, frame) -> None:
+    """One coarse frame (PROFILE_DTYPE[cy, cx]: Engine.coarse, or one frame of Engine.coarse_frames) in final_state.dat's
+    line format (write_final_state), one line per box, Y outer / X inner: 'X Y u_x u_y u pressure obstacle' with the box
+    indices as coordinates, the box means of u_x and u_y (profile_means) and their magnitude, the mean of rho * c_sq as
+    pressure, all rounded to float, and obstacle 1 where the box has no finite fluid cell (fluid == 0; its values are 0)."""
+    frame = np.asarray(frame)
+    if frame.dtype != PROFILE_DTYPE or frame.ndim != 2:
+        raise LbmError(f"write_coarse_state: frame must be one frame, PROFILE_DTYPE[cy, cx] (got shape {frame.shape}, dtype {frame.dtype})")
+    empty = frame["fluid"] == 0
+    m = profile_means(frame)
+    ux, uy, pr = (np.where(empty, 0.0, m[k]) for k in ("u_x", "u_y", "pressure"))
+    fields = {"u_x": ux.astype(np.float32), "u_y": uy.astype(np.float32), "u": np.sqrt(ux * ux + uy * uy).astype(np.float32),
+              "pressure": pr.astype(np.float32)}
+    write_final_state(path, fields, empty.astype(np.int32))
 
 
 # lbm_residual_row of include/lbm_hip.h, 40 bytes

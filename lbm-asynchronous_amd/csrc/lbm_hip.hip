@@ -428,15 +428,17 @@ struct GraphBuilder {
 // kind whose kernel reads rows a slab does not own (Slab::vort_edges).
 // The stream function (lbm_set_psi) likewise, by a scan of three sweeps and psi_extrema: a row of the extrema of psi, the
 // one kind whose slabs depend on each other (Slab::psi_in, psi_out).
-// These six gather kinds (records_behind) share one ring of int64 words per slab, Slab::gather_ring, whose slot holds
+// Coarse frames (lbm_set_coarse_frames) likewise, by coarse_gather: a frame of per-box sums, rounded on the device except
+// in the box rows that two slabs share.
+// These seven gather kinds (records_behind) share one ring of int64 words per slab, Slab::gather_ring, whose slot holds
 // gather_slot_words words; a batch arms them on itself (lbm_batch::rec) with one ring for all members.
 enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean,
        kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecResidual = 7, kRecProfiles = 8, kRecEnstrophy = 9,
-       kRecPsi = 10, kRecKinds = 11 };
+       kRecPsi = 10, kRecCoarse = 11, kRecKinds = 12 };
 // the kinds recorded by a gather launch behind the sub-call that ends at a sample step, whatever kernels advance the lattice
 constexpr bool records_behind(int kind) {
   return kind == kRecForces || kind == kRecStats || kind == kRecResidual || kind == kRecProfiles || kind == kRecEnstrophy ||
-         kind == kRecPsi;
+         kind == kRecPsi || kind == kRecCoarse;
 }
 struct Recorder {
   int kind = kRecNone;
@@ -450,6 +452,7 @@ struct Recorder {
   lbm_window window = {0, 0, 0, 0};  // ... and the window, global cells
   int base_steps = 0;       // velocity residuals: steps_done at arming, the step of the baseline (the first row's span)
   int axes = 0;             // line profiles: the LBM_PROFILE_* bits
+  int box_x = 0, box_y = 0; // coarse frames: the box's sides, cells
 };
 // what differs between the kinds in the host's messages (indexed by kind; kRecNone keeps the empty defaults)
 struct RecorderKind {
@@ -482,7 +485,9 @@ constexpr RecorderKind kRecorderKinds[kRecKinds] = {
     {.name = "enstrophy rows", .noun = "enstrophy", .record = "row", .setter = "lbm_set_enstrophy",
      .reader = "lbm_read_enstrophy", .disarm = "lbm_set_enstrophy(ctx, 0, 0)"},
     {.name = "stream function rows", .noun = "the stream function", .record = "row", .setter = "lbm_set_psi",
-     .reader = "lbm_read_psi_rows", .disarm = "lbm_set_psi(ctx, 0, 0)"}};
+     .reader = "lbm_read_psi_rows", .disarm = "lbm_set_psi(ctx, 0, 0)"},
+    {.name = "coarse frames", .noun = "coarse frames", .record = "frame", .setter = "lbm_set_coarse_frames",
+     .reader = "lbm_read_coarse_frames", .disarm = "lbm_set_coarse_frames(ctx, 0, 0, 0, 0)"}};
 
 struct lbm_ctx {
   lbm_params p;
@@ -550,7 +555,7 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentProbes> probe_table;  // device: [members], allocated when the first member arms probes
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
   DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
-  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
+  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
                                     // (a batch records one kind, so at most one count is non-zero; a gather kind is armed
                                     // on the batch, by its lbm_batch_set_* of kBatchKinds, and counts as one)
   // the gather kinds (records_behind) of all members: the members' own recorders stay off, the batch keeps the one
@@ -593,6 +598,7 @@ static int take_batch_residual(lbm_batch* bt, long long* row);
 static int take_batch_profiles(lbm_batch* bt, long long* record);
 static int take_batch_enstrophy(lbm_batch* bt, long long* row);
 static int take_batch_psi(lbm_batch* bt, long long* row);
+static int take_batch_coarse(lbm_batch* bt, long long* frame);
 struct BatchKind {
   int kind;
   const char* setter;
@@ -606,7 +612,9 @@ static const BatchKind kBatchKinds[] = {
     {kRecResidual, "lbm_batch_set_residual", "lbm_batch_read_residual", "lbm_batch_set_residual(batch, 0, 0)", take_batch_residual},
     {kRecProfiles, "lbm_batch_set_profiles", "lbm_batch_read_profiles", "lbm_batch_set_profiles(batch, 0, 0, 0)", take_batch_profiles},
     {kRecEnstrophy, "lbm_batch_set_enstrophy", "lbm_batch_read_enstrophy", "lbm_batch_set_enstrophy(batch, 0, 0)", take_batch_enstrophy},
-    {kRecPsi, "lbm_batch_set_psi", "lbm_batch_read_psi_rows", "lbm_batch_set_psi(batch, 0, 0)", take_batch_psi}};
+    {kRecPsi, "lbm_batch_set_psi", "lbm_batch_read_psi_rows", "lbm_batch_set_psi(batch, 0, 0)", take_batch_psi},
+    {kRecCoarse, "lbm_batch_set_coarse_frames", "lbm_batch_read_coarse_frames", "lbm_batch_set_coarse_frames(batch, 0, 0, 0, 0)",
+     take_batch_coarse}};
 static const BatchKind* batch_kind(int kind) {
   for (const BatchKind& k : kBatchKinds)
     if (k.kind == kind) return &k;
@@ -1428,10 +1436,10 @@ const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = f
       {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>, resident_form<false, kRecMean>,
        resident_form<false, kRecFields>, resident_form<false, kRecNone>, resident_form<false, kRecNone>,
        resident_form<false, kRecNone>, resident_form<false, kRecNone>, resident_form<false, kRecNone>,
-       resident_form<false, kRecNone>},  // (the gather kinds run the plain form)
+       resident_form<false, kRecNone>, resident_form<false, kRecNone>},  // (the gather kinds run the plain form)
       {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>, resident_form<true, kRecMean>,
        resident_form<true, kRecFields>, resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>,
-       resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>}};
+       resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>}};
   return forms[batch][rec]((rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
 }
 
@@ -1691,6 +1699,27 @@ void launch_profiles(const lbm_ctx* c, const Slab& sl, long long* lines) {
   }
 }
 
+// what a slab holds of the coarse grid of bx x by boxes (lbm_coarse_row.h), and the words of its slot
+lbm_coarse::SlabBoxRows coarse_slab_boxes(const lbm_ctx* c, const Slab& sl, int bx, int by) {
+  return lbm_coarse::slab_box_rows(c->p.nx, c->p.ny, bx, by, sl.row_first, sl.rows);
+}
+size_t coarse_slot_words(const lbm_ctx* c, const Slab& sl, int bx, int by) { return lbm_coarse::slot_words(coarse_slab_boxes(c, sl, bx, by)); }
+// workgroups of coarse_gather for one box row: a box each where bx > 64, else four wave spans of floor(64 / bx) boxes
+bool coarse_wide(int bx) { return bx > 64; }
+int coarse_groups(const lbm_coarse::SlabBoxRows& g) {
+  return coarse_wide(g.bx) ? g.cx : ceil_div(ceil_div(g.cx, 64 / g.bx), lbm::kBlock / 64);
+}
+
+// one coarse sample of a slab's current lattice into `words` (zeroed in front, on the same stream): its whole box rows as
+// lines, its partial ones as limb words
+void launch_coarse(const lbm_ctx* c, const Slab& sl, int bx, int by, long long* words) {
+  const lbm_coarse::SlabBoxRows g = coarse_slab_boxes(c, sl, bx, by);
+  const int groups = coarse_groups(g);
+  const dim3 grid((unsigned)g.count * (unsigned)groups);
+  hipLaunchKernelGGL(coarse_wide(bx) ? lbm::coarse_gather<true> : lbm::coarse_gather<false>, grid, dim3(lbm::kBlock), 0, sl.compute,
+                     lattice_args(c, sl), g, groups, words);
+}
+
 // rows of a band of vorticity_gather / vorticity_gather_batch for `rows` rows of nx cells: about kVortTargetUnits units
 // (a wave's strip of 64 * V columns of a band) where the grid has that many bands of kVortMinBand rows, so that small and
 // large grids both fill the device and a large one reads few rows twice
@@ -1842,7 +1871,8 @@ int take_psi_record(lbm_ctx* c) {
 
 // int64 words a gather kind records per slab (or batch member) and sample: of `bodies` bodies (forces), of `rows` rows of
 // nx cells along `axes` (profiles).  The one place a slot's size is computed: the setters call it with what they are about
-// to arm, everything else through gather_slot_words with what is armed.
+// to arm, everything else through gather_slot_words with what is armed.  (The coarse frames' slot follows from the slab's
+// box rows, not from a count: coarse_slot_words.)
 size_t gather_words(int kind, size_t bodies = 0, int rows = 0, int nx = 0, int axes = 0) {
   switch (kind) {
     case kRecForces: return bodies * (size_t)lbm::kForceWords;
@@ -1856,11 +1886,13 @@ size_t gather_words(int kind, size_t bodies = 0, int rows = 0, int nx = 0, int a
 }
 // words of one slot of a slab's gather_ring: this slab's share of a record
 size_t gather_slot_words(const lbm_ctx* c, const Slab& sl) {
+  if (c->rec.kind == kRecCoarse) return coarse_slot_words(c, sl, c->rec.box_x, c->rec.box_y);
   return gather_words(c->rec.kind, c->force_link_counts.size(), sl.rows, c->p.nx, c->rec.axes);
 }
 // ... and of a batch's: that of slab 0 for every member, one after the other
 size_t gather_slot_words(const lbm_batch* bt) {
   const lbm_ctx* c0 = bt->members[0];
+  if (bt->rec.kind == kRecCoarse) return bt->members.size() * coarse_slot_words(c0, c0->slab[0], bt->rec.box_x, bt->rec.box_y);
   return bt->members.size() * gather_words(bt->rec.kind, (size_t)bt->force_bodies, c0->slab[0].rows, c0->p.nx, bt->rec.axes);
 }
 
@@ -1927,6 +1959,8 @@ int take_record(lbm_ctx* c) {
           launch_residual_gather(c, sl, sl.residual_planes, words, false);  // also replaces the slab's remembered field by this lattice's
         else if (c->rec.kind == kRecProfiles)
           launch_profiles(c, sl, words);  // (profile_rows leaves a line's spare word as zeroed)
+        else if (c->rec.kind == kRecCoarse)
+          launch_coarse(c, sl, c->rec.box_x, c->rec.box_y, words);
         else if (c->rec.kind == kRecEnstrophy) {
           if (vort_edges && copy_vorticity_edges(c, s, sl.vort_edges) != LBM_SUCCESS) return LBM_FAILURE;
           launch_vorticity_gather(c, sl, vort_edges ? sl.vort_edges.get() : nullptr, 0, sl.rows, nullptr, words);
@@ -3851,6 +3885,101 @@ int lbm_read_profiles(lbm_ctx* c, int max_records, lbm_profile_line* out, int* s
   });
 }
 
+// ---- coarse frames -----------------------------------------------------------------------------------------------------
+// what every entry point refuses of a box (no device needed)
+static int coarse_box_ok(const char* who, const lbm_ctx* c, int bx, int by) {
+  if (bx < 1 || by < 1) LBM_FAIL(LBM_FAILURE, "%s: box %d x %d, a box side is at least 1", who, bx, by);
+  if (bx > c->p.nx) LBM_FAIL(LBM_FAILURE, "%s: box side bx %d is larger than the grid's nx %d", who, bx, c->p.nx);
+  if (by > c->p.ny) LBM_FAIL(LBM_FAILURE, "%s: box side by %d is larger than the grid's ny %d", who, by, c->p.ny);
+  if (bx > LBM_COARSE_MAX_BOX) LBM_FAIL(LBM_FAILURE, "%s: box side bx %d is larger than LBM_COARSE_MAX_BOX (%d)", who, bx, LBM_COARSE_MAX_BOX);
+  if (by > LBM_COARSE_MAX_BOX) LBM_FAIL(LBM_FAILURE, "%s: box side by %d is larger than LBM_COARSE_MAX_BOX (%d)", who, by, LBM_COARSE_MAX_BOX);
+  return LBM_SUCCESS;
+}
+
+// the slabs' slots of one record (one after the other) -> the frame
+static void coarse_frame(const lbm_ctx* c, const long long* record, int bx, int by, lbm_profile_line* out) {
+  int row_first[kMaxSlabs], row_count[kMaxSlabs];
+  for (int s = 0; s < c->n_slabs; s++) {
+    row_first[s] = c->slab[s].row_first;
+    row_count[s] = c->slab[s].rows;
+  }
+  lbm_coarse::coarse_frame_from_words(record, c->n_slabs, row_first, row_count, c->p.nx, c->p.ny, bx, by, out);
+}
+
+int lbm_read_coarse(lbm_ctx* c, int bx, int by, lbm_profile_line* out) {
+  if (!c || !out) LBM_FAIL(LBM_FAILURE, "lbm_read_coarse: NULL argument");
+  if (c->ranked || c->world > 1)
+    LBM_FAIL(LBM_FAILURE, "lbm_read_coarse: not available in a multi-process (rank) context: a box's cells would be spread over the ranks");
+  if (coarse_box_ok("lbm_read_coarse", c, bx, by) != LBM_SUCCESS) return LBM_FAILURE;
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
+  std::vector<long long> record;
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    const size_t words = coarse_slot_words(c, sl, bx, by), at = record.size();
+    record.resize(at + words);
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    DeviceBuf<long long> slot;  // the call's own: nothing armed is touched
+    if (slot.alloc(words) != hipSuccess) {
+      (void)hipGetLastError();
+      LBM_FAIL(LBM_FAILURE, "lbm_read_coarse: cannot allocate the frame's %.1f MiB of slab %d", (double)(words * sizeof(long long)) / 1048576.0, s);
+    }
+    HIP_TRY(LBM_FAILURE, hipMemsetAsync(slot, 0, words * sizeof(long long), sl.compute));
+    launch_coarse(c, sl, bx, by, slot);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    HIP_TRY(LBM_FAILURE, hipMemcpyAsync(record.data() + at, slot, words * sizeof(long long), hipMemcpyDeviceToHost, sl.compute));
+    HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+  }
+  coarse_frame(c, record.data(), bx, by, out);
+  return LBM_SUCCESS;
+}
+
+int lbm_set_coarse_frames(lbm_ctx* c, int every, int capacity, int bx, int by) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: null context");
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: negative interval %d", every);
+  if (every > 0) {
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: capacity %d, at least one frame is needed", capacity);
+    if (coarse_box_ok("lbm_set_coarse_frames", c, bx, by) != LBM_SUCCESS) return LBM_FAILURE;
+    for (int s = 0; s < c->n_slabs; s++) {
+      const long long slot_bytes = (long long)(coarse_slot_words(c, c->slab[s], bx, by) * sizeof(long long));
+      if ((long long)capacity * slot_bytes >= (1LL << 31))
+        LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: a ring of %d frames is 2 GiB or more (%lld bytes per frame and slab)", capacity, slot_bytes);
+    }
+    if (c->ranked || c->world > 1)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: not available in a multi-process (rank) context: a box's cells would be spread over the ranks");
+    if (c->batch)
+      LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
+               "end at, so the coarse frames of a batch are armed on the batch, with one `every` for all members (lbm_batch_set_coarse_frames)");
+  }
+  const int status = rearm_recorder(c, kRecCoarse, every, capacity, [&]() -> int {
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      const size_t ring_bytes = (size_t)capacity * coarse_slot_words(c, sl, bx, by) * sizeof(long long);
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      if (sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
+        LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: cannot allocate %d frames (%.1f MiB for slab %d); coarse frames stay off", capacity,
+                 (double)ring_bytes / 1048576.0, s);
+    }
+    return LBM_SUCCESS;
+  });
+  if (status == LBM_SUCCESS && every > 0) {
+    c->rec.box_x = bx;
+    c->rec.box_y = by;
+  }
+  return status;
+}
+
+int lbm_read_coarse_frames(lbm_ctx* c, int max_frames, lbm_profile_line* out, int* steps, int* n_read) {
+  return drain_recorder(c, kRecCoarse, max_frames, out != nullptr, steps, n_read, [&](int n) -> int {
+    const int bx = c->rec.box_x, by = c->rec.box_y;
+    std::vector<long long> records;
+    size_t record_words;
+    if (fetch_gather_records(c, n, records, &record_words) != LBM_SUCCESS) return LBM_FAILURE;
+    const size_t boxes = (size_t)lbm_coarse::coarse_boxes(c->p.nx, bx) * lbm_coarse::coarse_boxes(c->p.ny, by);
+    for (int i = 0; i < n; i++) coarse_frame(c, records.data() + (size_t)i * record_words, bx, by, out + (size_t)i * boxes);
+    return LBM_SUCCESS;
+  });
+}
+
 // the planes [first, first + 4) of every slab's sums, stitched by row_first; lbm_read_mean and lbm_read_mean2
 static int read_mean_planes(lbm_ctx* c, int first, double* const (&out)[4], long long* n_samples) {
   for (int s = 0; s < c->n_slabs; s++) {
@@ -4630,6 +4759,60 @@ int lbm_batch_read_profiles(lbm_batch* bt, int max_records, lbm_profile_line* ou
     const size_t member_words = gather_slot_words(bt) / n_members;
     for (size_t j = 0; j < (size_t)n * n_members; j++)
       lbm_profile::profile_lines_from_words(words + j * member_words, 1, &row_first, &ny, nx, ny, axes, out + j * lines);
+  });
+}
+
+// ---- coarse frames of a batch --------------------------------------------------------------------------------------
+// one launch for all members; a member is one slab, so every box row is whole and leaves as lines
+static int take_batch_coarse(lbm_batch* bt, long long* frame) {
+  lbm_ctx* c0 = bt->members[0];
+  const Slab& sl0 = c0->slab[0];
+  const size_t n_members = bt->members.size();
+  const int bx = bt->rec.box_x;
+  const lbm_coarse::SlabBoxRows g = coarse_slab_boxes(c0, sl0, bx, bt->rec.box_y);
+  const int groups = coarse_groups(g);
+  const long member_words = (long)lbm_coarse::slot_words(g);
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  const dim3 grid((unsigned)g.count * (unsigned)groups, 1, (unsigned)n_members);
+  hipLaunchKernelGGL(coarse_wide(bx) ? lbm::coarse_gather_batch<true> : lbm::coarse_gather_batch<false>, grid, dim3(lbm::kBlock), 0, bt->stream,
+                     lattice_args(c0, sl0), tab, g, groups, frame, member_words);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+
+int lbm_batch_set_coarse_frames(lbm_batch* bt, int every, int capacity, int bx, int by) {
+  size_t frame_bytes = 0;  // of all members
+  return rearm_batch_recorder(bt, kRecCoarse, every, capacity, [&]() -> int {
+    const lbm_ctx* c0 = bt->members[0];
+    const size_t n_members = bt->members.size();
+    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_coarse_frames: capacity %d, at least one frame is needed", capacity);
+    if (coarse_box_ok("lbm_batch_set_coarse_frames", c0, bx, by) != LBM_SUCCESS) return LBM_FAILURE;
+    const size_t member_bytes = coarse_slot_words(c0, c0->slab[0], bx, by) * sizeof(long long);
+    frame_bytes = n_members * member_bytes;
+    if ((long long)capacity * (long long)frame_bytes >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_coarse_frames: a ring of %d frames of %d members is %.2f GiB, 2 GiB or more (%zu bytes per member and frame)",
+               capacity, (int)n_members, (double)capacity * (double)frame_bytes / 1073741824.0, member_bytes);
+    return LBM_SUCCESS;
+  }, [&]() -> int {
+    const size_t ring_bytes = (size_t)capacity * frame_bytes;
+    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_coarse_frames: cannot allocate %d frames of %d members (%.1f MiB); coarse frames stay off", capacity,
+               (int)bt->members.size(), (double)ring_bytes / 1048576.0);
+    bt->rec.box_x = bx;
+    bt->rec.box_y = by;
+    return LBM_SUCCESS;
+  });
+}
+
+int lbm_batch_read_coarse_frames(lbm_batch* bt, int max_frames, lbm_profile_line* out, int* steps, int* n_read) {
+  return drain_batch_recorder(bt, kRecCoarse, max_frames, out != nullptr, steps, n_read, [&](int n, const long long* words) {
+    // a member's slot is its frame, line for line
+    const lbm_ctx* c0 = bt->members[0];
+    const int nx = c0->p.nx, ny = c0->slab[0].rows, row_first = 0, bx = bt->rec.box_x, by = bt->rec.box_y;
+    const size_t n_members = bt->members.size(), boxes = (size_t)lbm_coarse::coarse_boxes(nx, bx) * lbm_coarse::coarse_boxes(ny, by);
+    const size_t member_words = gather_slot_words(bt) / n_members;
+    for (size_t j = 0; j < (size_t)n * n_members; j++)
+      lbm_coarse::coarse_frame_from_words(words + j * member_words, 1, &row_first, &ny, nx, ny, bx, by, out + j * boxes);
   });
 }
 

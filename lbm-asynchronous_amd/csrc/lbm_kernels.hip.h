@@ -38,6 +38,7 @@
 #include "lbm_stats_row.h"
 #include "lbm_residual_row.h"
 #include "lbm_profile_row.h"
+#include "lbm_coarse_row.h"
 #include "lbm_enstrophy_row.h"
 #include "lbm_psi_row.h"
 #include "lbm_exact_round.h"
@@ -55,7 +56,8 @@ constexpr int kRecNone = 0, kRecFrames = 1, kRecProbes = 2, kRecMean = 3, kRecFi
 // lbm_set_profiles / lbm_batch_set_profiles, are recorder kinds of the host alone: force_gather, stats_gather,
 // residual_gather, profile_rows, profile_columns and their batch twins run behind the step kernels; so does the
 // vorticity's vorticity_gather, lbm_set_enstrophy / lbm_batch_set_enstrophy, and the stream function's scan, psi_band_totals,
-// psi_band_bases, psi_scan and psi_extrema, lbm_set_psi / lbm_batch_set_psi)
+// psi_band_bases, psi_scan and psi_extrema, lbm_set_psi / lbm_batch_set_psi, and the coarse frames' coarse_gather,
+// lbm_set_coarse_frames / lbm_batch_set_coarse_frames)
 
 // 1/3 rounded to fp32, and the two constant divisors of the equilibrium, folded in fp32
 // exactly as the reference's "2.f * c_sq" and "2.f * c_sq * c_sq" (SerialCode/d2q9-bgk.c:308,367-370)
@@ -3474,6 +3476,149 @@ __global__ __launch_bounds__(kBlock) void profile_columns_batch(const LatticeArg
                                                                 long long* lines, long member_words) {
   const int member = blockIdx.z;
   profile_column_lines(a, members[member].src, members[member].mask, rows, band_rows, lines + (size_t)member * member_words);
+}
+
+// ---------------------------------------------------------------------------------------------
+// coarse frames (lbm_set_coarse_frames, lbm_read_coarse): per box of bx x by cells what a line profile holds per line --
+// the exact sums of rho, jx, jy, ux, uy over the box's finite fluid cells and the two counts -- of a whole stored lattice
+// ---------------------------------------------------------------------------------------------
+// One sample is one launch per slab (behind the sub-call that ends at the sample step, like the profiles), over the box
+// rows that touch the slab (lbm_coarse_row.h: SlabBoxRows).  As in profile_columns a lane owns a column -- consecutive
+// lanes read consecutive addresses of a row -- and walks down it, here the rows of its box row that the slab owns, at most
+// LBM_COARSE_MAX_BOX of them, with profile_cell unchanged: five fixed-point accumulators and two counts per lane, a cell
+// that does not count added with sign 0.  The host picks one of two forms by bx:
+//   WIDE = false, bx <= 64: a wave owns a span of floor(64 / bx) whole boxes of one box row, lane l column l of the span;
+//     the lanes past the span's last box idle.  Workgroup g of a box row takes the spans 4 g .. 4 g + 3.  A box's lanes
+//     are totalled by a segmented reduction of shuffles -- offsets 1, 2, 4, ... below bx, a lane adds only what comes
+//     from a lane of its own box -- which leaves the box's total in its first lane, the head.  No LDS, no atomics.
+//   WIDE = true, 64 < bx <= 256: a workgroup owns one box, thread t < the box's width its column t.  A butterfly totals
+//     every word over the wave (as in profile_rows), lane i keeps word i, and the four waves meet in 48 words of LDS.
+// A box of a WHOLE box row is rounded here (exact_sum_round_hd: five roundings per box) and leaves as its 48-byte
+// line; a box of a PARTIAL box row leaves as its 47 limb and count words, stored plainly into the slot's seam area, whose
+// spare word the host has zeroed.  Every box has exactly one writer per slab: no global atomics, and no floating-point
+// addition happens on the device.
+template <bool WIDE>
+__device__ __forceinline__ void coarse_box_lines(const LatticeArgs& a, const float* src, const unsigned char* mask,
+                                                 const lbm_coarse::SlabBoxRows& g, int groups, long long* words) {
+  constexpr int L = lbm_exact::kExactLimbs, S = lbm_profile::kProfileSums, W = lbm_profile::kProfileWords;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int Y = g.first + (int)(blockIdx.x / (unsigned)groups), gx = (int)(blockIdx.x % (unsigned)groups);
+  // the slab's rows of box row Y, as rows of the slab
+  const int y0 = lbm_coarse::box_row_begin(g, Y), y1 = lbm_coarse::box_row_end(g, Y);
+  const int r0 = (y0 > g.row_first ? y0 : g.row_first) - g.row_first;
+  const int r1 = (y1 < g.row_first + g.rows ? y1 : g.row_first + g.rows) - g.row_first;
+  int X, x;       // this lane's box and column
+  bool active;    // the lane owns a column of the grid
+  bool head;      // ... the first of its box
+  if constexpr (WIDE) {
+    X = gx;
+    x = X * g.bx + (int)threadIdx.x;
+    active = (int)threadIdx.x < g.bx && x < a.nx;
+    head = threadIdx.x == 0;
+  } else {
+    const int per_wave = 64 / g.bx;  // boxes of a span
+    const int in_span = lane / g.bx;
+    X = (gx * (kBlock / 64) + wave) * per_wave + in_span;
+    x = (gx * (kBlock / 64) + wave) * per_wave * g.bx + lane;
+    active = in_span < per_wave && x < a.nx;
+    head = active && lane == in_span * g.bx;
+  }
+  long long acc[S][L];
+  int n_fluid = 0, n_bad = 0;
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int i = 0; i < L; i++) acc[j][i] = 0;
+  if (active) {
+#pragma unroll 1
+    for (int r = r0; r < r1; r++) {
+      const float* p = src + (long)r * a.row_pitch + x;
+      float f[kQ];
+#pragma unroll
+      for (int k = 0; k < kQ; k++) f[k] = p[k * a.plane_stride];
+      profile_cell(f, mask[(long)r * a.pitch + x] == 0, acc, n_fluid, n_bad);
+    }
+  }
+  bool whole;
+  if constexpr (WIDE) {
+    __shared__ unsigned long long sh[W];
+    if (threadIdx.x < W) sh[threadIdx.x] = 0ull;
+    long long mine = 0;
+    auto wave_total = [&](long long t, int word) {
+      for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+      mine = (lane == word) ? t : mine;
+    };
+#pragma unroll
+    for (int j = 0; j < S; j++)
+#pragma unroll
+      for (int i = 0; i < L; i++) wave_total(acc[j][i], j * L + i);
+    wave_total((long long)n_fluid, lbm_profile::kProfileFluidWord);
+    wave_total((long long)n_bad, lbm_profile::kProfileBadWord);
+    __syncthreads();
+    if (lane <= lbm_profile::kProfileBadWord && mine != 0) atomicAdd(sh + lane, (unsigned long long)mine);
+    __syncthreads();
+    long long* out = words + lbm_coarse::box_offset(g, X, Y, &whole);
+    if (whole) {  // threads 0 .. 4 round a sum each, thread 5 packs the counts
+      if (threadIdx.x < S) {
+        long long limbs[L];
+#pragma unroll
+        for (int i = 0; i < L; i++) limbs[i] = (long long)sh[threadIdx.x * L + i];
+        out[threadIdx.x] = __double_as_longlong(lbm_exact::exact_sum_round_hd(limbs));
+      } else if (threadIdx.x == S) {
+        out[S] = (long long)((sh[lbm_profile::kProfileBadWord] << 32) | (sh[lbm_profile::kProfileFluidWord] & 0xffffffffull));
+      }
+    } else if (threadIdx.x <= lbm_profile::kProfileBadWord) {
+      out[threadIdx.x] = (long long)sh[threadIdx.x];
+    }
+  } else {
+    // the segmented reduction: after the step of offset `off` a lane holds the sum of its box's lanes [lane, lane + 2 off)
+    const int box_end = (lane / g.bx + 1) * g.bx;  // one past the box's last lane
+    for (int off = 1; off < g.bx; off <<= 1) {
+      const bool take = lane + off < box_end;  // (a box's lanes lie in one wave: box_end <= 64 for every lane that counts)
+#pragma unroll
+      for (int j = 0; j < S; j++)
+#pragma unroll
+        for (int i = 0; i < L; i++) {
+          const long long t = __shfl_down(acc[j][i], off, 64);
+          acc[j][i] += take ? t : 0LL;
+        }
+      const int tf = __shfl_down(n_fluid, off, 64), tb = __shfl_down(n_bad, off, 64);
+      n_fluid += take ? tf : 0;
+      n_bad += take ? tb : 0;
+    }
+    if (head) {
+      long long* out = words + lbm_coarse::box_offset(g, X, Y, &whole);
+      if (whole) {
+        long long line[lbm_coarse::kCoarseLineWords];
+        lbm_coarse::line_words_from_sums(acc, n_fluid, n_bad, line);
+#pragma unroll
+        for (int i = 0; i < lbm_coarse::kCoarseLineWords; i++) out[i] = line[i];
+      } else {
+#pragma unroll
+        for (int j = 0; j < S; j++)
+#pragma unroll
+          for (int i = 0; i < L; i++) out[j * L + i] = acc[j][i];
+        out[lbm_profile::kProfileFluidWord] = (long long)n_fluid;
+        out[lbm_profile::kProfileBadWord] = (long long)n_bad;
+      }
+    }
+  }
+}
+
+// a slab's share of one coarse frame into its slot; grid: (box rows that touch the slab) * groups workgroups, box row
+// major, where groups = the workgroups of one box row: cx if WIDE, else ceil(ceil(cx / floor(64 / bx)) / 4)
+template <bool WIDE>
+__global__ __launch_bounds__(kBlock) void coarse_gather(const LatticeArgs a, const lbm_coarse::SlabBoxRows g, int groups, long long* words) {
+  coarse_box_lines<WIDE>(a, a.src, a.mask, g, groups, words);
+}
+
+// coarse_gather's twin for a batch: workgroup (., 0, member) on the member's current lattice and mask (members[member];
+// `a` carries the strides all members share), into the member's slot, member_words words apart
+template <bool WIDE>
+__global__ __launch_bounds__(kBlock) void coarse_gather_batch(const LatticeArgs a, const ResidentMember* members, const lbm_coarse::SlabBoxRows g,
+                                                              int groups, long long* words, long member_words) {
+  const int member = blockIdx.z;
+  coarse_box_lines<WIDE>(a, members[member].src, members[member].mask, g, groups, words + (size_t)member * member_words);
 }
 
 // ---------------------------------------------------------------------------------------------
