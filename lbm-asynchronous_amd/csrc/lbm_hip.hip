@@ -252,12 +252,8 @@ struct Slab {
                                            // lbm_set_mean_order(.., 2): eight, then u_x u_x, u_y u_y, u_x u_y, pressure pressure
   DeviceBuf<float> field_ring;             // lbm_set_field_frames: [slots][F][field_ny][window nx], this slab's rows of the window
   int field_y0 = 0, field_ny = 0;          // ... those rows: slab rows [field_y0, field_y0 + field_ny); none: no ring
-  DeviceBuf<long long> gather_ring;        // the gather kinds (records_behind): [slots][gather_slot_words]: this slab's exact sums
-                                           // (lbm_exact_sum.h) of a record.  lbm_set_forces: [bodies][lbm::kForceWords];
-                                           // lbm_set_stats: [lbm_stats::kStatsWords], the sums, a count and the max key;
-                                           // lbm_set_residual: [lbm_residual::kResidualWords], likewise; lbm_set_profiles:
-                                           // [rows (if ROWS) + nx (if COLUMNS)][lbm_profile::kProfileWords], this slab's row
-                                           // lines, then its rows' share of every column line
+  DeviceBuf<long long> gather_ring;        // the gather kinds (kGatherKinds): [slots][the kind's slot_words]: this slab's exact
+                                           // sums (lbm_exact_sum.h) of a record, laid out as the kind's slot_words says
   DeviceBuf<unsigned> force_links;         // lbm_set_forces: the boundary links of the owned blocked cells, by body, cell, k ...
   DeviceBuf<unsigned> force_starts;        // ... [bodies + 1]: where each body's links start
   int force_groups = 0;                    // workgroups per body of force_gather (0: the slab has no links)
@@ -430,16 +426,20 @@ struct GraphBuilder {
 // one kind whose slabs depend on each other (Slab::psi_in, psi_out).
 // Coarse frames (lbm_set_coarse_frames) likewise, by coarse_gather: a frame of per-box sums, rounded on the device except
 // in the box rows that two slabs share.
-// These seven gather kinds (records_behind) share one ring of int64 words per slab, Slab::gather_ring, whose slot holds
-// gather_slot_words words; a batch arms them on itself (lbm_batch::rec) with one ring for all members.
+// These seven gather kinds share one ring of int64 words per slab, Slab::gather_ring; a batch arms them on itself
+// (lbm_batch::rec) with one ring for all members.  What a gather kind is stands in one place, its entry of kGatherKinds.
 enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean,
        kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecResidual = 7, kRecProfiles = 8, kRecEnstrophy = 9,
-       kRecPsi = 10, kRecCoarse = 11, kRecKinds = 12 };
+       kRecPsi = 10, kRecCoarse = 11, kRecKinds = 12, kRecGatherFirst = kRecForces };
 // the kinds recorded by a gather launch behind the sub-call that ends at a sample step, whatever kernels advance the lattice
-constexpr bool records_behind(int kind) {
-  return kind == kRecForces || kind == kRecStats || kind == kRecResidual || kind == kRecProfiles || kind == kRecEnstrophy ||
-         kind == kRecPsi || kind == kRecCoarse;
-}
+constexpr bool is_gather(int kind) { return kind >= kRecGatherFirst && kind < kRecKinds; }
+// what a gather kind was armed with: the arguments of its setter that its slot's size, its launches and its reader depend on
+struct GatherArgs {
+  int bodies = 0;            // obstacle forces: bodies of the context, or of every member
+  int axes = 0;              // line profiles: the LBM_PROFILE_* bits
+  int box_x = 0, box_y = 0;  // coarse frames: the box's sides, cells
+  int base_steps = 0;        // steps_done at arming: the step of the residuals' baseline (the first row's span)
+};
 struct Recorder {
   int kind = kRecNone;
   int every = 0;
@@ -450,11 +450,9 @@ struct Recorder {
   int order = 0;            // mean fields: 1 = the four sums, 2 = also the four sums of products (lbm_set_mean_order)
   int fields = 0;           // field frames: the LBM_FIELD_* bits ...
   lbm_window window = {0, 0, 0, 0};  // ... and the window, global cells
-  int base_steps = 0;       // velocity residuals: steps_done at arming, the step of the baseline (the first row's span)
-  int axes = 0;             // line profiles: the LBM_PROFILE_* bits
-  int box_x = 0, box_y = 0; // coarse frames: the box's sides, cells
+  GatherArgs args;          // a gather kind: what it was armed with
 };
-// what differs between the kinds in the host's messages (indexed by kind; kRecNone keeps the empty defaults)
+// what differs between the kinds in the host's messages (kRecNone keeps the empty defaults)
 struct RecorderKind {
   const char* name = "";    // "<name> are armed"
   const char* noun = "";    // the short name
@@ -464,7 +462,8 @@ struct RecorderKind {
   const char* disarm = "";  // the call that disarms
   bool slotted = true;      // records wait in `slots` slots until read (false: they are accumulated, no call lacks room)
 };
-constexpr RecorderKind kRecorderKinds[kRecKinds] = {
+// the kinds the running kernels record themselves; the gather kinds' words stand in kGatherKinds (kind_words finds either)
+constexpr RecorderKind kRecorderKinds[kRecGatherFirst] = {
     {},
     {.name = "animation frames", .noun = "frames", .record = "frame", .setter = "lbm_set_frames",
      .reader = "lbm_read_frames", .disarm = "lbm_set_frames(ctx, 0, 0)"},
@@ -473,21 +472,54 @@ constexpr RecorderKind kRecorderKinds[kRecKinds] = {
     {.name = "mean fields", .noun = "mean fields", .record = "sample", .setter = "lbm_set_mean",
      .reader = "lbm_read_mean", .disarm = "lbm_set_mean(ctx, 0)", .slotted = false},
     {.name = "field frames", .noun = "field frames", .record = "field frame", .setter = "lbm_set_field_frames",
-     .reader = "lbm_read_field_frames", .disarm = "lbm_set_field_frames(ctx, 0, 0, 0, NULL)"},
-    {.name = "obstacle forces", .noun = "forces", .record = "row", .setter = "lbm_set_forces",
-     .reader = "lbm_read_forces", .disarm = "lbm_set_forces(ctx, 0, NULL, 0, 0)"},
-    {.name = "lattice statistics", .noun = "statistics", .record = "row", .setter = "lbm_set_stats",
-     .reader = "lbm_read_stats", .disarm = "lbm_set_stats(ctx, 0, 0)"},
-    {.name = "velocity residuals", .noun = "residuals", .record = "row", .setter = "lbm_set_residual",
-     .reader = "lbm_read_residual", .disarm = "lbm_set_residual(ctx, 0, 0)"},
-    {.name = "line profiles", .noun = "profiles", .record = "record", .setter = "lbm_set_profiles",
-     .reader = "lbm_read_profiles", .disarm = "lbm_set_profiles(ctx, 0, 0, 0)"},
-    {.name = "enstrophy rows", .noun = "enstrophy", .record = "row", .setter = "lbm_set_enstrophy",
-     .reader = "lbm_read_enstrophy", .disarm = "lbm_set_enstrophy(ctx, 0, 0)"},
-    {.name = "stream function rows", .noun = "the stream function", .record = "row", .setter = "lbm_set_psi",
-     .reader = "lbm_read_psi_rows", .disarm = "lbm_set_psi(ctx, 0, 0)"},
-    {.name = "coarse frames", .noun = "coarse frames", .record = "frame", .setter = "lbm_set_coarse_frames",
-     .reader = "lbm_read_coarse_frames", .disarm = "lbm_set_coarse_frames(ctx, 0, 0, 0, 0)"}};
+     .reader = "lbm_read_field_frames", .disarm = "lbm_set_field_frames(ctx, 0, 0, 0, NULL)"}};
+
+// Whose records a reader converts: the slabs of a context (one lattice, `shares` slabs), or the members of a batch (each a
+// lattice of one slab that starts at row 0).  The fetched words are [record][lattice][share][the share's slot]
+struct GatherOwner {
+  int nx = 0, ny = 0;
+  size_t lattices = 1;          // per record
+  int shares = 1;               // slabs per lattice
+  int row_first[kMaxSlabs] = {0}, row_count[kMaxSlabs] = {0};
+  size_t lattice_words = 0;     // ... and one lattice's shares are this many words
+};
+// A hook that allocates answers LBM_SUCCESS, LBM_FAILURE (it has said why) or kNoRoom: the driver then says that the ring
+// and `also` could not be allocated.
+constexpr int kNoRoom = 2;
+// One gather kind: everything that differs between the seven, for a context and for a batch.  The drivers (arm_gather,
+// arm_batch_gather, drain_gather, drain_batch_gather, take_record, lbm_batch_run) know no kind.
+struct GatherKind {
+  RecorderKind ctx;          // the words of a context's messages ...
+  const char* batch_setter;  // ... and those of a batch's that differ
+  const char* batch_reader;
+  const char* batch_disarm;
+  const char* stays_off;     // "cannot allocate ...; <stays_off>"
+  const char* spread;        // multi-process contexts: "<spread> would be spread over the ranks"
+  const char* of_a_batch;    // members: "so <of_a_batch> armed on the batch"
+  const char* of = "";       // "cannot allocate 4 rows<of> ...", a format of args.bodies
+  const char* also = "";     // "... (1.0 MiB per slab)<also>": what the kind's hook allocates besides, where kNoRoom tells of it
+  bool per_slab = false;     // the slot's size depends on the slab: the messages name the slab
+  // int64 words of one slab's (or member's) slot
+  size_t (*slot_words)(const lbm_ctx* c, const Slab& sl, const GatherArgs& a);
+  // refuses the kind's own arguments, or nothing (nullptr); members: of the batch that arms, 0: a context does
+  int (*check)(const char* who, const lbm_ctx* c, size_t members, int capacity, const GatherArgs& a) = nullptr;
+  // the kind's buffers besides the ring, or none (nullptr): of slab s behind its ring, and of a batch behind its ring;
+  // own: what the kind's setter hands to its hook
+  int (*alloc_slab)(const char* who, lbm_ctx* c, int s, const GatherArgs& a, const void* own) = nullptr;
+  int (*alloc_batch)(const char* who, lbm_batch* bt, const GatherArgs& a, const void* own) = nullptr;
+  // one record of a context: every slab's share into its zeroed slot (take_per_slab: launch(c, s, slot) on every slab's
+  // compute stream, side by side) ...
+  int (*take)(lbm_ctx* c);
+  int (*launch)(lbm_ctx* c, int s, long long* words) = nullptr;
+  // ... and of a batch: all members' into `slot`, zeroed, on the batch's stream
+  int (*take_batch)(lbm_batch* bt, long long* slot);
+  // the words of the n oldest records, fetched, into the caller's rows (r.read: the ordinal of the first)
+  void (*rows)(const GatherOwner& g, const Recorder& r, int n, const long long* words, void* out);
+};
+namespace {
+const GatherKind& gather_kind(int kind);     // kGatherKinds[kind - kRecGatherFirst]
+const RecorderKind& kind_words(int kind);    // of any kind, as a context speaks of it
+}
 
 struct lbm_ctx {
   lbm_params p;
@@ -557,18 +589,17 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
   int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
                                     // (a batch records one kind, so at most one count is non-zero; a gather kind is armed
-                                    // on the batch, by its lbm_batch_set_* of kBatchKinds, and counts as one)
-  // the gather kinds (records_behind) of all members: the members' own recorders stay off, the batch keeps the one
-  // recorder and the one ring (rearm_batch_recorder, drain_batch_recorder, release_batch_recorder); every lbm_batch_run
+                                    // on the batch, by its lbm_batch_set_*, and counts as one)
+  // the gather kinds (kGatherKinds) of all members: the members' own recorders stay off, the batch keeps the one
+  // recorder and the one ring (arm_batch_gather, drain_batch_gather, release_batch_recorder); every lbm_batch_run
   // runs as the sub-calls that end at its sample steps
-  Recorder rec;                                  // one of kBatchKinds while armed
-  DeviceBuf<long long> gather_ring;              // device: [slots][members][a member's gather_slot_words]
+  Recorder rec;                                  // a gather kind while armed
+  DeviceBuf<long long> gather_ring;              // device: [slots][members][the kind's slot_words of a member]
   DeviceBuf<float> residual_planes;              // lbm_batch_set_residual: device: [members][2][rows][nx]: the members' remembered u_x and u_y
   DeviceBuf<long long> psi_totals;               // lbm_batch_set_psi: device: [members][bands][nx][kExactLimbs]: the scan's totals, then bases
   DeviceBuf<lbm::PsiCandidate> psi_cand;         // ... [members][bands][column groups]
   int psi_band_rows = 0;                         // ... rows of a band of every member's scan
-  int force_bodies = 0;                          // lbm_batch_set_forces: bodies of every member
-  int force_groups = 0;                          // workgroups per (member, body) of force_gather_batch (0: no member has a link)
+  int force_groups = 0;                          // lbm_batch_set_forces: workgroups per (member, body) of force_gather_batch (0: no member has a link)
   std::vector<int> force_link_counts;            // [members][bodies]
   std::vector<DeviceBuf<unsigned>> force_links;  // [members]: the member's boundary links, by body, cell, k ...
   std::vector<DeviceBuf<unsigned>> force_starts; // ... and [bodies + 1]: where each body's links start
@@ -588,38 +619,6 @@ struct lbm_batch {
   DeviceBuf<long long> until_history;               // device: [until_history_rows][members][kResidualWords]
   size_t until_history_rows = 0;
 };
-
-// The kinds armed on a batch as a whole (lbm_batch::rec): what differs between them in the messages and in lbm_batch_run,
-// where take() launches the gather of all members into the record's zeroed slot behind a sub-call that ends at a sample
-// step.  The other words of the shared messages (noun, record) are the kind's of kRecorderKinds.
-static int take_batch_forces(lbm_batch* bt, long long* row);
-static int take_batch_stats(lbm_batch* bt, long long* row);
-static int take_batch_residual(lbm_batch* bt, long long* row);
-static int take_batch_profiles(lbm_batch* bt, long long* record);
-static int take_batch_enstrophy(lbm_batch* bt, long long* row);
-static int take_batch_psi(lbm_batch* bt, long long* row);
-static int take_batch_coarse(lbm_batch* bt, long long* frame);
-struct BatchKind {
-  int kind;
-  const char* setter;
-  const char* reader;
-  const char* disarm;
-  int (*take)(lbm_batch*, long long*);
-};
-static const BatchKind kBatchKinds[] = {
-    {kRecForces, "lbm_batch_set_forces", "lbm_batch_read_forces", "lbm_batch_set_forces(batch, 0, NULL, 0, 0)", take_batch_forces},
-    {kRecStats, "lbm_batch_set_stats", "lbm_batch_read_stats", "lbm_batch_set_stats(batch, 0, 0)", take_batch_stats},
-    {kRecResidual, "lbm_batch_set_residual", "lbm_batch_read_residual", "lbm_batch_set_residual(batch, 0, 0)", take_batch_residual},
-    {kRecProfiles, "lbm_batch_set_profiles", "lbm_batch_read_profiles", "lbm_batch_set_profiles(batch, 0, 0, 0)", take_batch_profiles},
-    {kRecEnstrophy, "lbm_batch_set_enstrophy", "lbm_batch_read_enstrophy", "lbm_batch_set_enstrophy(batch, 0, 0)", take_batch_enstrophy},
-    {kRecPsi, "lbm_batch_set_psi", "lbm_batch_read_psi_rows", "lbm_batch_set_psi(batch, 0, 0)", take_batch_psi},
-    {kRecCoarse, "lbm_batch_set_coarse_frames", "lbm_batch_read_coarse_frames", "lbm_batch_set_coarse_frames(batch, 0, 0, 0, 0)",
-     take_batch_coarse}};
-static const BatchKind* batch_kind(int kind) {
-  for (const BatchKind& k : kBatchKinds)
-    if (k.kind == kind) return &k;
-  return nullptr;
-}
 
 namespace {
 
@@ -1432,15 +1431,13 @@ const void* resident_form(int shape) {
 }
 const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = false) {
   using Form = const void* (*)(int);
-  static const Form forms[2][kRecKinds] = {
+  static const Form forms[2][kRecGatherFirst] = {
       {resident_form<false, kRecNone>, resident_form<false, kRecFrames>, resident_form<false, kRecProbes>, resident_form<false, kRecMean>,
-       resident_form<false, kRecFields>, resident_form<false, kRecNone>, resident_form<false, kRecNone>,
-       resident_form<false, kRecNone>, resident_form<false, kRecNone>, resident_form<false, kRecNone>,
-       resident_form<false, kRecNone>, resident_form<false, kRecNone>},  // (the gather kinds run the plain form)
+       resident_form<false, kRecFields>},
       {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>, resident_form<true, kRecMean>,
-       resident_form<true, kRecFields>, resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>,
-       resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>, resident_form<true, kRecNone>}};
-  return forms[batch][rec]((rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
+       resident_form<true, kRecFields>}};
+  return forms[batch][is_gather(rec) ? kRecNone : rec](  // (the gather kinds run the plain form)
+      (rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
 }
 
 // what the resident kernels read of a context's recorder (a batch keeps one such entry per member); all zero while that
@@ -1619,7 +1616,7 @@ long long recorded_between(const Recorder& r, long long from, long long to) {
 // lbm_run / lbm_batch_run refuse a call whose records would not fit the free slots, before any work is issued; a kind
 // that accumulates its records (the mean fields) has room for any call
 int recorder_fits(const Recorder& r, int steps_done, int n_steps, const char* who, const char* reader) {
-  const RecorderKind& k = kRecorderKinds[r.kind];
+  const RecorderKind& k = kind_words(r.kind);
   if (!k.slotted) return LBM_SUCCESS;
   const long long add = recorded_between(r, steps_done, (long long)steps_done + n_steps);
   const long long waiting = r.written - r.read;
@@ -1629,7 +1626,7 @@ int recorder_fits(const Recorder& r, int steps_done, int n_steps, const char* wh
   return LBM_SUCCESS;
 }
 int recorder_fits(const lbm_ctx* c, int n_steps, const char* who) {
-  return recorder_fits(c->rec, c->steps_done, n_steps, who, kRecorderKinds[c->rec.kind].reader);
+  return recorder_fits(c->rec, c->steps_done, n_steps, who, kind_words(c->rec.kind).reader);
 }
 
 // workgroups of stats_gather / stats_gather_batch for `cells` cells of a slab or member, V at a time per lane: one unit
@@ -1684,7 +1681,7 @@ int profile_band_rows(int rows, int nx) {
 // its share of the column lines
 void launch_profiles(const lbm_ctx* c, const Slab& sl, long long* lines) {
   const int nx = c->p.nx;
-  if (c->rec.axes & LBM_PROFILE_ROWS) {
+  if (c->rec.args.axes & LBM_PROFILE_ROWS) {
     const dim3 grid(ceil_div(sl.rows, lbm::kBlock / 64));
     if (stats_vector(nx) == 4)
       hipLaunchKernelGGL(lbm::profile_rows<4>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, lines);
@@ -1692,7 +1689,7 @@ void launch_profiles(const lbm_ctx* c, const Slab& sl, long long* lines) {
       hipLaunchKernelGGL(lbm::profile_rows<1>, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), sl.rows, lines);
     lines += (size_t)sl.rows * lbm_profile::kProfileWords;
   }
-  if (c->rec.axes & LBM_PROFILE_COLUMNS) {
+  if (c->rec.args.axes & LBM_PROFILE_COLUMNS) {
     const int band_rows = profile_band_rows(sl.rows, nx);
     hipLaunchKernelGGL(lbm::profile_columns, dim3(ceil_div(nx, lbm::kProfileColumns), ceil_div(sl.rows, band_rows)), dim3(lbm::kBlock), 0,
                        sl.compute, lattice_args(c, sl), sl.rows, band_rows, lines);
@@ -1869,31 +1866,12 @@ int take_psi_record(lbm_ctx* c) {
   return LBM_SUCCESS;
 }
 
-// int64 words a gather kind records per slab (or batch member) and sample: of `bodies` bodies (forces), of `rows` rows of
-// nx cells along `axes` (profiles).  The one place a slot's size is computed: the setters call it with what they are about
-// to arm, everything else through gather_slot_words with what is armed.  (The coarse frames' slot follows from the slab's
-// box rows, not from a count: coarse_slot_words.)
-size_t gather_words(int kind, size_t bodies = 0, int rows = 0, int nx = 0, int axes = 0) {
-  switch (kind) {
-    case kRecForces: return bodies * (size_t)lbm::kForceWords;
-    case kRecStats: return lbm_stats::kStatsWords;
-    case kRecResidual: return lbm_residual::kResidualWords;
-    case kRecProfiles: return lbm_profile::profile_slab_lines(rows, nx, axes) * lbm_profile::kProfileWords;
-    case kRecEnstrophy: return lbm_enstrophy::kEnstrophyWords;
-    case kRecPsi: return lbm_psi::kPsiWords;
-    default: return 0;
-  }
-}
-// words of one slot of a slab's gather_ring: this slab's share of a record
-size_t gather_slot_words(const lbm_ctx* c, const Slab& sl) {
-  if (c->rec.kind == kRecCoarse) return coarse_slot_words(c, sl, c->rec.box_x, c->rec.box_y);
-  return gather_words(c->rec.kind, c->force_link_counts.size(), sl.rows, c->p.nx, c->rec.axes);
-}
+// words of one slot of a slab's gather_ring: this slab's share of a record of the armed kind
+size_t gather_slot_words(const lbm_ctx* c, const Slab& sl) { return gather_kind(c->rec.kind).slot_words(c, sl, c->rec.args); }
 // ... and of a batch's: that of slab 0 for every member, one after the other
 size_t gather_slot_words(const lbm_batch* bt) {
   const lbm_ctx* c0 = bt->members[0];
-  if (bt->rec.kind == kRecCoarse) return bt->members.size() * coarse_slot_words(c0, c0->slab[0], bt->rec.box_x, bt->rec.box_y);
-  return bt->members.size() * gather_words(bt->rec.kind, (size_t)bt->force_bodies, c0->slab[0].rows, c0->p.nx, bt->rec.axes);
+  return bt->members.size() * gather_kind(bt->rec.kind).slot_words(c0, c0->slab[0], bt->rec.args);
 }
 
 // the slot of the next record of a gather ring, zeroed on `stream` (the gather kernels add into it): nullptr where that failed
@@ -1920,24 +1898,19 @@ int fetch_ring(const T* ring, size_t slot_words, const Recorder& r, int n, hipSt
 
 // the record of the current (stored) lattice into the next slot, on every slab's compute stream: the frame of its rows,
 // or the gathered samples of the probes in its rows; or, for the mean fields, the sample of its rows added to their sums;
-// or, for a gather kind, the slab's share of the record added into its zeroed slot
+// or, for a gather kind, what its take says
 int take_record(lbm_ctx* c) {
-  const size_t slot = kRecorderKinds[c->rec.kind].slotted ? (size_t)(c->rec.written % c->rec.slots) : 0;
-  const size_t n_probes = c->probe_cells.size();
-  const bool vort_edges = (c->rec.kind == kRecEnstrophy && c->n_slabs > 1);  // the sample reads the neighbours' boundary rows
-  if (vort_edges && mark_vorticity_ready(c) != LBM_SUCCESS) return LBM_FAILURE;
-  if (c->rec.kind == kRecPsi) {  // the slabs depend on each other: issued in their order
-    if (take_psi_record(c) != LBM_SUCCESS) return LBM_FAILURE;
+  if (is_gather(c->rec.kind)) {
+    if (gather_kind(c->rec.kind).take(c) != LBM_SUCCESS) return LBM_FAILURE;
     c->rec.written++;
     return LBM_SUCCESS;
   }
+  const size_t slot = kind_words(c->rec.kind).slotted ? (size_t)(c->rec.written % c->rec.slots) : 0;
+  const size_t n_probes = c->probe_cells.size();
   if (for_slabs(c, [&](int s) -> int {
         Slab& sl = c->slab[s];
         HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
         const long n = (long)sl.rows * c->p.nx;
-        long long* words = nullptr;
-        if (records_behind(c->rec.kind) && !(words = zeroed_slot(sl.gather_ring, gather_slot_words(c, sl), c->rec, sl.compute)))
-          return LBM_FAILURE;
         if (c->rec.kind == kRecFrames)
           hipLaunchKernelGGL(lbm::frame_umag, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              sl.frames + slot * n);
@@ -1948,23 +1921,6 @@ int take_record(lbm_ctx* c) {
             hipLaunchKernelGGL(lbm::field_frame, dim3(ceil_div(cells, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), c->p.density,
                                c->rec.fields, w.x0, sl.field_y0, w.nx, sl.field_ny,
                                sl.field_ring + slot * (size_t)__builtin_popcount((unsigned)c->rec.fields) * (size_t)cells);
-        } else if (c->rec.kind == kRecForces) {
-          // a slab without links records the zeros
-          if (sl.force_groups > 0)
-            hipLaunchKernelGGL(lbm::force_gather, dim3(sl.force_groups, (unsigned)c->force_link_counts.size()), dim3(lbm::kBlock), 0,
-                               sl.compute, lattice_args(c, sl), (const unsigned*)sl.force_links, (const unsigned*)sl.force_starts, words);
-        } else if (c->rec.kind == kRecStats)
-          launch_stats_gather(c, sl, words);
-        else if (c->rec.kind == kRecResidual)
-          launch_residual_gather(c, sl, sl.residual_planes, words, false);  // also replaces the slab's remembered field by this lattice's
-        else if (c->rec.kind == kRecProfiles)
-          launch_profiles(c, sl, words);  // (profile_rows leaves a line's spare word as zeroed)
-        else if (c->rec.kind == kRecCoarse)
-          launch_coarse(c, sl, c->rec.box_x, c->rec.box_y, words);
-        else if (c->rec.kind == kRecEnstrophy) {
-          if (vort_edges && copy_vorticity_edges(c, s, sl.vort_edges) != LBM_SUCCESS) return LBM_FAILURE;
-          launch_vorticity_gather(c, sl, vort_edges ? sl.vort_edges.get() : nullptr, 0, sl.rows, nullptr, words);
-          if (vort_edges) HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_vort_done, sl.compute));
         } else if (c->rec.kind == kRecMean)
           hipLaunchKernelGGL(lbm::mean_accumulate, dim3(ceil_div(n, 256)), dim3(256), 0, sl.compute, lattice_args(c, sl), sl.rows,
                              c->p.density, sl.mean_sums, n, c->rec.order);
@@ -1975,7 +1931,6 @@ int take_record(lbm_ctx* c) {
         return LBM_SUCCESS;
       }) != LBM_SUCCESS)
     return LBM_FAILURE;
-  if (vort_edges && await_vorticity_done(c) != LBM_SUCCESS) return LBM_FAILURE;
   c->rec.written++;
   return LBM_SUCCESS;
 }
@@ -2004,7 +1959,7 @@ int run_passes(lbm_ctx* c, int n_steps, bool resident, bool record_t0) {
     const long long records = recorded_between(c->rec, c->steps_done, (long long)c->steps_done + n_steps);
     if (run_resident(c, n_steps) != LBM_SUCCESS) return LBM_FAILURE;
     c->steps_done += n_steps;
-    if (!records_behind(c->rec.kind)) c->rec.written += records;  // recorded by the kernel itself (forces, statistics, residuals: by the caller, behind it)
+    if (!is_gather(c->rec.kind)) c->rec.written += records;  // recorded by the kernel itself (a gather kind: by the caller, behind it)
     return LBM_SUCCESS;
   }
 
@@ -2061,10 +2016,10 @@ int run_steps(lbm_ctx* c, int n_steps, float* kernel_ms) {
 
   // resident or per-pass: decided once per call, whether a recorder (frames or probes) is armed or not
   const bool resident = c->plan.resident && n_steps >= c->plan.resident_min_steps;
-  const bool behind = records_behind(c->rec.kind);
+  const bool behind = is_gather(c->rec.kind);
   if (c->rec.kind != kRecNone && (!resident || behind)) {
     // per-pass kernels: the call runs as the sub-calls that end at its recorder steps, each followed by its frame or
-    // its sample row (the step kernels themselves record nothing).  The forces and the statistics always run so, whatever kernels advance
+    // its sample row (the step kernels themselves record nothing).  The gather kinds always run so, whatever kernels advance
     // the lattice: a sub-call long enough for the resident kernel runs it (its plain form), as a call of that length would
     const int e = c->rec.every;
     for (int t = 0; t < n_steps;) {
@@ -2658,7 +2613,7 @@ lbm_ctx* create_common(const lbm_params* params, const ObstacleSource& obst, con
   return c;
 }
 
-// ---- the recorder of a context: what the setters and the readers of kRecorderKinds share --------------------------
+// ---- the recorder of a context: what the setters and the readers of every kind share -------------------------------
 // a batch member's entry of the table the batched launches of one kind read; the table is allocated, all zero, when the
 // first member arms that kind
 template <class Entry>
@@ -2714,13 +2669,13 @@ void release_recorder(lbm_ctx* c) {
   c->rec = Recorder{};
 }
 
-// What the setters of every kind of kRecorderKinds (for the mean fields: set_mean_order, behind lbm_set_mean and
+// What the setters of every kind (the gather kinds': arm_gather; for the mean fields: set_mean_order, behind lbm_set_mean and
 // lbm_set_mean_order) share behind their own argument checks.  Arming (every > 0) is refused, with nothing touched,
 // where this kind cannot record.  Then the launches in flight are awaited and a recorder of this kind is disarmed; to arm, allocate() provides the kind's buffers of every slab (and says what it could not) before the
 // recorder's fields, the member's batch entry and the batch's count of armed members are set.
 template <class Allocate>
 int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate allocate, const char* who = nullptr) {
-  const RecorderKind& k = kRecorderKinds[kind];
+  const RecorderKind& k = kind_words(kind);
   const char* const setter = who ? who : k.setter;  // the kind's other setter (lbm_set_mean_order) speaks under its own name
   lbm_batch* bt = c->batch;
   if (every > 0) {
@@ -2730,18 +2685,18 @@ int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate alloc
                c->halo_mode == LBM_HALO_STALE ? "stale" : "freshest", k.record, k.noun);
     for (int other = kRecFrames; other < kRecKinds; other++) {  // every other kind
       if (other == kind) continue;
-      const RecorderKind& o = kRecorderKinds[other];
+      const RecorderKind& o = kind_words(other);
       if (c->rec.kind == other)
         LBM_FAIL(LBM_FAILURE, "%s: %s are armed (%s) and a context has one recorder -- disarm them with %s first", setter, o.name,
                  o.setter, o.disarm);
       if (bt && bt->rec.kind == other)  // (a kind no member arms: the batch does)
         LBM_FAIL(LBM_FAILURE, "%s: this batch has %s armed (%s); a batch records one kind -- disarm them with %s first", setter, o.name,
-                 batch_kind(other)->setter, batch_kind(other)->disarm);
+                 gather_kind(other).batch_setter, gather_kind(other).batch_disarm);
       if (bt && bt->armed[other] > 0)
         LBM_FAIL(LBM_FAILURE, "%s: a member of this batch has %s armed (%s); a batch records one kind: frames, probes, mean fields or field frames",
                  setter, o.name, o.setter);
     }
-    if (c->plan.resident && !records_behind(kind)) {  // (the forces, the statistics and the residuals record behind the plain form, which every resident shape runs)
+    if (c->plan.resident && !is_gather(kind)) {  // (the gather kinds record behind the plain form, which every resident shape runs)
       // the recorder forms of four-row bands defer the acceleration of the interior pair only (lbm::resident_band): the lid
       // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form must run one workgroup per CU
       if (c->plan.resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
@@ -2781,12 +2736,12 @@ int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate alloc
   return LBM_SUCCESS;
 }
 
-// What the readers of the slotted kinds share, a context's (drain_recorder) and a batch's (drain_batch_recorder), once
+// What the readers of the slotted kinds share, a context's (drain_recorder) and a batch's (drain_batch_gather), once
 // the work in flight has been awaited: without outputs the call tells how many records of `kind` wait in r; else copy(n)
 // fetches the n oldest (at most max_records) before their steps are told and they are retired.
 template <class Copy>
 int drain_ring(Recorder& r, int kind, const char* reader, int max_records, bool has_out, int* steps, int* n_read, Copy copy) {
-  const RecorderKind& k = kRecorderKinds[kind];
+  const RecorderKind& k = kind_words(kind);
   const long long waiting = (r.kind == kind) ? r.written - r.read : 0;
   if (!has_out && !steps) {
     *n_read = (int)waiting;
@@ -2804,7 +2759,7 @@ int drain_ring(Recorder& r, int kind, const char* reader, int max_records, bool 
 }
 template <class Copy>
 int drain_recorder(lbm_ctx* c, int kind, int max_records, bool has_out, int* steps, int* n_read, Copy copy) {
-  const char* const reader = kRecorderKinds[kind].reader;
+  const char* const reader = kind_words(kind).reader;
   if (!c || !n_read) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", reader);
   *n_read = 0;
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
@@ -2812,7 +2767,7 @@ int drain_recorder(lbm_ctx* c, int kind, int max_records, bool has_out, int* ste
 }
 
 // every slab's share of the n oldest records of a gather kind, gathered as records[record][slab's share]; *record_words:
-// the words of one record, all shares.  The kind's words-to-row function merges the shares of a record.
+// the words of one record, all shares.  The kind's rows hook merges the shares of a record.
 int fetch_gather_records(lbm_ctx* c, int n, std::vector<long long>& records, size_t* record_words) {
   size_t share_at[kMaxSlabs + 1] = {0};  // where slab s's words start in a record's
   for (int s = 0; s < c->n_slabs; s++) share_at[s + 1] = share_at[s] + gather_slot_words(c, c->slab[s]);
@@ -2830,7 +2785,7 @@ int fetch_gather_records(lbm_ctx* c, int n, std::vector<long long>& records, siz
   return LBM_SUCCESS;
 }
 
-// ---- the recorder of a batch: what the lbm_batch_set_* and lbm_batch_read_* of kBatchKinds share ---------------------
+// ---- the recorder of a batch: what the lbm_batch_set_* and lbm_batch_read_* share ------------------------------------
 // what the batched kernels read of every member, [parity of cur][members]
 std::vector<lbm::ResidentMember> member_table(const lbm_batch* bt) {
   const size_t n_members = bt->members.size();
@@ -2874,7 +2829,7 @@ void release_batch_recorder(lbm_batch* bt) {
   bt->force_links.clear();
   bt->force_starts.clear();
   bt->force_link_counts.clear();
-  bt->force_bodies = bt->force_groups = 0;
+  bt->force_groups = 0;
   if (bt->rec.kind != kRecNone) bt->armed[bt->rec.kind] = 0;
   bt->rec = Recorder{};
 }
@@ -2892,62 +2847,9 @@ int batch_members_free(const lbm_batch* bt, const char* who) {
     const Recorder& r = bt->members[i]->rec;
     if (r.kind != kRecNone)
       LBM_FAIL(LBM_FAILURE, "%s: member %d has %s armed (%s); a batch records one kind -- disarm them with %s first", who, (int)i,
-               kRecorderKinds[r.kind].name, kRecorderKinds[r.kind].setter, kRecorderKinds[r.kind].disarm);
+               kind_words(r.kind).name, kind_words(r.kind).setter, kind_words(r.kind).disarm);
   }
   return LBM_SUCCESS;
-}
-
-// What the four lbm_batch_set_* share (rearm_recorder does so for a context).  Disarming while the batch's one recorder
-// holds another kind is a silent no-op, arming then is refused.  To arm, check() makes the kind's own checks of its
-// arguments; like every check here it runs, touching nothing of the recorder, before the launches in flight are awaited
-// and a recorder of this kind is released.  Then allocate() provides the kind's buffers (and says what it could not) and
-// sets the recorder's fields that only this kind has, before the common ones are set.
-template <class Check, class Allocate>
-int rearm_batch_recorder(lbm_batch* bt, int kind, int every, int capacity, Check check, Allocate allocate) {
-  const BatchKind& k = *batch_kind(kind);
-  if (!bt) LBM_FAIL(LBM_FAILURE, "%s: null batch", k.setter);
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "%s: negative interval %d", k.setter, every);
-  if (bt->rec.kind != kRecNone && bt->rec.kind != kind) {
-    if (every == 0) return LBM_SUCCESS;
-    const BatchKind* o = batch_kind(bt->rec.kind);
-    LBM_FAIL(LBM_FAILURE, "%s: this batch has %s armed (%s); a batch records one kind -- disarm them with %s first", k.setter,
-             kRecorderKinds[bt->rec.kind].name, o->setter, o->disarm);
-  }
-  if (every > 0 && (check() != LBM_SUCCESS || batch_members_free(bt, k.setter) != LBM_SUCCESS)) return LBM_FAILURE;
-  // the buffers may still be written by launches in flight
-  HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
-  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
-  release_batch_recorder(bt);
-  if (every == 0) return LBM_SUCCESS;
-  if (ensure_member_table(bt, k.setter, kRecorderKinds[kind].noun) != LBM_SUCCESS || allocate() != LBM_SUCCESS) {
-    (void)hipGetLastError();  // a failed allocation must not surface at the next launch
-    release_batch_recorder(bt);
-    return LBM_FAILURE;
-  }
-  bt->rec.kind = kind;
-  bt->rec.every = every;
-  bt->rec.slots = capacity;
-  bt->rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
-  bt->armed[kind] = 1;
-  return LBM_SUCCESS;
-}
-
-// What the four lbm_batch_read_* share (drain_recorder does so for a context): convert(n, words) turns the words of the n
-// oldest records, [record][member][a member's words], into the caller's rows.
-template <class Convert>
-int drain_batch_recorder(lbm_batch* bt, int kind, int max_records, bool has_out, int* steps, int* n_read, Convert convert) {
-  const char* const reader = batch_kind(kind)->reader;
-  if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", reader);
-  *n_read = 0;
-  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
-  return drain_ring(bt->rec, kind, reader, max_records, has_out, steps, n_read, [&](int n) -> int {
-    const size_t words = gather_slot_words(bt);
-    std::vector<long long> stage((size_t)n * words);
-    HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
-    if (fetch_ring(bt->gather_ring.get(), words, bt->rec, n, bt->stream, stage.data()) != LBM_SUCCESS) return LBM_FAILURE;
-    convert(n, stage.data());
-    return LBM_SUCCESS;
-  });
 }
 
 // ---- obstacle forces: what lbm_set_forces (per slab) and lbm_batch_set_forces (per member) share ------------------
@@ -3030,6 +2932,617 @@ void round_forces(const long long* words, size_t n, double* out) {
     out[2 * j] = finite ? 2.0 * lbm_exact::exact_sum_round(fx) : std::nan("");
     out[2 * j + 1] = finite ? 2.0 * lbm_exact::exact_sum_round(fy) : std::nan("");
   }
+}
+
+
+// ================================================================================================
+// The gather kinds: each kind's hooks, the one table of them, and the drivers that arm and drain any kind
+// ================================================================================================
+// whose records a reader converts (lattice_words: the caller's, once the words are fetched)
+GatherOwner context_owner(const lbm_ctx* c) {
+  GatherOwner g;
+  g.nx = c->p.nx;
+  g.ny = c->p.ny;
+  g.shares = c->n_slabs;
+  for (int s = 0; s < c->n_slabs; s++) {
+    g.row_first[s] = c->slab[s].row_first;
+    g.row_count[s] = c->slab[s].rows;
+  }
+  return g;
+}
+GatherOwner members_owner(const lbm_batch* bt) {
+  const lbm_ctx* c0 = bt->members[0];
+  GatherOwner g;
+  g.nx = c0->p.nx;
+  g.ny = g.row_count[0] = c0->slab[0].rows;
+  g.lattices = bt->members.size();
+  return g;
+}
+
+// ---- one record of a batch (the forces': below) ------------------------------------------------------------------------
+// the statistics: one stats_gather_batch for all members
+int take_batch_stats(lbm_batch* bt, long long* row) {
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  const Slab& sl0 = c0->slab[0];
+  const int v = stats_vector(c0->p.nx);
+  const dim3 grid((unsigned)stats_groups((long)sl0.rows * c0->p.nx, v), 1, (unsigned)n_members);
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  if (v == 4)
+    hipLaunchKernelGGL(lbm::stats_gather_batch<4>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, row);
+  else
+    hipLaunchKernelGGL(lbm::stats_gather_batch<1>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, row);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+
+// the enstrophy: one vorticity_gather_batch for all members, each a periodic slab of its own
+int take_batch_enstrophy(lbm_batch* bt, long long* row) {
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  const Slab& sl0 = c0->slab[0];
+  const int nx = c0->p.nx, band_rows = vorticity_band_rows(sl0.rows, nx);
+  const dim3 grid((unsigned)vorticity_groups(sl0.rows, nx, band_rows), 1, (unsigned)n_members);
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  hipLaunchKernelGGL(stats_vector(nx) == 4 ? lbm::vorticity_gather_batch<4> : lbm::vorticity_gather_batch<1>, grid, dim3(lbm::kBlock), 0,
+                     bt->stream, lattice_args(c0, sl0), tab, sl0.rows, band_rows, row);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+
+// the stream function: ONE launch of each of the scan's kernels for all members (grid z is the member; psi_extrema: grid x),
+// each member a grid of its own from row 0
+int take_batch_psi(lbm_batch* bt, long long* row) {
+  lbm_ctx* c0 = bt->members[0];
+  const unsigned n_members = (unsigned)bt->members.size();
+  const Slab& sl0 = c0->slab[0];
+  const int nx = c0->p.nx, band_rows = bt->psi_band_rows, bands = ceil_div(sl0.rows, band_rows);
+  const dim3 grid((unsigned)ceil_div(nx, lbm::kPsiColumns), (unsigned)bands, n_members);
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  hipLaunchKernelGGL(lbm::psi_band_totals_batch, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, band_rows,
+                     bt->psi_totals.get());
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  hipLaunchKernelGGL(lbm::psi_band_bases, dim3((unsigned)ceil_div(nx * lbm_exact::kExactLimbs, lbm::kBlock), 1, n_members), dim3(lbm::kBlock), 0, bt->stream, nx, bands,
+                     bt->psi_totals.get(), (const long long*)nullptr, (long long*)nullptr);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  hipLaunchKernelGGL(lbm::psi_scan_batch, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, band_rows,
+                     (const long long*)bt->psi_totals, bt->psi_cand.get());
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  hipLaunchKernelGGL(lbm::psi_extrema, dim3(n_members), dim3(64), 0, bt->stream, (const lbm::PsiCandidate*)bt->psi_cand, (int)(grid.x * grid.y), row);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+
+// ONE residual_gather_batch launch over all members' current (stored) lattices and planes, on the batch's stream:
+// the baseline (`planes` filled, `row` unused) or a sample against `planes` into `row`, [members][kResidualWords], which
+// the caller has zeroed in front
+int launch_batch_residual(lbm_batch* bt, float* planes, long long* row, bool baseline) {
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  const Slab& sl0 = c0->slab[0];
+  const int v = stats_vector(c0->p.nx);
+  const dim3 grid((unsigned)stats_groups((long)sl0.rows * c0->p.nx, v), 1, (unsigned)n_members);
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
+  if (v == 4)
+    hipLaunchKernelGGL(lbm::residual_gather_batch<4>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows,
+                       planes, row, (int)baseline);
+  else
+    hipLaunchKernelGGL(lbm::residual_gather_batch<1>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows,
+                       planes, row, (int)baseline);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+
+// the residuals: one sample launch against the members' remembered fields
+int take_batch_residual(lbm_batch* bt, long long* row) { return launch_batch_residual(bt, bt->residual_planes, row, false); }
+
+// the profiles: one launch per selected axis for all members
+int take_batch_profiles(lbm_batch* bt, long long* record) {
+  lbm_ctx* c0 = bt->members[0];
+  const Slab& sl0 = c0->slab[0];
+  const size_t n_members = bt->members.size();
+  const int nx = c0->p.nx, axes = bt->rec.args.axes;
+  const long member_words = (long)(gather_slot_words(bt) / n_members);
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  long long* lines = record;
+  if (axes & LBM_PROFILE_ROWS) {
+    const dim3 grid((unsigned)ceil_div(sl0.rows, lbm::kBlock / 64), 1, (unsigned)n_members);
+    if (stats_vector(nx) == 4)
+      hipLaunchKernelGGL(lbm::profile_rows_batch<4>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, lines, member_words);
+    else
+      hipLaunchKernelGGL(lbm::profile_rows_batch<1>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, lines, member_words);
+    lines += (size_t)sl0.rows * lbm_profile::kProfileWords;
+  }
+  if (axes & LBM_PROFILE_COLUMNS) {
+    const int band_rows = profile_band_rows(sl0.rows, nx);
+    const dim3 grid((unsigned)ceil_div(nx, lbm::kProfileColumns), (unsigned)ceil_div(sl0.rows, band_rows), (unsigned)n_members);
+    hipLaunchKernelGGL(lbm::profile_columns_batch, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, band_rows, lines,
+                       member_words);
+  }
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+
+// one launch for all members; a member is one slab, so every box row is whole and leaves as lines
+int take_batch_coarse(lbm_batch* bt, long long* frame) {
+  lbm_ctx* c0 = bt->members[0];
+  const Slab& sl0 = c0->slab[0];
+  const size_t n_members = bt->members.size();
+  const int bx = bt->rec.args.box_x;
+  const lbm_coarse::SlabBoxRows g = coarse_slab_boxes(c0, sl0, bx, bt->rec.args.box_y);
+  const int groups = coarse_groups(g);
+  const long member_words = (long)lbm_coarse::slot_words(g);
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  const dim3 grid((unsigned)g.count * (unsigned)groups, 1, (unsigned)n_members);
+  hipLaunchKernelGGL(coarse_wide(bx) ? lbm::coarse_gather_batch<true> : lbm::coarse_gather_batch<false>, grid, dim3(lbm::kBlock), 0, bt->stream,
+                     lattice_args(c0, sl0), tab, g, groups, frame, member_words);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+
+// ---- slot sizes ------------------------------------------------------------------------------------------------------
+template <int Words>
+size_t fixed_slot_words(const lbm_ctx*, const Slab&, const GatherArgs&) { return Words; }
+size_t forces_slot_words(const lbm_ctx*, const Slab&, const GatherArgs& a) { return (size_t)a.bodies * lbm::kForceWords; }
+// this slab's row lines, then its rows' share of every column line
+size_t profiles_slot_words(const lbm_ctx* c, const Slab& sl, const GatherArgs& a) {
+  return lbm_profile::profile_slab_lines(sl.rows, c->p.nx, a.axes) * lbm_profile::kProfileWords;
+}
+// the slab's whole box rows as lines, its partial ones as limb words
+size_t coarse_frames_slot_words(const lbm_ctx* c, const Slab& sl, const GatherArgs& a) { return coarse_slot_words(c, sl, a.box_x, a.box_y); }
+
+// ---- the kinds' own argument checks (no device needed) ---------------------------------------------------------------
+// the forces speak of their ring in bodies, so they refuse it themselves (the drivers' check then finds nothing)
+int check_forces(const char* who, const lbm_ctx* c, size_t members, int capacity, const GatherArgs& a) {
+  if (a.bodies < 1 || a.bodies > LBM_MAX_BODIES)
+    LBM_FAIL(LBM_FAILURE, "%s: %d bodies, between 1 and LBM_MAX_BODIES = %d are possible", who, a.bodies, LBM_MAX_BODIES);
+  const int body_bytes = lbm::kForceWords * (int)sizeof(long long);
+  const long long row_bytes = (long long)(members ? members : 1) * a.bodies * body_bytes;
+  if ((long long)capacity * row_bytes >= (1LL << 31)) {
+    if (!members)
+      LBM_FAIL(LBM_FAILURE, "%s: a ring of %d rows of %d bodies is 2 GiB or more (%d bytes per body and row)", who, capacity, a.bodies, body_bytes);
+    LBM_FAIL(LBM_FAILURE, "%s: a ring of %d rows of %d members of %d bodies is %.2f GiB, 2 GiB or more (%d bytes per body and row)", who,
+             capacity, (int)members, a.bodies, (double)capacity * (double)row_bytes / 1073741824.0, body_bytes);
+  }
+  if (members && (size_t)c->p.nx * c->p.ny > ((size_t)1 << 29))
+    LBM_FAIL(LBM_FAILURE, "%s: members of %d x %d cells; a link is cell * 8 + k - 1 in 32 bits (at most 2^29 cells)", who, c->p.nx, c->p.ny);
+  return LBM_SUCCESS;
+}
+int check_profiles(const char* who, const lbm_ctx*, size_t, int, const GatherArgs& a) {
+  if (a.axes < 1 || a.axes > (LBM_PROFILE_ROWS | LBM_PROFILE_COLUMNS))
+    LBM_FAIL(LBM_FAILURE, "%s: axes %d, LBM_PROFILE_ROWS (1), LBM_PROFILE_COLUMNS (2) or both (3) are possible", who, a.axes);
+  return LBM_SUCCESS;
+}
+// what every entry point refuses of a box
+int coarse_box_ok(const char* who, const lbm_ctx* c, int bx, int by) {
+  if (bx < 1 || by < 1) LBM_FAIL(LBM_FAILURE, "%s: box %d x %d, a box side is at least 1", who, bx, by);
+  if (bx > c->p.nx) LBM_FAIL(LBM_FAILURE, "%s: box side bx %d is larger than the grid's nx %d", who, bx, c->p.nx);
+  if (by > c->p.ny) LBM_FAIL(LBM_FAILURE, "%s: box side by %d is larger than the grid's ny %d", who, by, c->p.ny);
+  if (bx > LBM_COARSE_MAX_BOX) LBM_FAIL(LBM_FAILURE, "%s: box side bx %d is larger than LBM_COARSE_MAX_BOX (%d)", who, bx, LBM_COARSE_MAX_BOX);
+  if (by > LBM_COARSE_MAX_BOX) LBM_FAIL(LBM_FAILURE, "%s: box side by %d is larger than LBM_COARSE_MAX_BOX (%d)", who, by, LBM_COARSE_MAX_BOX);
+  return LBM_SUCCESS;
+}
+int check_coarse_frames(const char* who, const lbm_ctx* c, size_t, int, const GatherArgs& a) { return coarse_box_ok(who, c, a.box_x, a.box_y); }
+
+// ---- the kinds' buffers besides the ring -----------------------------------------------------------------------------
+// the forces' own: every slab's (or member's) labels as bytes on its device while the lists are built; none: every
+// blocked cell is body 0
+using ForceLabels = std::vector<DeviceBuf<unsigned char>>;
+
+// the links of one slab (or member) by body: its list on the device, the links of each body added to counts[bodies];
+// *most: the largest body so far
+int force_links_of(const char* who, lbm_ctx* c, Slab& sl, const unsigned char* labels, int n_bodies, DeviceBuf<unsigned>& links,
+                   DeviceBuf<unsigned>& starts_dev, int* counts, unsigned* most) {
+  std::vector<unsigned> starts;
+  if (build_link_list(who, c, sl, labels, n_bodies, links, starts_dev, starts) != LBM_SUCCESS) return LBM_FAILURE;
+  for (int b = 0; b < n_bodies; b++) {
+    const unsigned n = starts[(size_t)b + 1] - starts[(size_t)b];
+    counts[b] += (int)n;
+    if (n > *most) *most = n;
+  }
+  return LBM_SUCCESS;
+}
+int alloc_forces_slab(const char* who, lbm_ctx* c, int s, const GatherArgs& a, const void* own) {
+  const ForceLabels& labels = *static_cast<const ForceLabels*>(own);
+  Slab& sl = c->slab[s];
+  if (s == 0) c->force_link_counts.assign((size_t)a.bodies, 0);
+  unsigned most = 0;
+  if (force_links_of(who, c, sl, labels.empty() ? nullptr : labels[(size_t)s].get(), a.bodies, sl.force_links, sl.force_starts,
+                     c->force_link_counts.data(), &most) != LBM_SUCCESS)
+    return LBM_FAILURE;
+  sl.force_groups = gather_groups(most);
+  return LBM_SUCCESS;
+}
+int alloc_forces_batch(const char* who, lbm_batch* bt, const GatherArgs& a, const void* own) {
+  const ForceLabels& labels = *static_cast<const ForceLabels*>(own);
+  const size_t n_members = bt->members.size();
+  if (bt->force_lists.alloc(n_members) != hipSuccess) return kNoRoom;
+  bt->force_links.resize(n_members);
+  bt->force_starts.resize(n_members);
+  bt->force_link_counts.assign(n_members * (size_t)a.bodies, 0);
+  std::vector<lbm::ForceMember> lists(n_members);
+  unsigned most = 0;  // the x-extent suits the largest body of any member
+  for (size_t i = 0; i < n_members; i++) {
+    lbm_ctx* c = bt->members[i];
+    if (force_links_of(who, c, c->slab[0], labels.empty() ? nullptr : labels[i].get(), a.bodies, bt->force_links[i], bt->force_starts[i],
+                       &bt->force_link_counts[i * (size_t)a.bodies], &most) != LBM_SUCCESS)
+      return LBM_FAILURE;
+    lists[i] = {bt->force_links[i].get(), bt->force_starts[i].get()};
+  }
+  HIP_TRY(LBM_FAILURE, hipMemcpy(bt->force_lists, lists.data(), lists.size() * sizeof(lists[0]), hipMemcpyHostToDevice));
+  bt->force_groups = gather_groups(most);
+  return LBM_SUCCESS;
+}
+
+// the residuals: the remembered field, filled with the baseline, the field of the current lattice (the streams are idle:
+// the arming waited for them)
+int alloc_residual_slab(const char* who, lbm_ctx* c, int s, const GatherArgs&, const void*) {
+  Slab& sl = c->slab[s];
+  const size_t cells = (size_t)sl.rows * c->p.nx;
+  if (sl.residual_planes.alloc(2 * cells) != hipSuccess)
+    LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the remembered field of slab %d (%zu cells, %.1f MiB); residuals stay off", who, s, cells,
+             (double)(2 * cells * sizeof(float)) / 1048576.0);
+  launch_residual_gather(c, sl, sl.residual_planes, nullptr, true);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+int alloc_residual_batch(const char* who, lbm_batch* bt, const GatherArgs&, const void*) {
+  const lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size(), cells = (size_t)c0->slab[0].rows * c0->p.nx;
+  if (bt->residual_planes.alloc(n_members * 2 * cells) != hipSuccess)
+    LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the remembered fields of %d members (%zu cells each, %.1f MiB); residuals stay off", who,
+             (int)n_members, cells, (double)(n_members * 2 * cells * sizeof(float)) / 1048576.0);
+  return launch_batch_residual(bt, bt->residual_planes, nullptr, true);  // the baselines of all members: one launch
+}
+
+// the enstrophy on several slabs: where the neighbours' boundary rows are copied to
+int alloc_enstrophy_slab(const char*, lbm_ctx* c, int s, const GatherArgs&, const void*) {
+  return c->n_slabs > 1 && c->slab[s].vort_edges.alloc(2 * (size_t)c->row_pitch) != hipSuccess ? kNoRoom : LBM_SUCCESS;
+}
+
+// the stream function: the scan's scratch, and on several slabs what travels from slab to slab
+int alloc_psi_slab(const char*, lbm_ctx* c, int s, const GatherArgs&, const void*) {
+  Slab& sl = c->slab[s];
+  const int nx = c->p.nx;
+  const size_t base_words = (size_t)nx * lbm_exact::kExactLimbs;
+  sl.psi_band_rows = psi_band_rows(c, sl.rows, nx);
+  bool ok = sl.psi_totals.alloc(psi_total_words(sl.rows, nx, sl.psi_band_rows)) == hipSuccess &&
+            sl.psi_cand.alloc(psi_candidates(sl.rows, nx, sl.psi_band_rows)) == hipSuccess;
+  if (ok && c->n_slabs > 1) {
+    ok = sl.psi_in.alloc(base_words) == hipSuccess && sl.psi_out.alloc(base_words) == hipSuccess;
+    if (ok && !sl.ev_psi_out) ok = sl.ev_psi_out.create(hipEventDisableTiming) == hipSuccess;
+    if (ok && !sl.ev_psi_taken) ok = sl.ev_psi_taken.create(hipEventDisableTiming) == hipSuccess;
+  }
+  return ok ? LBM_SUCCESS : kNoRoom;
+}
+int alloc_psi_batch(const char*, lbm_batch* bt, const GatherArgs&, const void*) {
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  const int rows = c0->slab[0].rows, nx = c0->p.nx;
+  bt->psi_band_rows = psi_band_rows(c0, rows, nx);
+  return bt->psi_totals.alloc(n_members * psi_total_words(rows, nx, bt->psi_band_rows)) == hipSuccess &&
+                 bt->psi_cand.alloc(n_members * psi_candidates(rows, nx, bt->psi_band_rows)) == hipSuccess
+             ? LBM_SUCCESS
+             : kNoRoom;
+}
+
+// ---- one record of a context -------------------------------------------------------------------------------------------
+// the take of the kinds whose slabs record side by side: the kind's launch on every slab's compute stream, into the slab's
+// zeroed slot
+int take_per_slab(lbm_ctx* c) {
+  const GatherKind& k = gather_kind(c->rec.kind);
+  return for_slabs(c, [&](int s) -> int {
+    Slab& sl = c->slab[s];
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    long long* words = zeroed_slot(sl.gather_ring, gather_slot_words(c, sl), c->rec, sl.compute);
+    if (!words || k.launch(c, s, words) != LBM_SUCCESS) return LBM_FAILURE;
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+    return LBM_SUCCESS;
+  });
+}
+int launch_forces(lbm_ctx* c, int s, long long* words) {
+  const Slab& sl = c->slab[s];
+  if (sl.force_groups > 0)  // a slab without links records the zeros
+    hipLaunchKernelGGL(lbm::force_gather, dim3(sl.force_groups, (unsigned)c->rec.args.bodies), dim3(lbm::kBlock), 0, sl.compute,
+                       lattice_args(c, sl), (const unsigned*)sl.force_links, (const unsigned*)sl.force_starts, words);
+  return LBM_SUCCESS;
+}
+int launch_stats(lbm_ctx* c, int s, long long* words) {
+  launch_stats_gather(c, c->slab[s], words);
+  return LBM_SUCCESS;
+}
+int launch_residual(lbm_ctx* c, int s, long long* words) {
+  launch_residual_gather(c, c->slab[s], c->slab[s].residual_planes, words, false);  // also replaces the slab's remembered field by this lattice's
+  return LBM_SUCCESS;
+}
+int launch_profile_lines(lbm_ctx* c, int s, long long* words) {
+  launch_profiles(c, c->slab[s], words);  // (profile_rows leaves a line's spare word as zeroed)
+  return LBM_SUCCESS;
+}
+int launch_coarse_frame(lbm_ctx* c, int s, long long* words) {
+  launch_coarse(c, c->slab[s], c->rec.args.box_x, c->rec.args.box_y, words);
+  return LBM_SUCCESS;
+}
+// the enstrophy: on several slabs the sample reads the neighbours' boundary rows, so the slabs mark theirs as written in
+// front of the launches and await the neighbours' use of them behind
+int launch_enstrophy(lbm_ctx* c, int s, long long* words) {
+  Slab& sl = c->slab[s];
+  const bool edges = c->n_slabs > 1;
+  if (edges && copy_vorticity_edges(c, s, sl.vort_edges) != LBM_SUCCESS) return LBM_FAILURE;
+  launch_vorticity_gather(c, sl, edges ? sl.vort_edges.get() : nullptr, 0, sl.rows, nullptr, words);
+  if (edges) HIP_TRY(LBM_FAILURE, hipEventRecord(sl.ev_vort_done, sl.compute));
+  return LBM_SUCCESS;
+}
+int take_enstrophy(lbm_ctx* c) {
+  if (c->n_slabs == 1) return take_per_slab(c);
+  if (mark_vorticity_ready(c) != LBM_SUCCESS || take_per_slab(c) != LBM_SUCCESS) return LBM_FAILURE;
+  return await_vorticity_done(c);
+}
+// (the stream function's slabs depend on each other: take_psi_record issues them in their order)
+
+// ---- one record of a batch: the members' current (stored) lattices into `row`, the record's slot, which lbm_batch_run
+// has zeroed for all members at once, on the batch's stream (the current device's) ------------------------------------
+// the forces: one force_gather_batch for all members
+int take_batch_forces(lbm_batch* bt, long long* row) {
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  if (bt->force_groups > 0) {
+    hipLaunchKernelGGL(lbm::force_gather_batch, dim3((unsigned)bt->force_groups, (unsigned)bt->rec.args.bodies, (unsigned)n_members),
+                       dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, c0->slab[0]),
+                       (const lbm::ResidentMember*)(bt->table + (size_t)bt->cur * n_members), (const lbm::ForceMember*)bt->force_lists, row);
+    HIP_TRY(LBM_FAILURE, hipGetLastError());
+  }
+  return LBM_SUCCESS;
+}
+
+// ---- the fetched words of n records into the caller's rows -------------------------------------------------------------
+// the kinds whose row is `from` of a lattice's shares, merged and rounded
+template <class Row, Row (*from)(const long long*, int, int)>
+void rows_merged(const GatherOwner& g, const Recorder&, int n, const long long* words, void* out) {
+  for (size_t j = 0; j < (size_t)n * g.lattices; j++) static_cast<Row*>(out)[j] = from(words + j * g.lattice_words, g.shares, g.nx);
+}
+// the span of the row with ordinal `ord` since arming: from the baseline to the first sample, then `every`
+int residual_span(const Recorder& r, long long ord) {
+  return ord == 0 ? (int)((long long)r.ord0 * r.every + 1 - r.args.base_steps) : r.every;
+}
+void residual_rows(const GatherOwner& g, const Recorder& r, int n, const long long* words, void* out) {
+  for (size_t j = 0; j < (size_t)n * g.lattices; j++)
+    static_cast<lbm_residual_row*>(out)[j] = lbm_residual::residual_row_from_words(words + j * g.lattice_words, g.shares, g.nx,
+                                                                                   residual_span(r, r.read + (long long)(j / g.lattices)));
+}
+// every share's words of a lattice's row, added word by word -- integers: the order of the slabs does not matter -- then
+// each body's two sums rounded once and doubled (-2 c_k f)
+void forces_rows(const GatherOwner& g, const Recorder& r, int n, const long long* words, void* out) {
+  const size_t bodies = (size_t)r.args.bodies, share = g.lattice_words / (size_t)g.shares;
+  std::vector<long long> sum(share);
+  for (size_t j = 0; j < (size_t)n * g.lattices; j++) {
+    const long long* w = words + j * g.lattice_words;
+    sum.assign(w, w + share);
+    for (int s = 1; s < g.shares; s++)
+      for (size_t i = 0; i < share; i++) sum[i] += w[(size_t)s * share + i];
+    round_forces(sum.data(), bodies, static_cast<double*>(out) + j * 2 * bodies);
+  }
+}
+void profiles_rows(const GatherOwner& g, const Recorder& r, int n, const long long* words, void* out) {
+  const size_t lines = lbm_profile::profile_slab_lines(g.ny, g.nx, r.args.axes);
+  for (size_t j = 0; j < (size_t)n * g.lattices; j++)
+    lbm_profile::profile_lines_from_words(words + j * g.lattice_words, g.shares, g.row_first, g.row_count, g.nx, g.ny, r.args.axes,
+                                          static_cast<lbm_profile_line*>(out) + j * lines);
+}
+void coarse_frames_rows(const GatherOwner& g, const Recorder& r, int n, const long long* words, void* out) {
+  const int bx = r.args.box_x, by = r.args.box_y;
+  const size_t boxes = (size_t)lbm_coarse::coarse_boxes(g.nx, bx) * lbm_coarse::coarse_boxes(g.ny, by);
+  for (size_t j = 0; j < (size_t)n * g.lattices; j++)
+    lbm_coarse::coarse_frame_from_words(words + j * g.lattice_words, g.shares, g.row_first, g.row_count, g.nx, g.ny, bx, by,
+                                        static_cast<lbm_profile_line*>(out) + j * boxes);
+}
+
+// ---- the table ---------------------------------------------------------------------------------------------------------
+// To add a gather kind: its number in front of kRecKinds, its entry here, its hooks above, and its entry points, which pack
+// their arguments into GatherArgs and call arm_gather / drain_gather (arm_batch_gather / drain_batch_gather).
+const GatherKind kGatherKinds[kRecKinds - kRecGatherFirst] = {
+    {.ctx = {.name = "obstacle forces", .noun = "forces", .record = "row", .setter = "lbm_set_forces", .reader = "lbm_read_forces",
+             .disarm = "lbm_set_forces(ctx, 0, NULL, 0, 0)"},
+     .batch_setter = "lbm_batch_set_forces", .batch_reader = "lbm_batch_read_forces", .batch_disarm = "lbm_batch_set_forces(batch, 0, NULL, 0, 0)",
+     .stays_off = "forces stay off", .spread = "a body's links", .of_a_batch = "the forces of a batch are", .of = " of %d bodies",
+     .slot_words = forces_slot_words, .check = check_forces, .alloc_slab = alloc_forces_slab, .alloc_batch = alloc_forces_batch,
+     .take = take_per_slab, .launch = launch_forces, .take_batch = take_batch_forces, .rows = forces_rows},
+    {.ctx = {.name = "lattice statistics", .noun = "statistics", .record = "row", .setter = "lbm_set_stats", .reader = "lbm_read_stats",
+             .disarm = "lbm_set_stats(ctx, 0, 0)"},
+     .batch_setter = "lbm_batch_set_stats", .batch_reader = "lbm_batch_read_stats", .batch_disarm = "lbm_batch_set_stats(batch, 0, 0)",
+     .stays_off = "statistics stay off", .spread = "a row's sums", .of_a_batch = "the statistics of a batch are",
+     .slot_words = fixed_slot_words<lbm_stats::kStatsWords>,
+     .take = take_per_slab, .launch = launch_stats, .take_batch = take_batch_stats,
+     .rows = rows_merged<lbm_stats_row, lbm_stats::stats_row_from_words>},
+    {.ctx = {.name = "velocity residuals", .noun = "residuals", .record = "row", .setter = "lbm_set_residual", .reader = "lbm_read_residual",
+             .disarm = "lbm_set_residual(ctx, 0, 0)"},
+     .batch_setter = "lbm_batch_set_residual", .batch_reader = "lbm_batch_read_residual", .batch_disarm = "lbm_batch_set_residual(batch, 0, 0)",
+     .stays_off = "residuals stay off", .spread = "a row's sums", .of_a_batch = "the residuals of a batch are",
+     .slot_words = fixed_slot_words<lbm_residual::kResidualWords>, .alloc_slab = alloc_residual_slab, .alloc_batch = alloc_residual_batch,
+     .take = take_per_slab, .launch = launch_residual, .take_batch = take_batch_residual, .rows = residual_rows},
+    {.ctx = {.name = "line profiles", .noun = "profiles", .record = "record", .setter = "lbm_set_profiles", .reader = "lbm_read_profiles",
+             .disarm = "lbm_set_profiles(ctx, 0, 0, 0)"},
+     .batch_setter = "lbm_batch_set_profiles", .batch_reader = "lbm_batch_read_profiles", .batch_disarm = "lbm_batch_set_profiles(batch, 0, 0, 0)",
+     .stays_off = "profiles stay off", .spread = "a column's sums", .of_a_batch = "the profiles of a batch are", .per_slab = true,
+     .slot_words = profiles_slot_words, .check = check_profiles,
+     .take = take_per_slab, .launch = launch_profile_lines, .take_batch = take_batch_profiles, .rows = profiles_rows},
+    {.ctx = {.name = "enstrophy rows", .noun = "enstrophy", .record = "row", .setter = "lbm_set_enstrophy", .reader = "lbm_read_enstrophy",
+             .disarm = "lbm_set_enstrophy(ctx, 0, 0)"},
+     .batch_setter = "lbm_batch_set_enstrophy", .batch_reader = "lbm_batch_read_enstrophy", .batch_disarm = "lbm_batch_set_enstrophy(batch, 0, 0)",
+     .stays_off = "the enstrophy stays off", .spread = "a row's sums", .of_a_batch = "the enstrophy of a batch is",
+     .slot_words = fixed_slot_words<lbm_enstrophy::kEnstrophyWords>, .alloc_slab = alloc_enstrophy_slab,
+     .take = take_enstrophy, .launch = launch_enstrophy, .take_batch = take_batch_enstrophy,
+     .rows = rows_merged<lbm_enstrophy_row, lbm_enstrophy::enstrophy_row_from_words>},
+    {.ctx = {.name = "stream function rows", .noun = "the stream function", .record = "row", .setter = "lbm_set_psi",
+             .reader = "lbm_read_psi_rows", .disarm = "lbm_set_psi(ctx, 0, 0)"},
+     .batch_setter = "lbm_batch_set_psi", .batch_reader = "lbm_batch_read_psi_rows", .batch_disarm = "lbm_batch_set_psi(batch, 0, 0)",
+     .stays_off = "the stream function stays off", .spread = "a column's prefix", .of_a_batch = "the stream function of a batch is",
+     .also = " and the scan's buffers",
+     .slot_words = fixed_slot_words<lbm_psi::kPsiWords>, .alloc_slab = alloc_psi_slab, .alloc_batch = alloc_psi_batch,
+     .take = take_psi_record, .take_batch = take_batch_psi, .rows = rows_merged<lbm_psi_row, lbm_psi::psi_row_from_words>},
+    {.ctx = {.name = "coarse frames", .noun = "coarse frames", .record = "frame", .setter = "lbm_set_coarse_frames",
+             .reader = "lbm_read_coarse_frames", .disarm = "lbm_set_coarse_frames(ctx, 0, 0, 0, 0)"},
+     .batch_setter = "lbm_batch_set_coarse_frames", .batch_reader = "lbm_batch_read_coarse_frames",
+     .batch_disarm = "lbm_batch_set_coarse_frames(batch, 0, 0, 0, 0)",
+     .stays_off = "coarse frames stay off", .spread = "a box's cells", .of_a_batch = "the coarse frames of a batch are", .per_slab = true,
+     .slot_words = coarse_frames_slot_words, .check = check_coarse_frames,
+     .take = take_per_slab, .launch = launch_coarse_frame, .take_batch = take_batch_coarse, .rows = coarse_frames_rows}};
+const GatherKind& gather_kind(int kind) { return kGatherKinds[kind - kRecGatherFirst]; }
+const RecorderKind& kind_words(int kind) { return is_gather(kind) ? gather_kind(kind).ctx : kRecorderKinds[kind]; }
+
+// ---- arming a context --------------------------------------------------------------------------------------------------
+// " of 3 bodies" for the forces, nothing for every other kind
+struct OfWhat {
+  char text[32];
+  OfWhat(const GatherKind& k, const GatherArgs& a) { snprintf(text, sizeof(text), k.of, a.bodies); }
+};
+
+// What every lbm_set_<gather kind> refuses of its arguments and of the context, in this order, with nothing touched
+int gather_refusals(lbm_ctx* c, int kind, int every, int capacity, const GatherArgs& a) {
+  const GatherKind& k = gather_kind(kind);
+  const char* const who = k.ctx.setter;
+  if (!c) LBM_FAIL(LBM_FAILURE, "%s: null context", who);
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "%s: negative interval %d", who, every);
+  if (every == 0) return LBM_SUCCESS;
+  if (capacity < 1) LBM_FAIL(LBM_FAILURE, "%s: capacity %d, at least one %s is needed", who, capacity, k.ctx.record);
+  if (k.check && k.check(who, c, 0, capacity, a) != LBM_SUCCESS) return LBM_FAILURE;
+  for (int s = 0; s < c->n_slabs; s++) {
+    const long long slot_bytes = (long long)(k.slot_words(c, c->slab[s], a) * sizeof(long long));
+    if ((long long)capacity * slot_bytes >= (1LL << 31))
+      LBM_FAIL(LBM_FAILURE, "%s: a ring of %d %ss is 2 GiB or more (%lld bytes per %s%s)", who, capacity, k.ctx.record, slot_bytes, k.ctx.record,
+               k.per_slab ? " and slab" : "");
+  }
+  if (c->ranked || c->world > 1)
+    LBM_FAIL(LBM_FAILURE, "%s: not available in a multi-process (rank) context: %s would be spread over the ranks", who, k.spread);
+  if (c->batch)
+    LBM_FAIL(LBM_FAILURE, "%s: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
+             "end at, so %s armed on the batch, with one `every` for all members (%s)", who, k.of_a_batch, k.batch_setter);
+  return LBM_SUCCESS;
+}
+// ... and what it does once nothing is refused: rearm_recorder with every slab's ring and the kind's buffers behind it
+int arm_gather_checked(lbm_ctx* c, int kind, int every, int capacity, GatherArgs a, const void* own = nullptr) {
+  const GatherKind& k = gather_kind(kind);
+  const char* const who = k.ctx.setter;
+  const int status = rearm_recorder(c, kind, every, capacity, [&]() -> int {
+    for (int s = 0; s < c->n_slabs; s++) {
+      Slab& sl = c->slab[s];
+      const size_t ring_bytes = (size_t)capacity * k.slot_words(c, sl, a) * sizeof(long long);
+      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+      int rc = sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess ? kNoRoom : k.alloc_slab ? k.alloc_slab(who, c, s, a, own) : LBM_SUCCESS;
+      if (rc == kNoRoom) {
+        char where[32] = "per slab";
+        if (k.per_slab) snprintf(where, sizeof(where), "for slab %d", s);
+        LBM_FAIL(LBM_FAILURE, "%s: cannot allocate %d %ss%s (%.1f MiB %s)%s; %s", who, capacity, k.ctx.record, OfWhat(k, a).text,
+                 (double)ring_bytes / 1048576.0, where, k.also, k.stays_off);
+      }
+      if (rc != LBM_SUCCESS) return LBM_FAILURE;
+    }
+    return LBM_SUCCESS;
+  });
+  if (status == LBM_SUCCESS && every > 0) {
+    a.base_steps = c->steps_done;
+    c->rec.args = a;
+  }
+  return status;
+}
+int arm_gather(lbm_ctx* c, int kind, int every, int capacity, const GatherArgs& a) {
+  return gather_refusals(c, kind, every, capacity, a) != LBM_SUCCESS ? LBM_FAILURE : arm_gather_checked(c, kind, every, capacity, a);
+}
+
+// What the readers of the gather kinds share behind drain_recorder: the slabs' shares of the records, then the kind's rows
+int drain_gather(lbm_ctx* c, int kind, int max_records, void* out, int* steps, int* n_read) {
+  return drain_recorder(c, kind, max_records, out != nullptr, steps, n_read, [&](int n) -> int {
+    std::vector<long long> records;  // [record][slab's share]
+    GatherOwner g = context_owner(c);
+    if (fetch_gather_records(c, n, records, &g.lattice_words) != LBM_SUCCESS) return LBM_FAILURE;
+    gather_kind(kind).rows(g, c->rec, n, records.data(), out);
+    return LBM_SUCCESS;
+  });
+}
+
+// ---- arming a batch ----------------------------------------------------------------------------------------------------
+// What every lbm_batch_set_<gather kind> refuses, in this order, with nothing touched (gather_refusals does so for a
+// context).  Disarming while the batch's one recorder holds another kind is let through: arm_batch_gather_checked does
+// nothing then.
+int batch_gather_refusals(lbm_batch* bt, int kind, int every, int capacity, const GatherArgs& a) {
+  const GatherKind& k = gather_kind(kind);
+  const char* const who = k.batch_setter;
+  if (!bt) LBM_FAIL(LBM_FAILURE, "%s: null batch", who);
+  if (every < 0) LBM_FAIL(LBM_FAILURE, "%s: negative interval %d", who, every);
+  if (every == 0) return LBM_SUCCESS;
+  if (bt->rec.kind != kRecNone && bt->rec.kind != kind) {
+    const GatherKind& o = gather_kind(bt->rec.kind);
+    LBM_FAIL(LBM_FAILURE, "%s: this batch has %s armed (%s); a batch records one kind -- disarm them with %s first", who, o.ctx.name,
+             o.batch_setter, o.batch_disarm);
+  }
+  const lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  if (capacity < 1) LBM_FAIL(LBM_FAILURE, "%s: capacity %d, at least one %s is needed", who, capacity, k.ctx.record);
+  if (k.check && k.check(who, c0, n_members, capacity, a) != LBM_SUCCESS) return LBM_FAILURE;
+  const size_t member_bytes = k.slot_words(c0, c0->slab[0], a) * sizeof(long long), record_bytes = n_members * member_bytes;
+  if ((long long)capacity * (long long)record_bytes >= (1LL << 31))
+    LBM_FAIL(LBM_FAILURE, "%s: a ring of %d %ss of %d members is %.2f GiB, 2 GiB or more (%zu bytes per member and %s)", who, capacity,
+             k.ctx.record, (int)n_members, (double)capacity * (double)record_bytes / 1073741824.0, member_bytes, k.ctx.record);
+  return batch_members_free(bt, who);
+}
+// ... and what it does once nothing is refused (arm_gather_checked does so for a context): the launches in flight are
+// awaited and a recorder of this kind is released; to arm, the ring of all members and the kind's buffers behind it are
+// allocated before the recorder's fields are set
+int arm_batch_gather_checked(lbm_batch* bt, int kind, int every, int capacity, GatherArgs a, const void* own = nullptr) {
+  const GatherKind& k = gather_kind(kind);
+  const char* const who = k.batch_setter;
+  if (bt->rec.kind != kRecNone && bt->rec.kind != kind) return LBM_SUCCESS;  // (a disarming: a silent no-op)
+  // the buffers may still be written by launches in flight
+  HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
+  HIP_TRY(LBM_FAILURE, hipStreamSynchronize(bt->stream));
+  release_batch_recorder(bt);
+  if (every == 0) return LBM_SUCCESS;
+  const auto allocate = [&]() -> int {
+    const lbm_ctx* c0 = bt->members[0];
+    const size_t n_members = bt->members.size();
+    const size_t ring_bytes = (size_t)capacity * n_members * k.slot_words(c0, c0->slab[0], a) * sizeof(long long);
+    const int rc = bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess ? kNoRoom : k.alloc_batch ? k.alloc_batch(who, bt, a, own) : LBM_SUCCESS;
+    if (rc == kNoRoom)
+      LBM_FAIL(LBM_FAILURE, "%s: cannot allocate %d %ss of %d members%s (%.1f MiB)%s; %s", who, capacity, k.ctx.record, (int)n_members,
+               OfWhat(k, a).text, (double)ring_bytes / 1048576.0, k.also, k.stays_off);
+    return rc;
+  };
+  if (ensure_member_table(bt, who, k.ctx.noun) != LBM_SUCCESS || allocate() != LBM_SUCCESS) {
+    (void)hipGetLastError();  // a failed allocation must not surface at the next launch
+    release_batch_recorder(bt);
+    return LBM_FAILURE;
+  }
+  bt->rec.kind = kind;
+  bt->rec.every = every;
+  bt->rec.slots = capacity;
+  bt->rec.ord0 = (int)(((long long)bt->steps_done + every - 1) / every);
+  a.base_steps = bt->steps_done;
+  bt->rec.args = a;
+  bt->armed[kind] = 1;
+  return LBM_SUCCESS;
+}
+int arm_batch_gather(lbm_batch* bt, int kind, int every, int capacity, const GatherArgs& a) {
+  return batch_gather_refusals(bt, kind, every, capacity, a) != LBM_SUCCESS ? LBM_FAILURE : arm_batch_gather_checked(bt, kind, every, capacity, a);
+}
+
+// What the lbm_batch_read_* share (drain_gather does so for a context): the words of the n oldest records,
+// [record][member][a member's words], then the kind's rows
+int drain_batch_gather(lbm_batch* bt, int kind, int max_records, void* out, int* steps, int* n_read) {
+  const char* const reader = gather_kind(kind).batch_reader;
+  if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", reader);
+  *n_read = 0;
+  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
+  return drain_ring(bt->rec, kind, reader, max_records, out != nullptr, steps, n_read, [&](int n) -> int {
+    const size_t words = gather_slot_words(bt);
+    std::vector<long long> stage((size_t)n * words);
+    HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
+    if (fetch_ring(bt->gather_ring.get(), words, bt->rec, n, bt->stream, stage.data()) != LBM_SUCCESS) return LBM_FAILURE;
+    GatherOwner g = members_owner(bt);
+    g.lattice_words = words / g.lattices;
+    gather_kind(kind).rows(g, bt->rec, n, stage.data(), out);
+    return LBM_SUCCESS;
+  });
 }
 
 }  // namespace
@@ -3256,7 +3769,7 @@ int lbm_set_halo_mode(lbm_ctx* c, int mode) {
   if (mode != LBM_HALO_SYNC && mode != LBM_HALO_STALE && mode != LBM_HALO_FRESHEST) LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: unknown mode %d", mode);
   if (mode == LBM_HALO_FRESHEST && c->halo == HALO_HOST) LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: the freshest-available mode is not available with the hosted exchange");
   if (mode != LBM_HALO_SYNC && c->rec.kind != kRecNone) {
-    const RecorderKind& k = kRecorderKinds[c->rec.kind];
+    const RecorderKind& k = kind_words(c->rec.kind);
     LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: %s are armed (%s); the stale and freshest halo modes cannot record them -- "
              "disarm with %s first", k.name, k.setter, k.disarm);
   }
@@ -3487,22 +4000,11 @@ int lbm_read_field_frames(lbm_ctx* c, int max_frames, float* out, int* steps, in
 }
 
 int lbm_set_forces(lbm_ctx* c, int n_bodies, const int* body_of_cell, int every, int capacity) {
-  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_forces: null context");
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_forces: negative interval %d", every);
-  // the labels of every slab's owned cells as bytes (255: outside 0 .. n_bodies - 1), on its device while the lists are built
-  std::vector<DeviceBuf<unsigned char>> labels((size_t)(every > 0 && body_of_cell ? c->n_slabs : 0));
+  GatherArgs a;
+  a.bodies = n_bodies;
+  if (gather_refusals(c, kRecForces, every, capacity, a) != LBM_SUCCESS) return LBM_FAILURE;
+  ForceLabels labels((size_t)(every > 0 && body_of_cell ? c->n_slabs : 0));
   if (every > 0) {
-    if (n_bodies < 1 || n_bodies > LBM_MAX_BODIES)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_forces: %d bodies, between 1 and LBM_MAX_BODIES = %d are possible", n_bodies, LBM_MAX_BODIES);
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_forces: capacity %d, at least one row is needed", capacity);
-    if ((long long)capacity * (long long)(gather_words(kRecForces, (size_t)n_bodies) * sizeof(long long)) >= (1LL << 31))
-      LBM_FAIL(LBM_FAILURE, "lbm_set_forces: a ring of %d rows of %d bodies is 2 GiB or more (%d bytes per body and row)", capacity, n_bodies,
-               lbm::kForceWords * (int)sizeof(long long));
-    if (c->ranked || c->world > 1)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_forces: not available in a multi-process (rank) context: a body's links would be spread over the ranks");
-    if (c->batch)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_forces: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
-               "end at, so the forces of a batch are armed on the batch, with one `every` for all members (lbm_batch_set_forces)");
     for (int s = 0; s < c->n_slabs; s++)
       if ((long)c->slab[s].rows * c->p.nx > (1L << 29))
         LBM_FAIL(LBM_FAILURE, "lbm_set_forces: a slab of %d x %d cells; a link is cell * 8 + k - 1 in 32 bits (at most 2^29 cells per slab)",
@@ -3517,46 +4019,11 @@ int lbm_set_forces(lbm_ctx* c, int n_bodies, const int* body_of_cell, int every,
                  sl.row_first + (int)(first_bad / (unsigned)c->p.nx), src[first_bad], n_bodies - 1);
     }
   }
-  return rearm_recorder(c, kRecForces, every, capacity, [&]() -> int {
-    c->force_link_counts.assign((size_t)n_bodies, 0);
-    const size_t ring_bytes = (size_t)capacity * gather_words(kRecForces, (size_t)n_bodies) * sizeof(long long);
-    for (int s = 0; s < c->n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      if (sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_set_forces: cannot allocate %d rows of %d bodies (%.1f MiB per slab); forces stay off", capacity, n_bodies,
-                 (double)ring_bytes / 1048576.0);
-      std::vector<unsigned> starts;
-      if (build_link_list("lbm_set_forces", c, sl, labels.empty() ? nullptr : labels[s].get(), n_bodies, sl.force_links, sl.force_starts,
-                          starts) != LBM_SUCCESS)
-        return LBM_FAILURE;
-      unsigned most = 0;
-      for (int b = 0; b < n_bodies; b++) {
-        const unsigned links = starts[(size_t)b + 1] - starts[(size_t)b];
-        c->force_link_counts[(size_t)b] += (int)links;
-        if (links > most) most = links;
-      }
-      sl.force_groups = gather_groups(most);
-    }
-    return LBM_SUCCESS;
-  });
+  return arm_gather_checked(c, kRecForces, every, capacity, a, &labels);
 }
 
 int lbm_read_forces(lbm_ctx* c, int max_rows, double* out, int* steps, int* n_read) {
-  return drain_recorder(c, kRecForces, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
-    const size_t bodies = c->force_link_counts.size(), words = gather_slot_words(c, c->slab[0]);
-    // every slab's words of the n rows, added word by word -- integers: the order of the slabs does not matter -- then
-    // each body's two sums rounded once and doubled (-2 c_k f)
-    std::vector<long long> sum((size_t)n * words, 0), stage((size_t)n * words);
-    for (int s = 0; s < c->n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      if (fetch_ring(sl.gather_ring.get(), words, c->rec, n, sl.compute, stage.data()) != LBM_SUCCESS) return LBM_FAILURE;
-      for (size_t j = 0; j < sum.size(); j++) sum[j] += stage[j];
-    }
-    round_forces(sum.data(), (size_t)n * bodies, out);
-    return LBM_SUCCESS;
-  });
+  return drain_gather(c, kRecForces, max_rows, out, steps, n_read);
 }
 
 int lbm_forces_links(lbm_ctx* c, int* links_per_body) {
@@ -3566,81 +4033,17 @@ int lbm_forces_links(lbm_ctx* c, int* links_per_body) {
   return LBM_SUCCESS;
 }
 
-int lbm_set_stats(lbm_ctx* c, int every, int capacity) {
-  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_stats: null context");
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_stats: negative interval %d", every);
-  const long long kRowBytes = (long long)(gather_words(kRecStats) * sizeof(long long));
-  if (every > 0) {
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_stats: capacity %d, at least one row is needed", capacity);
-    if ((long long)capacity * kRowBytes >= (1LL << 31))
-      LBM_FAIL(LBM_FAILURE, "lbm_set_stats: a ring of %d rows is 2 GiB or more (%d bytes per row)", capacity, (int)kRowBytes);
-    if (c->ranked || c->world > 1)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_stats: not available in a multi-process (rank) context: a row's sums would be spread over the ranks");
-    if (c->batch)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_stats: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
-               "end at, so the statistics of a batch are armed on the batch, with one `every` for all members (lbm_batch_set_stats)");
-  }
-  return rearm_recorder(c, kRecStats, every, capacity, [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * (size_t)kRowBytes;
-    for (int s = 0; s < c->n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      if (sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_set_stats: cannot allocate %d rows (%.1f MiB per slab); statistics stay off", capacity,
-                 (double)ring_bytes / 1048576.0);
-    }
-    return LBM_SUCCESS;
-  });
-}
+int lbm_set_stats(lbm_ctx* c, int every, int capacity) { return arm_gather(c, kRecStats, every, capacity, GatherArgs{}); }
 
 int lbm_read_stats(lbm_ctx* c, int max_rows, lbm_stats_row* out, int* steps, int* n_read) {
-  return drain_recorder(c, kRecStats, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
-    // rows[row][slab][words]: the slabs of a row are merged and rounded by stats_row_from_words
-    std::vector<long long> rows;
-    size_t row_words;
-    if (fetch_gather_records(c, n, rows, &row_words) != LBM_SUCCESS) return LBM_FAILURE;
-    for (int i = 0; i < n; i++) out[i] = lbm_stats::stats_row_from_words(rows.data() + (size_t)i * row_words, c->n_slabs, c->p.nx);
-    return LBM_SUCCESS;
-  });
+  return drain_gather(c, kRecStats, max_rows, out, steps, n_read);
 }
 
 // ---- vorticity and enstrophy -------------------------------------------------------------------------------------------
-int lbm_set_enstrophy(lbm_ctx* c, int every, int capacity) {
-  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: null context");
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: negative interval %d", every);
-  const long long kRowBytes = (long long)(gather_words(kRecEnstrophy) * sizeof(long long));
-  if (every > 0) {
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: capacity %d, at least one row is needed", capacity);
-    if ((long long)capacity * kRowBytes >= (1LL << 31))
-      LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: a ring of %d rows is 2 GiB or more (%d bytes per row)", capacity, (int)kRowBytes);
-    if (c->ranked || c->world > 1)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: not available in a multi-process (rank) context: a row's sums would be spread over the ranks");
-    if (c->batch)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
-               "end at, so the enstrophy of a batch is armed on the batch, with one `every` for all members (lbm_batch_set_enstrophy)");
-  }
-  return rearm_recorder(c, kRecEnstrophy, every, capacity, [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * (size_t)kRowBytes;
-    for (int s = 0; s < c->n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      if (sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess || (c->n_slabs > 1 && sl.vort_edges.alloc(2 * (size_t)c->row_pitch) != hipSuccess))
-        LBM_FAIL(LBM_FAILURE, "lbm_set_enstrophy: cannot allocate %d rows (%.1f MiB per slab); the enstrophy stays off", capacity,
-                 (double)ring_bytes / 1048576.0);
-    }
-    return LBM_SUCCESS;
-  });
-}
+int lbm_set_enstrophy(lbm_ctx* c, int every, int capacity) { return arm_gather(c, kRecEnstrophy, every, capacity, GatherArgs{}); }
 
 int lbm_read_enstrophy(lbm_ctx* c, int max_rows, lbm_enstrophy_row* out, int* steps, int* n_read) {
-  return drain_recorder(c, kRecEnstrophy, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
-    // rows[row][slab][words]: the slabs of a row are merged and rounded by enstrophy_row_from_words
-    std::vector<long long> rows;
-    size_t row_words;
-    if (fetch_gather_records(c, n, rows, &row_words) != LBM_SUCCESS) return LBM_FAILURE;
-    for (int i = 0; i < n; i++) out[i] = lbm_enstrophy::enstrophy_row_from_words(rows.data() + (size_t)i * row_words, c->n_slabs, c->p.nx);
-    return LBM_SUCCESS;
-  });
+  return drain_gather(c, kRecEnstrophy, max_rows, out, steps, n_read);
 }
 
 int lbm_read_vorticity(lbm_ctx* c, float* w) {
@@ -3678,53 +4081,10 @@ int lbm_read_vorticity(lbm_ctx* c, float* w) {
 }
 
 // ---- stream function ---------------------------------------------------------------------------------------------------
-int lbm_set_psi(lbm_ctx* c, int every, int capacity) {
-  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_psi: null context");
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_psi: negative interval %d", every);
-  const long long kRowBytes = (long long)(gather_words(kRecPsi) * sizeof(long long));
-  if (every > 0) {
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_psi: capacity %d, at least one row is needed", capacity);
-    if ((long long)capacity * kRowBytes >= (1LL << 31))
-      LBM_FAIL(LBM_FAILURE, "lbm_set_psi: a ring of %d rows is 2 GiB or more (%d bytes per row)", capacity, (int)kRowBytes);
-    if (c->ranked || c->world > 1)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_psi: not available in a multi-process (rank) context: a column's prefix would be spread over the ranks");
-    if (c->batch)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_psi: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
-               "end at, so the stream function of a batch is armed on the batch, with one `every` for all members (lbm_batch_set_psi)");
-  }
-  return rearm_recorder(c, kRecPsi, every, capacity, [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * (size_t)kRowBytes;
-    const int nx = c->p.nx;
-    for (int s = 0; s < c->n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      sl.psi_band_rows = psi_band_rows(c, sl.rows, nx);
-      const size_t base_words = (size_t)nx * lbm_exact::kExactLimbs;
-      bool ok = sl.gather_ring.alloc_bytes(ring_bytes) == hipSuccess &&
-                sl.psi_totals.alloc(psi_total_words(sl.rows, nx, sl.psi_band_rows)) == hipSuccess &&
-                sl.psi_cand.alloc(psi_candidates(sl.rows, nx, sl.psi_band_rows)) == hipSuccess;
-      if (ok && c->n_slabs > 1) {
-        ok = sl.psi_in.alloc(base_words) == hipSuccess && sl.psi_out.alloc(base_words) == hipSuccess;
-        if (ok && !sl.ev_psi_out) ok = sl.ev_psi_out.create(hipEventDisableTiming) == hipSuccess;
-        if (ok && !sl.ev_psi_taken) ok = sl.ev_psi_taken.create(hipEventDisableTiming) == hipSuccess;
-      }
-      if (!ok)
-        LBM_FAIL(LBM_FAILURE, "lbm_set_psi: cannot allocate %d rows (%.1f MiB per slab) and the scan's buffers; the stream function stays off",
-                 capacity, (double)ring_bytes / 1048576.0);
-    }
-    return LBM_SUCCESS;
-  });
-}
+int lbm_set_psi(lbm_ctx* c, int every, int capacity) { return arm_gather(c, kRecPsi, every, capacity, GatherArgs{}); }
 
 int lbm_read_psi_rows(lbm_ctx* c, int max_rows, lbm_psi_row* out, int* steps, int* n_read) {
-  return drain_recorder(c, kRecPsi, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
-    // rows[row][slab][words]: the slabs' candidates of a row are merged by psi_row_from_words
-    std::vector<long long> rows;
-    size_t row_words;
-    if (fetch_gather_records(c, n, rows, &row_words) != LBM_SUCCESS) return LBM_FAILURE;
-    for (int i = 0; i < n; i++) out[i] = lbm_psi::psi_row_from_words(rows.data() + (size_t)i * row_words, c->n_slabs, c->p.nx);
-    return LBM_SUCCESS;
-  });
+  return drain_gather(c, kRecPsi, max_rows, out, steps, n_read);
 }
 
 int lbm_read_psi(lbm_ctx* c, double* psi) {
@@ -3774,138 +4134,23 @@ int lbm_read_psi(lbm_ctx* c, double* psi) {
   return LBM_SUCCESS;
 }
 
-// the span of the row with ordinal `ord` since arming: from the baseline to the first sample, then `every`
-static int residual_span(const Recorder& r, long long ord) {
-  return ord == 0 ? (int)((long long)r.ord0 * r.every + 1 - r.base_steps) : r.every;
-}
-
-int lbm_set_residual(lbm_ctx* c, int every, int capacity) {
-  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_residual: null context");
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_residual: negative interval %d", every);
-  const long long kRowBytes = (long long)(gather_words(kRecResidual) * sizeof(long long));
-  if (every > 0) {
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_residual: capacity %d, at least one row is needed", capacity);
-    if ((long long)capacity * kRowBytes >= (1LL << 31))
-      LBM_FAIL(LBM_FAILURE, "lbm_set_residual: a ring of %d rows is 2 GiB or more (%d bytes per row)", capacity, (int)kRowBytes);
-    if (c->ranked || c->world > 1)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_residual: not available in a multi-process (rank) context: a row's sums would be spread over the ranks");
-    if (c->batch)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_residual: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
-               "end at, so the residuals of a batch are armed on the batch, with one `every` for all members (lbm_batch_set_residual)");
-  }
-  const int status = rearm_recorder(c, kRecResidual, every, capacity, [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * (size_t)kRowBytes;
-    for (int s = 0; s < c->n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      const size_t cells = (size_t)sl.rows * c->p.nx;
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      if (sl.residual_planes.alloc(2 * cells) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_set_residual: cannot allocate the remembered field of slab %d (%zu cells, %.1f MiB); residuals stay off", s, cells,
-                 (double)(2 * cells * sizeof(float)) / 1048576.0);
-      if (sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_set_residual: cannot allocate %d rows (%.1f MiB per slab); residuals stay off", capacity,
-                 (double)ring_bytes / 1048576.0);
-    }
-    // the baseline: the field of the current lattice (the streams are idle: rearm_recorder waited for them)
-    for (int s = 0; s < c->n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      launch_residual_gather(c, sl, sl.residual_planes, nullptr, true);
-      HIP_TRY(LBM_FAILURE, hipGetLastError());
-    }
-    return LBM_SUCCESS;
-  });
-  if (status == LBM_SUCCESS && every > 0) c->rec.base_steps = c->steps_done;
-  return status;
-}
+int lbm_set_residual(lbm_ctx* c, int every, int capacity) { return arm_gather(c, kRecResidual, every, capacity, GatherArgs{}); }
 
 int lbm_read_residual(lbm_ctx* c, int max_rows, lbm_residual_row* out, int* steps, int* n_read) {
-  return drain_recorder(c, kRecResidual, max_rows, out != nullptr, steps, n_read, [&](int n) -> int {
-    // rows[row][slab][words]: the slabs of a row are merged and rounded by residual_row_from_words
-    std::vector<long long> rows;
-    size_t row_words;
-    if (fetch_gather_records(c, n, rows, &row_words) != LBM_SUCCESS) return LBM_FAILURE;
-    for (int i = 0; i < n; i++)
-      out[i] = lbm_residual::residual_row_from_words(rows.data() + (size_t)i * row_words, c->n_slabs, c->p.nx,
-                                                     residual_span(c->rec, c->rec.read + i));
-    return LBM_SUCCESS;
-  });
+  return drain_gather(c, kRecResidual, max_rows, out, steps, n_read);
 }
 
 int lbm_set_profiles(lbm_ctx* c, int every, int capacity, int axes) {
-  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: null context");
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: negative interval %d", every);
-  if (every > 0) {
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: capacity %d, at least one record is needed", capacity);
-    if (axes < 1 || axes > (LBM_PROFILE_ROWS | LBM_PROFILE_COLUMNS))
-      LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: axes %d, LBM_PROFILE_ROWS (1), LBM_PROFILE_COLUMNS (2) or both (3) are possible", axes);
-    for (int s = 0; s < c->n_slabs; s++) {
-      const long long slot_bytes = (long long)(gather_words(kRecProfiles, 0, c->slab[s].rows, c->p.nx, axes) * sizeof(long long));
-      if ((long long)capacity * slot_bytes >= (1LL << 31))
-        LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: a ring of %d records is 2 GiB or more (%lld bytes per record and slab)", capacity, slot_bytes);
-    }
-    if (c->ranked || c->world > 1)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: not available in a multi-process (rank) context: a column's sums would be spread over the ranks");
-    if (c->batch)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
-               "end at, so the profiles of a batch are armed on the batch, with one `every` for all members (lbm_batch_set_profiles)");
-  }
-  const int status = rearm_recorder(c, kRecProfiles, every, capacity, [&]() -> int {
-    for (int s = 0; s < c->n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      const size_t ring_bytes = (size_t)capacity * gather_words(kRecProfiles, 0, sl.rows, c->p.nx, axes) * sizeof(long long);
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      if (sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_set_profiles: cannot allocate %d records (%.1f MiB for slab %d); profiles stay off", capacity,
-                 (double)ring_bytes / 1048576.0, s);
-    }
-    return LBM_SUCCESS;
-  });
-  if (status == LBM_SUCCESS && every > 0) c->rec.axes = axes;
-  return status;
+  GatherArgs a;
+  a.axes = axes;
+  return arm_gather(c, kRecProfiles, every, capacity, a);
 }
 
 int lbm_read_profiles(lbm_ctx* c, int max_records, lbm_profile_line* out, int* steps, int* n_read) {
-  return drain_recorder(c, kRecProfiles, max_records, out != nullptr, steps, n_read, [&](int n) -> int {
-    const int nx = c->p.nx, ny = c->p.ny, axes = c->rec.axes;
-    // records[record][slab's share]: the shares of a record become its lines by profile_lines_from_words
-    int row_first[kMaxSlabs], row_count[kMaxSlabs];
-    for (int s = 0; s < c->n_slabs; s++) {
-      row_first[s] = c->slab[s].row_first;
-      row_count[s] = c->slab[s].rows;
-    }
-    std::vector<long long> records;
-    size_t record_words;
-    if (fetch_gather_records(c, n, records, &record_words) != LBM_SUCCESS) return LBM_FAILURE;
-    const size_t lines = lbm_profile::profile_slab_lines(ny, nx, axes);
-    for (int i = 0; i < n; i++)
-      lbm_profile::profile_lines_from_words(records.data() + (size_t)i * record_words, c->n_slabs, row_first, row_count, nx, ny, axes,
-                                            out + (size_t)i * lines);
-    return LBM_SUCCESS;
-  });
+  return drain_gather(c, kRecProfiles, max_records, out, steps, n_read);
 }
 
 // ---- coarse frames -----------------------------------------------------------------------------------------------------
-// what every entry point refuses of a box (no device needed)
-static int coarse_box_ok(const char* who, const lbm_ctx* c, int bx, int by) {
-  if (bx < 1 || by < 1) LBM_FAIL(LBM_FAILURE, "%s: box %d x %d, a box side is at least 1", who, bx, by);
-  if (bx > c->p.nx) LBM_FAIL(LBM_FAILURE, "%s: box side bx %d is larger than the grid's nx %d", who, bx, c->p.nx);
-  if (by > c->p.ny) LBM_FAIL(LBM_FAILURE, "%s: box side by %d is larger than the grid's ny %d", who, by, c->p.ny);
-  if (bx > LBM_COARSE_MAX_BOX) LBM_FAIL(LBM_FAILURE, "%s: box side bx %d is larger than LBM_COARSE_MAX_BOX (%d)", who, bx, LBM_COARSE_MAX_BOX);
-  if (by > LBM_COARSE_MAX_BOX) LBM_FAIL(LBM_FAILURE, "%s: box side by %d is larger than LBM_COARSE_MAX_BOX (%d)", who, by, LBM_COARSE_MAX_BOX);
-  return LBM_SUCCESS;
-}
-
-// the slabs' slots of one record (one after the other) -> the frame
-static void coarse_frame(const lbm_ctx* c, const long long* record, int bx, int by, lbm_profile_line* out) {
-  int row_first[kMaxSlabs], row_count[kMaxSlabs];
-  for (int s = 0; s < c->n_slabs; s++) {
-    row_first[s] = c->slab[s].row_first;
-    row_count[s] = c->slab[s].rows;
-  }
-  lbm_coarse::coarse_frame_from_words(record, c->n_slabs, row_first, row_count, c->p.nx, c->p.ny, bx, by, out);
-}
-
 int lbm_read_coarse(lbm_ctx* c, int bx, int by, lbm_profile_line* out) {
   if (!c || !out) LBM_FAIL(LBM_FAILURE, "lbm_read_coarse: NULL argument");
   if (c->ranked || c->world > 1)
@@ -3929,55 +4174,20 @@ int lbm_read_coarse(lbm_ctx* c, int bx, int by, lbm_profile_line* out) {
     HIP_TRY(LBM_FAILURE, hipMemcpyAsync(record.data() + at, slot, words * sizeof(long long), hipMemcpyDeviceToHost, sl.compute));
     HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
   }
-  coarse_frame(c, record.data(), bx, by, out);
+  const GatherOwner g = context_owner(c);  // the slabs' slots of the one record (one after the other) -> the frame
+  lbm_coarse::coarse_frame_from_words(record.data(), g.shares, g.row_first, g.row_count, g.nx, g.ny, bx, by, out);
   return LBM_SUCCESS;
 }
 
 int lbm_set_coarse_frames(lbm_ctx* c, int every, int capacity, int bx, int by) {
-  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: null context");
-  if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: negative interval %d", every);
-  if (every > 0) {
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: capacity %d, at least one frame is needed", capacity);
-    if (coarse_box_ok("lbm_set_coarse_frames", c, bx, by) != LBM_SUCCESS) return LBM_FAILURE;
-    for (int s = 0; s < c->n_slabs; s++) {
-      const long long slot_bytes = (long long)(coarse_slot_words(c, c->slab[s], bx, by) * sizeof(long long));
-      if ((long long)capacity * slot_bytes >= (1LL << 31))
-        LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: a ring of %d frames is 2 GiB or more (%lld bytes per frame and slab)", capacity, slot_bytes);
-    }
-    if (c->ranked || c->world > 1)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: not available in a multi-process (rank) context: a box's cells would be spread over the ranks");
-    if (c->batch)
-      LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: not available on a member of a batch (lbm_create_batch): the batched launches need common sample steps to "
-               "end at, so the coarse frames of a batch are armed on the batch, with one `every` for all members (lbm_batch_set_coarse_frames)");
-  }
-  const int status = rearm_recorder(c, kRecCoarse, every, capacity, [&]() -> int {
-    for (int s = 0; s < c->n_slabs; s++) {
-      Slab& sl = c->slab[s];
-      const size_t ring_bytes = (size_t)capacity * coarse_slot_words(c, sl, bx, by) * sizeof(long long);
-      HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      if (sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
-        LBM_FAIL(LBM_FAILURE, "lbm_set_coarse_frames: cannot allocate %d frames (%.1f MiB for slab %d); coarse frames stay off", capacity,
-                 (double)ring_bytes / 1048576.0, s);
-    }
-    return LBM_SUCCESS;
-  });
-  if (status == LBM_SUCCESS && every > 0) {
-    c->rec.box_x = bx;
-    c->rec.box_y = by;
-  }
-  return status;
+  GatherArgs a;
+  a.box_x = bx;
+  a.box_y = by;
+  return arm_gather(c, kRecCoarse, every, capacity, a);
 }
 
 int lbm_read_coarse_frames(lbm_ctx* c, int max_frames, lbm_profile_line* out, int* steps, int* n_read) {
-  return drain_recorder(c, kRecCoarse, max_frames, out != nullptr, steps, n_read, [&](int n) -> int {
-    const int bx = c->rec.box_x, by = c->rec.box_y;
-    std::vector<long long> records;
-    size_t record_words;
-    if (fetch_gather_records(c, n, records, &record_words) != LBM_SUCCESS) return LBM_FAILURE;
-    const size_t boxes = (size_t)lbm_coarse::coarse_boxes(c->p.nx, bx) * lbm_coarse::coarse_boxes(c->p.ny, by);
-    for (int i = 0; i < n; i++) coarse_frame(c, records.data() + (size_t)i * record_words, bx, by, out + (size_t)i * boxes);
-    return LBM_SUCCESS;
-  });
+  return drain_gather(c, kRecCoarse, max_frames, out, steps, n_read);
 }
 
 // the planes [first, first + 4) of every slab's sums, stitched by row_first; lbm_read_mean and lbm_read_mean2
@@ -4349,98 +4559,6 @@ static int batch_advance(lbm_batch* bt, int n_steps) {
   return LBM_SUCCESS;
 }
 
-// The take() of each batch kind: the record of the members' current (stored) lattices into `row`, its slot, which
-// lbm_batch_run has zeroed for all members at once, on the batch's stream (the current device's).
-// the forces: one force_gather_batch for all members
-static int take_batch_forces(lbm_batch* bt, long long* row) {
-  lbm_ctx* c0 = bt->members[0];
-  const size_t n_members = bt->members.size();
-  if (bt->force_groups > 0) {
-    hipLaunchKernelGGL(lbm::force_gather_batch, dim3((unsigned)bt->force_groups, (unsigned)bt->force_bodies, (unsigned)n_members),
-                       dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, c0->slab[0]),
-                       (const lbm::ResidentMember*)(bt->table + (size_t)bt->cur * n_members), (const lbm::ForceMember*)bt->force_lists, row);
-    HIP_TRY(LBM_FAILURE, hipGetLastError());
-  }
-  return LBM_SUCCESS;
-}
-
-// the statistics: one stats_gather_batch for all members
-static int take_batch_stats(lbm_batch* bt, long long* row) {
-  lbm_ctx* c0 = bt->members[0];
-  const size_t n_members = bt->members.size();
-  const Slab& sl0 = c0->slab[0];
-  const int v = stats_vector(c0->p.nx);
-  const dim3 grid((unsigned)stats_groups((long)sl0.rows * c0->p.nx, v), 1, (unsigned)n_members);
-  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
-  if (v == 4)
-    hipLaunchKernelGGL(lbm::stats_gather_batch<4>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, row);
-  else
-    hipLaunchKernelGGL(lbm::stats_gather_batch<1>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, row);
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  return LBM_SUCCESS;
-}
-
-// the enstrophy: one vorticity_gather_batch for all members, each a periodic slab of its own
-static int take_batch_enstrophy(lbm_batch* bt, long long* row) {
-  lbm_ctx* c0 = bt->members[0];
-  const size_t n_members = bt->members.size();
-  const Slab& sl0 = c0->slab[0];
-  const int nx = c0->p.nx, band_rows = vorticity_band_rows(sl0.rows, nx);
-  const dim3 grid((unsigned)vorticity_groups(sl0.rows, nx, band_rows), 1, (unsigned)n_members);
-  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
-  hipLaunchKernelGGL(stats_vector(nx) == 4 ? lbm::vorticity_gather_batch<4> : lbm::vorticity_gather_batch<1>, grid, dim3(lbm::kBlock), 0,
-                     bt->stream, lattice_args(c0, sl0), tab, sl0.rows, band_rows, row);
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  return LBM_SUCCESS;
-}
-
-// the stream function: ONE launch of each of the scan's kernels for all members (grid z is the member; psi_extrema: grid x),
-// each member a grid of its own from row 0
-static int take_batch_psi(lbm_batch* bt, long long* row) {
-  lbm_ctx* c0 = bt->members[0];
-  const unsigned n_members = (unsigned)bt->members.size();
-  const Slab& sl0 = c0->slab[0];
-  const int nx = c0->p.nx, band_rows = bt->psi_band_rows, bands = ceil_div(sl0.rows, band_rows);
-  const dim3 grid((unsigned)ceil_div(nx, lbm::kPsiColumns), (unsigned)bands, n_members);
-  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
-  hipLaunchKernelGGL(lbm::psi_band_totals_batch, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, band_rows,
-                     bt->psi_totals.get());
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  hipLaunchKernelGGL(lbm::psi_band_bases, dim3((unsigned)ceil_div(nx * lbm_exact::kExactLimbs, lbm::kBlock), 1, n_members), dim3(lbm::kBlock), 0, bt->stream, nx, bands,
-                     bt->psi_totals.get(), (const long long*)nullptr, (long long*)nullptr);
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  hipLaunchKernelGGL(lbm::psi_scan_batch, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, band_rows,
-                     (const long long*)bt->psi_totals, bt->psi_cand.get());
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  hipLaunchKernelGGL(lbm::psi_extrema, dim3(n_members), dim3(64), 0, bt->stream, (const lbm::PsiCandidate*)bt->psi_cand, (int)(grid.x * grid.y), row);
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  return LBM_SUCCESS;
-}
-
-// ONE residual_gather_batch launch over all members' current (stored) lattices and planes, on the batch's stream:
-// the baseline (`planes` filled, `row` unused) or a sample against `planes` into `row`, [members][kResidualWords], which
-// the caller has zeroed in front
-static int launch_batch_residual(lbm_batch* bt, float* planes, long long* row, bool baseline) {
-  lbm_ctx* c0 = bt->members[0];
-  const size_t n_members = bt->members.size();
-  const Slab& sl0 = c0->slab[0];
-  const int v = stats_vector(c0->p.nx);
-  const dim3 grid((unsigned)stats_groups((long)sl0.rows * c0->p.nx, v), 1, (unsigned)n_members);
-  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
-  HIP_TRY(LBM_FAILURE, hipSetDevice(sl0.device));
-  if (v == 4)
-    hipLaunchKernelGGL(lbm::residual_gather_batch<4>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows,
-                       planes, row, (int)baseline);
-  else
-    hipLaunchKernelGGL(lbm::residual_gather_batch<1>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows,
-                       planes, row, (int)baseline);
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  return LBM_SUCCESS;
-}
-
-// the residuals: one sample launch against the members' remembered fields
-static int take_batch_residual(lbm_batch* bt, long long* row) { return launch_batch_residual(bt, bt->residual_planes, row, false); }
-
 int lbm_batch_run(lbm_batch* bt, int n_steps) {
   if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: null batch");
   if (n_steps < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: negative step count");
@@ -4455,8 +4573,8 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
   // a gather kind armed: the call runs as the sub-calls that end at the sample steps, each advanced as a call of its
   // length would be and followed by the record of all members into its zeroed slot (lbm_run does the same for one context,
   // run_steps and take_record)
-  const BatchKind* kind = batch_kind(bt->rec.kind);
-  if (recorder_fits(bt->rec, bt->steps_done, n_steps, "lbm_batch_run", kind->reader) != LBM_SUCCESS) return LBM_FAILURE;
+  const GatherKind& kind = gather_kind(bt->rec.kind);
+  if (recorder_fits(bt->rec, bt->steps_done, n_steps, "lbm_batch_run", kind.batch_reader) != LBM_SUCCESS) return LBM_FAILURE;
   const int e = bt->rec.every;
   for (int t = 0; t < n_steps;) {
     const int tt = bt->steps_done, r = tt % e;
@@ -4466,7 +4584,7 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
     if (bt->steps_done - 1 == rec_tt) {
       HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
       long long* slot = zeroed_slot(bt->gather_ring, gather_slot_words(bt), bt->rec, bt->stream);
-      if (!slot || kind->take(bt, slot) != LBM_SUCCESS) return LBM_FAILURE;
+      if (!slot || kind.take_batch(bt, slot) != LBM_SUCCESS) return LBM_FAILURE;
       bt->rec.written++;
     }
     t += seg;
@@ -4494,72 +4612,27 @@ int lbm_batch_get_info(const lbm_batch* bt, lbm_batch_info* out) {
   return LBM_SUCCESS;
 }
 
-// ---- obstacle forces of a batch ------------------------------------------------------------------------------------
+// ---- the gather kinds of a batch -------------------------------------------------------------------------------------
 int lbm_batch_set_forces(lbm_batch* bt, int n_bodies, const int* body_of_cell, int every, int capacity) {
-  // every member's labels as bytes (255: outside 0 .. n_bodies - 1), on the device while the lists are built
-  std::vector<DeviceBuf<unsigned char>> labels;
-  return rearm_batch_recorder(bt, kRecForces, every, capacity, [&]() -> int {
-    const lbm_ctx* c0 = bt->members[0];
-    const size_t n_members = bt->members.size(), cells = (size_t)c0->p.nx * c0->p.ny;
-    if (n_bodies < 1 || n_bodies > LBM_MAX_BODIES)
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: %d bodies, between 1 and LBM_MAX_BODIES = %d are possible", n_bodies, LBM_MAX_BODIES);
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: capacity %d, at least one row is needed", capacity);
-    const long long row_bytes = (long long)(n_members * gather_words(kRecForces, (size_t)n_bodies) * sizeof(long long));
-    if ((long long)capacity * row_bytes >= (1LL << 31))
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: a ring of %d rows of %d members of %d bodies is %.2f GiB, 2 GiB or more (%d bytes per body and row)",
-               capacity, (int)n_members, n_bodies, (double)capacity * (double)row_bytes / 1073741824.0, lbm::kForceWords * (int)sizeof(long long));
-    if (cells > ((size_t)1 << 29))
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: members of %d x %d cells; a link is cell * 8 + k - 1 in 32 bits (at most 2^29 cells)",
-               c0->p.nx, c0->p.ny);
-    // the labels go to the device only once no member is in the way: rearm_batch_recorder's next check, made here first
-    if (batch_members_free(bt, "lbm_batch_set_forces") != LBM_SUCCESS) return LBM_FAILURE;
-    labels.resize(body_of_cell ? n_members : 0);
-    for (size_t i = 0; i < labels.size(); i++) {
-      lbm_ctx* c = bt->members[i];
-      const int* src = body_of_cell + i * cells;
-      unsigned first_bad;
-      if (upload_labels(c, c->slab[0], src, n_bodies, labels[i], &first_bad) != LBM_SUCCESS) return LBM_FAILURE;
-      if (first_bad != kNoBadLabel)
-        LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: member %d: the blocked cell (%d, %d) has body %d, outside 0 .. %d", (int)i,
-                 (int)(first_bad % (unsigned)c->p.nx), (int)(first_bad / (unsigned)c->p.nx), src[first_bad], n_bodies - 1);
-    }
-    return LBM_SUCCESS;
-  }, [&]() -> int {
-    const size_t n_members = bt->members.size();
-    const size_t ring_bytes = (size_t)capacity * n_members * gather_words(kRecForces, (size_t)n_bodies) * sizeof(long long);
-    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess || bt->force_lists.alloc(n_members) != hipSuccess)
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: cannot allocate %d rows of %d members of %d bodies (%.1f MiB); forces stay off", capacity,
-               (int)n_members, n_bodies, (double)ring_bytes / 1048576.0);
-    bt->force_links.resize(n_members);
-    bt->force_starts.resize(n_members);
-    bt->force_link_counts.assign(n_members * (size_t)n_bodies, 0);
-    std::vector<lbm::ForceMember> lists(n_members);
-    unsigned most = 0;
-    for (size_t i = 0; i < n_members; i++) {
-      lbm_ctx* c = bt->members[i];
-      std::vector<unsigned> starts;
-      if (build_link_list("lbm_batch_set_forces", c, c->slab[0], labels.empty() ? nullptr : labels[i].get(), n_bodies, bt->force_links[i],
-                          bt->force_starts[i], starts) != LBM_SUCCESS)
-        return LBM_FAILURE;
-      for (int b = 0; b < n_bodies; b++) {
-        const unsigned links = starts[(size_t)b + 1] - starts[(size_t)b];
-        bt->force_link_counts[i * (size_t)n_bodies + (size_t)b] = (int)links;
-        if (links > most) most = links;
-      }
-      lists[i] = {bt->force_links[i].get(), bt->force_starts[i].get()};
-    }
-    HIP_TRY(LBM_FAILURE, hipMemcpy(bt->force_lists, lists.data(), lists.size() * sizeof(lists[0]), hipMemcpyHostToDevice));
-    bt->force_groups = gather_groups(most);  // the x-extent suits the largest body of any member
-    bt->force_bodies = n_bodies;
-    return LBM_SUCCESS;
-  });
+  GatherArgs a;
+  a.bodies = n_bodies;
+  if (batch_gather_refusals(bt, kRecForces, every, capacity, a) != LBM_SUCCESS) return LBM_FAILURE;
+  // the labels go to the device only once nothing is refused and no member is in the way
+  ForceLabels labels(every > 0 && body_of_cell ? bt->members.size() : 0);
+  for (size_t i = 0; i < labels.size(); i++) {
+    lbm_ctx* c = bt->members[i];
+    const int* src = body_of_cell + i * ((size_t)c->p.nx * c->p.ny);
+    unsigned first_bad;
+    if (upload_labels(c, c->slab[0], src, n_bodies, labels[i], &first_bad) != LBM_SUCCESS) return LBM_FAILURE;
+    if (first_bad != kNoBadLabel)
+      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_forces: member %d: the blocked cell (%d, %d) has body %d, outside 0 .. %d", (int)i,
+               (int)(first_bad % (unsigned)c->p.nx), (int)(first_bad / (unsigned)c->p.nx), src[first_bad], n_bodies - 1);
+  }
+  return arm_batch_gather_checked(bt, kRecForces, every, capacity, a, &labels);
 }
 
 int lbm_batch_read_forces(lbm_batch* bt, int max_rows, double* out, int* steps, int* n_read) {
-  return drain_batch_recorder(bt, kRecForces, max_rows, out != nullptr, steps, n_read, [&](int n, const long long* words) {
-    // each body's two sums are rounded once and doubled
-    round_forces(words, (size_t)n * bt->members.size() * (size_t)bt->force_bodies, out);
-  });
+  return drain_batch_gather(bt, kRecForces, max_rows, out, steps, n_read);
 }
 
 int lbm_batch_forces_links(lbm_batch* bt, int* links) {
@@ -4570,250 +4643,49 @@ int lbm_batch_forces_links(lbm_batch* bt, int* links) {
   return LBM_SUCCESS;
 }
 
-// ---- lattice statistics of a batch ---------------------------------------------------------------------------------
-int lbm_batch_set_stats(lbm_batch* bt, int every, int capacity) {
-  size_t row_bytes = 0;  // of all members
-  return rearm_batch_recorder(bt, kRecStats, every, capacity, [&]() -> int {
-    const size_t n_members = bt->members.size();
-    row_bytes = n_members * gather_words(kRecStats) * sizeof(long long);
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: capacity %d, at least one row is needed", capacity);
-    if ((long long)capacity * (long long)row_bytes >= (1LL << 31))
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: a ring of %d rows of %d members is %.2f GiB, 2 GiB or more (%d bytes per member and row)",
-               capacity, (int)n_members, (double)capacity * (double)row_bytes / 1073741824.0,
-               lbm_stats::kStatsWords * (int)sizeof(long long));
-    return LBM_SUCCESS;
-  }, [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * row_bytes;
-    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_stats: cannot allocate %d rows of %d members (%.1f MiB); statistics stay off", capacity,
-               (int)bt->members.size(), (double)ring_bytes / 1048576.0);
-    return LBM_SUCCESS;
-  });
-}
+int lbm_batch_set_stats(lbm_batch* bt, int every, int capacity) { return arm_batch_gather(bt, kRecStats, every, capacity, GatherArgs{}); }
 
 int lbm_batch_read_stats(lbm_batch* bt, int max_rows, lbm_stats_row* out, int* steps, int* n_read) {
-  return drain_batch_recorder(bt, kRecStats, max_rows, out != nullptr, steps, n_read, [&](int n, const long long* words) {
-    // every member's words become its row
-    for (size_t j = 0; j < (size_t)n * bt->members.size(); j++)
-      out[j] = lbm_stats::stats_row_from_words(words + j * lbm_stats::kStatsWords, 1, bt->members[0]->p.nx);
-  });
+  return drain_batch_gather(bt, kRecStats, max_rows, out, steps, n_read);
 }
 
-// ---- enstrophy of a batch --------------------------------------------------------------------------------------------
-int lbm_batch_set_enstrophy(lbm_batch* bt, int every, int capacity) {
-  size_t row_bytes = 0;  // of all members
-  return rearm_batch_recorder(bt, kRecEnstrophy, every, capacity, [&]() -> int {
-    const size_t n_members = bt->members.size();
-    row_bytes = n_members * gather_words(kRecEnstrophy) * sizeof(long long);
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_enstrophy: capacity %d, at least one row is needed", capacity);
-    if ((long long)capacity * (long long)row_bytes >= (1LL << 31))
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_enstrophy: a ring of %d rows of %d members is %.2f GiB, 2 GiB or more (%d bytes per member and row)",
-               capacity, (int)n_members, (double)capacity * (double)row_bytes / 1073741824.0,
-               lbm_enstrophy::kEnstrophyWords * (int)sizeof(long long));
-    return LBM_SUCCESS;
-  }, [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * row_bytes;
-    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_enstrophy: cannot allocate %d rows of %d members (%.1f MiB); the enstrophy stays off", capacity,
-               (int)bt->members.size(), (double)ring_bytes / 1048576.0);
-    return LBM_SUCCESS;
-  });
-}
+int lbm_batch_set_enstrophy(lbm_batch* bt, int every, int capacity) { return arm_batch_gather(bt, kRecEnstrophy, every, capacity, GatherArgs{}); }
 
 int lbm_batch_read_enstrophy(lbm_batch* bt, int max_rows, lbm_enstrophy_row* out, int* steps, int* n_read) {
-  return drain_batch_recorder(bt, kRecEnstrophy, max_rows, out != nullptr, steps, n_read, [&](int n, const long long* words) {
-    // every member's words become its row
-    for (size_t j = 0; j < (size_t)n * bt->members.size(); j++)
-      out[j] = lbm_enstrophy::enstrophy_row_from_words(words + j * lbm_enstrophy::kEnstrophyWords, 1, bt->members[0]->p.nx);
-  });
+  return drain_batch_gather(bt, kRecEnstrophy, max_rows, out, steps, n_read);
 }
 
-// ---- stream function of a batch ---------------------------------------------------------------------------------------
-int lbm_batch_set_psi(lbm_batch* bt, int every, int capacity) {
-  size_t row_bytes = 0;  // of all members
-  return rearm_batch_recorder(bt, kRecPsi, every, capacity, [&]() -> int {
-    const size_t n_members = bt->members.size();
-    row_bytes = n_members * gather_words(kRecPsi) * sizeof(long long);
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_psi: capacity %d, at least one row is needed", capacity);
-    if ((long long)capacity * (long long)row_bytes >= (1LL << 31))
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_psi: a ring of %d rows of %d members is %.2f GiB, 2 GiB or more (%d bytes per member and row)",
-               capacity, (int)n_members, (double)capacity * (double)row_bytes / 1073741824.0, lbm_psi::kPsiWords * (int)sizeof(long long));
-    return LBM_SUCCESS;
-  }, [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * row_bytes, n_members = bt->members.size();
-    lbm_ctx* c0 = bt->members[0];
-    const int rows = c0->slab[0].rows, nx = c0->p.nx;
-    bt->psi_band_rows = psi_band_rows(c0, rows, nx);
-    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess ||
-        bt->psi_totals.alloc(n_members * psi_total_words(rows, nx, bt->psi_band_rows)) != hipSuccess ||
-        bt->psi_cand.alloc(n_members * psi_candidates(rows, nx, bt->psi_band_rows)) != hipSuccess)
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_psi: cannot allocate %d rows of %d members (%.1f MiB) and the scan's buffers; the stream function stays off",
-               capacity, (int)n_members, (double)ring_bytes / 1048576.0);
-    return LBM_SUCCESS;
-  });
-}
+int lbm_batch_set_psi(lbm_batch* bt, int every, int capacity) { return arm_batch_gather(bt, kRecPsi, every, capacity, GatherArgs{}); }
 
 int lbm_batch_read_psi_rows(lbm_batch* bt, int max_rows, lbm_psi_row* out, int* steps, int* n_read) {
-  return drain_batch_recorder(bt, kRecPsi, max_rows, out != nullptr, steps, n_read, [&](int n, const long long* words) {
-    // every member's words become its row
-    for (size_t j = 0; j < (size_t)n * bt->members.size(); j++)
-      out[j] = lbm_psi::psi_row_from_words(words + j * lbm_psi::kPsiWords, 1, bt->members[0]->p.nx);
-  });
+  return drain_batch_gather(bt, kRecPsi, max_rows, out, steps, n_read);
 }
 
-// ---- velocity residuals of a batch ---------------------------------------------------------------------------------
-int lbm_batch_set_residual(lbm_batch* bt, int every, int capacity) {
-  size_t row_bytes = 0;  // of all members
-  return rearm_batch_recorder(bt, kRecResidual, every, capacity, [&]() -> int {
-    const size_t n_members = bt->members.size();
-    row_bytes = n_members * gather_words(kRecResidual) * sizeof(long long);
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: capacity %d, at least one row is needed", capacity);
-    if ((long long)capacity * (long long)row_bytes >= (1LL << 31))
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: a ring of %d rows of %d members is %.2f GiB, 2 GiB or more (%d bytes per member and row)",
-               capacity, (int)n_members, (double)capacity * (double)row_bytes / 1073741824.0,
-               lbm_residual::kResidualWords * (int)sizeof(long long));
-    return LBM_SUCCESS;
-  }, [&]() -> int {
-    const lbm_ctx* c0 = bt->members[0];
-    const size_t n_members = bt->members.size(), ring_bytes = (size_t)capacity * row_bytes;
-    const size_t cells = (size_t)c0->slab[0].rows * c0->p.nx;
-    if (bt->residual_planes.alloc(n_members * 2 * cells) != hipSuccess)
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: cannot allocate the remembered fields of %d members (%zu cells each, %.1f MiB); residuals stay off",
-               (int)n_members, cells, (double)(n_members * 2 * cells * sizeof(float)) / 1048576.0);
-    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_residual: cannot allocate %d rows of %d members (%.1f MiB); residuals stay off", capacity,
-               (int)n_members, (double)ring_bytes / 1048576.0);
-    bt->rec.base_steps = bt->steps_done;
-    return launch_batch_residual(bt, bt->residual_planes, nullptr, true);  // the baselines of all members: one launch
-  });
-}
+int lbm_batch_set_residual(lbm_batch* bt, int every, int capacity) { return arm_batch_gather(bt, kRecResidual, every, capacity, GatherArgs{}); }
 
 int lbm_batch_read_residual(lbm_batch* bt, int max_rows, lbm_residual_row* out, int* steps, int* n_read) {
-  return drain_batch_recorder(bt, kRecResidual, max_rows, out != nullptr, steps, n_read, [&](int n, const long long* words) {
-    // every member's words become its row
-    const size_t n_members = bt->members.size();
-    for (size_t j = 0; j < (size_t)n * n_members; j++)
-      out[j] = lbm_residual::residual_row_from_words(words + j * lbm_residual::kResidualWords, 1, bt->members[0]->p.nx,
-                                                     residual_span(bt->rec, bt->rec.read + (long long)(j / n_members)));
-  });
-}
-
-// ---- line profiles of a batch --------------------------------------------------------------------------------------
-// the profiles: one launch per selected axis for all members
-static int take_batch_profiles(lbm_batch* bt, long long* record) {
-  lbm_ctx* c0 = bt->members[0];
-  const Slab& sl0 = c0->slab[0];
-  const size_t n_members = bt->members.size();
-  const int nx = c0->p.nx, axes = bt->rec.axes;
-  const long member_words = (long)(gather_slot_words(bt) / n_members);
-  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
-  long long* lines = record;
-  if (axes & LBM_PROFILE_ROWS) {
-    const dim3 grid((unsigned)ceil_div(sl0.rows, lbm::kBlock / 64), 1, (unsigned)n_members);
-    if (stats_vector(nx) == 4)
-      hipLaunchKernelGGL(lbm::profile_rows_batch<4>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, lines, member_words);
-    else
-      hipLaunchKernelGGL(lbm::profile_rows_batch<1>, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, lines, member_words);
-    lines += (size_t)sl0.rows * lbm_profile::kProfileWords;
-  }
-  if (axes & LBM_PROFILE_COLUMNS) {
-    const int band_rows = profile_band_rows(sl0.rows, nx);
-    const dim3 grid((unsigned)ceil_div(nx, lbm::kProfileColumns), (unsigned)ceil_div(sl0.rows, band_rows), (unsigned)n_members);
-    hipLaunchKernelGGL(lbm::profile_columns_batch, grid, dim3(lbm::kBlock), 0, bt->stream, lattice_args(c0, sl0), tab, sl0.rows, band_rows, lines,
-                       member_words);
-  }
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  return LBM_SUCCESS;
+  return drain_batch_gather(bt, kRecResidual, max_rows, out, steps, n_read);
 }
 
 int lbm_batch_set_profiles(lbm_batch* bt, int every, int capacity, int axes) {
-  size_t record_bytes = 0;  // of all members
-  return rearm_batch_recorder(bt, kRecProfiles, every, capacity, [&]() -> int {
-    const lbm_ctx* c0 = bt->members[0];
-    const size_t n_members = bt->members.size();
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: capacity %d, at least one record is needed", capacity);
-    if (axes < 1 || axes > (LBM_PROFILE_ROWS | LBM_PROFILE_COLUMNS))
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: axes %d, LBM_PROFILE_ROWS (1), LBM_PROFILE_COLUMNS (2) or both (3) are possible", axes);
-    const size_t member_bytes = gather_words(kRecProfiles, 0, c0->slab[0].rows, c0->p.nx, axes) * sizeof(long long);
-    record_bytes = n_members * member_bytes;
-    if ((long long)capacity * (long long)record_bytes >= (1LL << 31))
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: a ring of %d records of %d members is %.2f GiB, 2 GiB or more (%zu bytes per member and record)",
-               capacity, (int)n_members, (double)capacity * (double)record_bytes / 1073741824.0, member_bytes);
-    return LBM_SUCCESS;
-  }, [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * record_bytes;
-    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_profiles: cannot allocate %d records of %d members (%.1f MiB); profiles stay off", capacity,
-               (int)bt->members.size(), (double)ring_bytes / 1048576.0);
-    bt->rec.axes = axes;
-    return LBM_SUCCESS;
-  });
+  GatherArgs a;
+  a.axes = axes;
+  return arm_batch_gather(bt, kRecProfiles, every, capacity, a);
 }
 
 int lbm_batch_read_profiles(lbm_batch* bt, int max_records, lbm_profile_line* out, int* steps, int* n_read) {
-  return drain_batch_recorder(bt, kRecProfiles, max_records, out != nullptr, steps, n_read, [&](int n, const long long* words) {
-    // every member's words become its lines
-    const lbm_ctx* c0 = bt->members[0];
-    const int nx = c0->p.nx, ny = c0->slab[0].rows, row_first = 0, axes = bt->rec.axes;
-    const size_t n_members = bt->members.size(), lines = lbm_profile::profile_slab_lines(ny, nx, axes);
-    const size_t member_words = gather_slot_words(bt) / n_members;
-    for (size_t j = 0; j < (size_t)n * n_members; j++)
-      lbm_profile::profile_lines_from_words(words + j * member_words, 1, &row_first, &ny, nx, ny, axes, out + j * lines);
-  });
-}
-
-// ---- coarse frames of a batch --------------------------------------------------------------------------------------
-// one launch for all members; a member is one slab, so every box row is whole and leaves as lines
-static int take_batch_coarse(lbm_batch* bt, long long* frame) {
-  lbm_ctx* c0 = bt->members[0];
-  const Slab& sl0 = c0->slab[0];
-  const size_t n_members = bt->members.size();
-  const int bx = bt->rec.box_x;
-  const lbm_coarse::SlabBoxRows g = coarse_slab_boxes(c0, sl0, bx, bt->rec.box_y);
-  const int groups = coarse_groups(g);
-  const long member_words = (long)lbm_coarse::slot_words(g);
-  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
-  const dim3 grid((unsigned)g.count * (unsigned)groups, 1, (unsigned)n_members);
-  hipLaunchKernelGGL(coarse_wide(bx) ? lbm::coarse_gather_batch<true> : lbm::coarse_gather_batch<false>, grid, dim3(lbm::kBlock), 0, bt->stream,
-                     lattice_args(c0, sl0), tab, g, groups, frame, member_words);
-  HIP_TRY(LBM_FAILURE, hipGetLastError());
-  return LBM_SUCCESS;
+  return drain_batch_gather(bt, kRecProfiles, max_records, out, steps, n_read);
 }
 
 int lbm_batch_set_coarse_frames(lbm_batch* bt, int every, int capacity, int bx, int by) {
-  size_t frame_bytes = 0;  // of all members
-  return rearm_batch_recorder(bt, kRecCoarse, every, capacity, [&]() -> int {
-    const lbm_ctx* c0 = bt->members[0];
-    const size_t n_members = bt->members.size();
-    if (capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_batch_set_coarse_frames: capacity %d, at least one frame is needed", capacity);
-    if (coarse_box_ok("lbm_batch_set_coarse_frames", c0, bx, by) != LBM_SUCCESS) return LBM_FAILURE;
-    const size_t member_bytes = coarse_slot_words(c0, c0->slab[0], bx, by) * sizeof(long long);
-    frame_bytes = n_members * member_bytes;
-    if ((long long)capacity * (long long)frame_bytes >= (1LL << 31))
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_coarse_frames: a ring of %d frames of %d members is %.2f GiB, 2 GiB or more (%zu bytes per member and frame)",
-               capacity, (int)n_members, (double)capacity * (double)frame_bytes / 1073741824.0, member_bytes);
-    return LBM_SUCCESS;
-  }, [&]() -> int {
-    const size_t ring_bytes = (size_t)capacity * frame_bytes;
-    if (bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess)
-      LBM_FAIL(LBM_FAILURE, "lbm_batch_set_coarse_frames: cannot allocate %d frames of %d members (%.1f MiB); coarse frames stay off", capacity,
-               (int)bt->members.size(), (double)ring_bytes / 1048576.0);
-    bt->rec.box_x = bx;
-    bt->rec.box_y = by;
-    return LBM_SUCCESS;
-  });
+  GatherArgs a;
+  a.box_x = bx;
+  a.box_y = by;
+  return arm_batch_gather(bt, kRecCoarse, every, capacity, a);
 }
 
 int lbm_batch_read_coarse_frames(lbm_batch* bt, int max_frames, lbm_profile_line* out, int* steps, int* n_read) {
-  return drain_batch_recorder(bt, kRecCoarse, max_frames, out != nullptr, steps, n_read, [&](int n, const long long* words) {
-    // a member's slot is its frame, line for line
-    const lbm_ctx* c0 = bt->members[0];
-    const int nx = c0->p.nx, ny = c0->slab[0].rows, row_first = 0, bx = bt->rec.box_x, by = bt->rec.box_y;
-    const size_t n_members = bt->members.size(), boxes = (size_t)lbm_coarse::coarse_boxes(nx, bx) * lbm_coarse::coarse_boxes(ny, by);
-    const size_t member_words = gather_slot_words(bt) / n_members;
-    for (size_t j = 0; j < (size_t)n * n_members; j++)
-      lbm_coarse::coarse_frame_from_words(words + j * member_words, 1, &row_first, &ny, nx, ny, bx, by, out + j * boxes);
-  });
+  return drain_batch_gather(bt, kRecCoarse, max_frames, out, steps, n_read);
 }
 
 // ---- checked runs: to steady state on the average velocity (lbm_run_until) or the velocity residual (..._residual) ----
@@ -4881,7 +4753,7 @@ static int wait_stop_word(hipEvent_t ev, const int* slot, bool* stop) {
 // no recorder of a context (or batch member) may be armed in a checked run
 static int steady_recorder_off(const lbm_ctx* c, const char* who) {
   if (c->rec.kind == kRecNone) return LBM_SUCCESS;
-  const RecorderKind& k = kRecorderKinds[c->rec.kind];
+  const RecorderKind& k = kind_words(c->rec.kind);
   LBM_FAIL(LBM_FAILURE, kSteadyRecorder, who, k.name, k.setter, k.noun);
 }
 
@@ -4902,9 +4774,9 @@ static int checked_batch_ok(const lbm_batch* bt, const char* who, int max_steps,
   if (steady_args_ok(who, bt->steps_done, bt->members[0]->capacity, max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
   for (const lbm_ctx* c : bt->members)
     if (steady_recorder_off(c, who) != LBM_SUCCESS) return LBM_FAILURE;
-  if (bt->rec.kind != kRecNone)  // forces, statistics, residuals or profiles armed on the batch
-    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, who, kRecorderKinds[bt->rec.kind].name, batch_kind(bt->rec.kind)->setter,
-             kRecorderKinds[bt->rec.kind].noun);
+  if (bt->rec.kind != kRecNone)  // a gather kind armed on the batch
+    LBM_FAIL(LBM_FAILURE, kSteadyRecorder, who, kind_words(bt->rec.kind).name, gather_kind(bt->rec.kind).batch_setter,
+             kind_words(bt->rec.kind).noun);
   return LBM_SUCCESS;
 }
 

@@ -15,6 +15,7 @@ import pytest
 
 import vorticity_model
 from conftest import ROOT
+import makefile_rules
 
 NAMES = ("lbm_read_vorticity", "lbm_set_enstrophy", "lbm_read_enstrophy", "lbm_batch_set_enstrophy", "lbm_batch_read_enstrophy")
 FIELDS = ("enstrophy", "circulation", "nonfinite", "max_abs_w", "max_x", "max_y", "fluid")
@@ -122,7 +123,7 @@ def test_the_makefile_rebuilds_the_library_when_the_header_changes():
     assert "hip_runtime" not in text and "24 words = 192 bytes" in text          # no HIP; the size is stated in the header's text
     makefile = open(os.path.join(ROOT, "lbm-asynchronous_amd", "Makefile")).read()
     for target in ("liblbm_hip.so:", "asm:", "profile-lib:"):
-        line = next(l for l in makefile.splitlines() if l.startswith(target))
+        line = makefile_rules.rule_line(target)
         assert "csrc/lbm_enstrophy_row.h" in line, target
 
 

@@ -4,6 +4,7 @@ import os
 import subprocess
 
 from conftest import ROOT
+import makefile_rules
 
 CSRC = os.path.join(ROOT, "lbm-asynchronous_amd", "csrc")
 
@@ -32,5 +33,5 @@ def test_the_engine_splits_a_ring_nowhere_else():
     assert "slots - slot" not in src
     makefile = open(os.path.join(ROOT, "lbm-asynchronous_amd", "Makefile")).read()
     for target in ("liblbm_hip.so:", "asm:", "profile-lib:"):
-        line = next(l for l in makefile.splitlines() if l.startswith(target))
+        line = makefile_rules.rule_line(target)
         assert "csrc/lbm_ring.h" in line, target

@@ -5,6 +5,7 @@ import os
 import subprocess
 
 from conftest import ROOT
+import makefile_rules
 
 CSRC = os.path.join(ROOT, "lbm-asynchronous_amd", "csrc")
 
@@ -34,5 +35,5 @@ def test_the_engine_loops_over_segments_nowhere_else():
     assert "issued - judged" not in src
     makefile = open(os.path.join(ROOT, "lbm-asynchronous_amd", "Makefile")).read()
     for target in ("liblbm_hip.so:", "asm:", "profile-lib:"):
-        line = next(l for l in makefile.splitlines() if l.startswith(target))
+        line = makefile_rules.rule_line(target)
         assert "csrc/lbm_segments.h" in line, target
