@@ -964,7 +964,8 @@ int lbm_batch_read_coarse_frames(lbm_batch* batch, int max_frames, lbm_profile_l
  *   (lbm_create_rank*); batch members (a batch arms it as a whole: lbm_batch_set_enstrophy); LBM_HALO_STALE /
  *   LBM_HALO_FRESHEST (and lbm_set_halo_mode to those while armed); a context with another recorder armed (and the other
  *   setters while this one is armed); lbm_run_until and lbm_run_until_residual while armed.  Not offered: the double
- *   engine, recording inside the resident or stream kernels, higher-order stencils, the strain rate, a command-line mode.
+ *   engine, recording inside the resident or stream kernels, higher-order stencils, a command-line mode.  (The strain
+ *   rate comes from the second moment, without a stencil: lbm_read_stress and lbm_set_stress below.)
  * lbm_read_enstrophy: drains up to max_rows oldest rows into out[n] and steps[n] (their tt, may be NULL); out == NULL &&
  *   steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers.
  * lbm_batch_set_enstrophy / lbm_batch_read_enstrophy: the same for every member of a batch, armed on the BATCH with one
@@ -989,6 +990,86 @@ int lbm_set_enstrophy(lbm_ctx* ctx, int every, int capacity);
 int lbm_read_enstrophy(lbm_ctx* ctx, int max_rows, lbm_enstrophy_row* out, int* steps, int* n_read);
 int lbm_batch_set_enstrophy(lbm_batch* batch, int every, int capacity);
 int lbm_batch_read_enstrophy(lbm_batch* batch, int max_rows, lbm_enstrophy_row* out /* [n][members] */, int* steps, int* n_read);
+
+/* ---- stress and dissipation -----------------------------------------------------------------
+ * The second moment of the populations: the one quantity a lattice Boltzmann code has locally that a finite-difference
+ * code needs a stencil for.  The non-equilibrium momentum flux of a cell gives its strain-rate tensor, and from it the
+ * viscous dissipation (the sink of the energy budget whose other terms are sum_u_sq, the forces and the enstrophy), the
+ * shear rate and where it peaks, and the shear stress next to walls and obstacles.
+ * Per cell from its populations f[0..8] of the stored lattice, in fp32 with IEEE divide and no contraction, in exactly
+ * this order (rho, jx, jy, ux, uy and usq exactly as in the statistics' text above):
+ *     a56 = f5+f6            a78 = f7+f8
+ *     mxx = ((f1+f3)+a56)+a78          myy = ((f2+f4)+a56)+a78          mxy = (f5+f7)-(f6+f8)
+ *     third = rho / 3.0f
+ *     pxx = (mxx-third)-(jx*ux)        pyy = (myy-third)-(jy*uy)        pxy = mxy-(jx*uy)
+ *     txx = pxx/rho    tyy = pyy/rho    txy = pxy/rho
+ *     q   = ((txx*txx)+(tyy*tyy)) + (2.0f*(txy*txy))
+ * (The second moments of the D2Q9 equilibrium are rho/3 + rho ux^2, rho/3 + rho uy^2 and rho ux uy exactly, so p_ab is
+ * the non-equilibrium second moment Pi_ab.)  t_ab is the kinematic non-equilibrium stress of the STORED lattice, which is
+ * post-collision: its non-equilibrium part is (1 - omega) times the pre-collision one, so the strain rate is
+ *     S_ab = -c * t_ab,   c = 3 omega / (2 (1 - omega)),   S:S = c^2 * q,
+ * and with nu = (1/omega - 1/2)/3 the dissipation of a row is 2 nu c^2 sum_q and its largest shear rate |c| sqrt(2 max_q).
+ * The engine records t and q only: it does not know which omega the caller means to convert with, and at omega == 1 the
+ * stored lattice is pure equilibrium and carries no stress -- t is rounding noise there (still well defined) and the
+ * conversions of the Python package refuse it.
+ * fp32 accuracy: mxx - third cancels rho/3 and keeps the roundings of mxx and of third, so txx and tyy carry an ABSOLUTE
+ * error however small they are.  For populations >= 0, to first order in 2^-24 ("Stress and dissipation",
+ * counts it from the expression tree; tests/stress_model.py asserts it cell by cell):
+ *     |txx(fp32) - txx(exact)| <= 2^-24 * ((5 + 4|ux|) mxx/rho + 3 + 12 ux^2 + 10 |txx|)     about 4.7 * 2^-24; tyy alike
+ *     |txy(fp32) - txy(exact)| <= 2^-24 * ((f5+f6+f7+f8 + |mxy| + 2 (|ux| myy + |uy| mxx) + |pxy|) / rho + 12 |ux uy| + 9 |txy|)
+ * the second about (1/9 + 0.7 (|ux| + |uy|)) * 2^-24.  Measured on the 128 x 128 data set after 4000 steps: at most
+ * 1.69 * 2^-24 in txx and tyy (1.01e-8 in pxx, pyy at rho = 0.1), 0.096 * 2^-24 in txy.
+ * A blocked cell has t = 0 and q = 0 and contributes to nothing.  A fluid cell is NON-FINITE when one of rho, jx, jy, usq
+ * (the statistics' rule), txx, tyy, txy or q is not finite; such a cell adds to no sum and is counted in `nonfinite`.
+ *     sum_q = sum of q over the finite fluid cells;  sum_txy = sum of txy over them;  fluid = their number;
+ *     max_q = the largest q among them, at the GLOBAL cell (max_x, max_y) -- of several cells with that q the one with
+ *     the smallest y*nx+x; 0 at -1, -1 when there is no finite fluid cell.
+ * Both sums are taken EXACTLY (csrc/lbm_exact_sum.h, one float per cell and sum) and rounded to a double once: the value
+ * math.fsum gives for the same terms.  The maximum is the statistics' 64-bit key (the bits of q, which is >= +0, then
+ * 0xffffffff - cell) and does not depend on order either.  A row therefore has the same bits from a single call, split
+ * calls, resident or per-pass sub-calls, 1, 2, 3 or 8 slabs, a tiled context, a batch member, and from run to run.
+ * lbm_read_stress(ctx, txx, txy, tyy): the three fields of the current lattice, each [row_count * nx] row-major, t as
+ *   above, 0 on blocked cells; a non-finite value is stored as computed.  Any of the three may be NULL.  Synchronises like
+ *   the other readers, needs nothing armed and changes nothing (a temporary device buffer per slab, freed before it
+ *   returns).  Works on lbm_create / lbm_create_tiled contexts of any slab count and on batch member handles; refused on
+ *   rank contexts (lbm_create_rank*).
+ * lbm_set_stress(ctx, every, capacity): from now on, after global timestep tt (0-based, the numbering of lbm_set_frames)
+ *   with tt % every == 0, record one row of the lattice after tt+1 timesteps.  Rows wait in a device ring of `capacity`
+ *   rows (192 bytes per row and slab: the exact sums, rounded when read); an lbm_run that would record more rows than are
+ *   free fails before issuing any work.  every == 0 disarms and frees; re-arming discards unread rows.  No step kernel
+ *   records the stress: as with the statistics every call runs as the sub-calls that end at its sample steps, each
+ *   followed per slab by one memset of the row and one stress_gather launch (every == 1: correct, not fast).  The kernel
+ *   is pointwise: it reads a slab's owned rows only.  Recording never changes the lattice or av_vels: they equal those of
+ *   the same run issued as calls split at the sample steps.
+ *   Refused, as lbm_set_enstrophy refuses: negative every; capacity < 1; a ring of 2 GiB or more; rank contexts
+ *   (lbm_create_rank*); batch members (a batch arms it as a whole: lbm_batch_set_stress); LBM_HALO_STALE /
+ *   LBM_HALO_FRESHEST (and lbm_set_halo_mode to those while armed); a context with another recorder armed (and the other
+ *   setters while this one is armed); lbm_run_until and lbm_run_until_residual while armed.  Not offered: a d2q9-bgk
+ *   mode, the double engine, rank contexts, recording inside the resident or stream kernels, the pre-collision stress.
+ * lbm_read_stress_rows: drains up to max_rows oldest rows into out[n] and steps[n] (their tt, may be NULL); out == NULL
+ *   && steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers.
+ * lbm_batch_set_stress / lbm_batch_read_stress_rows: the same for every member of a batch, armed on the BATCH with one
+ *   `every` and ONE ring [slots][members][24 words]; rows are out[n][members].  Behind each sub-call that ends at a sample
+ *   step the batch's stream gets one memset of the row and ONE stress_gather_batch launch for all members (grid z is the
+ *   member).  Member i's rows, lattice and av_vels are bit-identical to those of an lbm_create context armed with
+ *   lbm_set_stress and advanced by the same calls.  An lbm_batch_run without room fails before any work and moves no
+ *   member's steps_done.  Refused as lbm_batch_set_enstrophy refuses: a member with a recorder armed, another kind armed
+ *   on the batch (and every member-level setter and the other batch-level setters while the stress is armed);
+ *   lbm_batch_run_until and lbm_batch_run_until_residual while armed.
+ */
+typedef struct {
+  double    sum_q;        /* exact sum of q over the finite fluid cells, rounded once (math.fsum's value) */
+  double    sum_txy;      /* exact sum of txy over the same cells */
+  long long nonfinite;    /* fluid cells left out of everything above and below */
+  float     max_q;        /* largest q of a finite fluid cell; 0 when there is none */
+  int       max_x, max_y; /* its GLOBAL cell; ties: the smallest y*nx+x; -1,-1 when there is none */
+  int       fluid;        /* finite fluid cells counted */
+} lbm_stress_row;         /* 40 bytes; offsets 0 8 16 24 28 32 36 */
+int lbm_read_stress(lbm_ctx* ctx, float* txx /* [row_count*nx] or NULL */, float* txy /* likewise */, float* tyy /* likewise */);
+int lbm_set_stress(lbm_ctx* ctx, int every, int capacity);
+int lbm_read_stress_rows(lbm_ctx* ctx, int max_rows, lbm_stress_row* out, int* steps, int* n_read);
+int lbm_batch_set_stress(lbm_batch* batch, int every, int capacity);
+int lbm_batch_read_stress_rows(lbm_batch* batch, int max_rows, lbm_stress_row* out /* [n][members] */, int* steps, int* n_read);
 
 /* ---- stream function ------------------------------------------------------------------------
  * The other field anyone draws of a lid-driven cavity, and the numbers it is validated by: the position of the primary

@@ -60,6 +60,7 @@ ABI_SYMBOLS = (
     "lbm_read_coarse", "lbm_set_coarse_frames", "lbm_read_coarse_frames", "lbm_batch_set_coarse_frames", "lbm_batch_read_coarse_frames",
     "lbm_read_vorticity", "lbm_set_enstrophy", "lbm_read_enstrophy", "lbm_batch_set_enstrophy", "lbm_batch_read_enstrophy",
     "lbm_read_psi", "lbm_set_psi", "lbm_read_psi_rows", "lbm_batch_set_psi", "lbm_batch_read_psi_rows",
+    "lbm_read_stress", "lbm_set_stress", "lbm_read_stress_rows", "lbm_batch_set_stress", "lbm_batch_read_stress_rows",
     "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
     "lbm_double_sync", "lbm_double_read_av_vels", "lbm_double_read_cells", "lbm_double_read_final_state",
     "lbm_double_av_velocity", "lbm_double_total_density", "lbm_double_calc_reynolds",
@@ -292,6 +293,11 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_read_enstrophy.argtypes = [P, I, P, P, PI]; lib.lbm_read_enstrophy.restype = I
     lib.lbm_batch_set_enstrophy.argtypes = [P, I, I]; lib.lbm_batch_set_enstrophy.restype = I
     lib.lbm_batch_read_enstrophy.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_enstrophy.restype = I
+    lib.lbm_read_stress.argtypes = [P, P, P, P]; lib.lbm_read_stress.restype = I
+    lib.lbm_set_stress.argtypes = [P, I, I]; lib.lbm_set_stress.restype = I
+    lib.lbm_read_stress_rows.argtypes = [P, I, P, P, PI]; lib.lbm_read_stress_rows.restype = I
+    lib.lbm_batch_set_stress.argtypes = [P, I, I]; lib.lbm_batch_set_stress.restype = I
+    lib.lbm_batch_read_stress_rows.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_stress_rows.restype = I
     lib.lbm_read_psi.argtypes = [P, P]; lib.lbm_read_psi.restype = I
     lib.lbm_set_psi.argtypes = [P, I, I]; lib.lbm_set_psi.restype = I
     lib.lbm_read_psi_rows.argtypes = [P, I, P, P, PI]; lib.lbm_read_psi_rows.restype = I
@@ -763,6 +769,28 @@ class Engine:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], ENSTROPHY_DTYPE[n])."""
         return _drain_rows(self.lib.lbm_read_enstrophy, self.lib, self.handle, "enstrophy", max_rows, (), ENSTROPHY_DTYPE, np.zeros)
 
+    # -- stress and dissipation (lbm_read_stress / lbm_set_stress / lbm_read_stress_rows) ------------
+    def stress(self) -> dict:
+        """The kinematic non-equilibrium stress of the current (stored, post-collision) lattice: {"txx", "txy", "tyy"},
+        float32 (row_count, nx) each, t_ab = Pi_ab / rho from the cell's second moment, blocked cells 0.  strain_rate()
+        converts it.  Needs nothing armed and changes nothing."""
+        shape = (self.info()["row_count"], self.params.nx)
+        out = {name: np.empty(shape, dtype=np.float32) for name in ("txx", "txy", "tyy")}
+        _check(self.lib, self.lib.lbm_read_stress(self.handle, out["txx"].ctypes.data, out["txy"].ctypes.data, out["tyy"].ctypes.data))
+        return out
+
+    def set_stress(self, every: int, capacity: int = 4096) -> None:
+        """Record one row of the stress' whole-lattice sums -- sum_q (q = txx^2 + tyy^2 + 2 txy^2) and sum_txy over the
+        finite fluid cells, summed exactly and rounded once, the largest q and its cell, the counts -- after every global
+        timestep tt with tt % every == 0, for the lattice after tt + 1 steps, into a device ring of `capacity` rows.
+        every == 0 disarms; re-arming discards unread rows.  dissipation() and shear_rate_max() convert the rows."""
+        every, capacity = _every_capacity("set_stress", every, capacity, "row")
+        _check(self.lib, self.lib.lbm_set_stress(self.handle, every, capacity))
+
+    def stress_rows(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], STRESS_DTYPE[n])."""
+        return _drain_rows(self.lib.lbm_read_stress_rows, self.lib, self.handle, "stress_rows", max_rows, (), STRESS_DTYPE, np.zeros)
+
     # -- stream function (lbm_read_psi / lbm_set_psi / lbm_read_psi_rows) ----------------------------
     def psi(self) -> np.ndarray:
         """The mass stream function of the current lattice, float64 (row_count, nx): psi[y, x] = the exact sum of j_x over
@@ -1125,6 +1153,18 @@ class Batch:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], ENSTROPHY_DTYPE[n, members])."""
         return _drain_rows(self.lib.lbm_batch_read_enstrophy, self.lib, self._live(), "enstrophy", max_rows, (len(self),),
                            ENSTROPHY_DTYPE, np.zeros)
+
+    # -- stress rows of all members (lbm_batch_set_stress / lbm_batch_read_stress_rows) --------------------------------------
+    def set_stress(self, every: int, capacity: int = 4096) -> None:
+        """Engine.set_stress for every member at once: one `every` and `capacity` for the batch, rows in one device ring,
+        one gather launch per sample whatever the number of members.  every == 0 disarms."""
+        every, capacity = _every_capacity("set_stress", every, capacity, "row")
+        _check(self.lib, self.lib.lbm_batch_set_stress(self._live(), every, capacity))
+
+    def stress_rows(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], STRESS_DTYPE[n, members])."""
+        return _drain_rows(self.lib.lbm_batch_read_stress_rows, self.lib, self._live(), "stress_rows", max_rows, (len(self),),
+                           STRESS_DTYPE, np.zeros)
 
     # -- stream function of all members (lbm_batch_set_psi / lbm_batch_read_psi_rows) ---------------------------------------
     def set_psi(self, every: int, capacity: int = 4096) -> None:
@@ -1499,6 +1539,59 @@ def write_enstrophy(path: str, steps, rows) -> None:
             fh.write("%d:\t%.12E\t%.12E\t%.12E\t%d\t%d\t%d\t%d\n" % (
                 tt, float(r["enstrophy"]), float(r["circulation"]), float(r["max_abs_w"]), int(r["max_x"]), int(r["max_y"]),
                 int(r["fluid"]), int(r["nonfinite"])))
+
+
+# lbm_stress_row of include/lbm_hip.h, 40 bytes
+STRESS_DTYPE = np.dtype([("sum_q", "<f8"), ("sum_txy", "<f8"), ("nonfinite", "<i8"), ("max_q", "<f4"),
+                         ("max_x", "<i4"), ("max_y", "<i4"), ("fluid", "<i4")])
+
+
+def write_stress_rows(path: str, steps, rows) -> None:
+    """One line per row in write_enstrophy's style: tt, a colon, then tab-separated sum_q, sum_txy and max_q as '%.12E'
+    and max_x, max_y, fluid and nonfinite as '%d'; `steps` int[n], `rows` STRESS_DTYPE[n] (Engine.stress_rows)."""
+    rows = np.asarray(rows)
+    steps = np.asarray(steps).ravel()
+    if rows.dtype != STRESS_DTYPE or rows.ndim != 1 or rows.shape[0] != steps.size:
+        raise LbmError(f"write_stress_rows: rows must be {steps.size} rows of STRESS_DTYPE (got shape {rows.shape}, dtype {rows.dtype})")
+    with open(path, "w") as fh:
+        for tt, r in zip(steps.tolist(), rows):
+            fh.write("%d:\t%.12E\t%.12E\t%.12E\t%d\t%d\t%d\t%d\n" % (
+                tt, float(r["sum_q"]), float(r["sum_txy"]), float(r["max_q"]), int(r["max_x"]), int(r["max_y"]),
+                int(r["fluid"]), int(r["nonfinite"])))
+
+
+def _strain_factor(who: str, omega) -> float:
+    """c = 3 omega / (2 (1 - omega)) of S_ab = -c t_ab: the stored lattice is post-collision, its non-equilibrium part
+    (1 - omega) times the pre-collision one.  Refuses omega outside (0, 2) and omega == 1."""
+    omega = float(omega)
+    if not 0.0 < omega < 2.0:
+        raise ValueError(f"{who}: omega {omega!r} lies outside (0, 2)")
+    if omega == 1.0:
+        raise ValueError(f"{who}: at omega == 1 the stored lattice is pure equilibrium and carries no stress: "
+                         "its second moment is rounding noise and the factor 1 / (1 - omega) does not exist")
+    return 3.0 * omega / (2.0 * (1.0 - omega))
+
+
+def strain_rate(stress: dict, omega: float) -> dict:
+    """The strain-rate tensor of Engine.stress()'s planes, float64: {"S_xx", "S_xy", "S_yy"}, S_ab = -c t_ab with
+    c = 3 omega / (2 (1 - omega)); `omega` is the one the lattice was advanced with."""
+    c = _strain_factor("strain_rate", omega)
+    return {"S_" + ab: -c * np.asarray(stress["t" + ab], dtype=np.float64) for ab in ("xx", "xy", "yy")}
+
+
+def dissipation(rows, omega: float) -> np.ndarray:
+    """The viscous dissipation 2 nu S:S summed over the finite fluid cells, per row of Engine.stress_rows, float64:
+    2 nu c^2 sum_q with nu = (1 / omega - 1 / 2) / 3 (lattice units, per unit density)."""
+    c = _strain_factor("dissipation", omega)
+    nu = (1.0 / float(omega) - 0.5) / 3.0
+    return 2.0 * nu * c * c * np.asarray(rows["sum_q"], dtype=np.float64)
+
+
+def shear_rate_max(rows, omega: float) -> np.ndarray:
+    """The largest shear rate sqrt(2 S:S) of a finite fluid cell, per row of Engine.stress_rows, float64:
+    |c| sqrt(2 max_q), at the row's (max_x, max_y)."""
+    c = _strain_factor("shear_rate_max", omega)
+    return abs(c) * np.sqrt(2.0 * np.asarray(rows["max_q"], dtype=np.float64))
 
 
 # lbm_psi_row of include/lbm_hip.h, 48 bytes

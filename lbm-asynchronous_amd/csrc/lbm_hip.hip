@@ -426,11 +426,12 @@ struct GraphBuilder {
 // one kind whose slabs depend on each other (Slab::psi_in, psi_out).
 // Coarse frames (lbm_set_coarse_frames) likewise, by coarse_gather: a frame of per-box sums, rounded on the device except
 // in the box rows that two slabs share.
-// These seven gather kinds share one ring of int64 words per slab, Slab::gather_ring; a batch arms them on itself
+// The stress (lbm_set_stress) likewise, by stress_gather: a row of whole-lattice sums of the second moment, pointwise.
+// These eight gather kinds share one ring of int64 words per slab, Slab::gather_ring; a batch arms them on itself
 // (lbm_batch::rec) with one ring for all members.  What a gather kind is stands in one place, its entry of kGatherKinds.
 enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean,
        kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecResidual = 7, kRecProfiles = 8, kRecEnstrophy = 9,
-       kRecPsi = 10, kRecCoarse = 11, kRecKinds = 12, kRecGatherFirst = kRecForces };
+       kRecPsi = 10, kRecCoarse = 11, kRecStress = 12, kRecKinds = 13, kRecGatherFirst = kRecForces };
 // the kinds recorded by a gather launch behind the sub-call that ends at a sample step, whatever kernels advance the lattice
 constexpr bool is_gather(int kind) { return kind >= kRecGatherFirst && kind < kRecKinds; }
 // what a gather kind was armed with: the arguments of its setter that its slot's size, its launches and its reader depend on
@@ -486,7 +487,7 @@ struct GatherOwner {
 // A hook that allocates answers LBM_SUCCESS, LBM_FAILURE (it has said why) or kNoRoom: the driver then says that the ring
 // and `also` could not be allocated.
 constexpr int kNoRoom = 2;
-// One gather kind: everything that differs between the seven, for a context and for a batch.  The drivers (arm_gather,
+// One gather kind: everything that differs between the eight, for a context and for a batch.  The drivers (arm_gather,
 // arm_batch_gather, drain_gather, drain_batch_gather, take_record, lbm_batch_run) know no kind.
 struct GatherKind {
   RecorderKind ctx;          // the words of a context's messages ...
@@ -587,7 +588,7 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentProbes> probe_table;  // device: [members], allocated when the first member arms probes
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
   DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
-  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
+  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
                                     // (a batch records one kind, so at most one count is non-zero; a gather kind is armed
                                     // on the batch, by its lbm_batch_set_*, and counts as one)
   // the gather kinds (kGatherKinds) of all members: the members' own recorders stay off, the batch keeps the one
@@ -1665,6 +1666,20 @@ void launch_residual_gather(const lbm_ctx* c, const Slab& sl, float* planes, lon
   else
     hipLaunchKernelGGL(v == 4 ? lbm::residual_gather<4> : lbm::residual_gather<1>, grid, block, 0, sl.compute, lattice_args(c, sl), sl.rows,
                        cell_first, px, py, words, (int)baseline);
+}
+
+// the stress of the rows [row_begin, row_begin + rows) of a slab's current lattice on its compute stream: into `field`
+// (three dense planes of rows * nx floats; or null) and / or `words` (a zeroed slot of the ring; or null).  The deal is
+// stats_gather's
+void launch_stress_gather(const lbm_ctx* c, const Slab& sl, int row_begin, int rows, float* field, long long* words) {
+  const int nx = c->p.nx;
+  const bool v4 = stats_vector(nx) == 4;
+  const dim3 grid(stats_groups((long)rows * nx, v4 ? 4 : 1));
+  const unsigned cell_first = (unsigned)sl.row_first * (unsigned)nx;
+  const auto kernel = field ? (v4 ? lbm::stress_gather<4, true> : lbm::stress_gather<1, true>)
+                            : (v4 ? lbm::stress_gather<4, false> : lbm::stress_gather<1, false>);  // (the form without the fields' stores)
+  hipLaunchKernelGGL(kernel, grid, dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), row_begin, rows, cell_first, field, (long)rows * nx,
+                     words);
 }
 
 // rows of a band of profile_columns / profile_columns_batch for `rows` rows of nx cells: about kProfileTargetGroups
@@ -2990,6 +3005,20 @@ int take_batch_enstrophy(lbm_batch* bt, long long* row) {
   return LBM_SUCCESS;
 }
 
+// the stress: one stress_gather_batch for all members
+int take_batch_stress(lbm_batch* bt, long long* row) {
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  const Slab& sl0 = c0->slab[0];
+  const int v = stats_vector(c0->p.nx);
+  const dim3 grid((unsigned)stats_groups((long)sl0.rows * c0->p.nx, v), 1, (unsigned)n_members);
+  const lbm::ResidentMember* tab = bt->table + (size_t)bt->cur * n_members;
+  hipLaunchKernelGGL(v == 4 ? lbm::stress_gather_batch<4> : lbm::stress_gather_batch<1>, grid, dim3(lbm::kBlock), 0, bt->stream,
+                     lattice_args(c0, sl0), tab, sl0.rows, row);
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+
 // the stream function: ONE launch of each of the scan's kernels for all members (grid z is the member; psi_extrema: grid x),
 // each member a grid of its own from row 0
 int take_batch_psi(lbm_batch* bt, long long* row) {
@@ -3279,6 +3308,10 @@ int take_enstrophy(lbm_ctx* c) {
   if (mark_vorticity_ready(c) != LBM_SUCCESS || take_per_slab(c) != LBM_SUCCESS) return LBM_FAILURE;
   return await_vorticity_done(c);
 }
+int launch_stress(lbm_ctx* c, int s, long long* words) {
+  launch_stress_gather(c, c->slab[s], 0, c->slab[s].rows, nullptr, words);
+  return LBM_SUCCESS;
+}
 // (the stream function's slabs depend on each other: take_psi_record issues them in their order)
 
 // ---- one record of a batch: the members' current (stored) lattices into `row`, the record's slot, which lbm_batch_run
@@ -3387,7 +3420,14 @@ const GatherKind kGatherKinds[kRecKinds - kRecGatherFirst] = {
      .batch_disarm = "lbm_batch_set_coarse_frames(batch, 0, 0, 0, 0)",
      .stays_off = "coarse frames stay off", .spread = "a box's cells", .of_a_batch = "the coarse frames of a batch are", .per_slab = true,
      .slot_words = coarse_frames_slot_words, .check = check_coarse_frames,
-     .take = take_per_slab, .launch = launch_coarse_frame, .take_batch = take_batch_coarse, .rows = coarse_frames_rows}};
+     .take = take_per_slab, .launch = launch_coarse_frame, .take_batch = take_batch_coarse, .rows = coarse_frames_rows},
+    {.ctx = {.name = "stress rows", .noun = "the stress", .record = "row", .setter = "lbm_set_stress", .reader = "lbm_read_stress_rows",
+             .disarm = "lbm_set_stress(ctx, 0, 0)"},
+     .batch_setter = "lbm_batch_set_stress", .batch_reader = "lbm_batch_read_stress_rows", .batch_disarm = "lbm_batch_set_stress(batch, 0, 0)",
+     .stays_off = "the stress stays off", .spread = "a row's sums", .of_a_batch = "the stress of a batch is",
+     .slot_words = fixed_slot_words<lbm_stress::kStressWords>,
+     .take = take_per_slab, .launch = launch_stress, .take_batch = take_batch_stress,
+     .rows = rows_merged<lbm_stress_row, lbm_stress::stress_row_from_words>}};
 const GatherKind& gather_kind(int kind) { return kGatherKinds[kind - kRecGatherFirst]; }
 const RecorderKind& kind_words(int kind) { return is_gather(kind) ? gather_kind(kind).ctx : kRecorderKinds[kind]; }
 
@@ -4080,6 +4120,41 @@ int lbm_read_vorticity(lbm_ctx* c, float* w) {
   return LBM_SUCCESS;
 }
 
+// ---- stress and dissipation --------------------------------------------------------------------------------------------
+int lbm_set_stress(lbm_ctx* c, int every, int capacity) { return arm_gather(c, kRecStress, every, capacity, GatherArgs{}); }
+
+int lbm_read_stress_rows(lbm_ctx* c, int max_rows, lbm_stress_row* out, int* steps, int* n_read) {
+  return drain_gather(c, kRecStress, max_rows, out, steps, n_read);
+}
+
+int lbm_read_stress(lbm_ctx* c, float* txx, float* txy, float* tyy) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_read_stress: NULL argument");
+  if (c->ranked || c->world > 1)
+    LBM_FAIL(LBM_FAILURE, "lbm_read_stress: not available in a multi-process (rank) context: the fields of a rank's rows are not offered");
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
+  float* const out[3] = {txx, txy, tyy};
+  const int nx = c->p.nx;
+  long chunk_rows = (16L << 20) / ((long)nx * sizeof(float));
+  if (chunk_rows < 1) chunk_rows = 1;
+  for (int s = 0; s < c->n_slabs; s++) {
+    Slab& sl = c->slab[s];
+    HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
+    DeviceBuf<float> stage;  // the call's own, three planes of a chunk: nothing armed is touched
+    HIP_TRY(LBM_FAILURE, stage.alloc(3 * (size_t)chunk_rows * nx));
+    for (int r0 = 0; r0 < sl.rows; r0 += (int)chunk_rows) {
+      const int nr = (sl.rows - r0 < chunk_rows) ? sl.rows - r0 : (int)chunk_rows;
+      launch_stress_gather(c, sl, r0, nr, stage, nullptr);
+      HIP_TRY(LBM_FAILURE, hipGetLastError());
+      for (int i = 0; i < 3; i++)
+        if (out[i])
+          HIP_TRY(LBM_FAILURE, hipMemcpyAsync(out[i] + (size_t)(sl.row_first - c->row_first + r0) * nx, stage + (size_t)i * nr * nx,
+                                              (size_t)nr * nx * sizeof(float), hipMemcpyDeviceToHost, sl.compute));
+      HIP_TRY(LBM_FAILURE, hipStreamSynchronize(sl.compute));
+    }
+  }
+  return LBM_SUCCESS;
+}
+
 // ---- stream function ---------------------------------------------------------------------------------------------------
 int lbm_set_psi(lbm_ctx* c, int every, int capacity) { return arm_gather(c, kRecPsi, every, capacity, GatherArgs{}); }
 
@@ -4653,6 +4728,12 @@ int lbm_batch_set_enstrophy(lbm_batch* bt, int every, int capacity) { return arm
 
 int lbm_batch_read_enstrophy(lbm_batch* bt, int max_rows, lbm_enstrophy_row* out, int* steps, int* n_read) {
   return drain_batch_gather(bt, kRecEnstrophy, max_rows, out, steps, n_read);
+}
+
+int lbm_batch_set_stress(lbm_batch* bt, int every, int capacity) { return arm_batch_gather(bt, kRecStress, every, capacity, GatherArgs{}); }
+
+int lbm_batch_read_stress_rows(lbm_batch* bt, int max_rows, lbm_stress_row* out, int* steps, int* n_read) {
+  return drain_batch_gather(bt, kRecStress, max_rows, out, steps, n_read);
 }
 
 int lbm_batch_set_psi(lbm_batch* bt, int every, int capacity) { return arm_batch_gather(bt, kRecPsi, every, capacity, GatherArgs{}); }

@@ -40,6 +40,7 @@
 #include "lbm_profile_row.h"
 #include "lbm_coarse_row.h"
 #include "lbm_enstrophy_row.h"
+#include "lbm_stress_row.h"
 #include "lbm_psi_row.h"
 #include "lbm_exact_round.h"
 #include "lbm_residual_until.h"
@@ -3830,6 +3831,168 @@ __global__ __launch_bounds__(kBlock) void vorticity_gather_batch(const LatticeAr
   const float* src = members[member].src;
   vorticity_cells<V, false>(a, src, members[member].mask, src + (long)(rows - 1) * a.row_pitch, src, rows, 0, rows, band_rows, 0u, nullptr,
                      row + (size_t)member * lbm_enstrophy::kEnstrophyWords);
+}
+
+// ---------------------------------------------------------------------------------------------
+// stress and dissipation (lbm_read_stress, lbm_set_stress): the kinematic non-equilibrium stress t_ab = Pi_ab / rho of
+// every cell of a stored lattice from its second moment, as three fields and / or as the exact sums of q = t:t and of
+// txy, the largest q with its cell and the counts of a row (lbm_stress_row.h)
+// ---------------------------------------------------------------------------------------------
+// The definition of include/lbm_hip.h, in its order: fp32, IEEE divide, no contraction (the build's -ffp-contract=off).
+// rho, jx, jy, ux, uy, usq are the statistics' (moments_exact).  The second moments of the D2Q9 equilibrium are rho/3 +
+// rho ux^2, rho/3 + rho uy^2 and rho ux uy exactly, so no per-direction equilibrium is evaluated.  The one place where the
+// row form and the field form get their per-cell values: they cannot drift apart.
+struct StressCell {
+  float txx, txy, tyy, q;
+  bool finite;  // rho, jx, jy, usq, txx, tyy, txy and q are all finite
+};
+__device__ __forceinline__ StressCell stress_cell(const float (&f)[kQ]) {
+  float rho, ux, uy;
+  moments_exact(f, rho, ux, uy);
+  const float jx = f[1] + f[5] + f[8] - (f[3] + f[6] + f[7]);
+  const float jy = f[2] + f[5] + f[6] - (f[4] + f[7] + f[8]);
+  const float usq = (ux * ux) + (uy * uy);
+  const float a56 = f[5] + f[6], a78 = f[7] + f[8];
+  const float mxx = ((f[1] + f[3]) + a56) + a78;
+  const float myy = ((f[2] + f[4]) + a56) + a78;
+  const float mxy = (f[5] + f[7]) - (f[6] + f[8]);
+  const float third = rho / 3.0f;
+  const float pxx = (mxx - third) - (jx * ux);
+  const float pyy = (myy - third) - (jy * uy);
+  const float pxy = mxy - (jx * uy);
+  StressCell c;
+  c.txx = pxx / rho;
+  c.tyy = pyy / rho;
+  c.txy = pxy / rho;
+  c.q = ((c.txx * c.txx) + (c.tyy * c.tyy)) + (2.0f * (c.txy * c.txy));
+  c.finite = lbm_exact::exact_sum_finite(__float_as_uint(rho)) && lbm_exact::exact_sum_finite(__float_as_uint(jx)) &&
+             lbm_exact::exact_sum_finite(__float_as_uint(jy)) && lbm_exact::exact_sum_finite(__float_as_uint(usq)) &&
+             lbm_exact::exact_sum_finite(__float_as_uint(c.txx)) && lbm_exact::exact_sum_finite(__float_as_uint(c.tyy)) &&
+             lbm_exact::exact_sum_finite(__float_as_uint(c.txy)) && lbm_exact::exact_sum_finite(__float_as_uint(c.q));
+  return c;
+}
+
+// One sample, built the way stats_cells is: the cells of the rows [row_begin, row_begin + rows) of a slab are dealt out V
+// at a time along x (V = 4 where nx % 4 == 0: nine 16-byte plane loads and one 4-byte mask load per lane; V = 1 otherwise)
+// to the lanes of a capped grid that strides; no unit reaches into the pitch padding (x + V <= nx).  A lane keeps two
+// fixed-point accumulators (q, txy), its two counts and its key, stats_key(bits of q, global cell) -- q >= +0; a cell that
+// does not contribute is added with sign 0.  The reduction is stats_cells': shuffles, LDS, 64-bit integer atomicAdd /
+// atomicMax into `words` (kStressWords of them, zeroed by the host); no floating-point addition across cells happens on
+// the device.  FIELD = true also stores txx, txy, tyy of every cell -- blocked cells 0, a non-finite value as computed --
+// to the dense planes field + {0, 1, 2} * field_stride ([rows][nx], row row_begin first; a null `field` or `words` is
+// skipped), with 16-byte stores at V = 4 (a unit is 16-byte aligned where nx % 4 == 0 and field_stride % 4 == 0).
+template <int V, bool FIELD>
+__device__ __forceinline__ void stress_cells(const LatticeArgs& a, const float* src, const unsigned char* mask, int row_begin, int rows,
+                                             unsigned cell_first, float* field, long field_stride, long long* words) {
+  constexpr int L = lbm_exact::kExactLimbs, S = lbm_stress::kStressSums, W = lbm_stress::kStressKeyWord + 1;
+  __shared__ long long sh[kBlock / 64][W];
+  long long acc[S][L], bad = 0, n_fluid = 0;
+  unsigned long long key = 0ull;
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int i = 0; i < L; i++) acc[j][i] = 0;
+  const long per_row = a.nx / V, n_units = (long)rows * per_row;
+  for (long u = (long)blockIdx.x * kBlock + threadIdx.x; u < n_units; u += (long)gridDim.x * kBlock) {
+    const int rr = (int)(u / per_row), x = (int)(u - (long)rr * per_row) * V, r = row_begin + rr;
+    const float* p = src + (long)r * a.row_pitch + x;
+    float f[V][kQ];
+    unsigned blocked;  // byte v: the mask of cell x + v
+    if constexpr (V == 4) {
+#pragma unroll
+      for (int k = 0; k < kQ; k++) {
+        const float4 q = *reinterpret_cast<const float4*>(p + k * a.plane_stride);
+        f[0][k] = q.x;  f[1][k] = q.y;  f[2][k] = q.z;  f[3][k] = q.w;
+      }
+      blocked = *reinterpret_cast<const unsigned*>(mask + (long)r * a.pitch + x);
+    } else {
+#pragma unroll
+      for (int k = 0; k < kQ; k++) f[0][k] = p[k * a.plane_stride];
+      blocked = mask[(long)r * a.pitch + x];
+    }
+    const unsigned cell = cell_first + (unsigned)r * (unsigned)a.nx + (unsigned)x;
+    [[maybe_unused]] float oxx[V], oxy[V], oyy[V];
+#pragma unroll
+    for (int v = 0; v < V; v++) {
+      const StressCell c = stress_cell(f[v]);
+      const bool fluid = ((blocked >> (8 * v)) & 0xffu) == 0u;
+      if constexpr (FIELD) {
+        oxx[v] = fluid ? c.txx : 0.f;
+        oxy[v] = fluid ? c.txy : 0.f;
+        oyy[v] = fluid ? c.tyy : 0.f;
+      }
+      const int s = (fluid && c.finite) ? 1 : 0;
+      lbm_exact::exact_sum_add(acc[0], __float_as_uint(c.q), s);
+      lbm_exact::exact_sum_add(acc[1], __float_as_uint(c.txy), s);
+      bad += (fluid && !c.finite) ? 1 : 0;
+      n_fluid += s;
+      const unsigned long long cell_key = lbm_stats::stats_key(__float_as_uint(c.q), cell + (unsigned)v);
+      key = (s && cell_key > key) ? cell_key : key;
+    }
+    if constexpr (FIELD) {
+      if (field) {
+        float* out = field + (long)rr * a.nx + x;
+        if constexpr (V == 4) {
+          *reinterpret_cast<float4*>(out) = make_float4(oxx[0], oxx[1], oxx[2], oxx[3]);
+          *reinterpret_cast<float4*>(out + field_stride) = make_float4(oxy[0], oxy[1], oxy[2], oxy[3]);
+          *reinterpret_cast<float4*>(out + 2 * field_stride) = make_float4(oyy[0], oyy[1], oyy[2], oyy[3]);
+        } else {
+          out[0] = oxx[0];
+          out[field_stride] = oxy[0];
+          out[2 * field_stride] = oyy[0];
+        }
+      }
+    }
+  }
+  if (!words) return;  // (uniform) the field alone
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  auto wave_total = [&](long long t, int word) {
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+    if (lane == 0) sh[wave][word] = t;
+  };
+#pragma unroll
+  for (int j = 0; j < S; j++)
+#pragma unroll
+    for (int i = 0; i < L; i++) wave_total(acc[j][i], j * L + i);
+  wave_total(bad, lbm_stress::kStressBadWord);
+  wave_total(n_fluid, lbm_stress::kStressFluidWord);
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long other = (unsigned long long)__shfl_down((long long)key, off, 64);
+    key = other > key ? other : key;
+  }
+  if (lane == 0) sh[wave][lbm_stress::kStressKeyWord] = (long long)key;
+  __syncthreads();
+  if (threadIdx.x < W) {
+    unsigned long long* word = reinterpret_cast<unsigned long long*>(words + threadIdx.x);
+    if (threadIdx.x == lbm_stress::kStressKeyWord) {
+      unsigned long long m = 0ull;
+      for (int w = 0; w < kBlock / 64; w++) m = (unsigned long long)sh[w][threadIdx.x] > m ? (unsigned long long)sh[w][threadIdx.x] : m;
+      if (m != 0ull) atomicMax(word, m);
+    } else {
+      long long t = 0;
+      for (int w = 0; w < kBlock / 64; w++) t += sh[w][threadIdx.x];
+      if (t != 0) atomicAdd(word, (unsigned long long)t);
+    }
+  }
+}
+
+// the rows [row_begin, row_begin + rows) of a slab's owned rows into `field` and / or its words of the ring row;
+// cell_first: the GLOBAL index of its first owned cell; grid: stats_groups (the host's rule) workgroups
+template <int V, bool FIELD>
+__global__ __launch_bounds__(kBlock) void stress_gather(const LatticeArgs a, int row_begin, int rows, unsigned cell_first, float* field,
+                                                        long field_stride, long long* words) {
+  stress_cells<V, FIELD>(a, a.src, a.mask, row_begin, rows, cell_first, field, field_stride, words);
+}
+
+// stress_gather's twin for a batch: one sample of every member in one launch, workgroup (g, 0, member) on the member's
+// current lattice and mask (members[member]; `a` carries the strides all members share), into the member's words of the
+// row, [members][kStressWords].  The recorder's form only, as vorticity_gather_batch: a batch member's lbm_read_stress
+// runs stress_gather<V, true> on the member's handle.
+template <int V>
+__global__ __launch_bounds__(kBlock) void stress_gather_batch(const LatticeArgs a, const ResidentMember* members, int rows, long long* row) {
+  const int member = blockIdx.z;
+  stress_cells<V, false>(a, members[member].src, members[member].mask, 0, rows, 0u, nullptr, 0,
+                         row + (size_t)member * lbm_stress::kStressWords);
 }
 
 // ---------------------------------------------------------------------------------------------
