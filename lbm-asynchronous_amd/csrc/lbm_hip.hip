@@ -1419,7 +1419,8 @@ size_t resident_gran_bytes(const lbm_ctx* c) {
 }
 
 // The forms of lbm::resident_band, [batched][recorder compiled in] x the five shapes: MAXT 1024 / 512 with two-row
-// bands, MAXT 1024 with four-row bands, MAXT 512 with four-row bands relaxed jointly or not
+// bands, MAXT 1024 with four-row bands, MAXT 512 with four-row bands relaxed jointly or not.  The shape is
+// lbm_plan::resident_form's answer (lbm_plan.h); tests/resident_forms.py names a GPU case for each of the 50 forms.
 template <bool BATCH, int REC>
 const void* resident_form(int shape) {
   switch (shape) {
@@ -1437,8 +1438,8 @@ const void* resident_kernel(int nx, int rows, int joint, int rec, bool batch = f
        resident_form<false, kRecFields>},
       {resident_form<true, kRecNone>, resident_form<true, kRecFrames>, resident_form<true, kRecProbes>, resident_form<true, kRecMean>,
        resident_form<true, kRecFields>}};
-  return forms[batch][is_gather(rec) ? kRecNone : rec](  // (the gather kinds run the plain form)
-      (rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4)));
+  // (the gather kinds run the plain form)
+  return forms[batch][is_gather(rec) ? kRecNone : rec](lbm_plan::resident_form(nx, rows, joint));
 }
 
 // what the resident kernels read of a context's recorder (a batch keeps one such entry per member); all zero while that
@@ -2713,13 +2714,16 @@ int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate alloc
     }
     if (c->plan.resident && !is_gather(kind)) {  // (the gather kinds record behind the plain form, which every resident shape runs)
       // the recorder forms of four-row bands defer the acceleration of the interior pair only (lbm::resident_band): the lid
-      // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form must run one workgroup per CU
+      // row (ny - 2) must be a band's row 2, which ny % 4 == 0 guarantees; and the form that will launch -- a batch member's
+      // is the batched one, whose field-frame forms take a register or a scratch word more than their single twins
+      // (profiles/resident_forms_resources.txt) -- must run one workgroup per CU
       if (c->plan.resident_rows == 4 && c->slab[0].accel_row % 4 != 2)
         LBM_FAIL(LBM_FAILURE, "%s: the lid row %d is not an interior row of a four-row band", setter, c->slab[0].accel_row);
       int per_cu = 0;
       HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
       HIP_TRY(LBM_FAILURE, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                               &per_cu, resident_kernel(c->p.nx, c->plan.resident_rows, c->plan.resident_joint, kind), c->p.nx * c->plan.resident_group, 0));
+                               &per_cu, resident_kernel(c->p.nx, c->plan.resident_rows, c->plan.resident_joint, kind, bt != nullptr),
+                               c->p.nx * c->plan.resident_group, 0));
       if (per_cu < 1) LBM_FAIL(LBM_FAILURE, "%s: the resident kernel's %s form does not fit a CU at this shape", setter, k.noun);
     }
   }

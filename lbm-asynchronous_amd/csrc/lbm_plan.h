@@ -517,4 +517,18 @@ inline StreamRow stream_row(const KernelPlan& pl, int k, bool exact) {
   return {ROW_STEP2_STREAM, math, pl.nts, pl.lane_cells == 2 ? 2 : 4, 2, 0, 0};
 }
 
+// ---- which shape of the resident kernel a plan launches -------------------------------------------------------------
+// lbm::resident_band<MAXT, JOINT, ROWS, BATCH, REC> is compiled in five shapes for each (BATCH, REC); lbm_hip.hip keeps
+// the instantiations (resident_form<BATCH, REC>) and indexes them with this answer; tests/plan_dump.cpp prints it
+// ("resident_form"), so which of the 50 forms a forced environment launches is known without a device
+// (tests/resident_forms.py).
+//   0  <1024, false, 2>   two-row bands, nx > 512
+//   1  <512, false, 2>    two-row bands, nx <= 512
+//   2  <1024, false, 4>   four-row bands, nx > 512
+//   3  <512, true, 4>     four-row bands, both pairs relaxed jointly (resident_joint)
+//   4  <512, false, 4>    four-row bands, the interior pair ahead of the halo wait
+inline int resident_form(int nx, int rows, int joint) {
+  return (rows == 2) ? (nx > 512 ? 0 : 1) : (nx > 512 ? 2 : (joint ? 3 : 4));
+}
+
 }  // namespace lbm_plan

@@ -1,6 +1,7 @@
 // plan_dump: prints what lbm_plan.h decides for one context, as one JSON object -- "plan" and "slabs", the fields of
 // tests/golden/kernel_plans.json, and "stream_rows", the stream-kernel instantiations an exact context with this plan
-// launches (tests/stream_rows.py).  Host arithmetic only; the LBM_* knobs come from the environment.
+// launches (tests/stream_rows.py), and "resident_form", the shape of the resident kernel it launches
+// (tests/resident_forms.py).  Host arithmetic only; the LBM_* knobs come from the environment.
 //   plan_dump nx ny world rank n_slabs halo cus n_devices distinct_devices
 // halo: 0 none, 1 device copies, 2 RCCL, 3 the host's message passing (lbm_plan::HaloKind)
 #include "../lbm-asynchronous_amd/csrc/lbm_plan.h"
@@ -55,6 +56,7 @@ int main(int argc, char** argv) {
     }
     printf("{\"family\":\"%s\",\"math\":0,\"nts\":%d,\"neigh\":%d}", p.vec4 ? "step_vec4" : "step_scalar", p.nts, p.neigh);
   }
-  printf("]}\n");
+  // the shape of lbm::resident_band a context with this plan launches (lbm_plan::resident_form), -1 without the resident kernel
+  printf("],\"resident_form\":%d}\n", p.resident ? lbm_plan::resident_form(in.nx, p.resident_rows, p.resident_joint) : -1);
   return 0;
 }

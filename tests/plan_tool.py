@@ -25,7 +25,7 @@ def build(directory) -> str:
 
 def run(exe, *, nx, ny, world=1, rank=0, n_slabs=1, halo=0, cus, n_devices=1, distinct_devices=0, env=None) -> dict:
     """One plan, in a child process whose only LBM_* variables are `env`.  Returns {"plan": {...}, "slabs": [...],
-    "stream_rows": [...]}."""
+    "stream_rows": [...], "resident_form": n}."""
     child_env = {k: v for k, v in os.environ.items() if not k.startswith("LBM_")}
     child_env.update(env or {})
     args = [nx, ny, world, rank, n_slabs, halo, cus, n_devices, int(distinct_devices)]

@@ -51,7 +51,7 @@ def cut(want_full, fields, window, p):
 
 
 RESIDENT_SHAPES = {"128x16": (128, 16, {}), "128x64-rows4": (128, 64, {"LBM_RESIDENT_ROWS": "4"}),
-                   "320x24-joint": (320, 24, {"LBM_RESIDENT_JOINT": "1"}), "1024x64": (1024, 64, {}),
+                   "320x24-rows2": (320, 24, {"LBM_RESIDENT_JOINT": "1"}), "1024x64": (1024, 64, {}),   # (JOINT is four-row only)
                    "128x128-group4": (128, 128, {"LBM_RESIDENT_ONE_XCD": "0", "LBM_RESIDENT_GROUP": "4"})}
 
 
@@ -94,9 +94,11 @@ def check_resident(lbm, case, fields, window):
 @pytest.mark.parametrize("win", ["whole", "column", "lid-row", "rows-1-2", "rows-3-4", "to-last-cell", "misses-lid-band"])
 @pytest.mark.parametrize("shape", list(RESIDENT_SHAPES))
 def test_resident_random_lattices(lbm, oracle, monkeypatch, shape, win):
-    """Bands of two and four rows, JOINT, MAXT = 1024, grouped workgroups; windows that are the whole grid, one column at
-    an odd x, the lid row, the interior pair of a four-row band, the top edge of one band and the bottom edge of the next,
-    a rectangle that ends at the last column and row, and one that misses the lid row's band."""
+    """Shapes 1, 3, 1, 0 and 1 of the resident kernel (tests/resident_forms.py): two-row bands; four-row JOINT bands (the
+    rows4 case, the only four-row one); two-row bands again at 320 x 24, where LBM_RESIDENT_JOINT=1 has no say; MAXT = 1024
+    with two-row bands; grouped workgroups.  Windows that are the whole grid, one column at an odd x, the lid row, the
+    interior pair of a four-row band, the top edge of one band and the bottom edge of the next, a rectangle that ends at
+    the last column and row, and one that misses the lid row's band.  Shapes 2 and 4: tests/test_gpu_resident_forms.py."""
     case = resident_case(lbm, oracle, monkeypatch, shape)
     nx, ny, _ = RESIDENT_SHAPES[shape]
     check_resident(lbm, case, FIELDS, resident_windows(nx, ny)[win])

@@ -75,8 +75,12 @@ def test_resident_reference_datasets(lbm, oracle, datasets, monkeypatch, name, c
                                        (128, 128, {"LBM_RESIDENT_ONE_XCD": "0", "LBM_RESIDENT_GROUP": "4"}),
                                        (128, 64, {"LBM_RESIDENT_GROUP": "2", "LBM_RESIDENT_XCD": "0"})])
 def test_resident_random_lattices(lbm, oracle, monkeypatch, nx, ny, env):
-    """Obstacles on the lid row and on the seam rows of the bands; bands of four and two rows, JOINT, one XCD and
-    grouped workgroups, seams written through everywhere."""
+    """Obstacles on the lid row and on the seam rows of the bands.  What the list launches at 256 CUs (pinned by
+    tests/test_resident_forms.py, table in tests/resident_forms.py): two-row bands everywhere but 128 x 64 with
+    LBM_RESIDENT_ROWS=4, which is the one four-row and the one JOINT case -- LBM_RESIDENT_JOINT has no say under two-row
+    bands, so 256 x 64 and 320 x 24 run <512, false, 2> like 128 x 16; both 1024-wide cases run <1024, false, 2>; one
+    XCD, grouped workgroups and seams written through are two-row cases.  The four-row forms without JOINT and at 1024
+    threads are launched by tests/test_gpu_resident_forms.py."""
     monkeypatch.setenv("LBM_RESIDENT_MIN_STEPS", "1")
     for k, v in env.items():
         monkeypatch.setenv(k, v)

@@ -62,8 +62,11 @@ def test_resident_reference_datasets(lbm, oracle, datasets, monkeypatch, name, c
                                        (128, 128, {"LBM_RESIDENT_ONE_XCD": "0", "LBM_RESIDENT_GROUP": "4"}),
                                        (128, 64, {"LBM_RESIDENT_GROUP": "2", "LBM_RESIDENT_XCD": "0"})])
 def test_resident_random_lattices(lbm, oracle, monkeypatch, nx, ny, env):
-    """Obstacles on the lid row and on the seam rows of the bands; bands of four and two rows, JOINT, one XCD and grouped
-    workgroups: every band form and both lid placements accumulate across four launches."""
+    """Obstacles on the lid row and on the seam rows of the bands; two-row bands at 512 and at 1024 threads, one XCD and
+    grouped workgroups, and -- 128 x 64 with LBM_RESIDENT_ROWS=4 only -- four-row JOINT bands (LBM_RESIDENT_JOINT has no say
+    under the two-row bands the planner prefers at these sizes; tests/resident_forms.py has the table): both lid
+    placements accumulate across four launches.  The four-row forms without JOINT and at 1024 threads:
+    tests/test_gpu_resident_forms.py."""
     monkeypatch.setenv("LBM_RESIDENT_MIN_STEPS", "1")
     for k, v in env.items():
         monkeypatch.setenv(k, v)

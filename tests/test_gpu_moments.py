@@ -73,8 +73,10 @@ def check_resident(lbm, oracle, key, p, ob, cells, calls, every):
                                        (128, 128, {"LBM_RESIDENT_ONE_XCD": "0", "LBM_RESIDENT_GROUP": "4"}),
                                        (1024, 64, {})])
 def test_resident_forms(lbm, oracle, monkeypatch, nx, ny, env):
-    """Two-row bands, four-row bands, JOINT, grouped workgroups, the 1024-thread form; obstacles on the lid row and on the
-    seam rows of the bands; four launches accumulate into the same eight planes."""
+    """Shapes 1, 3, 1, 1 and 0 of the resident kernel (tests/resident_forms.py): two-row bands, four-row JOINT bands
+    (128 x 64 with LBM_RESIDENT_ROWS=4), two-row bands again at 320 x 24 -- LBM_RESIDENT_JOINT=1 has no say there --,
+    grouped workgroups, and the 1024-thread form with two-row bands; obstacles on the lid row and on the seam rows of the
+    bands; four launches accumulate into the same eight planes.  Shapes 2 and 4: tests/test_gpu_resident_forms.py."""
     monkeypatch.setenv("LBM_RESIDENT_MIN_STEPS", "1")
     for k, v in env.items():
         monkeypatch.setenv(k, v)

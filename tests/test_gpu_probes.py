@@ -111,8 +111,10 @@ def test_resident_reference_datasets(lbm, oracle, datasets, monkeypatch, name, c
                                        (128, 128, {"LBM_RESIDENT_ONE_XCD": "0", "LBM_RESIDENT_GROUP": "4"}),
                                        (128, 64, {"LBM_RESIDENT_GROUP": "2", "LBM_RESIDENT_XCD": "0"})])
 def test_resident_random_lattices(lbm, oracle, monkeypatch, nx, ny, env):
-    """The shapes and variants of test_gpu_frames.py::test_resident_random_lattices: obstacles on the lid row and on
-    the seam rows of the bands; bands of four and two rows, JOINT, one XCD and grouped workgroups."""
+    """The shapes and variants of test_gpu_frames.py::test_resident_random_lattices, and the forms it says they launch:
+    obstacles on the lid row and on the seam rows of the bands; two-row bands (<512, false, 2> and <1024, false, 2>) but for
+    128 x 64 with LBM_RESIDENT_ROWS=4, the one four-row JOINT case; one XCD and grouped workgroups.  The other four-row
+    forms: tests/test_gpu_resident_forms.py."""
     monkeypatch.setenv("LBM_RESIDENT_MIN_STEPS", "1")
     for k, v in env.items():
         monkeypatch.setenv(k, v)
