@@ -1136,6 +1136,72 @@ int lbm_read_psi_rows(lbm_ctx* ctx, int max_rows, lbm_psi_row* out, int* steps, 
 int lbm_batch_set_psi(lbm_batch* batch, int every, int capacity);
 int lbm_batch_read_psi_rows(lbm_batch* batch, int max_rows, lbm_psi_row* out /* [n][members] */, int* steps, int* n_read);
 
+/* ---- tracer particles -------------------------------------------------------------------------
+ * Where the fluid goes: every other recorder says what happens at a cell.  n massless particles are advected on the
+ * device through the velocity field of the stored lattice, once per sample step, and their positions recorded: pathlines,
+ * streaklines, residence times, the stirring of a blob of dye, without the lattice leaving the device.
+ *
+ * A tracer is a position (x, y) in doubles, 0 <= x < nx and 0 <= y < ny; the centre of cell (i, j) lies at (i, j).
+ * u(i, j) is the pair of floats lbm_read_final_state gives at that cell for the current lattice, bit for bit (the exact
+ * arithmetic's moments; a blocked cell gives 0, 0), each widened to double.
+ *   Interpolation V(x, y): i0 = floor(x), fx = x - i0, i1 = i0 + 1, or 0 when that equals nx; j0, fy, j1 likewise in y.
+ *     Per component  a = u[j0][i0] + fx * (u[j0][i1] - u[j0][i0]),  b = u[j1][i0] + fx * (u[j1][i1] - u[j1][i0]),
+ *     v = a + fy * (b - a).  Every +, -, * is one IEEE double operation in that order; nothing is fused.
+ *   Wrap W(z, n) = z - n * floor(z / n); a result outside [0, n) (rounding: z = -1e-300 gives n) becomes 0.0.  W is total
+ *     on the finite doubles and the identity on [0, n); of a z that is not finite it is NaN.
+ *   One advance over a span of h timesteps, H = (double)h: the midpoint rule in the field of the sample step, held over
+ *     the span:  v1 = V(x, y);  xm = W(x + (0.5 * H) * v1x, nx), ym likewise;  v2 = V(xm, ym);
+ *     x' = W(x + H * v2x, nx), y' likewise.
+ *   Lost tracers: if v1, v2, xm, ym, x' or y' is not finite the tracer is lost: its position becomes (NaN, NaN) and stays
+ *     so.  No index is ever formed from a position that is not finite; a lost tracer is skipped and written through.
+ *   The span h is the number of timesteps since the previous sample, or since arming for the first sample (the rule of
+ *     lbm_residual_row.span): `every`, except for the first sample of a recorder armed between two sample steps.
+ * (csrc/lbm_tracer_step.h is this definition as code, for the kernel and for the CPU check alike; tests/tracer_model.py
+ * is its numpy model, written from the lines above.)
+ * Guidance: keep h * |u| well under one cell -- the field is held over the span and the midpoint rule is second order
+ * in h * |grad u|; every = 4 to 16 at the usual |u| <= 0.1 does that and keeps the passes at their full depth.  The
+ * velocity falls linearly to 0 at the centres of blocked cells, so a tracer at rest inside a body stays there.  Tracers
+ * seeded in row-major order (lbm_asynchronous_amd.tracer_seeds) share cache lines; a random order costs a line per cell.
+ *
+ * lbm_set_tracers(ctx, n, start, every, capacity): from now on, after global timestep tt (0-based, the numbering of
+ *   lbm_set_frames) with tt % every == 0, all n tracers advance once over the span and the row, the n positions after the
+ *   advance in the caller's order, goes into a device ring of `capacity` rows.  As with the statistics every call runs as
+ *   the sub-calls that end at its sample steps, each followed by ONE tracer_advance launch, a lane per tracer, which reads
+ *   the current lattice directly (two dependent gathers of 4 cells x 9 populations and 4 mask bytes) and updates the
+ *   positions in place; no step kernel knows of it, and the lattice and av_vels equal those of the same run issued as
+ *   calls split at the sample steps.  capacity == 0 arms WITHOUT a ring: nothing is recorded, no run lacks room,
+ *   lbm_read_tracers refuses and the positions come from lbm_tracers_now -- for a cloud of many tracers read once at the
+ *   end.  every == 0 or n == 0 disarms and frees; re-arming discards the positions and the rows.
+ *   Refused, before anything is released: negative every or capacity; n outside 0 .. LBM_MAX_TRACERS; a NULL start; a
+ *   context of more than one slab (a tracer's four cells can straddle two slabs, and a slab's lattice halo rows are not
+ *   current after a pass); a ring of 2 GiB or more; rank contexts (lbm_create_rank*); batch members (a batch arms them
+ *   as a whole: lbm_batch_set_tracers); a start position that is not finite or lies outside the grid (the first such
+ *   index is named); LBM_HALO_STALE / LBM_HALO_FRESHEST (and lbm_set_halo_mode to those while armed); a context with
+ *   another recorder armed (and the other setters while this one is armed); lbm_run_until and lbm_run_until_residual
+ *   while armed.  Not offered: several slabs, rank contexts, the double engine, finite-size or inertial particles,
+ *   unwrapped coordinates, seeding during a run.
+ * lbm_read_tracers: drains up to max_rows oldest rows into out[n_read][n] and steps[n_read] (their tt, may be NULL);
+ *   out == NULL && steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers.
+ * lbm_tracers_now: the current positions, out[n]: those of the last sample (of arming before the first).  Drains nothing;
+ *   synchronises like the readers.
+ * lbm_batch_set_tracers / lbm_batch_read_tracers / lbm_batch_tracers_now: the same for every member of a batch, n tracers
+ *   each, armed on the BATCH with one `every` and ONE ring [slots][members][n]; start and the positions are [members][n],
+ *   rows out[n_read][members][n].  Behind each sub-call that ends at a sample step the batch's stream gets ONE
+ *   tracer_advance_batch launch for all members (grid z is the member).  Member i's rows, lattice and av_vels are
+ *   bit-identical to those of an lbm_create context armed with lbm_set_tracers and advanced by the same calls.  Refused
+ *   as lbm_batch_set_stress refuses, and what lbm_set_tracers refuses of n, start and the ring.
+ */
+#define LBM_MAX_TRACERS (1 << 24)
+typedef struct {
+  double x, y;
+} lbm_tracer;             /* 16 bytes */
+int lbm_set_tracers(lbm_ctx* ctx, int n, const lbm_tracer* start /* [n] */, int every, int capacity);
+int lbm_read_tracers(lbm_ctx* ctx, int max_rows, lbm_tracer* out /* [rows][n] */, int* steps, int* n_read);
+int lbm_tracers_now(lbm_ctx* ctx, lbm_tracer* out /* [n] */);
+int lbm_batch_set_tracers(lbm_batch* batch, int n, const lbm_tracer* start /* [members][n] */, int every, int capacity);
+int lbm_batch_read_tracers(lbm_batch* batch, int max_rows, lbm_tracer* out /* [rows][members][n] */, int* steps, int* n_read);
+int lbm_batch_tracers_now(lbm_batch* batch, lbm_tracer* out /* [members][n] */);
+
 /* ---- double precision -----------------------------------------------------------------------
  * The reference's programs are `float`, but its published golden results (the .dat files of check/) are its algorithm evaluated in
  * IEEE double.  A double context computes exactly that: the driver loop of SerialCode/d2q9-bgk.c:166-170 with every

@@ -61,6 +61,7 @@ ABI_SYMBOLS = (
     "lbm_read_vorticity", "lbm_set_enstrophy", "lbm_read_enstrophy", "lbm_batch_set_enstrophy", "lbm_batch_read_enstrophy",
     "lbm_read_psi", "lbm_set_psi", "lbm_read_psi_rows", "lbm_batch_set_psi", "lbm_batch_read_psi_rows",
     "lbm_read_stress", "lbm_set_stress", "lbm_read_stress_rows", "lbm_batch_set_stress", "lbm_batch_read_stress_rows",
+    "lbm_set_tracers", "lbm_read_tracers", "lbm_tracers_now", "lbm_batch_set_tracers", "lbm_batch_read_tracers", "lbm_batch_tracers_now",
     "lbm_double_create", "lbm_double_destroy", "lbm_double_get_info", "lbm_double_run", "lbm_double_run_timed",
     "lbm_double_sync", "lbm_double_read_av_vels", "lbm_double_read_cells", "lbm_double_read_final_state",
     "lbm_double_av_velocity", "lbm_double_total_density", "lbm_double_calc_reynolds",
@@ -298,6 +299,12 @@ def load_library() -> ctypes.CDLL:
     lib.lbm_read_stress_rows.argtypes = [P, I, P, P, PI]; lib.lbm_read_stress_rows.restype = I
     lib.lbm_batch_set_stress.argtypes = [P, I, I]; lib.lbm_batch_set_stress.restype = I
     lib.lbm_batch_read_stress_rows.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_stress_rows.restype = I
+    lib.lbm_set_tracers.argtypes = [P, I, P, I, I]; lib.lbm_set_tracers.restype = I
+    lib.lbm_read_tracers.argtypes = [P, I, P, P, PI]; lib.lbm_read_tracers.restype = I
+    lib.lbm_tracers_now.argtypes = [P, P]; lib.lbm_tracers_now.restype = I
+    lib.lbm_batch_set_tracers.argtypes = [P, I, P, I, I]; lib.lbm_batch_set_tracers.restype = I
+    lib.lbm_batch_read_tracers.argtypes = [P, I, P, P, PI]; lib.lbm_batch_read_tracers.restype = I
+    lib.lbm_batch_tracers_now.argtypes = [P, P]; lib.lbm_batch_tracers_now.restype = I
     lib.lbm_read_psi.argtypes = [P, P]; lib.lbm_read_psi.restype = I
     lib.lbm_set_psi.argtypes = [P, I, I]; lib.lbm_set_psi.restype = I
     lib.lbm_read_psi_rows.argtypes = [P, I, P, P, PI]; lib.lbm_read_psi_rows.restype = I
@@ -791,6 +798,28 @@ class Engine:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], STRESS_DTYPE[n])."""
         return _drain_rows(self.lib.lbm_read_stress_rows, self.lib, self.handle, "stress_rows", max_rows, (), STRESS_DTYPE, np.zeros)
 
+    # -- tracer particles (lbm_set_tracers / lbm_read_tracers / lbm_tracers_now) ----------------------
+    def set_tracers(self, xy, every: int, capacity: int = 0) -> None:
+        """Advect the tracers `xy`, float64 (n, 2) positions (x, y) with 0 <= x < nx and 0 <= y < ny (a cell's centre is
+        its index), through the velocity field on the device: after every global timestep tt with tt % every == 0 each
+        advances once by the midpoint rule over the steps since the last sample, and the row of all positions goes into a
+        device ring of `capacity` rows.  capacity == 0 (the default) keeps no rows: tracers() gives the positions.
+        every == 0 or no tracers disarms; re-arming discards positions and rows.  tracer_seeds() makes a regular cloud."""
+        xy, every, capacity = _tracer_args("set_tracers", xy, (), every, capacity)
+        _check(self.lib, self.lib.lbm_set_tracers(self.handle, xy.shape[0], xy.ctypes.data, every, capacity))
+        self._n_tracers = xy.shape[0] if every > 0 else 0
+
+    def tracer_rows(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[rows], float64[rows, n, 2])."""
+        return _drain_rows(self.lib.lbm_read_tracers, self.lib, self.handle, "tracer_rows", max_rows, (getattr(self, "_n_tracers", 0), 2),
+                           np.float64, np.zeros)
+
+    def tracers(self) -> np.ndarray:
+        """The tracers' current positions, float64 (n, 2): those of the last sample.  Drains nothing."""
+        out = np.empty((getattr(self, "_n_tracers", 0), 2), dtype=np.float64)
+        _check(self.lib, self.lib.lbm_tracers_now(self.handle, out.ctypes.data))
+        return out
+
     # -- stream function (lbm_read_psi / lbm_set_psi / lbm_read_psi_rows) ----------------------------
     def psi(self) -> np.ndarray:
         """The mass stream function of the current lattice, float64 (row_count, nx): psi[y, x] = the exact sum of j_x over
@@ -1165,6 +1194,26 @@ class Batch:
         """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[n], STRESS_DTYPE[n, members])."""
         return _drain_rows(self.lib.lbm_batch_read_stress_rows, self.lib, self._live(), "stress_rows", max_rows, (len(self),),
                            STRESS_DTYPE, np.zeros)
+
+    # -- tracer particles of all members (lbm_batch_set_tracers / lbm_batch_read_tracers / lbm_batch_tracers_now) ------------
+    def set_tracers(self, xy, every: int, capacity: int = 0) -> None:
+        """Engine.set_tracers for every member at once: `xy` is float64 (members, n, 2), n tracers per member; one `every`
+        and `capacity` for the batch, rows in one device ring, one launch per sample whatever the number of members.
+        every == 0 or n == 0 disarms."""
+        xy, every, capacity = _tracer_args("set_tracers", xy, (len(self),), every, capacity)
+        _check(self.lib, self.lib.lbm_batch_set_tracers(self._live(), xy.shape[1], xy.ctypes.data, every, capacity))
+        self._n_tracers = xy.shape[1] if every > 0 else 0
+
+    def tracer_rows(self, max_rows: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Drain up to max_rows (default: all) waiting rows, oldest first: (steps int32[rows], float64[rows, members, n, 2])."""
+        return _drain_rows(self.lib.lbm_batch_read_tracers, self.lib, self._live(), "tracer_rows", max_rows,
+                           (len(self), getattr(self, "_n_tracers", 0), 2), np.float64, np.zeros)
+
+    def tracers(self) -> np.ndarray:
+        """Every member's tracers' current positions, float64 (members, n, 2).  Drains nothing."""
+        out = np.empty((len(self), getattr(self, "_n_tracers", 0), 2), dtype=np.float64)
+        _check(self.lib, self.lib.lbm_batch_tracers_now(self._live(), out.ctypes.data))
+        return out
 
     # -- stream function of all members (lbm_batch_set_psi / lbm_batch_read_psi_rows) ---------------------------------------
     def set_psi(self, every: int, capacity: int = 4096) -> None:
@@ -1558,6 +1607,50 @@ def write_stress_rows(path: str, steps, rows) -> None:
             fh.write("%d:\t%.12E\t%.12E\t%.12E\t%d\t%d\t%d\t%d\n" % (
                 tt, float(r["sum_q"]), float(r["sum_txy"]), float(r["max_q"]), int(r["max_x"]), int(r["max_y"]),
                 int(r["fluid"]), int(r["nonfinite"])))
+
+
+def _tracer_args(setter, xy, lead, every, capacity) -> tuple[np.ndarray, int, int]:
+    """set_tracers' argument checks (no device needed): `xy` real numbers of shape lead + (n, 2), as contiguous float64;
+    capacity 0 is allowed (no ring).  The library refuses positions outside the grid."""
+    every, capacity = _every_capacity(setter, every, capacity, None)
+    xy = np.asarray(xy)
+    if xy.dtype.kind not in "fiu":
+        raise LbmError(f"{setter}: xy must hold real numbers (got dtype {xy.dtype})")
+    if xy.ndim != len(lead) + 2 or xy.shape[:len(lead)] != tuple(lead) or xy.shape[-1] != 2:
+        want = "(" + ", ".join([str(m) for m in lead] + ["n", "2"]) + ")"
+        raise LbmError(f"{setter}: xy must have shape {want}: positions (x, y) (got shape {xy.shape})")
+    if xy.shape[-2] > MAX_TRACERS:
+        raise LbmError(f"{setter}: {xy.shape[-2]} tracers, at most LBM_MAX_TRACERS = {MAX_TRACERS} are possible")
+    return np.ascontiguousarray(xy, dtype=np.float64), every, capacity
+
+
+MAX_TRACERS = 1 << 24    # LBM_MAX_TRACERS of include/lbm_hip.h
+
+
+def write_tracers(path: str, steps, rows) -> None:
+    """One line per row in write_stress_rows' style: tt, a colon, then tab-separated x and y of every tracer in the
+    caller's order as '%.17E' (every double survives; a lost tracer reads NAN); `steps` int[rows], `rows`
+    float64[rows, n, 2] (Engine.tracer_rows)."""
+    rows = np.asarray(rows)
+    steps = np.asarray(steps).ravel()
+    if rows.dtype != np.float64 or rows.ndim != 3 or rows.shape[0] != steps.size or rows.shape[2] != 2:
+        raise LbmError(f"write_tracers: rows must be float64 of shape ({steps.size}, n, 2) (got shape {rows.shape}, dtype {rows.dtype})")
+    with open(path, "w") as fh:
+        for tt, r in zip(steps.tolist(), rows):
+            fh.write("%d:" % tt + "".join("\t%.17E\t%.17E" % (float(x), float(y)) for x, y in r) + "\n")
+
+
+def tracer_seeds(obstacles, spacing: int) -> np.ndarray:
+    """Start positions for set_tracers, float64 (n, 2): the centres (x, y) of the fluid cells among every `spacing`-th cell
+    of every `spacing`-th row of the map `obstacles` (ny, nx), row-major.  In this order neighbouring tracers read
+    neighbouring cells, which the kernel's loads then share; a shuffled cloud costs a cache line per cell."""
+    if isinstance(spacing, bool) or not isinstance(spacing, (int, np.integer)) or spacing < 1:
+        raise LbmError(f"tracer_seeds: spacing must be a positive integer (got {spacing!r})")
+    ob = np.asarray(obstacles)
+    if ob.ndim != 2:
+        raise LbmError(f"tracer_seeds: obstacles must be a map of shape (ny, nx) (got shape {ob.shape})")
+    ys, xs = np.nonzero(ob[::spacing, ::spacing] == 0)
+    return np.stack([xs * int(spacing), ys * int(spacing)], axis=1).astype(np.float64)
 
 
 def _strain_factor(who: str, omega) -> float:

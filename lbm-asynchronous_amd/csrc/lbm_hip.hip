@@ -267,6 +267,7 @@ struct Slab {
   DeviceBuf<long long> psi_in, psi_out;    // ... several slabs: [nx][kExactLimbs]: the limbs of every column below this slab (a copy of
                                            // the slab below's psi_out) and up to its last row
   Event ev_psi_out, ev_psi_taken;          // ... psi_out is written / the slab above has copied it
+  DeviceBuf<lbm_tracer> tracer_state;      // lbm_set_tracers: [n]: the tracers' current positions, advanced in place at every sample
   // freshest-available mode (LBM_HALO_FRESHEST), allocated at its first use in this order: whole once ev_fresh[1] exists
   DeviceBuf<float> fresh_stage;          // [parity][side: 0 south halo, 1 north halo][row_pitch]: this pass's rows, if they make it
   DeviceBuf<unsigned> fresh_arrived;     // [parity][side]: id (global step + 1) of the step whose row the staging holds
@@ -427,11 +428,13 @@ struct GraphBuilder {
 // Coarse frames (lbm_set_coarse_frames) likewise, by coarse_gather: a frame of per-box sums, rounded on the device except
 // in the box rows that two slabs share.
 // The stress (lbm_set_stress) likewise, by stress_gather: a row of whole-lattice sums of the second moment, pointwise.
-// These eight gather kinds share one ring of int64 words per slab, Slab::gather_ring; a batch arms them on itself
+// Tracer particles (lbm_set_tracers) likewise, by tracer_advance: a row of positions, the one kind whose state (the positions)
+// persists between samples and whose ring may have no slots (capacity 0: the positions are read with lbm_tracers_now).
+// These nine gather kinds share one ring of int64 words per slab, Slab::gather_ring; a batch arms them on itself
 // (lbm_batch::rec) with one ring for all members.  What a gather kind is stands in one place, its entry of kGatherKinds.
 enum { kRecNone = lbm::kRecNone, kRecFrames = lbm::kRecFrames, kRecProbes = lbm::kRecProbes, kRecMean = lbm::kRecMean,
        kRecFields = lbm::kRecFields, kRecForces = 5, kRecStats = 6, kRecResidual = 7, kRecProfiles = 8, kRecEnstrophy = 9,
-       kRecPsi = 10, kRecCoarse = 11, kRecStress = 12, kRecKinds = 13, kRecGatherFirst = kRecForces };
+       kRecPsi = 10, kRecCoarse = 11, kRecStress = 12, kRecTracers = 13, kRecKinds = 14, kRecGatherFirst = kRecForces };
 // the kinds recorded by a gather launch behind the sub-call that ends at a sample step, whatever kernels advance the lattice
 constexpr bool is_gather(int kind) { return kind >= kRecGatherFirst && kind < kRecKinds; }
 // what a gather kind was armed with: the arguments of its setter that its slot's size, its launches and its reader depend on
@@ -439,12 +442,13 @@ struct GatherArgs {
   int bodies = 0;            // obstacle forces: bodies of the context, or of every member
   int axes = 0;              // line profiles: the LBM_PROFILE_* bits
   int box_x = 0, box_y = 0;  // coarse frames: the box's sides, cells
-  int base_steps = 0;        // steps_done at arming: the step of the residuals' baseline (the first row's span)
+  int tracers = 0;           // tracer particles: tracers of the context, or of every member
+  int base_steps = 0;        // steps_done at arming: the step of the residuals' baseline (the first row's span); the tracers' likewise
 };
 struct Recorder {
   int kind = kRecNone;
   int every = 0;
-  int slots = 0;
+  int slots = 0;            // (0 while armed: a gather kind armed without a ring, GatherKind::ringless)
   int ord0 = 0;             // tt / every of the first record after arming
   long long written = 0;    // records issued since arming (ordinals 0 .. written - 1) ...
   long long read = 0;       // ... and drained by the kind's reader
@@ -487,7 +491,7 @@ struct GatherOwner {
 // A hook that allocates answers LBM_SUCCESS, LBM_FAILURE (it has said why) or kNoRoom: the driver then says that the ring
 // and `also` could not be allocated.
 constexpr int kNoRoom = 2;
-// One gather kind: everything that differs between the eight, for a context and for a batch.  The drivers (arm_gather,
+// One gather kind: everything that differs between the nine, for a context and for a batch.  The drivers (arm_gather,
 // arm_batch_gather, drain_gather, drain_batch_gather, take_record, lbm_batch_run) know no kind.
 struct GatherKind {
   RecorderKind ctx;          // the words of a context's messages ...
@@ -500,6 +504,7 @@ struct GatherKind {
   const char* of = "";       // "cannot allocate 4 rows<of> ...", a format of args.bodies
   const char* also = "";     // "... (1.0 MiB per slab)<also>": what the kind's hook allocates besides, where kNoRoom tells of it
   bool per_slab = false;     // the slot's size depends on the slab: the messages name the slab
+  bool ringless = false;     // capacity 0 arms the kind without a ring: its records go nowhere, no call lacks room, its reader refuses
   // int64 words of one slab's (or member's) slot
   size_t (*slot_words)(const lbm_ctx* c, const Slab& sl, const GatherArgs& a);
   // refuses the kind's own arguments, or nothing (nullptr); members: of the batch that arms, 0: a context does
@@ -588,7 +593,7 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentProbes> probe_table;  // device: [members], allocated when the first member arms probes
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
   DeviceBuf<lbm::ResidentFields> field_table;  // device: [members], allocated when the first member arms field frames
-  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
+  int armed[kRecKinds] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // members with a recorder of each kind armed: batched launches run that kind's kernel
                                     // (a batch records one kind, so at most one count is non-zero; a gather kind is armed
                                     // on the batch, by its lbm_batch_set_*, and counts as one)
   // the gather kinds (kGatherKinds) of all members: the members' own recorders stay off, the batch keeps the one
@@ -597,6 +602,7 @@ struct lbm_batch {
   Recorder rec;                                  // a gather kind while armed
   DeviceBuf<long long> gather_ring;              // device: [slots][members][the kind's slot_words of a member]
   DeviceBuf<float> residual_planes;              // lbm_batch_set_residual: device: [members][2][rows][nx]: the members' remembered u_x and u_y
+  DeviceBuf<lbm_tracer> tracer_state;            // lbm_batch_set_tracers: device: [members][n]: the members' tracers' current positions
   DeviceBuf<long long> psi_totals;               // lbm_batch_set_psi: device: [members][bands][nx][kExactLimbs]: the scan's totals, then bases
   DeviceBuf<lbm::PsiCandidate> psi_cand;         // ... [members][bands][column groups]
   int psi_band_rows = 0;                         // ... rows of a band of every member's scan
@@ -1619,7 +1625,7 @@ long long recorded_between(const Recorder& r, long long from, long long to) {
 // that accumulates its records (the mean fields) has room for any call
 int recorder_fits(const Recorder& r, int steps_done, int n_steps, const char* who, const char* reader) {
   const RecorderKind& k = kind_words(r.kind);
-  if (!k.slotted) return LBM_SUCCESS;
+  if (!k.slotted || r.slots == 0) return LBM_SUCCESS;  // (no slots: a gather kind armed without a ring)
   const long long add = recorded_between(r, steps_done, (long long)steps_done + n_steps);
   const long long waiting = r.written - r.read;
   if (waiting + add > r.slots)
@@ -1842,7 +1848,7 @@ void launch_psi_bases(const lbm_ctx* c, const Slab& sl, int band_rows, long long
 // psi_in, forms its bases and its psi_out, scans and reduces.  Slab s-1's next sample overwrites its psi_out only behind
 // slab s's copy (ev_psi_taken).  Issued by the calling thread, slab after slab: the chain has an order.
 size_t gather_slot_words(const lbm_ctx* c, const Slab& sl);
-long long* zeroed_slot(long long* ring, size_t slot_words, const Recorder& r, hipStream_t stream);
+long long* zeroed_slot(long long* ring, size_t slot_words, const Recorder& r, hipStream_t stream, bool* ringless);
 int take_psi_record(lbm_ctx* c) {
   const int nx = c->p.nx;
   const size_t base_bytes = (size_t)nx * lbm_exact::kExactLimbs * sizeof(long long);
@@ -1850,7 +1856,8 @@ int take_psi_record(lbm_ctx* c) {
   for (int s = 0; s < c->n_slabs; s++) {
     Slab& sl = c->slab[s];
     HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-    if (!(words[s] = zeroed_slot(sl.gather_ring, gather_slot_words(c, sl), c->rec, sl.compute))) return LBM_FAILURE;
+    bool ringless;
+    if (!(words[s] = zeroed_slot(sl.gather_ring, gather_slot_words(c, sl), c->rec, sl.compute, &ringless))) return LBM_FAILURE;
     launch_psi_totals(c, sl, sl.psi_band_rows, sl.psi_totals);
     HIP_TRY(LBM_FAILURE, hipGetLastError());
   }
@@ -1891,7 +1898,9 @@ size_t gather_slot_words(const lbm_batch* bt) {
 }
 
 // the slot of the next record of a gather ring, zeroed on `stream` (the gather kernels add into it): nullptr where that failed
-long long* zeroed_slot(long long* ring, size_t slot_words, const Recorder& r, hipStream_t stream) {
+// -- and where the kind is armed without a ring (*ringless: nullptr is then no failure; the kind's launch records nowhere)
+long long* zeroed_slot(long long* ring, size_t slot_words, const Recorder& r, hipStream_t stream, bool* ringless) {
+  if ((*ringless = r.slots == 0)) return nullptr;
   long long* slot = ring + (size_t)(r.written % r.slots) * slot_words;
   HIP_TRY(nullptr, hipMemsetAsync(slot, 0, slot_words * sizeof(long long), stream));
   return slot;
@@ -2678,6 +2687,7 @@ void release_recorder(lbm_ctx* c) {
     sl.psi_in.reset();
     sl.psi_out.reset();
     sl.psi_band_rows = 0;
+    sl.tracer_state.reset();
     sl.probe_count = 0;
   }
   c->probe_cells.clear();
@@ -2761,6 +2771,8 @@ int rearm_recorder(lbm_ctx* c, int kind, int every, int capacity, Allocate alloc
 template <class Copy>
 int drain_ring(Recorder& r, int kind, const char* reader, int max_records, bool has_out, int* steps, int* n_read, Copy copy) {
   const RecorderKind& k = kind_words(kind);
+  if (r.kind == kind && r.slots == 0)
+    LBM_FAIL(LBM_FAILURE, "%s: %s are armed without a ring (capacity 0): no %s is recorded", reader, k.name, k.record);
   const long long waiting = (r.kind == kind) ? r.written - r.read : 0;
   if (!has_out && !steps) {
     *n_read = (int)waiting;
@@ -2844,6 +2856,7 @@ void release_batch_recorder(lbm_batch* bt) {
   bt->psi_totals.reset();
   bt->psi_cand.reset();
   bt->psi_band_rows = 0;
+  bt->tracer_state.reset();
   bt->force_lists.reset();
   bt->force_links.clear();
   bt->force_starts.clear();
@@ -3268,8 +3281,9 @@ int take_per_slab(lbm_ctx* c) {
   return for_slabs(c, [&](int s) -> int {
     Slab& sl = c->slab[s];
     HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-    long long* words = zeroed_slot(sl.gather_ring, gather_slot_words(c, sl), c->rec, sl.compute);
-    if (!words || k.launch(c, s, words) != LBM_SUCCESS) return LBM_FAILURE;
+    bool ringless;
+    long long* words = zeroed_slot(sl.gather_ring, gather_slot_words(c, sl), c->rec, sl.compute, &ringless);
+    if ((!words && !ringless) || k.launch(c, s, words) != LBM_SUCCESS) return LBM_FAILURE;
     HIP_TRY(LBM_FAILURE, hipGetLastError());
     return LBM_SUCCESS;
   });
@@ -3375,6 +3389,70 @@ void coarse_frames_rows(const GatherOwner& g, const Recorder& r, int n, const lo
                                         static_cast<lbm_profile_line*>(out) + j * boxes);
 }
 
+// ---- tracer particles: the one kind with state between its samples -------------------------------------------------------
+size_t tracers_slot_words(const lbm_ctx*, const Slab&, const GatherArgs& a) { return 2 * (size_t)a.tracers; }  // a position: two doubles
+int check_tracers(const char* who, const lbm_ctx* c, size_t, int, const GatherArgs& a) {
+  if (a.tracers < 1 || a.tracers > LBM_MAX_TRACERS)
+    LBM_FAIL(LBM_FAILURE, "%s: %d tracers, between 0 (none: disarms) and LBM_MAX_TRACERS = %d are possible", who, a.tracers, LBM_MAX_TRACERS);
+  if (c->n_slabs > 1)
+    LBM_FAIL(LBM_FAILURE, "%s: the context has %d slabs; a tracer's four cells can straddle two slabs, and a slab's lattice halo rows are "
+             "not current after a pass: tracers need a context of one slab", who, c->n_slabs);
+  return LBM_SUCCESS;
+}
+// what the setters refuse of the start positions, `lattices` x n of them, once nothing else is refused
+int tracer_starts_ok(const char* who, const lbm_ctx* c, size_t lattices, int n, const lbm_tracer* start) {
+  if (!start) LBM_FAIL(LBM_FAILURE, "%s: NULL start positions", who);
+  for (size_t i = 0; i < lattices * (size_t)n; i++) {
+    const lbm_tracer& t = start[i];
+    if (std::isfinite(t.x) && std::isfinite(t.y) && t.x >= 0.0 && t.x < (double)c->p.nx && t.y >= 0.0 && t.y < (double)c->p.ny) continue;
+    char of[32] = "";
+    if (lattices > 1) snprintf(of, sizeof(of), " of member %d", (int)(i / (size_t)n));
+    LBM_FAIL(LBM_FAILURE, "%s: tracer %d%s starts at (%g, %g), not a finite position with 0 <= x < %d and 0 <= y < %d", who, (int)(i % (size_t)n),
+             of, t.x, t.y, c->p.nx, c->p.ny);
+  }
+  return LBM_SUCCESS;
+}
+// the positions, set to the caller's start (own)
+int alloc_tracers_slab(const char* who, lbm_ctx* c, int s, const GatherArgs& a, const void* own) {
+  Slab& sl = c->slab[s];
+  if (sl.tracer_state.alloc((size_t)a.tracers) != hipSuccess)
+    LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the positions of %d tracers (%.1f MiB); tracers stay off", who, a.tracers,
+             (double)a.tracers * sizeof(lbm_tracer) / 1048576.0);
+  HIP_TRY(LBM_FAILURE, hipMemcpy(sl.tracer_state, own, (size_t)a.tracers * sizeof(lbm_tracer), hipMemcpyHostToDevice));
+  return LBM_SUCCESS;
+}
+int alloc_tracers_batch(const char* who, lbm_batch* bt, const GatherArgs& a, const void* own) {
+  const size_t all = bt->members.size() * (size_t)a.tracers;
+  if (bt->tracer_state.alloc(all) != hipSuccess)
+    LBM_FAIL(LBM_FAILURE, "%s: cannot allocate the positions of %d members' %d tracers (%.1f MiB); tracers stay off", who, (int)bt->members.size(),
+             a.tracers, (double)all * sizeof(lbm_tracer) / 1048576.0);
+  HIP_TRY(LBM_FAILURE, hipMemcpy(bt->tracer_state, own, all * sizeof(lbm_tracer), hipMemcpyHostToDevice));
+  return LBM_SUCCESS;
+}
+// one advance of all tracers over the span that ends at this sample (residual_span: the record about to be written), the
+// row into `words` (null: armed without a ring)
+int launch_tracers(lbm_ctx* c, int s, long long* words) {
+  const Slab& sl = c->slab[s];
+  const int n = c->rec.args.tracers;
+  hipLaunchKernelGGL(lbm::tracer_advance, dim3(ceil_div(n, lbm::kBlock)), dim3(lbm::kBlock), 0, sl.compute, lattice_args(c, sl), c->p.ny, n,
+                     residual_span(c->rec, c->rec.written), reinterpret_cast<double2*>(sl.tracer_state.get()), reinterpret_cast<double2*>(words));
+  return LBM_SUCCESS;
+}
+int take_batch_tracers(lbm_batch* bt, long long* row) {
+  lbm_ctx* c0 = bt->members[0];
+  const size_t n_members = bt->members.size();
+  const int n = bt->rec.args.tracers;
+  hipLaunchKernelGGL(lbm::tracer_advance_batch, dim3(ceil_div(n, lbm::kBlock), 1, (unsigned)n_members), dim3(lbm::kBlock), 0, bt->stream,
+                     lattice_args(c0, c0->slab[0]), (const lbm::ResidentMember*)(bt->table + (size_t)bt->cur * n_members), c0->p.ny, n,
+                     residual_span(bt->rec, bt->rec.written), reinterpret_cast<double2*>(bt->tracer_state.get()), reinterpret_cast<double2*>(row));
+  HIP_TRY(LBM_FAILURE, hipGetLastError());
+  return LBM_SUCCESS;
+}
+// a row's words are its doubles
+void tracers_rows(const GatherOwner& g, const Recorder&, int n, const long long* words, void* out) {
+  memcpy(out, words, (size_t)n * g.lattices * g.lattice_words * sizeof(long long));
+}
+
 // ---- the table ---------------------------------------------------------------------------------------------------------
 // To add a gather kind: its number in front of kRecKinds, its entry here, its hooks above, and its entry points, which pack
 // their arguments into GatherArgs and call arm_gather / drain_gather (arm_batch_gather / drain_batch_gather).
@@ -3431,7 +3509,13 @@ const GatherKind kGatherKinds[kRecKinds - kRecGatherFirst] = {
      .stays_off = "the stress stays off", .spread = "a row's sums", .of_a_batch = "the stress of a batch is",
      .slot_words = fixed_slot_words<lbm_stress::kStressWords>,
      .take = take_per_slab, .launch = launch_stress, .take_batch = take_batch_stress,
-     .rows = rows_merged<lbm_stress_row, lbm_stress::stress_row_from_words>}};
+     .rows = rows_merged<lbm_stress_row, lbm_stress::stress_row_from_words>},
+    {.ctx = {.name = "tracer particles", .noun = "tracers", .record = "row", .setter = "lbm_set_tracers", .reader = "lbm_read_tracers",
+             .disarm = "lbm_set_tracers(ctx, 0, NULL, 0, 0)"},
+     .batch_setter = "lbm_batch_set_tracers", .batch_reader = "lbm_batch_read_tracers", .batch_disarm = "lbm_batch_set_tracers(batch, 0, NULL, 0, 0)",
+     .stays_off = "tracers stay off", .spread = "a tracer's cells", .of_a_batch = "the tracers of a batch are", .ringless = true,
+     .slot_words = tracers_slot_words, .check = check_tracers, .alloc_slab = alloc_tracers_slab, .alloc_batch = alloc_tracers_batch,
+     .take = take_per_slab, .launch = launch_tracers, .take_batch = take_batch_tracers, .rows = tracers_rows}};
 const GatherKind& gather_kind(int kind) { return kGatherKinds[kind - kRecGatherFirst]; }
 const RecorderKind& kind_words(int kind) { return is_gather(kind) ? gather_kind(kind).ctx : kRecorderKinds[kind]; }
 
@@ -3449,7 +3533,8 @@ int gather_refusals(lbm_ctx* c, int kind, int every, int capacity, const GatherA
   if (!c) LBM_FAIL(LBM_FAILURE, "%s: null context", who);
   if (every < 0) LBM_FAIL(LBM_FAILURE, "%s: negative interval %d", who, every);
   if (every == 0) return LBM_SUCCESS;
-  if (capacity < 1) LBM_FAIL(LBM_FAILURE, "%s: capacity %d, at least one %s is needed", who, capacity, k.ctx.record);
+  if (k.ringless && capacity < 0) LBM_FAIL(LBM_FAILURE, "%s: negative capacity %d (0: no ring)", who, capacity);
+  if (!k.ringless && capacity < 1) LBM_FAIL(LBM_FAILURE, "%s: capacity %d, at least one %s is needed", who, capacity, k.ctx.record);
   if (k.check && k.check(who, c, 0, capacity, a) != LBM_SUCCESS) return LBM_FAILURE;
   for (int s = 0; s < c->n_slabs; s++) {
     const long long slot_bytes = (long long)(k.slot_words(c, c->slab[s], a) * sizeof(long long));
@@ -3473,7 +3558,7 @@ int arm_gather_checked(lbm_ctx* c, int kind, int every, int capacity, GatherArgs
       Slab& sl = c->slab[s];
       const size_t ring_bytes = (size_t)capacity * k.slot_words(c, sl, a) * sizeof(long long);
       HIP_TRY(LBM_FAILURE, hipSetDevice(sl.device));
-      int rc = sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess ? kNoRoom : k.alloc_slab ? k.alloc_slab(who, c, s, a, own) : LBM_SUCCESS;
+      int rc = ring_bytes && sl.gather_ring.alloc_bytes(ring_bytes) != hipSuccess ? kNoRoom : k.alloc_slab ? k.alloc_slab(who, c, s, a, own) : LBM_SUCCESS;
       if (rc == kNoRoom) {
         char where[32] = "per slab";
         if (k.per_slab) snprintf(where, sizeof(where), "for slab %d", s);
@@ -3522,7 +3607,8 @@ int batch_gather_refusals(lbm_batch* bt, int kind, int every, int capacity, cons
   }
   const lbm_ctx* c0 = bt->members[0];
   const size_t n_members = bt->members.size();
-  if (capacity < 1) LBM_FAIL(LBM_FAILURE, "%s: capacity %d, at least one %s is needed", who, capacity, k.ctx.record);
+  if (k.ringless && capacity < 0) LBM_FAIL(LBM_FAILURE, "%s: negative capacity %d (0: no ring)", who, capacity);
+  if (!k.ringless && capacity < 1) LBM_FAIL(LBM_FAILURE, "%s: capacity %d, at least one %s is needed", who, capacity, k.ctx.record);
   if (k.check && k.check(who, c0, n_members, capacity, a) != LBM_SUCCESS) return LBM_FAILURE;
   const size_t member_bytes = k.slot_words(c0, c0->slab[0], a) * sizeof(long long), record_bytes = n_members * member_bytes;
   if ((long long)capacity * (long long)record_bytes >= (1LL << 31))
@@ -3546,7 +3632,7 @@ int arm_batch_gather_checked(lbm_batch* bt, int kind, int every, int capacity, G
     const lbm_ctx* c0 = bt->members[0];
     const size_t n_members = bt->members.size();
     const size_t ring_bytes = (size_t)capacity * n_members * k.slot_words(c0, c0->slab[0], a) * sizeof(long long);
-    const int rc = bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess ? kNoRoom : k.alloc_batch ? k.alloc_batch(who, bt, a, own) : LBM_SUCCESS;
+    const int rc = ring_bytes && bt->gather_ring.alloc_bytes(ring_bytes) != hipSuccess ? kNoRoom : k.alloc_batch ? k.alloc_batch(who, bt, a, own) : LBM_SUCCESS;
     if (rc == kNoRoom)
       LBM_FAIL(LBM_FAILURE, "%s: cannot allocate %d %ss of %d members%s (%.1f MiB)%s; %s", who, capacity, k.ctx.record, (int)n_members,
                OfWhat(k, a).text, (double)ring_bytes / 1048576.0, k.also, k.stays_off);
@@ -4131,6 +4217,28 @@ int lbm_read_stress_rows(lbm_ctx* c, int max_rows, lbm_stress_row* out, int* ste
   return drain_gather(c, kRecStress, max_rows, out, steps, n_read);
 }
 
+int lbm_set_tracers(lbm_ctx* c, int n, const lbm_tracer* start, int every, int capacity) {
+  GatherArgs a;
+  a.tracers = n;
+  if (n == 0) every = every < 0 ? every : 0;  // no tracers: disarms
+  if (gather_refusals(c, kRecTracers, every, capacity, a) != LBM_SUCCESS) return LBM_FAILURE;
+  if (every > 0 && tracer_starts_ok("lbm_set_tracers", c, 1, n, start) != LBM_SUCCESS) return LBM_FAILURE;
+  return arm_gather_checked(c, kRecTracers, every, capacity, a, start);
+}
+
+int lbm_read_tracers(lbm_ctx* c, int max_rows, lbm_tracer* out, int* steps, int* n_read) {
+  return drain_gather(c, kRecTracers, max_rows, out, steps, n_read);
+}
+
+int lbm_tracers_now(lbm_ctx* c, lbm_tracer* out) {
+  if (!c || !out) LBM_FAIL(LBM_FAILURE, "lbm_tracers_now: NULL argument");
+  if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
+  if (c->rec.kind != kRecTracers) LBM_FAIL(LBM_FAILURE, "lbm_tracers_now: tracer particles are not armed (lbm_set_tracers)");
+  HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
+  HIP_TRY(LBM_FAILURE, hipMemcpy(out, c->slab[0].tracer_state, (size_t)c->rec.args.tracers * sizeof(lbm_tracer), hipMemcpyDeviceToHost));
+  return LBM_SUCCESS;
+}
+
 int lbm_read_stress(lbm_ctx* c, float* txx, float* txy, float* tyy) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_read_stress: NULL argument");
   if (c->ranked || c->world > 1)
@@ -4662,8 +4770,9 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
     if (batch_advance(bt, seg) != LBM_SUCCESS) return LBM_FAILURE;
     if (bt->steps_done - 1 == rec_tt) {
       HIP_TRY(LBM_FAILURE, hipSetDevice(c0->slab[0].device));
-      long long* slot = zeroed_slot(bt->gather_ring, gather_slot_words(bt), bt->rec, bt->stream);
-      if (!slot || kind.take_batch(bt, slot) != LBM_SUCCESS) return LBM_FAILURE;
+      bool ringless;
+      long long* slot = zeroed_slot(bt->gather_ring, gather_slot_words(bt), bt->rec, bt->stream, &ringless);
+      if ((!slot && !ringless) || kind.take_batch(bt, slot) != LBM_SUCCESS) return LBM_FAILURE;
       bt->rec.written++;
     }
     t += seg;
@@ -4738,6 +4847,29 @@ int lbm_batch_set_stress(lbm_batch* bt, int every, int capacity) { return arm_ba
 
 int lbm_batch_read_stress_rows(lbm_batch* bt, int max_rows, lbm_stress_row* out, int* steps, int* n_read) {
   return drain_batch_gather(bt, kRecStress, max_rows, out, steps, n_read);
+}
+
+int lbm_batch_set_tracers(lbm_batch* bt, int n, const lbm_tracer* start, int every, int capacity) {
+  GatherArgs a;
+  a.tracers = n;
+  if (n == 0) every = every < 0 ? every : 0;  // no tracers: disarms
+  if (batch_gather_refusals(bt, kRecTracers, every, capacity, a) != LBM_SUCCESS) return LBM_FAILURE;
+  if (every > 0 && tracer_starts_ok("lbm_batch_set_tracers", bt->members[0], bt->members.size(), n, start) != LBM_SUCCESS) return LBM_FAILURE;
+  return arm_batch_gather_checked(bt, kRecTracers, every, capacity, a, start);
+}
+
+int lbm_batch_read_tracers(lbm_batch* bt, int max_rows, lbm_tracer* out, int* steps, int* n_read) {
+  return drain_batch_gather(bt, kRecTracers, max_rows, out, steps, n_read);
+}
+
+int lbm_batch_tracers_now(lbm_batch* bt, lbm_tracer* out) {
+  if (!bt || !out) LBM_FAIL(LBM_FAILURE, "lbm_batch_tracers_now: NULL argument");
+  if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
+  if (bt->rec.kind != kRecTracers) LBM_FAIL(LBM_FAILURE, "lbm_batch_tracers_now: tracer particles are not armed (lbm_batch_set_tracers)");
+  HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
+  HIP_TRY(LBM_FAILURE, hipMemcpy(out, bt->tracer_state, bt->members.size() * (size_t)bt->rec.args.tracers * sizeof(lbm_tracer),
+                                 hipMemcpyDeviceToHost));
+  return LBM_SUCCESS;
 }
 
 int lbm_batch_set_psi(lbm_batch* bt, int every, int capacity) { return arm_batch_gather(bt, kRecPsi, every, capacity, GatherArgs{}); }

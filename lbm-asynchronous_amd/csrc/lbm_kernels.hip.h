@@ -44,6 +44,7 @@
 #include "lbm_psi_row.h"
 #include "lbm_exact_round.h"
 #include "lbm_residual_until.h"
+#include "lbm_tracer_step.h"
 
 namespace lbm {
 
@@ -4236,6 +4237,52 @@ __global__ __launch_bounds__(64) void psi_extrema(const PsiCandidate* cand, int 
     words[lbm_psi::kPsiFluidWord] = n_fluid;
     words[lbm_psi::kPsiBadWord] = n_bad;
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// tracer particles (lbm_set_tracers): positions advected through the velocity field of a stored lattice
+// ---------------------------------------------------------------------------------------------
+// The one gather whose reads depend on data: a lane owns a tracer, reads its position, and per stage of the midpoint
+// step (lbm_tracer_step.h: tracer_advance, the function the CPU check runs) gathers the 4 cells around a position -- 36
+// populations through gather_cell's addressing and 4 mask bytes, all issued before the first moment is formed: the
+// callable below has no branch, a blocked cell's populations are loaded like any other and its velocity selected to 0, 0
+// behind moments_exact -- then forms the four velocities as final_state does and interpolates in doubles.  Two dependent
+// stages, so two round trips to memory per sample; neighbouring tracers share cache lines only where the caller seeded
+// them in row-major order.  The lane is the only writer of its tracer: the state is updated in place and the same 16
+// bytes go to the ring row (null: armed without a ring).  No atomics, no LDS.  A lost tracer is written through.
+// grid: (ceil(n / kBlock), 1, members)
+__device__ __forceinline__ void tracer_lane(const LatticeArgs& a, const float* __restrict__ src, const unsigned char* __restrict__ mask, int ny,
+                                            int n, int span, double2* state, double2* row) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const double2 p = state[i];
+  const auto u = [&](int x, int y) -> lbm_tracers::Vec {
+    const long c = (long)y * a.row_pitch + x;
+    float f[kQ];
+#pragma unroll
+    for (int k = 0; k < kQ; k++) f[k] = src[k * a.plane_stride + c];
+    const bool blocked = mask[(long)y * a.pitch + x] != 0;
+    float rho, ux, uy;
+    moments_exact(f, rho, ux, uy);
+    return {blocked ? 0.0 : (double)ux, blocked ? 0.0 : (double)uy};
+  };
+  const lbm_tracers::Vec q = lbm_tracers::tracer_advance(lbm_tracers::Vec{p.x, p.y}, a.nx, ny, span, u);
+  const double2 out = make_double2(q.x, q.y);
+  state[i] = out;
+  if (row) row[i] = out;
+}
+
+// one sample of a context's n tracers over `span` timesteps in the field of a.src, the whole grid of ny rows
+__global__ __launch_bounds__(kBlock) void tracer_advance(const LatticeArgs a, int ny, int n, int span, double2* state, double2* row) {
+  tracer_lane(a, a.src, a.mask, ny, n, span, state, row);
+}
+
+// tracer_advance's twin for a batch: one launch for all members' tracers, workgroup (g, 0, member) in the member's current
+// lattice and mask; state and row are [members][n]
+__global__ __launch_bounds__(kBlock) void tracer_advance_batch(const LatticeArgs a, const ResidentMember* members, int ny, int n, int span,
+                                                               double2* state, double2* row) {
+  const size_t member = blockIdx.z;
+  tracer_lane(a, members[member].src, members[member].mask, ny, n, span, state + member * (size_t)n, row ? row + member * (size_t)n : nullptr);
 }
 
 }  // namespace lbm
