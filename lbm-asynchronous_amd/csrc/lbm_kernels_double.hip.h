@@ -54,9 +54,11 @@ __device__ __forceinline__ bool cell_blocked_d(const LatticeArgsD& a, int row, i
   return a.mask[(long)row * a.pitch + x] != 0;
 }
 
-// local density and velocity (SerialCode/d2q9-bgk.c:325-347; 0.0 + f[0] is f[0])
+// local density and velocity (SerialCode/d2q9-bgk.c:325-347).  The sum starts from 0.0 as the reference's does: 0.0 + f[0]
+// is f[0] except for f[0] = -0.0, and nine -0.0 must sum to +0.0 (the sign of a zero pressure; without fast-math flags
+// the compiler keeps the add)
 __device__ __forceinline__ void moments_d(const double (&f)[kQ], double& rho, double& ux, double& uy) {
-  double d = f[0];
+  double d = 0.0 + f[0];
 #pragma unroll
   for (int k = 1; k < kQ; k++) d += f[k];
   rho = d;

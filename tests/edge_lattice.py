@@ -97,15 +97,16 @@ def accel_terms(density, accel, dtype=np.float32):
     return dtype(d * a / dtype(9)), dtype(d * a / dtype(36))
 
 
-def ramp(nx):
+def ramp(nx, lo=0.00125, span=16.0):
+    """lo at x mod 128 = 64, lo * span at x mod 128 = 0 (the defaults: the fp32 lattices' ramp)."""
     x = np.arange(nx)
-    return 0.00125 * 16.0 ** (np.abs(x % 128 - 64) / 64.0)
+    return lo * span ** (np.abs(x % 128 - 64) / 64.0)
 
 
-def apply_ramp(cells):
+def apply_ramp(cells, lo=0.00125, span=16.0):
     """In place, in the array's own precision."""
     ny, nx = cells.shape[:2]
-    s = ramp(nx).astype(cells.dtype)[:, None]
+    s = ramp(nx, lo, span).astype(cells.dtype)[:, None]
     for y in (ny - 4, ny - 3, ny - 2, ny - 1, 0):
         cells[y] *= s
 

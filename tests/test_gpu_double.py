@@ -6,7 +6,10 @@
 3. the reference's own pin: full runs against the double-precision goldens of check/ (tests/golden/check_goldens.npz),
    to the digits they are printed with;
 4. the command line, LBM_PRECISION=double;
-5. an fp32 Engine and a DoubleEngine side by side.
+5. an fp32 Engine and a DoubleEngine side by side;
+6. in tests/test_gpu_double_edges.py, on the inputs of tests/double_edge_lattice.py: the refused lid acceleration in
+   every kernel that accelerates, cells far from equilibrium (denormals, 2^1000, negative and zero density, Inf, NaN, a
+   cell of -0.0), more than 256 workgroups and 65 536 cells, the ring of partials across calls, lattices staged in chunks.
 
 Bounds.  Lattice, u_x, u_y, pressure and u (IEEE sqrt) are compared as bit patterns.  av_vels[t] is a sum of n = fluid
 cells non-negative terms that the kernels add in another order than the model (or the reference): two orders of such a
