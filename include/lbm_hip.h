@@ -292,6 +292,20 @@ int      lbm_read_halo_log(lbm_ctx* ctx, unsigned char* out, int n_steps);
  * with no host round trip per step.  Per-step sums of |u| accumulate on the device.
  * lbm_sync waits for the device (call it before reading the clock, as the reference's
  * "Elapsed Compute time" brackets the loop, :162-185).
+ *
+ * A RESIDENT GIVE-UP FAILS THE CONTEXT FOR GOOD.  A launch of the resident kernel whose workgroups were not all running
+ * at once gives up after its bound and leaves a status word; the lattice and every record are then invalid.  The call
+ * that first sees the word -- lbm_sync, every reader (each synchronises first), lbm_run_timed, lbm_run_until and
+ * lbm_run_until_residual, never lbm_run itself, which does not wait -- fails with "the resident kernel gave up ...", and
+ * the context is FAILED until it is destroyed: every later call that takes it fails (NULL for pointer results) with
+ *     "<function>: an earlier launch of the resident kernel gave up: the lattice and the records of this context or
+ *      batch are invalid, and it stays failed until it is destroyed"
+ * directly behind its NULL checks -- before "not armed", capacity and argument checks --, issues no device work, leaves
+ * steps_done and the caller's output arrays as they were and sets its count outputs (*n_read, *n_samples, steps_run,
+ * *kernel_ms_per_step) to 0.  lbm_destroy, lbm_get_info and lbm_rccl_info still work.  A batch fails as a whole: one
+ * give-up in any of its launches fails the batch and every member, for every call but lbm_destroy_batch,
+ * lbm_batch_get_info, lbm_batch_member and the three above on a member.  Nothing outlives the owner: a context created
+ * afterwards is healthy.
  */
 int lbm_run(lbm_ctx* ctx, int n_steps);
 int lbm_sync(lbm_ctx* ctx);
@@ -335,8 +349,8 @@ int   lbm_calc_reynolds(lbm_ctx* ctx, float* out);
  *   any work.  every == 0 disarms and frees the buffer; re-arming discards unread frames.  Refused in LBM_HALO_STALE and
  *   LBM_HALO_FRESHEST (and lbm_set_halo_mode to those modes while armed).  Works on batch members too.
  * lbm_read_frames: drains up to max_frames oldest frames into out[n][row_count*nx] and steps[n] (their tt, may be NULL);
- *   out == NULL && steps == NULL: *n_read = frames waiting, nothing drained.  Synchronises like the other readers (so a
- *   resident give-up is reported here too).
+ *   out == NULL && steps == NULL: *n_read = frames waiting, nothing drained.  Synchronises like the other readers (a
+ *   resident give-up: the rule at lbm_sync).
  */
 int lbm_set_frames(lbm_ctx* ctx, int every, int capacity);
 int lbm_read_frames(lbm_ctx* ctx, int max_frames, float* out, int* steps, int* n_read);
@@ -360,8 +374,8 @@ int lbm_read_frames(lbm_ctx* ctx, int max_frames, float* out, int* steps, int* n
  *   while armed), a context whose frames are armed (and lbm_set_frames while probes are armed: one recorder per
  *   context; in a batch one KIND of recorder per batch), lbm_run_until / lbm_batch_run_until while armed.
  * lbm_read_probes: drains up to max_samples oldest rows into out[n][n_probes] and steps[n] (their tt, may be NULL);
- *   out == NULL && steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers (so a
- *   resident give-up is reported here too).
+ *   out == NULL && steps == NULL: *n_read = rows waiting, nothing drained.  Synchronises like the other readers (a
+ *   resident give-up: the rule at lbm_sync).
  */
 #define LBM_MAX_PROBES 256
 typedef struct { int x, y; } lbm_probe;                               /* a GLOBAL cell, 0 <= x < nx, 0 <= y < ny */
@@ -397,8 +411,8 @@ int lbm_read_probes(lbm_ctx* ctx, int max_samples, lbm_probe_sample* out /* [n][
  *   of the resident kernel does not fit a CU (the checks lbm_set_frames makes, against this form).
  * lbm_read_mean: the sums of the owned rows of all slabs, double[row_count * nx] each, row-major (y * nx + x); any of the
  *   four may be NULL; *n_samples (may be NULL) = samples since arming.  With all four NULL it only reports n_samples.
- *   It does NOT reset: for a windowed mean read, then arm again.  Synchronises like the other readers (so a resident
- *   give-up is reported here too).  Fails on a context whose mean fields are not armed.
+ *   It does NOT reset: for a windowed mean read, then arm again.  Synchronises like the other readers (a resident
+ *   give-up: the rule at lbm_sync).  Fails on a context whose mean fields are not armed.
  */
 int lbm_set_mean(lbm_ctx* ctx, int every);
 int lbm_read_mean(lbm_ctx* ctx, double* sum_u_x, double* sum_u_y, double* sum_u_mag, double* sum_pressure,
@@ -462,7 +476,7 @@ int lbm_read_mean2(lbm_ctx* ctx, double* sum_uxux, double* sum_uyuy, double* sum
  *   checks lbm_set_frames makes, against this form).
  * lbm_read_field_frames: drains up to max_frames oldest frames into out[n][F][window.ny][window.nx] and steps[n] (their
  *   tt, may be NULL); out == NULL && steps == NULL: *n_read = frames waiting, nothing drained.  Synchronises like the
- *   other readers (so a resident give-up is reported here too).
+ *   other readers (a resident give-up: the rule at lbm_sync).
  */
 #define LBM_FIELD_UX       1
 #define LBM_FIELD_UY       2
@@ -575,7 +589,9 @@ int lbm_run_until(lbm_ctx* ctx, int max_steps, int check_every, double tol, int 
  * lbm_batch_member: a borrowed handle of member `index`; the readers (lbm_read_av_vels, lbm_read_cells,
  *   lbm_read_final_state, lbm_av_velocity, lbm_total_density, lbm_calc_reynolds, lbm_get_info) work on it and see every
  *   batched launch; lbm_run / lbm_run_timed on it fail; lbm_destroy on it does nothing.  If a batched launch gives up
- *   waiting (its workgroups were not co-resident), the next lbm_sync of EVERY member reports it.
+ *   waiting (its workgroups were not co-resident), the batch is failed as a whole (the rule at lbm_sync): the
+ *   lbm_batch_sync that sees it reports it for every member, and afterwards every call on the batch or on any member
+ *   fails, except lbm_destroy_batch, lbm_batch_get_info, lbm_batch_member and a member's lbm_get_info.
  */
 typedef struct lbm_batch lbm_batch; /* opaque batch handle */
 typedef struct {

@@ -553,6 +553,7 @@ struct lbm_ctx {
   SlabTeam* team = nullptr;         // one issuing thread per slab (one-process multi-GPU), or null
   GraphBuilder* builder = nullptr;  // non-null while a chunk is being built: launches become graph nodes
   bool resident_used = false;       // a resident launch is in flight / unchecked: lbm_sync reads its status
+  bool failed = false;              // a resident launch of this context gave up: failed until destroyed (a member: see lbm_batch::failed)
   lbm_batch* batch = nullptr;       // member of this batch (lbm_create_batch): advanced, synchronised and freed by it
   Recorder rec;                     // the one recorder: animation frames (lbm_set_frames), point probes (lbm_set_probes) or
                                     // mean fields (lbm_set_mean) or field frames (lbm_set_field_frames)
@@ -589,6 +590,7 @@ struct lbm_batch {
   DeviceBuf<lbm::ResidentMember> table;  // device: [parity of cur][members]
   DeviceBuf<int> status;            // device: 0, or kResidentTimeout once a workgroup of any batched launch gave up
   PinnedBuf<int> status_host;       // pinned copy behind every run; every member's lbm_sync reports it
+  bool failed = false;              // a batched launch gave up: the batch and all its members are failed until it is destroyed
   DeviceBuf<lbm::ResidentFrames> frame_table;  // device: [members], allocated when the first member arms frames
   DeviceBuf<lbm::ResidentProbes> probe_table;  // device: [members], allocated when the first member arms probes
   DeviceBuf<lbm::ResidentMean> mean_table;     // device: [members], allocated when the first member arms the mean fields
@@ -628,6 +630,35 @@ struct lbm_batch {
 };
 
 namespace {
+
+// ---- a resident give-up fails its owner for good ---------------------------------------------------------------------
+// The owner of a lattice is its context, or for a batch member the batch: one give-up in any batched launch fails the
+// batch and every member.  The flag is set where a non-zero status word is first seen (gave_up) and never cleared; every
+// entry point but lbm_destroy, lbm_destroy_batch, lbm_get_info, lbm_batch_get_info, lbm_batch_member and lbm_rccl_info
+// refuses a failed owner directly behind its NULL checks (REFUSE_FAILED), before any other check and any device work.
+const char kFailedOwner[] = "%s: an earlier launch of the resident kernel gave up: the lattice and the records of this context or "
+                            "batch are invalid, and it stays failed until it is destroyed";
+bool owner_failed(const lbm_ctx* c) { return c->batch ? c->batch->failed : c->failed; }
+bool owner_failed(const lbm_batch* bt) { return bt->failed; }
+#define REFUSE_FAILED(ret, owner, who)                              \
+  do {                                                              \
+    if (owner_failed(owner)) LBM_FAIL(ret, kFailedOwner, who);      \
+  } while (0)
+
+// the status word that the resident launches of c (a member: of its batch) left on the host; non-zero fails the owner.
+// The caller has waited for the copy behind those launches.
+int gave_up(lbm_ctx* c) {
+  const int status = c->batch ? *c->batch->status_host : *c->slab[0].res_status_host;
+  if (status != 0) (c->batch ? c->batch->failed : c->failed) = true;
+  return status;
+}
+// the first report of a give-up
+int report_give_up(const lbm_ctx* c, int status) {
+  LBM_FAIL(LBM_FAILURE, "the resident kernel gave up waiting for a neighbouring band after %.0f ms (status %d): its %d workgroups "
+           "were not all running at once -- is another process using the device?  The lattice of this context is no "
+           "longer valid; LBM_RESIDENT=0 selects the launch-per-pass kernels, LBM_RESIDENT_TIMEOUT_MS moves the bound",
+           (double)c->plan.resident_timeout / 1e5, status, c->plan.resident_bands);
+}
 
 // the acceleration weights of the lid row (SerialCode/d2q9-bgk.c:219-220), and the a1 / a2 fields of a kernel's arguments
 struct AccelWeights { float a1, a2; };
@@ -1074,6 +1105,14 @@ int read_step_timing(lbm_ctx* c, int n_steps, float* kernel_ms) {
     if (ms > worst) worst = ms;
   }
   *kernel_ms = worst / (float)n_steps;
+  if (c->resident_used) {
+    // the status copy of run_resident lies in front of ev_t1 on the compute stream: a call that gave up fails here
+    if (const int status = gave_up(c)) {
+      c->resident_used = false;
+      *kernel_ms = 0.f;
+      return report_give_up(c, status);
+    }
+  }
   return LBM_SUCCESS;
 }
 
@@ -2793,6 +2832,7 @@ int drain_recorder(lbm_ctx* c, int kind, int max_records, bool has_out, int* ste
   const char* const reader = kind_words(kind).reader;
   if (!c || !n_read) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", reader);
   *n_read = 0;
+  REFUSE_FAILED(LBM_FAILURE, c, reader);
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
   return drain_ring(c->rec, kind, reader, max_records, has_out, steps, n_read, copy);
 }
@@ -3531,6 +3571,7 @@ int gather_refusals(lbm_ctx* c, int kind, int every, int capacity, const GatherA
   const GatherKind& k = gather_kind(kind);
   const char* const who = k.ctx.setter;
   if (!c) LBM_FAIL(LBM_FAILURE, "%s: null context", who);
+  REFUSE_FAILED(LBM_FAILURE, c, who);
   if (every < 0) LBM_FAIL(LBM_FAILURE, "%s: negative interval %d", who, every);
   if (every == 0) return LBM_SUCCESS;
   if (k.ringless && capacity < 0) LBM_FAIL(LBM_FAILURE, "%s: negative capacity %d (0: no ring)", who, capacity);
@@ -3598,6 +3639,7 @@ int batch_gather_refusals(lbm_batch* bt, int kind, int every, int capacity, cons
   const GatherKind& k = gather_kind(kind);
   const char* const who = k.batch_setter;
   if (!bt) LBM_FAIL(LBM_FAILURE, "%s: null batch", who);
+  REFUSE_FAILED(LBM_FAILURE, bt, who);
   if (every < 0) LBM_FAIL(LBM_FAILURE, "%s: negative interval %d", who, every);
   if (every == 0) return LBM_SUCCESS;
   if (bt->rec.kind != kRecNone && bt->rec.kind != kind) {
@@ -3662,6 +3704,7 @@ int drain_batch_gather(lbm_batch* bt, int kind, int max_records, void* out, int*
   const char* const reader = gather_kind(kind).batch_reader;
   if (!bt || !n_read) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", reader);
   *n_read = 0;
+  REFUSE_FAILED(LBM_FAILURE, bt, reader);
   if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
   return drain_ring(bt->rec, kind, reader, max_records, out != nullptr, steps, n_read, [&](int n) -> int {
     const size_t words = gather_slot_words(bt);
@@ -3896,6 +3939,7 @@ int lbm_get_info(const lbm_ctx* c, lbm_info* out) {
 
 int lbm_set_halo_mode(lbm_ctx* c, int mode) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: null context");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_set_halo_mode");
   if (mode != LBM_HALO_SYNC && mode != LBM_HALO_STALE && mode != LBM_HALO_FRESHEST) LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: unknown mode %d", mode);
   if (mode == LBM_HALO_FRESHEST && c->halo == HALO_HOST) LBM_FAIL(LBM_FAILURE, "lbm_set_halo_mode: the freshest-available mode is not available with the hosted exchange");
   if (mode != LBM_HALO_SYNC && c->rec.kind != kRecNone) {
@@ -3909,6 +3953,7 @@ int lbm_set_halo_mode(lbm_ctx* c, int mode) {
 
 int lbm_set_frames(lbm_ctx* c, int every, int capacity) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_frames: null context");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_set_frames");
   if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_frames: negative interval %d", every);
   if (every > 0 && capacity < 1) LBM_FAIL(LBM_FAILURE, "lbm_set_frames: capacity %d, at least one frame slot is needed", capacity);
   return rearm_recorder(c, kRecFrames, every, capacity, [&]() -> int {
@@ -3947,6 +3992,7 @@ int lbm_read_frames(lbm_ctx* c, int max_frames, float* out, int* steps, int* n_r
 
 int lbm_set_probes(lbm_ctx* c, int n_probes, const lbm_probe* cells, int every, int capacity) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_probes: null context");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_set_probes");
   if (n_probes < 0 || n_probes > LBM_MAX_PROBES)
     LBM_FAIL(LBM_FAILURE, "lbm_set_probes: %d probes, between 0 and LBM_MAX_PROBES = %d are possible", n_probes, LBM_MAX_PROBES);
   if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_probes: negative interval %d", every);
@@ -4026,6 +4072,7 @@ int lbm_read_probes(lbm_ctx* c, int max_samples, lbm_probe_sample* out, int* ste
 // what lbm_set_mean and lbm_set_mean_order share: `who` names the caller, order 1 arms four planes, order 2 eight
 static int set_mean_order(lbm_ctx* c, int every, int order, const char* who) {
   if (!c) LBM_FAIL(LBM_FAILURE, "%s: null context", who);
+  REFUSE_FAILED(LBM_FAILURE, c, who);
   if (every < 0) LBM_FAIL(LBM_FAILURE, "%s: negative interval %d", who, every);
   if (order != 1 && order != 2) LBM_FAIL(LBM_FAILURE, "%s: order %d, the mean fields have order 1 (sums) or 2 (sums and sums of products)", who, order);
   if (every > 0 && (c->ranked || c->world > 1))
@@ -4057,6 +4104,7 @@ int lbm_set_mean_order(lbm_ctx* c, int every, int order) {
 
 int lbm_set_field_frames(lbm_ctx* c, int every, int capacity, int fields, const lbm_window* window) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_set_field_frames: null context");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_set_field_frames");
   if (every < 0) LBM_FAIL(LBM_FAILURE, "lbm_set_field_frames: negative interval %d", every);
   lbm_window w = {0, 0, c->p.nx, c->p.ny};
   if (every > 0) {
@@ -4158,6 +4206,7 @@ int lbm_read_forces(lbm_ctx* c, int max_rows, double* out, int* steps, int* n_re
 
 int lbm_forces_links(lbm_ctx* c, int* links_per_body) {
   if (!c || !links_per_body) LBM_FAIL(LBM_FAILURE, "lbm_forces_links: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_forces_links");
   if (c->rec.kind != kRecForces) LBM_FAIL(LBM_FAILURE, "lbm_forces_links: the obstacle forces are not armed (lbm_set_forces)");
   for (size_t b = 0; b < c->force_link_counts.size(); b++) links_per_body[b] = c->force_link_counts[b];
   return LBM_SUCCESS;
@@ -4178,6 +4227,7 @@ int lbm_read_enstrophy(lbm_ctx* c, int max_rows, lbm_enstrophy_row* out, int* st
 
 int lbm_read_vorticity(lbm_ctx* c, float* w) {
   if (!c || !w) LBM_FAIL(LBM_FAILURE, "lbm_read_vorticity: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_read_vorticity");
   if (c->ranked || c->world > 1)
     LBM_FAIL(LBM_FAILURE, "lbm_read_vorticity: not available in a multi-process (rank) context: the rows around this rank's belong to other processes");
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
@@ -4232,6 +4282,7 @@ int lbm_read_tracers(lbm_ctx* c, int max_rows, lbm_tracer* out, int* steps, int*
 
 int lbm_tracers_now(lbm_ctx* c, lbm_tracer* out) {
   if (!c || !out) LBM_FAIL(LBM_FAILURE, "lbm_tracers_now: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_tracers_now");
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
   if (c->rec.kind != kRecTracers) LBM_FAIL(LBM_FAILURE, "lbm_tracers_now: tracer particles are not armed (lbm_set_tracers)");
   HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[0].device));
@@ -4241,6 +4292,7 @@ int lbm_tracers_now(lbm_ctx* c, lbm_tracer* out) {
 
 int lbm_read_stress(lbm_ctx* c, float* txx, float* txy, float* tyy) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_read_stress: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_read_stress");
   if (c->ranked || c->world > 1)
     LBM_FAIL(LBM_FAILURE, "lbm_read_stress: not available in a multi-process (rank) context: the fields of a rank's rows are not offered");
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
@@ -4276,6 +4328,7 @@ int lbm_read_psi_rows(lbm_ctx* c, int max_rows, lbm_psi_row* out, int* steps, in
 
 int lbm_read_psi(lbm_ctx* c, double* psi) {
   if (!c || !psi) LBM_FAIL(LBM_FAILURE, "lbm_read_psi: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_read_psi");
   if (c->ranked || c->world > 1)
     LBM_FAIL(LBM_FAILURE, "lbm_read_psi: not available in a multi-process (rank) context: the rows below this rank's belong to other processes");
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
@@ -4340,6 +4393,7 @@ int lbm_read_profiles(lbm_ctx* c, int max_records, lbm_profile_line* out, int* s
 // ---- coarse frames -----------------------------------------------------------------------------------------------------
 int lbm_read_coarse(lbm_ctx* c, int bx, int by, lbm_profile_line* out) {
   if (!c || !out) LBM_FAIL(LBM_FAILURE, "lbm_read_coarse: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_read_coarse");
   if (c->ranked || c->world > 1)
     LBM_FAIL(LBM_FAILURE, "lbm_read_coarse: not available in a multi-process (rank) context: a box's cells would be spread over the ranks");
   if (coarse_box_ok("lbm_read_coarse", c, bx, by) != LBM_SUCCESS) return LBM_FAILURE;
@@ -4399,6 +4453,7 @@ static int read_mean_planes(lbm_ctx* c, int first, double* const (&out)[4], long
 int lbm_read_mean(lbm_ctx* c, double* sum_u_x, double* sum_u_y, double* sum_u_mag, double* sum_pressure, long long* n_samples) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_read_mean: null context");
   if (n_samples) *n_samples = 0;
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_read_mean");
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
   if (c->rec.kind != kRecMean) LBM_FAIL(LBM_FAILURE, "lbm_read_mean: the mean fields are not armed (lbm_set_mean)");
   double* const out[4] = {sum_u_x, sum_u_y, sum_u_mag, sum_pressure};
@@ -4408,6 +4463,7 @@ int lbm_read_mean(lbm_ctx* c, double* sum_u_x, double* sum_u_y, double* sum_u_ma
 int lbm_read_mean2(lbm_ctx* c, double* sum_uxux, double* sum_uyuy, double* sum_uxuy, double* sum_pp, long long* n_samples) {
   if (!c) LBM_FAIL(LBM_FAILURE, "lbm_read_mean2: null context");
   if (n_samples) *n_samples = 0;
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_read_mean2");
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
   if (c->rec.kind != kRecMean || c->rec.order != 2)
     LBM_FAIL(LBM_FAILURE, "lbm_read_mean2: the second moments are not armed (lbm_set_mean_order(ctx, every, 2))");
@@ -4418,18 +4474,24 @@ int lbm_read_mean2(lbm_ctx* c, double* sum_uxux, double* sum_uyuy, double* sum_u
 static const char kMemberRun[] = "%s: this context is a member of a batch (lbm_create_batch); lbm_batch_run advances all its members";
 
 int lbm_run(lbm_ctx* c, int n_steps) {
-  if (c && c->batch) LBM_FAIL(LBM_FAILURE, kMemberRun, "lbm_run");
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_run: null context");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_run");
+  if (c->batch) LBM_FAIL(LBM_FAILURE, kMemberRun, "lbm_run");
   return run_steps(c, n_steps, nullptr);
 }
 
 int lbm_run_timed(lbm_ctx* c, int n_steps, float* kernel_ms_per_step) {
-  if (c && c->batch) LBM_FAIL(LBM_FAILURE, kMemberRun, "lbm_run_timed");
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_run: null context");
+  if (kernel_ms_per_step) *kernel_ms_per_step = 0.f;
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_run_timed");
+  if (c->batch) LBM_FAIL(LBM_FAILURE, kMemberRun, "lbm_run_timed");
   if (!kernel_ms_per_step) LBM_FAIL(LBM_FAILURE, "lbm_run_timed: NULL output");
   return run_steps(c, n_steps, kernel_ms_per_step);
 }
 
-int lbm_sync(lbm_ctx* c) {
-  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_sync: null context");
+// what lbm_sync does behind its refusals, and what the library's own paths call: a path that has seen the give-up itself
+// (checked_run's judge) still gets the first report from here
+static int sync_ctx(lbm_ctx* c) {
   for (int s = 0; s < c->n_slabs; s++) {
     HIP_TRY(LBM_FAILURE, hipSetDevice(c->slab[s].device));
     HIP_TRY(LBM_FAILURE, hipStreamSynchronize(c->slab[s].compute));
@@ -4438,19 +4500,21 @@ int lbm_sync(lbm_ctx* c) {
   }
   if (c->resident_used) {
     // did every workgroup of the resident kernel get its neighbours' rows in time?  (a batch member: of any batched launch)
-    const int status = c->batch ? *c->batch->status_host : *c->slab[0].res_status_host;
     c->resident_used = false;
-    if (status != 0)
-      LBM_FAIL(LBM_FAILURE, "the resident kernel gave up waiting for a neighbouring band after %.0f ms (status %d): its %d workgroups "
-               "were not all running at once -- is another process using the device?  The lattice of this context is no "
-               "longer valid; LBM_RESIDENT=0 selects the launch-per-pass kernels, LBM_RESIDENT_TIMEOUT_MS moves the bound",
-               (double)c->plan.resident_timeout / 1e5, status, c->plan.resident_bands);
+    if (const int status = gave_up(c)) return report_give_up(c, status);
   }
   return LBM_SUCCESS;
 }
 
+int lbm_sync(lbm_ctx* c) {
+  if (!c) LBM_FAIL(LBM_FAILURE, "lbm_sync: null context");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_sync");
+  return sync_ctx(c);
+}
+
 int lbm_read_halo_log(lbm_ctx* c, unsigned char* out, int n) {
   if (!c || !out) LBM_FAIL(LBM_FAILURE, "lbm_read_halo_log: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_read_halo_log");
   if (n < 0 || n > c->steps_done) LBM_FAIL(LBM_FAILURE, "lbm_read_halo_log: %d steps requested, %d recorded", n, c->steps_done);
   if (n == 0) return LBM_SUCCESS;
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
@@ -4470,6 +4534,7 @@ int lbm_read_halo_log(lbm_ctx* c, unsigned char* out, int n) {
 
 int lbm_read_av_vels(lbm_ctx* c, float* out, int n) {
   if (!c || !out) LBM_FAIL(LBM_FAILURE, "lbm_read_av_vels: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_read_av_vels");
   if (n < 0 || n > c->steps_done) LBM_FAIL(LBM_FAILURE, "lbm_read_av_vels: %d steps requested, %d recorded", n, c->steps_done);
   if (n == 0) return LBM_SUCCESS;
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
@@ -4501,6 +4566,7 @@ int lbm_read_av_vels(lbm_ctx* c, float* out, int n) {
 
 int lbm_read_cells(lbm_ctx* c, float* cells_aos) {
   if (!c || !cells_aos) LBM_FAIL(LBM_FAILURE, "lbm_read_cells: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_read_cells");
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
   const int nx = c->p.nx;
   long chunk_rows = (64L << 20) / ((long)nx * lbm::kQ * sizeof(float));
@@ -4526,6 +4592,7 @@ int lbm_read_cells(lbm_ctx* c, float* cells_aos) {
 
 int lbm_read_final_state(lbm_ctx* c, float* u_x, float* u_y, float* u_mag, float* pressure) {
   if (!c || !u_x || !u_y || !u_mag || !pressure) LBM_FAIL(LBM_FAILURE, "lbm_read_final_state: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_read_final_state");
   if (lbm_sync(c) != LBM_SUCCESS) return LBM_FAILURE;
   const int nx = c->p.nx;
   long chunk_rows = (16L << 20) / ((long)nx * sizeof(float));
@@ -4589,6 +4656,7 @@ static int lattice_totals(lbm_ctx* c, double* speed, double* mass) {
 
 int lbm_av_velocity(lbm_ctx* c, float* out) {
   if (!c || !out) LBM_FAIL(LBM_FAILURE, "lbm_av_velocity: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_av_velocity");
   double speed, mass;
   if (lattice_totals(c, &speed, &mass) != LBM_SUCCESS) return LBM_FAILURE;
   *out = (float)speed / (float)c->fluid_cells;
@@ -4597,6 +4665,7 @@ int lbm_av_velocity(lbm_ctx* c, float* out) {
 
 int lbm_total_density(lbm_ctx* c, double* out) {
   if (!c || !out) LBM_FAIL(LBM_FAILURE, "lbm_total_density: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_total_density");
   double speed, mass;
   if (lattice_totals(c, &speed, &mass) != LBM_SUCCESS) return LBM_FAILURE;
   *out = mass;
@@ -4605,6 +4674,7 @@ int lbm_total_density(lbm_ctx* c, double* out) {
 
 int lbm_calc_reynolds(lbm_ctx* c, float* out) {
   if (!c || !out) LBM_FAIL(LBM_FAILURE, "lbm_calc_reynolds: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, c, "lbm_calc_reynolds");
   float av;
   if (lbm_av_velocity(c, &av) != LBM_SUCCESS) return LBM_FAILURE;
   const float viscosity = 1.f / 6.f * (2.f / c->p.omega - 1.f);  // SerialCode/d2q9-bgk.c:639
@@ -4748,6 +4818,7 @@ static int batch_advance(lbm_batch* bt, int n_steps) {
 
 int lbm_batch_run(lbm_batch* bt, int n_steps) {
   if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: null batch");
+  REFUSE_FAILED(LBM_FAILURE, bt, "lbm_batch_run");
   if (n_steps < 0) LBM_FAIL(LBM_FAILURE, "lbm_batch_run: negative step count");
   if (n_steps == 0) return LBM_SUCCESS;
   lbm_ctx* c0 = bt->members[0];
@@ -4780,12 +4851,18 @@ int lbm_batch_run(lbm_batch* bt, int n_steps) {
   return LBM_SUCCESS;
 }
 
+// what lbm_batch_sync does behind its refusals (sync_ctx does so for a context)
+static int sync_batch(lbm_batch* bt) {
+  int rc = LBM_SUCCESS;
+  for (lbm_ctx* c : bt->members)  // every member reports the verdict of the launches it was part of; the first fails the batch
+    if (sync_ctx(c) != LBM_SUCCESS) rc = LBM_FAILURE;
+  return rc;
+}
+
 int lbm_batch_sync(lbm_batch* bt) {
   if (!bt) LBM_FAIL(LBM_FAILURE, "lbm_batch_sync: null batch");
-  int rc = LBM_SUCCESS;
-  for (lbm_ctx* c : bt->members)  // every member reports (and clears) the verdict of the launches it was part of
-    if (lbm_sync(c) != LBM_SUCCESS) rc = LBM_FAILURE;
-  return rc;
+  REFUSE_FAILED(LBM_FAILURE, bt, "lbm_batch_sync");
+  return sync_batch(bt);
 }
 
 int lbm_batch_get_info(const lbm_batch* bt, lbm_batch_info* out) {
@@ -4825,6 +4902,7 @@ int lbm_batch_read_forces(lbm_batch* bt, int max_rows, double* out, int* steps, 
 
 int lbm_batch_forces_links(lbm_batch* bt, int* links) {
   if (!bt || !links) LBM_FAIL(LBM_FAILURE, "lbm_batch_forces_links: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, bt, "lbm_batch_forces_links");
   if (bt->rec.kind != kRecForces)
     LBM_FAIL(LBM_FAILURE, "lbm_batch_forces_links: the obstacle forces are not armed (lbm_batch_set_forces)");
   for (size_t j = 0; j < bt->force_link_counts.size(); j++) links[j] = bt->force_link_counts[j];
@@ -4864,6 +4942,7 @@ int lbm_batch_read_tracers(lbm_batch* bt, int max_rows, lbm_tracer* out, int* st
 
 int lbm_batch_tracers_now(lbm_batch* bt, lbm_tracer* out) {
   if (!bt || !out) LBM_FAIL(LBM_FAILURE, "lbm_batch_tracers_now: NULL argument");
+  REFUSE_FAILED(LBM_FAILURE, bt, "lbm_batch_tracers_now");
   if (lbm_batch_sync(bt) != LBM_SUCCESS) return LBM_FAILURE;
   if (bt->rec.kind != kRecTracers) LBM_FAIL(LBM_FAILURE, "lbm_batch_tracers_now: tracer particles are not armed (lbm_batch_set_tracers)");
   HIP_TRY(LBM_FAILURE, hipSetDevice(bt->members[0]->slab[0].device));
@@ -5042,8 +5121,8 @@ static int checked_run(lbm_ctx* c, int max_steps, int E, const std::function<int
     bool stop = false;
     if ((waited = wait_stop_word(c->ev_steady[index & 1], c->steady_stop_host + (index & 1), &stop)) != LBM_SUCCESS) return lbm_segments::kBreak;
     if (stop) return lbm_segments::kStop;
-    // a launch gave up (its status travels in front of the stop word): lbm_sync below reports it
-    return resident && *sl.res_status_host != 0 ? lbm_segments::kBreak : lbm_segments::kGoOn;
+    // a launch gave up (its status travels in front of the stop word): the context is failed, sync_ctx below reports it
+    return resident && gave_up(c) != 0 ? lbm_segments::kBreak : lbm_segments::kGoOn;
   };
   const lbm_segments::Outcome o = lbm_segments::run(n_seg, depth, issue, judge);
   if (o.failed || waited != LBM_SUCCESS) return LBM_FAILURE;
@@ -5056,12 +5135,12 @@ static int checked_run(lbm_ctx* c, int max_steps, int E, const std::function<int
     c->steps_done -= E;
     HIP_TRY(LBM_FAILURE, hipMemsetAsync(sl.res_gran, 0, resident_gran_bytes(c), sl.compute));
   }
-  if (!o.stopped && max_steps - n_seg * E > 0) {
+  if (!o.stopped && !owner_failed(c) && max_steps - n_seg * E > 0) {
     // the rest of the cap, shorter than a segment: run as lbm_run runs it, not checked
     const int rest = max_steps - n_seg * E;
     if (run_passes(c, rest, c->plan.resident && rest >= c->plan.resident_min_steps, false) != LBM_SUCCESS) return LBM_FAILURE;
   }
-  return lbm_sync(c);  // also reports a resident give-up
+  return sync_ctx(c);  // also reports a resident give-up
 }
 
 // One checked run of a batch that checked_batch_ok has passed, with begin() and check() as for a context; the checks set
@@ -5082,15 +5161,19 @@ static int checked_batch_run(lbm_batch* bt, int max_steps, int E, const std::fun
     if (check(index, first) != LBM_SUCCESS) return LBM_FAILURE;
     if (post_stop_word(&bt->steady_batch.get()->all_steady, bt->steady_stop_host, bt->ev_steady, bt->stream) != LBM_SUCCESS) return LBM_FAILURE;
     if (wait_stop_word(bt->ev_steady, bt->steady_stop_host, &stop) != LBM_SUCCESS) return LBM_FAILURE;
+    // a batched launch gave up (its status travels in front of the stop word): the batch is failed, sync_batch below reports it
+    if (bt->resident && gave_up(bt->members[0]) != 0) break;
   }
-  if (!stop && max_steps - n_seg * E > 0 && lbm_batch_run(bt, max_steps - n_seg * E) != LBM_SUCCESS) return LBM_FAILURE;
-  return lbm_batch_sync(bt);
+  if (!stop && !owner_failed(bt) && max_steps - n_seg * E > 0 && lbm_batch_run(bt, max_steps - n_seg * E) != LBM_SUCCESS) return LBM_FAILURE;
+  return sync_batch(bt);
 }
 
 // ---- ... on the average velocity: the check reads the segment's tot_u entries; SteadyState holds its state too
 int lbm_run_until(lbm_ctx* c, int max_steps, int check_every, double tol, int patience, lbm_steady_result* out) {
   static const char who[] = "lbm_run_until";
   if (!c || !out) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", who);
+  out->steps_run = 0;
+  REFUSE_FAILED(LBM_FAILURE, c, who);
   if (checked_ctx_ok(c, who, "sums", max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
   const Slab& sl = c->slab[0];
   const int E = check_every, start = c->steps_done;
@@ -5111,6 +5194,8 @@ int lbm_batch_run_until(lbm_batch* bt, int max_steps, int check_every, double to
                         int* steps_run) {
   static const char who[] = "lbm_batch_run_until";
   if (!bt || !out || !steps_run) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", who);
+  *steps_run = 0;
+  REFUSE_FAILED(LBM_FAILURE, bt, who);
   if (checked_batch_ok(bt, who, max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
   const int n_members = (int)bt->members.size(), E = check_every, start = bt->steps_done;
   const auto begin = [&]() -> int {
@@ -5189,6 +5274,8 @@ int lbm_run_until_residual(lbm_ctx* c, int max_steps, int check_every, double to
                            lbm_residual_row* history, int history_capacity) {
   static const char who[] = "lbm_run_until_residual";
   if (!c || !out) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", who);
+  out->steps_run = 0;
+  REFUSE_FAILED(LBM_FAILURE, c, who);
   if (checked_ctx_ok(c, who, "words", max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
   const Slab& sl = c->slab[0];
   const int E = check_every, start = c->steps_done;
@@ -5232,6 +5319,8 @@ int lbm_batch_run_until_residual(lbm_batch* bt, int max_steps, int check_every, 
                                  int* steps_run, lbm_residual_row* history, int history_capacity) {
   static const char who[] = "lbm_batch_run_until_residual";
   if (!bt || !out || !steps_run) LBM_FAIL(LBM_FAILURE, "%s: NULL argument", who);
+  *steps_run = 0;
+  REFUSE_FAILED(LBM_FAILURE, bt, who);
   if (checked_batch_ok(bt, who, max_steps, check_every, tol, patience) != LBM_SUCCESS) return LBM_FAILURE;
   const lbm_ctx* c0 = bt->members[0];
   const Slab& sl0 = c0->slab[0];
